@@ -18,7 +18,11 @@ sharded by screen tile -- rank r traces the r-th contiguous 64-aligned range of 
 index space and the AO rays of its own primary hits, against a BVH built once on rank 0 and
 broadcast; the only collective is the final gather of hit records to rank 0 over RCCL, timed
 separately.  Rank 0 then checks the assembled frame bit for bit against its own single-GPU trace.
-`--scaling weak` keeps the round-1 mode (every rank traces a full frame of its own camera)."""
+`--scaling weak` keeps the round-1 mode (every rank traces a full frame of its own camera).
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else -- the cold-order steps, trace stats and
+rooflines, the extras, the frame-per-rank mode and the CPU baseline with its parity check -- runs with `--full`.
+`--dump-outputs DIR` writes the last timed step's hit records as .npy files (see dump_outputs)."""
 import argparse
 import glob
 import json
@@ -195,15 +199,55 @@ def parse(argv=None):
     ap.add_argument("--one-device", action="store_true", default=os.environ.get("NTR_BENCH_ONE_DEVICE") == "1",
                     help="every rank uses cuda:0 (needs --dist-backend gloo: RCCL refuses two ranks on one GPU).  The ranks' kernels share "
                          "the chip, so the line's times are NOT a scaling measurement; the sharded frame -> gather -> bit-compare flow is what runs")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the cold-order steps, trace stats and rooflines, the extras (configs 3-5, "
+                         "HBM-resident point, ...), the frame-per-rank mode for N > 1 and the CPU baseline with its record-by-record parity check; "
+                         "without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the hit records of the last step as DIR/<name>.npy (float32 / float64; the AO "
+                         "records as a fixed seeded sample): outputs of two builds compare array by array")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extras (profiling runs)")
     ap.add_argument("--no-ao-prediction", action="store_true",
                     help="trace the AO batches without the leaf-depth dispatch hint made beside ray generation (buffer order until a launch has measured)")
-    ap.add_argument("--no-hbm-point", action="store_true", help="skip the 10 M-triangle HBM-resident roofline point (extras)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE configs 3-5 table (extras.configs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold-order", action="store_true", help="skip the extra K steps with the scheduling feedback off")
+    ap.add_argument("--no-hbm-point", action="store_true", help="with --full: skip the 10 M-triangle HBM-resident roofline point (extras)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the BASELINE configs 3-5 table (extras.configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cold-order", action="store_true", help="with --full: skip the extra K steps with the scheduling feedback off")
     ap.add_argument("--cpu-sample-rays", type=int, default=0, help="0 = auto (about 10-30 s of CPU work)")
     return ap.parse_args(argv)
+
+
+# --dump-outputs: at most this many records per output set; 20 bytes a record (id as float64, t / u / v as float32) keeps the
+# primary frame (1080p fits whole) and the AO sample under 64 MB together
+DUMP_PRIMARY_RECORDS = 1 << 21
+DUMP_AO_RECORDS = 1 << 20
+DUMP_SAMPLE_SEED = 20260401
+
+
+def dump_outputs(out_dir, frame, torch):
+    """The hit records the timed path left in this rank's result buffers after its last step (a caller of ntr_trace_bvh receives them):
+    the primary range and the AO batches in batch order, each as <set>_id (float64, exact for every int32), <set>_t and the barycentrics
+    <set>_u / <set>_v (the padA / padB bit patterns, 0 on a miss) as float32.  A set larger than its cap is a fixed, seeded sample of
+    its records (sorted indices), the same for the same arguments.  Returns {name: shape}."""
+    sets = [("primary", frame.own_primary_records(), DUMP_PRIMARY_RECORDS)]
+    if len(frame.batches) > 1:
+        sets.append(("ao", torch.cat([b["res_t"] for b in frame.batches[1:]]), DUMP_AO_RECORDS))
+    os.makedirs(out_dir, exist_ok=True)
+    written, nbytes = {}, 0
+    for name, res_u8, cap in sets:
+        rec = res_u8.view(torch.int32).view(-1, 4)
+        if rec.shape[0] > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rec.shape[0], cap, replace=False))
+            rec = rec[torch.from_numpy(idx).to(rec.device)]
+        r = rec.cpu().numpy()
+        cols = {"id": r[:, 0].astype(np.float64), "t": r[:, 1].view(np.float32), "u": r[:, 2].view(np.float32), "v": r[:, 3].view(np.float32)}
+        for k, a in cols.items():
+            a = np.ascontiguousarray(a)
+            np.save(os.path.join(out_dir, "%s_%s.npy" % (name, k)), a)
+            written["%s_%s" % (name, k)] = list(a.shape)
+            nbytes += a.nbytes
+    assert nbytes <= 64 * 10 ** 6, nbytes
+    return written
 
 
 def self_launch(args):
@@ -504,13 +548,14 @@ def main():
     _, elapsed_max = ntd.job_throughput(0, elapsed, dev)
     prim_live_total, prim_kernel_max = ntd.job_throughput(batches[0]["live"], float(kern_ms[:, 0].sum()) * 1e-3, dev)
     ao_live_total, ao_kernel_max = ntd.job_throughput(sum(b["live"] for b in batches[1:]), float(kern_ms[:, 1:].sum()) * 1e-3, dev)
+    dumped = dump_outputs(args.dump_outputs, frame, torch) if (args.dump_outputs and rank == 0) else None
 
     # ---- the same K steps with the library's scheduling feedback off (NTR_TRACE_AUTO_HINT=0): every launch dispatched as if its batch
     # had never been traced before (predicted order for the primary batch, buffer order for the AO batches).  `value` is the reference's
     # protocol, which re-traces the SAME batches step after step, so its launches run in the order learned from the previous step;
     # this is the figure for batches that are new every time.  Untimed by the driver contract (reported beside `value`).
     cold = None
-    if not args.no_cold_order:
+    if args.full and not args.no_cold_order:
         nt.set_tunables(NTR_TRACE_AUTO_HINT=0)
         for b in batches:
             run_batch(b)
@@ -584,24 +629,26 @@ def main():
                 if not (prim_equal and ao_equal):
                     raise SystemExit("bench.py: the assembled sharded frame differs from the single-GPU frame: %s" % frame_check)
 
-    # ---- algorithmic bytes of the dominant kernel (instrumented trace, untimed) -------------------------------------------
     b0 = batches[0]
-    st = view.trace_stats(args.kernel, b0["n"], False, b0["rays"], b0["res"], stream)
-    alg_bytes = st.algorithmic_bytes()
     prim_ms = float(kern_ms[:, 0].mean())
     ao_ms = float(kern_ms[:, 1:].sum(axis=1).mean()) if len(batches) > 1 else 0.0
-    achieved = alg_bytes / (prim_ms * 1e-3) / 1e9
-    ao_alg, ao_visits = 0, 0
-    for b in batches[1:]:
-        st_b = view.trace_stats(args.kernel, b["n"], True, b["rays"], b["res"], stream)
-        ao_alg += st_b.algorithmic_bytes()
-        ao_visits += st_b.numInnerVisits + st_b.numTriTests
     ao_live = sum(b["live"] for b in batches[1:])
+    # ---- (--full) algorithmic bytes of the dominant kernel (instrumented trace, untimed) ------------------------------------
+    st = None
+    if args.full:
+        st = view.trace_stats(args.kernel, b0["n"], False, b0["rays"], b0["res"], stream)
+        alg_bytes = st.algorithmic_bytes()
+        achieved = alg_bytes / (prim_ms * 1e-3) / 1e9
+        ao_alg, ao_visits = 0, 0
+        for b in batches[1:]:
+            st_b = view.trace_stats(args.kernel, b["n"], True, b["rays"], b["res"], stream)
+            ao_alg += st_b.algorithmic_bytes()
+            ao_visits += st_b.numInnerVisits + st_b.numTriTests
 
     # ---- N > 1: the mode in which this design scales by construction, in the SAME driver-parsed line: every rank traces a whole frame of
     # its own camera (no ray or record crosses a rank boundary), the same K steps
     frame_per_rank = None
-    if (world > 1 or use_dist) and args.scaling == "strong":   # (also at world size 1 under NTR_BENCH_FORCE_DIST=1: the GPU test tier runs this code)
+    if args.full and (world > 1 or use_dist) and args.scaling == "strong":   # (also at world size 1 under NTR_BENCH_FORCE_DIST=1: the GPU test tier runs this code)
         cam_r = dict(cam)
         eye = np.array(cam_r["eye"], dtype=np.float64)
         eye[2] += 2.0 * rank        # a slow camera move: the frames are distinct and about equally costly
@@ -623,7 +670,7 @@ def main():
         del frame_w, evw
 
     overlapped = None
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # every rank's frame share on three streams (no graph: one capture per rank is not worth its set-up here), between barriers;
         # the job's overlapped rate = rays of all ranks / MAX over ranks of the wall time per frame
         barrier()
@@ -632,7 +679,7 @@ def main():
         tot, ov_max = ntd.job_throughput(rays_per_step, ov_s, dev)
         overlapped = {"how": how + ", per rank, MAX over ranks", "ms_per_frame": ov_max * 1e3, "mrays_wall": tot / ov_max / 1e6}
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         try:
             extras = run_extras(args, nt, torch, scenes, view, frame, tri, pos, dev, stream, up, HBM_PEAK_GBS, cam)
         except Exception as e:  # extras never invalidate the headline
@@ -648,16 +695,6 @@ def main():
         return
 
     value = total_rays_per_step * args.steps / kernel_seconds_max / 1e6
-    # binding roofs of the primary launch from the committed PMC passes of the SAME kernel symbol and launch shape (the counters
-    # are fixed by the binary and the rays; the duration is this run's)
-    wide = bool(view.flags & nt.BVH_WIDE_LEAVES)
-    symbol = launched_symbol(args.kernel, wide)
-    pmc, pmc_src = load_pmc(symbol, launched_grid(args.kernel, b0["n"]))
-    visits = st.numInnerVisits + st.numTriTests   # lane steps of the unified-step loop (a terminator arrives with its triangle)
-    # (lanes per wave-iteration is only reported for the persistent kernels: the per-ray kernels' uniform prologue fetches through the
-    # scalar cache, so their vector-load count no longer counts iterations)
-    binding = profiled_shares(pmc, pmc_src, visits if "persistent" in symbol else None)
-    traffic = binding.get("hbm_traffic_bytes") if binding else None
     par = ("one frame sharded by screen tile over %d ranks (PixelTable ranges), BVH built on rank 0 and broadcast, %s gather of hit records"
            % (world, ("RCCL (the library's ntr_dist_* entry points)" if grp is not None else "RCCL (torch.distributed)") if args.dist_backend == "nccl" else "gloo (host-staged)")
            if not (args.scaling == "weak" and world > 1) else "weak scaling: one full frame per rank (camera shifted per rank), BVH replicated")
@@ -704,7 +741,7 @@ def main():
         "gather_native": native_gather if native_gather is not None else ({"fallback": native_note} if native_note else None),
         "sharded_frame_check": frame_check,
         "host_sah_build_s": sah_seconds,
-        "trace_stats": st.as_dict(),
+        "trace_stats": st.as_dict() if st is not None else None,
         "value_cold": cold["mrays"] if cold else None,
         "value_moving_camera": (extras.get("moving_camera") or {}).get("mrays") if isinstance(extras, dict) else None,
         "value_variants_note": "`value` re-traces the same batches every step (the reference's protocol), so each launch runs in the dispatch order its "
@@ -716,14 +753,14 @@ def main():
         "extras": extras,
         "roofline": None,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     # Roofline.  Top level = the SURVEY 8(d) figure of the step's dominant kernel (the AO launches), bound "hbm": algorithmic bytes per
     # launch / mean launch duration / 8 TB/s.  The 34 MB BVH of the headline workload is cache-resident, so that fraction exceeds 1
     # (`cache_served`: true) and is not an efficiency; the same bytes against the paths that serve them (vector L1s, XCD L2s) are nested
     # under `cache_paths`, busy shares of TA / VALU from a committed PMC summary of the same symbol and grid under `utilisation` (null
     # with a note when none matches).  The other kernel of the step sits beside it (`primary`); the launches whose bytes HBM really
     # delivers are `roofline_hbm_resident` and extras.configs[4 | 5].roofline.
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count
-
     def launch_roofline(alg, sec, launches, sym, grid, label, binding_):
         """SURVEY 8(d) block of one kernel of the step: algorithmic bytes per launch / mean launch duration against HBM peak.  The 34 MB BVH of
         the headline workload never leaves the caches, so frac > 1: `cache_served`; the same bytes against the data paths that do serve
@@ -744,30 +781,41 @@ def main():
                 "utilisation": binding_,
                 "utilisation_note": None if binding_ else "no committed PMC summary under profiles/ matches the launched symbol %s with grid %d" % (sym, grid)}
 
-    prim_roof = launch_roofline(alg_bytes, prim_ms * 1e-3, 1, "%s (%s)" % (symbol, args.kernel), launched_grid(args.kernel, b0["n"]),
-                                "the primary batch of rank 0 (closest hit); the HIP events around the library call include the launch's dispatch-order "
-                                "work (prediction or cost feedback, a few small kernels)", binding)
-    roof = prim_roof
-    if ao_ms > 0:
-        ao_sym = launched_symbol(args.kernel, wide, any_hit=True)
-        ao_pmc, ao_src = load_pmc(ao_sym, launched_grid(args.kernel, batches[1]["n"]))
-        ao_bind = profiled_shares(ao_pmc, ao_src, (ao_visits // max(len(batches) - 1, 1)) if "persistent" in ao_sym else None) if ao_pmc else None
-        ao_roof = launch_roofline(ao_alg, ao_ms * 1e-3, len(batches) - 1, "%s (%s)" % (ao_sym, args.kernel), launched_grid(args.kernel, batches[1]["n"]),
-                                  "the %d AO batches of rank 0 (any hit)" % (len(batches) - 1), ao_bind)
-        ao_roof["share_of_step"] = ao_ms / (ao_ms + prim_ms)
-        prim_roof["share_of_step"] = prim_ms / (ao_ms + prim_ms)
-        # top level = the step's DOMINANT kernel (the AO launches: three quarters of the step), the other one beside it
-        if ao_ms >= prim_ms:
-            roof = dict(ao_roof, primary=prim_roof)
-        else:
-            roof = dict(prim_roof, ao=ao_roof)
-    out["roofline"] = roof
-    hp = extras.get("hbm_resident_point") if isinstance(extras, dict) else None
-    if hp and hp.get("incoherent"):
-        out["roofline_hbm_resident"] = hp["incoherent"]["roofline"]
+    if st is not None:
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        # binding roofs of the primary launch from the committed PMC passes of the SAME kernel symbol and launch shape (the counters
+        # are fixed by the binary and the rays; the duration is this run's)
+        wide = bool(view.flags & nt.BVH_WIDE_LEAVES)
+        symbol = launched_symbol(args.kernel, wide)
+        pmc, pmc_src = load_pmc(symbol, launched_grid(args.kernel, b0["n"]))
+        visits = st.numInnerVisits + st.numTriTests   # lane steps of the unified-step loop (a terminator arrives with its triangle)
+        # (lanes per wave-iteration is only reported for the persistent kernels: the per-ray kernels' uniform prologue fetches through the
+        # scalar cache, so their vector-load count no longer counts iterations)
+        binding = profiled_shares(pmc, pmc_src, visits if "persistent" in symbol else None)
+        prim_roof = launch_roofline(alg_bytes, prim_ms * 1e-3, 1, "%s (%s)" % (symbol, args.kernel), launched_grid(args.kernel, b0["n"]),
+                                    "the primary batch of rank 0 (closest hit); the HIP events around the library call include the launch's dispatch-order "
+                                    "work (prediction or cost feedback, a few small kernels)", binding)
+        roof = prim_roof
+        if ao_ms > 0:
+            ao_sym = launched_symbol(args.kernel, wide, any_hit=True)
+            ao_pmc, ao_src = load_pmc(ao_sym, launched_grid(args.kernel, batches[1]["n"]))
+            ao_bind = profiled_shares(ao_pmc, ao_src, (ao_visits // max(len(batches) - 1, 1)) if "persistent" in ao_sym else None) if ao_pmc else None
+            ao_roof = launch_roofline(ao_alg, ao_ms * 1e-3, len(batches) - 1, "%s (%s)" % (ao_sym, args.kernel), launched_grid(args.kernel, batches[1]["n"]),
+                                      "the %d AO batches of rank 0 (any hit)" % (len(batches) - 1), ao_bind)
+            ao_roof["share_of_step"] = ao_ms / (ao_ms + prim_ms)
+            prim_roof["share_of_step"] = prim_ms / (ao_ms + prim_ms)
+            # top level = the step's DOMINANT kernel (the AO launches: three quarters of the step), the other one beside it
+            if ao_ms >= prim_ms:
+                roof = dict(ao_roof, primary=prim_roof)
+            else:
+                roof = dict(prim_roof, ao=ao_roof)
+        out["roofline"] = roof
+        hp = extras.get("hbm_resident_point") if isinstance(extras, dict) else None
+        if hp and hp.get("incoherent"):
+            out["roofline_hbm_resident"] = hp["incoherent"]["roofline"]
 
     # ---- CPU baseline: the oracle (restated reference CPU tracer) on a bounded sample, rank 0 at N=1 only -----------------
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle
         cores = os.cpu_count() or 1
         rays = frame.d_rays.cpu().numpy().view(nt.RAY_DTYPE)

@@ -4,8 +4,8 @@
 # Every step writes under gpurun_out/<tag>/ and is bounded by its own `timeout`.  Steps:
 #   tests            python -m pytest tests -m gpu -x -q
 #   tests:<expr>     ... with -k <expr>
-#   bench            python3 bench.py (default arguments) -> bench.json
-#   bench_quick      bench.py --no-extras --no-cpu-baseline
+#   bench            python3 bench.py --full (default arguments) -> bench.json
+#   bench_quick      bench.py --full --no-extras --no-cpu-baseline
 #   bench_dist1      the RCCL path at world size 1 (NTR_BENCH_FORCE_DIST=1)
 #   matrix:<scenes>  scripts/kernel_matrix.py <scenes> (comma separated)
 #   configs          scripts/config_table.py
@@ -30,11 +30,11 @@ for STEP in "$@"; do
     else timeout -k 5 1500 python3 -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1; fi
     echo "rc=$?"; tail -n 15 $OUT/tests.log ;;
   bench)
-    timeout -k 5 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; tail -c 3000 $OUT/bench.json; tail -n 3 $OUT/bench.err ;;
+    timeout -k 5 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; tail -c 3000 $OUT/bench.json; tail -n 3 $OUT/bench.err ;;
   bench_quick)
-    timeout -k 5 600 python3 bench.py --no-extras --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err; echo "rc=$?"; tail -c 1500 $OUT/bench_quick.json ;;
+    timeout -k 5 600 python3 bench.py --full --no-extras --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err; echo "rc=$?"; tail -c 1500 $OUT/bench_quick.json ;;
   bench_dist1)
-    NTR_BENCH_FORCE_DIST=1 timeout -k 5 600 python3 bench.py --no-extras --no-cpu-baseline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "rc=$?"; tail -c 1200 $OUT/bench_dist1.json ;;
+    NTR_BENCH_FORCE_DIST=1 timeout -k 5 600 python3 bench.py --full --no-extras --no-cpu-baseline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "rc=$?"; tail -c 1200 $OUT/bench_dist1.json ;;
   matrix)
     timeout -k 5 1200 python3 scripts/kernel_matrix.py $ARG 4 > $OUT/kernel_matrix_${ARG//,/_}.jsonl 2> $OUT/kernel_matrix.err; echo "rc=$?"
     python3 - $OUT/kernel_matrix_${ARG//,/_}.jsonl <<'EOF'
@@ -49,7 +49,7 @@ EOF
   profile)
     timeout -k 5 2400 bash scripts/profile_round.sh $TAG ${ARG//:/ } > $OUT/profile.log 2>&1; echo "rc=$?"; tail -n 5 $OUT/profile.log ;;
   prof_bench)
-    timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 bench.py --no-extras --no-cpu-baseline > $OUT/prof_bench.log 2>&1; echo "rc=$?"
+    timeout -k 5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 bench.py --full --no-extras --no-cpu-baseline > $OUT/prof_bench.log 2>&1; echo "rc=$?"
     python3 scripts/summarize_rocprof.py trace $OUT/prof_bench > $OUT/bench_kernel_summary.txt 2>&1; head -n 12 $OUT/bench_kernel_summary.txt
     find $OUT/prof_bench -name "*.csv" -size +8M -delete ;;
   shard)

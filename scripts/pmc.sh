@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/pmc_$TAG; mkdir -p $OUT
 i=0
 for C in "${SETS[@]}"; do
-  timeout -k 5 240 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/set$i -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" > $OUT/set$i.log 2>&1
+  timeout -k 5 240 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/set$i -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline "$@" > $OUT/set$i.log 2>&1
   i=$((i+1))
 done
 python3 - <<PY

@@ -6,7 +6,7 @@
 TAG=${1:-r05}
 OUT=gpurun_out/pair_pmc_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-cold-order"
+ARGS="--steps 3 --warmup 1 --full --no-extras --no-cpu-baseline --no-cold-order"
 for MODE in 0 1; do
   export NTR_TRACE_PAIR=$MODE
   i=0

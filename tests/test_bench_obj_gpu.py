@@ -35,7 +35,7 @@ def test_bench_scene_obj_path(tmp_path, camera):
     g = np.load(os.path.join(ROOT, "tests", "golden", "map_obj_mixed.npz"))
     obj = str(tmp_path / "map.obj")
     _write_obj(obj, g["tri"], g["pos"])
-    args = ["--scene-obj", obj, "--width", "320", "--height", "200", "--steps", "2", "--warmup", "1", "--no-extras"]
+    args = ["--scene-obj", obj, "--width", "320", "--height", "200", "--steps", "2", "--warmup", "1", "--full", "--no-extras"]
     if camera != "bounding-box":
         args += ["--camera", REF_SIGNATURE]
     out = _bench(args)
@@ -56,7 +56,7 @@ def test_bench_rccl_path_at_world_size_one(balance):
     env = dict(os.environ, NTR_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--width", "640", "--height", "360", "--steps", "2", "--warmup", "1",
-                        "--no-extras", "--no-cpu-baseline", "--balance", balance], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--no-extras", "--no-cpu-baseline", "--balance", balance], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["gather_ms"] is not None and out["gather_ms"] > 0
@@ -79,7 +79,7 @@ def _bench_ranks(n, extra, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", "--one-device", "--steps", "2",
-                        "--warmup", "1", "--no-extras", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=timeout, env=env)
+                        "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -114,3 +114,24 @@ def test_bench_frame_per_rank_mode_at_world_size_two():
     out = _bench_ranks(2, ["--width", "640", "--height", "360", "--scaling", "weak"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert out["config"]["rays_per_step"] > 1.5 * out["config"]["rays_per_step_rank0"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) prints the headline and nothing measured beside it; --dump-outputs writes the last timed step's hit records,
+    the same arrays in two runs with the same arguments."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = _bench(["--width", "320", "--height", "200", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "Mrays/s"
+        assert out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert "cpu_baseline" not in out and out["trace_stats"] is None and out["cold_dispatch_order"] is None and out["extras"] == {}
+        files = sorted(os.listdir(d))
+        assert files == sorted("%s_%s.npy" % (s, k) for s in ("primary", "ao") for k in ("id", "t", "u", "v"))
+        arrays = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+        assert arrays["primary_id.npy"].shape == (320 * 200,) and (arrays["primary_id.npy"] >= 0).any()
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a.view(np.uint8), dumps[1][f].view(np.uint8)), f

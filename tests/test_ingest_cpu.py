@@ -2,7 +2,8 @@
 
 Known answers from the reference itself: the camera signature string shipped in its config.conf
 (Benchmark.camera) must decode and re-encode to the same string, and the two OBJ assets in its data/
-directory have the triangle counts SURVEY.md section 2 row 24 records (Map.obj 488, head.obj 18 678)."""
+directory have the triangle counts SURVEY.md section 2 row 24 records (Map.obj 488, head.obj 18 678) in the geometry the
+importer read from them into tests/golden/."""
 import math
 import os
 
@@ -96,11 +97,23 @@ def test_obj_import_missing_file():
         nt.obj_load("/nonexistent/file.obj")
 
 
+# the geometry this repo's importer read from the reference's two OBJ assets, stored when the fixtures were made (tests/golden/make_golden.py)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ASSET_FIXTURES = {"data/models/Map/Map.obj": "map_obj_mixed.npz", "data/models/Head/head.obj": "head_obj_mixed.npz"}
+
+
 @pytest.mark.parametrize("rel,ntris", [("data/models/Map/Map.obj", 488), ("data/models/Head/head.obj", 18678)])
-def test_reference_assets_triangle_counts(rel, ntris):
-    path = os.path.join("/root/reference", rel)
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present on this box")
-    tri, pos, nsub = nt.obj_load(path)
+def test_reference_assets_triangle_counts(tmp_path, rel, ntris):
+    g = np.load(os.path.join(GOLDEN, ASSET_FIXTURES[rel]))
+    tri, pos = g["tri"], g["pos"]
     assert tri.shape[0] == ntris
     assert tri.min() >= 0 and tri.max() < pos.shape[0] and np.isfinite(pos).all()
+    # the same geometry written back as a Wavefront OBJ (%.9g: every float32 exactly) imports to the same triangles, corner by corner
+    path = tmp_path / os.path.basename(rel)
+    with open(path, "w") as f:
+        f.writelines("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]) for p in pos)
+        f.writelines("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1) for t in tri)
+    tri2, pos2, nsub = nt.obj_load(str(path))
+    assert nsub == 1 and tri2.shape[0] == ntris
+    assert tri2.min() >= 0 and tri2.max() < pos2.shape[0]
+    assert np.array_equal(pos2[tri2], pos[tri])
