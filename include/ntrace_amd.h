@@ -390,7 +390,7 @@ NTR_API int ntr_raygen_shadow(NtrRay* d_outRays, int32_t* d_outIDToSlot, int32_t
                               const float lightPos[3], float lightRadius, uint32_t kernelSeed, void* stream);
 
 /* countHitsKernel (src/rt/cuda/RendererKernels.cu:174-226; Renderer::getTotalNumRays,
- * Renderer.cpp:676-709): number of results with id != -1.  Blocking. */
+ * Renderer.cpp:676-709): number of results with id >= 0 (RendererKernels.cu:193).  Blocking. */
 NTR_API int ntr_count_hits(const NtrRayResult* d_results, int32_t numRays, int32_t* count, void* stream);
 
 /* ---- on-device LBVH build ------------------------------------------------------------------ */

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void raygen_ao_kernel(NtrRay* __restrict__ out
     }
 }
 
-// countHitsKernel (src/rt/cuda/RendererKernels.cu:174-226): number of rays with id != -1.
+// countHitsKernel (src/rt/cuda/RendererKernels.cu:174-226): number of rays with id >= 0 (:193).
 // rayGenShadowKernel (src/rt/ray/RayGenKernels.cu:240-301): numSamples rays from every input ray's hit point towards points inside a cube of
 // half-edge lightRadius around the light -- a (0,2)-sequence / Hammersley point per sample (sobol2D :52-73, hammersley :47-50), shifted per
 // input ray by a Jenkins-hashed offset (Cranley-Patterson, :267-286); tmax = the distance to the target, -1 for rays of missed inputs.
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void count_hits_kernel(const NtrRayResult* __r
 {
     int local = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < numRays; i += gridDim.x * blockDim.x)
-        local += (reinterpret_cast<const int4*>(results)[i].x != -1);
+        local += (reinterpret_cast<const int4*>(results)[i].x >= 0);
     for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off);
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
 }

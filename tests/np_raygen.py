@@ -1,6 +1,7 @@
-"""numpy restatement of rayGenAOKernel (src/rt/ray/RayGenKernels.cu:129-236) for testing the
-device ray generators to a floating-point tolerance (the reference builds these kernels with
--use_fast_math, so no bit-exact target exists for them)."""
+"""numpy restatements of the ray generators of src/rt/ray/RayGenKernels.cu (primary :77-125, AO :129-236, shadow :240-301) for
+testing the device ray generators to a floating-point tolerance (the reference builds these kernels with -use_fast_math, so no
+bit-exact target exists for them).  Values are float64; where a kernel branches on a float32 value, the branch is decided on the
+float32 value, as the kernel decides it, so that a case on the boundary is not a false mismatch."""
 import numpy as np
 
 
@@ -19,6 +20,52 @@ def _jenkins(a, b, c):
     return a, b, c
 
 
+def ao_normals(in_rays, in_results, normals, first=0, count=None):
+    """the AO generator's normal per input ray (RayGenKernels.cu:155-162): the hit triangle's normal, (1, 0, 0) for a missed input,
+    negated when it faces along the ray; the facing test is the kernel's float32 sum of products (exact 0: no flip)"""
+    count = in_rays.shape[0] - first if count is None else count
+    r = in_rays[first:first + count]
+    tri = in_results["id"][first:first + count]
+    n = np.where((tri != -1)[:, None], normals[np.maximum(tri, 0)].astype(np.float32), np.array([1.0, 0.0, 0.0], dtype=np.float32))
+    F = np.float32
+    dot = ((n[:, 0] * r["dx"]).astype(F) + (n[:, 1] * r["dy"]).astype(F)).astype(F) + (n[:, 2] * r["dz"]).astype(F)
+    n = n.astype(np.float64)
+    n[dot > 0] = -n[dot > 0]
+    return n
+
+
+# A pinhole camera whose eye is near the origin, looking obliquely: the kernel forms the direction as (world point - eye) in float32,
+# which for an eye far from the origin (the Cornell camera sits at |eye| ~ 850) cancels to ~1e-5 and would hide a wrong jitter of that size.
+NEAR_ORIGIN_CAM = {"eye": (0.3, -0.2, 0.5), "target": (-1.0, 0.4, 3.0), "up": (0.0, 1.0, 0.0), "fov_deg": 55.0, "far": 100.0}
+
+
+def primary_rays(index_to_pixel, origin, nscreen_to_world, w, h, max_dist, kernel_seed=0):
+    """rayGenPrimaryKernel (RayGenKernels.cu:77-125): (origins, unit directions, tmax) of the w * h rays in slot order.
+    kernel_seed != 0 offsets the normalised screen position by (F32)hash * 2^-32 * 0.005 (:95-106).  The normalised screen position is
+    the kernel's float32 sequence (2 (x + 0.5) / w - 1 cancels near the centre, and a 1000:1 frame magnifies that 1000-fold); the
+    jitter, the transform and the normalisation are float64."""
+    n = w * h
+    F = np.float32
+    pix = np.asarray(index_to_pixel[:n], dtype=np.int64)
+    nx = ((F(2.0) * ((pix % w).astype(F) + F(0.5))).astype(F) / F(w) - F(1.0)).astype(F).astype(np.float64)
+    ny = ((F(2.0) * ((pix // w).astype(F) + F(0.5))).astype(F) / F(h) - F(1.0)).astype(F).astype(np.float64)
+    if kernel_seed != 0:
+        with np.errstate(over="ignore"):
+            a = (np.uint32(kernel_seed) + np.arange(n, dtype=np.uint32)).astype(np.uint32)
+        b = np.full(n, 0x9e3779b9, dtype=np.uint32)
+        c = np.full(n, 0x9e3779b9, dtype=np.uint32)
+        a, b, c = _jenkins(a, b, c)
+        a, b, c = _jenkins(a, b, c)
+        nx = nx + a.astype(np.float32).astype(np.float64) * 2.0 ** -32 * 0.005
+        ny = ny + b.astype(np.float32).astype(np.float64) * 2.0 ** -32 * 0.005
+    m = np.asarray(nscreen_to_world, dtype=np.float32).astype(np.float64).reshape(4, 4)
+    world = m[:, 0][None, :] * nx[:, None] + m[:, 1][None, :] * ny[:, None] + m[:, 3][None, :]
+    o = np.asarray(origin, dtype=np.float32).astype(np.float64)
+    d = world[:, :3] / world[:, 3:4] - o[None, :]
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return np.repeat(o[None, :], n, axis=0), d, np.full(n, float(np.float32(max_dist)))
+
+
 def ao_rays(in_rays, in_results, normals, num_samples, max_dist, kernel_seed, first=0, count=None):
     count = in_rays.shape[0] - first if count is None else count
     r = in_rays[first:first + count]
@@ -28,10 +75,8 @@ def ao_rays(in_rays, in_results, normals, num_samples, max_dist, kernel_seed, fi
     back = np.maximum(res["t"].astype(np.float64) - 1.0e-4, 0.0)
     origin = o + d * back[:, None]
     tri = res["id"]
-    n = np.where((tri != -1)[:, None], normals[np.maximum(tri, 0)].astype(np.float64), np.array([1.0, 0.0, 0.0]))
-    flip = (n * d).sum(1) > 0
-    n[flip] = -n[flip]
-    na = np.abs(n)
+    n = ao_normals(in_rays, in_results, normals, first, count)
+    na = np.abs(n)          # float32 values held exactly: the ties nm == az, nm == ax are decided as in float32
     nm = na.max(1)
     perp = np.stack([n[:, 1], -n[:, 0], np.zeros(count)], 1)
     zc = nm == na[:, 2]
@@ -71,8 +116,9 @@ def ao_rays(in_rays, in_results, normals, num_samples, max_dist, kernel_seed, fi
     return out_o, out_d, tmax
 
 
-def shadow_rays(in_rays, in_results, num_samples, light_pos, light_radius, kernel_seed, first=0, count=None):
-    """rayGenShadowKernel (src/rt/ray/RayGenKernels.cu:240-301) in float64: (origins, unit directions, tmax) of count * num_samples rays."""
+def shadow_rays(in_rays, in_results, num_samples, light_pos, light_radius, kernel_seed, first=0, count=None, f32_wrap=False):
+    """rayGenShadowKernel (src/rt/ray/RayGenKernels.cu:240-301) in float64: (origins, unit directions, tmax) of count * num_samples rays.
+    f32_wrap: decide the `>= 1.0f` wrap of the shifted sample (:281-283) on the kernel's float32 sum, not on the float64 one."""
     count = in_rays.shape[0] - first if count is None else count
     r = in_rays[first:first + count]
     res = in_results[first:first + count]
@@ -102,7 +148,13 @@ def shadow_rays(in_rays, in_results, num_samples, light_pos, light_radius, kerne
             v2 ^= v2 >> 1
             k >>= 1
         pos = np.array([float(np.float32(r1)) * 2.0 ** -32, float(np.float32(r2)) * 2.0 ** -32, (i + 0.5) / num_samples])[None, :] + off
-        pos = np.where(pos >= 1.0, pos - 1.0, pos)
+        if f32_wrap:
+            F = np.float32
+            s32 = np.array([F(r1) * F(2.0 ** -32), F(r2) * F(2.0 ** -32), (F(i) + F(0.5)) / F(num_samples)], dtype=F)[None, :]
+            wrap = (s32 + off.astype(F)).astype(F) >= F(1.0)
+        else:
+            wrap = pos >= 1.0
+        pos = np.where(wrap, pos - 1.0, pos)
         pos = pos * 2.0 - 1.0
         direction = lp[None, :] + light_radius * pos - origin
         length = np.linalg.norm(direction, axis=1)

@@ -5,47 +5,9 @@ import pytest
 
 import ntrace_amd as nt
 from ntrace_amd import scenes
+from np_rayops import np_ray_box, np_ray_keys, np_reconstruct
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-
-
-def np_from_abgr(c):
-    c = c.astype(np.uint32)
-    k = F(1.0) / F(255.0)
-    return np.stack([(c & 0xFF).astype(F) * k, ((c >> 8) & 0xFF).astype(F) * k, ((c >> 16) & 0xFF).astype(F) * k,
-                     (c >> 24).astype(F) * k], -1).astype(F)
-
-
-def np_to_abgr(v):
-    b = (np.minimum(np.maximum(v, F(0)), F(1)) * F(255.0)).astype(np.uint32)
-    return b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16) | (b[:, 3] << 24)
-
-
-def np_reconstruct(ray_type, n_per, first, num, p_slot_to_id, p_res, b_id_to_slot, b_res, mat, shaded, pixels):
-    bg = np.array([0.2, 0.4, 0.8, 1.0], dtype=F)
-    for task in range(num):
-        pslot = first + task
-        pid = p_slot_to_id[pslot]
-        slots = b_id_to_slot[pid:pid + n_per] if ray_type == 0 else b_id_to_slot[task * n_per:(task + 1) * n_per]
-        col = np.zeros(4, dtype=F)
-        for s in slots:
-            tri = b_res["id"][s]
-            if tri == -1:
-                add = bg if ray_type == 0 else np.ones(4, dtype=F)
-            elif ray_type == 1:
-                add = np.array([0, 0, 0, 1], dtype=F)
-            else:
-                add = np_from_abgr(shaded[tri:tri + 1])[0]
-            col = (col + add).astype(F)
-        col = (col * (F(1.0) / F(n_per))).astype(F)
-        ptri = p_res["id"][pslot]
-        if ray_type == 1 and ptri == -1:
-            col = bg.copy()
-        if ray_type == 2:
-            col = (col * (bg if ptri == -1 else np_from_abgr(mat[ptri:ptri + 1])[0])).astype(F)
-        pixels[pid] = np_to_abgr(col[None])[0]
-    return pixels
 
 
 @pytest.mark.parametrize("ray_type", [0, 1, 2])
@@ -73,37 +35,6 @@ def test_reconstruct_matches_numpy(ray_type):
     exp = np_reconstruct(ray_type, ns, first, num, slot_to_id, p_res, b_id_to_slot, b_res, mat, shaded,
                          np.full(n, 0x11223344, dtype=np.uint32))
     assert np.array_equal(got, exp)
-
-
-def np_ray_box(rays):
-    o = np.stack([rays["ox"], rays["oy"], rays["oz"]], 1).astype(F)
-    d = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1).astype(F)
-    e = (o + d * rays["tmax"][:, None]).astype(F)
-    return np.minimum(o.min(0), e.min(0)).astype(F), np.maximum(o.max(0), e.max(0)).astype(F)
-
-
-def np_ray_keys(rays, box=None):
-    """the 192-bit sort keys (RayBuffer.cpp:103-165) as Python integers; `box`: the (lo, hi) of the batch the rays are a sample of"""
-    o = np.stack([rays["ox"], rays["oy"], rays["oz"]], 1).astype(F)
-    d = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1).astype(F)
-    lo, hi = box if box is not None else np_ray_box(rays)
-    with np.errstate(all="ignore"):
-        a = ((o - lo) / (hi - lo)).astype(F)
-        ln = np.sqrt(((d[:, 0] * d[:, 0]).astype(F) + (d[:, 1] * d[:, 1]).astype(F)).astype(F) + (d[:, 2] * d[:, 2]).astype(F)).astype(F)
-        inv = (F(1.0) * (F(1.0) / ln)).astype(F)
-        b = (((d * inv[:, None]).astype(F) + F(1.0)).astype(F) * F(0.5)).astype(F)
-    comp = [(a[:, k] * F(256.0) * F(65536.0)).astype(F) for k in range(3)] + [(b[:, k] * F(32.0) * F(65536.0)).astype(F) for k in range(3)]
-    comp = [c.astype(np.int64).astype(np.uint64) & 0xFFFFFFFF for c in comp]
-    key = np.zeros(rays.shape[0], dtype=object)
-    big = [int(0)] * rays.shape[0]
-    for k in range(6):
-        ck = comp[k]
-        for i in range(32):
-            bit = ((ck >> np.uint64(i)) & np.uint64(1)).astype(np.uint64)
-            pos = k + 6 * i
-            for r in np.nonzero(bit)[0]:
-                big[r] |= 1 << pos
-    return big
 
 
 def test_ray_morton_sort_matches_numpy():
