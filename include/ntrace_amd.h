@@ -308,6 +308,29 @@ NTR_API int ntr_predict_block_costs(int32_t numRays, const NtrRay* d_rays, const
 NTR_API int ntr_predict_batch_coherence(int32_t numRays, const NtrRay* d_rays, const void* d_nodes, int64_t nodesBytes,
                                         uint32_t* d_out, void* stream);
 
+/* The dispatch order a large closest-hit launch of this batch would be given, without tracing it: the same two launches as the launch
+ * path (class of every 256-ray block = min(boxes hit / 2, 63), class lists concatenated heaviest class first; inside one class the blocks
+ * of one group of 64 stay in buffer order) on the BVH's cached top-of-tree table, with the launch's wide pool K.  d_order receives
+ * (numRays + 255) / 256 block indices, d_word the batch word (ntr_predict_batch_coherence d_out[2]).  The class counters live in scratch
+ * of this call's own (never a launch's) and are zero again when it returns.  numRays == 0: nothing to do.  Blocking (waits for
+ * `stream`).  A diagnostic: no trace launch calls it or is changed by it. */
+NTR_API int ntr_predict_dispatch_order(int32_t numRays, const NtrRay* d_rays, const void* d_nodes, int64_t nodesBytes,
+                                       uint32_t* d_order, uint32_t* d_word, void* stream);
+
+/* What a scheduling hint holds, read back for tests and diagnostics: waits for `stream`, then fills *state and, when the pointers are
+ * non-null, copies the hint's numBlocks order words followed by its 3 batch words (h_order: numBlocks + 3 words; the last one is the
+ * batch word, ntr_predict_batch_coherence d_out[2]) and its numBlocks cost words (the costs the last refresh launch recorded, or the
+ * caller's prediction).  An unbound hint (numBlocks == 0) has no arrays: only *state is filled, and asking for them is an error.
+ * Changes nothing in the hint. */
+typedef struct {
+    int32_t numBlocks;   /* 0 = unbound */
+    int32_t device;
+    int32_t uses;        /* launches since the hint was (re)bound or predicted */
+    int32_t valid;       /* the next launch is dispatched in the hint's order */
+    int32_t predicted;   /* the order comes from ntr_sched_hint_predict and no launch has run it yet */
+} NtrSchedHintState;
+NTR_API int ntr_sched_hint_inspect(const NtrSchedHint* hint, NtrSchedHintState* state, uint32_t* h_order, uint32_t* h_cost, void* stream);
+
 /* Traversal counters: the reference's RayStats (src/rt/bvh/BVH.hpp:44-60), filled by its
  * CPU tracer at src/rt/cuda/CudaBVH.cpp:746-757 and 1107-1111.  numInnerVisits =
  * numNodeTests / 2.  These define the algorithmic bytes of a batch:

@@ -12,7 +12,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     raygen_primary, raygen_ao, raygen_shadow, count_hits, selftest_division, selftest_division_hard, bvh_leaf_depths, secondary_block_costs, lbvh_capacity,
                     lbvh_build, LbvhResult, reconstruct, ray_morton_sort, camera_decode, camera_reencode,
                     camera_nscreen_to_world, obj_load, SchedHint, trace_status, trace_plan, trace_plan_hint_step, TracePlan, set_tunables, host_bvh_wrap, use_library, trace_graph_reserve, trace_graph_release_all, stream_release, selftest_auto_hint_table, selftest_gather_rate, frame_shard, frame_ao_batches, DistGroup,
-                    lbvh_release_workspace, predict_block_costs, predict_batch_coherence)
+                    lbvh_release_workspace, predict_block_costs, predict_batch_coherence, predict_dispatch_order, SchedHintState)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16

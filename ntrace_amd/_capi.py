@@ -17,6 +17,10 @@ class NtrError(RuntimeError):
         self.code = code
 
 
+class SchedHintState(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("numBlocks", "device", "uses", "valid", "predicted")]
+
+
 class KernelConfig(C.Structure):
     _fields_ = [("bvhLayout", C.c_int32), ("blockWidth", C.c_int32), ("blockHeight", C.c_int32),
                 ("usePersistentThreads", C.c_int32)]
@@ -99,6 +103,7 @@ SYMBOLS = [
     ("ntr_tunables_reload", C.c_int, []),
     ("ntr_predict_block_costs", C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp]),
     ("ntr_predict_batch_coherence", C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp]),
+    ("ntr_predict_dispatch_order", C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     ("ntr_trace_graph_reserve", C.c_int, [_i32, _i32]),
     ("ntr_trace_graph_release_all", C.c_int, []),
     ("ntr_stream_release", C.c_int, [_vp]),
@@ -108,6 +113,7 @@ SYMBOLS = [
     ("ntr_sched_hint_destroy", C.c_int, [_vp]),
     ("ntr_sched_hint_reset", C.c_int, [_vp]),
     ("ntr_sched_hint_predict", C.c_int, [_vp, _vp, _i32, _vp]),
+    ("ntr_sched_hint_inspect", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("ntr_secondary_block_costs", C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
     ("ntr_bvh_leaf_depths", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, C.POINTER(_i32), _vp]),
     ("ntr_selftest_division", C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_u32), _vp]),
@@ -202,6 +208,20 @@ class SchedHint:
     def predict(self, d_block_cost, num_blocks, stream=0):
         """ntr_sched_hint_predict: dispatch the batch's next launch by these per-block cost estimates (device pointer, uint32 per block)"""
         _check(lib().ntr_sched_hint_predict(self._h, _vp(d_block_cost), int(num_blocks), _vp(stream)))
+
+    def inspect(self, stream=0):
+        """ntr_sched_hint_inspect (waits for `stream`): {numBlocks, device, uses, valid, predicted} plus, for a bound hint, "order" (its
+        numBlocks block indices), "words" (the 3 batch words stored after them) and "cost" (its numBlocks cost words), as uint32 arrays"""
+        st = SchedHintState()
+        _check(lib().ntr_sched_hint_inspect(self._h, C.byref(st), None, None, _vp(stream)))
+        out = {n: int(getattr(st, n)) for n, _ in st._fields_}
+        if st.numBlocks > 0:
+            order = np.zeros(st.numBlocks + 3, np.uint32)
+            cost = np.zeros(st.numBlocks, np.uint32)
+            _check(lib().ntr_sched_hint_inspect(self._h, C.byref(st), order.ctypes.data_as(_vp), cost.ctypes.data_as(_vp), _vp(stream)))
+            out.update({n: int(getattr(st, n)) for n, _ in st._fields_})
+            out["order"], out["words"], out["cost"] = order[:st.numBlocks], order[st.numBlocks:], cost
+        return out
 
     def close(self):
         if self._h:
@@ -348,8 +368,16 @@ class DistGroup:
 
 
 def predict_batch_coherence(num_rays, d_rays, d_nodes, nodes_bytes, d_out, stream=0):
-    """ntr_predict_batch_coherence: d_out[0] = 256-ray blocks whose sample rays start far apart, d_out[1] = the pool K derived from it."""
+    """ntr_predict_batch_coherence: d_out[0] = 256-ray blocks whose sample rays start far apart, d_out[1] = the divergence score (4 per block
+    of long rays that start together and point apart, 1 per block with a degenerate sample ray), d_out[2] = the batch word (bits 0-15 the
+    pool K, bit 16 NTR_BATCH_DIVERGENT)."""
     _check(lib().ntr_predict_batch_coherence(int(num_rays), _vp(d_rays), _vp(d_nodes), int(nodes_bytes), _vp(d_out), _vp(stream)))
+
+
+def predict_dispatch_order(num_rays, d_rays, d_nodes, nodes_bytes, d_order, d_word, stream=0):
+    """ntr_predict_dispatch_order (blocking): the block order a large closest-hit launch of this batch would be given, into d_order
+    ((num_rays + 255) // 256 words), and its batch word, into d_word (1 word)."""
+    _check(lib().ntr_predict_dispatch_order(int(num_rays), _vp(d_rays), _vp(d_nodes), int(nodes_bytes), _vp(d_order), _vp(d_word), _vp(stream)))
 
 
 def predict_block_costs(num_rays, d_rays, d_nodes, nodes_bytes, d_block_cost, stream=0):

@@ -553,8 +553,9 @@ static void sched_hint_release(NtrSchedHint* h)
 }
 
 // Binds a caller-owned hint to a batch of numBlocks blocks on `dev`: the arrays are reallocated only to grow (or on another device); a
-// hint bound to a different block count starts over.
-static int sched_hint_bind(NtrSchedHint* h, int numBlocks, int dev)
+// hint bound to a different block count starts over, its order the identity (in the order of `s`): a refresh launch that records no
+// cost leaves the order as it is (sched_order_kernel), so it must be a permutation of the blocks from the start.
+static int sched_hint_bind(NtrSchedHint* h, int numBlocks, int dev, hipStream_t s)
 {
     if (h->device != dev || h->capBlocks < numBlocks || !h->order) {
         sched_hint_release(h);
@@ -568,6 +569,8 @@ static int sched_hint_bind(NtrSchedHint* h, int numBlocks, int dev)
     if (h->numBlocks != numBlocks) {
         h->numBlocks = numBlocks;
         h->uses = 0; h->valid = false; h->predicted = false;
+        const hipError_t e = ntr_launch_identity_order(h->order, numBlocks, s);
+        if (e != hipSuccess) return hip_fail(e, "identity_order launch");
     }
     return NTR_OK;
 }
@@ -646,6 +649,11 @@ static int auto_hint_get(const void* d_rays, const void* d_nodes, int numRays, i
         h->numBlocks = numBlocks;
         h->device = dev;
         h->uses = 0; h->valid = false;
+        if (ntr_launch_identity_order(order, numBlocks, s) != hipSuccess) {   // (see sched_hint_bind)
+            (void)hipGetLastError();
+            auto_hint_release_async(h, s);
+            return NTR_OK;
+        }
     }
     *out = h;
     return NTR_OK;
@@ -747,7 +755,7 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
         int dev = 0;
         NTR_HIP(hipGetDevice(&dev));
         if (hint->numBlocks != orderBlocks || hint->device != dev) {
-            rc = sched_hint_bind(hint, orderBlocks, dev);   // (automatic hints arrive bound: auto_hint_get)
+            rc = sched_hint_bind(hint, orderBlocks, dev, s);   // (automatic hints arrive bound: auto_hint_get)
             if (rc != NTR_OK) return rc;
         }
         const HintStep hs = plan_hint_step(tun, hint->valid, hint->predicted, hint->uses);
@@ -767,7 +775,9 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
     }
 
     // Dispatch-order prediction (plan_trace: which launches qualify).  A launch whose hint holds no measured order yet -- the first one
-    // of a batch -- is predicted like an unhinted one.
+    // of a batch -- is predicted like an unhinted one, and the prediction is flattened straight into the hint's order (its batch word goes
+    // there too): when the launch records no cost -- the persistent body in dynamic-fetch mode -- the hint keeps the predicted order
+    // instead of one derived from nothing.
     TopTable* predTable = nullptr;
     PredictScratch* predScratch = nullptr;
     if (pl.predictable && !(hint && hint->valid) && !p.order) {
@@ -775,7 +785,7 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
         if (rc != NTR_OK) return rc;
         rc = predict_scratch_get(s, orderBlocks, &predScratch);
         if (rc != NTR_OK) return rc;
-        if (predScratch) p.order = predScratch->order;
+        if (predScratch) p.order = (hint && pl.hintable) ? hint->order : predScratch->order;
         else predTable = nullptr;   // (a captured launch that found no spare scratch: buffer order)
     }
 
@@ -841,7 +851,7 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
     }
     if (predScratch) {  // inside the timed bracket: the prediction is part of what the launch costs
         const hipError_t pe = ntr_launch_predict(d_rays, numRays, orderBlocks, predTable->table, predTable->count, predScratch->classCount,
-                                                 predScratch->classList, predScratch->order,
+                                                 predScratch->classList, (hint && pl.hintable) ? hint->order : predScratch->order,
                                                  (hint && pl.hintable) ? hint->order + orderBlocks + 2 : nullptr, pl.minipoolWide, s);
         if (pe != hipSuccess) return hip_fail(pe, "predict launch");
     } else if (probeCoherence) {   // (also inside the bracket)
@@ -864,7 +874,7 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
     }
     if (seconds) NTR_HIP(hipEventRecord(ev1, s));
     if (refresh) {
-        le = ntr_launch_sched_order(hint->cost, orderBlocks, tun.schedClasses, hint->order, s);
+        le = ntr_launch_sched_order(hint->cost, orderBlocks, tun.schedClasses, hint->order, 1, s);
         if (le != hipSuccess) return hip_fail(le, "sched_order launch");
         hint->valid = true;
     }
@@ -1002,6 +1012,36 @@ int ntr_predict_batch_coherence(int32_t numRays, const NtrRay* d_rays, const voi
     return NTR_OK;
 }
 
+int ntr_predict_dispatch_order(int32_t numRays, const NtrRay* d_rays, const void* d_nodes, int64_t nodesBytes, uint32_t* d_order, uint32_t* d_word,
+                               void* stream)
+{
+    if (numRays < 0) return set_error(NTR_ERR_INVALID, "ntr_predict_dispatch_order: numRays < 0");
+    if (numRays == 0) return NTR_OK;
+    if (!d_rays || !d_nodes || !d_order || !d_word) return set_error(NTR_ERR_INVALID, "ntr_predict_dispatch_order: null argument");
+    if (nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > kMaxNodesBytes)
+        return set_error(NTR_ERR_INVALID, "ntr_predict_dispatch_order: node buffer size must be a multiple of 64 in [64, 0x76543200]");
+    hipStream_t s = (hipStream_t)stream;
+    TopTable* t = nullptr;
+    int rc = top_table_get(d_nodes, nodesBytes, s, false, &t);
+    if (rc != NTR_OK) return rc;
+    int dev = 0;
+    NTR_HIP(hipGetDevice(&dev));
+    // one scratch per device for this query (never a launch's): held until the launches that use it have run
+    static std::mutex mu;
+    static PredictScratch scratch[kMaxDevices];
+    std::lock_guard<std::mutex> lk(mu);
+    const int numBlocks = (numRays + 255) / 256;
+    PredictScratch* p = &scratch[dev];
+    if (p->capBlocks < numBlocks && p->classList) NTR_HIP(hipStreamSynchronize(s));
+    rc = scratch_alloc(p, dev, numBlocks);
+    if (rc != NTR_OK) return rc;
+    const hipError_t e = ntr_launch_predict(d_rays, numRays, numBlocks, t->table, t->count, p->classCount, p->classList, d_order, d_word,
+                                            minipool_wide(tunables(), nodesBytes, numRays), s);
+    if (e != hipSuccess) return hip_fail(e, "predict launch");
+    NTR_HIP(hipStreamSynchronize(s));
+    return NTR_OK;
+}
+
 int ntr_trace_graph_reserve(int32_t launches, int32_t numRays)
 {
     if (launches < 0 || numRays < 0) return set_error(NTR_ERR_INVALID, "ntr_trace_graph_reserve: negative argument");
@@ -1116,6 +1156,25 @@ int ntr_sched_hint_reset(NtrSchedHint* hint)
     return NTR_OK;
 }
 
+int ntr_sched_hint_inspect(const NtrSchedHint* hint, NtrSchedHintState* state, uint32_t* h_order, uint32_t* h_cost, void* stream)
+{
+    if (!hint || !state) return set_error(NTR_ERR_INVALID, "ntr_sched_hint_inspect: null argument");
+    if (hint->numBlocks == 0 && (h_order || h_cost)) return set_error(NTR_ERR_INVALID, "ntr_sched_hint_inspect: the hint is not bound (it has no arrays)");
+    hipStream_t s = (hipStream_t)stream;
+    if (hint->numBlocks > 0) {
+        NTR_HIP(hipStreamSynchronize(s));
+        if (h_order) NTR_HIP(hipMemcpyAsync(h_order, hint->order, ((size_t)hint->numBlocks + 3) * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+        if (h_cost) NTR_HIP(hipMemcpyAsync(h_cost, hint->cost, (size_t)hint->numBlocks * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+        if (h_order || h_cost) NTR_HIP(hipStreamSynchronize(s));
+    }
+    state->numBlocks = hint->numBlocks;
+    state->device = hint->device;
+    state->uses = hint->uses;
+    state->valid = hint->valid ? 1 : 0;
+    state->predicted = hint->predicted ? 1 : 0;
+    return NTR_OK;
+}
+
 int ntr_sched_hint_predict(NtrSchedHint* hint, const uint32_t* d_blockCost, int32_t numBlocks, void* stream)
 {
     if (!hint || !d_blockCost || numBlocks < 1) return set_error(NTR_ERR_INVALID, "ntr_sched_hint_predict: bad argument");
@@ -1123,11 +1182,11 @@ int ntr_sched_hint_predict(NtrSchedHint* hint, const uint32_t* d_blockCost, int3
     int dev = 0;
     NTR_HIP(hipGetDevice(&dev));
     if (hint->numBlocks != numBlocks || hint->device != dev) {   // (the binding ntr_trace_bvh_hinted would make on first use)
-        const int rc = sched_hint_bind(hint, numBlocks, dev);
+        const int rc = sched_hint_bind(hint, numBlocks, dev, s);
         if (rc != NTR_OK) return rc;
     }
     NTR_HIP(hipMemcpyAsync(hint->cost, d_blockCost, (size_t)numBlocks * sizeof(unsigned int), hipMemcpyDeviceToDevice, s));
-    hipError_t le = ntr_launch_sched_order(hint->cost, numBlocks, tunables().schedClasses, hint->order, s);
+    hipError_t le = ntr_launch_sched_order(hint->cost, numBlocks, tunables().schedClasses, hint->order, 0, s);
     if (le == hipSuccess) le = ntr_launch_zero_words(hint->order + numBlocks, 3, s);   // the batch's coherence words / pool K: not estimated yet
     if (le != hipSuccess) return hip_fail(le, "sched_order launch");
     hint->uses = 0;      // the next launch starts the hint's life: it runs this order; the launches after it measure and refine

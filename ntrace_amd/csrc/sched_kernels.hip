@@ -246,6 +246,12 @@ __global__ void coherence_finish_kernel(unsigned int* __restrict__ out, int numB
     if (threadIdx.x == 0 && blockIdx.x == 0) out[2] = pool_k(out[0], out[1], numBlocks, poolKWide);
 }
 
+// order[i] = i: the identity order (a kernel, not a copy: see flatten_kernel).
+__global__ __launch_bounds__(256) void identity_order_kernel(unsigned int* __restrict__ order, int n)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) order[i] = (unsigned int)i;
+}
+
 // Clears `words` 32-bit words (a kernel, not hipMemsetAsync: see flatten_kernel).
 __global__ __launch_bounds__(256) void zero_words_kernel(unsigned int* __restrict__ p, int words)
 {
@@ -379,6 +385,15 @@ extern "C" hipError_t ntr_launch_coherence(const void* d_rays, int numRays, int 
     return hipGetLastError();
 }
 
+extern "C" hipError_t ntr_launch_identity_order(unsigned int* d_order, int numBlocks, hipStream_t stream)
+{
+    if (numBlocks <= 0) return hipSuccess;
+    int grid = (numBlocks + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(ntr::identity_order_kernel, dim3(grid), dim3(256), 0, stream, d_order, numBlocks);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t ntr_launch_zero_words(void* d_ptr, int words, hipStream_t stream)
 {
     if (words <= 0) return hipSuccess;
@@ -403,9 +418,11 @@ constexpr int SCHED_THREADS = 256;   // 64 classes x 256 threads x 4 B = 64 KB o
 constexpr int SCHED_MAX_CLASSES = 64;
 
 // MAXC: the classes the unrolled scans are written for (32: the default NTR_SCHED_CLASSES -- half the shuffles and registers of 64)
+// keepIfAllZero: every cost is zero -> order[] is left as it is.  A refresh launch whose body records no cost (the persistent body in
+// dynamic-fetch mode) measured nothing, and the identity order derived from nothing would replace the predicted one the launch ran.
 template <int MAXC>
 __global__ __launch_bounds__(SCHED_THREADS) void sched_order_kernel(const unsigned int* __restrict__ cost, int numBlocks, int classes,
-                                                                    unsigned int* __restrict__ order)
+                                                                    int keepIfAllZero, unsigned int* __restrict__ order)
 {
     __shared__ unsigned int s_cnt[MAXC][SCHED_THREADS];
     __shared__ unsigned int s_tot[MAXC][SCHED_THREADS / 64];
@@ -423,6 +440,7 @@ __global__ __launch_bounds__(SCHED_THREADS) void sched_order_kernel(const unsign
     __syncthreads();
     mx = 0;
     for (int w = 0; w < SCHED_THREADS / 64; w++) mx = max(mx, s_red[w]);
+    if (keepIfAllZero && mx == 0u) return;   // (workgroup-uniform: no barrier is left behind)
     // class 0 = heaviest.  Any monotone map of the cost onto [0, classes) will do -- the order only has to be a permutation, and both
     // passes below use the same map -- so a float multiply stands in for the 64-bit division (a hundred instructions per block).
     const float toClass = (float)classes / ((float)mx + 1.0f);
@@ -476,13 +494,13 @@ __global__ __launch_bounds__(SCHED_THREADS) void sched_order_kernel(const unsign
 }  // namespace ntr
 
 extern "C" hipError_t ntr_launch_sched_order(const unsigned int* d_cost, int numBlocks, int classes, unsigned int* d_order,
-                                             hipStream_t stream)
+                                             int keepIfAllZero, hipStream_t stream)
 {
     if (classes < 1) classes = 1;
     if (classes > ntr::SCHED_MAX_CLASSES) classes = ntr::SCHED_MAX_CLASSES;
     if (classes <= 32)
-        hipLaunchKernelGGL(ntr::sched_order_kernel<32>, dim3(1), dim3(ntr::SCHED_THREADS), 0, stream, d_cost, numBlocks, classes, d_order);
+        hipLaunchKernelGGL(ntr::sched_order_kernel<32>, dim3(1), dim3(ntr::SCHED_THREADS), 0, stream, d_cost, numBlocks, classes, keepIfAllZero, d_order);
     else
-        hipLaunchKernelGGL(ntr::sched_order_kernel<ntr::SCHED_MAX_CLASSES>, dim3(1), dim3(ntr::SCHED_THREADS), 0, stream, d_cost, numBlocks, classes, d_order);
+        hipLaunchKernelGGL(ntr::sched_order_kernel<ntr::SCHED_MAX_CLASSES>, dim3(1), dim3(ntr::SCHED_THREADS), 0, stream, d_cost, numBlocks, classes, keepIfAllZero, d_order);
     return hipGetLastError();
 }

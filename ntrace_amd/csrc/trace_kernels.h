@@ -113,8 +113,11 @@ extern "C" hipError_t ntr_launch_secondary_block_costs(const void* d_inResults, 
 extern "C" hipError_t ntr_launch_zero_words(void* d_ptr, int words, hipStream_t stream);
 // out[0] = atomicExch(status, 0): fetch-and-clear of the sticky status word in one device-side step
 extern "C" hipError_t ntr_launch_status_exchange(unsigned int* d_status, unsigned int* d_out, hipStream_t stream);
+// keepIfAllZero: a launch that recorded no cost (every word zero) leaves d_order as it is (the hint's refresh launches)
 extern "C" hipError_t ntr_launch_sched_order(const unsigned int* d_cost, int numBlocks, int classes, unsigned int* d_order,
-                                             hipStream_t stream);
+                                             int keepIfAllZero, hipStream_t stream);
+// d_order[i] = i for i < numBlocks (a freshly bound hint's order: a permutation before any launch reads it)
+extern "C" hipError_t ntr_launch_identity_order(unsigned int* d_order, int numBlocks, hipStream_t stream);
 extern "C" hipError_t ntr_launch_selftest_division(const float* d_x, const float* d_d, int nx, int nd,
                                                    unsigned int* d_mismatches, hipStream_t stream);
 extern "C" hipError_t ntr_launch_selftest_division_hard(int xe0, int de0, unsigned long long* d_counts, hipStream_t stream);

@@ -88,6 +88,35 @@ def test_sched_hint_object_lifecycle_without_device():
     assert L.ntr_sched_hint_destroy(None) == 0
 
 
+def test_sched_read_back_entry_points_check_their_arguments_without_device():
+    """ntr_sched_hint_inspect / ntr_predict_dispatch_order: null pointers, an unbound hint and empty or negative batches are answered
+    before any device work (an unbound hint has no arrays, so only its state can be read)."""
+    L = nt.lib()
+    h = C.c_void_p()
+    assert L.ntr_sched_hint_create(C.byref(h)) == 0
+    st = nt.SchedHintState()
+    st.numBlocks = st.uses = st.valid = st.predicted = 77
+    assert L.ntr_sched_hint_inspect(h, C.byref(st), None, None, None) == 0
+    assert (st.numBlocks, st.uses, st.valid, st.predicted) == (0, 0, 0, 0)
+    buf = np.zeros(16, np.uint32)
+    assert L.ntr_sched_hint_inspect(h, C.byref(st), buf.ctypes.data, None, None) == -1 and "not bound" in L.ntr_last_error().decode()
+    assert L.ntr_sched_hint_inspect(h, C.byref(st), None, buf.ctypes.data, None) == -1
+    assert L.ntr_sched_hint_inspect(h, None, None, None, None) == -1
+    assert L.ntr_sched_hint_inspect(None, C.byref(st), None, None, None) == -1
+    hint = nt.SchedHint()
+    assert hint.inspect() == {"numBlocks": 0, "device": -1, "uses": 0, "valid": 0, "predicted": 0}
+    hint.close()
+    assert L.ntr_sched_hint_destroy(h) == 0
+    one = np.zeros(64, np.uint8)
+    p = one.ctypes.data
+    assert L.ntr_predict_dispatch_order(-1, p, p, 64, p, p, None) == -1 and "numRays < 0" in L.ntr_last_error().decode()
+    assert L.ntr_predict_dispatch_order(0, None, None, 0, None, None, None) == 0          # an empty batch: nothing to do
+    for args in ((None, p, 64, p, p), (p, None, 64, p, p), (p, p, 64, None, p), (p, p, 64, p, None)):
+        assert L.ntr_predict_dispatch_order(10, *args, None) == -1 and "null argument" in L.ntr_last_error().decode()
+    for nbytes in (0, 100, 0x76543240):
+        assert L.ntr_predict_dispatch_order(10, p, p, nbytes, p, p, None) == -1
+
+
 def test_multi_gpu_partition_and_diagnostics_argument_checks():
     """The round-4 entry points check their arguments before any device or RCCL work: the partition arithmetic is pure host code, the
     diagnostics reject null / out-of-range arguments, and a group call without a group fails with a message instead of crashing."""
