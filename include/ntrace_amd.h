@@ -449,10 +449,34 @@ NTR_API int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_
                            void* d_nodes, int64_t nodesCapacity, void* d_triWoop, int64_t triWoopCapacity,
                            int32_t* d_triIndex, int64_t triIndexCapacity, NtrLbvhResult* result, void* stream);
 
+/* Result of ntr_hlbvh_build: the LBVH's counts, exact extents and times (lbvh.sortMs = Morton codes + sort, lbvh.emitMs = bottom-level
+ * emit, lbvh.refitMs = refit, lbvh.numLevels = creation batches refit), plus the cluster count, the number of top-level (SAH) inner
+ * nodes and levels, and the phase times of the clusters, the top level and the bottom level (emit + refit).  For hlbvhBits == 10 or
+ * numTris <= leafSize (the LBVH's tree) numClusters, topNodes and topLevels are 0 and lbvh is ntr_lbvh_build's result. */
+typedef struct NtrHlbvhResult {
+    NtrLbvhResult lbvh;
+    int32_t numClusters, topNodes, topLevels, pad;
+    float   clusterMs, topMs, bottomMs, pad2;
+} NtrHlbvhResult;
+
+/* HLBVHBuilder::buildHLBVH (src/rt/bvh/HLBVH/HLBVHBuilder.cpp:595-750; the path taken for hlbvh && hlbvhBits != 10, :44-47):
+ * the triangles are grouped into Morton clusters (equal code >> 3 * hlbvhBits, radixSort.cu:48-115), a binned-SAH tree of 8 bins per
+ * axis is built over the clusters (buildTopLevel :156-317, fillBins / findSplit / distribute, emitTreeKernel.cu:713-1027) and an LBVH
+ * inside each cluster (buildBottomLevel :319-406, starting level 3 * hlbvhBits - 1).  The ntr_lbvh_build arguments plus hlbvhBits in
+ * 0..10 (anything else is NTR_ERR_INVALID; 10 is ntr_lbvh_build).  Same Compact conventions, capacities (ntr_lbvh_capacity) and
+ * stream rules as ntr_lbvh_build; Renderer's HLBVH setup is hlbvhBits 4, leafSize 8, epsilon 0.001 (Renderer.cpp:201-209).  The
+ * tree equals the restatement tests/np_hlbvh.py in canonical form; its header lists the canonical choices where the reference is
+ * nondeterministic or broken.  Blocking. */
+NTR_API int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
+                            const float sceneMin[3], const float sceneMax[3], int32_t leafSize, float epsilon, int32_t hlbvhBits,
+                            void* d_nodes, int64_t nodesCapacity, void* d_triWoop, int64_t triWoopCapacity,
+                            int32_t* d_triIndex, int64_t triIndexCapacity, NtrHlbvhResult* result, void* stream);
+
 /* The builder keeps one grow-only scratch workspace per device between builds (a rebuild per frame must not pay allocations):
  * about 175 B per triangle on the default path (1.75 GB after a 10 M-triangle build).  A host that builds once and then only
  * traces returns it with this call (it waits for the device first); the next build allocates again.  ntr_ray_morton_sort keeps its
- * temporaries the same way (about 40 B per ray of the largest batch sorted so far); this call returns them too. */
+ * temporaries the same way (about 40 B per ray of the largest batch sorted so far), and ntr_hlbvh_build its own scratch (about 60 B per
+ * triangle plus about 500 B per Morton cluster); this call returns them too. */
 NTR_API int ntr_lbvh_release_workspace(void);
 
 /* reconstructKernel (src/rt/cuda/RendererKernels.cu:59-172; ReconstructInput, RendererKernels.hpp:46-70;

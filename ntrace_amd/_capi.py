@@ -50,6 +50,16 @@ class LbvhResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class HlbvhResult(C.Structure):
+    _fields_ = [("lbvh", LbvhResult), ("numClusters", C.c_int32), ("topNodes", C.c_int32), ("topLevels", C.c_int32),
+                ("pad", C.c_int32), ("clusterMs", C.c_float), ("topMs", C.c_float), ("bottomMs", C.c_float), ("pad2", C.c_float)]
+
+    def as_dict(self):
+        d = self.lbvh.as_dict()
+        d.update({k: getattr(self, k) for k, _ in self._fields_ if k not in ("lbvh", "pad", "pad2")})
+        return d
+
+
 class _HostBvhInfo(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
                 ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
@@ -130,6 +140,8 @@ SYMBOLS = [
     ("ntr_lbvh_capacity", C.c_int, [_i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     ("ntr_lbvh_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, C.c_float,
                                  _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(LbvhResult), _vp]),
+    ("ntr_hlbvh_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, C.c_float, _i32,
+                                  _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(HlbvhResult), _vp]),
     ("ntr_reconstruct", C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("ntr_ray_morton_sort", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_float)]),
     ("ntr_camera_decode", C.c_int, [C.c_char_p, C.POINTER(C.c_float)]),
@@ -526,6 +538,18 @@ def lbvh_build(num_tris, d_tri, num_verts, d_pos, scene_min, scene_max, leaf_siz
     _check(lib().ntr_lbvh_build(int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos), mn, mx, int(leaf_size),
                                 float(epsilon), _vp(d_nodes), int(nodes_cap), _vp(d_woop), int(woop_cap), _vp(d_idx),
                                 int(idx_cap), C.byref(res), _vp(stream)))
+    return res
+
+
+def hlbvh_build(num_tris, d_tri, num_verts, d_pos, scene_min, scene_max, leaf_size, epsilon, hlbvh_bits, d_nodes, nodes_cap,
+                d_woop, woop_cap, d_idx, idx_cap, stream=0):
+    """ntr_hlbvh_build: binned SAH over Morton clusters (HLBVHBuilder::buildHLBVH) into Compact buffers of lbvh_capacity() bytes."""
+    res = HlbvhResult()
+    mn = (C.c_float * 3)(*[float(x) for x in scene_min])
+    mx = (C.c_float * 3)(*[float(x) for x in scene_max])
+    _check(lib().ntr_hlbvh_build(int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos), mn, mx, int(leaf_size), float(epsilon),
+                                 int(hlbvh_bits), _vp(d_nodes), int(nodes_cap), _vp(d_woop), int(woop_cap), _vp(d_idx), int(idx_cap),
+                                 C.byref(res), _vp(stream)))
     return res
 
 

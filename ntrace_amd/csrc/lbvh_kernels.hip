@@ -36,6 +36,7 @@
 #include <mutex>
 #include "ntr_internal.h"
 #include "radix_sort.h"
+#include "woop_rows.h"   // woop_rows_verts / woop_rows (emitTreeKernel.cu:574-635)
 
 namespace ntr {
 
@@ -123,37 +124,6 @@ __global__ __launch_bounds__(MORTON_THREADS) void lbvh_morton_hist_kernel(int n,
         const unsigned int v = (&s_hist[0][0])[i];
         if (v) atomicAdd(&hist[i], v);
     }
-}
-
-// ---- Woop rows (emitTreeKernel.cu:574-635) ---------------------------------------------------------
-__device__ __forceinline__ void woop_rows_verts(float v0x, float v0y, float v0z, float v1x, float v1y, float v1z, float v2x, float v2y,
-                                                float v2z, float4& r0, float4& r1, float4& r2)
-{
-    const float c0x = v0x - v2x, c0y = v0y - v2y, c0z = v0z - v2z;
-    const float c1x = v1x - v2x, c1y = v1y - v2y, c1z = v1z - v2z;
-    const float c2x = c0y * c1z - c0z * c1y, c2y = c0z * c1x - c0x * c1z, c2z = c0x * c1y - c0y * c1x;
-    const float den = c0x * (c2z * c1y - c1z * c2y) - c0y * (c2z * c1x - c1z * c2x) + c0z * (c2y * c1x - c1y * c2x);
-    const float det = (float)(1.0 / (double)den);  // `1.0/(float)` is a binary64 divide in the reference (:589)
-
-    const float i0x = (c2z * c1y - c1z * c2y) * det, i0y = -(c2z * c1x - c1z * c2x) * det, i0z = (c2y * c1x - c1y * c2x) * det;
-    const float i1x = -(c2z * c0y - c0z * c2y) * det, i1y = (c2z * c0x - c0z * c2x) * det, i1z = -(c2y * c0x - c0y * c2x) * det;
-    const float i2x = (c1z * c0y - c0z * c1y) * det, i2y = -(c1z * c0x - c0z * c1x) * det, i2z = (c1y * c0x - c0y * c1x) * det;
-    const float o0w = -((-i2x) * v2x + (-i2y) * v2y + (-i2z) * v2z);
-    const float o1w = (-i0x) * v2x + (-i0y) * v2y + (-i0z) * v2z;
-    const float o2w = (-i1x) * v2x + (-i1y) * v2y + (-i1z) * v2z;
-    float o0x = i2x;
-    if (o0x == 0.0f) o0x = 0.0f;  // -0 would alias the leaf terminator
-    r0 = make_float4(o0x, i2y, i2z, o0w);
-    r1 = make_float4(i0x, i0y, i0z, o1w);
-    r2 = make_float4(i1x, i1y, i1z, o2w);
-}
-
-__device__ __forceinline__ void woop_rows(const int* __restrict__ tri, const float* __restrict__ pos, int t, float4& r0, float4& r1,
-                                          float4& r2)
-{
-    const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-    woop_rows_verts(pos[3 * i0], pos[3 * i0 + 1], pos[3 * i0 + 2], pos[3 * i1], pos[3 * i1 + 1], pos[3 * i1 + 2], pos[3 * i2],
-                    pos[3 * i2 + 1], pos[3 * i2 + 2], r0, r1, r2);
 }
 
 #include "lbvh_topdown.h"   // the top-down fallback (small scenes, oversize leaves)
@@ -1035,13 +1005,79 @@ using namespace ntr;
 
 #include "lbvh_workspace.h"   // PhaseEvents, the per-device workspace, Carver
 
+namespace ntr {
+// L1 + L2 of ntr_lbvh_build -- Morton codes and their stable sort, the same launches -- for the HLBVH builder (hlbvh_kernels.hip),
+// into scratch of at least lbvh_sort_scratch_bytes(n) bytes.  *errWord (device) is the chained scan's error word, read by the caller.
+static void lbvh_sort_layout(int n, size_t* off /* [7]: keysA keysB idxA idxB hist misc osState, [7] end */, int* osItems, int* osTiles)
+{
+    const Tunables tun = tunables();
+    *osItems = (tun.lbvhSortItems == 8 || tun.lbvhSortItems == 16 || tun.lbvhSortItems == 24 || tun.lbvhSortItems == 32)
+                   ? tun.lbvhSortItems : (n >= (1 << 23) ? 32 : (n >= (1 << 21) ? 24 : 8));
+    *osTiles = (n + OS_THREADS * *osItems - 1) / (OS_THREADS * *osItems);
+    Carver cv;
+    off[0] = cv.take((size_t)n * 4); off[1] = cv.take((size_t)n * 4);
+    off[2] = cv.take((size_t)n * 4); off[3] = cv.take((size_t)n * 4);
+    off[4] = cv.take(4 * 256 * 4); off[5] = cv.take(64);
+    off[6] = cv.take((size_t)*osTiles * 256 * 8);
+    off[7] = cv.off;
+}
+
+size_t lbvh_sort_scratch_bytes(int n)
+{
+    size_t off[8];
+    int items, tiles;
+    lbvh_sort_layout(n, off, &items, &tiles);
+    return off[7];
+}
+
+int lbvh_sort_codes(int n, const int32_t* d_tri, const float* d_pos, const float sceneMin[3], const float sceneMax[3], void* scratch,
+                    hipStream_t s, const unsigned int** keys, const int** idx, const unsigned int** errWord)
+{
+    size_t off[8];
+    int osItems, osTiles;
+    lbvh_sort_layout(n, off, &osItems, &osTiles);
+    char* ws = (char*)scratch;
+    unsigned int* osHist = (unsigned int*)(ws + off[4]);
+    unsigned int* osMisc = (unsigned int*)(ws + off[5]);
+    NTR_HIP(hipMemsetAsync(osHist, 0, off[6] - off[4], s));
+    const F3 lo = {sceneMin[0], sceneMin[1], sceneMin[2]};
+    const F3 step = {(sceneMax[0] - sceneMin[0]) / 1024.0f, (sceneMax[1] - sceneMin[1]) / 1024.0f, (sceneMax[2] - sceneMin[2]) / 1024.0f};
+    unsigned int *kIn = (unsigned int*)(ws + off[0]), *kOut = (unsigned int*)(ws + off[1]);
+    int *vIn = (int*)(ws + off[2]), *vOut = (int*)(ws + off[3]);
+    int mb = (n + 1024 * 4 - 1) / (1024 * 4);
+    if (mb > MORTON_SLOTS / 1024) mb = MORTON_SLOTS / 1024;
+    hipLaunchKernelGGL(lbvh_morton_hist_kernel<1024>, dim3(mb), dim3(1024), 0, s, n, d_tri, d_pos, lo, step, 0.0f, kIn, (int*)nullptr,
+                       (float2*)nullptr, (TriVerts*)nullptr, osHist, (unsigned long long*)(ws + off[6]), osTiles * 256);
+    for (int pass = 0; pass < 4; pass++) {
+        const unsigned int* dt = osHist + pass * 256;
+        unsigned long long* st = (unsigned long long*)(ws + off[6]);
+#define NTR_OS_LAUNCH(ITEMS)                                                                                                                \
+        onesweep_launch<ITEMS, 0, false>(s, osTiles, n, (const unsigned int*)kIn, pass == 0 ? (const int*)nullptr : (const int*)vIn, kOut, vOut, 1, pass * 8, pass, dt, st, \
+                                         osMisc + pass, osMisc + 4)
+        if (osItems == 32) NTR_OS_LAUNCH(32);
+        else if (osItems == 24) NTR_OS_LAUNCH(24);
+        else if (osItems == 16) NTR_OS_LAUNCH(16);
+        else NTR_OS_LAUNCH(8);
+#undef NTR_OS_LAUNCH
+        unsigned int* tk = kIn; kIn = kOut; kOut = tk;
+        int* tv = vIn; vIn = vOut; vOut = tv;
+    }
+    NTR_HIP(hipGetLastError());
+    *keys = kIn;
+    *idx = vIn;
+    *errWord = osMisc + 4;
+    return NTR_OK;
+}
+}  // namespace ntr
+
 extern "C" {
 
 int ntr_lbvh_release_workspace(void)
 {
     const int rc = workspace_release();
     const int rc2 = ntr::raysort_scratch_release();
-    return rc != NTR_OK ? rc : rc2;
+    const int rc3 = ntr::hlbvh_workspace_release();
+    return rc != NTR_OK ? rc : (rc2 != NTR_OK ? rc2 : rc3);
 }
 
 

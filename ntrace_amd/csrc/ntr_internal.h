@@ -23,6 +23,13 @@ bool stream_is_capturing(hipStream_t s);
 
 // rayops_kernels.hip: returns the per-device scratch of ntr_ray_morton_sort (ntr_lbvh_release_workspace calls it)
 int raysort_scratch_release();
+
+// lbvh_kernels.hip: Morton codes and their stable sort exactly as ntr_lbvh_build makes them (the HLBVH builder's first phase)
+size_t lbvh_sort_scratch_bytes(int n);
+int lbvh_sort_codes(int n, const int32_t* d_tri, const float* d_pos, const float sceneMin[3], const float sceneMax[3], void* scratch,
+                    hipStream_t s, const unsigned int** keys, const int** idx, const unsigned int** errWord);
+// hlbvh_kernels.hip: returns the HLBVH builder's per-device scratch (ntr_lbvh_release_workspace calls it)
+int hlbvh_workspace_release();
 }  // namespace ntr
 
 // ntr_api.cpp: (re)build the top-of-tree box table cached for this node buffer (dispatch-order prediction)

@@ -1,6 +1,6 @@
-// HLBVHBuilder.hpp -- GPU LBVH builder object (src/rt/bvh/HLBVH/HLBVHBuilder.hpp): a CudaBVH that
-// builds itself on the device.  Only the plain-LBVH path (buildLBVH, taken for !hlbvh ||
-// hlbvhBits == 10, HLBVHBuilder.cpp:44-47) is provided; buildHLBVH's SAH top level is out of scope.
+// HLBVHBuilder.hpp -- GPU LBVH / HLBVH builder object (src/rt/bvh/HLBVH/HLBVHBuilder.hpp): a CudaBVH that
+// builds itself on the device.  As in the reference (HLBVHBuilder.cpp:44-47), !hlbvh || hlbvhBits == 10 takes
+// buildLBVH (ntr_lbvh_build) and anything else buildHLBVH (ntr_hlbvh_build: binned SAH over Morton clusters).
 #pragma once
 #include "CudaBVH.hpp"
 #include "Scene.hpp"
@@ -24,9 +24,11 @@ public:
     F32  getGPUTime(void) const { return m_gpuTime; }
     void getStats(U32& nodes, U32& leaves, U32& nodeTop) const { nodes = m_nodesCnt; leaves = m_leafs; nodeTop = m_nodesCnt; }
     const NtrLbvhResult& getBuildResult(void) const { return m_result; }
+    const NtrHlbvhResult& getHlbvhResult(void) const { return m_hlResult; }   // zero after buildLBVH
 
 private:
     void buildLBVH(void);
+    void buildHLBVH(void);
 
     Scene*        m_scene;
     Platform      m_platform;
@@ -34,6 +36,7 @@ private:
     F32           m_gpuTime;
     U32           m_nodesCnt, m_leafs;
     NtrLbvhResult m_result;
+    NtrHlbvhResult m_hlResult;
 };
 
 }  // namespace FW

@@ -75,7 +75,10 @@ String Renderer::getCacheFileName(void)
     char name[64];
     const U32 h = hashBits(m_scene ? m_scene->hash() : 0u, m_platform.computeHash(), m_buildParams.computeHash(),
                            (U32)m_cudaTracer->getDesiredBVHLayout(), hashString("BVH"));
-    snprintf(name, sizeof(name), "/%08x_", h);
+    U32 hh = h;
+    if (m_builder == "HLBVH" && m_hlbvhParams.hlbvh)   // an HLBVH tree is never served as an LBVH tree or the reverse
+        hh = hashBits(h, 1u, (U32)m_hlbvhParams.hlbvhBits, hashString("HLBVH"));
+    snprintf(name, sizeof(name), "/%08x_", hh);
     return m_cachePath + name + m_builder + ".dat";
 }
 
@@ -97,11 +100,8 @@ CudaAS* Renderer::getCudaBVH(void)
         }
     }
     if (m_builder == "HLBVH") {
-        HLBVHParams params;  // Renderer.cpp:203-207 asks for hlbvh = true, hlbvhBits = 4; this backend
-        params.hlbvh = false;  // provides the plain LBVH pipeline of the same builder
-        params.leafSize = 8;
-        params.epsilon = 0.001f;
-        m_accelStruct = new HLBVHBuilder(m_scene, m_platform, params);
+        // Renderer.cpp:203-207 asks for hlbvh = true, hlbvhBits = 4; the default here stays the plain LBVH (setHLBVHParams)
+        m_accelStruct = new HLBVHBuilder(m_scene, m_platform, m_hlbvhParams);
     } else {
         BVH bvh(m_scene, m_platform, m_buildParams);
         m_accelStruct = new CudaBVH(bvh, layout);

@@ -35,6 +35,11 @@ public:
     void   setMesh(const WavefrontMesh* mesh);
     Scene* getScene(void) const { return m_scene; }
     void   setBuildParams(const BVH::BuildParams& params) { invalidateBVH(); m_buildParams = params; }
+    // Mirror extension (the reference reads these from its environment, Renderer.cpp:201-209): the parameters of the "HLBVH" builder.
+    // The default is hlbvh = false, leafSize 8, epsilon 0.001 -- the plain LBVH; hlbvh = true with hlbvhBits 4 is the reference's
+    // setup (binned SAH over Morton clusters, ntr_hlbvh_build).  Invalidates the BVH; cache names then depend on (hlbvh, hlbvhBits).
+    void   setHLBVHParams(const HLBVHParams& params) { invalidateBVH(); m_hlbvhParams = params; }
+    const HLBVHParams& getHLBVHParams(void) const { return m_hlbvhParams; }
     BVH::BuildParams& getBuildParams(void) { return m_buildParams; }
     void   invalidateBVH(void) { delete m_accelStruct; m_accelStruct = NULL; m_leafDepthOf = NULL; }
     void   setParams(const Params& params);
@@ -78,6 +83,7 @@ private:
     String             m_builder;
     Platform           m_platform;
     BVH::BuildParams   m_buildParams;
+    HLBVHParams        m_hlbvhParams;
     RayGen             m_raygen;
     Params             m_params;
     bool               m_enableRandom;
