@@ -1006,13 +1006,55 @@ using namespace ntr;
 #include "lbvh_workspace.h"   // PhaseEvents, the per-device workspace, Carver
 
 namespace ntr {
+// one-sweep tiles: 2048 keys while the launch is latency-bound; 6144 / 8192 for large inputs (fewer tiles to look back over, longer runs
+// per digit in the scatter: 10 M keys 80 -> 71 us per pass, scripts/jobs/gpu_job_r02sort.sh)
+static int onesweep_items(int n)
+{
+    const int items = tunables().lbvhSortItems;
+    if (items == 8 || items == 16 || items == 24 || items == 32) return items;
+    return n >= (1 << 23) ? 32 : (n >= (1 << 21) ? 24 : 8);
+}
+
+// L1: Morton codes (step = (max - min) / 1024 on the host, HLBVHBuilder.cpp:76-81), the sort's digit histograms and cleared tile state
+// -- and, when asked for, the LBVH's per-triangle box terms (boxMesh) or vertex records (triVerts), in mesh order.  Four triangles per
+// thread in 1024-thread workgroups (2.8 M triangles: 82 -> 65 us against 256-thread workgroups, a quarter of the histogram flushes).
+static void morton_launch(hipStream_t s, int n, const int32_t* tri, const float* pos, const float sceneMin[3], const float sceneMax[3], float eps,
+                          unsigned int* keys, float2* boxMesh, TriVerts* triVerts, unsigned int* hist, unsigned long long* tileState, int osTiles)
+{
+    const F3 lo = {sceneMin[0], sceneMin[1], sceneMin[2]};
+    const F3 step = {(sceneMax[0] - sceneMin[0]) / 1024.0f, (sceneMax[1] - sceneMin[1]) / 1024.0f, (sceneMax[2] - sceneMin[2]) / 1024.0f};
+    int mb = (n + 1024 * 4 - 1) / (1024 * 4);
+    if (mb > MORTON_SLOTS / 1024) mb = MORTON_SLOTS / 1024;
+    hipLaunchKernelGGL(lbvh_morton_hist_kernel<1024>, dim3(mb), dim3(1024), 0, s, n, tri, pos, lo, step, eps, keys, (int*)nullptr, boxMesh, triVerts,
+                       hist, tileState, osTiles * 256);
+}
+
+// L2: stable radix sort by key, 4 one-sweep passes of 8 bits (the 30-bit code fits).  The first pass numbers the keys itself; after the
+// fourth the sorted keys and triangle indices are back in the A buffers.  misc: [0..3] tickets, [4] the chained scan's error word.
+static void onesweep_sort(hipStream_t s, int n, int osItems, int osTiles, unsigned int* keysA, unsigned int* keysB, int* idxA, int* idxB,
+                          const unsigned int* hist, unsigned long long* tileState, unsigned int* misc)
+{
+    unsigned int *kIn = keysA, *kOut = keysB;
+    int *vIn = idxA, *vOut = idxB;
+    for (int pass = 0; pass < 4; pass++) {
+#define NTR_OS_LAUNCH(ITEMS)                                                                                                                \
+        onesweep_launch<ITEMS, 0, false>(s, osTiles, n, (const unsigned int*)kIn, pass == 0 ? (const int*)nullptr : (const int*)vIn, kOut, vOut, 1, pass * 8, pass, \
+                                         hist + pass * 256, tileState, misc + pass, misc + 4)
+        if (osItems == 32) NTR_OS_LAUNCH(32);
+        else if (osItems == 24) NTR_OS_LAUNCH(24);
+        else if (osItems == 16) NTR_OS_LAUNCH(16);
+        else NTR_OS_LAUNCH(8);
+#undef NTR_OS_LAUNCH
+        unsigned int* tk = kIn; kIn = kOut; kOut = tk;
+        int* tv = vIn; vIn = vOut; vOut = tv;
+    }
+}
+
 // L1 + L2 of ntr_lbvh_build -- Morton codes and their stable sort, the same launches -- for the HLBVH builder (hlbvh_kernels.hip),
 // into scratch of at least lbvh_sort_scratch_bytes(n) bytes.  *errWord (device) is the chained scan's error word, read by the caller.
 static void lbvh_sort_layout(int n, size_t* off /* [7]: keysA keysB idxA idxB hist misc osState, [7] end */, int* osItems, int* osTiles)
 {
-    const Tunables tun = tunables();
-    *osItems = (tun.lbvhSortItems == 8 || tun.lbvhSortItems == 16 || tun.lbvhSortItems == 24 || tun.lbvhSortItems == 32)
-                   ? tun.lbvhSortItems : (n >= (1 << 23) ? 32 : (n >= (1 << 21) ? 24 : 8));
+    *osItems = onesweep_items(n);
     *osTiles = (n + OS_THREADS * *osItems - 1) / (OS_THREADS * *osItems);
     Carver cv;
     off[0] = cv.take((size_t)n * 4); off[1] = cv.take((size_t)n * 4);
@@ -1039,32 +1081,14 @@ int lbvh_sort_codes(int n, const int32_t* d_tri, const float* d_pos, const float
     char* ws = (char*)scratch;
     unsigned int* osHist = (unsigned int*)(ws + off[4]);
     unsigned int* osMisc = (unsigned int*)(ws + off[5]);
+    unsigned long long* osState = (unsigned long long*)(ws + off[6]);
     NTR_HIP(hipMemsetAsync(osHist, 0, off[6] - off[4], s));
-    const F3 lo = {sceneMin[0], sceneMin[1], sceneMin[2]};
-    const F3 step = {(sceneMax[0] - sceneMin[0]) / 1024.0f, (sceneMax[1] - sceneMin[1]) / 1024.0f, (sceneMax[2] - sceneMin[2]) / 1024.0f};
-    unsigned int *kIn = (unsigned int*)(ws + off[0]), *kOut = (unsigned int*)(ws + off[1]);
-    int *vIn = (int*)(ws + off[2]), *vOut = (int*)(ws + off[3]);
-    int mb = (n + 1024 * 4 - 1) / (1024 * 4);
-    if (mb > MORTON_SLOTS / 1024) mb = MORTON_SLOTS / 1024;
-    hipLaunchKernelGGL(lbvh_morton_hist_kernel<1024>, dim3(mb), dim3(1024), 0, s, n, d_tri, d_pos, lo, step, 0.0f, kIn, (int*)nullptr,
-                       (float2*)nullptr, (TriVerts*)nullptr, osHist, (unsigned long long*)(ws + off[6]), osTiles * 256);
-    for (int pass = 0; pass < 4; pass++) {
-        const unsigned int* dt = osHist + pass * 256;
-        unsigned long long* st = (unsigned long long*)(ws + off[6]);
-#define NTR_OS_LAUNCH(ITEMS)                                                                                                                \
-        onesweep_launch<ITEMS, 0, false>(s, osTiles, n, (const unsigned int*)kIn, pass == 0 ? (const int*)nullptr : (const int*)vIn, kOut, vOut, 1, pass * 8, pass, dt, st, \
-                                         osMisc + pass, osMisc + 4)
-        if (osItems == 32) NTR_OS_LAUNCH(32);
-        else if (osItems == 24) NTR_OS_LAUNCH(24);
-        else if (osItems == 16) NTR_OS_LAUNCH(16);
-        else NTR_OS_LAUNCH(8);
-#undef NTR_OS_LAUNCH
-        unsigned int* tk = kIn; kIn = kOut; kOut = tk;
-        int* tv = vIn; vIn = vOut; vOut = tv;
-    }
+    morton_launch(s, n, d_tri, d_pos, sceneMin, sceneMax, 0.0f, (unsigned int*)(ws + off[0]), nullptr, nullptr, osHist, osState, osTiles);
+    onesweep_sort(s, n, osItems, osTiles, (unsigned int*)(ws + off[0]), (unsigned int*)(ws + off[1]), (int*)(ws + off[2]), (int*)(ws + off[3]),
+                  osHist, osState, osMisc);
     NTR_HIP(hipGetLastError());
-    *keys = kIn;
-    *idx = vIn;
+    *keys = (const unsigned int*)(ws + off[0]);
+    *idx = (const int*)(ws + off[2]);
     *errWord = osMisc + 4;
     return NTR_OK;
 }
@@ -1108,11 +1132,8 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     hipStream_t s = (hipStream_t)stream;
     const int n = numTris;
     if (n >= (1 << 28)) return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: at most 2^28 - 1 triangles");
-    // one-sweep tiles: 2048 keys while the launch is latency-bound; 6144 / 8192 for large inputs (fewer tiles to look back over, longer
-    // runs per digit in the scatter: 10 M keys 80 -> 71 us per pass, scripts/jobs/gpu_job_r02sort.sh)
     const Tunables tun = tunables();
-    const int osItems = (tun.lbvhSortItems == 8 || tun.lbvhSortItems == 16 || tun.lbvhSortItems == 24 || tun.lbvhSortItems == 32)
-                            ? tun.lbvhSortItems : (n >= (1 << 23) ? 32 : (n >= (1 << 21) ? 24 : 8));
+    const int osItems = onesweep_items(n);
     const int osTiles = (n + OS_THREADS * osItems - 1) / (OS_THREADS * osItems);
     if (n >= (1 << 27)) return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: at most 2^27 - 1 triangles");
 
@@ -1175,44 +1196,16 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
 
     NTR_HIP(hipMemsetAsync(ws + oState, 0, (bottomUp ? oAggZeroEnd : oClearEnd) - oState, s));
 
-    // L1: Morton codes (step = (max - min) / 1024 on the host, HLBVHBuilder.cpp:76-81)
-    F3 lo = {sceneMin[0], sceneMin[1], sceneMin[2]};
-    F3 step = {(sceneMax[0] - sceneMin[0]) / 1024.0f, (sceneMax[1] - sceneMin[1]) / 1024.0f, (sceneMax[2] - sceneMin[2]) / 1024.0f};
-    unsigned int *kIn = (unsigned int*)(ws + oKeysA), *kOut = (unsigned int*)(ws + oKeysB);
-    int *vIn = (int*)(ws + oIdxA), *vOut = (int*)(ws + oIdxB);
-    {
-        const int mortonKeys = tun.lbvhMortonKeys > 0 ? tun.lbvhMortonKeys : 4;
-        const int mortonThreads = tun.lbvhMortonThreads > 0 ? tun.lbvhMortonThreads : 1024;   // 2.8 M triangles: 82 -> 65 us against 256-thread workgroups (a quarter of the histogram flushes)
-        int mb = (n + mortonThreads * mortonKeys - 1) / (mortonThreads * mortonKeys);
-        if (mb > MORTON_SLOTS / mortonThreads) mb = MORTON_SLOTS / mortonThreads;
-#define NTR_MORTON_LAUNCH(T)                                                                                                                  \
-        hipLaunchKernelGGL(lbvh_morton_hist_kernel<T>, dim3(mb), dim3(T), 0, s, n, d_triVtxIndex, d_vtxPos, lo, step, epsilon, kIn, (int*)nullptr,     \
-                           bottomUp ? (float2*)nullptr : (float2*)(ws + oWoop), bottomUp ? (TriVerts*)(ws + oTriVerts) : (TriVerts*)nullptr, osHist, \
-                           (unsigned long long*)(ws + oOsState), osTiles * 256)
-        if (mortonThreads == 1024) NTR_MORTON_LAUNCH(1024); else if (mortonThreads == 512) NTR_MORTON_LAUNCH(512); else NTR_MORTON_LAUNCH(256);
-#undef NTR_MORTON_LAUNCH
-    }
+    // L1 + L2: Morton codes, then their stable sort
+    unsigned long long* osState = (unsigned long long*)(ws + oOsState);
+    morton_launch(s, n, d_triVtxIndex, d_vtxPos, sceneMin, sceneMax, epsilon, (unsigned int*)(ws + oKeysA), topDown ? (float2*)(ws + oWoop) : nullptr,
+                  bottomUp ? (TriVerts*)(ws + oTriVerts) : nullptr, osHist, osState, osTiles);
     pe.mark(1);
-
-    // L2: stable radix sort by key, 4 passes of 8 bits (the 30-bit code fits)
-    for (int pass = 0; pass < 4; pass++) {
-        const int shift = pass * 8;
-        const unsigned int* dt = osHist + pass * 256;
-        unsigned long long* st = (unsigned long long*)(ws + oOsState);
-#define NTR_OS_LAUNCH(ITEMS)                                                                                                                \
-        onesweep_launch<ITEMS, 0, false>(s, osTiles, n, (const unsigned int*)kIn, pass == 0 ? (const int*)nullptr : (const int*)vIn, kOut, vOut, 1, shift, pass, dt, st,   \
-                                         osMisc + pass, osMisc + 4)
-        if (osItems == 32) NTR_OS_LAUNCH(32);
-        else if (osItems == 24) NTR_OS_LAUNCH(24);
-        else if (osItems == 16) NTR_OS_LAUNCH(16);
-        else NTR_OS_LAUNCH(8);
-#undef NTR_OS_LAUNCH
-        unsigned int* tk = kIn; kIn = kOut; kOut = tk;
-        int* tv = vIn; vIn = vOut; vOut = tv;
-    }
+    onesweep_sort(s, n, osItems, osTiles, (unsigned int*)(ws + oKeysA), (unsigned int*)(ws + oKeysB), (int*)(ws + oIdxA), (int*)(ws + oIdxB), osHist,
+                  osState, osMisc);
     pe.mark(2);
-    const unsigned int* keys = kIn;  // after 4 passes the sorted data is back in the A buffers
-    const int* triSorted = vIn;
+    const unsigned int* keys = (const unsigned int*)(ws + oKeysA);
+    const int* triSorted = (const int*)(ws + oIdxA);
 
     // L4 (top-down path only): the per-triangle box terms in sorted order; its Woop rows are produced by lbvh_place_kernel once the leaves
     // have their slots.  The bottom-up path writes Woop rows inside the agglomerate kernel.
@@ -1235,22 +1228,6 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
         int4* q0 = (int4*)(ws + oQ0);
         int4* q1 = (int4*)(ws + oQ1);
         unsigned int* aggMisc = (unsigned int*)(ws + oAggMisc);
-        auto launch_subtrees = [&](int blocks) -> int {
-            const int subThreads = tun.lbvhSubThreads;
-            const size_t subLds = (size_t)c.spill * (4 + 16);  // keys + entry list
-            if (subLds > 65536) {
-                const void* fn = subThreads == 64 ? (const void*)lbvh_subtree_kernel<64>
-                               : subThreads == 256 ? (const void*)lbvh_subtree_kernel<256> : (const void*)lbvh_subtree_kernel<128>;
-                NTR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)subLds));
-            }
-            if (subThreads == 64)
-                hipLaunchKernelGGL(lbvh_subtree_kernel<64>, dim3(blocks), dim3(64), subLds, s, c, c.spill);
-            else if (subThreads == 256)
-                hipLaunchKernelGGL(lbvh_subtree_kernel<256>, dim3(blocks), dim3(256), subLds, s, c, c.spill);
-            else
-                hipLaunchKernelGGL(lbvh_subtree_kernel<128>, dim3(blocks), dim3(128), subLds, s, c, c.spill);
-            return NTR_OK;
-        };
         if (topMode == 3) {
             AggCtx a;
             a.keys = keys; a.triSorted = triSorted; a.triVerts = (const TriVerts*)(ws + oTriVerts);
@@ -1266,7 +1243,7 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
             // leaf starts and their prefix counts first: everything after it writes to final places
             // small builds are latency chains: one position per thread (262 k triangles: leaf marks 21 -> 16 us); large ones are
             // throughput: four positions per thread in a quarter of the threads (10 M: 70 against 82 us)
-            if (tun.lbvhMarkThreads == 256 || (tun.lbvhMarkThreads != 1024 && n >= (1 << 21)))
+            if (n >= (1 << 21))
                 hipLaunchKernelGGL(lbvh_leafmark_kernel<256>, dim3(cntTiles), dim3(256), 0, s, n, leafSize, keys, (unsigned long long*)(ws + oLeafBits),
                                    (unsigned long long*)(ws + oRunBits), (unsigned int*)(ws + oTileCount), (unsigned int*)(ws + oSubBase), (unsigned char*)(ws + oRunDepth), state);
             else
@@ -1306,13 +1283,11 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
         }
         pe.mark(4);
         int subBlocks = n / 2 + 1;
-        const int subMax = 256 * (2048 / (tun.lbvhSubThreads > 0 ? tun.lbvhSubThreads : 128));
-        if (subBlocks > subMax) subBlocks = subMax;
+        if (subBlocks > 256 * 16) subBlocks = 256 * 16;   // 16 128-thread workgroups per CU
         if (topMode == 0) subBlocks = 1;
-        {
-            const int rc = launch_subtrees(subBlocks);
-            if (rc != NTR_OK) return rc;
-        }
+        const size_t subLds = (size_t)c.spill * (4 + 16);  // keys + entry list
+        if (subLds > 65536) NTR_HIP(hipFuncSetAttribute((const void*)lbvh_subtree_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)subLds));
+        hipLaunchKernelGGL(lbvh_subtree_kernel<128>, dim3(subBlocks), dim3(128), subLds, s, c, c.spill);
         pe.mark(5);
         if (topMode == 2)
             hipLaunchKernelGGL(lbvh_top_refit_kernel, dim3(1), dim3(TOP_THREADS), 0, s, (const LbvhState*)state, (const int*)(ws + oTopLst),

@@ -20,11 +20,10 @@
 #endif
 
 // kernel variants (selected by the reference's kernel file names, see ntr_query_config)
-#define NTR_VARIANT_PERRAY 0      // one ray per lane, while-while
+// (3 and 4 were per-ray launches in 128- and 64-thread workgroups with the while-while loop; retired, the numbers are not reused)
+#define NTR_VARIANT_PERRAY 0      // one ray per lane: the name class of fermi_speculative_while_while (launched as 6 or 7)
 #define NTR_VARIANT_PERSISTENT 1  // persistent waves, ballot/mbcnt dynamic fetch
 #define NTR_VARIANT_PERRAY_STATS 2 // per-ray kernel + traversal counters
-#define NTR_VARIANT_PERRAY_W2 3    // per-ray kernel in 128-thread workgroups (any-hit launches)
-#define NTR_VARIANT_PERRAY_W1 4    // per-ray kernel in 64-thread workgroups
 #define NTR_VARIANT_PERSISTENT_UNIFIED 5  // persistent waves, unified-step loop (every live lane advances each iteration)
 #define NTR_VARIANT_PERRAY_UNIFIED_W1 6   // per-ray kernel, 64-thread workgroups, unified-step loop
 #define NTR_MINIPOOL_MAX_K 16             // a wave's private pool: at most this many 64-ray chunks

@@ -228,7 +228,7 @@ static constexpr int kNoNode = (int)0xFFFFFF00u;  // buffer offset beyond any ex
 
 // One inner-node step of trace<BVHLayout_Compact> (CudaBVH.cpp:721-775).  Executed by the whole
 // wave; only lanes whose current node is an inner node (`inner`) update their state.
-template <bool FAST, int OCT = 8>
+template <bool FAST>
 __device__ __forceinline__ void inner_step(Rsrc nodes, bool inner, const RayRegs& r,
                                            int& node, LaneStack& st, int (&spill)[SPILL_DEPTH], unsigned int* status)
 {
@@ -240,7 +240,7 @@ __device__ __forceinline__ void inner_step(Rsrc nodes, bool inner, const RayRegs
     keep(nc);
 
     float mn0, mx0, mn1, mx1;
-    ray_box2<FAST, OCT>(r, n0, n1, nz, mn0, mx0, mn1, mx1);
+    ray_box2<FAST>(r, n0, n1, nz, mn0, mx0, mn1, mx1);
 
     const bool i0 = (mn0 <= mx0) && (mx0 >= r.tmin) && (mn0 <= r.tmax);
     const bool i1 = (mn1 <= mx1) && (mx1 >= r.tmin) && (mn1 <= r.tmax);
@@ -327,7 +327,7 @@ __device__ __forceinline__ void load_ray(const NtrRay* __restrict__ rays, int ra
 // visiting order is exactly the CPU tracer's depth-first order, whatever the other lanes do.
 // SLICED (persistent kernels): the loop also ends after `slice` rounds of it (`slice` counts down; the caller looks at the wave -- posts the
 // dequeue of its next chunk -- and calls again).
-template <bool FAST, bool STATS, bool DYNAMIC_FETCH, int OCT = 8, bool SLICED = false>
+template <bool FAST, bool STATS, bool DYNAMIC_FETCH, bool SLICED = false>
 __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int& node,
                                          LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit,
                                          int& hitAddr, float& hitU, float& hitV, LaneStats& ls, unsigned int* status,
@@ -344,7 +344,7 @@ __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int&
             // lanes still hold an inner node while others already wait at a leaf, serve the leaves first
             // instead of letting a handful of stragglers stall the wave.
             if (__popcll(innerMask) < leafSwitchBelow && __ballot(node < 0) != 0ull) break;
-            inner_step<FAST, OCT>(nodes, inner, r, node, st, spill, status);
+            inner_step<FAST>(nodes, inner, r, node, st, spill, status);
             if (STATS && inner) ls.inner++;
         }
         if (node < 0) {
@@ -357,15 +357,15 @@ __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int&
         if (DYNAMIC_FETCH && !poolEmpty && __popcll(live) < fetchThreshold) break;
     }
 }
-template <bool FAST, bool STATS, bool DYNAMIC_FETCH, int OCT = 8>
+template <bool FAST, bool STATS, bool DYNAMIC_FETCH>
 __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int& node,
                                          LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit,
                                          int& hitAddr, float& hitU, float& hitV, LaneStats& ls, unsigned int* status,
                                          bool poolEmpty, int fetchThreshold, int leafSwitchBelow)
 {
     int never = 0;
-    traverse<FAST, STATS, DYNAMIC_FETCH, OCT, false>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, status, poolEmpty, fetchThreshold,
-                                                     leafSwitchBelow, never);
+    traverse<FAST, STATS, DYNAMIC_FETCH, false>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, status, poolEmpty, fetchThreshold,
+                                                leafSwitchBelow, never);
 }
 
 // Unified-step traversal (the dynamic-fetch kernel's loop).  The while-while loop above lets a wave alternate between an
@@ -645,9 +645,9 @@ __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs&
 namespace ntr {
 
 // ---------------------------------------------------------------------------------
-// Variant 1: one ray per lane, while-while ("fermi_speculative_while_while" slot).
+// Variant 1: one ray per lane ("fermi_speculative_while_while" slot).
 // ---------------------------------------------------------------------------------
-// UNIFIED: the unified-step loop (traverse_unified) -- for trees whose leaves hold several triangles (the device LBVH).
+// UNIFIED: the unified-step loop (traverse_unified) -- every per-ray launch but the stats one, which counts the while-while loop's steps.
 // MINI: the launch may run as the wave-private mini-pool instead (minipool_body below), decided on the device per batch.
 template <bool FLATF>
 __device__ __forceinline__ void minipool_body(const TraceParams& p, unsigned int K, lds_int* stackBase);
@@ -701,7 +701,7 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
     const bool fastWave = (p.bvhFlags & NTR_BVH_FASTDIV) && __ballot(node != kSentinel && !ray_is_nice(r, p.bvhFlags)) == 0ull;
     // direction signs shared by every live ray of the wave (a primary wave is an 8 x 8 pixel tile): the octant's own slab test
     int oct = 8;
-    if (!STATS && fastWave && p.octant && (p.bvhFlags & NTR_BVH_ORDERED)) {
+    if (UNIFIED && fastWave && p.octant && (p.bvhFlags & NTR_BVH_ORDERED)) {
         const unsigned long long liveMask = __ballot(node != kSentinel);
         const unsigned long long sx = __ballot(node != kSentinel && r.dx < 0.0f), sy = __ballot(node != kSentinel && r.dy < 0.0f),
                                  sz = __ballot(node != kSentinel && r.dz < 0.0f);
@@ -726,22 +726,7 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
 #undef NTR_UNIFIED_OCT
         else if (fastWave) traverse_unified<true, FLATF, 8, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
         else traverse_unified<false, FLATF, 8, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
-    } else
-#define NTR_TRAVERSE_OCT(O) traverse<true, STATS, false, O>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow)
-    if (!STATS && oct < 8) {
-        switch (oct) {
-            case 0: NTR_TRAVERSE_OCT(0); break;
-            case 1: NTR_TRAVERSE_OCT(1); break;
-            case 2: NTR_TRAVERSE_OCT(2); break;
-            case 3: NTR_TRAVERSE_OCT(3); break;
-            case 4: NTR_TRAVERSE_OCT(4); break;
-            case 5: NTR_TRAVERSE_OCT(5); break;
-            case 6: NTR_TRAVERSE_OCT(6); break;
-            default: NTR_TRAVERSE_OCT(7); break;
-        }
-    }
-#undef NTR_TRAVERSE_OCT
-    else if (fastWave) traverse<true, STATS, false>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow);
+    } else if (fastWave) traverse<true, STATS, false>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow);
     else traverse<false, STATS, false>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow);
 
     if (p.cost && lane == 0)  // scheduling feedback: a block's cost is the lifetime of its longest wave
@@ -996,8 +981,8 @@ __global__ __launch_bounds__(WAVES * 64, NTR_TRACE_PERSISTENT_MIN_WAVES_PER_SIMD
                 if (fastWave) uniform_prologue<true, 8>(ub, r, node, st, spill, p.status);
                 else uniform_prologue<false, 8>(ub, r, node, st, spill, p.status);
             }
-            if (fastWave) traverse<true, false, true, 8, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, slice);
-            else traverse<false, false, true, 8, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, slice);
+            if (fastWave) traverse<true, false, true, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, slice);
+            else traverse<false, false, true, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, slice);
         }
         // ---- dequeue-ahead: post the atomic of the wave's next chunk now (its latency hides behind the rest of this chunk) -------------
         if (!splitOn && prefetchIn >= 0 && !poolEmpty) {
@@ -1115,15 +1100,6 @@ extern "C" hipError_t ntr_launch_trace(int variant, const ntr::TraceParams* p, i
 {
     constexpr int WAVES = NTR_TRACE_WAVES_PER_BLOCK;
     switch (variant) {
-    case NTR_VARIANT_PERRAY:
-        hipLaunchKernelGGL((ntr::trace_bvh_perray<WAVES, false>), dim3(numBlocks), dim3(WAVES * 64), 0, stream, *p);
-        break;
-    case NTR_VARIANT_PERRAY_W2:   // smaller workgroups for short any-hit rays (numBlocks counts 128-ray blocks)
-        hipLaunchKernelGGL((ntr::trace_bvh_perray<2, false>), dim3(numBlocks), dim3(128), 0, stream, *p);
-        break;
-    case NTR_VARIANT_PERRAY_W1:
-        hipLaunchKernelGGL((ntr::trace_bvh_perray<1, false>), dim3(numBlocks), dim3(64), 0, stream, *p);
-        break;
     case NTR_VARIANT_PERRAY_UNIFIED_W1:   // flatFetch 0: the two-group descriptor fetch (A/B; extents below 64 bytes)
         if (p->flatFetch) hipLaunchKernelGGL((ntr::trace_bvh_perray<1, false, true, true>), dim3(numBlocks), dim3(64), 0, stream, *p);
         else hipLaunchKernelGGL((ntr::trace_bvh_perray<1, false, true, false>), dim3(numBlocks), dim3(64), 0, stream, *p);

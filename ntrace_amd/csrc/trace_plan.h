@@ -90,7 +90,7 @@ inline TracePlan plan_trace(const Tunables& tun, const TraceBatchDesc& b)
     // the persistent body of this launch: the name's own when the named body runs, kepler_dynamic_fetch's -- dynamic fetch, unified-step loop,
     // ray splitting: the body that is fast on incoherent batches -- in every routed launch, whatever the name
     const bool routedPersistentName = route && b.variant == NTR_VARIANT_PERSISTENT && !b.anyHit && bigEnough && (256 % pl.chunk) == 0 &&
-                                      tun.perrayUnified != 0 && tun.minipool < 0 && tun.predictPersistent != 0;
+                                      tun.minipool < 0 && tun.predictPersistent != 0;
     const bool persistentDynamic = (b.variant == NTR_VARIANT_PERSISTENT && !routedPersistentName) ? b.dynamicFetch : true;
     pl.unified = persistentDynamic && tun.unified != 0;
     pl.persistentFetchThreshold = tun.fetchThreshold >= 0 ? tun.fetchThreshold : (persistentDynamic ? (pl.unified ? 48 : 24) : 0);
@@ -139,32 +139,25 @@ inline TracePlan plan_trace(const Tunables& tun, const TraceBatchDesc& b)
     pl.predictable = (pl.variant == NTR_VARIANT_PERRAY || pl.persistentOrder) && !b.anyHit && bigEnough;
     pl.probeOnRefresh = pl.variant == NTR_VARIANT_PERRAY && !b.anyHit && tun.minipool < 0 && bigEnough;
 
-    // Workgroup size of the per-ray kernel: smaller workgroups retire (and are replaced) sooner.  The dispatch order and the cost
-    // feedback stay in units of 256 rays: numBlocks counts those, the launch has 4 / waves workgroups per unit.
+    // The per-ray kernel runs in one-wave workgroups (smaller workgroups retire, and are replaced, sooner: primary +2.1 %, AO +1.7 %
+    // against four waves) with the unified-step loop (one node OR one triangle per lane and iteration, one group of loads): closest-hit
+    // launches on any tree (atrium primary +5 %, conference +21 %, LBVH trees +50 %) and any-hit launches (multi-triangle leaves: always
+    // ahead; short AO rays in one-triangle-leaf trees: 4 % ahead since the one-correction divide -- profiles/r04_perray_unified_anyhit_knob.txt).
+    // The dispatch order and the cost feedback stay in units of 256 rays: numBlocks counts those, the launch has 4 workgroups per unit.
     pl.launchVariant = pl.variant;
     pl.launchBlocks = pl.numBlocks;
     if (pl.variant == NTR_VARIANT_PERSISTENT) pl.launchVariant = pl.persistentVariant;
-    const int wantWaves = b.anyHit ? tun.anyHitWaves : tun.closestWaves;
-    if (pl.variant == NTR_VARIANT_PERRAY && wantWaves < NTR_TRACE_WAVES_PER_BLOCK) {
-        const int waves = wantWaves <= 1 ? 1 : 2;
-        pl.launchVariant = waves == 1 ? NTR_VARIANT_PERRAY_W1 : NTR_VARIANT_PERRAY_W2;
-        pl.launchBlocks = pl.numBlocks * (4 / waves);
-        // unified-step loop (one node OR one triangle per lane and iteration, one group of loads): closest-hit launches on any tree
-        // (atrium primary +5 %, conference +21 %, LBVH trees +50 %) and any-hit launches (multi-triangle leaves: always ahead; short AO
-        // rays in one-triangle-leaf trees: the while-while loop was 2-3 % ahead while a step cost ~100 vector instructions, the unified
-        // loop is 4 % ahead since the one-correction divide -- profiles/r04_perray_unified_anyhit_knob.txt)
-        if (tun.perrayUnified > 0 || (tun.perrayUnified < 0 && (!b.anyHit || (b.bvhFlags & NTR_BVH_WIDE_LEAVES)))) {
-            pl.launchVariant = NTR_VARIANT_PERRAY_UNIFIED_W1;
-            pl.launchBlocks = pl.numBlocks * 4;
-            // wave-private mini-pool: a wave owns K x 64 rays and refills its finished lanes from them.  K is decided on the device: the
-            // prediction of this launch wrote it (incoherent batch: minipoolWide, else 1), or the batch's hint kept it from its first launch.
-            if (tun.minipool != 0 && !b.anyHit) {
-                pl.launchVariant = NTR_VARIANT_PERRAY_UNIFIED_MINI;
-                pl.minipool = true;
-                pl.fetchThreshold = tun.minipoolThreshold;
-                pl.poolKConst = tun.minipool > 0 ? tun.minipool : 1;
-                pl.poolKFromDevice = tun.minipool < 0;
-            }
+    if (pl.variant == NTR_VARIANT_PERRAY) {
+        pl.launchVariant = NTR_VARIANT_PERRAY_UNIFIED_W1;
+        pl.launchBlocks = pl.numBlocks * 4;
+        // wave-private mini-pool: a wave owns K x 64 rays and refills its finished lanes from them.  K is decided on the device: the
+        // prediction of this launch wrote it (incoherent batch: minipoolWide, else 1), or the batch's hint kept it from its first launch.
+        if (tun.minipool != 0 && !b.anyHit) {
+            pl.launchVariant = NTR_VARIANT_PERRAY_UNIFIED_MINI;
+            pl.minipool = true;
+            pl.fetchThreshold = tun.minipoolThreshold;
+            pl.poolKConst = tun.minipool > 0 ? tun.minipool : 1;
+            pl.poolKFromDevice = tun.minipool < 0;
         }
     }
 
@@ -174,7 +167,7 @@ inline TracePlan plan_trace(const Tunables& tun, const TraceBatchDesc& b)
         if (pl.variant == NTR_VARIANT_PERRAY && pl.launchVariant == NTR_VARIANT_PERRAY_UNIFIED_MINI && pl.poolKFromDevice) {
             pl.coherentRoute = 1;
             persistent_grid();
-        } else if (pl.variant == NTR_VARIANT_PERSISTENT && tun.perrayUnified != 0 && tun.minipool < 0 && pl.predictable) {
+        } else if (pl.variant == NTR_VARIANT_PERSISTENT && tun.minipool < 0 && pl.predictable) {
             pl.coherentRoute = 1;
         }
     }

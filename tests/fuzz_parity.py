@@ -153,9 +153,7 @@ def main(argv=None):
                 nt.set_tunables(NTR_LBVH_SPLIT=int(rng.choice([2, 16, 100, 3000])) if rng.random() < 0.3 else None,
                                 NTR_LBVH_AGG_LDS=int(rng.choice([1, 1, 0])),
                                 NTR_LBVH_AGG_STAGED=int(rng.choice([-1, 0, 1])),
-                                NTR_LBVH_SORT_ITEMS=int(rng.choice([0, 0, 8, 16, 24, 32])),
-                                NTR_LBVH_MORTON_THREADS=int(rng.choice([0, 0, 256, 512, 1024])), NTR_LBVH_MORTON_KEYS=int(rng.choice([0, 0, 1, 2, 16])),
-                                NTR_LBVH_MARK_THREADS=int(rng.choice([0, 256, 1024])))
+                                NTR_LBVH_SORT_ITEMS=int(rng.choice([0, 0, 8, 16, 24, 32])))
                 if os.environ.get("NTR_FUZZ_VERBOSE"):
                     print("lbvh n=%d leaf=%d eps=%g %s" % (tri.shape[0], leaf, eps, {k: v for k, v in os.environ.items() if k.startswith("NTR_LBVH")}),
                           file=sys.stderr, flush=True)
@@ -194,9 +192,9 @@ def main(argv=None):
                 nt.set_tunables(NTR_TRACE_PREDICT_MIN_RAYS=1, NTR_TRACE_PREDICT_MIN_NODES=1)
             else:
                 nt.set_tunables(NTR_TRACE_PREDICT_MIN_RAYS=None, NTR_TRACE_PREDICT_MIN_NODES=None)
-            # loop variants only change how the lanes of a wave interleave: while-while or unified-step loop in the per-ray kernel (by the
-            # tree's leaf sizes, or forced either way) and in kepler_dynamic_fetch, any dynamic-fetch threshold, any mini-pool depth
-            loop = dict(NTR_TRACE_PERRAY_UNIFIED=int(rng.choice([-1, 0, 1])), NTR_TRACE_UNIFIED=int(rng.choice([1, 1, 0])),
+            # loop variants only change how the lanes of a wave interleave: while-while or unified-step loop in kepler_dynamic_fetch, any
+            # dynamic-fetch threshold, any mini-pool depth
+            loop = dict(NTR_TRACE_UNIFIED=int(rng.choice([1, 1, 0])),
                         NTR_TRACE_FETCH_THRESHOLD=int(rng.choice([-1, -1, 1, 16, 33, 64])), NTR_TRACE_FLAT_FETCH=int(rng.choice([1, 1, 0])),
                         # wave-private mini-pool of the closest-hit per-ray launches: by the device's coherence estimate, off, or forced
                         NTR_TRACE_MINIPOOL=int(rng.choice([-1, -1, 0, 1, 2, 3, 4, 5, 8, 16])), NTR_TRACE_MINIPOOL_THRESHOLD=int(rng.choice([48, 48, 1, 33, 64])),
@@ -247,7 +245,7 @@ def main(argv=None):
         del keep
         os.environ.pop("NTR_TRACE_PREDICT_MIN_RAYS", None)
     # leave no tunable of the last round behind: run in-process (tests/test_fuzz_gpu.py) the draws would otherwise steer the tests that
-    # follow -- e.g. NTR_TRACE_PERRAY_UNIFIED=0 takes the per-ray launch off its pools, and the hand-off tests then hand nothing off
+    # follow -- e.g. NTR_TRACE_MINIPOOL=0 takes the per-ray launch off its pools, and the hand-off tests then hand nothing off
     nt.set_tunables(**{k: env_at_start.get(k) for k in set(list(os.environ) + list(env_at_start)) if k.startswith("NTR_TRACE_") or k.startswith("NTR_LBVH_")})
     tot["failures"] = [f for f in failures if f["kind"] != "trace"][:20] + [f for f in failures if f["kind"] == "trace"][:6]
     tot["seed"] = args.seed

@@ -256,14 +256,11 @@ def test_octant_slabs_change_no_record(soup, monkeypatch, octant):
             assert_parity(got, ref, "octant=%d %s anyHit=%d" % (octant, kernel, any_hit))
 
 
-@pytest.mark.parametrize("waves", [1, 2, 4])
-def test_workgroup_size_changes_no_record(soup, monkeypatch, waves):
-    """The per-ray kernel runs in workgroups of 1, 2 or 4 waves (NTR_TRACE_CLOSEST_WAVES / NTR_TRACE_ANYHIT_WAVES); the dispatch
-    order (prediction forced on) and the scheduling hint keep their 256-ray units.  Ragged ray counts, both ray kinds."""
+def test_workgroup_size_changes_no_record(soup, monkeypatch):
+    """The per-ray kernel runs in one-wave workgroups; the dispatch order (prediction forced on) and the scheduling hint keep their
+    256-ray units.  Ragged ray counts, both ray kinds."""
     from gpu_util import assert_parity, gpu_trace
     dbvh, cam = soup
-    monkeypatch.setenv("NTR_TRACE_CLOSEST_WAVES", str(waves))
-    monkeypatch.setenv("NTR_TRACE_ANYHIT_WAVES", str(waves))
     monkeypatch.setenv("NTR_TRACE_PREDICT_MIN_RAYS", "1")
     monkeypatch.setenv("NTR_TRACE_PREDICT_MIN_NODES", "1")
     nt.set_tunables()
@@ -273,7 +270,7 @@ def test_workgroup_size_changes_no_record(soup, monkeypatch, waves):
         for any_hit in (False, True):
             ref, _ = oracle.trace(dbvh.host.nodes, dbvh.host.woop, dbvh.host.tri_index, rays, any_hit=any_hit, threads=8)
             got, _ = gpu_trace("fermi_speculative_while_while", dbvh, rays, any_hit)
-            assert_parity(got, ref, "waves=%d n=%d anyHit=%d" % (waves, n, any_hit))
+            assert_parity(got, ref, "n=%d anyHit=%d" % (n, any_hit))
 
 
 def test_validate_flags_an_inverted_box_as_unordered():
@@ -330,10 +327,11 @@ def test_trace_launch_can_be_captured_in_a_hip_graph_and_replayed(soup, monkeypa
 
 @pytest.mark.parametrize("tree", ["sah leaves of 1", "sah leaves of up to 6", "device lbvh"])
 def test_unified_step_loop_changes_no_record(soup, monkeypatch, tree):
-    """The unified-step loop (every live lane advances by one inner node OR one triangle per iteration; kepler_dynamic_fetch always, the
-    per-ray kernel on trees flagged NTR_BVH_WIDE_LEAVES) interleaves the lanes differently from the while-while loop and nothing
-    else: forced on and off for both kernels, on one-triangle leaves, multi-triangle leaves and a device-built LBVH; coherent, edge-case
-    and random rays; ragged counts; closest hit and any hit; dynamic-fetch thresholds from 'never refill' to 'refill at once'."""
+    """The unified-step loop (every live lane advances by one inner node OR one triangle per iteration; the per-ray kernel always,
+    kepler_dynamic_fetch unless NTR_TRACE_UNIFIED=0) interleaves the lanes differently from the while-while loop and nothing else:
+    flat and two-descriptor fetch for both kernels, forced on and off for kepler_dynamic_fetch, on one-triangle leaves, multi-triangle
+    leaves and a device-built LBVH; coherent, edge-case and random rays; ragged counts; closest hit and any hit; dynamic-fetch
+    thresholds from 'never refill' to 'refill at once'."""
     import torch
     from gpu_util import DeviceBvh, assert_parity, gpu_trace, up
     tri, pos, cam = scenes.random_soup(6000, seed=23)
@@ -359,8 +357,7 @@ def test_unified_step_loop_changes_no_record(soup, monkeypatch, tree):
     allrays = np.concatenate([scenes.primary_rays(cam, 200, 160)[0], edge_rays(), scenes.random_rays(20000, seed=5)])
     for any_hit in (False, True):
         ref, _ = oracle.trace(dbvh.host.nodes, dbvh.host.woop, dbvh.host.tri_index, allrays, any_hit=any_hit, threads=8)
-        for env in ({"NTR_TRACE_PERRAY_UNIFIED": "1", "NTR_TRACE_FLAT_FETCH": "1"}, {"NTR_TRACE_PERRAY_UNIFIED": "1", "NTR_TRACE_FLAT_FETCH": "0"},
-                    {"NTR_TRACE_PERRAY_UNIFIED": "0"}):
+        for env in ({"NTR_TRACE_FLAT_FETCH": "1"}, {"NTR_TRACE_FLAT_FETCH": "0"}):
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
             nt.set_tunables()

@@ -2,13 +2,16 @@
 gets, as a pure function of the tunables and the batch -- checked without a device.  The launch half (tests -m gpu) binds run-time
 state to exactly this plan.  Reference behaviour it must keep: one selector per kernel file name (CudaBVHTracer.cpp:252-258), grid
 sized from the device for persistent kernels (:152-160)."""
+import os
+
+import numpy as np
 import pytest
 
 import ntrace_amd as nt
 
 MB = 1 << 20
 # csrc/trace_kernels.h
-PERRAY, PERSISTENT, STATS, W2, W1, PERSISTENT_UNIFIED, UNIFIED_W1, UNIFIED_MINI = range(8)
+PERRAY, PERSISTENT, STATS, PERSISTENT_UNIFIED, UNIFIED_W1, UNIFIED_MINI = 0, 1, 2, 5, 6, 7
 
 
 @pytest.fixture(autouse=True)
@@ -120,13 +123,36 @@ def test_tunables_steer_the_plan(monkeypatch):
     q = nt.trace_plan("kepler_dynamic_fetch", 2 * MB, False, 17 * MB, 17 * MB)
     assert not q.hintable and not q.useAutoHint and q.predictable
     nt.set_tunables(NTR_TRACE_PERSISTENT_HINTS=None)
-    nt.set_tunables(NTR_TRACE_MINIPOOL=4, NTR_TRACE_PERRAY_UNIFIED=-1)
+    nt.set_tunables(NTR_TRACE_MINIPOOL=4)
     p = nt.trace_plan("fermi_speculative_while_while", 2 * MB, False, 17 * MB, 17 * MB)
     assert p.minipool and p.poolKConst == 4 and not p.poolKFromDevice
-    a = nt.trace_plan("fermi_speculative_while_while", MB, True, 17 * MB, 17 * MB)                 # round 3's rule: any hit on a
-    assert a.launchVariant == W1                                                                    # one-triangle-leaf tree: while-while
-    a = nt.trace_plan("fermi_speculative_while_while", MB, True, 17 * MB, 17 * MB, bvh_flags=16)   # NTR_BVH_WIDE_LEAVES
-    assert a.launchVariant == UNIFIED_W1
+    for flags in (0, nt.BVH_WIDE_LEAVES):       # an any-hit per-ray launch: the unified-step loop on any tree, never the mini-pool
+        a = nt.trace_plan("fermi_speculative_while_while", MB, True, 17 * MB, 17 * MB, bvh_flags=flags)
+        assert a.launchVariant == UNIFIED_W1 and a.launchBlocks == 4 * 4096 and not a.minipool
+
+
+def test_plan_matches_the_golden():
+    """Every field of the plan over tests/golden/plan/trace_plan.npz's grid of batches (tests/golden/make_trace_plan_golden.py), under the
+    defaults and under each tunable that steers the plan: the launch policy changes only with the fixture."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan", "trace_plan.npz"))
+    assert list(g["fields"]) == [n for n, _ in nt._capi.TracePlan._fields_]
+    assert list(g["inputs_names"]) == ["config", "kernel", "any_hit", "num_rays", "nodes_bytes", "woop_bytes", "woop_ofs64", "bvh_flags",
+                                       "num_cus", "flags"]
+    nodes_addr = int(g["nodes_gib"]) << 30
+    for c, config in enumerate(g["configs"]):
+        name, _, value = str(config).partition("=")
+        nt.set_tunables(**({name: value} if name else {}))
+        rows = np.flatnonzero(g["inputs"][:, 0] == c)
+        assert rows.size > 0
+        for r in rows:
+            _, k, any_hit, num_rays, nb, wb, wofs, bvh_flags, cus, flags = (int(v) for v in g["inputs"][r])
+            p = nt.trace_plan(str(g["kernels"][k]), num_rays, any_hit, nb, wb, nodes_addr=nodes_addr, woop_addr=nodes_addr + wofs * 64,
+                              bvh_flags=bvh_flags, num_cus=cus, flags=flags)
+            got = [getattr(p, n) for n, _ in nt._capi.TracePlan._fields_]
+            assert got == list(g["plans"][r]), (str(config), [int(v) for v in g["inputs"][r]],
+                                                {n: (a, int(b)) for n, a, b in zip(g["fields"], got, g["plans"][r]) if a != b})
+        if name:
+            nt.set_tunables(**{name: None})
 
 
 def test_hint_life_cycle():
