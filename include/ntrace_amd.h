@@ -580,6 +580,65 @@ NTR_API int ntr_host_bvh_wrap(const void* nodes, int64_t nodesBytes, const void*
 NTR_API int ntr_host_bvh_trace(const NtrHostBvh* bvh, int32_t numRays, int32_t anyHit, const NtrRay* rays,
                                NtrRayResult* results, int32_t* visibility, int32_t numVisibility, NtrTraceStats* stats);
 
+/* ---- kd-tree (Renderer.dataStructure KDTree: Renderer.cpp:75-76, 309-382, 415-416) ---------------------- */
+
+/* Host kd-tree build + flatten: `KDTree kdtree(scene, platform, params); CudaKDTree(kdtree)` of Renderer::getCudaKDTree
+ * (Renderer.cpp:309-382; KDTree.cpp:36-63; CudaKDTree.cpp:18-183), no device work.  builder: NTR_KDTREE_SPATIAL_MEDIAN
+ * (NaiveKDTreeBuilder: axis level % 3, split at the cell's middle, leaves at <= maxLeafSize references or depth 18) or
+ * NTR_KDTREE_SAH (FastKDTreeBuilder: event sweep with clipping of straddling triangles, Platform("GPU") costs, depth
+ * <= (int)(1.2 log2 N + 2)); maxLeafSize applies to the spatial median only (the Renderer passes 1, Renderer.cpp:88-89).
+ * Both builders are single-threaded and deterministic.  numTris == 0 -> NTR_ERR_INVALID.
+ *
+ * Buffers (ntrace_amd/host/CudaKDTree.hpp):
+ *   nodes    16 B per inner node (left, right, floatBits(split), axis << 28), numbered by createNodeTriIdx's explicit stack;
+ *            a child is a node index (>= 0), ~offset of a non-empty leaf's list in triIndex, or 0x80000000 (empty leaf)
+ *   triIndex each non-empty leaf's triangle ids, then 0x80000000
+ *   triWoop  3 x float4 per scene triangle, by triangle id, padded to 4096 B (the rows of ntr_sah_build's tree)
+ *   sceneMin / sceneMax  the box of every triangle some leaf references; delta = length(sceneMax + sceneMin) * 1e-6
+ * DEVIATION: when the root is a leaf (one triangle, or no SAH split at the root) -- where the reference's kernel reads a
+ * child of the root -- the tree is one inner node on axis 0 at sceneMax.x with the leaf as child 0 and an empty leaf as
+ * child 1. */
+#define NTR_KDTREE_SPATIAL_MEDIAN 0
+#define NTR_KDTREE_SAH 1
+typedef struct NtrHostKdtree NtrHostKdtree;
+typedef struct NtrHostKdtreeInfo {
+    const void*    nodes;     int64_t nodesBytes;
+    const void*    triWoop;   int64_t triWoopBytes;
+    const int32_t* triIndex;  int64_t triIndexBytes;
+    float   sceneMin[3], sceneMax[3];
+    float   delta;
+    int32_t numInnerNodes, numLeafNodes, numEmptyLeaves, numTriRefs;
+    int32_t maxDepth;          /* inner nodes on the longest root-to-leaf path: the kernel's stack never holds more entries */
+    float   percentDuplicates; /* duplicated references / triangles * 100 (KDTree.cpp:68) */
+    float   buildSeconds;
+} NtrHostKdtreeInfo;
+NTR_API int  ntr_kdtree_build(int32_t builder, int32_t numTris, const int32_t* triVtxIndex /* 3 per tri */,
+                              int32_t numVerts, const float* vtxPos /* 3 per vertex */, int32_t maxLeafSize, NtrHostKdtree** out);
+NTR_API int  ntr_host_kdtree_info(const NtrHostKdtree* kdtree, NtrHostKdtreeInfo* info);
+NTR_API void ntr_host_kdtree_free(NtrHostKdtree* kdtree);
+
+/* A host kd-tree over copies of buffers made elsewhere (e.g. CudaKDTree(InputStream&), CudaKDTree.cpp:35-40).  The tree is
+ * walked from node 0 first: every child index in range, every axis 0..2, every leaf list inside triIndex and terminated by
+ * 0x80000000 with its ids inside triWoop, no node reached twice (no cycles, no shared subtrees), and a depth (inner nodes on a
+ * root-to-leaf path) of at most 64, the kernel's stack.  Otherwise NTR_ERR_INVALID (sizes, nulls) or NTR_ERR_LAYOUT. */
+NTR_API int  ntr_host_kdtree_wrap(const void* nodes, int64_t nodesBytes, const void* triWoop, int64_t triWoopBytes,
+                                  const int32_t* triIndex, int64_t triIndexBytes, const float sceneMin[3], const float sceneMax[3],
+                                  NtrHostKdtree** out);
+
+/* Replaces the `trace_kdtree` launch of CudaKDTreeTracer::traceBatch (CudaKDTreeTracer.cpp:70-128; kernel
+ * fermi_kdtree_while_while_leafRef.cu with SHORTSTACK 0, restated in csrc/kdtree_kernels.hip).  delta is computed here as
+ * the reference does: length(sceneMax + sceneMin) * 1e-6f in binary32.
+ *   numRays == 0 -> NTR_OK, *seconds = 0;  a null buffer -> NTR_ERR_INVALID;  seconds != NULL -> timed and blocking (the
+ *   kernel's GPU time), NTR_ERR_OVERFLOW if a ray's stack overflowed, NTR_ERR_LAYOUT if a ray met an index outside its
+ *   buffer;  seconds == NULL -> asynchronous, the status bits go to the per-device word of ntr_trace_status (bit 0 overflow,
+ *   bit 1 index out of range).
+ * Records: hit = (triId, t, bits(u), bits(v)); miss = (-1, ray.tmax, 0, 0) -- DEVIATION: the reference stores its working
+ * tmax on a miss, a value nothing reads.  anyHit is ignored, as by the reference's kernel. */
+NTR_API int ntr_trace_kdtree(int32_t numRays, int32_t anyHit, const float sceneMin[3], const float sceneMax[3],
+                             const NtrRay* d_rays, NtrRayResult* d_results, const void* d_nodes, int64_t nodesBytes,
+                             const void* d_triWoop, int64_t triWoopBytes, const int32_t* d_triIndex, int64_t triIndexBytes,
+                             void* stream, float* seconds);
+
 /* ---- scene ingest (host only) ----------------------------------------------- */
 
 /* CameraControls::decodeSignature / encodeSignature (src/framework/3d/CameraControls.cpp:342-399, 471-545):

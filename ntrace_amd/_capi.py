@@ -67,6 +67,14 @@ class _HostBvhInfo(C.Structure):
                 ("maxDepth", C.c_int32), ("buildSeconds", C.c_float)]
 
 
+class _HostKdtreeInfo(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
+                ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
+                ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3), ("delta", C.c_float),
+                ("numInnerNodes", C.c_int32), ("numLeafNodes", C.c_int32), ("numEmptyLeaves", C.c_int32), ("numTriRefs", C.c_int32),
+                ("maxDepth", C.c_int32), ("percentDuplicates", C.c_float), ("buildSeconds", C.c_float)]
+
+
 def lib_path():
     # NTR_LIB_OVERRIDE: another build of the library (scripts/ only: a patched build for an A/B run, scripts/studies/rejected_patches/)
     return os.environ.get("NTR_LIB_OVERRIDE") or os.path.join(_HERE, "libntrace_amd.so")
@@ -156,6 +164,12 @@ SYMBOLS = [
     ("ntr_host_bvh_free", None, [_vp]),
     ("ntr_host_bvh_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(_vp)]),
     ("ntr_host_bvh_trace", C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.POINTER(TraceStats)]),
+    ("ntr_kdtree_build", C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, C.POINTER(_vp)]),
+    ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
+    ("ntr_host_kdtree_free", None, [_vp]),
+    ("ntr_host_kdtree_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_vp)]),
+    ("ntr_trace_kdtree", C.c_int, [_i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                   _vp, C.POINTER(C.c_float)]),
 ]
 
 
@@ -681,3 +695,82 @@ def sah_build(tri_vtx_index, vtx_pos, min_leaf=1, max_leaf=1, keep_handle=False)
     else:
         lib().ntr_host_bvh_free(h)
     return out
+
+
+# ---- kd-tree ------------------------------------------------------------------------------------------------------------
+KDTREE_SPATIAL_MEDIAN, KDTREE_SAH = 0, 1
+_KDTREE_BUILDERS = {"SpatialMedianKDTree": KDTREE_SPATIAL_MEDIAN, "SAHKDTree": KDTREE_SAH,
+                    KDTREE_SPATIAL_MEDIAN: KDTREE_SPATIAL_MEDIAN, KDTREE_SAH: KDTREE_SAH}
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(np.float32(x)) for x in v])
+
+
+class HostKdtree:
+    """Host kd-tree buffers (numpy copies of nodes / triWoop / triIndex, include/ntrace_amd.h) with the scene box, delta and
+    the build's statistics (info)."""
+
+    def __init__(self, nodes, woop, tri_index, scene_min, scene_max, delta, info=None):
+        self.nodes = nodes            # int32[numInner, 4]: (left, right, floatBits(split), axis << 28)
+        self.woop = woop              # uint8[triWoopBytes]
+        self.tri_index = tri_index    # int32[]
+        self.scene_min = scene_min    # float32[3]
+        self.scene_max = scene_max
+        self.delta = delta            # float32
+        self.info = info or {}
+
+    def trace(self, num_rays, any_hit, d_rays, d_results, d_nodes, d_woop, d_tri_index, stream=0, timed=True):
+        """ntr_trace_kdtree over device copies of this tree's buffers."""
+        return trace_kdtree(num_rays, any_hit, self.scene_min, self.scene_max, d_rays, d_results, d_nodes, self.nodes.nbytes,
+                            d_woop, self.woop.nbytes, d_tri_index, self.tri_index.nbytes, stream, timed)
+
+
+def _kdtree_from_handle(h):
+    info = _HostKdtreeInfo()
+    _check(lib().ntr_host_kdtree_info(h, C.byref(info)))
+    nodes = np.ctypeslib.as_array(C.cast(info.nodes, C.POINTER(C.c_int32)), (info.nodesBytes // 4,)).copy().reshape(-1, 4)
+    woop = np.ctypeslib.as_array(C.cast(info.triWoop, C.POINTER(C.c_uint8)), (info.triWoopBytes,)).copy()
+    tidx = np.ctypeslib.as_array(C.cast(info.triIndex, C.POINTER(C.c_int32)), (info.triIndexBytes // 4,)).copy()
+    meta = dict(numInnerNodes=info.numInnerNodes, numLeafNodes=info.numLeafNodes, numEmptyLeaves=info.numEmptyLeaves,
+                numTriRefs=info.numTriRefs, maxDepth=info.maxDepth, percentDuplicates=float(info.percentDuplicates),
+                buildSeconds=float(info.buildSeconds))
+    return HostKdtree(nodes, woop, tidx, np.array(info.sceneMin[:], dtype=np.float32), np.array(info.sceneMax[:], dtype=np.float32),
+                      np.float32(info.delta), meta)
+
+
+def kdtree_build(tri_vtx_index, vtx_pos, builder="SAHKDTree", max_leaf=1):
+    """ntr_kdtree_build: builder "SpatialMedianKDTree" / "SAHKDTree" (or NTR_KDTREE_* values) -> HostKdtree."""
+    tri = np.ascontiguousarray(tri_vtx_index, dtype=np.int32).reshape(-1, 3)
+    pos = np.ascontiguousarray(vtx_pos, dtype=np.float32).reshape(-1, 3)
+    h = _vp()
+    _check(lib().ntr_kdtree_build(_KDTREE_BUILDERS.get(builder, -1) if not isinstance(builder, int) else builder, tri.shape[0],
+                                  tri.ctypes.data_as(_vp), pos.shape[0], pos.ctypes.data_as(_vp), int(max_leaf), C.byref(h)))
+    try:
+        return _kdtree_from_handle(h)
+    finally:
+        lib().ntr_host_kdtree_free(h)
+
+
+def host_kdtree_wrap(nodes, woop, tri_index, scene_min, scene_max):
+    """ntr_host_kdtree_wrap: validates buffers made elsewhere and returns them as a HostKdtree (NtrError on a bad tree)."""
+    nodes = np.ascontiguousarray(nodes).view(np.uint8).reshape(-1)
+    woop = np.ascontiguousarray(woop).view(np.uint8).reshape(-1)
+    tri_index = np.ascontiguousarray(tri_index, dtype=np.int32).reshape(-1)
+    h = _vp()
+    _check(lib().ntr_host_kdtree_wrap(nodes.ctypes.data_as(_vp), nodes.nbytes, woop.ctypes.data_as(_vp), woop.nbytes,
+                                      tri_index.ctypes.data_as(_vp), tri_index.nbytes, _f3(scene_min), _f3(scene_max), C.byref(h)))
+    try:
+        return _kdtree_from_handle(h)
+    finally:
+        lib().ntr_host_kdtree_free(h)
+
+
+def trace_kdtree(num_rays, any_hit, scene_min, scene_max, d_rays, d_results, d_nodes, nodes_bytes, d_woop, woop_bytes, d_tri_index,
+                 tri_index_bytes, stream=0, timed=True):
+    """ntr_trace_kdtree on raw device pointers (ints).  Returns GPU seconds if timed else None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_kdtree(int(num_rays), int(bool(any_hit)), _f3(scene_min), _f3(scene_max), _vp(d_rays), _vp(d_results),
+                                  _vp(d_nodes), int(nodes_bytes), _vp(d_woop), int(woop_bytes), _vp(d_tri_index), int(tri_index_bytes),
+                                  _vp(stream), C.byref(sec) if timed else None))
+    return float(sec.value) if timed else None

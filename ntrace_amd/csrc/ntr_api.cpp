@@ -947,13 +947,24 @@ int ntr_trace_plan_hint_step(int32_t valid, int32_t predicted, int32_t uses, int
     return NTR_OK;
 }
 
-int ntr_trace_status(void* stream, uint32_t* statusBits)
+}  // extern "C"
+
+namespace ntr {
+int device_status_word(unsigned int** status)
 {
-    if (statusBits) *statusBits = 0;
     DeviceState* ds = nullptr;
     const int rc = get_device_state(&ds);
     if (rc != NTR_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    *status = ds->status;
+    return NTR_OK;
+}
+
+int device_status_fetch(hipStream_t s, unsigned int* bits)
+{
+    *bits = 0;
+    DeviceState* ds = nullptr;
+    const int rc = get_device_state(&ds);
+    if (rc != NTR_OK) return rc;
     unsigned int st = 0;
     // fetched and cleared in ONE device-side step: a bit set by a launch on another stream is either in this answer or in the next
     std::lock_guard<std::mutex> lk(g_statusMu);   // the result word ds->status[8] is shared by the callers of one device
@@ -961,6 +972,19 @@ int ntr_trace_status(void* stream, uint32_t* statusBits)
     if (xe != hipSuccess) return hip_fail(xe, "status_exchange launch");
     NTR_HIP(hipMemcpyAsync(&st, ds->status + 8, sizeof(st), hipMemcpyDeviceToHost, s));
     NTR_HIP(hipStreamSynchronize(s));
+    *bits = st;
+    return NTR_OK;
+}
+}  // namespace ntr
+
+extern "C" {
+
+int ntr_trace_status(void* stream, uint32_t* statusBits)
+{
+    if (statusBits) *statusBits = 0;
+    unsigned int st = 0;
+    const int rc = device_status_fetch((hipStream_t)stream, &st);
+    if (rc != NTR_OK) return rc;
     if (statusBits) *statusBits = st;
     if (st & NTR_STATUS_STACK_OVERFLOW)
         return set_error(NTR_ERR_OVERFLOW, "trace_bvh: traversal stack overflow in a launch since the last status check");

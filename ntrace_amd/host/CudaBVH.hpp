@@ -35,6 +35,7 @@ public:
     void invalidateTraceFlags(void) { m_flagsValid = false; }
 
 protected:
+    friend class CudaKDTree;  // the kd-tree's Woop rows are CudaBVH's (CudaKDTree.hpp)
     void createCompact(const BVH& bvh, int nodeOffsetSizeDiv);  // CudaBVH.cpp:579-664
     static void woopify(const Vec3i* triVtxIndex, const Vec3f* vtxPos, S32 tri, Vec4f (&out)[3]);  // CudaBVH.cpp:668-687
 

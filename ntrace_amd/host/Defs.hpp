@@ -85,6 +85,7 @@ public:
     AABB(const Vec3f& mn, const Vec3f& mx) : m_mn(mn), m_mx(mx) {}
     void  grow(const Vec3f& pt) { m_mn = m_mn.min(pt); m_mx = m_mx.max(pt); }
     void  grow(const AABB& aabb) { grow(aabb.m_mn); grow(aabb.m_mx); }
+    void  intersect(const AABB& aabb) { m_mn = m_mn.max(aabb.m_mn); m_mx = m_mx.min(aabb.m_mx); }
     bool  valid(void) const { return m_mn.x <= m_mx.x && m_mn.y <= m_mx.y && m_mn.z <= m_mx.z; }
     F32   area(void) const
     {

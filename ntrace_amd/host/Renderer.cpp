@@ -11,20 +11,21 @@ namespace FW {
 
 // Renderer::Renderer (Renderer.cpp:44-94): m_raygen(1 << 20), Platform("GPU") with leaf preferences (1,1).
 Renderer::Renderer(const String& builder)
-    : m_builder(builder), m_raygen(1 << 20), m_enableRandom(false), m_scene(NULL), m_mesh(NULL), m_ownsScene(false), m_cameraFar(0.0f), m_newBatch(true),
+    : m_builder(builder), m_isKDTree(builder == "SpatialMedianKDTree" || builder == "SAHKDTree"), m_raygen(1 << 20), m_enableRandom(false), m_scene(NULL), m_mesh(NULL), m_ownsScene(false), m_cameraFar(0.0f), m_newBatch(true),
       m_batchRays(NULL), m_batchStart(0), m_accelStruct(NULL), m_cachePath("bvhcache"), m_cacheDataStructure(false),
       m_predictSecondary(true), m_leafDepthOf(NULL), m_secondaryHint(NULL), m_shardRank(0), m_shardWorld(1), m_shardLo(0), m_shardHi(0)
 {
-    m_cudaTracer = new CudaBVHTracer();
+    // Renderer.cpp:75-76: the kd-tree data structure has its own tracer
+    m_cudaTracer = m_isKDTree ? (CudaVirtualTracer*)new CudaKDTreeTracer() : (CudaVirtualTracer*)new CudaBVHTracer();
     m_cudaTracer->setScene(NULL);
     m_platform = Platform("GPU");
     m_platform.setLeafPreferences(1, 1);
-    m_buildParams.builder = (builder == "HLBVH") ? "SAHBVH" : builder;
+    m_buildParams.builder = (builder == "HLBVH" || m_isKDTree) ? "SAHBVH" : builder;
 }
 
 Renderer::~Renderer(void)
 {
-    static_cast<CudaBVHTracer*>(m_cudaTracer)->setSchedHint(NULL);
+    if (!m_isKDTree) static_cast<CudaBVHTracer*>(m_cudaTracer)->setSchedHint(NULL);
     if (m_secondaryHint) (void)ntr_sched_hint_destroy(m_secondaryHint);
     delete m_accelStruct;
     delete m_cudaTracer;
@@ -85,6 +86,7 @@ String Renderer::getCacheFileName(void)
 // Renderer::getCudaBVH (Renderer.cpp:147-305) without the OcclusionBVH branch.
 CudaAS* Renderer::getCudaBVH(void)
 {
+    if (m_isKDTree) return getCudaKDTree();
     BVHLayout layout = m_cudaTracer->getDesiredBVHLayout();
     if (!m_scene || (m_accelStruct && m_accelStruct->getLayout() == layout)) return m_accelStruct;
     delete m_accelStruct;
@@ -115,6 +117,22 @@ CudaAS* Renderer::getCudaBVH(void)
     return m_accelStruct;
 }
 
+CudaAS* Renderer::getCudaKDTree(void)
+{
+    if (!m_scene || m_accelStruct) return m_accelStruct;
+    KDTree::BuildParams params;
+    params.builder = m_builder;
+    KDTree kdtree(m_scene, m_platform, params);
+    m_accelStruct = new CudaKDTree(kdtree);
+    return m_accelStruct;
+}
+
+F32 Renderer::traceRange(RayBuffer& rays, S32 first, S32 count)
+{
+    if (m_isKDTree) return static_cast<CudaKDTreeTracer*>(m_cudaTracer)->traceRange(rays, first, count);
+    return static_cast<CudaBVHTracer*>(m_cudaTracer)->traceRange(rays, first, count);
+}
+
 // Renderer::beginFrame (Renderer.cpp:405-497)
 void Renderer::beginFrame(const CameraView& camera)
 {
@@ -128,7 +146,7 @@ void Renderer::beginFrame(const CameraView& camera)
     m_shardHi = hi;
     m_raygen.setInputRange(lo, hi);
     if (m_params.rayType != RayType_Primary)  // :482-488
-        static_cast<CudaBVHTracer*>(m_cudaTracer)->traceRange(m_primaryRays, lo, hi - lo);
+        traceRange(m_primaryRays, lo, hi - lo);
     m_cameraFar = camera.cameraFar;
     m_newBatch = true;
     m_batchRays = NULL;
@@ -161,7 +179,9 @@ bool Renderer::nextBatch(void)
     // Renderer.cpp:559-563
     if (m_params.sortSecondary && m_params.rayType != RayType_Primary) m_batchRays->mortonSort();
     // AO batches: a dispatch hint from the tree (not for sorted batches: their blocks no longer follow the input rays)
-    if (m_params.rayType == RayType_AO && m_predictSecondary && !m_params.sortSecondary && m_batchRays->getSize() > 0) predictSecondaryOrder();
+    // (BVH only: the leaf depths behind the hint are a BVH's; kd-tree records do not depend on it either way)
+    if (m_params.rayType == RayType_AO && m_predictSecondary && !m_params.sortSecondary && !m_isKDTree && m_batchRays->getSize() > 0)
+        predictSecondaryOrder();
     return true;
 }
 
@@ -210,7 +230,8 @@ F32 Renderer::traceBatch(void)  // Renderer.cpp:568-579
 {
     if (!m_batchRays) fail("Renderer::traceBatch: no batch");
     if (m_batchRays == &m_primaryRays)   // the primary batch: this rank's range of it
-        return static_cast<CudaBVHTracer*>(m_cudaTracer)->traceRange(m_primaryRays, m_shardLo, m_shardHi - m_shardLo);
+        return traceRange(m_primaryRays, m_shardLo, m_shardHi - m_shardLo);
+    if (m_isKDTree) return m_cudaTracer->traceBatch(*m_batchRays);
     CudaBVHTracer* tracer = static_cast<CudaBVHTracer*>(m_cudaTracer);
     tracer->setSchedHint((m_params.rayType == RayType_AO && m_predictSecondary && !m_params.sortSecondary) ? m_secondaryHint : NULL);
     const F32 sec = m_cudaTracer->traceBatch(*m_batchRays);

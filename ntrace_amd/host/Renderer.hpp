@@ -1,11 +1,13 @@
 // Renderer.hpp -- frame driver with the reference's batching semantics
 // (src/rt/cuda/Renderer.hpp:78-115; Renderer.cpp:44-94, 147-305, 405-497, 501-579, 676-710).
 // Kept: setMesh / setScene / setParams / getCudaBVH / beginFrame / nextBatch / traceBatch / updateResult (countHits + reconstruct:
-// SURVEY 8(f-2)) / getTotalNumRays for the primary, AO and diffuse ray types; setShard for the multi-GPU extension.
-// Out of scope: GL display, visualisation, VPL, kd-tree.
+// SURVEY 8(f-2)) / getTotalNumRays for the primary, AO and diffuse ray types; setShard for the multi-GPU extension; the kd-tree data
+// structure (builders "SpatialMedianKDTree" / "SAHKDTree": CudaKDTreeTracer over getCudaKDTree, Renderer.cpp:75-76, 309-382, 415-416).
+// Out of scope: GL display, visualisation, VPL, the PersistentKDTree builder, kd-tree cache files.
 #pragma once
 #include "MeshWavefrontIO.hpp"
 #include "CudaBVHTracer.hpp"
+#include "CudaKDTreeTracer.hpp"
 #include "HLBVHBuilder.hpp"
 #include "RayGen.hpp"
 
@@ -24,7 +26,8 @@ public:
         Params(void) : kernelName(""), rayType(RayType_Primary), aoRadius(1.0f), numSamples(32), sortSecondary(false) {}
     };
 
-    // builder: "SAHBVH" (host, leaf preferences (1,1)) or "HLBVH" (device LBVH) -- Renderer.builder in config.conf
+    // builder: "SAHBVH" (host, leaf preferences (1,1)), "HLBVH" (device LBVH), or a kd-tree: "SpatialMedianKDTree" / "SAHKDTree"
+    // (host builds, traced by CudaKDTreeTracer) -- Renderer.builder / Renderer.dataStructure in config.conf
     explicit Renderer(const String& builder = "SAHBVH");
     ~Renderer(void);
 
@@ -45,7 +48,9 @@ public:
     void   setParams(const Params& params);
     void   setEnableRandom(bool enable) { m_enableRandom = enable; }
     CudaVirtualTracer& getCudaTracer(void) { return *m_cudaTracer; }
-    CudaAS* getCudaBVH(void);
+    CudaAS* getCudaBVH(void);   // the kd-tree for a kd-tree builder
+    CudaAS* getCudaKDTree(void);  // Renderer.cpp:309-382 without the PersistentKDTree branch (no cache files)
+    bool    isKDTree(void) const { return m_isKDTree; }
     // Multi-GPU (no counterpart in the reference, which is single-device).  setShard: this Renderer traces the rank-th of
     // `world` screen-tile ranges of every frame -- contiguous 64-aligned ranges of the PixelTable index space (ntr_frame_shard) -- and
     // the AO / diffuse rays of its own primary hits; (0, 1) = the whole frame.  adoptCudaBVH: use a BVH built elsewhere (the root's,
@@ -77,10 +82,12 @@ public:
 
 private:
     void predictSecondaryOrder(void);
+    F32  traceRange(RayBuffer& rays, S32 first, S32 count);  // the BVH or kd-tree tracer's traceRange
     Renderer(const Renderer&);
     Renderer& operator=(const Renderer&);
 
     String             m_builder;
+    bool               m_isKDTree;
     Platform           m_platform;
     BVH::BuildParams   m_buildParams;
     HLBVHParams        m_hlbvhParams;
