@@ -639,6 +639,65 @@ NTR_API int ntr_trace_kdtree(int32_t numRays, int32_t anyHit, const float sceneM
                              const void* d_triWoop, int64_t triWoopBytes, const int32_t* d_triIndex, int64_t triIndexBytes,
                              void* stream, float* seconds);
 
+/* On-device kd-tree build: the reference's persistent kd-tree builder as configured (Renderer.cpp:348-353 "PersistentKDTree";
+ * CudaPersistentKDTreeBuilder.cpp, persistent_kdtree.cu with CudaTracerDefines.h SPLIT_TYPE 5, PLANE_COUNT 32, TRIANGLE_CLIPPING 0,
+ * BINNING_TYPE 2; config.conf block PersistentKDTree), rebuilt breadth first, one level per round, without its persistent task pool
+ * or device heap (csrc/kdtree_build_kernels.hip; the spec is tests/np_kdtree_binned.py).  The tree feeds ntr_trace_kdtree unchanged.
+ *   candidates  32 planes per task, 11 / 11 / 10 on x / y / z, pos = lo + (hi - lo) * ((1 + k) / 12.f), two roundings
+ *               (findPlaneAABB, rt_common.cu:1007-1030)
+ *   sides       no clipping: a triangle is left iff fl(pos - min) > -1e-8f and right iff fl(pos - max) < 1e-8f over its extent on
+ *               the axis -- exactly getPlanePosition (rt_common.cu:331-400) over its three vertices, as rounded subtraction is monotone
+ *   cost        s = areaL * nL + areaR * nR (areaAABBX/Y/Z, rt_common.cu:850-905); CANONICAL: the lowest finite s wins (+0 == -0),
+ *               then the lowest plane (lower axis, then lower position); NaN and infinite s never win; no finite s -> the task is a leaf
+ *   termination (persistent_kdtree.cu:454-510) ratio = (ct + ci * s / areaParent) / (ci * n); ratio > failRq increments the task's
+ *               failure counter (children inherit it) and a counter above failureCount makes the task a leaf; a NaN ratio (a cell of
+ *               zero area) does not; a child with <= triLimit references or below a parent of depth > maxDepth - 2 is a leaf, with
+ *               maxDepth = int(depthK1 * log2f(numTris) + depthK2) (CudaPersistentKDTreeBuilder.cpp:451), root depth 0.
+ *               triMaxLimit is only read by the reference's object-SAH path (not compiled with SPLIT_TYPE 5): accepted, unused.
+ *   cells       the root cell is the box of the triangles' vertices (min / max with -0 < +0); children cut it at the plane
+ *   order       inner nodes in level order (root 0, child 0 before child 1); leaf lists in the same order, ascending triangle ids
+ *               (the partition is stable), each followed by 0x80000000; empty leaves are the child 0x80000000.  The buffers are those
+ *               of NtrHostKdtreeInfo: Woop rows of woop_rows.h (the device builders' rows) by triangle id, padded to 4096 B.
+ * DEVIATION: a root with <= triLimit triangles, or one the failure test or the no-finite-cost rule ends, is the root-leaf tree of
+ *   ntr_kdtree_build (one inner node on axis 0 at sceneMax.x over the leaf and an empty leaf).
+ * DEVIATION: the reference's builder overwrites failureCount with int(failK1 * maxDepth + failK2) (CudaPersistentKDTreeBuilder.cpp:452);
+ *   here it is the parameter as given (config.conf: 0).
+ * NTR_ERR_INVALID: numTris < 1 or > 2^28, numVerts < 1, a null pointer, triLimit < 1, triMaxLimit < 0, failureCount < 0, a
+ *   non-finite depthK1 / depthK2 / ci / ct / failRq, a maxDepth above 64 (the trace kernel's stack), or (found on the device) a
+ *   vertex index outside [0, numVerts).  NTR_ERR_NOMEM: device memory, or a level whose references, leaf entries or nodes would not
+ *   fit the kernels' int32 indexing.  NTR_ERR_LAYOUT: an internal consistency check of the partition failed (a reference's rank
+ *   outside its child's range; not expected, reported instead of writing out of bounds).
+ * The call blocks (one 32 B read-back per level).  The scratch is a per-device grow-only pool returned by ntr_lbvh_release_workspace:
+ * one build per device at a time.  The tree's buffers belong to its handle, so trees coexist until ntr_device_kdtree_free.
+ * params == NULL: the config.conf defaults (ntr_kdtree_device_params_default). */
+typedef struct NtrKdtreeDeviceParams {
+    int32_t triLimit, triMaxLimit, failureCount, pad;
+    float   depthK1, depthK2, ci, ct, failRq;
+} NtrKdtreeDeviceParams;
+typedef struct NtrDeviceKdtree NtrDeviceKdtree;
+typedef struct NtrDeviceKdtreeInfo {   /* device pointers (owned by the tree) and exact byte sizes, as NtrHostKdtreeInfo */
+    const void*    nodes;     int64_t nodesBytes;
+    const void*    triWoop;   int64_t triWoopBytes;
+    const int32_t* triIndex;  int64_t triIndexBytes;
+    float   sceneMin[3], sceneMax[3], delta;
+    int32_t numInnerNodes, numLeafNodes, numEmptyLeaves, numTriRefs;
+    int32_t maxDepth;          /* inner nodes on the longest root-to-leaf path */
+    int32_t numLevels;         /* rounds of the level loop */
+    float   percentDuplicates; /* (numTriRefs - numTris) / numTris * 100 */
+    float   seconds;           /* host wall clock of the whole call */
+    float   prepMs, levelsMs, emitMs;   /* GPU event times: per-triangle data, the level loop, the final copies */
+} NtrDeviceKdtreeInfo;
+NTR_API int  ntr_kdtree_device_params_default(NtrKdtreeDeviceParams* params);
+NTR_API int  ntr_kdtree_device_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
+                                     const NtrKdtreeDeviceParams* params, NtrDeviceKdtree** out, void* stream);
+NTR_API int  ntr_device_kdtree_info(const NtrDeviceKdtree* tree, NtrDeviceKdtreeInfo* info);
+NTR_API void ntr_device_kdtree_free(NtrDeviceKdtree* tree);
+/* Blocking copies of the three buffers (nodesBytes / triWoopBytes / triIndexBytes of the info) to host memory; a null destination
+ * is skipped. */
+/* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int  ntr_kdtree_device_scratch_bytes(int64_t* bytes);
+NTR_API int  ntr_device_kdtree_download(const NtrDeviceKdtree* tree, void* nodes, void* triWoop, int32_t* triIndex);
+
 /* ---- scene ingest (host only) ----------------------------------------------- */
 
 /* CameraControls::decodeSignature / encodeSignature (src/framework/3d/CameraControls.cpp:342-399, 471-545):

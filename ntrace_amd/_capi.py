@@ -75,6 +75,20 @@ class _HostKdtreeInfo(C.Structure):
                 ("maxDepth", C.c_int32), ("percentDuplicates", C.c_float), ("buildSeconds", C.c_float)]
 
 
+class KdtreeDeviceParams(C.Structure):
+    _fields_ = [("triLimit", C.c_int32), ("triMaxLimit", C.c_int32), ("failureCount", C.c_int32), ("pad", C.c_int32),
+                ("depthK1", C.c_float), ("depthK2", C.c_float), ("ci", C.c_float), ("ct", C.c_float), ("failRq", C.c_float)]
+
+
+class _DeviceKdtreeInfo(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
+                ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
+                ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3), ("delta", C.c_float),
+                ("numInnerNodes", C.c_int32), ("numLeafNodes", C.c_int32), ("numEmptyLeaves", C.c_int32), ("numTriRefs", C.c_int32),
+                ("maxDepth", C.c_int32), ("numLevels", C.c_int32), ("percentDuplicates", C.c_float), ("seconds", C.c_float),
+                ("prepMs", C.c_float), ("levelsMs", C.c_float), ("emitMs", C.c_float)]
+
+
 def lib_path():
     # NTR_LIB_OVERRIDE: another build of the library (scripts/ only: a patched build for an A/B run, scripts/studies/rejected_patches/)
     return os.environ.get("NTR_LIB_OVERRIDE") or os.path.join(_HERE, "libntrace_amd.so")
@@ -165,6 +179,12 @@ SYMBOLS = [
     ("ntr_host_bvh_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(_vp)]),
     ("ntr_host_bvh_trace", C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.POINTER(TraceStats)]),
     ("ntr_kdtree_build", C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, C.POINTER(_vp)]),
+    ("ntr_kdtree_device_params_default", C.c_int, [C.POINTER(KdtreeDeviceParams)]),
+    ("ntr_kdtree_device_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(KdtreeDeviceParams), C.POINTER(_vp), _vp]),
+    ("ntr_device_kdtree_info", C.c_int, [_vp, C.POINTER(_DeviceKdtreeInfo)]),
+    ("ntr_device_kdtree_free", None, [_vp]),
+    ("ntr_device_kdtree_download", C.c_int, [_vp, _vp, _vp, _vp]),
+    ("ntr_kdtree_device_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
     ("ntr_host_kdtree_free", None, [_vp]),
     ("ntr_host_kdtree_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_vp)]),
@@ -774,3 +794,84 @@ def trace_kdtree(num_rays, any_hit, scene_min, scene_max, d_rays, d_results, d_n
                                   _vp(d_nodes), int(nodes_bytes), _vp(d_woop), int(woop_bytes), _vp(d_tri_index), int(tri_index_bytes),
                                   _vp(stream), C.byref(sec) if timed else None))
     return float(sec.value) if timed else None
+
+
+# ---- on-device kd-tree build ----------------------------------------------------------------------------------------------
+KDTREE_DEVICE_DEFAULTS = dict(triLimit=16, triMaxLimit=16, failureCount=0, depthK1=1.2, depthK2=2.0, ci=1.0, ct=1.0, failRq=0.9)
+
+
+def kdtree_device_params(**kw):
+    """NtrKdtreeDeviceParams: the config.conf defaults with the given fields replaced."""
+    p = KdtreeDeviceParams()
+    _check(lib().ntr_kdtree_device_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if k not in KDTREE_DEVICE_DEFAULTS:
+            raise TypeError("unknown kd-tree parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class DeviceKdtree:
+    """A kd-tree built on the device (ntr_kdtree_device_build).  It owns its device buffers until close(); the info fields are
+    attributes (nodes / triWoop / triIndex are device pointers, *Bytes their exact sizes)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        info = _DeviceKdtreeInfo()
+        _check(lib().ntr_device_kdtree_info(handle, C.byref(info)))
+        for name, _ in _DeviceKdtreeInfo._fields_:
+            v = getattr(info, name)
+            setattr(self, name, v[:] if name in ("sceneMin", "sceneMax") else v)
+        self.scene_min = np.array(info.sceneMin[:], dtype=np.float32)
+        self.scene_max = np.array(info.sceneMax[:], dtype=np.float32)
+        self.delta = np.float32(info.delta)
+
+    @property
+    def info(self):
+        return {name: getattr(self, name) for name, _ in _DeviceKdtreeInfo._fields_}
+
+    def trace(self, num_rays, any_hit, d_rays, d_results, stream=0, timed=True):
+        """ntr_trace_kdtree over this tree's buffers (the signature of HostKdtree.trace without the buffer pointers)."""
+        if self._h is None:
+            raise NtrError(-1, "DeviceKdtree: closed")
+        return trace_kdtree(num_rays, any_hit, self.scene_min, self.scene_max, d_rays, d_results, self.nodes, self.nodesBytes,
+                            self.triWoop, self.triWoopBytes, self.triIndex, self.triIndexBytes, stream, timed)
+
+    def download(self):
+        """(nodes int32[n, 4], woop uint8[], tri_index int32[]) copied to the host (ntr_device_kdtree_download)."""
+        if self._h is None:
+            raise NtrError(-1, "DeviceKdtree: closed")
+        nodes = np.zeros(self.nodesBytes // 4, np.int32)
+        woop = np.zeros(self.triWoopBytes, np.uint8)
+        idx = np.zeros(self.triIndexBytes // 4, np.int32)
+        _check(lib().ntr_device_kdtree_download(self._h, nodes.ctypes.data_as(_vp), woop.ctypes.data_as(_vp), idx.ctypes.data_as(_vp)))
+        return nodes.reshape(-1, 4), woop, idx
+
+    def close(self):
+        if self._h is not None:
+            lib().ntr_device_kdtree_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kdtree_device_scratch_bytes():
+    """ntr_kdtree_device_scratch_bytes: bytes the device kd-tree builder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_kdtree_device_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def kdtree_device_build(d_tri, num_tris, d_pos, num_verts, params=None, stream=0):
+    """ntr_kdtree_device_build on raw device pointers (ints).  params: None (config.conf defaults), a dict of
+    NtrKdtreeDeviceParams fields, or a KdtreeDeviceParams.  Returns a DeviceKdtree."""
+    if isinstance(params, dict):
+        params = kdtree_device_params(**params)
+    h = _vp()
+    _check(lib().ntr_kdtree_device_build(int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos),
+                                         C.byref(params) if params is not None else None, C.byref(h), _vp(stream)))
+    return DeviceKdtree(h)

@@ -1101,7 +1101,8 @@ int ntr_lbvh_release_workspace(void)
     const int rc = workspace_release();
     const int rc2 = ntr::raysort_scratch_release();
     const int rc3 = ntr::hlbvh_workspace_release();
-    return rc != NTR_OK ? rc : (rc2 != NTR_OK ? rc2 : rc3);
+    const int rc4 = ntr::kdtree_build_workspace_release();
+    return rc != NTR_OK ? rc : (rc2 != NTR_OK ? rc2 : (rc3 != NTR_OK ? rc3 : rc4));
 }
 
 

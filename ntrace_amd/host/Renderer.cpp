@@ -11,7 +11,7 @@ namespace FW {
 
 // Renderer::Renderer (Renderer.cpp:44-94): m_raygen(1 << 20), Platform("GPU") with leaf preferences (1,1).
 Renderer::Renderer(const String& builder)
-    : m_builder(builder), m_isKDTree(builder == "SpatialMedianKDTree" || builder == "SAHKDTree"), m_raygen(1 << 20), m_enableRandom(false), m_scene(NULL), m_mesh(NULL), m_ownsScene(false), m_cameraFar(0.0f), m_newBatch(true),
+    : m_builder(builder), m_isKDTree(builder == "SpatialMedianKDTree" || builder == "SAHKDTree" || builder == "PersistentKDTree"), m_raygen(1 << 20), m_enableRandom(false), m_scene(NULL), m_mesh(NULL), m_ownsScene(false), m_cameraFar(0.0f), m_newBatch(true),
       m_batchRays(NULL), m_batchStart(0), m_accelStruct(NULL), m_cachePath("bvhcache"), m_cacheDataStructure(false),
       m_predictSecondary(true), m_leafDepthOf(NULL), m_secondaryHint(NULL), m_shardRank(0), m_shardWorld(1), m_shardLo(0), m_shardHi(0)
 {
@@ -120,6 +120,10 @@ CudaAS* Renderer::getCudaBVH(void)
 CudaAS* Renderer::getCudaKDTree(void)
 {
     if (!m_scene || m_accelStruct) return m_accelStruct;
+    if (m_builder == "PersistentKDTree") {   // Renderer.cpp:348-353: the GPU builder, config.conf's PersistentKDTree parameters
+        m_accelStruct = new CudaPersistentKDTreeBuilder(m_scene);
+        return m_accelStruct;
+    }
     KDTree::BuildParams params;
     params.builder = m_builder;
     KDTree kdtree(m_scene, m_platform, params);

@@ -2,12 +2,14 @@
 // (src/rt/cuda/Renderer.hpp:78-115; Renderer.cpp:44-94, 147-305, 405-497, 501-579, 676-710).
 // Kept: setMesh / setScene / setParams / getCudaBVH / beginFrame / nextBatch / traceBatch / updateResult (countHits + reconstruct:
 // SURVEY 8(f-2)) / getTotalNumRays for the primary, AO and diffuse ray types; setShard for the multi-GPU extension; the kd-tree data
-// structure (builders "SpatialMedianKDTree" / "SAHKDTree": CudaKDTreeTracer over getCudaKDTree, Renderer.cpp:75-76, 309-382, 415-416).
-// Out of scope: GL display, visualisation, VPL, the PersistentKDTree builder, kd-tree cache files.
+// structure (builders "SpatialMedianKDTree" / "SAHKDTree" on the host and "PersistentKDTree" on the device: CudaKDTreeTracer over
+// getCudaKDTree, Renderer.cpp:75-76, 309-382, 415-416).
+// Out of scope: GL display, visualisation, VPL, the PersistentKDTree builder's task pool and allocators, kd-tree cache files.
 #pragma once
 #include "MeshWavefrontIO.hpp"
 #include "CudaBVHTracer.hpp"
 #include "CudaKDTreeTracer.hpp"
+#include "CudaPersistentKDTreeBuilder.hpp"
 #include "HLBVHBuilder.hpp"
 #include "RayGen.hpp"
 
@@ -27,7 +29,8 @@ public:
     };
 
     // builder: "SAHBVH" (host, leaf preferences (1,1)), "HLBVH" (device LBVH), or a kd-tree: "SpatialMedianKDTree" / "SAHKDTree"
-    // (host builds, traced by CudaKDTreeTracer) -- Renderer.builder / Renderer.dataStructure in config.conf
+    // (host builds) or "PersistentKDTree" (device build, CudaPersistentKDTreeBuilder), traced by CudaKDTreeTracer --
+    // Renderer.builder / Renderer.dataStructure in config.conf
     explicit Renderer(const String& builder = "SAHBVH");
     ~Renderer(void);
 
@@ -49,7 +52,7 @@ public:
     void   setEnableRandom(bool enable) { m_enableRandom = enable; }
     CudaVirtualTracer& getCudaTracer(void) { return *m_cudaTracer; }
     CudaAS* getCudaBVH(void);   // the kd-tree for a kd-tree builder
-    CudaAS* getCudaKDTree(void);  // Renderer.cpp:309-382 without the PersistentKDTree branch (no cache files)
+    CudaAS* getCudaKDTree(void);  // Renderer.cpp:309-382 with the PersistentKDTree branch (:348-353), no cache files
     bool    isKDTree(void) const { return m_isKDTree; }
     // Multi-GPU (no counterpart in the reference, which is single-device).  setShard: this Renderer traces the rank-th of
     // `world` screen-tile ranges of every frame -- contiguous 64-aligned ranges of the PixelTable index space (ntr_frame_shard) -- and

@@ -1,0 +1,73 @@
+"""The host mirror's device kd-tree path (tests/host/kdtree_device_host_test.cpp, compiled here against libntrace_amd.so):
+Renderer("PersistentKDTree") is a kd-tree builder; on a GPU, CudaPersistentKDTreeBuilder's tree equals the numpy spec, its stream
+round-trips byte for byte, and the Renderer's primary and AO frames equal ntr_trace_kdtree on the same tree."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import ntrace_amd as nt
+
+import np_kdtree
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "host", "kdtree_device_host_test.cpp")
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, "ntrace_amd", "csrc")])
+    out = str(tmp_path_factory.mktemp("kdtree_device_host") / "kdtree_device_host_test")
+    lib = os.path.join(ROOT, "ntrace_amd")
+    inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "ntrace_amd", "csrc"), "-I" + os.path.join(ROOT, "ntrace_amd", "host")]
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-ffp-contract=off"] + inc + [SRC, "-o", out, "-L" + lib, "-lntrace_amd",
+                           "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib"])
+    return out
+
+
+def test_renderer_persistent_kdtree_is_a_kdtree_cpu(exe):
+    out = subprocess.run([exe, "cpu"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "kdtree_device_host_test cpu: ok" in out.stdout
+
+
+@pytest.mark.gpu
+def test_renderer_persistent_kdtree_frames_gpu(exe, tmp_path):
+    import torch
+    from gpu_util import up
+
+    import np_kdtree_binned as kb
+
+    out = subprocess.run([exe, "gpu", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "kdtree_device_host_test gpu: ok" in out.stdout
+    print(out.stdout)
+    rd = lambda name, dt: np.fromfile(str(tmp_path / name), dtype=dt)  # noqa: E731
+    nodes, woop, idx = rd("nodes.bin", np.int32).reshape(-1, 4), rd("woop.bin", np.uint8), rd("index.bin", np.int32)
+    bbox = rd("bbox.bin", np.float32)
+    # the Renderer's tree is the device build of the spec
+    tri, verts = rd("tris.bin", np.int32).reshape(-1, 3), rd("verts.bin", np.float32).reshape(-1, 3)
+    ref = kb.build(tri, verts)
+    assert np.array_equal(nodes, ref["nodes"]) and np.array_equal(idx, ref["tri_index"]) and np.array_equal(woop, ref["woop"])
+    assert bbox.view(np.uint32).tolist() == np.concatenate([ref["scene_min"], ref["scene_max"]]).view(np.uint32).tolist()
+    # the stream: CudaKDTree's format (box, then the three buffers as S64 size + bytes)
+    stream = rd("stream.bin", np.uint8)
+    expect = [bbox.tobytes()]
+    for b in (nodes, woop, idx):
+        expect += [np.int64(b.nbytes).tobytes(), b.tobytes()]
+    assert stream.tobytes() == b"".join(expect)
+    d_nodes, d_woop, d_idx = up(nodes), up(woop), up(idx)
+    for kind, any_hit in (("primary", False), ("ao", True)):
+        rays = rd(kind + "_rays.bin", np.uint8).view(nt.RAY_DTYPE)
+        got = rd(kind + "_results.bin", np.uint8).view(nt.RESULT_DTYPE)
+        d_rays = up(rays)
+        d_res = torch.zeros(rays.shape[0] * 16, dtype=torch.uint8, device="cuda:0")
+        nt.trace_kdtree(rays.shape[0], any_hit, bbox[:3], bbox[3:], d_rays.data_ptr(), d_res.data_ptr(), d_nodes.data_ptr(), nodes.nbytes,
+                        d_woop.data_ptr(), woop.nbytes, d_idx.data_ptr(), idx.nbytes)
+        torch.cuda.synchronize()
+        direct = d_res.cpu().numpy().view(nt.RESULT_DTYPE)
+        assert np.array_equal(got.view(np.uint32), direct.view(np.uint32)), kind
+        if kind == "primary":
+            assert np.array_equal(got.view(np.uint32), np_kdtree.trace(nodes, woop, idx, bbox[:3], bbox[3:], rays).view(np.uint32))
+        assert (got["id"] >= 0).any()
