@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "ntr_internal.h"
+#include "device_scratch.h"
 
 namespace ntr {
 
@@ -95,21 +96,17 @@ extern "C" int ntr_selftest_gather_rate(int64_t tableBytes, int32_t waves, int32
     NTR_HIP(hipMalloc(&d_t, (size_t)tableBytes));
     if (hipMalloc((void**)&d_o, (size_t)waves * 64 * sizeof(unsigned int)) != hipSuccess) { (void)hipFree(d_t); return set_error(NTR_ERR_NOMEM, "ntr_selftest_gather_rate: out of device memory"); }
     hipLaunchKernelGGL(gather_fill_kernel, dim3(4096), dim3(256), 0, s, (unsigned int*)d_t, (size_t)tableBytes / 4);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
+    StreamEvents<2> ev(s);
+    hipError_t err = ev.create();
     float best = 1e30f;
     for (int rep = 0; rep < 3 && err == hipSuccess; rep++) {
-        err = hipEventRecord(e0, s);
+        err = ev.record(0);
         hipLaunchKernelGGL(gather_chase_kernel, dim3(waves), dim3(64), 0, s, (const uint4*)d_t, (unsigned int)(pow2 - 1), steps, lanesPerWave, d_o);
-        if (err == hipSuccess) err = hipEventRecord(e1, s);
-        if (err == hipSuccess) err = hipEventSynchronize(e1);
+        if (err == hipSuccess) err = ev.record(1);
         float ms = 0.0f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+        if (err == hipSuccess) err = ev.elapsed(0, 1, &ms);
         if (err == hipSuccess && ms < best) best = ms;
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(d_t);
     (void)hipFree(d_o);
     if (err != hipSuccess) return hip_fail(err, "ntr_selftest_gather_rate");

@@ -4,12 +4,12 @@
 // which lists the canonical choices (bin conversion, split-missed fallback and its box, fewer than two clusters).
 //   calcMorton + radixSortCuda   -> lbvh_sort_codes (lbvh_kernels.hip): the LBVH's own codes and stable sort, same launches
 //   createClusters (radixSort.cu:48-115), clusterAABB (emitTreeKernel.cu:1090-)
-//                                -> hl_head_count / hl_scan_blocks / hl_head_emit: boundary flags on code >> 3*bits, a scan, cluster
+//                                -> hl_head_count / scan_block_sums / hl_head_emit: boundary flags on code >> 3*bits, a scan, cluster
 //                                   starts; hl_cluster_box: segmented min / max, 16 positions per thread, wave-level combine of the
-//                                   partial segments and integer atomics on the f2i encoding only where a cluster crosses a chunk
+//                                   partial segments and integer atomics on the ord_enc_int encoding only where a cluster crosses a chunk
 //   buildTopLevel (HLBVHBuilder.cpp:156-317; fillBins / findSplit / distribute, emitTreeKernel.cu:713-1027)
-//                                -> per level: hl_fill_bins (integer atomics on the f2i encoding, LDS bins when a workgroup's clusters
-//                                   share one task), hl_find_split (one thread per task), hl_left_count + hl_scan_blocks +
+//                                -> per level: hl_fill_bins (integer atomics on the ord_enc encoding, LDS bins when a workgroup's clusters
+//                                   share one task), hl_find_split (one thread per task), hl_left_count + scan_block_sums +
 //                                   hl_partition (a stable partition by scan keeps every task's clusters contiguous and in Morton
 //                                   order, so the object split is "the first cntL of the range"; single clusters become leaves or
 //                                   bottom-level roots here), hl_level_end.  Levels are launched in chunks of HL_CHUNK with device-side
@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "ntr_internal.h"
+#include "device_prims.h"
 #include "device_scratch.h"
 #include "woop_rows.h"
 
@@ -53,7 +54,7 @@ struct HlState {
 
 struct HlCls {           // clusters, in the current partitioned order
     int* start; int* end;
-    int* box;            // 6 per cluster: f2i(lo.xyz), f2i(hi.xyz)
+    int* box;            // 6 per cluster: ord_enc_int(lo.xyz), ord_enc_int(hi.xyz)
     int* task;           // task of the current level, -1: done
 };
 struct HlTasks {
@@ -70,13 +71,8 @@ struct HlOut {
     int leafSize; float eps;
 };
 
-__device__ __forceinline__ int f2i(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7FFFFFFF; }
-__device__ __forceinline__ float i2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
-// bin words: zero is the identity of both (atomicMax on unsigned), so one memset clears them
-__device__ __forceinline__ unsigned int enc_lo(float f) { return ~((unsigned int)f2i(f) ^ 0x80000000u); }
-__device__ __forceinline__ unsigned int enc_hi(float f) { return (unsigned int)f2i(f) ^ 0x80000000u; }
-__device__ __forceinline__ int dec_lo(unsigned int u) { return (int)(~u ^ 0x80000000u); }
-__device__ __forceinline__ int dec_hi(unsigned int u) { return (int)(u ^ 0x80000000u); }
+// bin words: ~ord_enc(lo) and ord_enc(hi) (through the signed form), so that zero is the identity of both (atomicMax on unsigned) and
+// one memset clears them
 
 // clamp((int)floorf(q), 0, 7) with cvt.rzi.s32.f32 semantics: NaN -> 0, +inf -> 7, -inf -> 0 (a plain cast of NaN is undefined)
 __device__ __forceinline__ int bin_of(float q)
@@ -85,26 +81,6 @@ __device__ __forceinline__ int bin_of(float q)
     if (!(f >= 0.0f)) return 0;
     if (f >= (float)(HL_BINS - 1)) return HL_BINS - 1;
     return (int)f;
-}
-
-__device__ __forceinline__ float area3(float x, float y, float z) { return (x * y + y * z + z * x) * 2.0f; }  // emitTreeKernel.cu:119-121
-
-template <int THREADS>
-__device__ __forceinline__ int block_excl_scan(int v, int* s, int& total)
-{
-    const int t = threadIdx.x;
-    s[t] = v;
-    for (int off = 1; off < THREADS; off <<= 1) {
-        __syncthreads();
-        const int o = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += o;
-    }
-    __syncthreads();
-    total = s[THREADS - 1];
-    const int r = s[t] - v;
-    __syncthreads();
-    return r;
 }
 
 // ---- leaves and nodes ----------------------------------------------------------------------------
@@ -144,41 +120,23 @@ __device__ __forceinline__ bool is_head(const unsigned int* keys, int i, int bit
 // 1024 positions per workgroup (256 threads x 4): number of cluster heads
 __global__ __launch_bounds__(256) void hl_head_count(int n, int bits, const unsigned int* __restrict__ keys, int* __restrict__ blockCnt)
 {
-    __shared__ int s[256];
     const int base = blockIdx.x * 1024 + threadIdx.x * 4;
     int v = 0;
     for (int k = 0; k < 4; k++) v += (base + k < n && is_head(keys, base + k, bits)) ? 1 : 0;
     int total;
-    block_excl_scan<256>(v, s, total);
+    block_exclusive_scan<256>(v, &total);
     if (threadIdx.x == 0) blockCnt[blockIdx.x] = total;
-}
-
-// exclusive scan of nb block counts by one workgroup; the total goes to *total
-__global__ __launch_bounds__(1024) void hl_scan_blocks(int nb, const int* __restrict__ cnt, int* __restrict__ excl, unsigned int* total)
-{
-    __shared__ int s[1024];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const int v = i < nb ? cnt[i] : 0;
-        int t;
-        const int e = block_excl_scan<1024>(v, s, t);
-        if (i < nb) excl[i] = carry + e;
-        carry += t;
-    }
-    if (threadIdx.x == 0 && total) *total = (unsigned int)carry;
 }
 
 // cluster starts (clsStart[C] = n) and every position's cluster
 __global__ __launch_bounds__(256) void hl_head_emit(int n, int bits, const unsigned int* __restrict__ keys, const int* __restrict__ blockExcl,
                                                     int* __restrict__ clsStart, int* __restrict__ clsOf)
 {
-    __shared__ int s[256];
     const int base = blockIdx.x * 1024 + threadIdx.x * 4;
     int f[4], v = 0;
     for (int k = 0; k < 4; k++) { f[k] = (base + k < n && is_head(keys, base + k, bits)) ? 1 : 0; v += f[k]; }
     int total;
-    int r = blockExcl[blockIdx.x] + block_excl_scan<256>(v, s, total);
+    int r = blockExcl[blockIdx.x] + block_exclusive_scan<256>(v, &total);
     for (int k = 0; k < 4; k++) {
         const int i = base + k;
         if (i >= n) break;
@@ -196,14 +154,14 @@ __global__ void hl_cluster_init(int C, const int* __restrict__ clsStart, HlCls c
     c.start[i] = clsStart[i];
     c.end[i] = clsStart[i + 1];
     c.task[i] = 0;
-    for (int k = 0; k < 3; k++) { c.box[6 * i + k] = f2i(FLT_MAX); c.box[6 * i + 3 + k] = f2i(-FLT_MAX); }
+    for (int k = 0; k < 3; k++) { c.box[6 * i + k] = ord_enc_int(FLT_MAX); c.box[6 * i + 3 + k] = ord_enc_int(-FLT_MAX); }
 }
 
 __device__ __forceinline__ void tri_raw_box(const int* tri, const float* pos, int t, int lo[3], int hi[3])
 {
     const int v[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
     for (int k = 0; k < 3; k++) {
-        const int a = f2i(pos[3 * v[0] + k]), b = f2i(pos[3 * v[1] + k]), c = f2i(pos[3 * v[2] + k]);
+        const int a = ord_enc_int(pos[3 * v[0] + k]), b = ord_enc_int(pos[3 * v[1] + k]), c = ord_enc_int(pos[3 * v[2] + k]);
         lo[k] = min(a, min(b, c));
         hi[k] = max(a, max(b, c));
     }
@@ -214,7 +172,7 @@ __device__ __forceinline__ void box_atomic(int* box, const int lo[3], const int 
     for (int k = 0; k < 3; k++) { atomicMin(&box[k], lo[k]); atomicMax(&box[3 + k], hi[k]); }
 }
 
-// Raw vertex box per cluster (emitTreeKernel.cu:1090-, no epsilon) in the f2i order.  A thread folds 16 consecutive positions: segments
+// Raw vertex box per cluster (emitTreeKernel.cu:1090-, no epsilon) in the ord_enc_int order.  A thread folds 16 consecutive positions: segments
 // that start and end inside its chunk are stored, its first segment (when it is not also the last) goes out by atomics, and the last
 // segments of a wave's lanes are combined by cluster across the wave first, so a cluster of millions of triangles costs one set of
 // atomics per 1024 triangles, not per triangle.
@@ -274,7 +232,7 @@ __global__ __launch_bounds__(256) void hl_fill_bins(int C, HlCls c, HlTasks tk, 
     const bool uniform = __syncthreads_and(task < 0 || task == t0) != 0;
     if (task >= 0) {
         float lo[3], hi[3];
-        for (int k = 0; k < 3; k++) { lo[k] = i2f(c.box[6 * i + k]); hi[k] = i2f(c.box[6 * i + 3 + k]); }
+        for (int k = 0; k < 3; k++) { lo[k] = ord_dec_int(c.box[6 * i + k]); hi[k] = ord_dec_int(c.box[6 * i + 3 + k]); }
         const float* tb = tk.box + 6 * task;
         int b[3];
         for (int a = 0; a < 3; a++) {
@@ -286,7 +244,10 @@ __global__ __launch_bounds__(256) void hl_fill_bins(int C, HlCls c, HlTasks tk, 
         unsigned int* dst = uniform ? s_bins : bins + (size_t)task * HL_BIN_WORDS;
         for (int a = 0; a < 3; a++) {
             unsigned int* w = dst + (a * HL_BINS + b[a]) * 8;
-            for (int k = 0; k < 3; k++) { atomicMax(&w[k], enc_lo(lo[k])); atomicMax(&w[3 + k], enc_hi(hi[k])); }
+            for (int k = 0; k < 3; k++) {
+                atomicMax(&w[k], ~ord_from_int(ord_enc_int(lo[k])));
+                atomicMax(&w[3 + k], ord_from_int(ord_enc_int(hi[k])));
+            }
             atomicAdd(&w[6], 1u);
         }
     }
@@ -301,7 +262,7 @@ __global__ __launch_bounds__(256) void hl_fill_bins(int C, HlCls c, HlTasks tk, 
     }
 }
 
-// findSplit (emitTreeKernel.cu:779-938), one thread per task; the sweeps run on the f2i encoding (min / max there are fminf / fmaxf)
+// findSplit (emitTreeKernel.cu:779-938), one thread per task; the sweeps run on the ord_enc_int encoding (min / max there are fminf / fmaxf)
 __global__ __launch_bounds__(256) void hl_find_split(const unsigned int* __restrict__ taskCount, unsigned int* __restrict__ nextCount,
                                                      HlTasks tin, HlTasks tout, unsigned int* __restrict__ bins, HlDec* __restrict__ dec,
                                                      HlOut o, HlState* st)
@@ -318,28 +279,35 @@ __global__ __launch_bounds__(256) void hl_find_split(const unsigned int* __restr
                 const unsigned int* w = bw + (a * HL_BINS + b) * 8;
                 bc[b] = (int)w[6];
                 for (int k = 0; k < 3; k++) {
-                    blo[b][k] = bc[b] ? dec_lo(w[k]) : f2i(FLT_MAX);
-                    bhi[b][k] = bc[b] ? dec_hi(w[3 + k]) : f2i(-FLT_MAX);
+                    blo[b][k] = bc[b] ? ord_to_int(~w[k]) : ord_enc_int(FLT_MAX);
+                    bhi[b][k] = bc[b] ? ord_to_int(w[3 + k]) : ord_enc_int(-FLT_MAX);
                 }
             }
             int mn[HL_BINS - 1][3], mx[HL_BINS - 1][3], cr[HL_BINS - 1];
-            int mnr[3] = {f2i(FLT_MAX), f2i(FLT_MAX), f2i(FLT_MAX)}, mxr[3] = {f2i(-FLT_MAX), f2i(-FLT_MAX), f2i(-FLT_MAX)};
+            int mnr[3] = {ord_enc_int(FLT_MAX), ord_enc_int(FLT_MAX), ord_enc_int(FLT_MAX)};
+            int mxr[3] = {ord_enc_int(-FLT_MAX), ord_enc_int(-FLT_MAX), ord_enc_int(-FLT_MAX)};
             int cc = 0;
             for (int b = HL_BINS - 1; b > 0; b--) {
                 for (int k = 0; k < 3; k++) { mnr[k] = min(mnr[k], blo[b][k]); mxr[k] = max(mxr[k], bhi[b][k]); mn[b - 1][k] = mnr[k]; mx[b - 1][k] = mxr[k]; }
                 cc += bc[b];
                 cr[b - 1] = cc;
             }
-            int mnl[3] = {f2i(FLT_MAX), f2i(FLT_MAX), f2i(FLT_MAX)}, mxl[3] = {f2i(-FLT_MAX), f2i(-FLT_MAX), f2i(-FLT_MAX)};
+            int mnl[3] = {ord_enc_int(FLT_MAX), ord_enc_int(FLT_MAX), ord_enc_int(FLT_MAX)};
+            int mxl[3] = {ord_enc_int(-FLT_MAX), ord_enc_int(-FLT_MAX), ord_enc_int(-FLT_MAX)};
             cc = 0;
             for (int b = 0; b < HL_BINS - 1; b++) {
                 for (int k = 0; k < 3; k++) { mnl[k] = min(mnl[k], blo[b][k]); mxl[k] = max(mxl[k], bhi[b][k]); }
                 cc += bc[b];
-                const float s = (float)cc * area3(i2f(mxl[0]) - i2f(mnl[0]), i2f(mxl[1]) - i2f(mnl[1]), i2f(mxl[2]) - i2f(mnl[2])) +
-                                (float)cr[b] * area3(i2f(mx[b][0]) - i2f(mn[b][0]), i2f(mx[b][1]) - i2f(mn[b][1]), i2f(mx[b][2]) - i2f(mn[b][2]));
+                const float s = (float)cc * area3(ord_dec_int(mxl[0]) - ord_dec_int(mnl[0]), ord_dec_int(mxl[1]) - ord_dec_int(mnl[1]),
+                                                  ord_dec_int(mxl[2]) - ord_dec_int(mnl[2])) +
+                                (float)cr[b] * area3(ord_dec_int(mx[b][0]) - ord_dec_int(mn[b][0]), ord_dec_int(mx[b][1]) - ord_dec_int(mn[b][1]),
+                                                     ord_dec_int(mx[b][2]) - ord_dec_int(mn[b][2]));
                 if (s < best) {
                     best = s; split = b; axis = a; cntL = cc; cntR = cr[b];
-                    for (int k = 0; k < 3; k++) { bl[k] = i2f(mnl[k]); bl[3 + k] = i2f(mxl[k]); br[k] = i2f(mn[b][k]); br[3 + k] = i2f(mx[b][k]); }
+                    for (int k = 0; k < 3; k++) {
+                        bl[k] = ord_dec_int(mnl[k]); bl[3 + k] = ord_dec_int(mxl[k]);
+                        br[k] = ord_dec_int(mn[b][k]); br[3 + k] = ord_dec_int(mx[b][k]);
+                    }
                 }
             }
         }
@@ -350,7 +318,10 @@ __global__ __launch_bounds__(256) void hl_find_split(const unsigned int* __restr
             for (int b = 0; b < HL_BINS; b++) {
                 const unsigned int* w = bw + b * 8;
                 if (w[6]) {
-                    for (int k = 0; k < 3; k++) { bl[k] = br[k] = i2f(dec_lo(w[k])); bl[3 + k] = br[3 + k] = i2f(dec_hi(w[3 + k])); }
+                    for (int k = 0; k < 3; k++) {
+                        bl[k] = br[k] = ord_dec_int(ord_to_int(~w[k]));
+                        bl[3 + k] = br[3 + k] = ord_dec_int(ord_to_int(w[3 + k]));
+                    }
                     break;
                 }
             }
@@ -392,7 +363,6 @@ __device__ __forceinline__ bool goes_left(const HlDec& d, int i, int tBeg, uchar
 __global__ __launch_bounds__(256) void hl_left_count(int C, HlCls c, HlTasks tk, const HlDec* __restrict__ dec, const uchar4* __restrict__ cBin,
                                                      int* __restrict__ inBlock, int* __restrict__ blockCnt)
 {
-    __shared__ int s[256];
     const int base = blockIdx.x * 1024 + threadIdx.x * 4;
     int f[4], v = 0;
     for (int k = 0; k < 4; k++) {
@@ -405,7 +375,7 @@ __global__ __launch_bounds__(256) void hl_left_count(int C, HlCls c, HlTasks tk,
         v += f[k];
     }
     int total;
-    int r = block_excl_scan<256>(v, s, total);
+    int r = block_exclusive_scan<256>(v, &total);
     for (int k = 0; k < 4; k++) {
         if (base + k < C) inBlock[base + k] = r;
         r += f[k];
@@ -547,34 +517,13 @@ __global__ __launch_bounds__(256) void hl_refit(int batch, const unsigned int* _
 
 // Two grow-only pools per device: the first (codes, sort, clusters) is sized by numTris, the second (top-level tasks and bins) by the
 // number of clusters, which is only known after the first phase.
+namespace {
 DeviceScratchPool g_hlA, g_hlB;
-int hlbvh_workspace_release()
-{
-    const int a = g_hlA.release();
-    const int b = g_hlB.release();
-    return a != NTR_OK ? a : b;
-}
-
-struct HlCarver {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
+}  // namespace
 
 }  // namespace ntr
 
 using namespace ntr;
-
-namespace {
-struct HlEvents {
-    enum { N = 7 };
-    hipEvent_t ev[N] = {};
-    hipStream_t s;
-    explicit HlEvents(hipStream_t st) : s(st) { for (auto& e : ev) (void)hipEventCreate(&e); }
-    ~HlEvents() { for (auto& e : ev) (void)hipEventDestroy(e); }
-    void mark(int i) { (void)hipEventRecord(ev[i], s); }
-    float ms(int a, int b) { float v = 0; (void)hipEventElapsedTime(&v, ev[a], ev[b]); return v; }
-};
-}  // namespace
 
 extern "C" {
 
@@ -605,7 +554,7 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
 
     // ---- phase 1: codes, sort, clusters (pool A, sized by n) ----
     const int nb = (n + 1023) / 1024;
-    HlCarver ca;
+    ScratchCarver ca;
     const size_t oSort = ca.take(lbvh_sort_scratch_bytes(n));
     const size_t oState = ca.take(sizeof(HlState));
     const size_t oBlk = ca.take((size_t)nb * 4), oBlkEx = ca.take((size_t)nb * 4);
@@ -622,7 +571,8 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
     int* clsOf = (int*)(wa + oClsOf);
     int4* bq[2] = {(int4*)(wa + oBq0), (int4*)(wa + oBq1)};
 
-    HlEvents pe(s);
+    StreamEvents<6> pe(s);
+    (void)pe.create();
     pe.mark(0);
     {
         HlState init;
@@ -639,7 +589,8 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
     }
     pe.mark(1);
     hipLaunchKernelGGL(hl_head_count, dim3(nb), dim3(256), 0, s, n, bits, keys, (int*)(wa + oBlk));
-    hipLaunchKernelGGL(hl_scan_blocks, dim3(1), dim3(1024), 0, s, nb, (const int*)(wa + oBlk), (int*)(wa + oBlkEx), &st->numClusters);
+    hipLaunchKernelGGL((scan_block_sums<1024, int>), dim3(1), dim3(1024), 0, s, nb, (const int*)(wa + oBlk), (int*)(wa + oBlkEx),
+                       (int*)&st->numClusters);
     hipLaunchKernelGGL(hl_head_emit, dim3(nb), dim3(256), 0, s, n, bits, keys, (const int*)(wa + oBlkEx), clsStart, clsOf);
     NTR_HIP(hipGetLastError());
     unsigned int C = 0;
@@ -652,7 +603,7 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
     const int maxLevels = (int)C + HL_CHUNK + 2;
     const int maxBatches = maxLevels + 3 * bits + 2;
     const int cb = ((int)C + 1023) / 1024;
-    HlCarver cbv;
+    ScratchCarver cbv;
     size_t oC[2][4], oT[2][4];
     for (int p = 0; p < 2; p++) {
         oC[p][0] = cbv.take((size_t)C * 4); oC[p][1] = cbv.take((size_t)C * 4); oC[p][2] = cbv.take((size_t)C * 24); oC[p][3] = cbv.take((size_t)C * 4);
@@ -730,7 +681,7 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
                                    tks[p ^ 1], bins, dec, o, st);
                 hipLaunchKernelGGL(hl_left_count, dim3(cb), dim3(256), 0, s, (int)C, cls[p], tks[p], (const HlDec*)dec, (const uchar4*)cBin,
                                    (int*)(wb + oInBlock), (int*)(wb + oCBlk));
-                hipLaunchKernelGGL(hl_scan_blocks, dim3(1), dim3(1024), 0, s, cb, (const int*)(wb + oCBlk), (int*)(wb + oCBlkEx), (unsigned int*)nullptr);
+                hipLaunchKernelGGL((scan_block_sums<1024, int>), dim3(1), dim3(1024), 0, s, cb, (const int*)(wb + oCBlk), (int*)(wb + oCBlkEx), (int*)nullptr);
                 hipLaunchKernelGGL(hl_partition, dim3(gC), dim3(256), 0, s, (int)C, cls[p], cls[p ^ 1], tks[p], (const HlDec*)dec, (const uchar4*)cBin,
                                    (const int*)(wb + oInBlock), (const int*)(wb + oCBlkEx), bq[0], o, st);
                 hipLaunchKernelGGL(hl_level_end, dim3(1), dim3(1), 0, s, level + 1, (const unsigned int*)(tCount + level), lvlEnd, st, level);

@@ -11,9 +11,9 @@
 //                     references are reduced per task with ballots and added with one integer atomic per (task, plane, side)
 //                   kd_decide: one wave per task, one lane per plane: cost, split choice (lowest cost, then lowest plane), failure
 //                     test, children's leaf flags
-//                   kd_task_scan_local + kd_scan_blocks + kd_task_emit: node numbers, leaf list offsets, child tasks and child
+//                   kd_task_scan_local + scan_block_sums + kd_task_emit: node numbers, leaf list offsets, child tasks and child
 //                     reference offsets by an exclusive scan over the tasks; node records, parent links and leaf terminators
-//                   kd_ref_scan_local + kd_scan_blocks + kd_ref_scatter: each task's left / right ranks of its references by a scan
+//                   kd_ref_scan_local + scan_block_sums + kd_ref_scatter: each task's left / right ranks of its references by a scan
 //                     over the whole reference array (a task's rank is the difference to the scan at its first reference), then a
 //                     stable scatter into the next level's list or the leaf list
 //   end             the staged node and index arrays are copied into the tree's own buffers at their exact sizes
@@ -32,6 +32,7 @@
 #include <new>
 
 #include "ntr_internal.h"
+#include "device_prims.h"
 #include "device_scratch.h"
 #include "kdtree_kernels.h"
 #include "woop_rows.h"
@@ -60,7 +61,10 @@ struct KdDecision {     // 32 B
 struct KdPlace {        // a task's global offsets after the task scan
     int childTask, childRef, leafOff, nodeIdx;
 };
-struct U4 { unsigned int x, y, z, w; };
+struct U4 {
+    unsigned int x, y, z, w;
+    __device__ U4 operator+(const U4& b) const { return U4{x + b.x, y + b.y, z + b.z, w + b.w}; }
+};
 struct KdTotals {       // the per-level read-back
     U4 t;               // inner nodes, leaf index entries, next level's references, non-empty leaves of this level
     unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child (never expected)
@@ -71,55 +75,10 @@ struct KdParams {
     float ci, ct, failRq, pad;
 };
 
-__device__ __forceinline__ U4 vadd(U4 a, U4 b) { return U4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
-__device__ __forceinline__ unsigned long long vadd(unsigned long long a, unsigned long long b) { return a + b; }
-__device__ __forceinline__ void vzero(U4& a) { a = U4{0, 0, 0, 0}; }
-__device__ __forceinline__ void vzero(unsigned long long& a) { a = 0ull; }
-
-__device__ __forceinline__ unsigned int ord_enc(float f)
-{
-    const unsigned int b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__host__ __device__ __forceinline__ float ord_dec(unsigned int u)
-{
-    const unsigned int b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
-}
-
 __device__ __forceinline__ float sel3(const float* v, int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : v[2]); }
 
 // findPlaneAABB (rt_common.cu:1007-1030): pos = mn + (mx - mn) * rpos, two roundings
 __device__ __forceinline__ float plane_pos(float mn, float mx, int kk) { return mn + (mx - mn) * kRpos[kk]; }
-
-// areaAABB (rt_common.cu:850-858)
-__device__ __forceinline__ float area3(float dx, float dy, float dz) { return (dx * dy + dy * dz + dz * dx) * 2.0f; }
-
-// Exclusive scan over a block of KD_BLOCK threads (Hillis-Steele in LDS); *total receives the block's sum.
-template <class V>
-__device__ V block_exclusive_scan(V v, V* total)
-{
-    __shared__ V sh[KD_BLOCK];
-    const int i = threadIdx.x;
-    sh[i] = v;
-    __syncthreads();
-    for (int off = 1; off < KD_BLOCK; off <<= 1) {
-        V a;
-        vzero(a);
-        if (i >= off) a = sh[i - off];
-        __syncthreads();
-        if (i >= off) sh[i] = vadd(sh[i], a);
-        __syncthreads();
-    }
-    *total = sh[KD_BLOCK - 1];
-    V ex;
-    vzero(ex);
-    if (i > 0) ex = sh[i - 1];
-    __syncthreads();   // sh is reused by the next call
-    return ex;
-}
 
 // ---- once per build ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(KD_BLOCK) void kd_prep(int n, const int* __restrict__ tri, int numVerts, const float* __restrict__ pos,
@@ -287,28 +246,9 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_task_scan_local(int T, const KdTa
         else v = U4{1u, 0u, (unsigned int)d.nL + (unsigned int)d.nR, 0u};
     }
     U4 total;
-    const U4 ex = block_exclusive_scan(v, &total);
+    const U4 ex = block_exclusive_scan<KD_BLOCK>(v, &total);
     if (t < T) local[t] = ex;
     if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
-}
-
-// One workgroup: exclusive scan of nb block sums in place, the grand total to *total.
-template <class V>
-__global__ __launch_bounds__(KD_BLOCK) void kd_scan_blocks(int nb, V* __restrict__ sums, V* __restrict__ total)
-{
-    V carry;
-    vzero(carry);
-    for (int base = 0; base < nb; base += KD_BLOCK) {
-        const int i = base + threadIdx.x;
-        V v;
-        vzero(v);
-        if (i < nb) v = sums[i];
-        V chunk;
-        const V ex = block_exclusive_scan(v, &chunk);
-        if (i < nb) sums[i] = vadd(carry, ex);
-        carry = vadd(carry, chunk);
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 __global__ __launch_bounds__(KD_BLOCK) void kd_task_emit(int T, int level, const KdTask* __restrict__ tasks,
@@ -320,7 +260,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_task_emit(int T, int level, const
     const int t = blockIdx.x * KD_BLOCK + threadIdx.x;
     if (t >= T) return;
     const U4 l = local[t], b = blockSums[blockIdx.x];
-    const U4 g = vadd(l, b);
+    const U4 g = l + b;
     const KdDecision d = dec[t];
     const KdTask tk = tasks[t];
     const int n = tk.refCount;
@@ -387,7 +327,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_ref_scan_local(int R, const int* 
         }
     }
     unsigned long long total;
-    const unsigned long long ex = block_exclusive_scan(v, &total);
+    const unsigned long long ex = block_exclusive_scan<KD_BLOCK>(v, &total);
     if (r < R) local[r] = ex;
     if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
 }
@@ -436,28 +376,29 @@ struct KdCaps {
 struct KdLayout {
     size_t off = 0;
     size_t boxLo, boxHi, tasks[2], refs[2], taskOf[2], bins, dec, place, tLocal, tBlocks, rLocal, rBlocks, nodes, idx, sceneBox, totals;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
     KdLayout(int64_t n, const KdCaps& c)
     {
+        ScratchCarver cv;
         const int64_t nbT = c.tasks / KD_BLOCK + 1, nbR = c.refs / KD_BLOCK + 1;
-        boxLo = take((size_t)n * 16);
-        boxHi = take((size_t)n * 16);
+        boxLo = cv.take((size_t)n * 16);
+        boxHi = cv.take((size_t)n * 16);
         for (int k = 0; k < 2; k++) {
-            tasks[k] = take((size_t)c.tasks * sizeof(KdTask));
-            refs[k] = take((size_t)c.refs * 4);
-            taskOf[k] = take((size_t)c.refs * 4);
+            tasks[k] = cv.take((size_t)c.tasks * sizeof(KdTask));
+            refs[k] = cv.take((size_t)c.refs * 4);
+            taskOf[k] = cv.take((size_t)c.refs * 4);
         }
-        bins = take((size_t)c.tasks * 64 * 4);
-        dec = take((size_t)c.tasks * sizeof(KdDecision));
-        place = take((size_t)c.tasks * sizeof(KdPlace));
-        tLocal = take((size_t)c.tasks * sizeof(U4));
-        tBlocks = take((size_t)nbT * sizeof(U4));
-        rLocal = take((size_t)c.refs * 8);
-        rBlocks = take((size_t)(nbR + 1) * 8);   // + the grand total
-        nodes = take((size_t)c.nodes * 16);
-        idx = take((size_t)c.idx * 4);
-        sceneBox = take(6 * 4);
-        totals = take(sizeof(KdTotals));
+        bins = cv.take((size_t)c.tasks * 64 * 4);
+        dec = cv.take((size_t)c.tasks * sizeof(KdDecision));
+        place = cv.take((size_t)c.tasks * sizeof(KdPlace));
+        tLocal = cv.take((size_t)c.tasks * sizeof(U4));
+        tBlocks = cv.take((size_t)nbT * sizeof(U4));
+        rLocal = cv.take((size_t)c.refs * 8);
+        rBlocks = cv.take((size_t)(nbR + 1) * 8);   // + the grand total
+        nodes = cv.take((size_t)c.nodes * 16);
+        idx = cv.take((size_t)c.idx * 4);
+        sceneBox = cv.take(6 * 4);
+        totals = cv.take(sizeof(KdTotals));
+        off = cv.off;
     }
 };
 
@@ -472,10 +413,6 @@ int64_t grown(int64_t need, int64_t have, int64_t limit)
 }
 
 }  // namespace
-
-int kdtree_build_workspace_release() { return g_kdPool.release(); }
-size_t kdtree_build_workspace_bytes() { return g_kdPool.held(); }
-
 }  // namespace ntr
 
 using namespace ntr;
@@ -488,27 +425,6 @@ struct NtrDeviceKdtree {
 };
 
 namespace {
-
-struct KdEvents {
-    enum { N = 4 };
-    hipEvent_t ev[N] = {};
-    hipStream_t s;
-    explicit KdEvents(hipStream_t st) : s(st) { for (auto& e : ev) (void)hipEventCreate(&e); }
-    ~KdEvents() { for (auto& e : ev) (void)hipEventDestroy(e); }
-    void mark(int i) { (void)hipEventRecord(ev[i], s); }
-    float ms(int a, int b) { float v = 0; (void)hipEventElapsedTime(&v, ev[a], ev[b]); return v; }
-};
-
-int kd_malloc(void** p, size_t bytes, const char* what)
-{
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
-        (void)hipGetLastError();
-        return set_error(NTR_ERR_NOMEM, "ntr_kdtree_device_build: out of device memory (%s, %zu B)", what, bytes);
-    }
-    if (e != hipSuccess) return hip_fail(e, what);
-    return NTR_OK;
-}
 
 void free_tree(NtrDeviceKdtree* t)
 {
@@ -527,7 +443,7 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
     NtrDeviceKdtreeInfo& info = t->info;
     info.triWoopBytes = ((int64_t)n * 48 + 4095) & ~(int64_t)4095;
     {
-        const int rc = kd_malloc(&t->woop, (size_t)info.triWoopBytes, "triWoop");
+        const int rc = device_malloc(&t->woop, (size_t)info.triWoopBytes, "ntr_kdtree_device_build: triWoop");
         if (rc != NTR_OK) return rc;
     }
     NTR_HIP(hipMemsetAsync(t->woop, 0, (size_t)info.triWoopBytes, s));
@@ -553,7 +469,8 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
     }
     auto P = [&](size_t o) { return (char*)base + o; };
 
-    KdEvents ev(s);
+    StreamEvents<4> ev(s);
+    (void)ev.create();
     ev.mark(0);
     NTR_HIP(hipMemsetAsync(P(lay.totals), 0, sizeof(KdTotals), s));
     const unsigned int boxInit[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
@@ -638,7 +555,7 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
                                               (const float4*)P(lay.boxLo), (const float4*)P(lay.boxHi), (unsigned int*)P(lay.bins));
         kd_decide<<<(Ti + 3) / 4, KD_BLOCK, 0, s>>>(Ti, tasks, (const unsigned int*)P(lay.bins), (KdDecision*)P(lay.dec), kp);
         kd_task_scan_local<<<nbT, KD_BLOCK, 0, s>>>(Ti, tasks, (const KdDecision*)P(lay.dec), (U4*)P(lay.tLocal), (U4*)P(lay.tBlocks));
-        kd_scan_blocks<U4><<<1, KD_BLOCK, 0, s>>>(nbT, (U4*)P(lay.tBlocks), &((KdTotals*)P(lay.totals))->t);
+        scan_block_sums<KD_BLOCK, U4><<<1, KD_BLOCK, 0, s>>>(nbT, (U4*)P(lay.tBlocks), (U4*)P(lay.tBlocks), &((KdTotals*)P(lay.totals))->t);
         kd_task_emit<<<nbT, KD_BLOCK, 0, s>>>(Ti, level, tasks, (const KdDecision*)P(lay.dec), (const U4*)P(lay.tLocal),
                                               (const U4*)P(lay.tBlocks), (int)innerBase, (int)leafBase, info.sceneMax[0], (int*)P(lay.nodes),
                                               (int*)P(lay.idx), (KdTask*)P(lay.tasks[nxt]), (KdPlace*)P(lay.place));
@@ -646,8 +563,9 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
             kd_ref_scan_local<<<nbR, KD_BLOCK, 0, s>>>(Ri, (const int*)P(lay.refs[cur]), (const int*)P(lay.taskOf[cur]),
                                                        (const KdDecision*)P(lay.dec), (const float4*)P(lay.boxLo), (const float4*)P(lay.boxHi),
                                                        (unsigned long long*)P(lay.rLocal), (unsigned long long*)P(lay.rBlocks));
-            kd_scan_blocks<unsigned long long><<<1, KD_BLOCK, 0, s>>>(nbR, (unsigned long long*)P(lay.rBlocks),
-                                                                     (unsigned long long*)P(lay.rBlocks) + nbR);
+            scan_block_sums<KD_BLOCK, unsigned long long><<<1, KD_BLOCK, 0, s>>>(nbR, (unsigned long long*)P(lay.rBlocks),
+                                                                                (unsigned long long*)P(lay.rBlocks),
+                                                                                (unsigned long long*)P(lay.rBlocks) + nbR);
             kd_ref_scatter<<<nbR, KD_BLOCK, 0, s>>>(Ri, (const int*)P(lay.refs[cur]), (const int*)P(lay.taskOf[cur]), tasks,
                                                     (const KdDecision*)P(lay.dec), (const KdPlace*)P(lay.place), (const float4*)P(lay.boxLo),
                                                     (const float4*)P(lay.boxHi), (const unsigned long long*)P(lay.rLocal),
@@ -684,8 +602,8 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
     info.nodesBytes = innerBase * 16;
     info.triIndexBytes = leafBase * 4;
     {
-        int rc = kd_malloc(&t->nodes, (size_t)info.nodesBytes, "nodes");
-        if (rc == NTR_OK) rc = kd_malloc((void**)&t->idx, (size_t)info.triIndexBytes, "triIndex");
+        int rc = device_malloc(&t->nodes, (size_t)info.nodesBytes, "ntr_kdtree_device_build: nodes");
+        if (rc == NTR_OK) rc = device_malloc((void**)&t->idx, (size_t)info.triIndexBytes, "ntr_kdtree_device_build: triIndex");
         if (rc != NTR_OK) return rc;
     }
     NTR_HIP(hipMemcpyAsync(t->nodes, P(lay.nodes), (size_t)info.nodesBytes, hipMemcpyDeviceToDevice, s));
@@ -770,7 +688,7 @@ void ntr_device_kdtree_free(NtrDeviceKdtree* t) { free_tree(t); }
 int ntr_kdtree_device_scratch_bytes(int64_t* bytes)
 {
     if (!bytes) return set_error(NTR_ERR_INVALID, "ntr_kdtree_device_scratch_bytes: null");
-    *bytes = (int64_t)kdtree_build_workspace_bytes();
+    *bytes = (int64_t)g_kdPool.held();
     return NTR_OK;
 }
 

@@ -19,7 +19,7 @@
 //   refit), lbvh_top_refit_kernel, lbvh_place_kernel (Woop rows straight into the slots the leaves reserved).
 // The round-1 / round-2 paths (one launch per level, three-kernel sort passes, cell-table top pass) are kept as a patch:
 // scripts/studies/rejected_patches/lbvh_superseded_paths.patch.
-// This file is the shipped bottom-up pipeline and the build driver (ntr_lbvh_build); lbvh_workspace.h holds the driver's host helpers.
+// This file is the shipped bottom-up pipeline and the build driver (ntr_lbvh_build); device_scratch.h holds the driver's host helpers.
 //
 // The tree is the reference's tree: same split rule (highest differing Morton bit at or below the
 // level's bit, median when none), same leaf rule (count <= leafSize, or the level's bit is 0), same
@@ -1003,7 +1003,12 @@ __global__ __launch_bounds__(THREADS) void lbvh_leafmark_kernel(int n, int leafS
 
 using namespace ntr;
 
-#include "lbvh_workspace.h"   // PhaseEvents, the per-device workspace, Carver
+#include "device_scratch.h"   // StreamEvents, the per-device workspace, ScratchCarver
+
+namespace {
+// Grow-only scratch memory of the builder, kept between builds: a rebuild per frame must not pay nine hipMalloc/hipFree pairs.
+ntr::DeviceScratchPool g_ws;
+}  // namespace
 
 namespace ntr {
 // one-sweep tiles: 2048 keys while the launch is latency-bound; 6144 / 8192 for large inputs (fewer tiles to look back over, longer runs
@@ -1056,7 +1061,7 @@ static void lbvh_sort_layout(int n, size_t* off /* [7]: keysA keysB idxA idxB hi
 {
     *osItems = onesweep_items(n);
     *osTiles = (n + OS_THREADS * *osItems - 1) / (OS_THREADS * *osItems);
-    Carver cv;
+    ScratchCarver cv;
     off[0] = cv.take((size_t)n * 4); off[1] = cv.take((size_t)n * 4);
     off[2] = cv.take((size_t)n * 4); off[3] = cv.take((size_t)n * 4);
     off[4] = cv.take(4 * 256 * 4); off[5] = cv.take(64);
@@ -1098,11 +1103,7 @@ extern "C" {
 
 int ntr_lbvh_release_workspace(void)
 {
-    const int rc = workspace_release();
-    const int rc2 = ntr::raysort_scratch_release();
-    const int rc3 = ntr::hlbvh_workspace_release();
-    const int rc4 = ntr::kdtree_build_workspace_release();
-    return rc != NTR_OK ? rc : (rc2 != NTR_OK ? rc2 : (rc3 != NTR_OK ? rc3 : rc4));
+    return DeviceScratchPool::release_all();
 }
 
 
@@ -1150,7 +1151,7 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     const bool topDown = topMode != 3;
 
     // workspace: only the slices of the path that runs are reserved (bottom-up: about 175 B per triangle, top-down: about 100 B)
-    Carver cv;
+    ScratchCarver cv;
     auto takeIf = [&](bool cond, size_t bytes) { return cv.take(cond ? bytes : 0); };
     const size_t oKeysA = cv.take((size_t)n * 4), oKeysB = cv.take((size_t)n * 4);
     const size_t oIdxA = cv.take((size_t)n * 4), oIdxB = cv.take((size_t)n * 4);
@@ -1184,7 +1185,7 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     const size_t oSubBase = takeIf(bottomUp, (size_t)cntTiles * MARK_SUBS * 4);
     void* wsBase = nullptr;
     {
-        const int rc = workspace_reserve(cv.off, &wsBase);
+        const int rc = g_ws.reserve(cv.off, &wsBase);
         if (rc != NTR_OK) return rc;
     }
     char* ws = (char*)wsBase;
@@ -1192,7 +1193,8 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     unsigned int* osHist = (unsigned int*)(ws + oOsHist);
     unsigned int* osMisc = (unsigned int*)(ws + oOsMisc);
 
-    PhaseEvents pe(s);
+    StreamEvents<7> pe(s);
+    (void)pe.create();
     pe.mark(0);
 
     NTR_HIP(hipMemsetAsync(ws + oState, 0, (bottomUp ? oAggZeroEnd : oClearEnd) - oState, s));

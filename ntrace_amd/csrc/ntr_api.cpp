@@ -16,6 +16,7 @@
 
 #include "ntrace_amd.h"
 #include "ntr_internal.h"
+#include "device_scratch.h"
 #include "trace_kernels.h"
 #include "trace_plan.h"
 
@@ -830,17 +831,11 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
         if (variant == NTR_VARIANT_PERSISTENT) { p.fetchThreshold = pl.perrayFetchThreshold; p.poolKConst = 1; }
     }
 
-    struct EventPair {   // destroyed on every return path of the timed bracket
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    hipEvent_t& ev0 = ev.a;
-    hipEvent_t& ev1 = ev.b;
+    StreamEvents<2> ev(s);   // the timed bracket
     if (seconds) {
-        NTR_HIP(hipEventCreate(&ev0));
-        NTR_HIP(hipEventCreate(&ev1));
+        NTR_HIP(ev.create());
         NTR_HIP(hipStreamSynchronize(s));  // launchTimed syncs first (CudaKernel.cpp:193)
-        NTR_HIP(hipEventRecord(ev0, s));
+        NTR_HIP(ev.record(0));
     }
     if (predScratch) {  // inside the timed bracket: the prediction is part of what the launch costs
         const hipError_t pe = ntr_launch_predict(d_rays, numRays, orderBlocks, predTable->table, predTable->count, predScratch->classCount,
@@ -865,23 +860,19 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
                                                : ntr_launch_trace(pl.launchVariant, &p, pl.launchBlocks, s);
         if (le != hipSuccess) return hip_fail(le, "trace_bvh launch");
     }
-    if (seconds) NTR_HIP(hipEventRecord(ev1, s));
+    if (seconds) NTR_HIP(ev.record(1));
     if (refresh) {
         le = ntr_launch_sched_order(hint->cost, orderBlocks, tun.schedClasses, hint->order, 1, s);
         if (le != hipSuccess) return hip_fail(le, "sched_order launch");
         hint->valid = true;
     }
     if (seconds) {
-        NTR_HIP(hipEventSynchronize(ev1));
         float ms = 0.0f;
-        NTR_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+        NTR_HIP(ev.elapsed(0, 1, &ms));
         *seconds = ms * 1e-3f;
-        unsigned int st = 0;   // fetch-and-clear in one device-side step (the word is shared by all streams of the device)
-        std::lock_guard<std::mutex> slk(g_statusMu);
-        const hipError_t xe = ntr_launch_status_exchange(ds->status, ds->status + 8, s);
-        if (xe != hipSuccess) return hip_fail(xe, "status_exchange launch");
-        NTR_HIP(hipMemcpyAsync(&st, ds->status + 8, sizeof(st), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));
+        unsigned int st = 0;
+        rc = device_status_fetch(s, &st);
+        if (rc != NTR_OK) return rc;
         if (st & NTR_STATUS_STACK_OVERFLOW) return set_error(NTR_ERR_OVERFLOW, "trace_bvh: traversal stack overflow");
     }
     if (stats) {

@@ -21,18 +21,10 @@ Tunables tunables();
 // lifetime of the graph, so it is taken from never-recycled storage.
 bool stream_is_capturing(hipStream_t s);
 
-// rayops_kernels.hip: returns the per-device scratch of ntr_ray_morton_sort (ntr_lbvh_release_workspace calls it)
-int raysort_scratch_release();
-
 // lbvh_kernels.hip: Morton codes and their stable sort exactly as ntr_lbvh_build makes them (the HLBVH builder's first phase)
 size_t lbvh_sort_scratch_bytes(int n);
 int lbvh_sort_codes(int n, const int32_t* d_tri, const float* d_pos, const float sceneMin[3], const float sceneMax[3], void* scratch,
                     hipStream_t s, const unsigned int** keys, const int** idx, const unsigned int** errWord);
-// hlbvh_kernels.hip: returns the HLBVH builder's per-device scratch (ntr_lbvh_release_workspace calls it)
-int hlbvh_workspace_release();
-// kdtree_build_kernels.hip: returns the device kd-tree builder's per-device scratch (ntr_lbvh_release_workspace calls it)
-int kdtree_build_workspace_release();
-size_t kdtree_build_workspace_bytes();
 
 // ntr_api.cpp: the current device's sticky status word (the one ntr_trace_status reads) for launches made in other translation
 // units, and its fetch-and-clear (waits for `s`; *bits receives the word)

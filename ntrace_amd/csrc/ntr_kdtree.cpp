@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "CudaKDTree.hpp"
+#include "device_scratch.h"
 #include "kdtree_kernels.h"
 #include "ntr_internal.h"
 #include "trace_kernels.h"
@@ -233,22 +234,17 @@ int ntr_trace_kdtree(int32_t numRays, int32_t anyHit, const float sceneMin[3], c
     if (rc != NTR_OK) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    struct EventPair {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
+    ntr::StreamEvents<2> ev(s);
     if (seconds) {
-        NTR_HIP(hipEventCreate(&ev.a));
-        NTR_HIP(hipEventCreate(&ev.b));
-        NTR_HIP(hipEventRecord(ev.a, s));
+        NTR_HIP(ev.create());
+        NTR_HIP(ev.record(0));
     }
     const hipError_t le = ntr_launch_trace_kdtree(&p, s);
     if (le != hipSuccess) return ntr::hip_fail(le, "trace_kdtree launch");
     if (seconds) {
-        NTR_HIP(hipEventRecord(ev.b, s));
-        NTR_HIP(hipEventSynchronize(ev.b));
         float ms = 0.0f;
-        NTR_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+        NTR_HIP(ev.record(1));
+        NTR_HIP(ev.elapsed(0, 1, &ms));
         *seconds = ms * 1e-3f;
         unsigned int st = 0;
         rc = ntr::device_status_fetch(s, &st);

@@ -9,9 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <float.h>
-#include <mutex>
 
 #include "ntr_internal.h"
+#include "device_prims.h"
 #include "device_scratch.h"
 #include "radix_sort.h"
 
@@ -67,12 +67,8 @@ __global__ __launch_bounds__(256) void reconstruct_kernel(int rayType, int numRa
 }
 
 // ---- ray sort --------------------------------------------------------------------------------------
-// order-preserving float <-> uint mapping for atomicMin/Max on floats
-__device__ __forceinline__ unsigned int f2ord(float f) { unsigned int u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float ord2f(unsigned int u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
-
 // findAABBKernel (RayBufferKernels.cu:70-136): box of ray origins and end points origin + direction * tmax.
-__global__ __launch_bounds__(256) void ray_aabb_kernel(int n, const NtrRay* __restrict__ rays, unsigned int* __restrict__ box /* lo xyz, hi xyz (ordered uints) */)
+__global__ __launch_bounds__(256) void ray_aabb_kernel(int n, const NtrRay* __restrict__ rays, unsigned int* __restrict__ box /* lo xyz, hi xyz (ord_enc) */)
 {
     float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -101,14 +97,14 @@ __global__ __launch_bounds__(256) void ray_aabb_kernel(int n, const NtrRay* __re
         const int k = threadIdx.x;
         float a = s_lo[0][k], b = s_hi[0][k];
         for (int w = 1; w < 4; w++) { a = fminf(a, s_lo[w][k]); b = fmaxf(b, s_hi[w][k]); }
-        atomicMin(&box[k], f2ord(a));
-        atomicMax(&box[3 + k], f2ord(b));
+        atomicMin(&box[k], ord_enc(a));
+        atomicMax(&box[3 + k], ord_enc(b));
     }
 }
 
 __global__ void ray_aabb_decode_kernel(const unsigned int* __restrict__ box, float* __restrict__ out)
 {
-    if (threadIdx.x < 6) out[threadIdx.x] = ord2f(box[threadIdx.x]);
+    if (threadIdx.x < 6) out[threadIdx.x] = ord_dec(box[threadIdx.x]);
 }
 
 // genMortonKeysKernel (RayBufferKernels.cu:140-175): 6 x 32 bits interleaved (component c, bit i -> bit c + 6 i).
@@ -178,10 +174,6 @@ namespace {
 ntr::DeviceScratchPool g_sortScratch;
 }  // namespace
 
-namespace ntr {
-int raysort_scratch_release() { return g_sortScratch.release(); }
-}  // namespace ntr
-
 // Framebuffer gather of the multi-GPU path (ntr_dist.cpp): a rank's pixels packed in slot order / scattered back on the root.
 __global__ __launch_bounds__(256) void pixels_pack_kernel(const uint32_t* __restrict__ pixels, const int32_t* __restrict__ slotToPixel, int first, int count,
                                                          uint32_t* __restrict__ out)
@@ -242,13 +234,13 @@ int ntr_ray_morton_sort(int32_t numRays, const NtrRay* d_inRays, const int32_t* 
     const int tiles = (n + OS_THREADS * ITEMS - 1) / (OS_THREADS * ITEMS);
     // one zeroed block: digit histograms, per-pass tickets, error flag, then the tile state of the chained scans
     const size_t histWords = (size_t)RAY_KEY_DIGITS * 256, miscWords = 32, stateWords = (size_t)tiles * 256 * 2;   // 64-bit state words
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t oKeys = take((size_t)n * 24), oWordA = take((size_t)n * 4), oWordB = take((size_t)n * 4), oIdxA = take((size_t)n * 4), oIdxB = take((size_t)n * 4);
-    const size_t oZero = take((histWords + miscWords + stateWords) * 4), oBox = take(64);
+    ScratchCarver cv;
+    const size_t oKeys = cv.take((size_t)n * 24), oWordA = cv.take((size_t)n * 4), oWordB = cv.take((size_t)n * 4);
+    const size_t oIdxA = cv.take((size_t)n * 4), oIdxB = cv.take((size_t)n * 4);
+    const size_t oZero = cv.take((histWords + miscWords + stateWords) * 4), oBox = cv.take(64);
     void* base = nullptr;
     {
-        const int rc = g_sortScratch.reserve(off, &base);
+        const int rc = g_sortScratch.reserve(cv.off, &base);
         if (rc != NTR_OK) return rc;
     }
     char* ws = (char*)base;
@@ -256,8 +248,11 @@ int ntr_ray_morton_sort(int32_t numRays, const NtrRay* d_inRays, const int32_t* 
     unsigned int* histp = (unsigned int*)scratch.p;
     unsigned int* misc = histp + histWords;      // [0..18] tickets, [31] error flag
     unsigned long long* state = (unsigned long long*)(misc + miscWords);   // 8-byte aligned: histWords and miscWords are even
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (seconds) { NTR_HIP(hipEventCreate(&e0)); NTR_HIP(hipEventCreate(&e1)); NTR_HIP(hipEventRecord(e0, s)); }
+    StreamEvents<2> ev(s);
+    if (seconds) {
+        NTR_HIP(ev.create());
+        NTR_HIP(ev.record(0));
+    }
     NTR_HIP(hipMemsetAsync(scratch.p, 0, (histWords + miscWords + stateWords) * 4, s));
 
     unsigned int* ubox = (unsigned int*)box.p;
@@ -293,13 +288,10 @@ int ntr_ray_morton_sort(int32_t numRays, const NtrRay* d_inRays, const int32_t* 
                        d_outRays, d_outIDToSlot, d_outSlotToID);
     NTR_HIP(hipGetLastError());
     if (seconds) {
-        NTR_HIP(hipEventRecord(e1, s));
-        NTR_HIP(hipEventSynchronize(e1));
         float ms = 0;
-        NTR_HIP(hipEventElapsedTime(&ms, e0, e1));
+        NTR_HIP(ev.record(1));
+        NTR_HIP(ev.elapsed(0, 1, &ms));
         *seconds = ms * 1e-3f;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
     }
     unsigned int sortErr = 0;
     NTR_HIP(hipMemcpyAsync(&sortErr, misc + 31, sizeof(sortErr), hipMemcpyDeviceToHost, s));
