@@ -188,7 +188,6 @@ public:
 private:
     static std::vector<DeviceScratchPool*>& registry() { static std::vector<DeviceScratchPool*> r; return r; }
     static std::mutex& registry_mu() { static std::mutex m; return m; }
-    static constexpr int kMaxDevices = 64;
     struct Slot { void* p = nullptr; size_t bytes = 0; };
     Slot slots_[kMaxDevices];
     std::mutex mu_;

@@ -5,6 +5,8 @@
 #include "ntrace_amd.h"
 
 namespace ntr {
+constexpr int kMaxDevices = 64;   // device indices the per-device state of the library covers
+
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int hip_fail(hipError_t e, const char* what);
 
@@ -25,14 +27,9 @@ bool stream_is_capturing(hipStream_t s);
 size_t lbvh_sort_scratch_bytes(int n);
 int lbvh_sort_codes(int n, const int32_t* d_tri, const float* d_pos, const float sceneMin[3], const float sceneMax[3], void* scratch,
                     hipStream_t s, const unsigned int** keys, const int** idx, const unsigned int** errWord);
-
-// ntr_api.cpp: the current device's sticky status word (the one ntr_trace_status reads) for launches made in other translation
-// units, and its fetch-and-clear (waits for `s`; *bits receives the word)
-int device_status_word(unsigned int** status);
-int device_status_fetch(hipStream_t s, unsigned int* bits);
 }  // namespace ntr
 
-// ntr_api.cpp: (re)build the top-of-tree box table cached for this node buffer (dispatch-order prediction)
+// sched_state.cpp: (re)build the top-of-tree box table cached for this node buffer (dispatch-order prediction)
 extern "C" int ntr_top_table_refresh(const void* d_nodes, int64_t nodesBytes, void* stream);
 
 #define NTR_HIP(call)                                            \

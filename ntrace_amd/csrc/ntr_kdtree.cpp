@@ -12,6 +12,7 @@
 #include "device_scratch.h"
 #include "kdtree_kernels.h"
 #include "ntr_internal.h"
+#include "sched_state.h"
 #include "trace_kernels.h"
 
 using namespace FW;
@@ -230,8 +231,10 @@ int ntr_trace_kdtree(int32_t numRays, int32_t anyHit, const float sceneMin[3], c
     // CudaKDTreeTracer.cpp:97: (bbox.max + bbox.min).length() * 0.000001f
     const float sx = sceneMax[0] + sceneMin[0], sy = sceneMax[1] + sceneMin[1], sz = sceneMax[2] + sceneMin[2];
     p.delta = ::sqrtf(sx * sx + sy * sy + sz * sz) * 0.000001f;
-    int rc = ntr::device_status_word(&p.status);
+    ntr::DeviceState* ds = nullptr;   // the sticky status word ntr_trace_status reads
+    int rc = ntr::current_device_state_ready(&ds);
     if (rc != NTR_OK) return rc;
+    p.status = ds->status;
 
     hipStream_t s = (hipStream_t)stream;
     ntr::StreamEvents<2> ev(s);
@@ -247,7 +250,7 @@ int ntr_trace_kdtree(int32_t numRays, int32_t anyHit, const float sceneMin[3], c
         NTR_HIP(ev.elapsed(0, 1, &ms));
         *seconds = ms * 1e-3f;
         unsigned int st = 0;
-        rc = ntr::device_status_fetch(s, &st);
+        rc = ntr::status_fetch(ds, s, &st);
         if (rc != NTR_OK) return rc;
         if (st & NTR_STATUS_STACK_OVERFLOW) return ntr::set_error(NTR_ERR_OVERFLOW, "trace_kdtree: traversal stack overflow");
         if (st & NTR_STATUS_KDTREE_RANGE) return ntr::set_error(NTR_ERR_LAYOUT, "trace_kdtree: an index outside its buffer");
