@@ -479,6 +479,66 @@ NTR_API int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32
  * triangle plus about 500 B per Morton cluster); this call returns them too. */
 NTR_API int ntr_lbvh_release_workspace(void);
 
+/* On-device binned SAH BVH build: the reference's persistent BVH builder as configured (Renderer.cpp:262-267 "PersistentBVH";
+ * CudaPersistentBVHBuilder.cpp, persistent_bvh.cu with CudaTracerDefines.h SPLIT_TYPE 5, PLANE_COUNT 32, BINNING_TYPE 2, AABB_TYPE 3,
+ * SAH_TERMINATION, COMPUTE_MEDIAN_BOUNDS; config.conf block PersistentBVH), rebuilt breadth first, one level per round, without its
+ * persistent task pool or device heap (csrc/bvh_build_kernels.hip; the spec is tests/np_bvh_binned.py).  The tree feeds ntr_trace_bvh
+ * unchanged.
+ *   candidates  32 planes per task, 11 / 11 / 10 on x / y / z, pos = lo + (hi - lo) * ((1 + k) / 12.f), two roundings, over the task's
+ *               box as written into its parent node (the root's: sceneMin / sceneMax) (findPlaneAABB, rt_common.cu:1007-1030)
+ *   sides       the centroid c = fl(fl(mn + mx) * 0.5f) of the triangle's box; fl(pos - c) < 1e-8f is side -1, which goes to child 0
+ *               (getPlaneCentroidPosition, rt_common.cu:449-468): child 0 holds the centroids at or above the plane
+ *   cost        s = area(boxL) * nL + area(boxR) * nR over the sides' union boxes; an empty side's box is (FLT_MAX, -FLT_MAX), so its
+ *               cost is NaN.  CANONICAL: the lowest finite s wins (+0 == -0), then the lowest plane; NaN and infinite s never win
+ *   median      no winning plane -> child 0 gets the first n / 2 references of the task, child 1 the rest (persistent_bvh.cu:1815-1822)
+ *   boxes       a child's box is fl(min - epsilon) / fl(max + epsilon) of its triangles' union (min / max with -0 < +0), on the SAH
+ *               and the median path alike (persistent_bvh.cu:1855-1863, 4259-4261)
+ *   termination (persistent_bvh.cu:245-271) nL + nR <= triMaxLimit and ci * n < ct + ci * (areaL / area * nL + areaR / area * nR)
+ *               makes the task a leaf; otherwise a child with <= triLimit references or below a parent of depth > maxDepth - 2 is a
+ *               leaf, root depth 0
+ *   order       inner nodes in level order (root 0, child 0 before child 1); leaf Woop blocks and triIndex entries in the same order,
+ *               ascending triangle ids (the partition is stable): 3 rows per triangle (woop_rows.h), then a terminator row of
+ *               0x80000000; the triIndex entry of a triangle's first row is its id, the others are 0.  Compact nodes as ntr_lbvh_build
+ *               writes them: an inner child is 64 * index, a leaf child ~row, word 14 the split axis (0 for a median split), word 15 0.
+ * DEVIATION: the root is never a leaf (a Compact root is an inner node).  A root that termination ends (numTris <= triLimit, or the
+ *   SAH test) is split by its plane, else the median, into two leaves; one triangle gives an empty child 0 (box (FLT_MAX, -FLT_MAX),
+ *   a terminator row only) and the triangle in child 1, as the LBVH's one-triangle tree.
+ * Output: caller-owned BVHLayout_Compact buffers of at least ntr_lbvh_capacity() bytes, which bound the tree: a BVH without duplicate
+ *   references has at most max(N - 1, 1) inner nodes and 3N + leaves <= 4N + 1 Woop rows.  The result's *Bytes are the exact extents.
+ * Params: triLimit, triMaxLimit, maxDepth, ci, ct, epsilon; params == NULL is config.conf's block with epsilon = FLT_EPSILON
+ *   (Renderer.cpp:264).  childLimit, popCount and granularity configure SPLIT_TYPE 6 and the task pool and have no counterpart here.
+ * NTR_ERR_INVALID: numTris < 1 or >= 2^28, numVerts < 1, a null pointer, triLimit < 1, triMaxLimit < 0, maxDepth outside 1..100 (the
+ *   reference CPU tracer's stack of 100 entries, CudaBVH.cpp:701; the kernels hold 16 + 88), a non-finite ci / ct / epsilon, a
+ *   negative epsilon, a scene box with a non-finite coordinate or min > max on an axis (the planes must not decrease along an axis),
+ *   output buffers smaller than ntr_lbvh_capacity(), or (found on the device) a vertex index outside [0, numVerts).
+ *   NTR_ERR_OVERFLOW: the tree would have more than 0x76543200 / 64 = 31 019 208 inner nodes, which Compact's signed 32-bit child byte
+ *   offsets below the sentinel 0x76543210 cannot address (as ntr_lbvh_build; possible only beyond 31 M triangles with small leaves).
+ *   No node at or beyond that bound is written.  NTR_ERR_NOMEM: device memory (for numTris < 2^28 every index of the kernels fits
+ *   int32, so no level exceeds their indexing).  NTR_ERR_LAYOUT: an internal consistency check failed (not expected; reported instead
+ *   of writing out of bounds).
+ * The call blocks (one 32 B read-back per level).  The scratch is a per-device grow-only pool that ntr_lbvh_release_workspace returns:
+ *   one build per device at a time. */
+typedef struct NtrPersistentBvhParams {
+    int32_t triLimit, triMaxLimit, maxDepth, pad;
+    float   ci, ct, epsilon, pad2;
+} NtrPersistentBvhParams;
+typedef struct NtrPersistentBvhResult {
+    int32_t numNodes, numLeaves, numLevels, maxDepth;   /* inner nodes, leaves (the empty one included), rounds, inner nodes on the
+                                                           longest root-to-leaf path */
+    int32_t medianFallbacks, costLeaves, depthLeaves, pad;   /* tasks split at the median; tasks the SAH test ended; children with
+                                                                more than triLimit references made leaves by the depth cap */
+    int64_t nodesBytes, triWoopBytes, triIndexBytes;   /* exact extents of what was written */
+    float   seconds;                   /* host wall clock of the whole call */
+    float   prepMs, levelsMs, emitMs;  /* GPU event times: per-triangle terms, the level loop, the leaves' Woop rows */
+} NtrPersistentBvhResult;
+NTR_API int ntr_persistent_bvh_params_default(NtrPersistentBvhParams* params);
+NTR_API int ntr_persistent_bvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
+                                     const float sceneMin[3], const float sceneMax[3], const NtrPersistentBvhParams* params,
+                                     void* d_nodes, int64_t nodesCapacity, void* d_triWoop, int64_t triWoopCapacity,
+                                     int32_t* d_triIndex, int64_t triIndexCapacity, NtrPersistentBvhResult* result, void* stream);
+/* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_persistent_bvh_scratch_bytes(int64_t* bytes);
+
 /* reconstructKernel (src/rt/cuda/RendererKernels.cu:59-172; ReconstructInput, RendererKernels.hpp:46-70;
  * Renderer::updateResult, Renderer.cpp:583-659): hit records of one batch -> ABGR8 pixels.
  * rayType 0 = primary, 1 = AO, 2 = diffuse (textured / path-traced / VPL shading: out of scope). */

@@ -1,4 +1,4 @@
-"""ntrace_amd -- MI355X-native tracer backend for NTrace (BVH trace + LBVH build, kd-tree build (host and device) + trace).
+"""ntrace_amd -- MI355X-native tracer backend for NTrace (BVH trace + LBVH / HLBVH / binned SAH builds, kd-tree build (host and device) + trace).
 
 The product is libntrace_amd.so (hand-written HIP kernels for gfx950 behind the C-ABI
 of include/ntrace_amd.h) plus the C++ host mirror of the reference's Renderer / CudaBVH /
@@ -15,7 +15,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     lbvh_release_workspace, predict_block_costs, predict_batch_coherence, predict_dispatch_order, SchedHintState,
                     HostKdtree, kdtree_build, host_kdtree_wrap, trace_kdtree, KDTREE_SPATIAL_MEDIAN, KDTREE_SAH,
                     DeviceKdtree, KdtreeDeviceParams, kdtree_device_build, kdtree_device_params, KDTREE_DEVICE_DEFAULTS,
-                    kdtree_device_scratch_bytes)
+                    kdtree_device_scratch_bytes, PersistentBvhParams, PersistentBvhResult, persistent_bvh_params,
+                    persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -26,4 +27,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "lib_path", "query_config", "sah_build", "trace_bvh", "trace_bvh_stats", "TraceStats", "pixel_table", "raygen_primary", "raygen_ao", "count_hits", "selftest_division", "selftest_division_hard", "bvh_leaf_depths", "secondary_block_costs", "lbvh_capacity", "lbvh_build", "LbvhResult", "hlbvh_build", "HlbvhResult", "reconstruct", "ray_morton_sort", "camera_decode", "camera_reencode", "camera_nscreen_to_world", "obj_load", "SchedHint", "trace_status", "set_tunables", "host_bvh_wrap", "BVHLayout_Compact", "KERNELS",
            "HostKdtree", "kdtree_build", "host_kdtree_wrap", "trace_kdtree", "KDTREE_SPATIAL_MEDIAN", "KDTREE_SAH",
            "DeviceKdtree", "KdtreeDeviceParams", "kdtree_device_build", "kdtree_device_params", "KDTREE_DEVICE_DEFAULTS",
-           "kdtree_device_scratch_bytes"]
+           "kdtree_device_scratch_bytes", "PersistentBvhParams", "PersistentBvhResult", "persistent_bvh_params",
+           "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS"]

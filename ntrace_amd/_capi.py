@@ -80,6 +80,21 @@ class KdtreeDeviceParams(C.Structure):
                 ("depthK1", C.c_float), ("depthK2", C.c_float), ("ci", C.c_float), ("ct", C.c_float), ("failRq", C.c_float)]
 
 
+class PersistentBvhParams(C.Structure):
+    _fields_ = [("triLimit", C.c_int32), ("triMaxLimit", C.c_int32), ("maxDepth", C.c_int32), ("pad", C.c_int32),
+                ("ci", C.c_float), ("ct", C.c_float), ("epsilon", C.c_float), ("pad2", C.c_float)]
+
+
+class PersistentBvhResult(C.Structure):
+    _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numLevels", C.c_int32), ("maxDepth", C.c_int32),
+                ("medianFallbacks", C.c_int32), ("costLeaves", C.c_int32), ("depthLeaves", C.c_int32), ("pad", C.c_int32),
+                ("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
+                ("seconds", C.c_float), ("prepMs", C.c_float), ("levelsMs", C.c_float), ("emitMs", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class _DeviceKdtreeInfo(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
                 ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
@@ -185,6 +200,10 @@ SYMBOLS = [
     ("ntr_device_kdtree_free", None, [_vp]),
     ("ntr_device_kdtree_download", C.c_int, [_vp, _vp, _vp, _vp]),
     ("ntr_kdtree_device_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_persistent_bvh_params_default", C.c_int, [C.POINTER(PersistentBvhParams)]),
+    ("ntr_persistent_bvh_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(PersistentBvhParams),
+                                           _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(PersistentBvhResult), _vp]),
+    ("ntr_persistent_bvh_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
     ("ntr_host_kdtree_free", None, [_vp]),
     ("ntr_host_kdtree_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_vp)]),
@@ -585,6 +604,42 @@ def hlbvh_build(num_tris, d_tri, num_verts, d_pos, scene_min, scene_max, leaf_si
                                  int(hlbvh_bits), _vp(d_nodes), int(nodes_cap), _vp(d_woop), int(woop_cap), _vp(d_idx), int(idx_cap),
                                  C.byref(res), _vp(stream)))
     return res
+
+
+PERSISTENT_BVH_DEFAULTS = dict(triLimit=16, triMaxLimit=16, maxDepth=50, ci=1.0, ct=1.0, epsilon=float(np.finfo(np.float32).eps))
+
+
+def persistent_bvh_params(**kw):
+    """NtrPersistentBvhParams: config.conf's PersistentBVH block (epsilon FLT_EPSILON) with the given fields replaced."""
+    p = PersistentBvhParams()
+    _check(lib().ntr_persistent_bvh_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if k not in PERSISTENT_BVH_DEFAULTS:
+            raise TypeError("unknown persistent BVH parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def persistent_bvh_build(num_tris, d_tri, num_verts, d_pos, scene_min, scene_max, d_nodes, nodes_cap, d_woop, woop_cap, d_idx, idx_cap,
+                         params=None, stream=0):
+    """ntr_persistent_bvh_build: binned SAH on the device (the reference's PersistentBVH) into Compact buffers of lbvh_capacity() bytes.
+    params: None (the defaults), a dict of NtrPersistentBvhParams fields, or a PersistentBvhParams.  Returns a PersistentBvhResult."""
+    if isinstance(params, dict):
+        params = persistent_bvh_params(**params)
+    res = PersistentBvhResult()
+    mn = (C.c_float * 3)(*[float(x) for x in scene_min])
+    mx = (C.c_float * 3)(*[float(x) for x in scene_max])
+    _check(lib().ntr_persistent_bvh_build(int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos), mn, mx,
+                                          C.byref(params) if params is not None else None, _vp(d_nodes), int(nodes_cap), _vp(d_woop),
+                                          int(woop_cap), _vp(d_idx), int(idx_cap), C.byref(res), _vp(stream)))
+    return res
+
+
+def persistent_bvh_scratch_bytes():
+    """ntr_persistent_bvh_scratch_bytes: bytes the device BVH builder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_persistent_bvh_scratch_bytes(C.byref(v)))
+    return int(v.value)
 
 
 def camera_decode(signature):

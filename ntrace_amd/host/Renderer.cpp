@@ -20,7 +20,7 @@ Renderer::Renderer(const String& builder)
     m_cudaTracer->setScene(NULL);
     m_platform = Platform("GPU");
     m_platform.setLeafPreferences(1, 1);
-    m_buildParams.builder = (builder == "HLBVH" || m_isKDTree) ? "SAHBVH" : builder;
+    m_buildParams.builder = (builder == "HLBVH" || builder == "PersistentBVH" || m_isKDTree) ? "SAHBVH" : builder;
 }
 
 Renderer::~Renderer(void)
@@ -104,6 +104,8 @@ CudaAS* Renderer::getCudaBVH(void)
     if (m_builder == "HLBVH") {
         // Renderer.cpp:203-207 asks for hlbvh = true, hlbvhBits = 4; the default here stays the plain LBVH (setHLBVHParams)
         m_accelStruct = new HLBVHBuilder(m_scene, m_platform, m_hlbvhParams);
+    } else if (m_builder == "PersistentBVH") {   // Renderer.cpp:262-267: CudaPersistentBVHBuilder(*m_scene, FLT_EPSILON)
+        m_accelStruct = new CudaPersistentBVHBuilder(m_scene, FLT_EPSILON);
     } else {
         BVH bvh(m_scene, m_platform, m_buildParams);
         m_accelStruct = new CudaBVH(bvh, layout);
