@@ -539,6 +539,51 @@ NTR_API int ntr_persistent_bvh_build(int32_t numTris, const int32_t* d_triVtxInd
 /* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_persistent_bvh_scratch_bytes(int64_t* bytes);
 
+/* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
+ * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by
+ * the numpy spec tests/np_bvh_refit.py, not by reference lines.  It works on any Compact tree whatever built it -- ntr_sah_build
+ * (uploaded), ntr_lbvh_build, ntr_hlbvh_build, ntr_persistent_bvh_build, a bvhcache file -- as long as the mesh keeps its triangles
+ * (d_triVtxIndex, numTris) and only d_vtxPos changes.
+ *   written      in place: the 12 box floats of every node a link reaches, and the three Woop rows of every triangle of every leaf
+ *   not written  child words, the split word and the fourth word of a node's link float4, leaf terminators, d_triIndex, the rows
+ *                behind a leaf's terminator, and node slots no link reaches (zero-filled slots inside the extent, NtrLbvhResult)
+ *   Woop rows    of the row group r, r+1, r+2 of a leaf: woop_rows.h of triangle d_triIndex[r] over the new positions -- the device
+ *                builders' function, so the rows equal a fresh device build's bit for bit (a host SAH tree's rows, made by the
+ *                host's woopify, may change in their last bits even for unmoved vertices)
+ *   leaf box     per axis the minimum and maximum over the three vertices of every triangle of the leaf, then fl(lo - epsilon),
+ *                fl(hi + epsilon) (the LBVH's rule; epsilon 0 is the exact union, which a host SAH tree stores).  A leaf without
+ *                rows (the one-triangle tree's empty child 0) keeps its box words
+ *   inner box    the union of the two boxes stored in that child's node; epsilon is applied at the leaves only (a "PersistentBVH"
+ *                tree, which grows every level by its epsilon, comes out valid and slightly tighter, not identical)
+ *   min / max    in the total order -0 < +0, so no result depends on the order of the operands or of the threads: the output is
+ *                deterministic.  NaN coordinates are out of contract (result unspecified; nothing outside the buffers is touched)
+ *   d_sceneBox   optional, 6 floats min.xyz max.xyz: the union of the root's two boxes
+ * Two launches on `stream` that re-initialise their own state, no host read-back: with result == NULL the call is asynchronous and
+ * can be captured into a HIP graph like ntr_trace_bvh.  With result != NULL it blocks, reads back what the passes counted and the
+ * GPU time, and reports a malformed tree (a link or row outside the extents, a triangle or vertex index out of range:
+ * NTR_ERR_LAYOUT; such a part is never followed, and with result == NULL it is skipped silently).  The topology arrays (8 B per node
+ * slot, and 16 KB of counters) live in a per-device grow-only pool that ntr_lbvh_release_workspace returns.  The pool regrows only
+ * after the device has drained, so a call that must grow it cannot be captured: a captured call needs one earlier uncaptured call on
+ * a tree at least as large (inside a capture a too-small pool is NTR_ERR_INVALID, never an allocation), and the pool must not be
+ * regrown or released while such a graph lives.  One refit per device at a time.
+ * Afterwards the caller re-runs ntr_bvh_validate: the FASTDIV / NOTINY / ORDERED / FINITE flags and the top-of-tree table depend on the
+ * boxes.  Scheduling hints (NtrSchedHint) learned on the old boxes stay legal, because they only ever order blocks.
+ * NTR_ERR_INVALID (before any device work): a null pointer (d_sceneBox and result may be null), nodesBytes not a multiple of 64 in
+ * [64, 0x76543200], triWoopBytes not a positive multiple of 16, triIndexBytes * 4 < triWoopBytes, numTris < 1, numVerts < 1, epsilon
+ * negative or not finite.  Without a device: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrBvhRefitResult {
+    int32_t numNodes, numLeaves, numRows, pad;   /* what the passes counted: 1 + inner links, leaf links, rows of the leaves with
+                                                    their terminators (read back only when result != NULL) */
+    float   seconds;                             /* GPU time of the call when result != NULL, else untouched */
+} NtrBvhRefitResult;
+NTR_API int ntr_bvh_refit(void* d_nodes, int64_t nodesBytes, void* d_triWoop, int64_t triWoopBytes,
+                          const int32_t* d_triIndex, int64_t triIndexBytes,
+                          int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
+                          float epsilon, float* d_sceneBox /* may be NULL */,
+                          NtrBvhRefitResult* result /* NULL: asynchronous, capturable */, void* stream);
+/* Bytes the refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_refit_scratch_bytes(int64_t* bytes);
+
 /* reconstructKernel (src/rt/cuda/RendererKernels.cu:59-172; ReconstructInput, RendererKernels.hpp:46-70;
  * Renderer::updateResult, Renderer.cpp:583-659): hit records of one batch -> ABGR8 pixels.
  * rayType 0 = primary, 1 = AO, 2 = diffuse (textured / path-traced / VPL shading: out of scope). */

@@ -16,7 +16,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     HostKdtree, kdtree_build, host_kdtree_wrap, trace_kdtree, KDTREE_SPATIAL_MEDIAN, KDTREE_SAH,
                     DeviceKdtree, KdtreeDeviceParams, kdtree_device_build, kdtree_device_params, KDTREE_DEVICE_DEFAULTS,
                     kdtree_device_scratch_bytes, PersistentBvhParams, PersistentBvhResult, persistent_bvh_params,
-                    persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS)
+                    persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS, BvhRefitResult, bvh_refit,
+                    bvh_refit_scratch_bytes)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -28,4 +29,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "HostKdtree", "kdtree_build", "host_kdtree_wrap", "trace_kdtree", "KDTREE_SPATIAL_MEDIAN", "KDTREE_SAH",
            "DeviceKdtree", "KdtreeDeviceParams", "kdtree_device_build", "kdtree_device_params", "KDTREE_DEVICE_DEFAULTS",
            "kdtree_device_scratch_bytes", "PersistentBvhParams", "PersistentBvhResult", "persistent_bvh_params",
-           "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS"]
+           "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS", "BvhRefitResult", "bvh_refit",
+           "bvh_refit_scratch_bytes"]

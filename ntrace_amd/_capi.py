@@ -95,6 +95,13 @@ class PersistentBvhResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class BvhRefitResult(C.Structure):
+    _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("pad", C.c_int32), ("seconds", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class _DeviceKdtreeInfo(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
                 ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
@@ -204,6 +211,8 @@ SYMBOLS = [
     ("ntr_persistent_bvh_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(PersistentBvhParams),
                                            _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(PersistentBvhResult), _vp]),
     ("ntr_persistent_bvh_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
+    ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
     ("ntr_host_kdtree_free", None, [_vp]),
     ("ntr_host_kdtree_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_vp)]),
@@ -639,6 +648,25 @@ def persistent_bvh_scratch_bytes():
     """ntr_persistent_bvh_scratch_bytes: bytes the device BVH builder's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_persistent_bvh_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def bvh_refit(d_nodes, nodes_bytes, d_woop, woop_bytes, d_idx, idx_bytes, num_tris, d_tri, num_verts, d_pos, epsilon=0.0, d_scene_box=0,
+              stream=0, blocking=True):
+    """ntr_bvh_refit: recompute a Compact tree's boxes and Woop rows in place from the vertex positions at d_pos (an extension; the
+    rule is tests/np_bvh_refit.py).  blocking=True returns a BvhRefitResult (counts, GPU seconds); blocking=False passes result = NULL:
+    the call is asynchronous on `stream` (capturable) and returns None."""
+    res = BvhRefitResult() if blocking else None
+    _check(lib().ntr_bvh_refit(_vp(d_nodes), int(nodes_bytes), _vp(d_woop), int(woop_bytes), _vp(d_idx), int(idx_bytes), int(num_tris),
+                               _vp(d_tri), int(num_verts), _vp(d_pos), float(epsilon), _vp(d_scene_box),
+                               C.byref(res) if blocking else None, _vp(stream)))
+    return res
+
+
+def bvh_refit_scratch_bytes():
+    """ntr_bvh_refit_scratch_bytes: bytes the refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_refit_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

@@ -12,7 +12,7 @@
 
 namespace FW {
 
-CudaBVH::CudaBVH(const BVH& bvh, BVHLayout layout) : m_layout(layout), m_flags(0), m_flagsValid(false)
+CudaBVH::CudaBVH(const BVH& bvh, BVHLayout layout) : m_layout(layout), m_flags(0), m_flagsValid(false), m_refitResult()
 {
     // This fork builds Compact only (CudaBVH.cpp:65-82 asserts on anything else).
     // The reference additionally permutes non-root node slots at random
@@ -22,7 +22,7 @@ CudaBVH::CudaBVH(const BVH& bvh, BVHLayout layout) : m_layout(layout), m_flags(0
     createCompact(bvh, 1);
 }
 
-CudaBVH::CudaBVH(std::istream& in) : m_flags(0), m_flagsValid(false)
+CudaBVH::CudaBVH(std::istream& in) : m_flags(0), m_flagsValid(false), m_refitResult()
 {
     S32 layout = 0;
     in.read((char*)&layout, sizeof(layout));
@@ -55,6 +55,19 @@ U32 CudaBVH::getTraceFlags(void)
         m_flagsValid = true;
     }
     return m_flags;
+}
+
+void CudaBVH::refit(Scene& scene, F32 epsilon)
+{
+    if (m_layout != BVHLayout_Compact) fail("CudaBVH::refit: only BVHLayout_Compact is supported");
+    NtrBvhRefitResult res = NtrBvhRefitResult();
+    const int rc = ntr_bvh_refit(m_nodes.getMutableCudaPtr(), m_nodes.getSize(), m_triWoop.getMutableCudaPtr(), m_triWoop.getSize(),
+                                 (const int32_t*)m_triIndex.getCudaPtr(), m_triIndex.getSize(), scene.getNumTriangles(),
+                                 (const int32_t*)scene.getTriVtxIndexBuffer().getCudaPtr(), scene.getNumVertices(),
+                                 (const float*)scene.getVtxPosBuffer().getCudaPtr(), epsilon, NULL, &res, NULL);
+    if (rc != NTR_OK) fail("CudaBVH::refit: %s", ntr_last_error());
+    m_refitResult = res;
+    invalidateTraceFlags();   // FASTDIV / NOTINY / ORDERED and the top-of-tree table depend on the boxes
 }
 
 // Emission order of CudaBVH::createCompact (CudaBVH.cpp:594-652): explicit stack,

@@ -18,7 +18,7 @@ public:
     enum { Align = 4096 };
 
     explicit CudaBVH(const BVH& bvh, BVHLayout layout);         // CudaBVH.cpp:60-103
-    explicit CudaBVH(BVHLayout layout) : m_layout(layout), m_flags(0), m_flagsValid(false) {}
+    explicit CudaBVH(BVHLayout layout) : m_layout(layout), m_flags(0), m_flagsValid(false), m_refitResult() {}
     explicit CudaBVH(std::istream& in);                          // CudaBVH.cpp:105-108
     virtual ~CudaBVH(void) {}
 
@@ -34,6 +34,17 @@ public:
     U32 getTraceFlags(void);
     void invalidateTraceFlags(void) { m_flagsValid = false; }
 
+    // Mirror extension (the reference's scenes are static; no counterpart there): keep the topology and recompute every box and Woop
+    // row on the device from the scene's CURRENT vertex positions (ntr_bvh_refit on this tree's buffers; the scene must hold the
+    // triangles the tree was built over, see Scene::setVertexPositions), then invalidateTraceFlags().  Works on a tree of any
+    // origin, a bvhcache import included.  epsilon grows the leaf boxes; refit(scene) takes getRefitEpsilon(): 0, the exact union a
+    // host SAH tree stores, unless the builder says otherwise (HLBVHBuilder: the epsilon it was built with).  Blocking; fails
+    // (FW::fail) with the library's message.
+    void        refit(Scene& scene, F32 epsilon);
+    void        refit(Scene& scene) { refit(scene, getRefitEpsilon()); }
+    virtual F32 getRefitEpsilon(void) const { return 0.0f; }
+    const NtrBvhRefitResult& getRefitResult(void) const { return m_refitResult; }   // of the last refit (zero before the first)
+
 protected:
     friend class CudaKDTree;  // the kd-tree's Woop rows are CudaBVH's (CudaKDTree.hpp)
     void createCompact(const BVH& bvh, int nodeOffsetSizeDiv);  // CudaBVH.cpp:579-664
@@ -45,6 +56,7 @@ protected:
     Buffer    m_triIndex;
     U32       m_flags;
     bool      m_flagsValid;
+    NtrBvhRefitResult m_refitResult;
 };
 
 }  // namespace FW

@@ -119,6 +119,15 @@ CudaAS* Renderer::getCudaBVH(void)
     return m_accelStruct;
 }
 
+void Renderer::refit(void)
+{
+    if (m_isKDTree) fail("Renderer::refit: the kd-tree has no refit");
+    if (!m_scene) fail("Renderer: no scene");
+    CudaBVH* bvh = dynamic_cast<CudaBVH*>(getCudaBVH());   // built first if there is none
+    if (!bvh) fail("Renderer::refit: not a BVH");
+    bvh->refit(*m_scene);                                  // m_leafDepth stays: leaf depths are topology
+}
+
 CudaAS* Renderer::getCudaKDTree(void)
 {
     if (!m_scene || m_accelStruct) return m_accelStruct;

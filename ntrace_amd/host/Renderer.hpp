@@ -50,6 +50,10 @@ public:
     const HLBVHParams& getHLBVHParams(void) const { return m_hlbvhParams; }
     BVH::BuildParams& getBuildParams(void) { return m_buildParams; }
     void   invalidateBVH(void) { delete m_accelStruct; m_accelStruct = NULL; m_leafDepthOf = NULL; }
+    // Mirror extension (no counterpart in the reference): after Scene::setVertexPositions, bring the current BVH up to date with
+    // CudaBVH::refit instead of rebuilding it (it is built first if there is none).  The leaf depths behind the AO dispatch hint are
+    // kept: they are topology.  A bvhcache file is not rewritten.  A kd-tree builder fails: "Renderer::refit: the kd-tree has no refit".
+    void   refit(void);
     void   setParams(const Params& params);
     void   setEnableRandom(bool enable) { m_enableRandom = enable; }
     CudaVirtualTracer& getCudaTracer(void) { return *m_cudaTracer; }

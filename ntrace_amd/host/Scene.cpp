@@ -12,6 +12,20 @@ Scene::Scene(S32 numTris, const Vec3i* triVtxIndex, S32 numVerts, const Vec3f* v
     m_triVtxIndex.set(triVtxIndex, (S64)numTris * sizeof(Vec3i));
     m_vtxPos.set(vtxPos, (S64)numVerts * sizeof(Vec3f));
     m_triNormal.resizeDiscard((S64)numTris * sizeof(Vec3f));
+    updateDerived(vtxPos);
+}
+
+void Scene::setVertexPositions(const Vec3f* vtxPos)
+{
+    if (!vtxPos) fail("Scene::setVertexPositions: null positions");
+    m_vtxPos.set(vtxPos);   // into whichever copy, host or device, is current
+    updateDerived(vtxPos);
+}
+
+void Scene::updateDerived(const Vec3f* vtxPos)
+{
+    const S32 numTris = m_numTriangles, numVerts = m_numVertices;
+    const Vec3i* triVtxIndex = (const Vec3i*)m_triVtxIndex.getPtr();
     Vec3f* nrm = (Vec3f*)m_triNormal.getMutablePtr();
 
     // Scene.cpp:112-135: bbox over vertices, per-triangle geometric normal.

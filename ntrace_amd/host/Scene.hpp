@@ -18,10 +18,15 @@ public:
     Buffer& getTriNormalBuffer(void) { return m_triNormal; }
     void    getBBox(Vec3f& lo, Vec3f& hi) const { lo = m_AABBMin; hi = m_AABBMax; }
     U32     hash(void);
+    // Mirror extension (the reference's scenes are static): replaces the positions of all getNumVertices() vertices and recomputes the
+    // triangle normals and the box the way the constructor does, so that AO ray generation follows the moved surface.  A tree built
+    // over the old positions is brought up to date by CudaBVH::refit / Renderer::refit, or rebuilt (Renderer::invalidateBVH).
+    void    setVertexPositions(const Vec3f* vtxPos);
 
 private:
     Scene(const Scene&);
     Scene& operator=(const Scene&);
+    void   updateDerived(const Vec3f* vtxPos);   // box and triangle normals from the positions just stored (Scene.cpp:112-135)
 
     S32    m_numTriangles;
     S32    m_numVertices;
