@@ -584,6 +584,64 @@ NTR_API int ntr_bvh_refit(void* d_nodes, int64_t nodesBytes, void* d_triWoop, in
 /* Bytes the refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_bvh_refit_scratch_bytes(int64_t* bytes);
 
+/* On-device treelet restructuring: raise the quality of a BVHLayout_Compact tree in place, whatever built or refitted it
+ * (csrc/bvh_optimize_kernels.hip).  EXTENSION without a reference counterpart: the rule is pinned by the numpy spec
+ * tests/np_bvh_optimize.py (its docstring is the normative text), not by reference lines.  The algorithm is the treelet part of Karras
+ * and Aila, "Fast parallel construction of high-quality bounding volume hierarchies" (HPG 2013) with treelets of 7 entries.
+ * Only the node buffer is read and written: leaves stay as they are (d_triWoop and d_triIndex are not even passed), leaf links move
+ * between parents, so ntr_trace_bvh and ntr_bvh_refit work on the result unchanged.
+ *   per pass     every reached slot with at least 7 leaf links below it roots a treelet, in ascending height (slots of one height have
+ *                disjoint subtrees: one launch per height).  The treelet grows from the root's two children by expanding, six times
+ *                in all, the inner entry of the largest area; a dynamic programme over the 127 subsets of the 7 entries finds the
+ *                binary topology with the smallest sum of inner-node areas (binary32, no contraction, ties to the lowest mask)
+ *   written      a treelet is rewritten only if that sum is STRICTLY smaller than its existing topology's; then its root and its five
+ *                other internal slots (handed out in ascending index in preorder) get the new boxes (unions in the total order
+ *                -0 < +0) and links, and split word 0 (no kernel reads the split word).  The output is deterministic
+ *   not written  the fourth word of a link float4, every treelet that does not improve, slots no link reaches, the root's parent
+ * passes in 1..8; the gain per pass falls quickly.  Restructuring can deepen a tree: the tracer's stack limit (104
+ * entries) and its sticky overflow word (ntr_trace_status) are unchanged, and result->heightAfter lets a caller check.
+ * The call BLOCKS: per pass the host reads the height histogram back to size its launches, so it cannot be captured into a HIP graph
+ * (NTR_ERR_INVALID on a capturing stream).  result may be NULL.  Scratch (48 B per node slot; 56 B for ntr_bvh_sah_cost, which shares the pool) comes from a per-device grow-only
+ * pool that ntr_lbvh_release_workspace returns.  One optimise or refit per device at a time.
+ * Afterwards the caller re-runs ntr_bvh_validate (flags and the top-of-tree table depend on the boxes) and recomputes
+ * ntr_bvh_leaf_depths (they are topology); scheduling hints (NtrSchedHint) stay legal, because they only ever order blocks.
+ * A child link outside the node extent, or a child word 0 below the root, is never followed: it counts as a leaf link that cannot be
+ * expanded, and the former makes the call return NTR_ERR_LAYOUT after the work, as ntr_bvh_refit's blocking form does.  Boxes with
+ * NaN are out of contract: the result is then unspecified but still a tree over the same leaf links, and nothing outside the buffer
+ * is touched.
+ * NTR_ERR_INVALID (before any device work): null d_nodes, nodesBytes not a multiple of 64 in [64, 0x76543200], passes outside 1..8.
+ * Without a device: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrBvhOptimizeResult {
+    int32_t passes, numNodes, numLeafLinks, pad;   /* passes run; reached slots and the leaf links below them */
+    int32_t formed[8], rewritten[8];               /* per pass: treelets formed, and those of them rewritten */
+    int32_t heightBefore[8], heightAfter[8];       /* per pass: inner nodes on the longest root-to-leaf path */
+    float   seconds;                               /* GPU time of the call */
+} NtrBvhOptimizeResult;
+NTR_API int ntr_bvh_optimize(void* d_nodes, int64_t nodesBytes, int32_t passes, NtrBvhOptimizeResult* result /* may be NULL */,
+                             void* stream);
+/* Bytes the scratch pool of ntr_bvh_optimize / ntr_bvh_sah_cost holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_optimize_scratch_bytes(int64_t* bytes);
+
+/* HLBVHBuilder::calcSAHGPU (src/rt/bvh/HLBVH/HLBVHBuilder.cpp:752-770; kernel calcSAH / calcSAHNode / calcLeafs,
+ * emitTreeKernel.cu:1351-1400): the SAH cost of a Compact tree, sahCost = calcSAHNode(0).  The reference runs the recursion in one
+ * thread and compiles it -use_fast_math, so it defines no bits; here every node is computed in strict binary32 in source order
+ * (fminf / fmaxf: the other operand for a NaN, else the total order -0 < +0; areas 2*((dx*dy + dy*dz) + dz*dx); the node's value
+ * fl(fl(1 + fl(fl(pl/pa) * l)) + fl(fl(pr/pa) * r)) with the correctly rounded divide; a leaf child's value is its triangle count up
+ * to the terminator) by a parallel bottom-up pass in which the second arrival at a node computes it, so the result does not depend on
+ * timing.  Zero areas give infinities and NaNs as IEEE does; they are returned as they come.  The numpy spec is
+ * tests/np_bvh_optimize.py sah_cost().  Blocking, not capturable.  A child link outside the extent or a leaf without a terminator
+ * inside d_triWoop counts as 0 and makes the call return NTR_ERR_LAYOUT; a child word 0 counts as 0.
+ * NTR_ERR_INVALID (before any device work): a null pointer, nodesBytes not a multiple of 64 in [64, 0x76543200], triWoopBytes not a
+ * positive multiple of 16.  Without a device: NTR_ERR_NO_DEVICE / NTR_ERR_HIP. */
+typedef struct NtrBvhSahResult {
+    float   sahCost;
+    int32_t numNodes, numLeaves, numTris, height;   /* reached slots, their negative child words, the leaves' triangles, inner nodes
+                                                       on the longest root-to-leaf path */
+    float   seconds;                                /* GPU time of the call */
+} NtrBvhSahResult;
+NTR_API int ntr_bvh_sah_cost(const void* d_nodes, int64_t nodesBytes, const void* d_triWoop, int64_t triWoopBytes,
+                             NtrBvhSahResult* result, void* stream);
+
 /* reconstructKernel (src/rt/cuda/RendererKernels.cu:59-172; ReconstructInput, RendererKernels.hpp:46-70;
  * Renderer::updateResult, Renderer.cpp:583-659): hit records of one batch -> ABGR8 pixels.
  * rayType 0 = primary, 1 = AO, 2 = diffuse (textured / path-traced / VPL shading: out of scope). */

@@ -17,7 +17,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     DeviceKdtree, KdtreeDeviceParams, kdtree_device_build, kdtree_device_params, KDTREE_DEVICE_DEFAULTS,
                     kdtree_device_scratch_bytes, PersistentBvhParams, PersistentBvhResult, persistent_bvh_params,
                     persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS, BvhRefitResult, bvh_refit,
-                    bvh_refit_scratch_bytes)
+                    bvh_refit_scratch_bytes, BvhOptimizeResult, BvhSahResult, bvh_optimize, bvh_optimize_scratch_bytes, bvh_sah_cost)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -30,4 +30,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "DeviceKdtree", "KdtreeDeviceParams", "kdtree_device_build", "kdtree_device_params", "KDTREE_DEVICE_DEFAULTS",
            "kdtree_device_scratch_bytes", "PersistentBvhParams", "PersistentBvhResult", "persistent_bvh_params",
            "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS", "BvhRefitResult", "bvh_refit",
-           "bvh_refit_scratch_bytes"]
+           "bvh_refit_scratch_bytes", "BvhOptimizeResult", "BvhSahResult", "bvh_optimize", "bvh_optimize_scratch_bytes",
+           "bvh_sah_cost"]

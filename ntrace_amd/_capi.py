@@ -102,6 +102,25 @@ class BvhRefitResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class BvhOptimizeResult(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("numNodes", C.c_int32), ("numLeafLinks", C.c_int32), ("pad", C.c_int32),
+                ("formed", C.c_int32 * 8), ("rewritten", C.c_int32 * 8), ("heightBefore", C.c_int32 * 8), ("heightAfter", C.c_int32 * 8),
+                ("seconds", C.c_float)]
+
+    def as_dict(self):
+        n = self.passes
+        return {k: (list(getattr(self, k))[:n] if k in ("formed", "rewritten", "heightBefore", "heightAfter") else getattr(self, k))
+                for k, _ in self._fields_ if k != "pad"}
+
+
+class BvhSahResult(C.Structure):
+    _fields_ = [("sahCost", C.c_float), ("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numTris", C.c_int32), ("height", C.c_int32),
+                ("seconds", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class _DeviceKdtreeInfo(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
                 ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
@@ -213,6 +232,9 @@ SYMBOLS = [
     ("ntr_persistent_bvh_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
+    ("ntr_bvh_optimize_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_sah_cost", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhSahResult), _vp]),
     ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
     ("ntr_host_kdtree_free", None, [_vp]),
     ("ntr_host_kdtree_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_vp)]),
@@ -668,6 +690,29 @@ def bvh_refit_scratch_bytes():
     v = _i64(0)
     _check(lib().ntr_bvh_refit_scratch_bytes(C.byref(v)))
     return int(v.value)
+
+
+def bvh_optimize(d_nodes, nodes_bytes, passes=1, stream=0):
+    """ntr_bvh_optimize: restructure a Compact tree's treelets in place (an extension; the rule is tests/np_bvh_optimize.py).  Blocks;
+    returns a BvhOptimizeResult (per pass: treelets formed and rewritten, height before and after; GPU seconds)."""
+    res = BvhOptimizeResult()
+    _check(lib().ntr_bvh_optimize(_vp(d_nodes), int(nodes_bytes), int(passes), C.byref(res), _vp(stream)))
+    return res
+
+
+def bvh_optimize_scratch_bytes():
+    """ntr_bvh_optimize_scratch_bytes: bytes the scratch pool of bvh_optimize / bvh_sah_cost holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_optimize_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def bvh_sah_cost(d_nodes, nodes_bytes, d_woop, woop_bytes, stream=0):
+    """ntr_bvh_sah_cost: the reference's calcSAHGPU in strict binary32 (spec: tests/np_bvh_optimize.py sah_cost).  Blocks; returns a
+    BvhSahResult (sahCost, reached slots, leaves, triangles, height, GPU seconds)."""
+    res = BvhSahResult()
+    _check(lib().ntr_bvh_sah_cost(_vp(d_nodes), int(nodes_bytes), _vp(d_woop), int(woop_bytes), C.byref(res), _vp(stream)))
+    return res
 
 
 def camera_decode(signature):

@@ -70,6 +70,26 @@ void CudaBVH::refit(Scene& scene, F32 epsilon)
     invalidateTraceFlags();   // FASTDIV / NOTINY / ORDERED and the top-of-tree table depend on the boxes
 }
 
+void CudaBVH::optimize(int passes)
+{
+    if (m_layout != BVHLayout_Compact) fail("CudaBVH::optimize: only BVHLayout_Compact is supported");
+    NtrBvhOptimizeResult res = NtrBvhOptimizeResult();
+    const int rc = ntr_bvh_optimize(m_nodes.getMutableCudaPtr(), m_nodes.getSize(), passes, &res, NULL);
+    invalidateTraceFlags();   // the flags and the top-of-tree table depend on the boxes, also after a failure half way
+    if (rc != NTR_OK) fail("CudaBVH::optimize: %s", ntr_last_error());
+    m_optimizeResult = res;
+}
+
+F32 CudaBVH::calcSAHCost(void)
+{
+    if (m_layout != BVHLayout_Compact) fail("CudaBVH::calcSAHCost: only BVHLayout_Compact is supported");
+    NtrBvhSahResult res = NtrBvhSahResult();
+    if (ntr_bvh_sah_cost(m_nodes.getCudaPtr(), m_nodes.getSize(), m_triWoop.getCudaPtr(), m_triWoop.getSize(), &res, NULL) != NTR_OK)
+        fail("CudaBVH::calcSAHCost: %s", ntr_last_error());
+    m_sahResult = res;
+    return res.sahCost;
+}
+
 // Emission order of CudaBVH::createCompact (CudaBVH.cpp:594-652): explicit stack,
 // pop -> for child 0 then child 1: an inner child takes the next 64-B slot at once
 // (so siblings are adjacent) and is pushed; a leaf child appends its triangles and

@@ -45,6 +45,19 @@ public:
     virtual F32 getRefitEpsilon(void) const { return 0.0f; }
     const NtrBvhRefitResult& getRefitResult(void) const { return m_refitResult; }   // of the last refit (zero before the first)
 
+    // Mirror extension (no counterpart in the reference): restructure the tree's treelets on the device for a lower SAH cost
+    // (ntr_bvh_optimize on this tree's node buffer; triangles and leaves stay), then invalidateTraceFlags().  Works on a tree of any
+    // origin, fresh or refitted.  Leaf depths change with the topology: whoever cached ntr_bvh_leaf_depths recomputes them
+    // (Renderer::optimizeBVH does).  passes in 1..8; DefaultOptimizePasses is the count after which the measured trace rate stopped
+    // improving by more than its run-to-run spread.  Nothing calls this implicitly.  Blocking; fails (FW::fail) with
+    // the library's message.
+    enum { DefaultOptimizePasses = 2 };
+    void        optimize(int passes = DefaultOptimizePasses);
+    const NtrBvhOptimizeResult& getOptimizeResult(void) const { return m_optimizeResult; }   // of the last optimize (zero before)
+    // HLBVHBuilder::calcSAHGPU (HLBVHBuilder.cpp:752-770) for a tree of any origin: ntr_bvh_sah_cost on this tree's buffers.
+    F32         calcSAHCost(void);
+    const NtrBvhSahResult& getSAHResult(void) const { return m_sahResult; }                   // of the last calcSAHCost
+
 protected:
     friend class CudaKDTree;  // the kd-tree's Woop rows are CudaBVH's (CudaKDTree.hpp)
     void createCompact(const BVH& bvh, int nodeOffsetSizeDiv);  // CudaBVH.cpp:579-664
@@ -57,6 +70,8 @@ protected:
     U32       m_flags;
     bool      m_flagsValid;
     NtrBvhRefitResult m_refitResult;
+    NtrBvhOptimizeResult m_optimizeResult = NtrBvhOptimizeResult();
+    NtrBvhSahResult   m_sahResult = NtrBvhSahResult();
 };
 
 }  // namespace FW

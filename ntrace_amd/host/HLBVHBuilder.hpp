@@ -23,6 +23,7 @@ public:
 
     F32  getGPUTime(void) const { return m_gpuTime; }
     virtual F32 getRefitEpsilon(void) const { return m_params.epsilon; }   // CudaBVH::refit grows the leaf boxes as the build did
+    F32  calcSAHGPU(void) { return calcSAHCost(); }                         // HLBVHBuilder.cpp:752-770 (CudaBVH::calcSAHCost)
     void getStats(U32& nodes, U32& leaves, U32& nodeTop) const { nodes = m_nodesCnt; leaves = m_leafs; nodeTop = m_nodesCnt; }
     const NtrLbvhResult& getBuildResult(void) const { return m_result; }
     const NtrHlbvhResult& getHlbvhResult(void) const { return m_hlResult; }   // zero after buildLBVH

@@ -128,6 +128,16 @@ void Renderer::refit(void)
     bvh->refit(*m_scene);                                  // m_leafDepth stays: leaf depths are topology
 }
 
+void Renderer::optimizeBVH(int passes)
+{
+    if (m_isKDTree) fail("Renderer::optimizeBVH: the kd-tree has no treelet optimiser");
+    if (!m_scene) fail("Renderer: no scene");
+    CudaBVH* bvh = dynamic_cast<CudaBVH*>(getCudaBVH());   // built first if there is none
+    if (!bvh) fail("Renderer::optimizeBVH: not a BVH");
+    m_leafDepthOf = NULL;                                  // leaf depths are topology: recomputed with the next AO batch
+    bvh->optimize(passes);
+}
+
 CudaAS* Renderer::getCudaKDTree(void)
 {
     if (!m_scene || m_accelStruct) return m_accelStruct;

@@ -54,6 +54,11 @@ public:
     // CudaBVH::refit instead of rebuilding it (it is built first if there is none).  The leaf depths behind the AO dispatch hint are
     // kept: they are topology.  A bvhcache file is not rewritten.  A kd-tree builder fails: "Renderer::refit: the kd-tree has no refit".
     void   refit(void);
+    // Mirror extension (no counterpart in the reference): CudaBVH::optimize on the current BVH (it is built first if there is none),
+    // for a fresh tree or after refit().  The leaf depths behind the AO dispatch hint are recomputed at the next AO batch: they are
+    // topology, which this changes.  A bvhcache file is not rewritten.  A kd-tree builder fails:
+    // "Renderer::optimizeBVH: the kd-tree has no treelet optimiser".  Nothing calls this implicitly.
+    void   optimizeBVH(int passes = CudaBVH::DefaultOptimizePasses);
     void   setParams(const Params& params);
     void   setEnableRandom(bool enable) { m_enableRandom = enable; }
     CudaVirtualTracer& getCudaTracer(void) { return *m_cudaTracer; }
