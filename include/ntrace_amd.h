@@ -539,6 +539,59 @@ NTR_API int ntr_persistent_bvh_build(int32_t numTris, const int32_t* d_triVtxInd
 /* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_persistent_bvh_scratch_bytes(int64_t* bytes);
 
+/* On-device full-sweep SAH BVH build: the tree of ntr_sah_build -- the host builder host/bvh/SAHBVHBuilder.cpp, i.e. the reference's
+ * SAHBVHBuilder (src/rt/bvh/SAHBVHBuilder.cpp:51-254) with Platform("GPU") (Renderer.cpp:88-89: node cost 1, triangle cost 1, batch
+ * sizes 1) and leaf preferences (minLeafSize, maxLeafSize) -- node for node and triangle for triangle, built one level per round
+ * from three axis orders sorted once (csrc/sah_build_kernels.hip; the spec is tests/np_sah_sweep.py).  The tree feeds ntr_trace_bvh,
+ * ntr_bvh_refit and ntr_bvh_optimize unchanged.
+ *   triangles   box = min / max of the vertices (-0 < +0); key on axis d = fl(min[d] + max[d]); a triangle whose box has a negative
+ *               extent or at most one non-zero extent (size.min() < 0 || size.sum() == size.max(), :141-151) is dropped and reaches no
+ *               leaf; the root's box covers every triangle, the dropped ones too (:70-84)
+ *   order       ascending key (-0 == +0), ties by ascending triangle id (:106-115); every node owns the same range of all three orders
+ *   sweep       node of m references, area A (AABB::area, 0 for an invalid box): for each axis and i = 1 .. m-1
+ *               sah = fl(fl(A * 2 + fl(areaL(i) * fl(i))) + fl(areaR(i) * fl(m - i))), balance = fl(fl(i)^2 + fl(m - i)^2); the winner is
+ *               the lexicographic minimum of (sah, balance, axis, i) under float < / == starting from (FLT_MAX, FLT_MAX) (:221-232): a
+ *               NaN or infinite sah never wins.  Without a winner (m < 2, overflowing areas) ALL references go to child 1 and none to
+ *               child 0, as the host's default split has it; that chain ends at depth 64
+ *   leaves      level != 0 && m <= minLeafSize, or level >= 64, before the search; level != 0 && min(leafSAH, sah) == leafSAH &&
+ *               m <= maxLeafSize after it (:155-156, :163-165), leafSAH = fl(A * fl(m)).  The root is never a leaf.  A leaf lists its
+ *               triangles back to front of the order its range was last arranged by: axis 2 after a search, else the parent's split
+ *               axis (:193-203)
+ *   children    the first numLeft of the winning axis' order are child 0; boxes are the exact unions without epsilon, an empty child's
+ *               (FLT_MAX, -FLT_MAX); word 14 is SplitInfo::getBitCode() (the axis; 0 without a winner), word 15 is 0
+ *   order       CANONICAL (the host's createCompact numbers by an explicit stack instead; compare the trees by walking them): inner
+ *               nodes in level order (root 0, child 0 before child 1); leaf Woop blocks and triIndex entries in the same order: 3 rows
+ *               per triangle (woop_rows.h, as the other device builders), then a terminator row of 0x80000000; the triIndex entry of a
+ *               triangle's first row is its id, the others are 0
+ * The sign of a zero box coordinate is the one freedom against the host tree (FW::min / max keep the first operand's zero); no area,
+ * cost or decision depends on it.  NaN coordinates are out of contract.
+ * Output: caller-owned BVHLayout_Compact buffers of at least ntr_lbvh_capacity() bytes.  They hold every tree whose splits all have a
+ *   winner (at most max(N - 1, 1) inner nodes, 3N + leaves <= 4N + 1 rows); a chain of splits without a winner adds one inner node and
+ *   one empty leaf per level, and a tree that outgrows the buffers passed is NTR_ERR_OVERFLOW (pass larger ones).  The result's *Bytes
+ *   are the exact extents.
+ * NTR_ERR_INVALID (before any device work): numTris < 1 or >= 2^28, numVerts < 1, a null pointer, minLeafSize < 1, maxLeafSize <
+ *   minLeafSize, output buffers smaller than ntr_lbvh_capacity(); (found on the device) a vertex index outside [0, numVerts).
+ *   NTR_ERR_OVERFLOW: more than 0x76543200 / 64 inner nodes (Compact's 32-bit child offsets), or a tree beyond the buffers passed; no
+ *   node or row beyond either bound is written.  NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a device: there is no CPU fallback.
+ *   NTR_ERR_NOMEM: device memory.  NTR_ERR_LAYOUT: an internal consistency check failed (not expected).  A failed call zeroes *result.
+ * The call blocks (one 32 B read-back per level).  The scratch (about 310 B per triangle) is a per-device grow-only pool that
+ *   ntr_lbvh_release_workspace returns: one build per device at a time. */
+typedef struct NtrSahDeviceResult {
+    int32_t numNodes, numLeaves, numLevels, maxDepth;   /* inner nodes, leaves (empty ones included), rounds, inner nodes on the
+                                                           longest root-to-leaf path */
+    int32_t numDropped, pad[3];            /* triangles the drop test removed */
+    int64_t nodesBytes, triWoopBytes, triIndexBytes;   /* exact extents of what was written */
+    float   seconds;                       /* host wall clock of the whole call */
+    float   prepMs, sortMs, levelsMs, emitMs;          /* GPU event times: boxes and live list, the three sorts, the level loop, the
+                                                           leaves' Woop rows */
+} NtrSahDeviceResult;
+NTR_API int ntr_sah_device_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
+                                 int32_t minLeafSize, int32_t maxLeafSize, void* d_nodes, int64_t nodesCapacity, void* d_triWoop,
+                                 int64_t triWoopCapacity, int32_t* d_triIndex, int64_t triIndexCapacity, NtrSahDeviceResult* result,
+                                 void* stream);
+/* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_sah_device_scratch_bytes(int64_t* bytes);
+
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by
  * the numpy spec tests/np_bvh_refit.py, not by reference lines.  It works on any Compact tree whatever built it -- ntr_sah_build

@@ -16,7 +16,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     HostKdtree, kdtree_build, host_kdtree_wrap, trace_kdtree, KDTREE_SPATIAL_MEDIAN, KDTREE_SAH,
                     DeviceKdtree, KdtreeDeviceParams, kdtree_device_build, kdtree_device_params, KDTREE_DEVICE_DEFAULTS,
                     kdtree_device_scratch_bytes, PersistentBvhParams, PersistentBvhResult, persistent_bvh_params,
-                    persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS, BvhRefitResult, bvh_refit,
+                    persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS, SahDeviceResult,
+                    sah_device_build, sah_device_scratch_bytes, BvhRefitResult, bvh_refit,
                     bvh_refit_scratch_bytes, BvhOptimizeResult, BvhSahResult, bvh_optimize, bvh_optimize_scratch_bytes, bvh_sah_cost)
 
 BVHLayout_Compact = 4
@@ -29,6 +30,7 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "HostKdtree", "kdtree_build", "host_kdtree_wrap", "trace_kdtree", "KDTREE_SPATIAL_MEDIAN", "KDTREE_SAH",
            "DeviceKdtree", "KdtreeDeviceParams", "kdtree_device_build", "kdtree_device_params", "KDTREE_DEVICE_DEFAULTS",
            "kdtree_device_scratch_bytes", "PersistentBvhParams", "PersistentBvhResult", "persistent_bvh_params",
-           "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS", "BvhRefitResult", "bvh_refit",
+           "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS", "SahDeviceResult",
+           "sah_device_build", "sah_device_scratch_bytes", "BvhRefitResult", "bvh_refit",
            "bvh_refit_scratch_bytes", "BvhOptimizeResult", "BvhSahResult", "bvh_optimize", "bvh_optimize_scratch_bytes",
            "bvh_sah_cost"]

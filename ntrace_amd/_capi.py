@@ -95,6 +95,16 @@ class PersistentBvhResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class SahDeviceResult(C.Structure):
+    _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numLevels", C.c_int32), ("maxDepth", C.c_int32),
+                ("numDropped", C.c_int32), ("pad", C.c_int32 * 3),
+                ("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
+                ("seconds", C.c_float), ("prepMs", C.c_float), ("sortMs", C.c_float), ("levelsMs", C.c_float), ("emitMs", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class BvhRefitResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("pad", C.c_int32), ("seconds", C.c_float)]
 
@@ -230,6 +240,8 @@ SYMBOLS = [
     ("ntr_persistent_bvh_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(PersistentBvhParams),
                                            _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(PersistentBvhResult), _vp]),
     ("ntr_persistent_bvh_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_sah_device_build", C.c_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(SahDeviceResult), _vp]),
+    ("ntr_sah_device_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
@@ -670,6 +682,23 @@ def persistent_bvh_scratch_bytes():
     """ntr_persistent_bvh_scratch_bytes: bytes the device BVH builder's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_persistent_bvh_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def sah_device_build(num_tris, d_tri, num_verts, d_pos, d_nodes, nodes_cap, d_woop, woop_cap, d_idx, idx_cap, min_leaf=1, max_leaf=1,
+                     stream=0):
+    """ntr_sah_device_build: the host SAH builder's tree (sah_build, leaf preferences min_leaf / max_leaf) built on the device by full
+    sweeps over three presorted axis orders, into Compact buffers of at least lbvh_capacity() bytes.  Returns a SahDeviceResult."""
+    res = SahDeviceResult()
+    _check(lib().ntr_sah_device_build(int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos), int(min_leaf), int(max_leaf), _vp(d_nodes),
+                                      int(nodes_cap), _vp(d_woop), int(woop_cap), _vp(d_idx), int(idx_cap), C.byref(res), _vp(stream)))
+    return res
+
+
+def sah_device_scratch_bytes():
+    """ntr_sah_device_scratch_bytes: bytes the device SAH builder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_sah_device_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

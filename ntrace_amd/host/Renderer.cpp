@@ -20,7 +20,7 @@ Renderer::Renderer(const String& builder)
     m_cudaTracer->setScene(NULL);
     m_platform = Platform("GPU");
     m_platform.setLeafPreferences(1, 1);
-    m_buildParams.builder = (builder == "HLBVH" || builder == "PersistentBVH" || m_isKDTree) ? "SAHBVH" : builder;
+    m_buildParams.builder = (builder == "HLBVH" || builder == "PersistentBVH" || builder == "DeviceSAHBVH" || m_isKDTree) ? "SAHBVH" : builder;
 }
 
 Renderer::~Renderer(void)
@@ -106,6 +106,8 @@ CudaAS* Renderer::getCudaBVH(void)
         m_accelStruct = new HLBVHBuilder(m_scene, m_platform, m_hlbvhParams);
     } else if (m_builder == "PersistentBVH") {   // Renderer.cpp:262-267: CudaPersistentBVHBuilder(*m_scene, FLT_EPSILON)
         m_accelStruct = new CudaPersistentBVHBuilder(m_scene, FLT_EPSILON);
+    } else if (m_builder == "DeviceSAHBVH") {    // an extension: "SAHBVH"'s tree (the same platform and leaf preferences) built on the device
+        m_accelStruct = new CudaSAHBVHBuilder(m_scene, m_platform);
     } else {
         BVH bvh(m_scene, m_platform, m_buildParams);
         m_accelStruct = new CudaBVH(bvh, layout);

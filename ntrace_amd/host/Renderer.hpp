@@ -3,7 +3,8 @@
 // Kept: setMesh / setScene / setParams / getCudaBVH / beginFrame / nextBatch / traceBatch / updateResult (countHits + reconstruct:
 // SURVEY 8(f-2)) / getTotalNumRays for the primary, AO and diffuse ray types; setShard for the multi-GPU extension; the kd-tree data
 // structure (builders "SpatialMedianKDTree" / "SAHKDTree" on the host and "PersistentKDTree" on the device: CudaKDTreeTracer over
-// getCudaKDTree, Renderer.cpp:75-76, 309-382, 415-416); the device BVH builders "HLBVH" and "PersistentBVH" (Renderer.cpp:194-267).
+// getCudaKDTree, Renderer.cpp:75-76, 309-382, 415-416); the device BVH builders "HLBVH" and "PersistentBVH" (Renderer.cpp:194-267)
+// and, as an extension, "DeviceSAHBVH".
 // Out of scope: GL display, visualisation, VPL, the persistent builders' task pools and allocators, kd-tree cache files.
 #pragma once
 #include "MeshWavefrontIO.hpp"
@@ -11,6 +12,7 @@
 #include "CudaKDTreeTracer.hpp"
 #include "CudaPersistentBVHBuilder.hpp"
 #include "CudaPersistentKDTreeBuilder.hpp"
+#include "CudaSAHBVHBuilder.hpp"
 #include "HLBVHBuilder.hpp"
 #include "RayGen.hpp"
 
@@ -30,7 +32,7 @@ public:
     };
 
     // builder: "SAHBVH" (host, leaf preferences (1,1)), "HLBVH" (device LBVH), "PersistentBVH" (device binned SAH,
-    // CudaPersistentBVHBuilder), or a kd-tree: "SpatialMedianKDTree" / "SAHKDTree"
+    // CudaPersistentBVHBuilder), "DeviceSAHBVH" ("SAHBVH"'s tree built on the device, CudaSAHBVHBuilder), or a kd-tree: "SpatialMedianKDTree" / "SAHKDTree"
     // (host builds) or "PersistentKDTree" (device build, CudaPersistentKDTreeBuilder), traced by CudaKDTreeTracer --
     // Renderer.builder / Renderer.dataStructure in config.conf
     explicit Renderer(const String& builder = "SAHBVH");

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""The on-device binned SAH BVH build (ntr_persistent_bvh_build) against the other BVH builders: build times, tree statistics and
-trace rates.
+"""The on-device SAH BVH builds -- binned (ntr_persistent_bvh_build) and full sweep (ntr_sah_device_build, the host SAH builder's
+tree) -- against the other BVH builders: build times, tree statistics and trace rates.
 
 For each scene: the build's time (the call's wall clock, the span of its GPU events and their phases, median of --reps builds after
 --warmup builds) beside the GPU times the LBVH (ntr_lbvh_build, leafSize 8, epsilon 0.001) and the HLBVH (hlbvhBits 4) report and
 the host SAH build (one build, wall clock); and the
-ntr_trace_bvh Mrays/s of the device SAH tree, the LBVH and the host SAH tree on the same rays -- a 1920x1080 primary batch and the
+ntr_trace_bvh Mrays/s of the device SAH trees, the LBVH and the host SAH tree on the same rays -- a 1920x1080 primary batch and the
 8 x AO batch made from the LBVH's primary hits (ntr_raygen_ao, radius 5 as bench.py).  A rate is the rays over the sum of the kernel
-times of --reps launches after --warmup launches.  Prints one JSON line per scene.
+times of --reps launches after --warmup launches; the host tree is measured a second time at the end ("host_sah_again_*": its
+run-to-run spread in this process), and the ntr_trace_bvh_stats counters of the host tree and the full-sweep device tree -- the
+same nodes in another numbering -- are reported for the primary batch.  Prints one JSON line per scene.
 
     python scripts/bvh_build_bench.py [--scenes atrium conference_room hairball] [--reps 5] [--warmup 2] [--out f.json]
 """
@@ -95,6 +97,24 @@ def main():
                                  "levels_ms": float(np.median(runs[:, 2])), "emit_ms": float(np.median(runs[:, 3])),
                                  **{k: getattr(r, k) for k in ("numNodes", "numLeaves", "numLevels", "maxDepth", "medianFallbacks")}}
         trees["persistent"] = (pb, r.nodesBytes, r.triWoopBytes)
+        # the full-sweep device SAH build: the host SAH builder's tree
+        sb = buffers()
+
+        def sweep():
+            r = nt.sah_device_build(n_tri, d_tri.data_ptr(), pos.shape[0], d_pos.data_ptr(), sb[0].data_ptr(), capn, sb[1].data_ptr(), capw,
+                                    sb[2].data_ptr(), capi, 1, 1, stream)
+            sweep.last = r
+            return r.seconds, r.prepMs, r.sortMs, r.levelsMs, r.emitMs
+
+        runs = np.array(median_build(sweep, args.reps, args.warmup))
+        r = sweep.last
+        row["sah_device"] = {"wall_ms_median": float(np.median(runs[:, 0]) * 1e3),
+                             "gpu_event_ms_median": float(np.median(runs[:, 1:].sum(axis=1))),
+                             "prep_ms": float(np.median(runs[:, 1])), "sort_ms": float(np.median(runs[:, 2])),
+                             "levels_ms": float(np.median(runs[:, 3])), "emit_ms": float(np.median(runs[:, 4])),
+                             "scratch_bytes_per_tri": nt.sah_device_scratch_bytes() / n_tri,
+                             **{k: getattr(r, k) for k in ("numNodes", "numLeaves", "numLevels", "maxDepth", "numDropped")}}
+        trees["sah_device"] = (sb, r.nodesBytes, r.triWoopBytes)
         # LBVH and HLBVH (bits 4): the builds' own GPU times
         lb = buffers()
 
@@ -149,6 +169,15 @@ def main():
         for key in trees:
             m[key + "_primary"] = rate(lambda: trace(key, n, False, d_rays, d_res), n, args.reps, args.warmup)
             m[key + "_ao"] = rate(lambda: trace(key, n_ao, True, d_ao, d_ao_res), n_ao, args.reps, args.warmup)
+        if "host_sah" in trees:
+            m["host_sah_again_primary"] = rate(lambda: trace("host_sah", n, False, d_rays, d_res), n, args.reps, args.warmup)
+            m["host_sah_again_ao"] = rate(lambda: trace("host_sah", n_ao, True, d_ao, d_ao_res), n_ao, args.reps, args.warmup)
+            st = {}
+            for key in ("host_sah", "sah_device"):
+                b, nb, wb = trees[key]
+                st[key] = nt.trace_bvh_stats(args.kernel, n, False, d_rays.data_ptr(), d_res.data_ptr(), b[0].data_ptr(), nb, b[1].data_ptr(), wb,
+                                             b[2].data_ptr(), bvh_flags=flags[key], stream=stream).as_dict()
+            row["primary_trace_stats"] = st
         row["mrays_s"] = m
         print(json.dumps(row), flush=True)
         results.append(row)
