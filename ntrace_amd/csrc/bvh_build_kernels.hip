@@ -15,7 +15,7 @@
 //                     offsets and bin slots by an exclusive scan over the tasks; inner nodes, parent links and leaf terminators
 //                   bv_ref_scan_local + scan_block_sums + bv_ref_scatter: each task's child 0 ranks by a scan over the references,
 //                     then a stable scatter into the next level's list, or the leaf row of a reference whose task is a leaf
-//   end             bv_emit_leaves: every triangle's three Woop rows (woop_rows.h) and its triIndex entries at its leaf row
+//   end             emit_leaf_rows (device_prims.h): every triangle's three Woop rows and its triIndex entries at its leaf row
 // Phases hand data over only at kernel boundaries.  The host reads one 32-byte record per level (the level's totals and the error
 // word) to size the next level; nothing else comes back until the build ends.  Outputs go straight into the caller's buffers.
 #include <hip/hip_runtime.h>
@@ -30,9 +30,9 @@
 #include <cmath>
 
 #include "ntr_internal.h"
+#include "compact_bvh.h"
 #include "device_prims.h"
 #include "device_scratch.h"
-#include "woop_rows.h"
 
 namespace ntr {
 namespace {
@@ -43,7 +43,6 @@ constexpr int BV_BINS = 3 * (BV_PER_AXIS + 1) - 1;     // 12 + 12 + 11
 constexpr int BV_SLOT = BV_BINS * 8 + 16;              // words per splitting task: 35 bins of 8 words, then the median boxes
 constexpr float BV_EPS = 1e-8f;                        // rt_common.cuh:37
 constexpr int BV_BLOCK = 256;
-constexpr unsigned int BV_TERM = 0x80000000u;
 constexpr int BV_MAX_DEPTH = 100;                      // CudaBVH.cpp:701: the CPU tracer's stack; the kernels hold 16 + 88
 
 // rpos = (float)(1 + k) / (float)(planesPerAxis + 1) (rt_common.cu:1013), folded by the compiler with IEEE rounding
@@ -63,10 +62,6 @@ struct BvDecision {     // 64 B
 struct BvPlace {        // a task's global offsets after the task scan
     int childTask, childRef, row, nodeIdx;
 };
-struct U4 {
-    unsigned int x, y, z, w;
-    __device__ U4 operator+(const U4& b) const { return U4{x + b.x, y + b.y, z + b.z, w + b.w}; }
-};
 struct BvTotals {       // the per-level read-back
     U4 t;               // inner nodes, Woop rows of the level's leaves, next level's references, next level's splitting tasks
     unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child, bit 2: an output row or node
@@ -78,15 +73,11 @@ struct BvParams {
     float ci, ct, eps, pad;
 };
 
-__device__ __forceinline__ float sel3(const float* v, int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : v[2]); }
 __device__ __forceinline__ float sel4(const float4& v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
 // findPlaneAABB (rt_common.cu:1007-1030): pos = mn + (mx - mn) * rpos, two roundings
 __device__ __forceinline__ float plane_pos(float mn, float mx, int j) { return mn + (mx - mn) * kBvRpos[j]; }
 // getPlaneCentroidPosition (rt_common.cu:449-468) == -1: planeDistance with the plane (-1, 0, 0, pos) is fl(pos - c)
 __device__ __forceinline__ bool side_neg(float pos, float c) { return (pos - c) < BV_EPS; }
-// min / max in the total order -0 < +0
-__device__ __forceinline__ float omin(float a, float b) { return ord_enc(a) <= ord_enc(b) ? a : b; }
-__device__ __forceinline__ float omax(float a, float b) { return ord_enc(a) >= ord_enc(b) ? a : b; }
 
 // ---- once per build ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BV_BLOCK) void bv_prep(int n, const int* __restrict__ tri, int numVerts, const float* __restrict__ pos,
@@ -95,17 +86,11 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_prep(int n, const int* __restrict
 {
     const int i = blockIdx.x * BV_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const int i0 = tri[3 * i], i1 = tri[3 * i + 1], i2 = tri[3 * i + 2];
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo, c = lo;
-    if (i0 < 0 || i0 >= numVerts || i1 < 0 || i1 >= numVerts || i2 < 0 || i2 >= numVerts) {
+    float l[3], h[3];
+    if (!tri_box_checked(tri, numVerts, pos, i, l, h)) {
         atomicOr(&tot->err, 1u);
     } else {
-        float l[3], h[3];
-        for (int k = 0; k < 3; k++) {
-            const float a = pos[3 * i0 + k], b = pos[3 * i1 + k], d = pos[3 * i2 + k];
-            l[k] = omin(omin(a, b), d);
-            h[k] = omax(omax(a, b), d);
-        }
         lo = make_float4(l[0], l[1], l[2], 0.f);
         hi = make_float4(h[0], h[1], h[2], 0.f);
         // getCentroid (rt_common.cu:440-444): (mn + mx) * 0.5f
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_prep(int n, const int* __restrict
 }
 
 // ---- per level: bin ------------------------------------------------------------------------------------------------------
-// A bin's 8 words: count, ~ord_enc(min) x3 and ord_enc(max) x3 (both merged by max, so that zero is the identity of an empty bin), pad.
+// A bin's 8 words: count, the box's six words (box_words: merged by max, so that zero is the identity of an empty bin), pad.
 __device__ __forceinline__ int ref_bin(const float* lo, const float* hi, int a, float c)
 {
     const int m = a < 2 ? BV_PER_AXIS : BV_PLANES - 2 * BV_PER_AXIS;
@@ -151,17 +136,14 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_bin(int R, const int* __restrict_
         if (tk.binSlot >= 0) {
             const int id = refs[r];
             const float4 c = cen[id], bl = boxLo[id], bh = boxHi[id];
-            const unsigned int lw[3] = {~ord_enc(bl.x), ~ord_enc(bl.y), ~ord_enc(bl.z)};
-            const unsigned int hw[3] = {ord_enc(bh.x), ord_enc(bh.y), ord_enc(bh.z)};
+            unsigned int w[6];
+            box_words(bl, bh, w);
             unsigned int* dst = shared ? sh : slots + (size_t)tk.binSlot * BV_SLOT;
 #pragma unroll
             for (int a = 0; a < 3; a++) {
                 unsigned int* bin = dst + (a * (BV_PER_AXIS + 1) + ref_bin(tk.lo, tk.hi, a, sel4(c, a))) * 8;
                 atomicAdd(&bin[0], 1u);
-                for (int k = 0; k < 3; k++) {
-                    atomicMax(&bin[1 + k], lw[k]);
-                    atomicMax(&bin[4 + k], hw[k]);
-                }
+                atomic_max_box(bin + 1, w);
             }
         }
     }
@@ -178,20 +160,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_bin(int R, const int* __restrict_
 }
 
 // ---- per level: decide (one wave per task) -------------------------------------------------------------------------------
-__device__ __forceinline__ float box_area(const float* lo, const float* hi) { return area3(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]); }
-
-// union words -> box, with grow: fl(min - eps), fl(max + eps); an empty side keeps (FLT_MAX, -FLT_MAX)
-__device__ __forceinline__ void grow_box(int count, const unsigned int* lw, const unsigned int* hw, float eps, bool grow, float* lo,
-                                         float* hi)
-{
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float l = ord_dec(~lw[k]), h = ord_dec(hw[k]);
-        lo[k] = count ? (grow ? l - eps : l) : FLT_MAX;
-        hi[k] = count ? (grow ? h + eps : h) : -FLT_MAX;
-    }
-}
-
+// The areas here are box_area (device_prims.h): areaAABB without an invalid-box test.
 // taskTerminationCriteria (persistent_bvh.cu:245-271) over the partition; the root is never a leaf (DEVIATION, see the header)
 __device__ void finish_decision(const BvTask& tk, BvDecision& d, const BvParams& prm, BvTotals* tot)
 {
@@ -235,7 +204,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_decide(int T, const BvTask* __res
     unsigned long long key = ~0ull;
     float p = 0.f;
     int nL = 0, nR = 0;
-    unsigned int lw0[3] = {0u, 0u, 0u}, hw0[3] = {0u, 0u, 0u}, lw1[3] = {0u, 0u, 0u}, hw1[3] = {0u, 0u, 0u};
+    unsigned int w[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // the box words of child 0, then of child 1
     if (lane < BV_PLANES) {
         const int a = lane / BV_PER_AXIS, j = lane - a * BV_PER_AXIS;
         const int m = a < 2 ? BV_PER_AXIS : BV_PLANES - 2 * BV_PER_AXIS;
@@ -244,38 +213,29 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_decide(int T, const BvTask* __res
         const unsigned int* bins = slots + (size_t)tk.binSlot * BV_SLOT + a * (BV_PER_AXIS + 1) * 8;
         for (int b = 0; b <= m; b++) {
             const uint4 w0 = *(const uint4*)(bins + 8 * b), w1 = *(const uint4*)(bins + 8 * b + 4);
+            const unsigned int bw[6] = {w0.y, w0.z, w0.w, w1.x, w1.y, w1.z};
             if (b > j) {
                 nL += (int)w0.x;
-                lw0[0] = max(lw0[0], w0.y); lw0[1] = max(lw0[1], w0.z); lw0[2] = max(lw0[2], w0.w);
-                hw0[0] = max(hw0[0], w1.x); hw0[1] = max(hw0[1], w1.y); hw0[2] = max(hw0[2], w1.z);
+#pragma unroll
+                for (int k = 0; k < 6; k++) w[k] = max(w[k], bw[k]);
             } else {
                 nR += (int)w0.x;
-                lw1[0] = max(lw1[0], w0.y); lw1[1] = max(lw1[1], w0.z); lw1[2] = max(lw1[2], w0.w);
-                hw1[0] = max(hw1[0], w1.x); hw1[1] = max(hw1[1], w1.y); hw1[2] = max(hw1[2], w1.z);
+#pragma unroll
+                for (int k = 0; k < 6; k++) w[6 + k] = max(w[6 + k], bw[k]);
             }
         }
         float l0[3], h0[3], l1[3], h1[3];
-        grow_box(nL, lw0, hw0, 0.0f, false, l0, h0);   // the cost's boxes carry no epsilon
-        grow_box(nR, lw1, hw1, 0.0f, false, l1, h1);
+        words_box(nL, w, 0.0f, false, l0, h0);   // the cost's boxes carry no epsilon
+        words_box(nR, w + 6, 0.0f, false, l1, h1);
         const float s = box_area(l0, h0) * (float)nL + box_area(l1, h1) * (float)nR;
         if (isfinite(s)) key = ((unsigned long long)__float_as_uint(s + 0.0f) << 32) | (unsigned int)lane;   // -0 -> +0
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)key, off);
-        const unsigned int hi = (unsigned int)__shfl_xor((int)(unsigned int)(key >> 32), off);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        key = o < key ? o : key;
-    }
+    key = wave_min_u64(key);
     const int kb = (int)(key & 63ull);
     const int nLb = __shfl(nL, kb), nRb = __shfl(nR, kb);
     const float pb = __shfl(p, kb);
-    unsigned int w[12];
-    for (int k = 0; k < 3; k++) {
-        w[k] = (unsigned int)__shfl((int)lw0[k], kb);
-        w[3 + k] = (unsigned int)__shfl((int)hw0[k], kb);
-        w[6 + k] = (unsigned int)__shfl((int)lw1[k], kb);
-        w[9 + k] = (unsigned int)__shfl((int)hw1[k], kb);
-    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) w[k] = (unsigned int)__shfl((int)w[k], kb);
     if (lane != 0) return;
     BvDecision d;
     memset(&d, 0, sizeof(d));
@@ -289,8 +249,8 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_decide(int T, const BvTask* __res
     d.split = pb;
     d.axis = kb / BV_PER_AXIS;
     d.nL = nLb;
-    grow_box(nLb, w, w + 3, prm.eps, true, d.lo0, d.hi0);   // persistent_bvh.cu:1855-1863
-    grow_box(nRb, w + 6, w + 9, prm.eps, true, d.lo1, d.hi1);
+    words_box(nLb, w, prm.eps, true, d.lo0, d.hi0);   // persistent_bvh.cu:1855-1863
+    words_box(nRb, w + 6, prm.eps, true, d.lo1, d.hi1);
     finish_decision(tk, d, prm, tot);
     dec[t] = d;
 }
@@ -309,9 +269,9 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_median_bounds(int R, const int* _
     const int side = (r - tk.refStart) < tk.refCount / 2 ? 0 : 1;
     unsigned int* m = slots + (size_t)tk.binSlot * BV_SLOT + BV_BINS * 8 + 8 * side;
     const int id = refs[r];
-    const float4 bl = boxLo[id], bh = boxHi[id];
-    atomicMax(&m[0], ~ord_enc(bl.x)); atomicMax(&m[1], ~ord_enc(bl.y)); atomicMax(&m[2], ~ord_enc(bl.z));
-    atomicMax(&m[3], ord_enc(bh.x)); atomicMax(&m[4], ord_enc(bh.y)); atomicMax(&m[5], ord_enc(bh.z));
+    unsigned int w[6];
+    box_words(boxLo[id], boxHi[id], w);
+    atomic_max_box(m, w);
 }
 
 __global__ __launch_bounds__(BV_BLOCK) void bv_median_finish(int T, const BvTask* __restrict__ tasks, const unsigned int* __restrict__ slots,
@@ -323,8 +283,8 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_median_finish(int T, const BvTask
     if (!(d.flags & BV_MEDIAN)) return;
     const BvTask tk = tasks[t];
     const unsigned int* m = slots + (size_t)tk.binSlot * BV_SLOT + BV_BINS * 8;
-    grow_box(d.nL, m, m + 3, prm.eps, true, d.lo0, d.hi0);
-    grow_box(tk.refCount - d.nL, m + 8, m + 11, prm.eps, true, d.lo1, d.hi1);
+    words_box(d.nL, m, prm.eps, true, d.lo0, d.hi0);
+    words_box(tk.refCount - d.nL, m + 8, prm.eps, true, d.lo1, d.hi1);
     finish_decision(tk, d, prm, tot);
     dec[t] = d;
 }
@@ -341,10 +301,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_task_scan_local(int T, const BvTa
         if (d.flags & BV_LEAF) v = U4{0u, 3u * n + 1u, 0u, 0u};
         else v = U4{1u, 0u, n, (d.flags & BV_LEAF0 ? 0u : 1u) + (d.flags & BV_LEAF1 ? 0u : 1u)};
     }
-    U4 total;
-    const U4 ex = block_exclusive_scan<BV_BLOCK>(v, &total);
-    if (t < T) local[t] = ex;
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
+    scan_local_store<BV_BLOCK>(v, t < T, t, local, blockSums, blockIdx.x);
 }
 
 __device__ __forceinline__ BvTask child_task(const float* lo, const float* hi, int refStart, int refCount, int parentSlot, int binSlot)
@@ -373,25 +330,19 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_task_emit(int T, const BvTask* __
     if (d.flags & BV_LEAF) {
         const int row = rowBase + (int)g.y;
         if (row + 3 * n >= rowCap) { atomicOr(&tot->err, 4u); place[t] = BvPlace{-1, -1, -1, -1}; return; }
-        if (tk.parentSlot >= 0) nodes[tk.parentSlot] = ~row;
-        woop[row + 3 * n] = make_uint4(BV_TERM, BV_TERM, BV_TERM, BV_TERM);
-        triIndex[row + 3 * n] = 0;
+        if (tk.parentSlot >= 0) nodes[tk.parentSlot] = leaf_link(row);
+        write_leaf_terminator(woop, triIndex, row + 3 * n);
         place[t] = BvPlace{-1, -1, row, -1};
         return;
     }
     const int nodeIdx = innerBase + (int)g.x;
     if (nodeIdx >= nodeCap) { atomicOr(&tot->err, 4u); place[t] = BvPlace{-1, -1, -1, -1}; return; }
-    if (tk.parentSlot >= 0) nodes[tk.parentSlot] = 64 * nodeIdx;
-    int* nd = nodes + 16 * nodeIdx;
-    const float w[12] = {d.lo0[0], d.hi0[0], d.lo0[1], d.hi0[1], d.lo1[0], d.hi1[0], d.lo1[1], d.hi1[1],
-                         d.lo0[2], d.hi0[2], d.lo1[2], d.hi1[2]};
-    for (int k = 0; k < 12; k++) nd[k] = __float_as_int(w[k]);
-    nd[14] = (d.flags & BV_MEDIAN) ? 0 : d.axis;
-    nd[15] = 0;
+    if (tk.parentSlot >= 0) nodes[tk.parentSlot] = inner_link(nodeIdx);
+    write_inner_node(nodes, nodeIdx, d.lo0, d.hi0, d.lo1, d.hi1, (d.flags & BV_MEDIAN) ? 0 : d.axis);
     const int ct = 2 * (int)g.x, cr = (int)g.z;
     const bool leaf0 = (d.flags & BV_LEAF0) != 0, leaf1 = (d.flags & BV_LEAF1) != 0;
-    next[ct] = child_task(d.lo0, d.hi0, cr, d.nL, 16 * nodeIdx + 12, leaf0 ? -1 : (int)g.w);
-    next[ct + 1] = child_task(d.lo1, d.hi1, cr + d.nL, n - d.nL, 16 * nodeIdx + 13, leaf1 ? -1 : (int)g.w + (leaf0 ? 0 : 1));
+    next[ct] = child_task(d.lo0, d.hi0, cr, d.nL, kNodeWords * nodeIdx + kLinkWord, leaf0 ? -1 : (int)g.w);
+    next[ct + 1] = child_task(d.lo1, d.hi1, cr + d.nL, n - d.nL, kNodeWords * nodeIdx + kLinkWord + 1, leaf1 ? -1 : (int)g.w + (leaf0 ? 0 : 1));
     place[t] = BvPlace{ct, cr, -1, nodeIdx};
 }
 
@@ -414,10 +365,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_ref_scan_local(int R, const int* 
         const BvDecision d = dec[t];
         if (!(d.flags & BV_LEAF)) v = ref_neg(d, tasks[t], r, cen[refs[r]]) ? 1u : 0u;
     }
-    unsigned int total;
-    const unsigned int ex = block_exclusive_scan<BV_BLOCK>(v, &total);
-    if (r < R) local[r] = ex;
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
+    scan_local_store<BV_BLOCK>(v, r < R, r, local, blockSums, blockIdx.x);
 }
 
 __global__ __launch_bounds__(BV_BLOCK) void bv_ref_scatter(int R, const int* __restrict__ refs, const int* __restrict__ taskOf,
@@ -457,25 +405,6 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_ref_scatter(int R, const int* __r
     nextTaskOf[pl.childRef + o] = pl.childTask + side;
 }
 
-// ---- end: the leaves' Woop rows ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BV_BLOCK) void bv_emit_leaves(int n, const int* __restrict__ tri, const float* __restrict__ pos,
-                                                           const int* __restrict__ leafRow, int rowCap, float4* __restrict__ woop,
-                                                           int* __restrict__ triIndex, BvTotals* __restrict__ tot)
-{
-    const int i = blockIdx.x * BV_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int row = leafRow[i];
-    if (row < 0 || row + 2 >= rowCap) { atomicOr(&tot->err, 4u); return; }
-    float4 r0, r1, r2;
-    woop_rows(tri, pos, i, r0, r1, r2);
-    woop[row] = r0;
-    woop[row + 1] = r1;
-    woop[row + 2] = r2;
-    triIndex[row] = i;
-    triIndex[row + 1] = 0;
-    triIndex[row + 2] = 0;
-}
-
 // ---- scratch layout ------------------------------------------------------------------------------------------------------
 // Everything but the bin slots is sized by the triangle count once: references never duplicate (R <= n) and a level has at most
 // n + 1 tasks.  The bin slots come last, so that growing them keeps the rest at its offsets.
@@ -508,11 +437,9 @@ struct BvLayout {
 
 DeviceScratchPool g_bvPool;
 
-// BVHLayout_Compact child links are S32 byte offsets below the traversal sentinel 0x76543210 (CudaBVH.hpp:42-46), as for
-// ntr_lbvh_build: a tree of more inner nodes cannot be written.  Below this bound a node's words (16 * index + 15) fit int32 too, and
-// with numTris < 2^28 so do references, tasks (<= n + 1), leaf rows (< 4n + 4) and bin slots (<= n / 2 + 1): no level exceeds the
-// kernels' int32 indexing.
-constexpr int64_t BV_MAX_NODES = 0x76543200ll / 64;
+// A tree of more than kMaxNodes inner nodes (compact_bvh.h) cannot be written.  Below this bound a node's words (16 * index + 15) fit
+// int32 too, and with numTris < 2^28 so do references, tasks (<= n + 1), leaf rows (< 4n + 4) and bin slots (<= n / 2 + 1): no level
+// exceeds the kernels' int32 indexing.
 
 int bv_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, const float* sceneMin, const float* sceneMax,
              const NtrPersistentBvhParams& prm, void* d_nodes, int64_t nodeCap, void* d_woop, int64_t rowCap, int32_t* d_idx,
@@ -613,10 +540,7 @@ int bv_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
         NTR_HIP(hipStreamSynchronize(s));
         const int64_t inner = h.t.x;
         // checked before the error word: bv_task_emit writes no node at or beyond the bound and flags the level instead
-        if (innerBase + inner > BV_MAX_NODES)
-            return set_error(NTR_ERR_OVERFLOW, "ntr_persistent_bvh_build: level %d brings the tree to %lld inner nodes, more than the %lld "
-                             "that BVHLayout_Compact's 32-bit child offsets address", level, (long long)(innerBase + inner),
-                             (long long)BV_MAX_NODES);
+        if (innerBase + inner > kMaxNodes) return node_overflow_error("ntr_persistent_bvh_build", level, innerBase + inner);
         if (h.err)
             return set_error(NTR_ERR_LAYOUT, "ntr_persistent_bvh_build: internal check failed: error 0x%x at level %d", h.err, level);
         res->numLevels = level + 1;
@@ -634,8 +558,8 @@ int bv_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
         level++;
     }
     ev.mark(2);
-    bv_emit_leaves<<<nbN, BV_BLOCK, 0, s>>>(n, d_tri, d_pos, (const int*)P(lay.leafRow), (int)rowCap, (float4*)d_woop, d_idx,
-                                            (BvTotals*)P(lay.totals));
+    emit_leaf_rows<BV_BLOCK><<<nbN, BV_BLOCK, 0, s>>>(n, d_tri, d_pos, (const unsigned char*)nullptr, (const int*)P(lay.leafRow), (int)rowCap,
+                                                      (float4*)d_woop, d_idx, &((BvTotals*)P(lay.totals))->err, 4u);
     NTR_HIP(hipGetLastError());
     ev.mark(3);
     BvTotals h;
@@ -703,14 +627,12 @@ int ntr_persistent_bvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int3
         if (!std::isfinite(sceneMin[k]) || !std::isfinite(sceneMax[k]) || !(sceneMin[k] <= sceneMax[k]))
             return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_build: scene box axis %d is [%g, %g]; it must be finite with min <= max", k,
                              (double)sceneMin[k], (double)sceneMax[k]);
-    int64_t needN, needW, needI;
-    ntr_lbvh_capacity(numTris, &needN, &needW, &needI);
-    if (!d_nodes || !d_triWoop || !d_triIndex || nodesCapacity < needN || triWoopCapacity < needW || triIndexCapacity < needI)
-        return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_build: output buffers smaller than ntr_lbvh_capacity()");
+    int64_t nodeCap, rowCap;
+    if (const int rc = check_build_outputs("ntr_persistent_bvh_build", numTris, d_nodes, nodesCapacity, d_triWoop, triWoopCapacity, d_triIndex,
+                                           triIndexCapacity, &nodeCap, &rowCap))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t rowCap = std::min<int64_t>(triWoopCapacity / 16, triIndexCapacity / 4);
-    const int rc = bv_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, sceneMin, sceneMax, p, d_nodes,
-                            std::min<int64_t>(nodesCapacity / 64, BV_MAX_NODES), d_triWoop, std::min<int64_t>(rowCap, INT_MAX), d_triIndex,
+    const int rc = bv_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, sceneMin, sceneMax, p, d_nodes, nodeCap, d_triWoop, rowCap, d_triIndex,
                             result, s);
     if (rc != NTR_OK) {
         (void)hipStreamSynchronize(s);

@@ -8,13 +8,10 @@
 // pass instead of one thread's recursion.
 //
 // Shape of a pass of the optimiser:
-//   opt_topology      one thread per node slot: clears the slot's arrival counter, height and histogram word and writes
-//                     parent[child] = 2 * node + k for every inner link (as refit_topology; parent words are only believed where the
-//                     node they name links back)
-//   opt_climb<false>  one thread per child word that is a leaf link: arrives at its node with (height 0, 1 leaf link); the SECOND
-//                     arrival at a node owns it, stores the node's height (1 + max) and leaf links (sum) and arrives at the parent.
-//                     Integers only, so arrival order cannot matter.  The hand-off is refit_climb's: agent-scope stores of what the
-//                     owner will read, s_waitcnt vmcnt(0), a returning agent-scope atomic, agent-scope loads.  Nobody waits.
+//   opt_topology      one thread per node slot: the topology step of bvh_climb.h; clears the slot's height and histogram word
+//   opt_climb<false>  one thread per child word that is a leaf link: the climb of bvh_climb.h with the payload (height 0, 1 leaf
+//                     link); the owner of a node stores its height (1 + max) and leaf links (sum).  Integers only, so arrival order
+//                     cannot matter.  The layout is compact_bvh.h's; the arrival protocol is stated in bvh_climb.h and lives only there
 //   opt_histogram     one thread per slot with leafLinks >= 7 walks its parent words up to the root (only reached slots root a
 //                     treelet) and counts itself under its height
 //   opt_scan, opt_scatter  the roots into per-height lists (the scan reads the root's height on the device); then the host reads the
@@ -38,6 +35,7 @@
 #include <vector>
 
 #include "ntr_internal.h"
+#include "bvh_climb.h"
 #include "device_prims.h"
 #include "device_scratch.h"
 
@@ -50,7 +48,6 @@ constexpr int OP_FULL = (1 << OP_N) - 1;
 constexpr int OP_MAX_PASSES = 8;
 constexpr int OP_STAT_SLOTS = 64;            // the rewritten-treelet counters of a pass: a workgroup adds to slot blockIdx % 64
 constexpr int OP_HIST_LDS = 1024;            // heights below this are counted in LDS first
-constexpr unsigned int OP_TERM = 0x80000000u;
 enum : unsigned int { OP_ERR_LINK = 1u, OP_ERR_ROW = 2u };
 
 struct OpRoot {                              // what the owner of slot 0 reports; `done` stays 0 if the climb never got there
@@ -62,12 +59,6 @@ static_assert(sizeof(OpRoot) == 64, "OpRoot must be 64 bytes");
 
 DeviceScratchPool g_opPool;
 
-__device__ __forceinline__ bool op_inner(int c, int numSlots) { return c > 0 && (c & 63) == 0 && (c >> 6) < numSlots; }
-
-// word w < 12 of a node holds component j (lo.x hi.x lo.y hi.y lo.z hi.z) of child k's box
-__device__ __forceinline__ int op_word_child(int w) { return w < 8 ? (w >> 2) : ((w - 8) >> 1); }
-__device__ __forceinline__ int op_word_comp(int w) { return w < 8 ? (w & 3) : 4 + ((w - 8) & 1); }
-
 __global__ __launch_bounds__(OP_BLOCK) void opt_topology(int numSlots, const int* __restrict__ nodes, unsigned int* __restrict__ parent,
                                                          unsigned int* __restrict__ arrive, int* __restrict__ height /* or null */,
                                                          unsigned int* __restrict__ hist /* numSlots + 1 words, or null */,
@@ -77,17 +68,10 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_topology(int numSlots, const int
     if (node > numSlots) return;
     if (hist) hist[node] = 0u;
     if (node == numSlots) return;
-    arrive[node] = 0u;
     if (height) height[node] = 0;
-    const int2 link = *reinterpret_cast<const int2*>(nodes + (size_t)node * 16 + 12);
-    const int c[2] = {link.x, link.y};
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        if (op_inner(c[k], numSlots)) parent[c[k] >> 6] = 2u * (unsigned int)node + (unsigned int)k;
-        else if (c[k] > 0) bad = true;
-    }
-    if (bad) atomicOr(&root->err, OP_ERR_LINK);   // a malformed tree only
+    int kind[2];
+    topology_slot(node, numSlots, nodes, parent, arrive, kind);
+    if (kind[0] == LINK_BAD || kind[1] == LINK_BAD) atomicOr(&root->err, OP_ERR_LINK);   // a malformed tree only
 }
 
 // What a child reports to its node.  SAH: three 8-byte words (value | height, leaves | triangles, slots); else one (height | leaf links).
@@ -129,8 +113,8 @@ __device__ __forceinline__ void op_acquire(const unsigned long long* info, size_
 }
 
 // fminf / fmaxf of calcSAHNode pinned: the other operand for a NaN, else by the total order -0 < +0
-__device__ __forceinline__ float op_fmin(float a, float b) { return a != a ? b : (b != b ? a : (ord_enc(a) <= ord_enc(b) ? a : b)); }
-__device__ __forceinline__ float op_fmax(float a, float b) { return a != a ? b : (b != b ? a : (ord_enc(a) >= ord_enc(b) ? a : b)); }
+__device__ __forceinline__ float op_fmin(float a, float b) { return a != a ? b : (b != b ? a : ord_min(a, b)); }
+__device__ __forceinline__ float op_fmax(float a, float b) { return a != a ? b : (b != b ? a : ord_max(a, b)); }
 // 2 * ((dx*dy + dy*dz) + dz*dx), left to right (emitTreeKernel.cu:1374-1376); this file is compiled without contraction
 __device__ __forceinline__ float op_sah_area(float xi, float xa, float yi, float ya, float zi, float za)
 {
@@ -147,28 +131,24 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_climb(int numSlots, const int* _
     const long long g = (long long)blockIdx.x * OP_BLOCK + threadIdx.x;
     if (g >= 2ll * numSlots) return;
     int node = (int)(g >> 1), k = (int)(g & 1);
-    const int link = nodes[(size_t)node * 16 + 12 + k];
-    if (op_inner(link, numSlots)) return;        // an inner child arrives with the owner of its node
+    const int link = nodes[(size_t)node * kNodeWords + kLinkWord + k];
+    if (is_inner_link(link, numSlots)) return;   // an inner child arrives with the owner of its node
     OpInfo<SAH> mine = OpInfo<SAH>();
     mine.leafLinks = 1u;
     if (SAH && link < 0) {
         mine.leaves = 1u;
-        long long r = (long long)~link;
-        while (r < numRows && __float_as_uint(woop[r].x) != OP_TERM) {   // calcLeafs (emitTreeKernel.cu:1351-1359), inside the extent
+        long long r = (long long)leaf_row(link);
+        while (r < numRows && __float_as_uint(woop[r].x) != kLeafTerm) {   // calcLeafs (emitTreeKernel.cu:1351-1359), inside the extent
             mine.tris++;
             r += 3;
         }
         if (r >= numRows) atomicOr(&root->err, OP_ERR_ROW);
         mine.value = (float)mine.tris;
     }
-    op_publish<SAH>(info, 2 * (size_t)node + k, mine);
-    for (;;) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // what the owner will read has reached memory before the arrival is announced
-        const unsigned int old = __hip_atomic_fetch_add(&arrive[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old != 1u) return;                   // the first to arrive exits
-        asm volatile("" ::: "memory");
-        OpInfo<SAH> sib;
-        op_acquire<SAH>(info, 2 * (size_t)node + (k ^ 1), sib);
+    OpInfo<SAH> sib;
+    const auto publish = [&](int n, int ck) { op_publish<SAH>(info, 2 * (size_t)n + ck, mine); };
+    const auto acquire = [&](int n, int ck) { op_acquire<SAH>(info, 2 * (size_t)n + ck, sib); };
+    const auto merge = [&](int n, int ck) {
         OpInfo<SAH> up = OpInfo<SAH>();
         up.height = 1u + max(mine.height, sib.height);
         up.leafLinks = mine.leafLinks + sib.leafLinks;
@@ -176,32 +156,27 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_climb(int numSlots, const int* _
             up.slots = 1u + mine.slots + sib.slots;
             up.leaves = mine.leaves + sib.leaves;
             up.tris = mine.tris + sib.tris;
-            const float* nf = reinterpret_cast<const float*>(nodes + (size_t)node * 16);
+            const float* nf = reinterpret_cast<const float*>(nodes + (size_t)n * kNodeWords);
             const float4 n0 = *reinterpret_cast<const float4*>(nf), n1 = *reinterpret_cast<const float4*>(nf + 4),
                          n2 = *reinterpret_cast<const float4*>(nf + 8);
             const float pa = op_sah_area(op_fmin(n0.x, n1.x), op_fmax(n0.y, n1.y), op_fmin(n0.z, n1.z), op_fmax(n0.w, n1.w),
                                          op_fmin(n2.x, n2.z), op_fmax(n2.y, n2.w));
             const float pl = op_sah_area(n0.x, n0.y, n0.z, n0.w, n2.x, n2.y);
             const float pr = op_sah_area(n1.x, n1.y, n1.z, n1.w, n2.z, n2.w);
-            const float l = k == 0 ? mine.value : sib.value, r = k == 0 ? sib.value : mine.value;
+            const float l = ck == 0 ? mine.value : sib.value, r = ck == 0 ? sib.value : mine.value;
             up.value = (1.0f + (pl / pa) * l) + (pr / pa) * r;
         } else {
-            height[node] = (int)up.height;
-            leafLinks[node] = up.leafLinks;
+            height[n] = (int)up.height;
+            leafLinks[n] = up.leafLinks;
         }
-        if (node == 0) {                         // the root reports to no parent
+        if (n == 0) {                         // the root reports to no parent
             root->height = up.height; root->leafLinks = up.leafLinks; root->slots = up.slots; root->leaves = up.leaves;
             root->tris = up.tris; root->sah = up.value; root->done = 1u;
-            return;
         }
-        const unsigned int p = parent[node];
-        const int pn = (int)(p >> 1), pk = (int)(p & 1u);
-        if (pn >= numSlots || nodes[(size_t)pn * 16 + 12 + pk] != node * 64) return;   // no link leads here (a stale parent word)
-        node = pn;
-        k = pk;
         mine = up;
-        op_publish<SAH>(info, 2 * (size_t)node + k, mine);
-    }
+    };
+    publish(node, k);
+    climb(node, k, numSlots, nodes, parent, arrive, publish, acquire, merge);
 }
 
 // qual[slot] = the slot's height if it roots a treelet (reached, leafLinks >= 7), else 0; hist[height] counts them.
@@ -220,9 +195,8 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_histogram(int numSlots, const in
             int n = slot;
             for (int steps = 0; n != 0 && steps < numSlots; steps++) {
                 const unsigned int p = parent[n];
-                const int pn = (int)(p >> 1), pk = (int)(p & 1u);
-                if (pn >= numSlots || nodes[(size_t)pn * 16 + 12 + pk] != n * 64) break;
-                n = pn;
+                if (!parent_links_back(p, n, numSlots, nodes)) break;
+                n = (int)(p >> 1);
             }
             if (n == 0) q = h;
         }
@@ -303,9 +277,9 @@ __global__ __launch_bounds__(64) void opt_treelets(int numSlots, int* __restrict
     for (int n = 2;; n++) {
         if (lane < 12) {
             const int w = lane;
-            sBox[op_word_child(w) ? pos1 : pos0][op_word_comp(w)] = ord_enc(__int_as_float(nodes[(size_t)from * 16 + w]));
+            sBox[box_word_child(w) ? pos1 : pos0][box_word_comp(w)] = ord_enc(__int_as_float(nodes[(size_t)from * kNodeWords + w]));
         } else if (lane < 14) {
-            sLink[lane == 12 ? pos0 : pos1] = nodes[(size_t)from * 16 + lane];
+            sLink[lane == kLinkWord ? pos0 : pos1] = nodes[(size_t)from * kNodeWords + lane];
         }
         __syncthreads();
         if (n == OP_N) break;
@@ -318,7 +292,7 @@ __global__ __launch_bounds__(64) void opt_treelets(int numSlots, int* __restrict
             for (int j = 0; j < 6; j++) b[j] = sBox[lane][j];
             myArea = op_area(b);
         }
-        const unsigned long long inner = __ballot(lane < n && op_inner(myLink, numSlots));
+        const unsigned long long inner = __ballot(lane < n && is_inner_link(myLink, numSlots));
         if (!inner) return;                      // cannot happen with leafLinks >= 7 in a tree; uniform
         int cand = __ffsll((long long)inner) - 1;
         float best = __shfl(myArea, cand);
@@ -326,7 +300,7 @@ __global__ __launch_bounds__(64) void opt_treelets(int numSlots, int* __restrict
             const float a = __shfl(myArea, e);
             if (((inner >> e) & 1ull) && a > best) { best = a; cand = e; }
         }
-        from = __shfl(myLink, cand) >> 6;
+        from = inner_index(__shfl(myLink, cand));
         pos0 = cand;
         pos1 = n;
         const unsigned int bit = 1u << cand, fresh = 1u << n;
@@ -418,7 +392,7 @@ __global__ __launch_bounds__(64) void opt_treelets(int numSlots, int* __restrict
         const int slot = i == 0 ? R : sSorted[i - 1];
         int word = 0;                            // w == 14: the split word, which no kernel reads
         if (w < 12) {
-            const int q = op_word_child(w) ? o : p, j = op_word_comp(w);
+            const int q = box_word_child(w) ? o : p, j = box_word_comp(w);
             unsigned int v = (j & 1) ? 0u : 0xFFFFFFFFu;
             for (int e = 0; e < OP_N; e++)
                 if ((q >> e) & 1) v = (j & 1) ? max(v, sBox[e][j]) : min(v, sBox[e][j]);
@@ -430,10 +404,10 @@ __global__ __launch_bounds__(64) void opt_treelets(int numSlots, int* __restrict
                 word = sLink[__ffs(q | (1 << (OP_N - 1))) - 1];
             } else {
                 const int idx = w == 12 ? i + 1 : i + np;
-                word = 64 * sSorted[min(max(idx, 1), OP_N - 2) - 1];
+                word = inner_link(sSorted[min(max(idx, 1), OP_N - 2) - 1]);
             }
         }
-        nodes[(size_t)slot * 16 + w] = word;
+        nodes[(size_t)slot * kNodeWords + w] = word;
     }
 }
 
@@ -463,9 +437,7 @@ struct OpLayout {
 int check_nodes(const char* fn, const void* d_nodes, int64_t nodesBytes)
 {
     if (!d_nodes) return set_error(NTR_ERR_INVALID, "%s: null d_nodes", fn);
-    if (nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > 0x76543200ll)
-        return set_error(NTR_ERR_INVALID, "%s: nodesBytes must be a multiple of 64 in [64, 0x76543200]", fn);
-    return NTR_OK;
+    return check_nodes_bytes(fn, "nodesBytes", nodesBytes);
 }
 
 // opt_topology + opt_climb on stream s, then the root's report read back (blocks)

@@ -9,22 +9,15 @@
 // Shape: two launches, no host read-back, so the call is asynchronous and can be captured into a HIP graph.  All per-call state is
 // re-initialised by the first launch, not by a memset node (memset nodes were observed not to re-execute on a graph replay; the
 // counters of the blocking form, which is never captured, are the one exception).
-//   refit_topology   one thread per node slot: clears the slot's arrival counter and writes parent[child] = 2 * node + slot for every
-//                    inner child other than offset 0 (the root is nobody's child; a zero-filled slot no link reaches reads as "two
-//                    inner children at offset 0" and so names nobody); counts the links for the result.  Parent words are not
-//                    cleared: one is only believed where the node it names links back (a stale word of an earlier call cannot)
+//   refit_topology   one thread per node slot: the topology step of bvh_climb.h; counts the links for the result
 //   refit_climb      one thread, or a group of 4 or 8 lanes, per child slot that holds a leaf: walks the leaf's row groups to the
-//                    terminator, writes their Woop rows, folds the box, writes it into its slot of the parent's node and arrives there.  The SECOND arrival
-//                    at a node owns it: it reads the sibling's box, forms the union, writes it into the grandparent's slot and
-//                    arrives there; the first arrival exits.  Nobody waits for anybody, so no forward-progress assumption is made.
-// The hand-off crosses workgroups and XCDs (a box a thread reads was written by another CU), in the form lbvh_agglomerate_kernel uses
-// for its meeting slots: the box words another thread will read are agent-scope (write-through) stores, drained with s_waitcnt
-// vmcnt(0), then the returning agent-scope atomic on the node's counter; the owner reads the sibling's words with agent-scope loads,
-// which are served past its L1.  Every other access is to bytes that no other thread of the launch writes (link words, rows,
-// triIndex, the mesh, the parent words of the previous launch) and is a plain access.
+//                    terminator, writes their Woop rows, folds the box, writes it into its slot of the parent's node and climbs
+//                    (bvh_climb.h: the second arrival at a node forms the union and carries it to the grandparent's slot)
+// The layout is compact_bvh.h's; the arrival protocol and its memory ordering are stated in bvh_climb.h and live only there.  The
+// payload here is a child's box inside its parent's node.  Every access other than the payload's is to bytes that no other thread of
+// the launch writes (link words, rows, triIndex, the mesh, the parent words of the previous launch) and is a plain access.
 // A malformed tree (a link or row outside the extents, a triangle or vertex index out of range) is never followed: the thread sets an
-// error bit and stops, so nothing outside the caller's buffers is touched.  A node reached by more than two arrivals (not a tree) is
-// owned once (the arrival that reads 1), so the pass ends on any input.
+// error bit and stops, so nothing outside the caller's buffers is touched.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
@@ -36,6 +29,7 @@
 #include <mutex>
 
 #include "ntr_internal.h"
+#include "bvh_climb.h"
 #include "device_prims.h"
 #include "device_scratch.h"
 #include "woop_rows.h"
@@ -44,7 +38,6 @@ namespace ntr {
 namespace {
 
 constexpr int RF_BLOCK = 256;
-constexpr unsigned int RF_TERM = 0x80000000u;
 enum : unsigned int { RF_ERR_LINK = 1u, RF_ERR_ROW = 2u, RF_ERR_TRI = 4u, RF_ERR_VERTEX = 8u };
 
 // Counters of the blocking form, first block of the scratch; zeroed and read back by that form only.  A workgroup adds to the slot of
@@ -59,28 +52,24 @@ static_assert(sizeof(RfStats) == 64, "RfStats must be 64 bytes");
 
 DeviceScratchPool g_rfPool;
 
-// min / max in the total order -0 < +0 (the float-order integer encoding of bv_bin)
-__device__ __forceinline__ float rf_min(float a, float b) { return ord_enc(a) <= ord_enc(b) ? a : b; }
-__device__ __forceinline__ float rf_max(float a, float b) { return ord_enc(a) >= ord_enc(b) ? a : b; }
-
-// A child's box inside its parent's 64-byte node: words 4k .. 4k+3 = lo.x hi.x lo.y hi.y, words 8+2k, 9+2k = lo.z hi.z: three aligned
-// 8-byte granules.  Published and read at agent scope (write-through stores, loads past the L1), as agg_store_slot / agg_load_slot.
+// A child's box inside its parent's node (box_word, compact_bvh.h) is three aligned 8-byte granules: components 0-1, 2-3 and 4-5.
+// Published and read at agent scope (write-through stores, loads past the L1), as agg_store_slot / agg_load_slot.
 __device__ __forceinline__ void rf_publish_box(int* nodes, int node, int k, const float (&b)[6])
 {
-    unsigned long long* p = reinterpret_cast<unsigned long long*>(nodes + (size_t)node * 16);
+    unsigned long long* p = reinterpret_cast<unsigned long long*>(nodes + (size_t)node * kNodeWords);
     const unsigned long long w0 = (unsigned long long)__float_as_uint(b[0]) | ((unsigned long long)__float_as_uint(b[1]) << 32);
     const unsigned long long w1 = (unsigned long long)__float_as_uint(b[2]) | ((unsigned long long)__float_as_uint(b[3]) << 32);
     const unsigned long long w2 = (unsigned long long)__float_as_uint(b[4]) | ((unsigned long long)__float_as_uint(b[5]) << 32);
-    __hip_atomic_store(p + 2 * k, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(p + 2 * k + 1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(p + 4 + k, w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + box_word(k, 0) / 2, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + box_word(k, 2) / 2, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + box_word(k, 4) / 2, w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void rf_acquire_box(const int* nodes, int node, int k, float (&b)[6])
 {
-    const unsigned long long* p = reinterpret_cast<const unsigned long long*>(nodes + (size_t)node * 16);
-    const unsigned long long w0 = __hip_atomic_load(p + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long w1 = __hip_atomic_load(p + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long w2 = __hip_atomic_load(p + 4 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long* p = reinterpret_cast<const unsigned long long*>(nodes + (size_t)node * kNodeWords);
+    const unsigned long long w0 = __hip_atomic_load(p + box_word(k, 0) / 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long w1 = __hip_atomic_load(p + box_word(k, 2) / 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long w2 = __hip_atomic_load(p + box_word(k, 4) / 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     b[0] = __uint_as_float((unsigned int)w0); b[1] = __uint_as_float((unsigned int)(w0 >> 32));
     b[2] = __uint_as_float((unsigned int)w1); b[3] = __uint_as_float((unsigned int)(w1 >> 32));
     b[4] = __uint_as_float((unsigned int)w2); b[5] = __uint_as_float((unsigned int)(w2 >> 32));
@@ -93,31 +82,21 @@ __global__ __launch_bounds__(RF_BLOCK) void refit_topology(int numSlots, const i
     const int node = blockIdx.x * RF_BLOCK + threadIdx.x;
     unsigned int inner = 0, leaf = 0, err = 0;
     if (node < numSlots) {
-        arrive[node] = 0u;
-        const int2 link = *reinterpret_cast<const int2*>(nodes + (size_t)node * 16 + 12);
-        const int c[2] = {link.x, link.y};
+        int kind[2];
+        topology_slot(node, numSlots, nodes, parent, arrive, kind);
 #pragma unroll
         for (int k = 0; k < 2; k++) {
-            if (c[k] < 0) {
-                leaf++;
-            } else if (c[k] > 0) {
-                if ((c[k] & 63) != 0 || (c[k] >> 6) >= numSlots) {
-                    err |= RF_ERR_LINK;
-                } else {
-                    parent[c[k] >> 6] = 2u * (unsigned int)node + (unsigned int)k;
-                    inner++;
-                }
-            }
+            leaf += kind[k] == LINK_LEAF ? 1u : 0u;
+            inner += kind[k] == LINK_INNER ? 1u : 0u;
+            if (kind[k] == LINK_BAD) err |= RF_ERR_LINK;
         }
     }
     if (!stats) return;
     stats += blockIdx.x % RF_STAT_SLOTS;
     // one add per wave and counter
-    for (int o = 32; o > 0; o >>= 1) {
-        inner += __shfl_xor(inner, o);
-        leaf += __shfl_xor(leaf, o);
-        err |= __shfl_xor(err, o);
-    }
+    inner = wave_sum_u32(inner);
+    leaf = wave_sum_u32(leaf);
+    err = wave_or_u32(err);
     if ((threadIdx.x & 63) == 0) {
         if (inner) atomicAdd(&stats->innerLinks, inner);
         if (leaf) atomicAdd(&stats->leafLinks, leaf);
@@ -145,16 +124,16 @@ __global__ __launch_bounds__(RF_BLOCK) void refit_climb(int numSlots, int* __res
     const int g = gid / G, sub = gid % G;
     const int groupShift = (threadIdx.x & 63) & ~(G - 1);   // the group's first lane
     int node = g >> 1, k = g & 1;
-    const int link = g < 2 * numSlots ? nodes[(size_t)node * 16 + 12 + k] : 0;
+    const int link = g < 2 * numSlots ? nodes[(size_t)node * kNodeWords + kLinkWord + k] : 0;
     const bool leaf = link < 0;                  // an inner child arrives with the owner of its node; offset 0 is no child at all
     unsigned int err = 0;
     unsigned int rows = 0;
     unsigned int lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};   // ord_enc words: min / max as integers
     if (leaf) {                                  // uniform within a group, and so is the trip count of this loop
-        for (long long r0 = (long long)~link;; r0 += 3 * G) {
+        for (long long r0 = (long long)leaf_row(link);; r0 += 3 * G) {
             const long long r = r0 + 3 * sub;
             const bool inside = r < numRows;
-            const bool term = !inside || __float_as_uint(woop[r].x) == RF_TERM;
+            const bool term = !inside || __float_as_uint(woop[r].x) == kLeafTerm;
             const unsigned int terms = (unsigned int)((__ballot(term) >> groupShift) & ((1ull << G) - 1ull));
             const int first = terms ? __ffs((int)terms) - 1 : G;   // the group's lanes below `first` hold triangles
             if (sub == first) {
@@ -166,8 +145,8 @@ __global__ __launch_bounds__(RF_BLOCK) void refit_climb(int numSlots, int* __res
                 } else if (t < 0 || t >= numTris) {
                     err |= RF_ERR_TRI;
                 } else {
-                    const int i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-                    if (i0 < 0 || i0 >= numVerts || i1 < 0 || i1 >= numVerts || i2 < 0 || i2 >= numVerts) {
+                    int i0, i1, i2;
+                    if (!tri_indices_checked(tri, numVerts, t, i0, i1, i2)) {
                         err |= RF_ERR_VERTEX;
                     } else {
                         float v[9];
@@ -206,11 +185,8 @@ __global__ __launch_bounds__(RF_BLOCK) void refit_climb(int numSlots, int* __res
     }
     const unsigned int groupErr = leaf ? (unsigned int)((__ballot(err != 0) >> groupShift) & ((1ull << G) - 1ull)) : 0u;
     if (stats) {                                 // one add per workgroup and counter, by the wave that finishes its leaves last:
-        unsigned int waveRows = rows, waveErr = err;   // no barrier, nobody's climb waits for the workgroup's longest leaf
-        for (int o = 32; o > 0; o >>= 1) {       // the whole wave is here: nobody has returned yet
-            waveRows += (unsigned int)__shfl_xor((int)waveRows, o);
-            waveErr |= (unsigned int)__shfl_xor((int)waveErr, o);
-        }
+        // no barrier, nobody's climb waits for the workgroup's longest leaf; the whole wave is here: nobody has returned yet
+        const unsigned int waveRows = wave_sum_u32(rows), waveErr = wave_or_u32(err);
         if ((threadIdx.x & 63) == 0) {
             if (waveRows) atomicAdd(&sCount[0], waveRows);
             if (waveErr) atomicOr(&sCount[1], waveErr);
@@ -233,36 +209,26 @@ __global__ __launch_bounds__(RF_BLOCK) void refit_climb(int numSlots, int* __res
         }
         rf_publish_box(nodes, node, k, box);
     } else {                                     // a leaf without rows keeps its box words (nobody writes them in this launch)
-        const float* nf = reinterpret_cast<const float*>(nodes + (size_t)node * 16);
-        box[0] = nf[4 * k]; box[1] = nf[4 * k + 1]; box[2] = nf[4 * k + 2]; box[3] = nf[4 * k + 3];
-        box[4] = nf[8 + 2 * k]; box[5] = nf[9 + 2 * k];
-    }
-    for (;;) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the box (and the rows) have reached memory before the arrival is announced
-        const unsigned int old = __hip_atomic_fetch_add(&arrive[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old != 1u) return;                   // the first to arrive exits
-        asm volatile("" ::: "memory");
-        float sib[6];
-        rf_acquire_box(nodes, node, k ^ 1, sib);
+        const float* nf = reinterpret_cast<const float*>(nodes + (size_t)node * kNodeWords);
 #pragma unroll
-        for (int q = 0; q < 3; q++) {
-            box[2 * q] = rf_min(box[2 * q], sib[2 * q]);
-            box[2 * q + 1] = rf_max(box[2 * q + 1], sib[2 * q + 1]);
-        }
-        if (node == 0) {                         // the root reports to no parent
-            if (sceneBox) {
+        for (int j = 0; j < 6; j++) box[j] = nf[box_word(k, j)];
+    }
+    // the box (and the rows) have reached memory before the first arrival is announced: climb() drains them
+    float sib[6];
+    climb(
+        node, k, numSlots, nodes, parent, arrive, [&](int pn, int pk) { rf_publish_box(nodes, pn, pk, box); },
+        [&](int n, int sk) { rf_acquire_box(nodes, n, sk, sib); },
+        [&](int n, int) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                box[2 * q] = ord_min(box[2 * q], sib[2 * q]);
+                box[2 * q + 1] = ord_max(box[2 * q + 1], sib[2 * q + 1]);
+            }
+            if (n == 0 && sceneBox) {            // the root reports to no parent
                 sceneBox[0] = box[0]; sceneBox[1] = box[2]; sceneBox[2] = box[4];
                 sceneBox[3] = box[1]; sceneBox[4] = box[3]; sceneBox[5] = box[5];
             }
-            return;
-        }
-        const unsigned int p = parent[node];
-        const int pn = (int)(p >> 1), pk = (int)(p & 1u);
-        if (pn >= numSlots || nodes[(size_t)pn * 16 + 12 + pk] != node * 64) return;   // no link leads here (a stale parent word)
-        node = pn;
-        k = pk;
-        rf_publish_box(nodes, node, k, box);
-    }
+        });
 }
 
 struct RfLayout {
@@ -292,8 +258,7 @@ int ntr_bvh_refit(void* d_nodes, int64_t nodesBytes, void* d_triWoop, int64_t tr
         result->numNodes = result->numLeaves = result->numRows = result->pad = 0;
     }
     if (!d_nodes) return set_error(NTR_ERR_INVALID, "ntr_bvh_refit: null d_nodes");
-    if (nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > 0x76543200ll)
-        return set_error(NTR_ERR_INVALID, "ntr_bvh_refit: nodesBytes must be a multiple of 64 in [64, 0x76543200]");
+    if (const int rc = check_nodes_bytes("ntr_bvh_refit", "nodesBytes", nodesBytes)) return rc;
     if (!d_triWoop) return set_error(NTR_ERR_INVALID, "ntr_bvh_refit: null d_triWoop");
     if (triWoopBytes < 16 || (triWoopBytes % 16) != 0 || triWoopBytes / 16 > INT_MAX)
         return set_error(NTR_ERR_INVALID, "ntr_bvh_refit: triWoopBytes must be a positive multiple of 16 (at most 2^31 - 1 rows)");

@@ -5,6 +5,8 @@
 #include <vector>
 
 #include "ntr_internal.h"
+#include "compact_bvh.h"
+#include "device_prims.h"
 #include "device_scratch.h"
 
 namespace ntr {
@@ -40,11 +42,8 @@ __global__ __launch_bounds__(256) void bvh_validate_kernel(const float4* __restr
                               (__ballot(tiny) != 0ull ? 4u : 0u) | (__ballot(unordered) != 0ull ? 8u : 0u);
     if (bits && (threadIdx.x & 63) == 0) atomicOr(bad, bits);
     // leaf statistics (NTR_BVH_WIDE_LEAVES): number of leaves and the last leaf's offset ~ the triWoop extent
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        leaves += (unsigned int)__shfl_xor((int)leaves, off);
-        maxLeafOfs = max(maxLeafOfs, (unsigned int)__shfl_xor((int)maxLeafOfs, off));
-    }
+    leaves = wave_sum_u32(leaves);
+    maxLeafOfs = wave_max_u32(maxLeafOfs);
     // per-workgroup partials, summed on the host (thousands of waves adding to ONE word cost more than the whole pass)
     __shared__ unsigned int s_leaves[4], s_max[4];
     if ((threadIdx.x & 63) == 0) { s_leaves[threadIdx.x >> 6] = leaves; s_max[threadIdx.x >> 6] = maxLeafOfs; }
@@ -119,9 +118,8 @@ extern "C" int ntr_bvh_validate(const void* d_nodes, int64_t nodesBytes, uint32_
     using namespace ntr;
     if (!flags) return set_error(NTR_ERR_INVALID, "ntr_bvh_validate: null flags");
     *flags = 0;
-    // the same extent rule as ntr_trace_bvh: child pointers are S32 byte offsets below the sentinel 0x76543210
-    if (!d_nodes || nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > 0x76543200ll)
-        return set_error(NTR_ERR_INVALID, "ntr_bvh_validate: node buffer size must be a multiple of 64 in [64, 0x76543200]");
+    // the same extent rule as ntr_trace_bvh; no buffer is a buffer of no size
+    if (const int rc = check_nodes_bytes("ntr_bvh_validate", "node buffer size", d_nodes ? nodesBytes : 0)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n4 = nodesBytes / 16;
     int blocks = (int)((n4 + 255) / 256);

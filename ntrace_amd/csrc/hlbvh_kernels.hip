@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "ntr_internal.h"
+#include "compact_bvh.h"
 #include "device_prims.h"
 #include "device_scratch.h"
 #include "woop_rows.h"
@@ -537,10 +538,9 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
     if (hlbvhBits < 0 || hlbvhBits > 10) return set_error(NTR_ERR_INVALID, "ntr_hlbvh_build: hlbvhBits %d outside 0..10", (int)hlbvhBits);
     if (numTris < 1 || numVerts < 1 || leafSize < 1 || !d_triVtxIndex || !d_vtxPos || !sceneMin || !sceneMax)
         return set_error(NTR_ERR_INVALID, "ntr_hlbvh_build: bad geometry arguments");
-    int64_t needN, needW, needI;
-    ntr_lbvh_capacity(numTris, &needN, &needW, &needI);
-    if (!d_nodes || !d_triWoop || !d_triIndex || nodesCapacity < needN || triWoopCapacity < needW || triIndexCapacity < needI)
-        return set_error(NTR_ERR_INVALID, "ntr_hlbvh_build: output buffers smaller than ntr_lbvh_capacity()");
+    if (const int rc = check_build_outputs("ntr_hlbvh_build", numTris, d_nodes, nodesCapacity, d_triWoop, triWoopCapacity, d_triIndex,
+                                           triIndexCapacity, nullptr, nullptr))
+        return rc;
     const int n = numTris;
     if (n >= (1 << 27)) return set_error(NTR_ERR_INVALID, "ntr_hlbvh_build: at most 2^27 - 1 triangles");
     // HLBVHBuilder.cpp:44-47: hlbvhBits == 10 is buildLBVH; n <= leafSize is the LBVH's single root too (canonical)
@@ -723,7 +723,7 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
     if (h.overflow & 4u) return set_error(NTR_ERR_HIP, "ntr_hlbvh_build: a work queue left its bounds (internal error)");
     if (h.overflow) return set_error(NTR_ERR_OVERFLOW, "ntr_hlbvh_build: output buffer overflow (flags %u)", h.overflow);
     if (h.bottomCount[3 * bits] != 0) return set_error(NTR_ERR_HIP, "ntr_hlbvh_build: bottom level did not terminate (internal error)");
-    if ((unsigned long long)h.nodeCount * 64ull > 0x76543200ull)
+    if ((int64_t)h.nodeCount > kMaxNodes)
         return set_error(NTR_ERR_OVERFLOW, "ntr_hlbvh_build: %u nodes exceed what BVHLayout_Compact's 32-bit child offsets address", h.nodeCount);
     const unsigned int leafs = (unsigned int)(h.leafPtr & 0xFFFFFFFFull);
     NtrLbvhResult& r = result->lbvh;

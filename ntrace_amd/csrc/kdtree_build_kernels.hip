@@ -61,10 +61,6 @@ struct KdDecision {     // 32 B
 struct KdPlace {        // a task's global offsets after the task scan
     int childTask, childRef, leafOff, nodeIdx;
 };
-struct U4 {
-    unsigned int x, y, z, w;
-    __device__ U4 operator+(const U4& b) const { return U4{x + b.x, y + b.y, z + b.z, w + b.w}; }
-};
 struct KdTotals {       // the per-level read-back
     U4 t;               // inner nodes, leaf index entries, next level's references, non-empty leaves of this level
     unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child (never expected)
@@ -75,7 +71,6 @@ struct KdParams {
     float ci, ct, failRq, pad;
 };
 
-__device__ __forceinline__ float sel3(const float* v, int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : v[2]); }
 
 // findPlaneAABB (rt_common.cu:1007-1030): pos = mn + (mx - mn) * rpos, two roundings
 __device__ __forceinline__ float plane_pos(float mn, float mx, int kk) { return mn + (mx - mn) * kRpos[kk]; }
@@ -89,9 +84,9 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_prep(int n, const int* __restrict
     const int i = blockIdx.x * KD_BLOCK + threadIdx.x;
     unsigned int mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
     if (i < n) {
-        const int i0 = tri[3 * i], i1 = tri[3 * i + 1], i2 = tri[3 * i + 2];
+        int i0, i1, i2;
         float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, lo = r0, hi = r0;
-        if (i0 < 0 || i0 >= numVerts || i1 < 0 || i1 >= numVerts || i2 < 0 || i2 >= numVerts) {
+        if (!tri_indices_checked(tri, numVerts, i, i0, i1, i2)) {
             atomicOr(&tot->err, 1u);
         } else {
             const float v[3][3] = {{pos[3 * i0], pos[3 * i0 + 1], pos[3 * i0 + 2]},
@@ -117,11 +112,10 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_prep(int n, const int* __restrict
         refs[i] = i;
         taskOf[i] = 0;
     }
-    for (int c = 0; c < 3; c++)
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[c] = min(mn[c], (unsigned int)__shfl_xor((int)mn[c], off));
-            mx[c] = max(mx[c], (unsigned int)__shfl_xor((int)mx[c], off));
-        }
+    for (int c = 0; c < 3; c++) {
+        mn[c] = wave_min_u32(mn[c]);
+        mx[c] = wave_max_u32(mx[c]);
+    }
     if ((threadIdx.x & 63) == 0)
         for (int c = 0; c < 3; c++) {
             atomicMin(&sceneBox[c], mn[c]);
@@ -203,12 +197,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_decide(int T, const KdTask* __res
         s = aL * (float)nL + aR * (float)nR;
         if (isfinite(s)) key = ((unsigned long long)__float_as_uint(s + 0.0f) << 32) | (unsigned int)lane;   // -0 -> +0
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)key, off);
-        const unsigned int hi = (unsigned int)__shfl_xor((int)(unsigned int)(key >> 32), off);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        key = o < key ? o : key;
-    }
+    key = wave_min_u64(key);
     const int kb = (int)(key & 63ull);
     const float pb = __shfl(p, kb), sb = __shfl(s, kb);
     const int nLb = __shfl(nL, kb), nRb = __shfl(nR, kb);
@@ -245,10 +234,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_task_scan_local(int T, const KdTa
         if (d.leaf) v = U4{0u, n ? n + 1u : 0u, 0u, n ? 1u : 0u};
         else v = U4{1u, 0u, (unsigned int)d.nL + (unsigned int)d.nR, 0u};
     }
-    U4 total;
-    const U4 ex = block_exclusive_scan<KD_BLOCK>(v, &total);
-    if (t < T) local[t] = ex;
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
+    scan_local_store<KD_BLOCK>(v, t < T, t, local, blockSums, blockIdx.x);
 }
 
 __global__ __launch_bounds__(KD_BLOCK) void kd_task_emit(int T, int level, const KdTask* __restrict__ tasks,
@@ -326,10 +312,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_ref_scan_local(int R, const int* 
             v = ref_bits(d, boxLo[id], boxHi[id]);
         }
     }
-    unsigned long long total;
-    const unsigned long long ex = block_exclusive_scan<KD_BLOCK>(v, &total);
-    if (r < R) local[r] = ex;
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
+    scan_local_store<KD_BLOCK>(v, r < R, r, local, blockSums, blockIdx.x);
 }
 
 __global__ __launch_bounds__(KD_BLOCK) void kd_ref_scatter(int R, const int* __restrict__ refs, const int* __restrict__ taskOf,

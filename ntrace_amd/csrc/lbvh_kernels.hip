@@ -35,6 +35,7 @@
 #include <string.h>
 #include <mutex>
 #include "ntr_internal.h"
+#include "compact_bvh.h"
 #include "radix_sort.h"
 #include "woop_rows.h"   // woop_rows_verts / woop_rows (emitTreeKernel.cu:574-635)
 
@@ -1127,10 +1128,9 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     memset(result, 0, sizeof(*result));
     if (numTris < 1 || numVerts < 1 || leafSize < 1 || !d_triVtxIndex || !d_vtxPos || !sceneMin || !sceneMax)
         return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: bad geometry arguments");
-    int64_t needN, needW, needI;
-    ntr_lbvh_capacity(numTris, &needN, &needW, &needI);
-    if (!d_nodes || !d_triWoop || !d_triIndex || nodesCapacity < needN || triWoopCapacity < needW || triIndexCapacity < needI)
-        return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: output buffers smaller than ntr_lbvh_capacity()");
+    if (const int rc = check_build_outputs("ntr_lbvh_build", numTris, d_nodes, nodesCapacity, d_triWoop, triWoopCapacity, d_triIndex,
+                                           triIndexCapacity, nullptr, nullptr))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     const int n = numTris;
     if (n >= (1 << 28)) return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: at most 2^28 - 1 triangles");
@@ -1324,9 +1324,9 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     const unsigned int numNodes = h.nodeCount;
     const int numLevels = (int)h.maxLevel;
 
-    // Compact child references are S32 byte offsets below the sentinel 0x76543210 (CudaBVH.hpp:42-46): a tree with more nodes than that
-    // cannot be expressed (the buffers were sized for it, so nothing was written out of bounds; the references are what overflowed)
-    if ((unsigned long long)numNodes * 64ull > 0x76543200ull)
+    // a tree of more nodes than Compact's child references address (compact_bvh.h) cannot be expressed (the buffers were sized for it, so
+    // nothing was written out of bounds; the references are what overflowed)
+    if ((int64_t)numNodes > kMaxNodes)
         return set_error(NTR_ERR_OVERFLOW, "ntr_lbvh_build: %u nodes exceed what BVHLayout_Compact's 32-bit child offsets address", numNodes);
     const unsigned int leafs = (unsigned int)(h.leafPtr & 0xFFFFFFFFull);
     result->numNodes = (int32_t)numNodes;

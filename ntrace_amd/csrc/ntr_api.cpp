@@ -14,6 +14,7 @@
 
 #include "ntrace_amd.h"
 #include "ntr_internal.h"
+#include "compact_bvh.h"
 #include "device_scratch.h"
 #include "sched_state.h"
 #include "trace_kernels.h"
@@ -76,18 +77,6 @@ static const KernelInfo* find_kernel(const char* name)
     for (const KernelInfo& k : kKernels)
         if (strcmp(k.name, name) == 0) return &k;
     return nullptr;
-}
-
-static constexpr int64_t kMaxNodesBytes = 0x76543200ll;  // largest multiple of 64 below the sentinel 0x76543210
-
-// The node buffer size of the entry points that take a BVH; `fn` names the entry point in the message.  Compact child pointers are S32
-// byte offsets and 0x76543210 is the traversal's stack sentinel (EntrypointSentinel, CudaTracerKernels.hpp:38): a node at or beyond that
-// offset cannot be addressed.
-static int check_nodes_bytes(const char* fn, int64_t nodesBytes)
-{
-    if (nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > kMaxNodesBytes)
-        return set_error(NTR_ERR_INVALID, "%s: node buffer size must be a multiple of 64 in [64, 0x76543200]", fn);
-    return NTR_OK;
 }
 
 // The batch as the launch plan sees it (trace_plan.h): for a launch (trace_impl) and for the CPU tier's query (ntr_trace_plan) alike.
@@ -284,7 +273,7 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
     if (!d_rays || !d_results) return set_error(NTR_ERR_INVALID, "ntr_trace_bvh: null ray/result buffer");
     // The sizes play the role of the reference's texref extents (setTexRef(..., size),
     // CudaBVHTracer.cpp:142-150); buffer descriptors address at most 4 GiB.
-    int rc = check_nodes_bytes("ntr_trace_bvh", nodesBytes);
+    int rc = check_nodes_bytes("ntr_trace_bvh", "node buffer size", nodesBytes);
     if (rc != NTR_OK) return rc;
     if (triWoopBytes < 16 || (triWoopBytes % 16) != 0 || triWoopBytes > 0xFFFFFFFFll)
         return set_error(NTR_ERR_INVALID, "ntr_trace_bvh: triWoop buffer size must be a multiple of 16 in [16, 4 GiB)");
@@ -529,7 +518,7 @@ int ntr_trace_status(void* stream, uint32_t* statusBits)
 // The current device's top-of-tree table for the node buffer of a prediction query (`fn` names the query in messages).
 static int query_table(const char* fn, const void* d_nodes, int64_t nodesBytes, hipStream_t s, DeviceState** ds, TopTable** t)
 {
-    int rc = check_nodes_bytes(fn, nodesBytes);
+    int rc = check_nodes_bytes(fn, "node buffer size", nodesBytes);
     if (rc == NTR_OK) rc = current_device_state(ds, "hipGetDevice(&dev)");
     if (rc == NTR_OK) rc = top_table_get(*ds, d_nodes, nodesBytes, s, false, t);
     return rc;
@@ -614,7 +603,7 @@ int ntr_bvh_leaf_depths(const void* d_nodes, int64_t nodesBytes, const void* d_t
                         int32_t numTris, int32_t* d_depthByTri, int32_t* maxDepth, void* stream)
 {
     if (maxDepth) *maxDepth = 0;
-    if (!d_nodes || nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > 0x76543200ll || !d_triWoop || triWoopBytes < 16 || !d_triIndex ||
+    if (!d_nodes || nodesBytes < 64 || (nodesBytes % 64) != 0 || nodesBytes > kMaxNodesBytes || !d_triWoop || triWoopBytes < 16 || !d_triIndex ||
         numTris < 1 || !d_depthByTri)
         return set_error(NTR_ERR_INVALID, "ntr_bvh_leaf_depths: bad argument");
     hipStream_t s = (hipStream_t)stream;

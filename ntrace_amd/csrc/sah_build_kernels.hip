@@ -19,7 +19,7 @@
 //                   sw_task_emit: inner nodes, parent links, leaf terminators, the next level's tasks
 //                   sw_ref_scan_local + scan_block_sums + sw_ref_scatter: per axis each task's child 0 ranks, then the stable
 //                     partition into the other buffer; the leaf row of every triangle of a task that became a leaf
-//   end             sw_emit_leaves: every live triangle's three Woop rows (woop_rows.h) and its triIndex entries at its leaf row
+//   end             emit_leaf_rows (device_prims.h): every live triangle's three Woop rows and its triIndex entries at its leaf row
 // Box unions are exact, so any grouping of the scans gives the host's areas; every cost expression keeps the spec's order of
 // operations (the library is compiled without contraction).  The host reads one 32-byte record per level.
 #include <hip/hip_runtime.h>
@@ -33,10 +33,10 @@
 #include <chrono>
 
 #include "ntr_internal.h"
+#include "compact_bvh.h"
 #include "device_prims.h"
 #include "device_scratch.h"
 #include "radix_sort.h"
-#include "woop_rows.h"
 
 namespace ntr {
 namespace {
@@ -45,7 +45,6 @@ constexpr int SW_BLOCK = 256;                 // per-task and per-triangle kerne
 constexpr int SW_PB = 512;                    // per-position kernels: fewer workgroup aggregates for the one workgroup that carries them
 constexpr int SW_SUMS = 1024;
 constexpr int SW_MAX_DEPTH = 64;              // SAHBVHBuilder.hpp MaxDepth
-constexpr unsigned int SW_TERM = 0x80000000u;
 constexpr int SW_SORT_ITEMS = 8;
 constexpr int SW_HIST_BLOCKS = 512;
 constexpr int SW_SEARCH = -2, SW_INNER = -1;  // task states; >= 0: a leaf listed by that axis' sequence
@@ -57,17 +56,13 @@ struct SwTask {         // 40 B
 struct SwDecision { int state, axis, numLeft, pad; };
 struct SwPlace { int childTask, row, nodeIdx, pad; };
 struct SwCost { float leafSah, nodeSah; };
-struct U4 {
-    unsigned int x, y, z, w;
-    __device__ U4 operator+(const U4& b) const { return U4{x + b.x, y + b.y, z + b.z, w + b.w}; }
-};
 struct SwTotals {       // the per-level read-back
     U4 t;               // x: inner nodes of the level, y: Woop rows of its leaves
     unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child or the sort's chained scan gave up,
                         // bit 2: a node or row beyond the caller's capacity
     unsigned int live, pad[2];
 };
-// A box as six words merged by integer max: ~ord_enc(min) x3, ord_enc(max) x3; all zero is the empty box.  flag: a segment starts here.
+// w: a box as six words merged by integer max (box_words, device_prims.h).  flag: a segment starts here.
 struct SwSeg {
     unsigned int w[6], flag, pad;
 };
@@ -81,15 +76,7 @@ __device__ __forceinline__ SwSeg seg_join(const SwSeg& a /* earlier */, const Sw
     r.pad = 0u;
     return r;
 }
-__device__ __forceinline__ SwSeg seg_zero()
-{
-    SwSeg r;
-#pragma unroll
-    for (int k = 0; k < 6; k++) r.w[k] = 0u;
-    r.flag = 0u;
-    r.pad = 0u;
-    return r;
-}
+__device__ __forceinline__ SwSeg seg_zero() { return SwSeg{}; }
 
 // Exclusive segmented scan over a workgroup: lane shuffles inside a wave, the waves' joins through LDS (sh[THREADS / 64]); *total is
 // the join of all values.  Every thread of the workgroup calls it.
@@ -129,51 +116,9 @@ __device__ SwSeg seg_block_exclusive(const SwSeg& v, SwSeg* total, SwSeg* sh)
     return seg_join(before, ex);
 }
 
-// min / max in the total order -0 < +0
-__device__ __forceinline__ float omin(float a, float b) { return ord_enc(a) <= ord_enc(b) ? a : b; }
-__device__ __forceinline__ float omax(float a, float b) { return ord_enc(a) >= ord_enc(b) ? a : b; }
 __device__ __forceinline__ float fw_min(float a, float b) { return a < b ? a : b; }   // FW::min
 __device__ __forceinline__ float fw_max(float a, float b) { return a > b ? a : b; }
-
-// AABB::area: 0 for an invalid box
-__device__ __forceinline__ float box_area(const float* lo, const float* hi)
-{
-    if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) return 0.0f;
-    return area3(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
-}
-__device__ __forceinline__ float words_area(const unsigned int* w)
-{
-    const float lo[3] = {ord_dec(~w[0]), ord_dec(~w[1]), ord_dec(~w[2])};
-    const float hi[3] = {ord_dec(w[3]), ord_dec(w[4]), ord_dec(w[5])};
-    return box_area(lo, hi);
-}
-__device__ __forceinline__ void box_words(const float4& lo, const float4& hi, unsigned int* w)
-{
-    w[0] = ~ord_enc(lo.x); w[1] = ~ord_enc(lo.y); w[2] = ~ord_enc(lo.z);
-    w[3] = ord_enc(hi.x); w[4] = ord_enc(hi.y); w[5] = ord_enc(hi.z);
-}
-__device__ __forceinline__ unsigned int wave_max_u32(unsigned int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned int)__shfl_xor((int)v, off));
-    return v;
-}
-__device__ __forceinline__ unsigned int wave_min_u32(unsigned int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = min(v, (unsigned int)__shfl_xor((int)v, off));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)v, off);
-        const unsigned int hi = (unsigned int)__shfl_xor((int)(unsigned int)(v >> 32), off);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
-// every lane of the wave holds the same g (all 64 lanes call it)
-__device__ __forceinline__ bool wave_uniform(int g) { return __all(g == __shfl(g, 0)) != 0; }
+// The areas here are box_area_valid / words_area (device_prims.h): AABB::area, 0 for an invalid box.
 
 // ---- once per build ---------------------------------------------------------------------------------------------------
 // rootWords[6]: the union of every triangle's box, the dropped ones too (SAHBVHBuilder.cpp run(), reference :70-84)
@@ -185,19 +130,13 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_prep(int n, const int* __restrict
     const int i = blockIdx.x * SW_BLOCK + threadIdx.x;
     unsigned int w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     if (i < n) {
-        const int i0 = tri[3 * i], i1 = tri[3 * i + 1], i2 = tri[3 * i + 2];
         float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
         bool live = false;
-        if (i0 < 0 || i0 >= numVerts || i1 < 0 || i1 >= numVerts || i2 < 0 || i2 >= numVerts) {
+        float l[3], h[3];
+        if (!tri_box_checked(tri, numVerts, pos, i, l, h)) {
             atomicOr(&tot->err, 1u);
         } else {
-            float l[3], h[3], sz[3];
-            for (int k = 0; k < 3; k++) {
-                const float a = pos[3 * i0 + k], b = pos[3 * i1 + k], d = pos[3 * i2 + k];
-                l[k] = omin(omin(a, b), d);
-                h[k] = omax(omax(a, b), d);
-                sz[k] = h[k] - l[k];
-            }
+            const float sz[3] = {h[0] - l[0], h[1] - l[1], h[2] - l[2]};
             lo = make_float4(l[0], l[1], l[2], 0.f);
             hi = make_float4(h[0], h[1], h[2], 0.f);
             // reference :141-151: a negative extent, or at most one non-zero extent
@@ -222,10 +161,7 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_live_scan_local(int n, const unsi
 {
     const int i = blockIdx.x * SW_BLOCK + threadIdx.x;
     const unsigned int v = i < n ? (unsigned int)liveFlag[i] : 0u;
-    unsigned int total;
-    const unsigned int ex = block_exclusive_scan<SW_BLOCK>(v, &total);
-    if (i < n) local[i] = ex;
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
+    scan_local_store<SW_BLOCK>(v, i < n, i, local, blockSums, blockIdx.x);
 }
 
 // the live triangles in ascending id; key on axis d = fl(min[d] + max[d]), as ord_enc(key + 0.0f): -0 and +0 sort as equal
@@ -271,10 +207,7 @@ __global__ void sw_root(const unsigned int* __restrict__ rootWords, const SwTota
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     SwTask r;
-    for (int k = 0; k < 3; k++) {
-        r.lo[k] = ord_dec(~rootWords[k]);
-        r.hi[k] = ord_dec(rootWords[3 + k]);
-    }
+    words_box(1, rootWords, 0.0f, false, r.lo, r.hi);
     r.begin = 0;
     r.end = (int)tot->live;
     r.parentSlot = -1;
@@ -295,7 +228,7 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_task_begin(int T, const SwTask* _
     // reference :155-156: small enough or too deep; the root is never a leaf
     const bool leaf = (level != 0 && m <= minLeaf) || level >= SW_MAX_DEPTH;
     dec[t] = SwDecision{leaf ? tk.arranged : SW_SEARCH, 0, 0, 0};
-    const float a = box_area(tk.lo, tk.hi);
+    const float a = box_area_valid(tk.lo, tk.hi);
     cost[t] = SwCost{a * (float)m, a * 2.0f};   // area * triCost(m), area * nodeCost(2) with Platform("GPU")
     minSah[t] = 0xFFFFFFFFu;
     minKey[t] = ~0ull;
@@ -403,12 +336,7 @@ __global__ __launch_bounds__(SW_PB) void sw_sah(int P, int cap, const int* __res
         }
         sahOut[(size_t)d * cap + p] = sah;
     }
-    if (wave_uniform(g)) {
-        const unsigned int m = wave_min_u32(enc);
-        if (g >= 0 && (threadIdx.x & 63) == 0) atomicMin(&minSah[g], m);
-    } else if (g >= 0) {
-        atomicMin(&minSah[g], enc);
-    }
+    wave_grouped_atomic(g, enc, wave_min_u32, [&](int t, unsigned int v) { atomicMin(&minSah[t], v); });
 }
 
 // grid (nb, 3): the lowest (balance, axis, i) among the positions that hold the task's lowest sah
@@ -434,12 +362,7 @@ __global__ __launch_bounds__(SW_PB) void sw_pick(int P, int cap, const int* __re
             }
         }
     }
-    if (wave_uniform(g)) {
-        const unsigned long long m = wave_min_u64(key);
-        if (g >= 0 && (threadIdx.x & 63) == 0) atomicMin(&minKey[g], m);
-    } else if (g >= 0) {
-        atomicMin(&minKey[g], key);
-    }
+    wave_grouped_atomic(g, key, wave_min_u64, [&](int t, unsigned long long v) { atomicMin(&minKey[t], v); });
 }
 
 // ---- per level: decisions, task scan, emit --------------------------------------------------------------------------------
@@ -467,10 +390,7 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_decide_scan_local(int T, const Sw
         }
         v = d.state >= 0 ? U4{0u, 3u * (unsigned int)m + 1u, 0u, 0u} : U4{1u, 0u, 0u, 0u};
     }
-    U4 total;
-    const U4 ex = block_exclusive_scan<SW_BLOCK>(v, &total);
-    if (t < T) local[t] = ex;
-    if (threadIdx.x == 0) blockSums[blockIdx.x] = total;
+    scan_local_store<SW_BLOCK>(v, t < T, t, local, blockSums, blockIdx.x);
 }
 
 // the side of every triangle of a split task (1: child 0) and the children's boxes: childBox[t][child][6]
@@ -495,25 +415,15 @@ __global__ __launch_bounds__(SW_PB) void sw_mark(int P, int cap, const int* __re
             }
         }
     }
-    if (wave_uniform(g)) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) {
-            const unsigned int m = wave_max_u32(w[k]);
-            if (g >= 0 && (threadIdx.x & 63) == 0) atomicMax(&childBox[(size_t)g * 6 + k], m);
-        }
-    } else if (g >= 0) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) atomicMax(&childBox[(size_t)g * 6 + k], w[k]);
-    }
+    for (int k = 0; k < 6; k++)
+        wave_grouped_atomic(g, w[k], wave_max_u32, [&](int c, unsigned int v) { atomicMax(&childBox[(size_t)c * 6 + k], v); });
 }
 
 __device__ __forceinline__ SwTask child_task(const unsigned int* w, int begin, int end, int parentSlot, int arranged)
 {
     SwTask c;
-    for (int k = 0; k < 3; k++) {   // an empty child keeps AABB's initial box
-        c.lo[k] = end > begin ? ord_dec(~w[k]) : FLT_MAX;
-        c.hi[k] = end > begin ? ord_dec(w[3 + k]) : -FLT_MAX;
-    }
+    words_box(end - begin, w, 0.0f, false, c.lo, c.hi);   // an empty child keeps AABB's initial box
     c.begin = begin;
     c.end = end;
     c.parentSlot = parentSlot;
@@ -537,25 +447,20 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_task_emit(int T, const SwTask* __
     if (d.state >= 0) {
         const long long row = (long long)rowBase + g.y;
         if (row + 3ll * m >= (long long)rowCap) { atomicOr(&tot->err, 4u); place[t] = SwPlace{-1, -1, -1, 0}; return; }
-        if (tk.parentSlot >= 0) nodes[tk.parentSlot] = ~(int)row;
-        woop[row + 3 * m] = make_uint4(SW_TERM, SW_TERM, SW_TERM, SW_TERM);
-        triIndex[row + 3 * m] = 0;
+        if (tk.parentSlot >= 0) nodes[tk.parentSlot] = leaf_link((int)row);
+        write_leaf_terminator(woop, triIndex, row + 3 * m);
         place[t] = SwPlace{-1, (int)row, -1, 0};
         return;
     }
     const long long nodeIdx = (long long)innerBase + g.x;
     if (nodeIdx >= (long long)nodeCap) { atomicOr(&tot->err, 4u); place[t] = SwPlace{-1, -1, -1, 0}; return; }
-    if (tk.parentSlot >= 0) nodes[tk.parentSlot] = 64 * (int)nodeIdx;
+    if (tk.parentSlot >= 0) nodes[tk.parentSlot] = inner_link((int)nodeIdx);
     const int ct = 2 * (int)g.x;
     const int mid = tk.begin + d.numLeft;
-    const SwTask c0 = child_task(childBox + (size_t)t * 12, tk.begin, mid, 16 * (int)nodeIdx + 12, d.axis);
-    const SwTask c1 = child_task(childBox + (size_t)t * 12 + 6, mid, tk.end, 16 * (int)nodeIdx + 13, d.axis);
-    int* nd = nodes + 16 * nodeIdx;
-    const float w[12] = {c0.lo[0], c0.hi[0], c0.lo[1], c0.hi[1], c1.lo[0], c1.hi[0], c1.lo[1], c1.hi[1],
-                         c0.lo[2], c0.hi[2], c1.lo[2], c1.hi[2]};
-    for (int k = 0; k < 12; k++) nd[k] = __float_as_int(w[k]);
-    nd[14] = d.axis;   // SplitInfo(axis, SAH, false).getBitCode(); the default split's axis 0 without a winner
-    nd[15] = 0;
+    const SwTask c0 = child_task(childBox + (size_t)t * 12, tk.begin, mid, kNodeWords * (int)nodeIdx + kLinkWord, d.axis);
+    const SwTask c1 = child_task(childBox + (size_t)t * 12 + 6, mid, tk.end, kNodeWords * (int)nodeIdx + kLinkWord + 1, d.axis);
+    // the split word: SplitInfo(axis, SAH, false).getBitCode(); the default split's axis 0 without a winner
+    write_inner_node(nodes, nodeIdx, c0.lo, c0.hi, c1.lo, c1.hi, d.axis);
     next[ct] = c0;
     next[ct + 1] = c1;
     place[t] = SwPlace{ct, -1, (int)nodeIdx, 0};
@@ -575,10 +480,7 @@ __global__ __launch_bounds__(SW_PB) void sw_ref_scan_local(int P, int cap, const
         const int t = taskOf[p];
         if (t >= 0 && dec[t].state == SW_INNER) v = side[order[(size_t)d * cap + p]];
     }
-    unsigned int total;
-    const unsigned int ex = block_exclusive_scan<SW_PB>(v, &total);
-    if (p < P) local[(size_t)d * cap + p] = ex;
-    if (threadIdx.x == 0) blockSums[d * gridDim.x + blockIdx.x] = total;
+    scan_local_store<SW_PB>(v, p < P, (size_t)d * cap + p, local, blockSums, d * gridDim.x + blockIdx.x);
 }
 
 // grid (nb, 3): stable partition of every split task's range on every axis (the identity on the winning axis); a leaf's triangles get
@@ -622,26 +524,6 @@ __global__ __launch_bounds__(SW_PB) void sw_ref_scatter(int P, int cap, const in
         if (o < dc.numLeft || o >= m) { atomicOr(&tot->err, 2u); return; }
     }
     nextOrder[(size_t)d * cap + tk.begin + o] = id;
-}
-
-// ---- end: the leaves' Woop rows ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SW_BLOCK) void sw_emit_leaves(int n, const int* __restrict__ tri, const float* __restrict__ pos,
-                                                           const unsigned char* __restrict__ liveFlag, const int* __restrict__ leafRow,
-                                                           int rowCap, float4* __restrict__ woop, int* __restrict__ triIndex,
-                                                           SwTotals* __restrict__ tot)
-{
-    const int i = blockIdx.x * SW_BLOCK + threadIdx.x;
-    if (i >= n || !liveFlag[i]) return;
-    const int row = leafRow[i];
-    if (row < 0 || row + 2 >= rowCap) { atomicOr(&tot->err, 2u); return; }
-    float4 r0, r1, r2;
-    woop_rows(tri, pos, i, r0, r1, r2);
-    woop[row] = r0;
-    woop[row + 1] = r1;
-    woop[row + 2] = r2;
-    triIndex[row] = i;
-    triIndex[row + 1] = 0;
-    triIndex[row + 2] = 0;
 }
 
 // ---- scratch layout ------------------------------------------------------------------------------------------------------
@@ -691,9 +573,6 @@ struct SwLayout {
 };
 
 DeviceScratchPool g_swPool;
-
-// as bvh_build_kernels.hip: Compact child links are S32 byte offsets below the traversal sentinel 0x76543210
-constexpr int64_t SW_MAX_NODES = 0x76543200ll / 64;
 
 int sw_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, int minLeaf, int maxLeaf, void* d_nodes, int64_t nodeCap,
              void* d_woop, int64_t rowCap, int32_t* d_idx, NtrSahDeviceResult* res, hipStream_t s)
@@ -816,9 +695,7 @@ int sw_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
         NTR_HIP(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
         NTR_HIP(hipStreamSynchronize(s));
         const int64_t inner = h.t.x;
-        if (innerBase + inner > SW_MAX_NODES)
-            return set_error(NTR_ERR_OVERFLOW, "ntr_sah_device_build: level %d brings the tree to %lld inner nodes, more than the %lld that "
-                             "BVHLayout_Compact's 32-bit child offsets address", level, (long long)(innerBase + inner), (long long)SW_MAX_NODES);
+        if (innerBase + inner > kMaxNodes) return node_overflow_error("ntr_sah_device_build", level, innerBase + inner);
         if (h.err & 4u)
             return set_error(NTR_ERR_OVERFLOW, "ntr_sah_device_build: level %d does not fit the output buffers (%lld inner nodes, %lld rows so "
                              "far): splits without a winner chain nodes beyond ntr_lbvh_capacity()", level, (long long)(innerBase + inner),
@@ -835,7 +712,8 @@ int sw_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
         level++;
     }
     ev.mark(3);
-    sw_emit_leaves<<<nbN, SW_BLOCK, 0, s>>>(n, d_tri, d_pos, liveFlag, (const int*)P_(lay.leafRow), (int)rowCap, (float4*)d_woop, d_idx, tot);
+    emit_leaf_rows<SW_BLOCK><<<nbN, SW_BLOCK, 0, s>>>(n, d_tri, d_pos, liveFlag, (const int*)P_(lay.leafRow), (int)rowCap, (float4*)d_woop, d_idx,
+                                                      &tot->err, 2u);
     NTR_HIP(hipGetLastError());
     ev.mark(4);
     unsigned int sortErr = 0;
@@ -877,14 +755,12 @@ int ntr_sah_device_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t 
     if (minLeafSize < 1 || maxLeafSize < minLeafSize)
         return set_error(NTR_ERR_INVALID, "ntr_sah_device_build: leaf preferences (%d, %d): 1 <= minLeafSize <= maxLeafSize", (int)minLeafSize,
                          (int)maxLeafSize);
-    int64_t needN, needW, needI;
-    ntr_lbvh_capacity(numTris, &needN, &needW, &needI);
-    if (!d_nodes || !d_triWoop || !d_triIndex || nodesCapacity < needN || triWoopCapacity < needW || triIndexCapacity < needI)
-        return set_error(NTR_ERR_INVALID, "ntr_sah_device_build: output buffers smaller than ntr_lbvh_capacity()");
+    int64_t nodeCap, rowCap;
+    if (const int rc = check_build_outputs("ntr_sah_device_build", numTris, d_nodes, nodesCapacity, d_triWoop, triWoopCapacity, d_triIndex,
+                                           triIndexCapacity, &nodeCap, &rowCap))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t rowCap = std::min<int64_t>(triWoopCapacity / 16, triIndexCapacity / 4);
-    const int rc = sw_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, minLeafSize, maxLeafSize, d_nodes,
-                            std::min<int64_t>(nodesCapacity / 64, SW_MAX_NODES), d_triWoop, std::min<int64_t>(rowCap, INT_MAX), d_triIndex,
+    const int rc = sw_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, minLeafSize, maxLeafSize, d_nodes, nodeCap, d_triWoop, rowCap, d_triIndex,
                             result, s);
     if (rc != NTR_OK) {
         (void)hipStreamSynchronize(s);
