@@ -298,6 +298,9 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
     p.numHeads = pl.numHeads; p.chunk = pl.chunk; p.fetchThreshold = pl.fetchThreshold; p.wholeWave = pl.wholeWave; p.prefetchAfter = pl.prefetchAfter;
     p.flatFetch = pl.flatFetch; p.uniformPrologue = pl.uniformPrologue; p.splitSlice = pl.splitSlice; p.leafSwitchBelow = pl.leafSwitchBelow;
     p.octant = pl.octant; p.poolKConst = pl.poolKConst;
+    // (not part of the plan: it changes no launch shape)  1: any-hit launches -- short occlusion rays, where four prologue steps in five are
+    // certain; the closest-hit launch of a camera batch finds one step in eight certain and lost 1 % to asking (EXPERIMENTS.md); 2: every launch
+    p.certainSteps = (tun.certainSteps >= 2 || (tun.certainSteps == 1 && anyHit)) ? 1 : 0;
     if (stats) NTR_HIP(hipMemsetAsync(ds->stats, 0, 4 * sizeof(unsigned long long), s));
 
     rc = bind_trace(ds, tun, pl, bd.capturing, nodesBytes, s, hint, &L);
@@ -333,6 +336,7 @@ static void tunables_load_locked()
     t.octant = env_int("NTR_TRACE_OCTANT", 1);
     t.flatFetch = env_int("NTR_TRACE_FLAT_FETCH", 1);             // unified-step loop: one group of global loads per iteration (0 = two masked groups of range-checked buffer loads)
     t.uniformPrologue = env_int("NTR_TRACE_UNIFORM_PROLOGUE", 1);  // per-ray kernels: scalar node fetches while the lanes of a fresh wave all hold the same inner node
+    t.certainSteps = env_int("NTR_TRACE_CERTAIN_STEPS", 1);   // per-ray kernels, in the uniform prologue: steps that comparisons settle for every live lane skip the exact slab test (1 = any-hit launches, 2 = every launch, 0 = off)
     t.splitSlice = env_int("NTR_TRACE_SPLIT_SLICE", 8);   // persistent kernels, unified-step loop: once the pool is dry, lanes without a ray take over stack entries of the wave's live rays; looked at every N steps (0 = off)
     t.wholeWave = env_int("NTR_TRACE_WHOLE_WAVE", 1);      // kepler_dynamic_fetch: waves start in whole-wave mode and switch to single-lane refills per wave (0 = dynamic fetch from the start, as until round 5)
     t.prefetchAfter = env_int("NTR_TRACE_PREFETCH_AFTER", 8);   // persistent kernels: iterations into a chunk after which a wave posts the dequeue of its next one (-1 = never)

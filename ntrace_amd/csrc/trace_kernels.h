@@ -70,6 +70,9 @@ struct TraceParams {
     int32_t octant;          // per-ray kernel: specialise the slab test for waves whose rays share their direction signs
     int32_t flatFetch;       // unified-step loop: one group of global loads for nodes and triangles (needs both extents >= 64 bytes)
     int32_t uniformPrologue; // per-ray kernels, unified-step loop: scalar node fetches while every live lane of the wave holds the same inner node
+    int32_t certainSteps;    // per-ray kernels, in that prologue: a step whose outcome plain comparisons settle for every live lane (origin inside one child
+                             // box, the sibling out of the ray's reach) skips the exact slab test; needs NTR_BVH_ORDERED and tmin == 0 (trace_kernels.hip).  Set per launch from
+                             // NTR_TRACE_CERTAIN_STEPS: 1 (default) any-hit launches, 2 every launch, 0 none
     int32_t splitSlice;      // persistent kernels, unified-step loop: once the pool is dry, idle lanes take over stack entries of the wave's
                              // live rays; the lanes are looked at every splitSlice steps (trace_split.h); 0 = off
     const unsigned int* order;     // per-ray kernel: workgroup i traces ray block order[i] (null = identity); persistent kernels: the pool
