@@ -695,6 +695,47 @@ typedef struct NtrBvhSahResult {
 NTR_API int ntr_bvh_sah_cost(const void* d_nodes, int64_t nodesBytes, const void* d_triWoop, int64_t triWoopBytes,
                              NtrBvhSahResult* result, void* stream);
 
+/* On-device renumbering: copy a BVHLayout_Compact tree, whatever built, refitted or restructured it, into the node and row order of
+ * the host builder (CudaBVH::createCompact, CudaBVH.cpp:594-652): a stack holding slot 0; pop a slot and, for child 0 then child 1, an
+ * inner child takes the next node slot and is pushed, a leaf child takes the next rows.  So siblings share a 128-byte line, a node's
+ * direct leaves precede everything below it, and a subtree is contiguous (child 1's before child 0's).
+ * (csrc/bvh_reorder_kernels.hip).  EXTENSION without a reference counterpart as a pass of its own: the rule is pinned by the numpy
+ * spec tests/np_bvh_reorder.py (its docstring is the normative text).  Out of place and deterministic; the input tree is only read.
+ *   written      d_outNodes[0, 64 * numNodes): node v at its new slot, words 0-11, 14 and 15 unchanged, words 12 and 13 the new links
+ *                (64 * new slot, ~new row, or 0); d_outTriWoop[0, 16 * numRows) and d_outTriIndex[0, 4 * numRows): for every leaf
+ *                link its own copy, bit for bit, of the leaf's rows (row ~link + 3j up to the first whose x word is 0x80000000, that
+ *                terminator included; only a triangle's first row is tested) and of the triIndex words beside them.  A leaf two
+ *                links name is copied twice
+ *   not written  everything beyond those extents; node slots no link reaches and rows no reached leaf link names are dropped
+ *   errors       a child link > 0 that names no slot of the buffer is copied unchanged, and a leaf without a terminator inside
+ *                d_triWoop is emitted as a lone terminator row (so the output stays traceable); either makes the call return
+ *                NTR_ERR_LAYOUT after the work.  Links that form no tree under slot 0 (a cycle, a slot named twice): NTR_ERR_LAYOUT,
+ *                nothing written.  NTR_ERR_OVERFLOW, nothing written: the tree has more nodes or rows (the counts saturate) than the
+ *                output capacities, 31 019 208 nodes or 2^31 - 1 rows hold; result then still carries the counts and extents.
+ *                Capacities equal to the input extents always suffice for a tree whose leaf links name distinct leaves
+ * The call BLOCKS and makes one read-back (the totals and the error word) between the placement and the copies, so it cannot be
+ * captured into a HIP graph (NTR_ERR_INVALID on a capturing stream).  It ends on any input: every loop is bounded and no workgroup
+ * waits for another.  Scratch (52 B per node slot and 16 KB of counters) comes from a per-device grow-only pool that
+ * ntr_lbvh_release_workspace returns.  One reorder, optimise or refit per device at a time.
+ * Afterwards ntr_bvh_validate flags, ntr_bvh_sah_cost and ntr_bvh_leaf_depths of the output equal the input's (the tree is the same);
+ * the top-of-tree table is the output buffer's own, so the caller validates the new buffer before a flagged trace.
+ * NTR_ERR_INVALID (before any device work): a null pointer (result included), nodesBytes not a multiple of 64 in [64, 0x76543200],
+ * triWoopBytes not a positive multiple of 16, triIndexBytes * 4 < triWoopBytes, an output capacity <= 0, an output range that
+ * overlaps an input range or another output range.  Without a device: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrBvhReorderResult {
+    int64_t nodesBytes, triWoopBytes, triIndexBytes;   /* extents of the output tree */
+    int32_t numNodes, numLeaves, numRows, numDroppedSlots;   /* reached slots, their leaf links, the rows written, slots of the
+                                                                 input no link reaches */
+    float   seconds;                                   /* GPU time of the call */
+} NtrBvhReorderResult;
+NTR_API int ntr_bvh_reorder(const void* d_nodes, int64_t nodesBytes, const void* d_triWoop, int64_t triWoopBytes,
+                            const int32_t* d_triIndex, int64_t triIndexBytes,
+                            void* d_outNodes, int64_t outNodesCapacity, void* d_outTriWoop, int64_t outTriWoopCapacity,
+                            int32_t* d_outTriIndex, int64_t outTriIndexCapacity,
+                            NtrBvhReorderResult* result, void* stream);
+/* Bytes the reorder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_reorder_scratch_bytes(int64_t* bytes);
+
 /* reconstructKernel (src/rt/cuda/RendererKernels.cu:59-172; ReconstructInput, RendererKernels.hpp:46-70;
  * Renderer::updateResult, Renderer.cpp:583-659): hit records of one batch -> ABGR8 pixels.
  * rayType 0 = primary, 1 = AO, 2 = diffuse (textured / path-traced / VPL shading: out of scope). */

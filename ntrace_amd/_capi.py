@@ -123,6 +123,15 @@ class BvhOptimizeResult(C.Structure):
                 for k, _ in self._fields_ if k != "pad"}
 
 
+class BvhReorderResult(C.Structure):
+    _fields_ = [("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
+                ("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("numDroppedSlots", C.c_int32),
+                ("seconds", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class BvhSahResult(C.Structure):
     _fields_ = [("sahCost", C.c_float), ("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numTris", C.c_int32), ("height", C.c_int32),
                 ("seconds", C.c_float)]
@@ -247,6 +256,8 @@ SYMBOLS = [
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
     ("ntr_bvh_optimize_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_sah_cost", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhSahResult), _vp]),
+    ("ntr_bvh_reorder", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(BvhReorderResult), _vp]),
+    ("ntr_bvh_reorder_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
     ("ntr_host_kdtree_free", None, [_vp]),
     ("ntr_host_kdtree_wrap", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_vp)]),
@@ -733,6 +744,25 @@ def bvh_optimize_scratch_bytes():
     """ntr_bvh_optimize_scratch_bytes: bytes the scratch pool of bvh_optimize / bvh_sah_cost holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_bvh_optimize_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def bvh_reorder(d_nodes, nodes_bytes, d_woop, woop_bytes, d_idx, idx_bytes, d_out_nodes, out_nodes_capacity, d_out_woop, out_woop_capacity,
+                d_out_idx, out_idx_capacity, stream=0, result=None):
+    """ntr_bvh_reorder: copy a Compact tree into the host builder's node and row order (an extension; the rule is
+    tests/np_bvh_reorder.py).  Out of place; blocks; returns a BvhReorderResult (the output's extents, counts, GPU seconds).  Pass a
+    BvhReorderResult as `result` to keep the counts of a call that raises NTR_ERR_OVERFLOW or NTR_ERR_LAYOUT."""
+    res = BvhReorderResult() if result is None else result
+    _check(lib().ntr_bvh_reorder(_vp(d_nodes), int(nodes_bytes), _vp(d_woop), int(woop_bytes), _vp(d_idx), int(idx_bytes), _vp(d_out_nodes),
+                                 int(out_nodes_capacity), _vp(d_out_woop), int(out_woop_capacity), _vp(d_out_idx), int(out_idx_capacity),
+                                 C.byref(res), _vp(stream)))
+    return res
+
+
+def bvh_reorder_scratch_bytes():
+    """ntr_bvh_reorder_scratch_bytes: bytes the reorder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_reorder_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

@@ -1,5 +1,5 @@
 // compact_bvh.h -- the BVHLayout_Compact node layout, stated once, for the device code that writes, rewrites or checks such a tree
-// (bvh_build_, sah_build_, bvh_refit_, bvh_optimize_kernels.hip, bvh_utils.hip) and for the C-ABI front doors that take or fill one
+// (bvh_build_, sah_build_, bvh_refit_, bvh_optimize_, bvh_reorder_kernels.hip, bvh_utils.hip) and for the C-ABI front doors that take or fill one
 // (ntr_api.cpp, lbvh_kernels.hip, hlbvh_kernels.hip).  bvh_climb.h holds the bottom-up pass over it.
 // A node is 16 words, 64 bytes (CudaBVH.hpp:42-46):
 //   words 0..3    child 0: lo.x hi.x lo.y hi.y      words 4..7    child 1: lo.x hi.x lo.y hi.y

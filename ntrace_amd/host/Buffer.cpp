@@ -2,6 +2,8 @@
 // (setOwner's valid/dirty state machine) for the CPU and device modules.
 #include "Buffer.hpp"
 
+#include <utility>
+
 #include <cstdlib>
 #include <istream>
 #include <ostream>
@@ -92,6 +94,17 @@ void Buffer::realloc(S64 size)
     tmp.m_exists = Module_None;  // ownership moved
     tmp.m_cpuPtr = NULL;
     tmp.m_cudaPtr = NULL;
+}
+
+void Buffer::swap(Buffer& other)
+{
+    std::swap(m_size, other.m_size);
+    std::swap(m_original, other.m_original);
+    std::swap(m_owner, other.m_owner);
+    std::swap(m_exists, other.m_exists);
+    std::swap(m_dirty, other.m_dirty);
+    std::swap(m_cpuPtr, other.m_cpuPtr);
+    std::swap(m_cudaPtr, other.m_cudaPtr);
 }
 
 void Buffer::validateCPU(void)

@@ -38,6 +38,7 @@ public:
     void resize(S64 size) { realloc(size); }                                  // keeps contents
     void resizeDiscard(S64 size) { if (m_size != size) reset(NULL, size); }  // drops contents
     void free(Module module);
+    void swap(Buffer& other);                                                 // exchanges the two buffers' memory, sizes and states
 
     void getRange(void* dst, S64 srcOfs, S64 size) const;
     void get(void* ptr) { getRange(ptr, 0, getSize()); }

@@ -80,6 +80,27 @@ void CudaBVH::optimize(int passes)
     m_optimizeResult = res;
 }
 
+void CudaBVH::reorder(void)
+{
+    if (m_layout != BVHLayout_Compact) fail("CudaBVH::reorder: only BVHLayout_Compact is supported");
+    Buffer nodes(NULL, m_nodes.getSize()), triWoop(NULL, m_triWoop.getSize()), triIndex(NULL, m_triIndex.getSize());
+    NtrBvhReorderResult res = NtrBvhReorderResult();
+    const int rc = ntr_bvh_reorder(m_nodes.getCudaPtr(), m_nodes.getSize(), m_triWoop.getCudaPtr(), m_triWoop.getSize(),
+                                   (const int32_t*)m_triIndex.getCudaPtr(), m_triIndex.getSize(), nodes.getMutableCudaPtrDiscard(),
+                                   nodes.getSize(), triWoop.getMutableCudaPtrDiscard(), triWoop.getSize(),
+                                   (int32_t*)triIndex.getMutableCudaPtrDiscard(), triIndex.getSize(), &res, NULL);
+    // NTR_ERR_LAYOUT after the work leaves a complete, traceable output; every other failure leaves the tree as it was
+    if (rc != NTR_OK) fail("CudaBVH::reorder: %s", ntr_last_error());
+    m_nodes.swap(nodes);
+    m_triWoop.swap(triWoop);
+    m_triIndex.swap(triIndex);
+    m_nodes.resize(res.nodesBytes);
+    m_triWoop.resize(res.triWoopBytes);
+    m_triIndex.resize(res.triIndexBytes);
+    m_reorderResult = res;
+    invalidateTraceFlags();   // the top-of-tree table is the node buffer's
+}
+
 F32 CudaBVH::calcSAHCost(void)
 {
     if (m_layout != BVHLayout_Compact) fail("CudaBVH::calcSAHCost: only BVHLayout_Compact is supported");

@@ -54,6 +54,13 @@ public:
     enum { DefaultOptimizePasses = 2 };
     void        optimize(int passes = DefaultOptimizePasses);
     const NtrBvhOptimizeResult& getOptimizeResult(void) const { return m_optimizeResult; }   // of the last optimize (zero before)
+    // Mirror extension (no counterpart in the reference as a pass of its own): renumber the tree on the device into the node and row
+    // order createCompact gives a host tree (ntr_bvh_reorder into three fresh Buffers of the current sizes, which are swapped in and
+    // trimmed to the result's extents), then invalidateTraceFlags(): the top-of-tree table belongs to the node buffer.  The tree --
+    // boxes, topology, leaf contents, leaf depths -- stays; slots and rows no link reaches are dropped.  Works on a tree of any
+    // origin.  Nothing calls this implicitly.  Blocking; fails (FW::fail) with the library's message, the tree then as it was.
+    void        reorder(void);
+    const NtrBvhReorderResult& getReorderResult(void) const { return m_reorderResult; }       // of the last reorder (zero before)
     // HLBVHBuilder::calcSAHGPU (HLBVHBuilder.cpp:752-770) for a tree of any origin: ntr_bvh_sah_cost on this tree's buffers.
     F32         calcSAHCost(void);
     const NtrBvhSahResult& getSAHResult(void) const { return m_sahResult; }                   // of the last calcSAHCost
@@ -72,6 +79,7 @@ protected:
     NtrBvhRefitResult m_refitResult;
     NtrBvhOptimizeResult m_optimizeResult = NtrBvhOptimizeResult();
     NtrBvhSahResult   m_sahResult = NtrBvhSahResult();
+    NtrBvhReorderResult m_reorderResult = NtrBvhReorderResult();
 };
 
 }  // namespace FW

@@ -140,6 +140,15 @@ void Renderer::optimizeBVH(int passes)
     bvh->optimize(passes);
 }
 
+void Renderer::reorderBVH(void)
+{
+    if (m_isKDTree) fail("Renderer::reorderBVH: the kd-tree has no node order to restore");
+    if (!m_scene) fail("Renderer: no scene");
+    CudaBVH* bvh = dynamic_cast<CudaBVH*>(getCudaBVH());   // built first if there is none
+    if (!bvh) fail("Renderer::reorderBVH: not a BVH");
+    bvh->reorder();                                        // m_leafDepth stays: leaf depths are per triangle
+}
+
 CudaAS* Renderer::getCudaKDTree(void)
 {
     if (!m_scene || m_accelStruct) return m_accelStruct;

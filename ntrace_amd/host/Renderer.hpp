@@ -61,6 +61,11 @@ public:
     // topology, which this changes.  A bvhcache file is not rewritten.  A kd-tree builder fails:
     // "Renderer::optimizeBVH: the kd-tree has no treelet optimiser".  Nothing calls this implicitly.
     void   optimizeBVH(int passes = CudaBVH::DefaultOptimizePasses);
+    // Mirror extension: CudaBVH::reorder on the current BVH (it is built first if there is none), for a tree of any BVH builder,
+    // fresh, refitted or optimised.  The leaf depths behind the AO dispatch hint are kept: they are per triangle and the tree is the
+    // same.  A bvhcache file is not rewritten.  A kd-tree builder fails: "Renderer::reorderBVH: the kd-tree has no node order to
+    // restore".  Nothing calls this implicitly.
+    void   reorderBVH(void);
     void   setParams(const Params& params);
     void   setEnableRandom(bool enable) { m_enableRandom = enable; }
     CudaVirtualTracer& getCudaTracer(void) { return *m_cudaTracer; }

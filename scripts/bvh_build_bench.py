@@ -9,7 +9,11 @@ ntr_trace_bvh Mrays/s of the device SAH trees, the LBVH and the host SAH tree on
 8 x AO batch made from the LBVH's primary hits (ntr_raygen_ao, radius 5 as bench.py).  A rate is the rays over the sum of the kernel
 times of --reps launches after --warmup launches; the host tree is measured a second time at the end ("host_sah_again_*": its
 run-to-run spread in this process), and the ntr_trace_bvh_stats counters of the host tree and the full-sweep device tree -- the
-same nodes in another numbering -- are reported for the primary batch.  Prints one JSON line per scene.
+same nodes in another numbering -- are reported for the primary batch.
+Reordered columns ("*_reordered"): the full-sweep, binned and LBVH trees copied into the host builder's node and row order by
+ntr_bvh_reorder and traced on the same rays; "reorder" holds the pass's GPU time on the full-sweep and the LBVH tree (median of
+--reps calls after --warmup calls) beside ntr_bvh_refit of the same tree with unmoved vertices, and whether the reordered
+full-sweep tree's node buffer equals the host tree's as values.  Prints one JSON line per scene.
 
     python scripts/bvh_build_bench.py [--scenes atrium conference_room hairball] [--reps 5] [--warmup 2] [--out f.json]
 """
@@ -41,6 +45,14 @@ def rate(fn, n, reps, warmup):
     for _ in range(reps):
         total += fn()
     return n * reps / total / 1e6
+
+
+def slab(sizes):
+    """Buffers of `sizes` bytes as 256-byte aligned slices of ONE allocation: the trace's flat fetch needs a tree's node and row
+    buffers inside one 4 GiB window (csrc/trace_plan.h), which must not depend on where the allocator puts three late allocations."""
+    offs = np.concatenate([[0], np.cumsum([(int(c) + 255) & ~255 for c in sizes])])
+    t = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda:0")
+    return [t[int(o):int(o) + int(c)] for o, c in zip(offs, sizes)]
 
 
 def median_build(build, reps, warmup):
@@ -96,7 +108,7 @@ def main():
                                  "prep_ms": float(np.median(runs[:, 1])),
                                  "levels_ms": float(np.median(runs[:, 2])), "emit_ms": float(np.median(runs[:, 3])),
                                  **{k: getattr(r, k) for k in ("numNodes", "numLeaves", "numLevels", "maxDepth", "medianFallbacks")}}
-        trees["persistent"] = (pb, r.nodesBytes, r.triWoopBytes)
+        trees["persistent"] = (pb, r.nodesBytes, r.triWoopBytes, r.triIndexBytes)
         # the full-sweep device SAH build: the host SAH builder's tree
         sb = buffers()
 
@@ -114,7 +126,7 @@ def main():
                              "levels_ms": float(np.median(runs[:, 3])), "emit_ms": float(np.median(runs[:, 4])),
                              "scratch_bytes_per_tri": nt.sah_device_scratch_bytes() / n_tri,
                              **{k: getattr(r, k) for k in ("numNodes", "numLeaves", "numLevels", "maxDepth", "numDropped")}}
-        trees["sah_device"] = (sb, r.nodesBytes, r.triWoopBytes)
+        trees["sah_device"] = (sb, r.nodesBytes, r.triWoopBytes, r.triIndexBytes)
         # LBVH and HLBVH (bits 4): the builds' own GPU times
         lb = buffers()
 
@@ -126,7 +138,7 @@ def main():
 
         runs = np.array(median_build(lbvh, args.reps, args.warmup))
         row["lbvh"] = {"ms_median": float(np.median(runs[:, 0]) * 1e3), "numNodes": lbvh.last.numNodes}
-        trees["lbvh"] = (lb, lbvh.last.nodesBytes, lbvh.last.triWoopBytes)
+        trees["lbvh"] = (lb, lbvh.last.nodesBytes, lbvh.last.triWoopBytes, lbvh.last.triIndexBytes)
         hb = buffers()
 
         def hlbvh():
@@ -141,17 +153,48 @@ def main():
             t0 = time.time()
             host = nt.sah_build(tri, pos)
             row["host_sah"] = {"build_ms": (time.time() - t0) * 1e3}
-            trees["host_sah"] = ([up(host.nodes), up(host.woop), up(host.tri_index)], host.nodes.nbytes, host.woop.nbytes)
+            trees["host_sah"] = ([up(host.nodes), up(host.woop), up(host.tri_index)], host.nodes.nbytes, host.woop.nbytes,
+                                 host.tri_index.nbytes)
+        # the same trees in the host builder's order (ntr_bvh_reorder), and what the pass costs beside a refit of the same tree
+        row["reorder"] = {}
+        for key in ("sah_device", "persistent", "lbvh"):
+            b, nb, wb, ib = trees[key]
+            ob = slab((nb, wb, ib))
+
+            def reorder():
+                reorder.last = nt.bvh_reorder(b[0].data_ptr(), nb, b[1].data_ptr(), wb, b[2].data_ptr(), ib, ob[0].data_ptr(), nb,
+                                              ob[1].data_ptr(), wb, ob[2].data_ptr(), ib, stream)
+                return (reorder.last.seconds,)
+
+            runs = np.array(median_build(reorder, args.reps, args.warmup))
+            ro = reorder.last
+            trees[key + "_reordered"] = (ob, ro.nodesBytes, ro.triWoopBytes, ro.triIndexBytes)
+            cb = [t.clone() for t in b]                  # the refit of the same tree, vertices unmoved, on a copy
+
+            def refit():
+                return (nt.bvh_refit(cb[0].data_ptr(), nb, cb[1].data_ptr(), wb, cb[2].data_ptr(), ib, n_tri, d_tri.data_ptr(), pos.shape[0],
+                                     d_pos.data_ptr(), 0.0 if key == "sah_device" else 0.001, 0, stream, True).seconds,)
+
+            row["reorder"][key] = {"ms_median": float(np.median(runs[:, 0]) * 1e3),
+                                   "refit_ms_median": float(np.median(np.array(median_build(refit, args.reps, args.warmup))[:, 0]) * 1e3),
+                                   "scratch_bytes_per_slot": nt.bvh_reorder_scratch_bytes() / (nb // 64), **ro.as_dict()}
+            del cb
+        if "host_sah" in trees:
+            got = trees["sah_device_reordered"][0][0].cpu().numpy().view(np.float32).reshape(-1, 16)
+            ref = host.nodes.view(np.float32).reshape(-1, 16)
+            row["reorder"]["sah_device"]["nodes_equal_host_as_values"] = bool(
+                got.shape == ref.shape and np.array_equal(got[:, :12], ref[:, :12])
+                and np.array_equal(got[:, 12:].view(np.int32), ref[:, 12:].view(np.int32)))
         # rays: primary, then 8 x AO from the LBVH's primary hits
         rays, _ = scenes.primary_rays(cam, args.width, args.height)
         n = rays.shape[0]
         d_rays = up(rays)
         d_res = torch.zeros(n * 16, dtype=torch.uint8, device="cuda:0")
 
-        flags = {key: nt.bvh_validate(b[0].data_ptr(), nb, stream) for key, (b, nb, _) in trees.items()}
+        flags = {key: nt.bvh_validate(b[0].data_ptr(), nb, stream) for key, (b, nb, _, _) in trees.items()}
 
         def trace(key, count, any_hit, d_r, d_out):
-            b, nb, wb = trees[key]
+            b, nb, wb, _ = trees[key]
             return nt.trace_bvh(args.kernel, count, any_hit, d_r.data_ptr(), d_out.data_ptr(), b[0].data_ptr(), nb, b[1].data_ptr(), wb,
                                 b[2].data_ptr(), bvh_flags=flags[key], stream=stream)
 
@@ -173,8 +216,8 @@ def main():
             m["host_sah_again_primary"] = rate(lambda: trace("host_sah", n, False, d_rays, d_res), n, args.reps, args.warmup)
             m["host_sah_again_ao"] = rate(lambda: trace("host_sah", n_ao, True, d_ao, d_ao_res), n_ao, args.reps, args.warmup)
             st = {}
-            for key in ("host_sah", "sah_device"):
-                b, nb, wb = trees[key]
+            for key in ("host_sah", "sah_device", "sah_device_reordered"):
+                b, nb, wb, _ = trees[key]
                 st[key] = nt.trace_bvh_stats(args.kernel, n, False, d_rays.data_ptr(), d_res.data_ptr(), b[0].data_ptr(), nb, b[1].data_ptr(), wb,
                                              b[2].data_ptr(), bvh_flags=flags[key], stream=stream).as_dict()
             row["primary_trace_stats"] = st

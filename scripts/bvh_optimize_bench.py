@@ -7,7 +7,9 @@ For each scene, everything of a row in one process and over the same rays:
     own stream events around every launch and read-back of the call), beside ntr_lbvh_build, the binned SAH build and the host SAH
     build of the same mesh; each device time a median of --reps calls after --warmup calls, every optimise on a fresh copy of the tree;
   * quality: SAH cost (ntr_bvh_sah_cost) and ntr_trace_bvh Mrays/s with freshly validated flags for LBVH, LBVH + 1 / 2 / 3 passes,
-    HLBVH (bits 4), binned SAH, binned SAH + 3, host SAH, host SAH + 3, on a 1920x1080 primary batch and the 8 x AO batch made from
+    HLBVH (bits 4), binned SAH, binned SAH + 3, host SAH, host SAH + 3, and LBVH, LBVH + 2 and binned SAH copied into the host
+    builder's node order by ntr_bvh_reorder ("... reordered"; the optimiser hands a rewritten treelet's slots out wherever they
+    lie), with the host SAH tree a second time at the end as its run-to-run spread, on a 1920x1080 primary batch and the 8 x AO batch made from
     the LBVH's primary hits (ntr_raygen_ao, radius 5 as bench.py).  A rate is the rays over the sum of the kernel times of --reps
     launches after --warmup launches;
   * repair: at every a of --amplitudes, with pos' = pos + a * d * sin(k * pos.yzx + phase) as scripts/bvh_refit_bench.py: the host SAH
@@ -53,6 +55,14 @@ def deform(pos, a):
     return np.ascontiguousarray((pos + (F(F(a) * d) * s).astype(F)).astype(F))
 
 
+def slab(sizes):
+    """Buffers of `sizes` bytes as 256-byte aligned slices of ONE allocation: the trace's flat fetch needs a tree's node and row
+    buffers inside one 4 GiB window (csrc/trace_plan.h), which must not depend on where the allocator puts three late allocations."""
+    offs = np.concatenate([[0], np.cumsum([(int(c) + 255) & ~255 for c in sizes])])
+    t = torch.zeros(int(offs[-1]), dtype=torch.uint8, device="cuda:0")
+    return [t[int(o):int(o) + int(c)] for o, c in zip(offs, sizes)]
+
+
 def rate(fn, n, reps, warmup):
     for _ in range(warmup):
         fn()
@@ -82,7 +92,10 @@ class Tree:
         return Tree([up(h.nodes), up(h.woop), up(h.tri_index)], h.nodes.nbytes, h.woop.nbytes, h.tri_index.nbytes), ms
 
     def clone(self):
-        return Tree([b.clone() for b in self.bufs], self.nb, self.wb, self.ib)
+        bufs = slab([b.numel() for b in self.bufs])
+        for d, b in zip(bufs, self.bufs):
+            d.copy_(b)
+        return Tree(bufs, self.nb, self.wb, self.ib)
 
     def refit(self, n_tri, d_tri, n_vert, d_pos, eps, stream):
         return nt.bvh_refit(self.bufs[0].data_ptr(), self.nb, self.bufs[1].data_ptr(), self.wb, self.bufs[2].data_ptr(), self.ib, n_tri,
@@ -95,6 +108,13 @@ class Tree:
         t = self.clone()
         t.optimize(passes, stream)
         return t
+
+    def reordered(self, stream):
+        """This tree in the host builder's node and row order (ntr_bvh_reorder), in buffers of its own."""
+        bufs = slab((self.nb, self.wb, self.ib))
+        r = nt.bvh_reorder(self.bufs[0].data_ptr(), self.nb, self.bufs[1].data_ptr(), self.wb, self.bufs[2].data_ptr(), self.ib,
+                           bufs[0].data_ptr(), self.nb, bufs[1].data_ptr(), self.wb, bufs[2].data_ptr(), self.ib, stream)
+        return Tree(bufs, r.nodesBytes, r.triWoopBytes, r.triIndexBytes)
 
     def sah(self, stream):
         return nt.bvh_sah_cost(self.bufs[0].data_ptr(), self.nb, self.bufs[1].data_ptr(), self.wb, stream)
@@ -201,6 +221,8 @@ def main():
         trees = {"lbvh": lbvh0, "lbvh+1": lbvh0.optimized(1, stream), "lbvh+2": lbvh0.optimized(2, stream),
                  "lbvh+3": lbvh0.optimized(3, stream), "hlbvh4": hlbvh0, "binned": binned0, "binned+3": binned0.optimized(3, stream),
                  "host_sah": sah0, "host_sah+3": sah0.optimized(3, stream)}
+        trees.update({"lbvh reordered": lbvh0.reordered(stream), "lbvh+2 reordered": trees["lbvh+2"].reordered(stream),
+                      "binned reordered": binned0.reordered(stream), "host_sah again": sah0})
         row["quality"] = measure(trees, "lbvh", pos)
 
         row["repair"] = {}
