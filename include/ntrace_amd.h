@@ -234,6 +234,10 @@ NTR_API int ntr_trace_plan(const char* kernelName, int32_t numRays, int32_t anyH
 /* One launch in the life of a scheduling hint: out[0] = the hint's pool-depth words are cleared, out[1] = the launch records per-block
  * costs (refresh), out[2] = the launch is dispatched in the hint's order. */
 NTR_API int ntr_trace_plan_hint_step(int32_t valid, int32_t predicted, int32_t uses, int32_t out[3]);
+/* The two per-launch switches of the per-ray kernels' prologue that change no launch shape and so are not part of NtrTracePlan:
+ * out[0] = a closest-hit (anyHit = 0) or any-hit launch takes certain steps (NTR_TRACE_CERTAIN_STEPS), out[1] = ... and keeps the node in a
+ * scalar register through a run of them (NTR_TRACE_CERTAIN_DESCENT). */
+NTR_API int ntr_trace_plan_certain(int32_t anyHit, int32_t out[2]);
 
 /* Re-reads the NTR_* environment tunables.  They are read once, at first use; sweep scripts
  * that change a variable inside one process call this afterwards.  Not needed by applications. */

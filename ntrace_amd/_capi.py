@@ -179,6 +179,7 @@ SYMBOLS = [
     ("ntr_trace_status", C.c_int, [_vp, C.POINTER(_u32)]),
     ("ntr_trace_plan", C.c_int, [C.c_char_p, _i32, _i32, C.c_uint64, _i64, C.c_uint64, _i64, _u32, _i32, _i32, _vp]),
     ("ntr_trace_plan_hint_step", C.c_int, [_i32, _i32, _i32, C.POINTER(_i32 * 3)]),
+    ("ntr_trace_plan_certain", C.c_int, [_i32, C.POINTER(_i32 * 2)]),
     ("ntr_selftest_gather_rate", C.c_int, [_i64, _i32, _i32, _i32, _vp, C.POINTER(C.c_float)]),
     ("ntr_frame_shard", C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     ("ntr_frame_ao_batches", C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, C.POINTER(_i32)]),
@@ -398,6 +399,13 @@ def trace_plan_hint_step(valid, predicted, uses):
     out = (_i32 * 3)()
     _check(lib().ntr_trace_plan_hint_step(int(bool(valid)), int(bool(predicted)), int(uses), C.byref(out)))
     return dict(zeroK=bool(out[0]), refresh=bool(out[1]), useOrder=bool(out[2]))
+
+
+def trace_plan_certain(any_hit):
+    """ntr_trace_plan_certain: what the tunables make of the prologue's certain steps for such a launch (no device needed)."""
+    out = (_i32 * 2)()
+    _check(lib().ntr_trace_plan_certain(int(bool(any_hit)), C.byref(out)))
+    return dict(certainSteps=bool(out[0]), certainDescent=bool(out[1]))
 
 
 def trace_status(stream=0):

@@ -255,6 +255,8 @@ static int launch_trace(DeviceState* ds, const Tunables& tun, const TracePlan& p
 }
 
 // validate -> describe -> bind -> launch
+static int32_t certain_steps_of(const Tunables& tun, bool anyHit) { return (tun.certainSteps >= 2 || (tun.certainSteps == 1 && anyHit)) ? 1 : 0; }
+
 static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, const NtrRay* d_rays,
                       NtrRayResult* d_results, const void* d_nodes, int64_t nodesBytes, const void* d_triWoop,
                       int64_t triWoopBytes, const int32_t* d_triIndex, int32_t layout, uint32_t bvhFlags,
@@ -300,7 +302,8 @@ static int trace_impl(const char* kernelName, int32_t numRays, int32_t anyHit, c
     p.octant = pl.octant; p.poolKConst = pl.poolKConst;
     // (not part of the plan: it changes no launch shape)  1: any-hit launches -- short occlusion rays, where four prologue steps in five are
     // certain; the closest-hit launch of a camera batch finds one step in eight certain and lost 1 % to asking (EXPERIMENTS.md); 2: every launch
-    p.certainSteps = (tun.certainSteps >= 2 || (tun.certainSteps == 1 && anyHit)) ? 1 : 0;
+    p.certainSteps = certain_steps_of(tun, anyHit != 0);
+    p.certainDescent = tun.certainDescent != 0 ? 1 : 0;
     if (stats) NTR_HIP(hipMemsetAsync(ds->stats, 0, 4 * sizeof(unsigned long long), s));
 
     rc = bind_trace(ds, tun, pl, bd.capturing, nodesBytes, s, hint, &L);
@@ -337,6 +340,7 @@ static void tunables_load_locked()
     t.flatFetch = env_int("NTR_TRACE_FLAT_FETCH", 1);             // unified-step loop: one group of global loads per iteration (0 = two masked groups of range-checked buffer loads)
     t.uniformPrologue = env_int("NTR_TRACE_UNIFORM_PROLOGUE", 1);  // per-ray kernels: scalar node fetches while the lanes of a fresh wave all hold the same inner node
     t.certainSteps = env_int("NTR_TRACE_CERTAIN_STEPS", 1);   // per-ray kernels, in the uniform prologue: steps that comparisons settle for every live lane skip the exact slab test (1 = any-hit launches, 2 = every launch, 0 = off)
+    t.certainDescent = env_int("NTR_TRACE_CERTAIN_DESCENT", 1);   // ... and the node stays in a scalar register from one certain step to the next while every live lane takes the same inner child (0 = every step writes the child to the lanes and the loop top reads it back)
     t.splitSlice = env_int("NTR_TRACE_SPLIT_SLICE", 8);   // persistent kernels, unified-step loop: once the pool is dry, lanes without a ray take over stack entries of the wave's live rays; looked at every N steps (0 = off)
     t.wholeWave = env_int("NTR_TRACE_WHOLE_WAVE", 1);      // kepler_dynamic_fetch: waves start in whole-wave mode and switch to single-lane refills per wave (0 = dynamic fetch from the start, as until round 5)
     t.prefetchAfter = env_int("NTR_TRACE_PREFETCH_AFTER", 8);   // persistent kernels: iterations into a chunk after which a wave posts the dequeue of its next one (-1 = never)
@@ -494,6 +498,14 @@ int ntr_trace_plan(const char* kernelName, int32_t numRays, int32_t anyHit, uint
                                              (flags & NTR_PLAN_FLAG_STATS) != 0, (flags & NTR_PLAN_FLAG_CAPTURING) != 0,
                                              (flags & NTR_PLAN_FLAG_CALLER_HINT) != 0, numCUs);
     *plan = plan_trace(tunables(), bd);
+    return NTR_OK;
+}
+
+int ntr_trace_plan_certain(int32_t anyHit, int32_t out[2])
+{
+    if (!out) return set_error(NTR_ERR_INVALID, "ntr_trace_plan_certain: null argument");
+    const Tunables tun = tunables();
+    out[0] = certain_steps_of(tun, anyHit != 0); out[1] = tun.certainDescent != 0 ? 1 : 0;
     return NTR_OK;
 }
 

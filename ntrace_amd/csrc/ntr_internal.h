@@ -12,7 +12,7 @@ int hip_fail(hipError_t e, const char* what);
 
 // Tunables (environment overrides for sweeps), read once at first use -- see ntr_api.cpp.
 struct Tunables {
-    int chunk, fetchThreshold, leafSwitchBelow, blocksPerCU, blocksPerCUIncoherent, blocksPerCUDivergent, poolHeads, octant, unified, flatFetch, uniformPrologue, certainSteps, splitSlice, wholeWave, prefetchAfter, minipool, minipoolThreshold, minipoolWide;
+    int chunk, fetchThreshold, leafSwitchBelow, blocksPerCU, blocksPerCUIncoherent, blocksPerCUDivergent, poolHeads, octant, unified, flatFetch, uniformPrologue, certainSteps, certainDescent, splitSlice, wholeWave, prefetchAfter, minipool, minipoolThreshold, minipoolWide;
     int autoHint, autoHintMinRays, persistentHints, route, predict, predictPersistent, predictDepth, predictMinRays, predictMinNodes;
     int schedRefreshEvery, schedClasses;
     int lbvhSplit, lbvhAggLds, lbvhAggStaged, lbvhSortItems;

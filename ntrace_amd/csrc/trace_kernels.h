@@ -73,6 +73,8 @@ struct TraceParams {
     int32_t certainSteps;    // per-ray kernels, in that prologue: a step whose outcome plain comparisons settle for every live lane (origin inside one child
                              // box, the sibling out of the ray's reach) skips the exact slab test; needs NTR_BVH_ORDERED and tmin == 0 (trace_kernels.hip).  Set per launch from
                              // NTR_TRACE_CERTAIN_STEPS: 1 (default) any-hit launches, 2 every launch, 0 none
+    int32_t certainDescent;  // ... and while every live lane of a certain step takes the same inner child, the wave keeps the node in a scalar register and
+                             // goes from record to record without writing it to the lanes (NTR_TRACE_CERTAIN_DESCENT: 1 default, 0 = every step through the lanes)
     int32_t splitSlice;      // persistent kernels, unified-step loop: once the pool is dry, idle lanes take over stack entries of the wave's
                              // live rays; the lanes are looked at every splitSlice steps (trace_split.h); 0 = off
     const unsigned int* order;     // per-ray kernel: workgroup i traces ray block order[i] (null = identity); persistent kernels: the pool

@@ -459,6 +459,7 @@ struct UnifiedBufs {
     u32x4 rNodes, rWoop;
     bool uniformPrologue;   // per-ray kernels: scalar fetches while the wave's lanes all hold the same inner node (TraceParams::uniformPrologue)
     bool certainSteps;      // ... and their steps decided by comparisons where the slab test's outcome is certain (TraceParams::certainSteps; boxes lo <= hi)
+    bool certainDescent;    // ... and the node kept a scalar from one such step to the next while every live lane takes the same child (TraceParams::certainDescent)
     // FLAT fetch: both buffers lie inside one 4 GiB window (the host checks it before it selects the flat fetch), so a lane's 64 bytes
     // are base + a 32-bit offset -- the global load takes the scalar base and the lane's offset as they are, where two unrelated 64-bit
     // pointers cost every iteration a per-lane 64-bit select and add (round 5)
@@ -475,6 +476,7 @@ __device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
     u.rNodes = rsrc_words(p.nodes, p.nodesBytes); u.rWoop = rsrc_words(p.woop, p.woopBytes);
     u.uniformPrologue = p.uniformPrologue != 0;
     u.certainSteps = p.certainSteps != 0 && (p.bvhFlags & NTR_BVH_ORDERED) != 0;
+    u.certainDescent = p.certainDescent != 0;
     const unsigned long long an = (unsigned long long)p.nodes, aw = (unsigned long long)p.woop;
     const unsigned long long lo = an < aw ? an : aw;
     u.base = (const char*)lo;
@@ -614,6 +616,14 @@ typedef const __attribute__((address_space(4))) f32x4* const_f32x4_ptr;   // con
 //      the near plane hi_c.  So mn > tmax: rejected.
 //  (d) inside_c and out_c exclude each other (segLo <= o <= segHi), so a certain lane accepts exactly one child: no ordering decision, no push.
 // The test costs 12 to 24 VALU against the 88 of the exact step; a wave whose lanes are uncertain twice in a row stops asking.
+// Carried descent (TraceParams::certainDescent).  A certain step in which every live lane is inside the SAME child c gives every live lane
+// the node c, pushes nothing and leaves tmax alone; the loop top would then read c back out of the first live lane and find the lanes
+// agreed.  So while c is an inner node whose record lies inside the buffer (the loop top's own test) the wave keeps it in a scalar register
+// and loads the next record at once: about 30 instructions a step where writing c to the lanes and proving them uniform again issues
+// about 75.  The lanes are written once, when the run ends: the lanes part (certain, both children taken), some lane is uncertain (the
+// exact step runs on the record already loaded, counted as uncertain as before), or the child is a leaf.  There node, stack and tmax of
+// every lane are what the per-step path has at the same step, and lanes at kSentinel are never written.  The predicate is certain_masks'
+// either way, so (a)-(d) are the whole argument.
 static constexpr int kCertainGiveUpAfter = 2;   // consecutive uncertain steps after which a wave runs the exact prologue only
 
 // reach >= tmax |d| (1 + 13 u): p = RN(tmax |d|) >= tmax |d| (1 - u) while p is normal, and RN(p (1 + 2^-20)) >= p (1 + 16 u)(1 - u).  A product
@@ -641,13 +651,18 @@ __device__ __forceinline__ float certain_end(float o, float reach)
 // instructions and no mask arithmetic -- written as `a <= x && x <= b && ...` the compiler forms every comparison into an SGPR pair and
 // folds them with one scalar instruction each, about 50 SALU a step that wait for the VALU one by one (measured: VALU -12 %, SALU +19 %, no
 // time gained).  Planes are scalar operands (the node came through the scalar cache).
-__device__ __forceinline__ void certain_masks(f32x4 A, f32x4 B, f32x4 C, const RayRegs& r, float loX, float hiX, float loY, float hiY, float loZ,
-                                              float hiZ, unsigned long long live, unsigned long long& in0, unsigned long long& in1,
-                                              unsigned long long& reach)
+// Returns the wave's next node where it is a scalar: the child word c0 (c1) when the wave is certain AND every live lane is inside child 0
+// (child 1) -- in0 (in1) == live, reach == 0 -- and kSentinel otherwise.  The common case, every live lane inside child 0, is tested first and
+// costs the twelve v_cmpx and eight scalar instructions; the masks are the same whichever path formed them.
+__device__ __forceinline__ int certain_masks(f32x4 A, f32x4 B, f32x4 C, int c0, int c1, const RayRegs& r, float loX, float hiX, float loY, float hiY,
+                                             float loZ, float hiZ, unsigned long long live, unsigned long long& in0, unsigned long long& in1,
+                                             unsigned long long& reach)
 {
     unsigned long long sav;
+    int next;
     asm volatile(
         "s_mov_b64 %[sav], exec\n\t"
+        "s_mov_b32 %[next], %[none]\n\t"
         "s_and_b64 exec, %[sav], %[live]\n\t"
         "v_cmpx_le_f32 vcc, %[ax], %[ox]\n\t"      // inside child 0: lo <= o && hi >= o per axis
         "v_cmpx_ge_f32 vcc, %[ay], %[ox]\n\t"
@@ -656,6 +671,20 @@ __device__ __forceinline__ void certain_masks(f32x4 A, f32x4 B, f32x4 C, const R
         "v_cmpx_le_f32 vcc, %[cx], %[oz]\n\t"
         "v_cmpx_ge_f32 vcc, %[cy], %[oz]\n\t"
         "s_mov_b64 %[in0], exec\n\t"
+        "s_cmp_eq_u64 %[in0], %[live]\n\t"
+        "s_cbranch_scc0 .Lcs_g%=\n\t"
+        "s_mov_b64 %[in1], 0\n\t"                   // every live lane is inside child 0: child 1 within reach of any?
+        "v_cmpx_le_f32 vcc, %[bx], %[hx]\n\t"
+        "v_cmpx_ge_f32 vcc, %[by], %[lx]\n\t"
+        "v_cmpx_le_f32 vcc, %[bz], %[hy]\n\t"
+        "v_cmpx_ge_f32 vcc, %[bw], %[ly]\n\t"
+        "v_cmpx_le_f32 vcc, %[cz], %[hz]\n\t"
+        "v_cmpx_ge_f32 vcc, %[cw], %[lz]\n\t"
+        "s_mov_b64 %[reach], exec\n\t"
+        "s_cbranch_execnz .Lcs_e%=\n\t"
+        "s_mov_b32 %[next], %[c0]\n\t"
+        "s_branch .Lcs_e%=\n"
+        ".Lcs_g%=:\n\t"
         "s_and_b64 exec, %[sav], %[live]\n\t"
         "s_andn2_b64 exec, exec, %[in0]\n\t"      // the other live lanes: inside child 1?
         "s_cbranch_execz .Lcs_a%=\n\t"
@@ -689,12 +718,18 @@ __device__ __forceinline__ void certain_masks(f32x4 A, f32x4 B, f32x4 C, const R
         "v_cmpx_ge_f32 vcc, %[cw], %[lz]\n\t"
         "s_or_b64 %[reach], %[reach], exec\n"
         ".Lcs_c%=:\n\t"
+        "s_cmp_eq_u64 %[in1], %[live]\n\t"          // every live lane inside child 1 and child 0 out of everyone's reach?
+        "s_cbranch_scc0 .Lcs_e%=\n\t"
+        "s_cmp_eq_u64 %[reach], 0\n\t"
+        "s_cselect_b32 %[next], %[c1], %[next]\n"
+        ".Lcs_e%=:\n\t"
         "s_mov_b64 exec, %[sav]"
-        : [sav] "=&s"(sav), [in0] "=&s"(in0), [in1] "=&s"(in1), [reach] "=&s"(reach)
+        : [sav] "=&s"(sav), [in0] "=&s"(in0), [in1] "=&s"(in1), [reach] "=&s"(reach), [next] "=&s"(next)
         : [live] "s"(live), [ax] "s"(A.x), [ay] "s"(A.y), [az] "s"(A.z), [aw] "s"(A.w), [bx] "s"(B.x), [by] "s"(B.y), [bz] "s"(B.z), [bw] "s"(B.w),
-          [cx] "s"(C.x), [cy] "s"(C.y), [cz] "s"(C.z), [cw] "s"(C.w), [ox] "v"(r.ox), [oy] "v"(r.oy), [oz] "v"(r.oz), [lx] "v"(loX), [hx] "v"(hiX),
-          [ly] "v"(loY), [hy] "v"(hiY), [lz] "v"(loZ), [hz] "v"(hiZ)
+          [cx] "s"(C.x), [cy] "s"(C.y), [cz] "s"(C.z), [cw] "s"(C.w), [c0] "s"(c0), [c1] "s"(c1), [none] "i"(kSentinel), [ox] "v"(r.ox), [oy] "v"(r.oy),
+          [oz] "v"(r.oz), [lx] "v"(loX), [hx] "v"(hiX), [ly] "v"(loY), [hy] "v"(hiY), [lz] "v"(loZ), [hz] "v"(hiZ)
         : "vcc", "scc");
+    return next;
 }
 // node = c0 in the lanes of m0, c1 in the lanes of m1 (disjoint); the other lanes keep theirs
 __device__ __forceinline__ void take_children(int& node, int c0, int c1, unsigned long long m0, unsigned long long m1)
@@ -729,6 +764,10 @@ __device__ __forceinline__ void uniform_prologue(const UnifiedBufs& ub, const Ra
             loZ = r.dz < 0.0f ? certain_end<-1>(r.oz, fz) : r.oz; hiZ = r.dz < 0.0f ? r.oz : certain_end<1>(r.oz, fz);
         }
     }
+    // carried certain descent: a child word c is the wave's next scalar node when 1 <= c <= descentLim -- an inner node whose 64 bytes lie
+    // inside the buffer (the test of the loop top below; 0, the root, is no child of a well-formed tree and goes through the lanes); 0 = off
+    unsigned int descentLim = !ub.certainDescent ? 0u : ub.nodesBytes - 64u < (unsigned)kSentinel ? ub.nodesBytes - 64u : (unsigned)kSentinel - 1u;
+    asm volatile("" : "+s"(descentLim));   // (one number to compare with: left to see through it, the compiler tests the switch again on every step)
     for (;;) {
         const bool live = node != kSentinel;
         const unsigned long long liveMask = __ballot(live);
@@ -736,17 +775,30 @@ __device__ __forceinline__ void uniform_prologue(const UnifiedBufs& ub, const Ra
         const int unode = __builtin_amdgcn_readlane(node, (int)__builtin_ctzll(liveMask));   // the first live lane's node: a scalar
         if (__ballot(live && node != unode) != 0ull) return;                                  // the lanes disagree: the general loop from here on
         if ((unsigned)unode >= (unsigned)kSentinel || (unsigned)unode > ub.nodesBytes - 64u) return;   // a leaf (or a malformed offset): likewise
-        const const_f32x4_ptr q = (const_f32x4_ptr)(ub.nodes + (unsigned)unode);
-        const f32x4 A = q[0], B = q[1], C = q[2], D = q[3];
+        unsigned int snode = (unsigned)unode;   // the wave's node while it is a scalar (carried certain descent)
+        f32x4 A, B, C, D;
         if (CERTAIN && FAST && tryCertain) {
             unsigned long long in0, in1, reach;
-            certain_masks(A, B, C, r, loX, hiX, loY, hiY, loZ, hiZ, liveMask, in0, in1, reach);
+            for (;;) {
+                const const_f32x4_ptr q = (const_f32x4_ptr)(ub.nodes + snode);
+                A = q[0]; B = q[1]; C = q[2]; D = q[3];
+                const int next = certain_masks(A, B, C, __float_as_int(D.x), __float_as_int(D.y), r, loX, hiX, loY, hiY, loZ, hiZ, liveMask, in0, in1, reach);
+                if ((unsigned)next - 1u >= descentLim) break;   // not certain, the lanes part, or the child is a leaf (beyond the extent): the lanes take over
+                snode = (unsigned)next;                   // certain, every live lane to the same inner child: nothing to write, the next record
+            }
+            if (snode != (unsigned)unode) {               // carried steps were certain steps: the lanes arrive where they would have stepped to
+                if (live) node = (int)snode;
+                uncertain = 0;
+            }
             if ((in0 | in1) == liveMask && reach == 0ull) {
                 take_children(node, __float_as_int(D.x), __float_as_int(D.y), in0, in1);
                 uncertain = 0;
                 continue;
             }
             if (++uncertain >= kCertainGiveUpAfter) tryCertain = false;
+        } else {
+            const const_f32x4_ptr q = (const_f32x4_ptr)(ub.nodes + snode);
+            A = q[0]; B = q[1]; C = q[2]; D = q[3];
         }
         if (live)
             inner_advance<FAST, OCT>(make_float4(A.x, A.y, A.z, A.w), make_float4(B.x, B.y, B.z, B.w), make_float4(C.x, C.y, C.z, C.w),
