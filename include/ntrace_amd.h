@@ -359,7 +359,7 @@ NTR_API int ntr_trace_bvh_stats(const char* kernelName, int32_t numRays, int32_t
  *   NTR_BVH_FINITE   every box coordinate is finite and |x| < 2^100.
  *   NTR_BVH_FASTDIV  every box coordinate has |x| < 2^55: together with a per-ray check this
  *                    is the range in which the kernels' refactored divide is the hardware
- *                    divide (see trace_kernels.hip).
+ *                    divide (see csrc/trace_lane.h).
  *   NTR_BVH_NOTINY   every box coordinate is 0 or |x| >= 2^-93 (lets rays with an exactly-zero
  *                    origin component use the same path).
  *   NTR_BVH_ORDERED  every child box has lo <= hi on each axis: for a wave whose rays share the signs of their direction

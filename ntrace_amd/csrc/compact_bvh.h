@@ -1,6 +1,6 @@
 // compact_bvh.h -- the BVHLayout_Compact node layout, stated once, for the device code that writes, rewrites or checks such a tree
-// (bvh_build_, sah_build_, bvh_refit_, bvh_optimize_, bvh_reorder_kernels.hip, bvh_utils.hip) and for the C-ABI front doors that take or fill one
-// (ntr_api.cpp, lbvh_kernels.hip, hlbvh_kernels.hip).  bvh_climb.h holds the bottom-up pass over it.
+// (bvh_build_, sah_build_, bvh_refit_, bvh_optimize_, bvh_reorder_kernels.hip, bvh_utils.hip), for the kernels that traverse one (trace_kernels.hip
+// and its trace_*.h) and for the C-ABI front doors that take or fill one (ntr_api.cpp, lbvh_kernels.hip, hlbvh_kernels.hip).  bvh_climb.h holds the bottom-up pass over it.
 // A node is 16 words, 64 bytes (CudaBVH.hpp:42-46):
 //   words 0..3    child 0: lo.x hi.x lo.y hi.y      words 4..7    child 1: lo.x hi.x lo.y hi.y
 //   words 8..11   child 0: lo.z hi.z, child 1: lo.z hi.z
@@ -20,9 +20,15 @@ namespace ntr {
 
 constexpr int kNodeWords = 16, kNodeBytes = 64;
 constexpr int kLinkWord = 12;                                 // + k for child k
+constexpr int kSentinel = 0x76543210;                         // CudaTracerKernels.hpp:38 (EntrypointSentinel)
 constexpr int64_t kMaxNodesBytes = 0x76543200ll;              // largest multiple of 64 below the sentinel
 constexpr int64_t kMaxNodes = kMaxNodesBytes / kNodeBytes;    // 31 019 208
+static_assert(kMaxNodesBytes == kSentinel / kNodeBytes * kNodeBytes, "the node buffer ends below the sentinel");
 constexpr unsigned int kLeafTerm = 0x80000000u;
+// A Woop row is four words; a triangle is three rows (z, u, v: woop_rows.h), and the x word of the row after it says whether the leaf ends there
+constexpr int kRowBytes = 16, kRowShift = 4;                  // byte offset = row << kRowShift
+constexpr int kTriRows = 3, kTriBytes = kTriRows * kRowBytes;
+static_assert(kRowBytes == 1 << kRowShift && kTriBytes + kRowBytes == kNodeBytes, "a triangle and the word after it are as long as a node");
 
 // word (< 12) of component j (lo.x hi.x lo.y hi.y lo.z hi.z) of child k's box, and back
 __host__ __device__ __forceinline__ int box_word(int k, int j) { return j < 4 ? 4 * k + j : 8 + 2 * k + (j - 4); }
@@ -71,7 +77,7 @@ inline int check_build_outputs(const char* fn, int32_t numTris, const void* d_no
     if (!d_nodes || !d_triWoop || !d_triIndex || nodesCapacity < needN || triWoopCapacity < needW || triIndexCapacity < needI)
         return set_error(NTR_ERR_INVALID, "%s: output buffers smaller than ntr_lbvh_capacity()", fn);
     if (nodeCap) *nodeCap = std::min<int64_t>(nodesCapacity / kNodeBytes, kMaxNodes);
-    if (rowCap) *rowCap = std::min<int64_t>(std::min<int64_t>(triWoopCapacity / 16, triIndexCapacity / 4), INT_MAX);
+    if (rowCap) *rowCap = std::min<int64_t>(std::min<int64_t>(triWoopCapacity / kRowBytes, triIndexCapacity / 4), INT_MAX);
     return NTR_OK;
 }
 

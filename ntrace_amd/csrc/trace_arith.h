@@ -1,4 +1,4 @@
-// trace_arith.h -- the FAST slab path's exact division (shared by trace_kernels.hip and the device self tests, selftest_kernels.hip).
+// trace_arith.h -- the FAST slab path's exact division (shared by the trace kernels, trace_lane.h, and the device self tests, selftest_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

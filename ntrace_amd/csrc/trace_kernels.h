@@ -71,7 +71,7 @@ struct TraceParams {
     int32_t flatFetch;       // unified-step loop: one group of global loads for nodes and triangles (needs both extents >= 64 bytes)
     int32_t uniformPrologue; // per-ray kernels, unified-step loop: scalar node fetches while every live lane of the wave holds the same inner node
     int32_t certainSteps;    // per-ray kernels, in that prologue: a step whose outcome plain comparisons settle for every live lane (origin inside one child
-                             // box, the sibling out of the ray's reach) skips the exact slab test; needs NTR_BVH_ORDERED and tmin == 0 (trace_kernels.hip).  Set per launch from
+                             // box, the sibling out of the ray's reach) skips the exact slab test; needs NTR_BVH_ORDERED and tmin == 0 (trace_prologue.h).  Set per launch from
                              // NTR_TRACE_CERTAIN_STEPS: 1 (default) any-hit launches, 2 every launch, 0 none
     int32_t certainDescent;  // ... and while every live lane of a certain step takes the same inner child, the wave keeps the node in a scalar register and
                              // goes from record to record without writing it to the lanes (NTR_TRACE_CERTAIN_DESCENT: 1 default, 0 = every step through the lanes)

@@ -7,33 +7,14 @@
 //   kepler_dynamic_fetch.cu:61-322            -> trace_bvh_persistent (persistent waves,
 //                                                 ballot/mbcnt refill, LDS stack)
 //
-// ARITHMETIC.  The hit records must be bit-exact against the reference's *CPU*
-// tracer (CudaBVH::trace<BVHLayout_Compact>, src/rt/cuda/CudaBVH.cpp:698-784), so
-// every decision reproduces its binary32 expressions, not the CUDA kernels':
-//   slabs      (lo - o) / d, true IEEE division      (src/rt/Util.cpp:39-40)
-//   min / max  selects (a<b)?a:b, folded x,y,z       (Defs.hpp:212-213, Math.hpp:146-147)
-//   accept     tmin<=tmax && tmax>=ray.tmin && tmin<=ray.tmax   (CudaBVH.cpp:742-743)
-//   order      near child = smaller tmin, ties -> child 0         (CudaBVH.cpp:761)
-//   Woop       unfused left-to-right dots incl. the leading 0 and the w term
-//              (Util.cpp:106-121, Math.hpp:185), 1.f/x then multiply
-// Compiled with -ffp-contract=off and without fast-math.
-//
-// Two code paths compute the slab test, both exact:
-//   GENERIC  `/` (hipcc's correctly rounded f32 divide: v_div_scale / v_rcp / fma chain /
-//            v_div_fmas / v_div_fixup) and select-form min/max.  Valid for every input
-//            (zero direction components, NaN, infinities, denormals).
-//   FAST     for waves whose rays are all "nice" (see ray_is_nice) over a BVH flagged
-//            NTR_BVH_FASTDIV: in that range nothing over- or underflows and v_div_scale never
-//            rescales, so a quotient is  r = RN(1/d)  (the IEEE divide, once per ray and axis) and,
-//            per quotient,  q0 = x*r;  e = fma(-d,q0,x);  q = fma(e,r,q0)  -- three operations.
-//            With the CORRECTLY ROUNDED reciprocal one residual correction gives RN(x/d), the
-//            GENERIC path's bits (exact_rcp below: why, and how every quotient that could differ
-//            was checked).  Rounds 1-3 used the hardware divide's own chain instead -- v_rcp
-//            refined once, which is not always RN(1/d), and therefore TWO corrections: five
-//            operations per quotient, sixty of the ~100 vector instructions of an inner-node step.
-//            No NaN/inf can arise in the range either, so v_min3/v_max3 equal the select-form
-//            folds up to the sign of zero, which no later comparison can observe.
-//   ntr_selftest_division() / ntr_selftest_division_hard() check FAST == GENERIC bit for bit on the device.
+// This file holds the loops (traverse, traverse_unified), the three bodies that run them (perray_body, trace_bvh_persistent,
+// minipool_body) and the launcher.  What a loop is made of is stated once each, in
+//   trace_lane.h      a lane's ray and stack and the steps it takes; ARITHMETIC: why every step is bit-exact against the reference's CPU
+//                     tracer, and the GENERIC and FAST forms of the slab test;
+//   trace_fetch.h     how 64 bytes reach a lane: descriptor loads, the masked two-buffer fetch, the flat fetch and the end of a buffer;
+//   trace_prologue.h  the wave-uniform prologue and its certain steps, with the proof that they decide what the slab test decides;
+//   trace_split.h     the drain phase of the persistent waves: idle lanes take over parts of the wave's long rays;
+//   compact_bvh.h     the node and triangle layout.
 //
 // DATA PATH.  The while-while loop (traverse) fetches nodes and Woop triangles with buffer
 // loads through wave-uniform resource descriptors (voffset = the Compact layout's own byte
@@ -58,269 +39,14 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <float.h>
 
 #include "trace_kernels.h"
-#include "trace_arith.h"
+#include "trace_lane.h"
+#include "trace_fetch.h"
+#include "trace_prologue.h"
+#include "trace_split.h"
 
 namespace ntr {
-
-static constexpr int kSentinel = 0x76543210;  // CudaTracerKernels.hpp:38 (EntrypointSentinel)
-static constexpr int LDS_DEPTH = 16;
-static constexpr int SPILL_DEPTH = 88;        // 16 + 88 >= the reference CPU stack of 100 (CudaBVH.cpp:701)
-
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ Rsrc make_rsrc(const void* p, unsigned int bytes)
-{
-    // built from kernel arguments only -> provably wave-uniform (no waterfall loops)
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 ld4(Rsrc r, int byteOfs)
-{
-    u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, byteOfs, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ unsigned int ld1(Rsrc r, int byteOfs)
-{
-    return __builtin_amdgcn_raw_buffer_load_b32(r, byteOfs, 0, 0);
-}
-
-
-__device__ __forceinline__ float sel_min(float a, float b) { return (a < b) ? a : b; }
-__device__ __forceinline__ float sel_max(float a, float b) { return (a > b) ? a : b; }
-
-struct RayRegs {
-    float ox, oy, oz, tmin;
-    float dx, dy, dz, tmax;  // tmax shrinks to the closest accepted t (CudaBVH.cpp:1215)
-    float rx, ry, rz;        // FAST path: correctly rounded reciprocals of dx,dy,dz
-};
-
-// ---- FAST-path preconditions ---------------------------------------------------------
-// FAST-path ranges.  Directions: 2^-40 <= |d| <= 2^20.  Box coordinates: |c| < 2^55 (BVH flag
-// NTR_BVH_FASTDIV).  Ray origin components: 2^-36 <= |o| < 2^55 -- then x = c - o is 0 or
-// |x| >= 2^-84 for ANY such c (a c much smaller than o leaves x = -o; otherwise both operands
-// are >= 2^-61 and a non-zero difference is at least one ulp of that).  An origin component
-// that is exactly 0 makes x = c, which is only safe when the BVH has no tiny coordinates
-// (flag NTR_BVH_NOTINY: c == 0 or |c| >= 2^-93).  In these ranges |x| < 2^56,
-// exponent(x) - exponent(d) < 96, |x| >= 2^-103 and |x/d| >= 2^-113: none of v_div_scale's
-// rescaling cases, and every residual of the fma chain is exactly representable.
-__device__ __forceinline__ bool nice_dir(float v) { const float a = fabsf(v); return a >= 0x1p-40f && a <= 0x1p20f; }
-__device__ __forceinline__ bool nice_pos(float v, bool zeroOk)
-{
-    const float a = fabsf(v);
-    return (a >= 0x1p-36f && a < 0x1p55f) || (zeroOk && v == 0.0f);
-}
-__device__ __forceinline__ bool ray_is_nice(const RayRegs& r, uint32_t bvhFlags)
-{
-    const bool zeroOk = (bvhFlags & NTR_BVH_NOTINY) != 0;
-    return nice_dir(r.dx) && nice_dir(r.dy) && nice_dir(r.dz) && nice_pos(r.ox, zeroOk) && nice_pos(r.oy, zeroOk) &&
-           nice_pos(r.oz, zeroOk);
-}
-// Intersect::RayBox for BOTH children of a node (Util.cpp:34-46).  The FAST form evaluates
-// the twelve quotients stage by stage (all q0, then all e1, ...) so that consecutive
-// instructions are independent: a lone wave cannot issue a VALU op that depends on the
-// previous one back to back.
-// OCT < 8 (FAST only): every live ray of the wave has direction signs OCT (bit 0: dx < 0, bit 1: dy < 0, bit 2: dz < 0) and every box
-// has lo <= hi (NTR_BVH_ORDERED).  Rounding is monotone, so (lo - o) / d <= (hi - o) / d for d > 0 and >= for d < 0: the smaller
-// quotient of a slab is known without comparing -- the same value min / max would pick, six instructions per child less.
-template <bool FAST, int OCT = 8>
-__device__ __forceinline__ void ray_box2(const RayRegs& r, const float4& n0, const float4& n1, const float4& nz,
-                                         float& mn0, float& mx0, float& mn1, float& mx1)
-{
-    if (FAST) {
-        // x[k] = plane - origin ; axis of slot k: x x y y z z (child 0), x x y y z z (child 1)
-        float x[12] = {n0.x - r.ox, n0.y - r.ox, n0.z - r.oy, n0.w - r.oy, nz.x - r.oz, nz.y - r.oz,
-                       n1.x - r.ox, n1.y - r.ox, n1.z - r.oy, n1.w - r.oy, nz.z - r.oz, nz.w - r.oz};
-        const float d[3] = {r.dx, r.dy, r.dz};
-        const float rc[3] = {r.rx, r.ry, r.rz};
-        float q[12], e[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) q[k] = x[k] * rc[(k % 6) >> 1];
-#pragma unroll
-        for (int k = 0; k < 12; k++) e[k] = __builtin_fmaf(-d[(k % 6) >> 1], q[k], x[k]);
-#pragma unroll
-        for (int k = 0; k < 12; k++) q[k] = __builtin_fmaf(e[k], rc[(k % 6) >> 1], q[k]);
-        if (OCT < 8) {
-            constexpr int sx = OCT & 1, sy = (OCT >> 1) & 1, sz = (OCT >> 2) & 1;   // 1: the hi plane is the near one
-            mn0 = fmaxf(fmaxf(q[0 + sx], q[2 + sy]), q[4 + sz]);
-            mx0 = fminf(fminf(q[1 - sx], q[3 - sy]), q[5 - sz]);
-            mn1 = fmaxf(fmaxf(q[6 + sx], q[8 + sy]), q[10 + sz]);
-            mx1 = fminf(fminf(q[7 - sx], q[9 - sy]), q[11 - sz]);
-        } else {
-            mn0 = fmaxf(fmaxf(fminf(q[0], q[1]), fminf(q[2], q[3])), fminf(q[4], q[5]));
-            mx0 = fminf(fminf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3])), fmaxf(q[4], q[5]));
-            mn1 = fmaxf(fmaxf(fminf(q[6], q[7]), fminf(q[8], q[9])), fminf(q[10], q[11]));
-            mx1 = fminf(fminf(fmaxf(q[6], q[7]), fmaxf(q[8], q[9])), fmaxf(q[10], q[11]));
-        }
-    } else {
-        float t0x = (n0.x - r.ox) / r.dx, t1x = (n0.y - r.ox) / r.dx;
-        float t0y = (n0.z - r.oy) / r.dy, t1y = (n0.w - r.oy) / r.dy;
-        float t0z = (nz.x - r.oz) / r.dz, t1z = (nz.y - r.oz) / r.dz;
-        mn0 = sel_max(sel_max(sel_min(t0x, t1x), sel_min(t0y, t1y)), sel_min(t0z, t1z));
-        mx0 = sel_min(sel_min(sel_max(t0x, t1x), sel_max(t0y, t1y)), sel_max(t0z, t1z));
-        t0x = (n1.x - r.ox) / r.dx; t1x = (n1.y - r.ox) / r.dx;
-        t0y = (n1.z - r.oy) / r.dy; t1y = (n1.w - r.oy) / r.dy;
-        t0z = (nz.z - r.oz) / r.dz; t1z = (nz.w - r.oz) / r.dz;
-        mn1 = sel_max(sel_max(sel_min(t0x, t1x), sel_min(t0y, t1y)), sel_min(t0z, t1z));
-        mx1 = sel_min(sel_min(sel_max(t0x, t1x), sel_max(t0y, t1y)), sel_max(t0z, t1z));
-    }
-}
-
-// dot(Vec4f a, Vec4f(b,bw)) as Math.hpp:185: r = 0; r += a[i]*b[i].
-__device__ __forceinline__ float dot4(float4 a, float bx, float by, float bz, float bw)
-{
-    float r = 0.0f;
-    r += a.x * bx;
-    r += a.y * by;
-    r += a.z * bz;
-    r += a.w * bw;
-    return r;
-}
-
-// Per-lane traversal stack: entries [0, LDS_DEPTH) in LDS laid out [entry][lane] (bank =
-// lane % 32 whatever the per-lane depth -> conflict-free), deeper entries in a scratch array
-// that only the (rare) overflow branches touch.  `sp` and the LDS base stay in registers.
-typedef __attribute__((address_space(3))) int lds_int;
-
-struct LaneStack {
-    lds_int* lds;  // &s_stack[wave][0][lane]
-    int sp;        // entries held in memory (LDS, then scratch)
-    int tos;       // top of the stack, kept in a register: a pop hands out the next node without
-                   // waiting for LDS; the entry below it is fetched off the critical path
-};
-
-#define NTR_STACK_RESET(st) do { (st).sp = 0; (st).tos = kSentinel; } while (0)
-
-template <int LD = LDS_DEPTH>   // LD: the entries this stack has in LDS
-__device__ __forceinline__ void stack_push(LaneStack& st, int (&spill)[SPILL_DEPTH], int v, unsigned int* status)
-{
-    if (__builtin_expect(st.sp < LD, 1)) st.lds[st.sp * 64] = st.tos;
-    else if (st.sp < LD + SPILL_DEPTH) spill[st.sp - LD] = st.tos;
-    else { atomicOr(status, NTR_STATUS_STACK_OVERFLOW); return; }
-    st.sp++;
-    st.tos = v;
-}
-template <int LD = LDS_DEPTH>
-__device__ __forceinline__ int stack_pop(LaneStack& st, int (&spill)[SPILL_DEPTH])
-{
-    const int r = st.tos;
-    if (st.sp > 0) {
-        st.sp--;
-        st.tos = __builtin_expect(st.sp < LD, 1) ? st.lds[st.sp * 64] : spill[st.sp - LD];
-    } else {
-        st.tos = kSentinel;
-    }
-    return r;
-}
-
-// Keeps a loaded value live at this point so that hipcc cannot sink its load into a later
-// conditional block (which would turn one memory round trip per node into two).
-__device__ __forceinline__ void keep(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-__device__ __forceinline__ void keep(unsigned int& v) { asm volatile("" : "+v"(v)); }
-
-struct LaneStats {
-    unsigned int inner, tris, leaves;
-};
-
-static constexpr int kNoNode = (int)0xFFFFFF00u;  // buffer offset beyond any extent (< 4 GiB)
-
-// One inner-node step of trace<BVHLayout_Compact> (CudaBVH.cpp:721-775).  Executed by the whole
-// wave; only lanes whose current node is an inner node (`inner`) update their state.
-template <bool FAST>
-__device__ __forceinline__ void inner_step(Rsrc nodes, bool inner, const RayRegs& r,
-                                           int& node, LaneStack& st, int (&spill)[SPILL_DEPTH], unsigned int* status)
-{
-    // every lane fetches its own node (4 x 16 B; the quad-cooperative LDS-DMA fetch of rounds 1-2 was 1.2-3.7x slower in this loop:
-    // scripts/studies/rejected_patches/coop_fetch.patch)
-    const int ofs = inner ? node : kNoNode;
-    const float4 n0 = ld4(nodes, ofs), n1 = ld4(nodes, ofs + 16), nz = ld4(nodes, ofs + 32);
-    float4 nc = ld4(nodes, ofs + 48);   // (an 8-byte load of the two child words alone: 0.9 % slower, profiles/r03_ab_child_load_b64.jsonl)
-    keep(nc);
-
-    float mn0, mx0, mn1, mx1;
-    ray_box2<FAST>(r, n0, n1, nz, mn0, mx0, mn1, mx1);
-
-    const bool i0 = (mn0 <= mx0) && (mx0 >= r.tmin) && (mn0 <= r.tmax);
-    const bool i1 = (mn1 <= mx1) && (mx1 >= r.tmin) && (mn1 <= r.tmax);
-
-    const int c0 = __float_as_int(nc.x), c1 = __float_as_int(nc.y);
-    const bool swp = i1 && (!i0 || mn0 > mn1);  // visit c1 first (ties -> c0, CudaBVH.cpp:761)
-    const int nearC = swp ? c1 : c0;
-    const int farC = swp ? c0 : c1;
-    if (inner) {
-        if (i0 && i1) stack_push(st, spill, farC, status);
-        node = (i0 || i1) ? nearC : stack_pop(st, spill);
-    }
-}
-
-// intersectTriangles<BVHLayout_Compact> + updateHit (CudaBVH.cpp:1084-1126, 1183-1225).
-// Returns true when an any-hit ray terminates.
-template <bool STATS>
-__device__ __forceinline__ bool leaf_step(Rsrc woop, RayRegs& r, int leaf, bool anyHit, int& hitAddr,
-                                          float& hitU, float& hitV, LaneStats& ls)
-{
-    for (int ofs = (~leaf) * 16;; ofs += 48) {
-        const float4 z = ld4(woop, ofs);
-        float4 u4 = ld4(woop, ofs + 16);         // past a terminator these may run off the
-        float4 v4 = ld4(woop, ofs + 32);         // buffer: range-checked loads return 0
-        unsigned int nextWord = ld1(woop, ofs + 48);
-        keep(u4); keep(v4); keep(nextWord);      // one round trip per triangle, not four
-        if (__float_as_uint(z.x) == 0x80000000u) {  // terminator (CudaBVH.cpp:1091)
-            if (STATS) ls.leaves++;
-            break;
-        }
-        if (STATS) ls.tris++;  // numTriangleTests (CudaBVH.cpp:1107-1111)
-
-        // Intersect::RayTriangleWoop (Util.cpp:99-127)
-        const float Oz = z.w - r.ox * z.x - r.oy * z.y - r.oz * z.z;
-        const float ooDz = 1.0f / dot4(z, r.dx, r.dy, r.dz, 0.0f);
-        const float t = Oz * ooDz;
-        float tt = FLT_MAX, uu = 0.0f, vv = 0.0f;  // miss -> bary[2] = FW_F32_MAX
-        if (t > r.tmin && t < r.tmax) {
-            const float u = dot4(u4, r.ox, r.oy, r.oz, 1.0f) + t * dot4(u4, r.dx, r.dy, r.dz, 0.0f);
-            if (u >= 0.0f) {
-                const float v = dot4(v4, r.ox, r.oy, r.oz, 1.0f) + t * dot4(v4, r.dx, r.dy, r.dz, 0.0f);
-                if (v >= 0.0f && (u + v) <= 1.0f) { tt = t; uu = u; vv = v; }
-            }
-        }
-        // updateHit re-tests the returned t, so with tmax = +inf a *missed* test
-        // is recorded at t = FLT_MAX exactly like the reference (CudaBVH.cpp:1200).
-        if (tt > r.tmin && tt < r.tmax) {
-            r.tmax = tt;
-            hitAddr = ofs >> 4;
-            hitU = uu;
-            hitV = vv;
-            if (anyHit) return true;
-        }
-        if (nextWord == 0x80000000u) {  // the terminator was fetched with this triangle
-            if (STATS) ls.leaves++;
-            break;
-        }
-    }
-    return false;
-}
-
-__device__ __forceinline__ void store_result(NtrRayResult* __restrict__ results, const int* __restrict__ triIndex,
-                                             int rayIdx, int hitAddr, float t, float u, float v)
-{
-    int4 out;
-    out.x = (hitAddr < 0) ? -1 : triIndex[hitAddr];
-    out.y = __float_as_int(t);
-    out.z = (hitAddr < 0) ? 0 : __float_as_int(u);
-    out.w = (hitAddr < 0) ? 0 : __float_as_int(v);
-    reinterpret_cast<int4*>(results)[rayIdx] = out;
-}
-
-__device__ __forceinline__ void load_ray(const NtrRay* __restrict__ rays, int rayIdx, RayRegs& r)
-{
-    const float4 o = reinterpret_cast<const float4*>(rays)[rayIdx * 2 + 0];
-    const float4 d = reinterpret_cast<const float4*>(rays)[rayIdx * 2 + 1];
-    r.ox = o.x; r.oy = o.y; r.oz = o.z; r.tmin = o.w;
-    r.dx = d.x; r.dy = d.y; r.dz = d.z; r.tmax = d.w;
-    r.rx = exact_rcp(d.x); r.ry = exact_rcp(d.y); r.rz = exact_rcp(d.z);
-}
 
 // While-while traversal of the lanes' current rays until every lane is done (or, in the
 // persistent kernel, until too few lanes are live).  Both loops are wave-uniform (ballots); per-ray
@@ -331,11 +57,11 @@ template <bool FAST, bool STATS, bool DYNAMIC_FETCH, bool SLICED = false>
 __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int& node,
                                          LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit,
                                          int& hitAddr, float& hitU, float& hitV, LaneStats& ls, unsigned int* status,
-                                         bool poolEmpty, int fetchThreshold, int leafSwitchBelow, int& slice)
+                                         bool poolEmpty, int fetchThreshold, int leafSwitchBelow, int* slice = nullptr)
 {
     unsigned long long live = __ballot(node != kSentinel);
     while (live != 0ull) {
-        if (SLICED && --slice < 0) break;
+        if (SLICED && --*slice < 0) break;
         for (;;) {
             const bool inner = (unsigned)node < (unsigned)kSentinel;
             const unsigned long long innerMask = __ballot(inner);
@@ -357,16 +83,6 @@ __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int&
         if (DYNAMIC_FETCH && !poolEmpty && __popcll(live) < fetchThreshold) break;
     }
 }
-template <bool FAST, bool STATS, bool DYNAMIC_FETCH>
-__device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int& node,
-                                         LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit,
-                                         int& hitAddr, float& hitU, float& hitV, LaneStats& ls, unsigned int* status,
-                                         bool poolEmpty, int fetchThreshold, int leafSwitchBelow)
-{
-    int never = 0;
-    traverse<FAST, STATS, DYNAMIC_FETCH, false>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, status, poolEmpty, fetchThreshold,
-                                                leafSwitchBelow, never);
-}
 
 // Unified-step traversal (the dynamic-fetch kernel's loop).  The while-while loop above lets a wave alternate between an
 // inner-node phase and a leaf phase, and a leaf of k triangles costs k dependent round trips during which the lanes that hold
@@ -377,441 +93,12 @@ __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int&
 // A lane's own visiting order -- and with it every hit record -- is exactly that of traverse(): only the interleaving of the
 // lanes changes.  `node` < 0 doubles as the triangle cursor: the lane's next triangle is at float4 index ~node (a leaf
 // reference IS the index of its first triangle; advancing one triangle subtracts 3).
-// Buffer resource descriptor as four scalar words (what make_rsrc builds): base, base_hi (stride 0), extent in bytes, flags.
-__device__ __forceinline__ u32x4 rsrc_words(const void* p, unsigned int bytes)
-{
-    const unsigned long long a = (unsigned long long)p;
-    u32x4 w;
-    w.x = __builtin_amdgcn_readfirstlane((unsigned int)a);
-    w.y = __builtin_amdgcn_readfirstlane((unsigned int)(a >> 32) & 0xFFFFu);
-    w.z = __builtin_amdgcn_readfirstlane(bytes);
-    w.w = 0x00020000u;
-    return w;
-}
-
-// Lanes of maskA fetch 64 B at byte offset `ofs` of buffer A, lanes of maskB at `ofs` of buffer B (range-checked: beyond the extent
-// a load returns 0 and touches no memory); the other lanes fetch nothing and their a..d are undefined.
-__device__ __forceinline__ void fetch64_two_buffers(u32x4 rsrcA, u32x4 rsrcB, int ofs, unsigned long long maskA,
-                                                    unsigned long long maskB, float4& a, float4& b, float4& c, float4& d)
-{
-    u32x4 va, vb, vc, vd;
-    unsigned long long sav;
-    asm volatile(
-        "s_mov_b64 %[sav], exec\n\t"
-        "s_and_b64 exec, %[sav], %[ma]\n\t"
-        "buffer_load_dwordx4 %[a], %[ofs], %[ra], 0 offen\n\t"
-        "buffer_load_dwordx4 %[b], %[ofs], %[ra], 0 offen offset:16\n\t"
-        "buffer_load_dwordx4 %[c], %[ofs], %[ra], 0 offen offset:32\n\t"
-        "buffer_load_dwordx4 %[d], %[ofs], %[ra], 0 offen offset:48\n\t"
-        "s_and_b64 exec, %[sav], %[mb]\n\t"
-        "buffer_load_dwordx4 %[a], %[ofs], %[rb], 0 offen\n\t"
-        "buffer_load_dwordx4 %[b], %[ofs], %[rb], 0 offen offset:16\n\t"
-        "buffer_load_dwordx4 %[c], %[ofs], %[rb], 0 offen offset:32\n\t"
-        "buffer_load_dwordx4 %[d], %[ofs], %[rb], 0 offen offset:48\n\t"
-        "s_mov_b64 exec, %[sav]\n\t"
-        "s_waitcnt vmcnt(0)"
-        : [a] "=&v"(va), [b] "=&v"(vb), [c] "=&v"(vc), [d] "=&v"(vd), [sav] "=&s"(sav)
-        : [ofs] "v"(ofs), [ra] "s"(rsrcA), [rb] "s"(rsrcB), [ma] "s"(maskA), [mb] "s"(maskB)
-        : "memory", "scc");   // (s_and_b64 writes SCC)
-    a = make_float4(__uint_as_float(va.x), __uint_as_float(va.y), __uint_as_float(va.z), __uint_as_float(va.w));
-    b = make_float4(__uint_as_float(vb.x), __uint_as_float(vb.y), __uint_as_float(vb.z), __uint_as_float(vb.w));
-    c = make_float4(__uint_as_float(vc.x), __uint_as_float(vc.y), __uint_as_float(vc.z), __uint_as_float(vc.w));
-    d = make_float4(__uint_as_float(vd.x), __uint_as_float(vd.y), __uint_as_float(vd.z), __uint_as_float(vd.w));
-}
-
-// The same loads INTO registers that already hold other lanes' data (read-write operands: lanes outside both masks keep theirs).
-__device__ __forceinline__ void fetch64_two_buffers_into(u32x4 rsrcA, u32x4 rsrcB, int ofs, unsigned long long maskA,
-                                                         unsigned long long maskB, float4& a, float4& b, float4& c, float4& d)
-{
-    u32x4 va = {__float_as_uint(a.x), __float_as_uint(a.y), __float_as_uint(a.z), __float_as_uint(a.w)};
-    u32x4 vb = {__float_as_uint(b.x), __float_as_uint(b.y), __float_as_uint(b.z), __float_as_uint(b.w)};
-    u32x4 vc = {__float_as_uint(c.x), __float_as_uint(c.y), __float_as_uint(c.z), __float_as_uint(c.w)};
-    u32x4 vd = {__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(d.w)};
-    unsigned long long sav;
-    asm volatile(
-        "s_mov_b64 %[sav], exec\n\t"
-        "s_and_b64 exec, %[sav], %[ma]\n\t"
-        "buffer_load_dwordx4 %[a], %[ofs], %[ra], 0 offen\n\t"
-        "buffer_load_dwordx4 %[b], %[ofs], %[ra], 0 offen offset:16\n\t"
-        "buffer_load_dwordx4 %[c], %[ofs], %[ra], 0 offen offset:32\n\t"
-        "buffer_load_dwordx4 %[d], %[ofs], %[ra], 0 offen offset:48\n\t"
-        "s_and_b64 exec, %[sav], %[mb]\n\t"
-        "buffer_load_dwordx4 %[a], %[ofs], %[rb], 0 offen\n\t"
-        "buffer_load_dwordx4 %[b], %[ofs], %[rb], 0 offen offset:16\n\t"
-        "buffer_load_dwordx4 %[c], %[ofs], %[rb], 0 offen offset:32\n\t"
-        "buffer_load_dwordx4 %[d], %[ofs], %[rb], 0 offen offset:48\n\t"
-        "s_mov_b64 exec, %[sav]\n\t"
-        "s_waitcnt vmcnt(0)"
-        : [a] "+v"(va), [b] "+v"(vb), [c] "+v"(vc), [d] "+v"(vd), [sav] "=&s"(sav)
-        : [ofs] "v"(ofs), [ra] "s"(rsrcA), [rb] "s"(rsrcB), [ma] "s"(maskA), [mb] "s"(maskB)
-        : "memory", "scc");   // (s_and_b64 writes SCC)
-    a = make_float4(__uint_as_float(va.x), __uint_as_float(va.y), __uint_as_float(va.z), __uint_as_float(va.w));
-    b = make_float4(__uint_as_float(vb.x), __uint_as_float(vb.y), __uint_as_float(vb.z), __uint_as_float(vb.w));
-    c = make_float4(__uint_as_float(vc.x), __uint_as_float(vc.y), __uint_as_float(vc.z), __uint_as_float(vc.w));
-    d = make_float4(__uint_as_float(vd.x), __uint_as_float(vd.y), __uint_as_float(vd.z), __uint_as_float(vd.w));
-}
-
-// The two buffers of a unified fetch, as plain pointers + extents (FLAT = true: one set of four global loads for all live lanes) and as
-// descriptor words (the range-checked two-buffer form: lanes whose 64 bytes would cross the end of their buffer, FLAT = false).
-struct UnifiedBufs {
-    const char* nodes; const char* woop;
-    unsigned int nodesBytes, woopBytes;
-    u32x4 rNodes, rWoop;
-    bool uniformPrologue;   // per-ray kernels: scalar fetches while the wave's lanes all hold the same inner node (TraceParams::uniformPrologue)
-    bool certainSteps;      // ... and their steps decided by comparisons where the slab test's outcome is certain (TraceParams::certainSteps; boxes lo <= hi)
-    bool certainDescent;    // ... and the node kept a scalar from one such step to the next while every live lane takes the same child (TraceParams::certainDescent)
-    // FLAT fetch: both buffers lie inside one 4 GiB window (the host checks it before it selects the flat fetch), so a lane's 64 bytes
-    // are base + a 32-bit offset -- the global load takes the scalar base and the lane's offset as they are, where two unrelated 64-bit
-    // pointers cost every iteration a per-lane 64-bit select and add (round 5)
-    const char* base;       // the lower of the two buffers
-    unsigned int dN, dW;    // nodes - base, woop - base
-    unsigned int limNode;   // largest inner-node offset whose 64 bytes lie inside the node buffer (below the sentinel: `node <= limNode` implies inner)
-    int limTri;             // smallest (most negative) triangle cursor ~index whose 64 bytes lie inside triWoop
-};
-__device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
-{
-    UnifiedBufs u;
-    u.nodes = (const char*)p.nodes; u.woop = (const char*)p.woop;
-    u.nodesBytes = p.nodesBytes; u.woopBytes = p.woopBytes;
-    u.rNodes = rsrc_words(p.nodes, p.nodesBytes); u.rWoop = rsrc_words(p.woop, p.woopBytes);
-    u.uniformPrologue = p.uniformPrologue != 0;
-    u.certainSteps = p.certainSteps != 0 && (p.bvhFlags & NTR_BVH_ORDERED) != 0;
-    u.certainDescent = p.certainDescent != 0;
-    const unsigned long long an = (unsigned long long)p.nodes, aw = (unsigned long long)p.woop;
-    const unsigned long long lo = an < aw ? an : aw;
-    u.base = (const char*)lo;
-    u.dN = (unsigned int)(an - lo); u.dW = (unsigned int)(aw - lo);
-    u.limNode = p.nodesBytes - 64u;
-    u.limTri = ~(int)((p.woopBytes - 64u) >> 4);
-    return u;
-}
-
-// FLAT: the texture-address unit charges a wave-level load instruction about 16 cycles whatever its exec mask, so the two masked
-// groups of fetch64_two_buffers cost 128 TA cycles per iteration and made the unified loop TA-bound (0.6-0.87 busy, profiles/r03v_*).
-// With FLAT every live lane forms the 64-bit address of its own 64 bytes and ONE group of four global loads serves nodes and triangles
-// alike (64 TA cycles).  Global loads are not range-checked: a lane whose 64 bytes would end beyond its buffer (an empty leaf's
-// terminator in the last 48 bytes of triWoop; a malformed child offset) takes the descriptor path instead, which reads zeros there.
-// One unified step, in two halves (the two-rays-per-lane experiment of round 5 stepped two rays per iteration with them: 24 % slower --
-// 85 VGPRs, five waves per SIMD; scripts/studies/rejected_patches/two_rays_per_lane.patch, EXPERIMENTS.md).
-// unified_fetch: one 64-byte fetch per lane from its own buffer -- the node of a lane at an inner node, the triangle (48 B + the following
-// word) of a lane at a leaf.  Issues the loads and, apart from the rare end-of-buffer lanes, does not wait for them.
-template <bool FLAT>
-__device__ __forceinline__ void unified_fetch(const UnifiedBufs& ub, int node, float4& a, float4& b, float4& c, float4& d)
-{
-    const bool inner = (unsigned)node < (unsigned)kSentinel;
-    const bool atTri = node < 0;
-    // (Written as `inner ? ld4(nodes, ..) : ld4(woop, ..)` hipcc selects the descriptor per lane and wraps every load in a waterfall loop.)
-    if (FLAT) {
-        asm volatile("" : "=v"(a.x), "=v"(a.y), "=v"(a.z), "=v"(a.w), "=v"(b.x), "=v"(b.y), "=v"(b.z), "=v"(b.w));   // defined, whatever the lane
-        asm volatile("" : "=v"(c.x), "=v"(c.y), "=v"(c.z), "=v"(c.w), "=v"(d.x), "=v"(d.y), "=v"(d.z), "=v"(d.w));
-        const bool okNode = (unsigned)node <= ub.limNode, okTri = atTri && node >= ub.limTri;   // (extents are >= 64 here)
-        const bool flatOk = okNode || okTri;
-        const unsigned int cofs = okNode ? ub.dN + (unsigned)node : ub.dW + ((unsigned)(~node) << 4);   // from the scalar base: a 32-bit offset
-        if (flatOk) {   // (global address space spelled out: the base comes out of integer arithmetic, and a generic pointer would be a flat_load)
-            typedef const __attribute__((address_space(1))) u32x4* global_u4_ptr;
-            const global_u4_ptr q = (global_u4_ptr)((const __attribute__((address_space(1))) char*)ub.base + cofs);
-            const u32x4 qa = q[0], qb = q[1], qc = q[2], qd = q[3];
-            a = make_float4(__uint_as_float(qa.x), __uint_as_float(qa.y), __uint_as_float(qa.z), __uint_as_float(qa.w));
-            b = make_float4(__uint_as_float(qb.x), __uint_as_float(qb.y), __uint_as_float(qb.z), __uint_as_float(qb.w));
-            c = make_float4(__uint_as_float(qc.x), __uint_as_float(qc.y), __uint_as_float(qc.z), __uint_as_float(qc.w));
-            d = make_float4(__uint_as_float(qd.x), __uint_as_float(qd.y), __uint_as_float(qd.z), __uint_as_float(qd.w));
-        }
-        const unsigned long long odd = __ballot((inner || atTri) && !flatOk);
-        if (odd != 0ull)   // rare: range-checked descriptor loads, into the same registers, for the lanes at the very end of a buffer
-            fetch64_two_buffers_into(ub.rNodes, ub.rWoop, inner ? node : (~node) * 16, __ballot(inner && !flatOk), __ballot(atTri && !flatOk), a, b, c, d);
-    } else {
-        const int ofs = inner ? node : (~node) * 16;   // four loads under the inner lanes' mask and four under the triangle lanes' mask into the SAME registers, one wait
-        fetch64_two_buffers(ub.rNodes, ub.rWoop, ofs, __ballot(inner), __ballot(atTri), a, b, c, d);
-    }
-}
-
-// unified_advance: the lane's ray takes the step its 64 bytes allow -- one inner node (trace<BVHLayout_Compact>, CudaBVH.cpp:721-775) or one
-// triangle (intersectTriangles + updateHit, CudaBVH.cpp:1084-1126, 1183-1225).
-// one inner node of trace<BVHLayout_Compact> (CudaBVH.cpp:721-775): both child boxes, nearer child first (ties -> child 0), the other pushed
-template <bool FAST, int OCT, int LD = LDS_DEPTH>
-__device__ __forceinline__ void inner_advance(const float4& a, const float4& b, const float4& c, const float4& d, const RayRegs& r, int& node,
-                                              LaneStack& st, int (&spill)[SPILL_DEPTH], unsigned int* status)
-{
-    float mn0, mx0, mn1, mx1;
-    ray_box2<FAST, OCT>(r, a, b, c, mn0, mx0, mn1, mx1);
-    const bool i0 = (mn0 <= mx0) && (mx0 >= r.tmin) && (mn0 <= r.tmax);
-    const bool i1 = (mn1 <= mx1) && (mx1 >= r.tmin) && (mn1 <= r.tmax);
-    const int c0 = __float_as_int(d.x), c1 = __float_as_int(d.y);
-    const bool swp = i1 && (!i0 || mn0 > mn1);
-    const int nearC = swp ? c1 : c0, farC = swp ? c0 : c1;
-    if (i0 && i1) stack_push<LD>(st, spill, farC, status);
-    node = (i0 || i1) ? nearC : stack_pop<LD>(st, spill);
-}
-
-template <bool FAST, int OCT, int LD = LDS_DEPTH>
-__device__ __forceinline__ void unified_advance(const float4& a, const float4& b, const float4& c, const float4& d, RayRegs& r, int& node,
-                                                LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
-                                                unsigned int* status)
-{
-    const bool inner = (unsigned)node < (unsigned)kSentinel;
-    const bool atTri = node < 0;
-    if (inner) {
-        inner_advance<FAST, OCT, LD>(a, b, c, d, r, node, st, spill, status);
-    } else if (atTri) {
-        bool leafDone = __float_as_uint(a.x) == 0x80000000u;   // terminator: an empty leaf
-        if (!leafDone) {
-            const float Oz = a.w - r.ox * a.x - r.oy * a.y - r.oz * a.z;
-            const float ooDz = 1.0f / dot4(a, r.dx, r.dy, r.dz, 0.0f);
-            const float t = Oz * ooDz;
-            float tt = FLT_MAX, uu = 0.0f, vv = 0.0f;
-            if (t > r.tmin && t < r.tmax) {
-                const float u = dot4(b, r.ox, r.oy, r.oz, 1.0f) + t * dot4(b, r.dx, r.dy, r.dz, 0.0f);
-                if (u >= 0.0f) {
-                    const float v = dot4(c, r.ox, r.oy, r.oz, 1.0f) + t * dot4(c, r.dx, r.dy, r.dz, 0.0f);
-                    if (v >= 0.0f && (u + v) <= 1.0f) { tt = t; uu = u; vv = v; }
-                }
-            }
-            bool terminated = false;
-            if (tt > r.tmin && tt < r.tmax) {
-                r.tmax = tt;
-                hitAddr = ~node;
-                hitU = uu;
-                hitV = vv;
-                terminated = anyHit;
-            }
-            if (terminated) node = kSentinel;
-            else if (__float_as_uint(d.x) == 0x80000000u) leafDone = true;   // the terminator came with this triangle
-            else node -= 3;
-        }
-        if (leafDone) node = stack_pop<LD>(st, spill);
-    }
-}
-
-// Wave-uniform prologue (round 5).  The rays of a fresh wave all start at the root, and the rays of one wave -- an 8 x 8 pixel tile, or
-// the AO samples of eight neighbouring pixels -- take the same way down the top of the tree: while every live lane holds the SAME inner
-// node, that node is fetched ONCE through the scalar cache (s_load, no texture-path cycles: the per-lane fetch costs the TA 64 cycles per
-// wave and iteration whatever the lanes hold) and the planes are scalar operands of the same arithmetic.  The loop ends for good at the
-// first iteration in which the lanes disagree, or hold a leaf: the test (one v_readlane, one compare) is paid only while it succeeds --
-// run on EVERY iteration it cost more than the fetches it saved (round 2), and looking again every 2 / 4 / 8 / 16 iterations of the
-// general loop loses 1-4 % (profiles/r05_uniform_recheck_knob.txt): once apart, the lanes of a wave rarely all meet again.  Measured
-// and left out as well: the same for a triangle every lane stands at (no gain, and 2.5 % lost to the larger loop:
-// profiles/r05_uniform_prologue_levels_knob.txt), and the prologue after a persistent wave's refill (nothing).  Per-ray arithmetic, visiting order and
-// stack are untouched: hit records cannot change.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) f32x4* const_f32x4_ptr;   // constant address space: a wave-uniform load becomes s_load
-
-// CERTAIN (per-ray kernels, TraceParams::certainSteps): certain steps.  A short ray near the top of the tree -- an AO ray of length 5 in a
-// 3 600-unit hall, 1e-4 off the surface it starts from -- has its origin inside one child box while the sibling is out of its reach, and
-// plain comparisons of the planes against per-ray constants decide that exactly as the twelve quotients of the slab test would.
-// Per ray and axis k, once per wave: the segment [segLo[k], segHi[k]] that contains the ray's extent on that axis.  The origin side is
-// o[k] itself; the far side is o[k] +- reach[k] rounded outward (certain_reach, certain_end).  Per step and child c:
-//   inside_c: lo_c[k] <= o[k] <= hi_c[k] on the three axes;    out_c: lo_c[k] > segHi[k] or hi_c[k] < segLo[k] on some axis.
-// A lane is certain when (inside_0 && out_1) || (inside_1 && out_0); when EVERY live lane is, each takes the child it is inside, nothing
-// is pushed and no quotient is formed.  Otherwise the step is inner_advance as before.
-// Why the outcome is the slab test's own (FAST ranges above: no NaN, no zero divisor, every x = plane - o and every quotient is 0 or a
-// normal number; tmin == 0; boxes lo <= hi; u = 2^-24; the quotient of the FAST path is the correctly rounded one, trace_arith.h):
-//  (a) RN(a - b) has the sign of a - b and RN(x / d) the sign of x / d (0 only for x == 0).  So for inside_c the near quotient of every axis
-//      is <= 0 and the far one >= 0, whichever way d points: mn <= 0 <= mx, mx >= 0 = tmin, mn <= 0 < tmax (a live ray has tmin < tmax; no
-//      leaf is visited in the prologue, so tmax is still the ray's own).  All three accept tests hold: the child is accepted.
-//  (b) Behind the origin.  d > 0: segLo = o, and hi_c < o makes the far quotient RN(RN(hi_c - o) / d) < 0.  d < 0: segHi = o, and lo_c > o
-//      makes the far quotient RN(RN(lo_c - o) / d) < 0.  Either way mx < 0 = tmin: rejected.  No margin is needed.
-//  (c) Beyond the reach.  d > 0: lo_c > segHi >= o + reach (real numbers, certain_end) gives x = lo_c - o > reach >= tmax |d| (1 + 13 u)
-//      (certain_reach).  RN(x) >= x (1 - u), and the exact quotient of that by d is >= tmax (1 + 13 u)(1 - u) > tmax (1 + 2 u), which is at
-//      least the float after tmax, so by monotone rounding the near quotient is > tmax.  d < 0: the same with hi_c < segLo <= o - reach and
-//      the near plane hi_c.  So mn > tmax: rejected.
-//  (d) inside_c and out_c exclude each other (segLo <= o <= segHi), so a certain lane accepts exactly one child: no ordering decision, no push.
-// The test costs 12 to 24 VALU against the 88 of the exact step; a wave whose lanes are uncertain twice in a row stops asking.
-// Carried descent (TraceParams::certainDescent).  A certain step in which every live lane is inside the SAME child c gives every live lane
-// the node c, pushes nothing and leaves tmax alone; the loop top would then read c back out of the first live lane and find the lanes
-// agreed.  So while c is an inner node whose record lies inside the buffer (the loop top's own test) the wave keeps it in a scalar register
-// and loads the next record at once: about 30 instructions a step where writing c to the lanes and proving them uniform again issues
-// about 75.  The lanes are written once, when the run ends: the lanes part (certain, both children taken), some lane is uncertain (the
-// exact step runs on the record already loaded, counted as uncertain as before), or the child is a leaf.  There node, stack and tmax of
-// every lane are what the per-step path has at the same step, and lanes at kSentinel are never written.  The predicate is certain_masks'
-// either way, so (a)-(d) are the whole argument.
-static constexpr int kCertainGiveUpAfter = 2;   // consecutive uncertain steps after which a wave runs the exact prologue only
-
-// reach >= tmax |d| (1 + 13 u): p = RN(tmax |d|) >= tmax |d| (1 - u) while p is normal, and RN(p (1 + 2^-20)) >= p (1 + 16 u)(1 - u).  A product
-// too small for that argument (or not a number) makes the far side unbounded: such a ray is never certain there.  tmax = inf likewise.
-__device__ __forceinline__ float certain_reach(float tmax, float d)
-{
-    const float p = tmax * fabsf(d);
-    return (p >= 0x1p-100f) ? p * 0x1.00001p0f : __builtin_inff();
-}
-// The far end o + reach (SIGN = +1) or o - reach (SIGN = -1), rounded outward: s = RN(o +- reach) is off by at most half an ulp of s -- a
-// large loss relative to reach when |o| >> reach -- and |s| 2^-22 is two to four ulp of s (|s| < 2^-100 happens only when o and reach
-// cancel, and then the sum is exact), so the result lies on the far side of the real o +- reach, and of o.  (Comparing a PLANE against s
-// would already be safe -- a float above RN(y) is above y, rounding being monotone; the step outward is margin, one fma per axis and wave.)
-template <int SIGN>
-__device__ __forceinline__ float certain_end(float o, float reach)
-{
-    const float s = SIGN > 0 ? o + reach : o - reach;
-    return __builtin_fmaf(fabsf(s), SIGN > 0 ? 0x1p-22f : -0x1p-22f, s);
-}
-
-// The comparisons of a certain step as lane masks, for the lanes of `live`: in0 = origin inside the closed box of child 0; in1 = the other lanes
-// whose origin is inside child 1; reach = lanes of in0 / in1 whose sibling box is NOT out of reach (lo <= segHi and hi >= segLo on every axis).
-// The wave is certain when in0 | in1 == live and reach == 0.  (A lane inside both boxes counts for in0 and then shows in `reach`: its sibling
-// holds the origin.)  Each conjunction of six comparisons is a chain of v_cmpx, which narrows EXEC as it goes: twelve to twenty-four VALU
-// instructions and no mask arithmetic -- written as `a <= x && x <= b && ...` the compiler forms every comparison into an SGPR pair and
-// folds them with one scalar instruction each, about 50 SALU a step that wait for the VALU one by one (measured: VALU -12 %, SALU +19 %, no
-// time gained).  Planes are scalar operands (the node came through the scalar cache).
-// Returns the wave's next node where it is a scalar: the child word c0 (c1) when the wave is certain AND every live lane is inside child 0
-// (child 1) -- in0 (in1) == live, reach == 0 -- and kSentinel otherwise.  The common case, every live lane inside child 0, is tested first and
-// costs the twelve v_cmpx and eight scalar instructions; the masks are the same whichever path formed them.
-__device__ __forceinline__ int certain_masks(f32x4 A, f32x4 B, f32x4 C, int c0, int c1, const RayRegs& r, float loX, float hiX, float loY, float hiY,
-                                             float loZ, float hiZ, unsigned long long live, unsigned long long& in0, unsigned long long& in1,
-                                             unsigned long long& reach)
-{
-    unsigned long long sav;
-    int next;
-    asm volatile(
-        "s_mov_b64 %[sav], exec\n\t"
-        "s_mov_b32 %[next], %[none]\n\t"
-        "s_and_b64 exec, %[sav], %[live]\n\t"
-        "v_cmpx_le_f32 vcc, %[ax], %[ox]\n\t"      // inside child 0: lo <= o && hi >= o per axis
-        "v_cmpx_ge_f32 vcc, %[ay], %[ox]\n\t"
-        "v_cmpx_le_f32 vcc, %[az], %[oy]\n\t"
-        "v_cmpx_ge_f32 vcc, %[aw], %[oy]\n\t"
-        "v_cmpx_le_f32 vcc, %[cx], %[oz]\n\t"
-        "v_cmpx_ge_f32 vcc, %[cy], %[oz]\n\t"
-        "s_mov_b64 %[in0], exec\n\t"
-        "s_cmp_eq_u64 %[in0], %[live]\n\t"
-        "s_cbranch_scc0 .Lcs_g%=\n\t"
-        "s_mov_b64 %[in1], 0\n\t"                   // every live lane is inside child 0: child 1 within reach of any?
-        "v_cmpx_le_f32 vcc, %[bx], %[hx]\n\t"
-        "v_cmpx_ge_f32 vcc, %[by], %[lx]\n\t"
-        "v_cmpx_le_f32 vcc, %[bz], %[hy]\n\t"
-        "v_cmpx_ge_f32 vcc, %[bw], %[ly]\n\t"
-        "v_cmpx_le_f32 vcc, %[cz], %[hz]\n\t"
-        "v_cmpx_ge_f32 vcc, %[cw], %[lz]\n\t"
-        "s_mov_b64 %[reach], exec\n\t"
-        "s_cbranch_execnz .Lcs_e%=\n\t"
-        "s_mov_b32 %[next], %[c0]\n\t"
-        "s_branch .Lcs_e%=\n"
-        ".Lcs_g%=:\n\t"
-        "s_and_b64 exec, %[sav], %[live]\n\t"
-        "s_andn2_b64 exec, exec, %[in0]\n\t"      // the other live lanes: inside child 1?
-        "s_cbranch_execz .Lcs_a%=\n\t"
-        "v_cmpx_le_f32 vcc, %[bx], %[ox]\n\t"
-        "v_cmpx_ge_f32 vcc, %[by], %[ox]\n\t"
-        "v_cmpx_le_f32 vcc, %[bz], %[oy]\n\t"
-        "v_cmpx_ge_f32 vcc, %[bw], %[oy]\n\t"
-        "v_cmpx_le_f32 vcc, %[cz], %[oz]\n\t"
-        "v_cmpx_ge_f32 vcc, %[cw], %[oz]\n\t"
-        "s_cbranch_execz .Lcs_a%=\n\t"
-        "s_mov_b64 %[in1], exec\n\t"
-        "v_cmpx_le_f32 vcc, %[ax], %[hx]\n\t"      // ... and child 0 within their reach?  lo <= segHi && hi >= segLo per axis
-        "v_cmpx_ge_f32 vcc, %[ay], %[lx]\n\t"
-        "v_cmpx_le_f32 vcc, %[az], %[hy]\n\t"
-        "v_cmpx_ge_f32 vcc, %[aw], %[ly]\n\t"
-        "v_cmpx_le_f32 vcc, %[cx], %[hz]\n\t"
-        "v_cmpx_ge_f32 vcc, %[cy], %[lz]\n\t"
-        "s_mov_b64 %[reach], exec\n\t"
-        "s_branch .Lcs_b%=\n"
-        ".Lcs_a%=:\n\t"
-        "s_mov_b64 %[in1], 0\n\t"
-        "s_mov_b64 %[reach], 0\n"
-        ".Lcs_b%=:\n\t"
-        "s_mov_b64 exec, %[in0]\n\t"
-        "s_cbranch_execz .Lcs_c%=\n\t"
-        "v_cmpx_le_f32 vcc, %[bx], %[hx]\n\t"      // the lanes inside child 0: child 1 within their reach?
-        "v_cmpx_ge_f32 vcc, %[by], %[lx]\n\t"
-        "v_cmpx_le_f32 vcc, %[bz], %[hy]\n\t"
-        "v_cmpx_ge_f32 vcc, %[bw], %[ly]\n\t"
-        "v_cmpx_le_f32 vcc, %[cz], %[hz]\n\t"
-        "v_cmpx_ge_f32 vcc, %[cw], %[lz]\n\t"
-        "s_or_b64 %[reach], %[reach], exec\n"
-        ".Lcs_c%=:\n\t"
-        "s_cmp_eq_u64 %[in1], %[live]\n\t"          // every live lane inside child 1 and child 0 out of everyone's reach?
-        "s_cbranch_scc0 .Lcs_e%=\n\t"
-        "s_cmp_eq_u64 %[reach], 0\n\t"
-        "s_cselect_b32 %[next], %[c1], %[next]\n"
-        ".Lcs_e%=:\n\t"
-        "s_mov_b64 exec, %[sav]"
-        : [sav] "=&s"(sav), [in0] "=&s"(in0), [in1] "=&s"(in1), [reach] "=&s"(reach), [next] "=&s"(next)
-        : [live] "s"(live), [ax] "s"(A.x), [ay] "s"(A.y), [az] "s"(A.z), [aw] "s"(A.w), [bx] "s"(B.x), [by] "s"(B.y), [bz] "s"(B.z), [bw] "s"(B.w),
-          [cx] "s"(C.x), [cy] "s"(C.y), [cz] "s"(C.z), [cw] "s"(C.w), [c0] "s"(c0), [c1] "s"(c1), [none] "i"(kSentinel), [ox] "v"(r.ox), [oy] "v"(r.oy),
-          [oz] "v"(r.oz), [lx] "v"(loX), [hx] "v"(hiX), [ly] "v"(loY), [hy] "v"(hiY), [lz] "v"(loZ), [hz] "v"(hiZ)
-        : "vcc", "scc");
-    return next;
-}
-// node = c0 in the lanes of m0, c1 in the lanes of m1 (disjoint); the other lanes keep theirs
-__device__ __forceinline__ void take_children(int& node, int c0, int c1, unsigned long long m0, unsigned long long m1)
-{
-    unsigned long long sav;
-    asm volatile(
-        "s_mov_b64 %[sav], exec\n\t"
-        "s_mov_b64 exec, %[m1]\n\t"
-        "v_mov_b32 %[node], %[c1]\n\t"
-        "s_mov_b64 exec, %[m0]\n\t"
-        "v_mov_b32 %[node], %[c0]\n\t"
-        "s_mov_b64 exec, %[sav]"
-        : [sav] "=&s"(sav), [node] "+v"(node)
-        : [m0] "s"(m0), [m1] "s"(m1), [c0] "s"(c0), [c1] "s"(c1));
-}
-
-template <bool FAST, int OCT, bool CERTAIN = false>
-__device__ __forceinline__ void uniform_prologue(const UnifiedBufs& ub, const RayRegs& r, int& node, LaneStack& st, int (&spill)[SPILL_DEPTH],
-                                                 unsigned int* status)
-{
-    if ((reinterpret_cast<unsigned long long>(ub.nodes) & 63ull) != 0ull) return;   // (s_load_dwordx16 wants the record 64-byte aligned)
-    // certain steps: wave-uniform preconditions, checked once (FAST is the caller's fastWave)
-    bool tryCertain = false;
-    int uncertain = 0;
-    float loX = 0.0f, hiX = 0.0f, loY = 0.0f, hiY = 0.0f, loZ = 0.0f, hiZ = 0.0f;   // segLo / segHi
-    if (CERTAIN && FAST) {
-        tryCertain = ub.certainSteps && __ballot(node != kSentinel && r.tmin != 0.0f) == 0ull;
-        if (tryCertain) {
-            const float fx = certain_reach(r.tmax, r.dx), fy = certain_reach(r.tmax, r.dy), fz = certain_reach(r.tmax, r.dz);
-            loX = r.dx < 0.0f ? certain_end<-1>(r.ox, fx) : r.ox; hiX = r.dx < 0.0f ? r.ox : certain_end<1>(r.ox, fx);
-            loY = r.dy < 0.0f ? certain_end<-1>(r.oy, fy) : r.oy; hiY = r.dy < 0.0f ? r.oy : certain_end<1>(r.oy, fy);
-            loZ = r.dz < 0.0f ? certain_end<-1>(r.oz, fz) : r.oz; hiZ = r.dz < 0.0f ? r.oz : certain_end<1>(r.oz, fz);
-        }
-    }
-    // carried certain descent: a child word c is the wave's next scalar node when 1 <= c <= descentLim -- an inner node whose 64 bytes lie
-    // inside the buffer (the test of the loop top below; 0, the root, is no child of a well-formed tree and goes through the lanes); 0 = off
-    unsigned int descentLim = !ub.certainDescent ? 0u : ub.nodesBytes - 64u < (unsigned)kSentinel ? ub.nodesBytes - 64u : (unsigned)kSentinel - 1u;
-    asm volatile("" : "+s"(descentLim));   // (one number to compare with: left to see through it, the compiler tests the switch again on every step)
-    for (;;) {
-        const bool live = node != kSentinel;
-        const unsigned long long liveMask = __ballot(live);
-        if (liveMask == 0ull) return;
-        const int unode = __builtin_amdgcn_readlane(node, (int)__builtin_ctzll(liveMask));   // the first live lane's node: a scalar
-        if (__ballot(live && node != unode) != 0ull) return;                                  // the lanes disagree: the general loop from here on
-        if ((unsigned)unode >= (unsigned)kSentinel || (unsigned)unode > ub.nodesBytes - 64u) return;   // a leaf (or a malformed offset): likewise
-        unsigned int snode = (unsigned)unode;   // the wave's node while it is a scalar (carried certain descent)
-        f32x4 A, B, C, D;
-        if (CERTAIN && FAST && tryCertain) {
-            unsigned long long in0, in1, reach;
-            for (;;) {
-                const const_f32x4_ptr q = (const_f32x4_ptr)(ub.nodes + snode);
-                A = q[0]; B = q[1]; C = q[2]; D = q[3];
-                const int next = certain_masks(A, B, C, __float_as_int(D.x), __float_as_int(D.y), r, loX, hiX, loY, hiY, loZ, hiZ, liveMask, in0, in1, reach);
-                if ((unsigned)next - 1u >= descentLim) break;   // not certain, the lanes part, or the child is a leaf (beyond the extent): the lanes take over
-                snode = (unsigned)next;                   // certain, every live lane to the same inner child: nothing to write, the next record
-            }
-            if (snode != (unsigned)unode) {               // carried steps were certain steps: the lanes arrive where they would have stepped to
-                if (live) node = (int)snode;
-                uncertain = 0;
-            }
-            if ((in0 | in1) == liveMask && reach == 0ull) {
-                take_children(node, __float_as_int(D.x), __float_as_int(D.y), in0, in1);
-                uncertain = 0;
-                continue;
-            }
-            if (++uncertain >= kCertainGiveUpAfter) tryCertain = false;
-        } else {
-            const const_f32x4_ptr q = (const_f32x4_ptr)(ub.nodes + snode);
-            A = q[0]; B = q[1]; C = q[2]; D = q[3];
-        }
-        if (live)
-            inner_advance<FAST, OCT>(make_float4(A.x, A.y, A.z, A.w), make_float4(B.x, B.y, B.z, B.w), make_float4(C.x, C.y, C.z, C.w),
-                                     make_float4(D.x, D.y, D.z, D.w), r, node, st, spill, status);
-    }
-}
-
 // SLICED (persistent kernels): the loop also ends after `slice` iterations (`slice` counts down: the caller posts the dequeue of the wave's
 // next chunk, or -- drain phase -- looks at the wave's lanes again: split_settle / split_donate, trace_split.h).
-template <bool FAST, bool FLAT, int OCT, bool PROLOGUE, bool SLICED>
+template <bool FAST, bool FLAT, int OCT = 8, bool PROLOGUE = false, bool SLICED = false>
 __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs& r, int& node, LaneStack& st,
                                                  int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
-                                                 unsigned int* status, bool poolEmpty, int fetchThreshold, int& slice)
+                                                 unsigned int* status, bool poolEmpty, int fetchThreshold, int* slice = nullptr)
 {
     if (PROLOGUE && ub.uniformPrologue) uniform_prologue<FAST, OCT, true>(ub, r, node, st, spill, status);   // (PROLOGUE: the per-ray kernels)
     for (;;) {
@@ -819,25 +106,34 @@ __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs&
         if (live == 0ull) break;
         // dynamic fetch (kepler_dynamic_fetch.cu:310): too few live lanes while rays remain in the pool -> refill
         if (!poolEmpty && __popcll(live) < fetchThreshold) break;
-        if (SLICED && --slice < 0) break;
+        if (SLICED && --*slice < 0) break;
         float4 a, b, c, d;
         unified_fetch<FLAT>(ub, node, a, b, c, d);
         if (FLAT) { keep(a); keep(b); keep(c); keep(d); }
         unified_advance<FAST, OCT>(a, b, c, d, r, node, st, spill, anyHit, hitAddr, hitU, hitV, status);
     }
 }
-template <bool FAST, bool FLAT, int OCT = 8, bool PROLOGUE = false>
-__device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs& r, int& node, LaneStack& st,
-                                                 int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
-                                                 unsigned int* status, bool poolEmpty, int fetchThreshold)
+// A lane of a ray pool (the persistent kernels' refill, minipool_body) starts ray rayIdx at the root.  Returns whether the ray qualifies for the FAST path.
+__device__ __forceinline__ bool start_ray(const TraceParams& p, int rayIdx, RayRegs& r, int& node, LaneStack& st,
+                                          int& hitAddr, float& hitU, float& hitV)
 {
-    int never = 0;
-    traverse_unified<FAST, FLAT, OCT, PROLOGUE, false>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, status, poolEmpty, fetchThreshold, never);
+    load_ray(p.rays, rayIdx, r);
+    hitAddr = -1;
+    hitU = hitV = 0.0f;
+    stack_reset(st);
+    // tmin < tmax is necessary for any accept (t>tmin && t<tmax):
+    // degenerate rays (Util.hpp:65) are misses without traversal.
+    node = (r.tmin < r.tmax) ? 0 : kSentinel;
+    return ray_is_nice(r, p.bvhFlags);
 }
 
-}  // namespace ntr
-#include "trace_split.h"   // drain phase of the persistent waves: idle lanes take over parts of the wave's long rays
-namespace ntr {
+// a whole-wave refill's walk down the top of the tree through the scalar cache while the wave's rays agree (uniform_prologue)
+__device__ __forceinline__ void fresh_prologue(bool fastWave, const UnifiedBufs& ub, const RayRegs& r, int& node, LaneStack& st,
+                                               int (&spill)[SPILL_DEPTH], unsigned int* status)
+{
+    if (fastWave) uniform_prologue<true, 8>(ub, r, node, st, spill, status);
+    else uniform_prologue<false, 8>(ub, r, node, st, spill, status);
+}
 
 // ---------------------------------------------------------------------------------
 // Variant 1: one ray per lane ("fermi_speculative_while_while" slot).
@@ -884,7 +180,7 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
     LaneStack st;
     int spill[SPILL_DEPTH];
     st.lds = (lds_int*)&s_stack[wave][0][lane];
-    NTR_STACK_RESET(st);
+    stack_reset(st);
 
     int hitAddr = -1;
     float hitU = 0.0f, hitV = 0.0f;
@@ -1010,8 +306,7 @@ __global__ __launch_bounds__(WAVES * 64, NTR_TRACE_PERSISTENT_MIN_WAVES_PER_SIMD
     LaneStack st;
     int spill[SPILL_DEPTH];
     st.lds = (lds_int*)&s_stack[wave][0][lane];
-    st.sp = 0;
-    st.tos = kSentinel;
+    stack_reset(st);
 
     RayRegs r = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int node = kSentinel, rayIdx = -1, hitAddr = -1;
@@ -1127,21 +422,12 @@ __global__ __launch_bounds__(WAVES * 64, NTR_TRACE_PERSISTENT_MIN_WAVES_PER_SIMD
         const bool refill = !poolEmpty && (wholeWave || (dynamicFetch && 64 - __popcll(empty) < p.fetchThreshold));
         while (refill && empty != 0ull && !poolEmpty) {
             if (chunkNext >= chunkEnd && !grab()) { poolEmpty = true; break; }
-            // rank of this lane among the empty lanes (wave64 prefix popcount)
-            const int prefix = __builtin_amdgcn_mbcnt_hi((unsigned)(empty >> 32),
-                               __builtin_amdgcn_mbcnt_lo((unsigned)empty, 0));
+            const int prefix = lane_rank(empty);
             const int avail = chunkEnd - chunkNext;
             const int pos = chunkNext + prefix + chunkDelta;   // pool position -> ray index (beyond the batch: skipped)
             if (rayIdx < 0 && prefix < avail && pos < p.numRays) {
                 rayIdx = pos;
-                load_ray(p.rays, rayIdx, r);
-                hitAddr = -1;
-                hitU = hitV = 0.0f;
-                NTR_STACK_RESET(st);
-                // tmin < tmax is necessary for any accept (t>tmin && t<tmax):
-                // degenerate rays (Util.hpp:65) are misses without traversal.
-                node = (r.tmin < r.tmax) ? 0 : kSentinel;
-                nice = ray_is_nice(r, p.bvhFlags);
+                nice = start_ray(p, rayIdx, r, node, st, hitAddr, hitU, hitV);
             }
             chunkNext += min(__popcll(empty), avail);
             empty = __ballot(rayIdx < 0);
@@ -1163,21 +449,14 @@ __global__ __launch_bounds__(WAVES * 64, NTR_TRACE_PERSISTENT_MIN_WAVES_PER_SIMD
         const int fetchBelow = dynamicFetch ? p.fetchThreshold : 0;
         if (UNIFIED) {
             const UnifiedBufs ub = unified_bufs(p);
-            if (fresh && p.uniformPrologue) {   // the top of the tree through the scalar cache while the wave's rays agree (uniform_prologue)
-                if (fastWave) uniform_prologue<true, 8>(ub, r, node, st, spill, p.status);
-                else uniform_prologue<false, 8>(ub, r, node, st, spill, p.status);
-            }
-            if (fastWave) traverse_unified<true, FLATF, 8, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, fetchBelow, slice);
-            else traverse_unified<false, FLATF, 8, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, fetchBelow, slice);
+            if (fresh && p.uniformPrologue) fresh_prologue(fastWave, ub, r, node, st, spill, p.status);
+            if (fastWave) traverse_unified<true, FLATF, 8, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, fetchBelow, &slice);
+            else traverse_unified<false, FLATF, 8, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, fetchBelow, &slice);
             if (splitOn) split_settle(split, r, node, st, hitAddr, hitU, hitV, anyHit);
         } else {
-            if (fresh && p.uniformPrologue) {   // the top of the tree through the scalar cache while the wave's rays agree (uniform_prologue)
-                const UnifiedBufs ub = unified_bufs(p);
-                if (fastWave) uniform_prologue<true, 8>(ub, r, node, st, spill, p.status);
-                else uniform_prologue<false, 8>(ub, r, node, st, spill, p.status);
-            }
-            if (fastWave) traverse<true, false, true, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, slice);
-            else traverse<false, false, true, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, slice);
+            if (fresh && p.uniformPrologue) fresh_prologue(fastWave, unified_bufs(p), r, node, st, spill, p.status);
+            if (fastWave) traverse<true, false, true, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, &slice);
+            else traverse<false, false, true, true>(nodes, woop, r, node, st, spill, anyHit, hitAddr, hitU, hitV, ls, p.status, poolEmpty, fetchBelow, p.leafSwitchBelow, &slice);
         }
         // ---- dequeue-ahead: post the atomic of the wave's next chunk now (its latency hides behind the rest of this chunk) -------------
         if (!splitOn && prefetchIn >= 0 && !poolEmpty) {
@@ -1241,7 +520,7 @@ __device__ __forceinline__ void minipool_body(const TraceParams& p, unsigned int
     LaneStack st;
     int spill[SPILL_DEPTH];
     st.lds = stackBase;
-    NTR_STACK_RESET(st);
+    stack_reset(st);
     RayRegs r = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int node = kSentinel, rayIdx = -1, hitAddr = -1;
     float hitU = 0.0f, hitV = 0.0f;
@@ -1257,16 +536,11 @@ __device__ __forceinline__ void minipool_body(const TraceParams& p, unsigned int
         }
         const unsigned long long empty = __ballot(rayIdx < 0);
         if (empty != 0ull && poolNext < poolEnd) {
-            const int prefix = __builtin_amdgcn_mbcnt_hi((unsigned)(empty >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)empty, 0));
+            const int prefix = lane_rank(empty);
             const int avail = poolEnd - poolNext;
             if (rayIdx < 0 && prefix < avail) {
                 rayIdx = poolNext + prefix;
-                load_ray(p.rays, rayIdx, r);
-                hitAddr = -1;
-                hitU = hitV = 0.0f;
-                NTR_STACK_RESET(st);
-                node = (r.tmin < r.tmax) ? 0 : kSentinel;   // degenerate rays (Util.hpp:65) are misses without traversal
-                nice = ray_is_nice(r, p.bvhFlags);
+                nice = start_ray(p, rayIdx, r, node, st, hitAddr, hitU, hitV);
             }
             poolNext += min(__popcll(empty), avail);
         }

@@ -1,5 +1,4 @@
 // trace_split.h -- lanes of a wave that have run out of rays take over parts of the wave's long rays (round 5).
-// Included by trace_kernels.hip (needs RayRegs, LaneStack, kSentinel, LDS_DEPTH, NTR_STACK_RESET).
 //
 // Why.  A divergent closest-hit launch is bound by its longest ray: the 2^21 box rays over the 10 M-triangle tree take 86 steps on
 // average, the longest 3 500-3 700, and a step is a dependent fetch -- 1.2 us under load -- so the launch cannot end before
@@ -31,6 +30,7 @@
 // entry has finished without one -- the acceptance rule above --, and a lane that has a hit, its own or one it took over, drops the
 // slots it still has out instead of settling them: the lone ray would never have got there.
 #pragma once
+#include "trace_lane.h"
 
 namespace ntr {
 
@@ -53,10 +53,6 @@ __device__ __forceinline__ void split_reset(SplitState& s)
 __device__ __forceinline__ float split_shfl(float v, int l) { return __int_as_float(__builtin_amdgcn_ds_bpermute(l << 2, __float_as_int(v))); }
 __device__ __forceinline__ int split_shfl(int v, int l) { return __builtin_amdgcn_ds_bpermute(l << 2, v); }
 __device__ __forceinline__ float split_readlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ int split_rank(unsigned long long m)   // set bits of m below this lane
-{
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-}
 // the dead zone loses its top slot: the slot below becomes the top (its entry moves to the register, the sentinel takes its place)
 __device__ __forceinline__ void split_drop_top(SplitState& s, LaneStack& st)
 {
@@ -143,8 +139,8 @@ __device__ __forceinline__ void split_donate(SplitState& s, RayRegs& r, int& nod
     const unsigned long long donors = __ballot(can);
     if (donors == 0ull) return;
     const int pairs = min((int)__popcll(idleMask), (int)__popcll(donors));
-    const bool giving = can && split_rank(donors) < pairs;
-    const bool taking = idle && split_rank(idleMask) < pairs;
+    const bool giving = can && lane_rank(donors) < pairs;
+    const bool taking = idle && lane_rank(idleMask) < pairs;
     int give = kSentinel;
     if (giving) {
         give = st.lds[bottom * 64];
@@ -171,7 +167,7 @@ __device__ __forceinline__ void split_donate(SplitState& s, RayRegs& r, int& nod
         r.ox = ox; r.oy = oy; r.oz = oz; r.tmin = tmin; r.dx = dx; r.dy = dy; r.dz = dz; r.tmax = tmax; r.rx = rx; r.ry = ry; r.rz = rz;
         nice = gNice != 0;
         node = gNode;
-        NTR_STACK_RESET(st);
+        stack_reset(st);
         hitAddr = -1; hitU = hitV = 0.0f;
         split_reset(s);
         s.parent = D; s.slot = gSlot; s.bound0 = tmax; s.parentEpoch = gEpoch;
