@@ -18,6 +18,7 @@
 //   end             emit_leaf_rows (device_prims.h): every triangle's three Woop rows and its triIndex entries at its leaf row
 // Phases hand data over only at kernel boundaries.  The host reads one 32-byte record per level (the level's totals and the error
 // word) to size the next level; nothing else comes back until the build ends.  Outputs go straight into the caller's buffers.
+// The plane table, that read-back (read_totals) and the level's bookkeeping (LevelState) are level_build.h's.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
@@ -30,24 +31,15 @@
 #include <cmath>
 
 #include "ntr_internal.h"
-#include "compact_bvh.h"
-#include "device_prims.h"
-#include "device_scratch.h"
+#include "level_build.h"
 
 namespace ntr {
 namespace {
 
-constexpr int BV_PLANES = 32;
-constexpr int BV_PER_AXIS = (BV_PLANES + 2) / 3;       // 11: x and y get 11 planes, z gets 10
-constexpr int BV_BINS = 3 * (BV_PER_AXIS + 1) - 1;     // 12 + 12 + 11
+constexpr int BV_BINS = 3 * (kPlanesPerAxis + 1) - 1;  // 12 + 12 + 11
 constexpr int BV_SLOT = BV_BINS * 8 + 16;              // words per splitting task: 35 bins of 8 words, then the median boxes
-constexpr float BV_EPS = 1e-8f;                        // rt_common.cuh:37
 constexpr int BV_BLOCK = 256;
 constexpr int BV_MAX_DEPTH = 100;                      // CudaBVH.cpp:701: the CPU tracer's stack; the kernels hold 16 + 88
-
-// rpos = (float)(1 + k) / (float)(planesPerAxis + 1) (rt_common.cu:1013), folded by the compiler with IEEE rounding
-__constant__ float kBvRpos[BV_PER_AXIS] = {1.0f / 12.0f, 2.0f / 12.0f, 3.0f / 12.0f, 4.0f / 12.0f, 5.0f / 12.0f, 6.0f / 12.0f,
-                                           7.0f / 12.0f, 8.0f / 12.0f, 9.0f / 12.0f, 10.0f / 12.0f, 11.0f / 12.0f};
 
 struct BvTask {         // 40 B
     float lo[3], hi[3];
@@ -62,10 +54,7 @@ struct BvDecision {     // 64 B
 struct BvPlace {        // a task's global offsets after the task scan
     int childTask, childRef, row, nodeIdx;
 };
-struct BvTotals {       // the per-level read-back
-    U4 t;               // inner nodes, Woop rows of the level's leaves, next level's references, next level's splitting tasks
-    unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child, bit 2: an output row or node
-                        // beyond the caller's capacity (neither of the last two is expected)
+struct BvTotals : LevelTotals {   // t.z: next level's references, t.w: next level's splitting tasks
     unsigned int median, costLeaves, depthLeaves;
 };
 struct BvParams {
@@ -74,10 +63,8 @@ struct BvParams {
 };
 
 __device__ __forceinline__ float sel4(const float4& v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
-// findPlaneAABB (rt_common.cu:1007-1030): pos = mn + (mx - mn) * rpos, two roundings
-__device__ __forceinline__ float plane_pos(float mn, float mx, int j) { return mn + (mx - mn) * kBvRpos[j]; }
 // getPlaneCentroidPosition (rt_common.cu:449-468) == -1: planeDistance with the plane (-1, 0, 0, pos) is fl(pos - c)
-__device__ __forceinline__ bool side_neg(float pos, float c) { return (pos - c) < BV_EPS; }
+__device__ __forceinline__ bool side_neg(float pos, float c) { return (pos - c) < kPlaneEps; }
 
 // ---- once per build ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BV_BLOCK) void bv_prep(int n, const int* __restrict__ tri, int numVerts, const float* __restrict__ pos,
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_prep(int n, const int* __restrict
 // A bin's 8 words: count, the box's six words (box_words: merged by max, so that zero is the identity of an empty bin), pad.
 __device__ __forceinline__ int ref_bin(const float* lo, const float* hi, int a, float c)
 {
-    const int m = a < 2 ? BV_PER_AXIS : BV_PLANES - 2 * BV_PER_AXIS;
+    const int m = planes_on_axis(a);
     int b = 0;
     const float mn = sel3(lo, a), mx = sel3(hi, a);
     for (int j = 0; j < m; j++) b += side_neg(plane_pos(mn, mx, j), c) ? 1 : 0;
@@ -141,7 +128,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_bin(int R, const int* __restrict_
             unsigned int* dst = shared ? sh : slots + (size_t)tk.binSlot * BV_SLOT;
 #pragma unroll
             for (int a = 0; a < 3; a++) {
-                unsigned int* bin = dst + (a * (BV_PER_AXIS + 1) + ref_bin(tk.lo, tk.hi, a, sel4(c, a))) * 8;
+                unsigned int* bin = dst + (a * (kPlanesPerAxis + 1) + ref_bin(tk.lo, tk.hi, a, sel4(c, a))) * 8;
                 atomicAdd(&bin[0], 1u);
                 atomic_max_box(bin + 1, w);
             }
@@ -205,12 +192,12 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_decide(int T, const BvTask* __res
     float p = 0.f;
     int nL = 0, nR = 0;
     unsigned int w[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // the box words of child 0, then of child 1
-    if (lane < BV_PLANES) {
-        const int a = lane / BV_PER_AXIS, j = lane - a * BV_PER_AXIS;
-        const int m = a < 2 ? BV_PER_AXIS : BV_PLANES - 2 * BV_PER_AXIS;
+    if (lane < kPlanes) {
+        const int a = lane / kPlanesPerAxis, j = lane - a * kPlanesPerAxis;
+        const int m = a < 2 ? kPlanesPerAxis : kPlanes - 2 * kPlanesPerAxis;
         p = plane_pos(sel3(tk.lo, a), sel3(tk.hi, a), j);
         // plane j: side -1 (child 0) = bins j+1..m, side +1 (child 1) = bins 0..j
-        const unsigned int* bins = slots + (size_t)tk.binSlot * BV_SLOT + a * (BV_PER_AXIS + 1) * 8;
+        const unsigned int* bins = slots + (size_t)tk.binSlot * BV_SLOT + a * (kPlanesPerAxis + 1) * 8;
         for (int b = 0; b <= m; b++) {
             const uint4 w0 = *(const uint4*)(bins + 8 * b), w1 = *(const uint4*)(bins + 8 * b + 4);
             const unsigned int bw[6] = {w0.y, w0.z, w0.w, w1.x, w1.y, w1.z};
@@ -247,7 +234,7 @@ __global__ __launch_bounds__(BV_BLOCK) void bv_decide(int T, const BvTask* __res
         return;
     }
     d.split = pb;
-    d.axis = kb / BV_PER_AXIS;
+    d.axis = kb / kPlanesPerAxis;
     d.nL = nLb;
     words_box(nLb, w, prm.eps, true, d.lo0, d.hi0);   // persistent_bvh.cu:1855-1863
     words_box(nRb, w + 6, prm.eps, true, d.lo1, d.hi1);
@@ -452,21 +439,17 @@ int bv_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
     for (const size_t held = g_bvPool.held(); 2 * slotCap <= maxSlots && BvLayout((int64_t)n, 2 * slotCap).off <= held;) slotCap *= 2;
     BvLayout lay((int64_t)n, slotCap);
     void* base = nullptr;
-    {
-        const int rc = g_bvPool.regrow(lay.off, &base, [](void*, void*) { return (int)NTR_OK; });
-        if (rc != NTR_OK) return rc;
-    }
-    auto P = [&](size_t o) { return (char*)base + o; };
-
+    if (const int rc = first_block(g_bvPool, lay.off, &base)) return rc;
     StreamEvents<4> ev(s);
     (void)ev.create();
     ev.mark(0);
-    NTR_HIP(hipMemsetAsync(P(lay.totals), 0, sizeof(BvTotals), s));
-    int cur = 0;
+    NTR_HIP(hipMemsetAsync(at<BvTotals>(base, lay.totals), 0, sizeof(BvTotals), s));
     const int nbN = (n + BV_BLOCK - 1) / BV_BLOCK;
-    bv_prep<<<nbN, BV_BLOCK, 0, s>>>(n, d_tri, numVerts, d_pos, (float4*)P(lay.boxLo), (float4*)P(lay.boxHi), (float4*)P(lay.cen),
-                                     (int*)P(lay.refs[cur]), (int*)P(lay.taskOf[cur]), (BvTotals*)P(lay.totals));
+    bv_prep<<<nbN, BV_BLOCK, 0, s>>>(n, d_tri, numVerts, d_pos, at<float4>(base, lay.boxLo), at<float4>(base, lay.boxHi),
+                                     at<float4>(base, lay.cen), at<int>(base, lay.refs[0]), at<int>(base, lay.taskOf[0]),
+                                     at<BvTotals>(base, lay.totals));
     NTR_HIP(hipGetLastError());
+    BvTotals h;
     {
         BvTask root;
         memset(&root, 0, sizeof(root));
@@ -475,18 +458,15 @@ int bv_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
         root.refCount = n;
         root.parentSlot = -1;
         root.binSlot = 0;
-        NTR_HIP(hipMemcpyAsync(P(lay.tasks[cur]), &root, sizeof(root), hipMemcpyHostToDevice, s));
-        BvTotals tot;
-        NTR_HIP(hipMemcpyAsync(&tot, P(lay.totals), sizeof(tot), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));   // `root` leaves scope; the vertex check is read
-        if (tot.err & 1u) return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_build: vertex index out of range");
+        NTR_HIP(hipMemcpyAsync(at<BvTask>(base, lay.tasks[0]), &root, sizeof(root), hipMemcpyHostToDevice, s));
+        if (const int rc = read_totals(&h, at<BvTotals>(base, lay.totals), s)) return rc;   // `root` leaves scope; the vertex check is read
+        if (h.err & 1u) return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_build: vertex index out of range");
     }
     ev.mark(1);
 
-    int64_t T = 1, R = n, S = 1, innerBase = 0, rowBase = 0;
-    int level = 0;
-    unsigned int median = 0, costLeaves = 0, depthLeaves = 0;
-    while (T > 0) {
+    LevelState lv;
+    int64_t R = n, S = 1;
+    while (lv.T > 0) {
         if (S > slotCap) {   // grow the bin slots; everything before them keeps its place
             const int64_t nc = std::min<int64_t>(maxSlots, std::max<int64_t>(S, slotCap + slotCap / 2));
             const BvLayout nl((int64_t)n, nc);
@@ -500,80 +480,60 @@ int bv_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
             slotCap = nc;
             lay = nl;
         }
-        const int nxt = cur ^ 1;
-        const int Ti = (int)T, Ri = (int)R;
+        const int Ti = (int)lv.T, Ri = (int)R;
         const int nbT = (Ti + BV_BLOCK - 1) / BV_BLOCK, nbR = (Ri + BV_BLOCK - 1) / BV_BLOCK;
-        BvParams kp{prm.triLimit, prm.triMaxLimit, prm.maxDepth, level, prm.ci, prm.ct, prm.epsilon, 0.f};
-        const BvTask* tasks = (const BvTask*)P(lay.tasks[cur]);
-        const int* refs = (const int*)P(lay.refs[cur]);
-        const int* taskOf = (const int*)P(lay.taskOf[cur]);
-        BvTotals* tot = (BvTotals*)P(lay.totals);
-        unsigned int* slots = (unsigned int*)P(lay.slots);
-        const float4* cen = (const float4*)P(lay.cen);
+        BvParams kp{prm.triLimit, prm.triMaxLimit, prm.maxDepth, lv.level, prm.ci, prm.ct, prm.epsilon, 0.f};
+        // resolved per level: growing the slots moves the block
+        BvTask *tasks = at<BvTask>(base, lay.tasks[lv.cur]), *next = at<BvTask>(base, lay.tasks[lv.nxt()]);
+        int *refs = at<int>(base, lay.refs[lv.cur]), *nextRefs = at<int>(base, lay.refs[lv.nxt()]);
+        int *taskOf = at<int>(base, lay.taskOf[lv.cur]), *nextTaskOf = at<int>(base, lay.taskOf[lv.nxt()]);
+        float4 *boxLo = at<float4>(base, lay.boxLo), *boxHi = at<float4>(base, lay.boxHi), *cen = at<float4>(base, lay.cen);
+        BvDecision* dec = at<BvDecision>(base, lay.dec);
+        BvPlace* place = at<BvPlace>(base, lay.place);
+        U4 *tLocal = at<U4>(base, lay.tLocal), *tBlocks = at<U4>(base, lay.tBlocks);
+        unsigned int *rLocal = at<unsigned int>(base, lay.rLocal), *rBlocks = at<unsigned int>(base, lay.rBlocks);
+        unsigned int* slots = at<unsigned int>(base, lay.slots);
+        BvTotals* tot = at<BvTotals>(base, lay.totals);
         if (S > 0) NTR_HIP(hipMemsetAsync(slots, 0, (size_t)S * BV_SLOT * 4, s));
         NTR_HIP(hipMemsetAsync(&tot->t, 0, sizeof(U4), s));
-        if (S > 0 && Ri > 0)
-            bv_bin<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, (const float4*)P(lay.boxLo), (const float4*)P(lay.boxHi), cen, slots);
-        bv_decide<<<(Ti + 3) / 4, BV_BLOCK, 0, s>>>(Ti, tasks, slots, (BvDecision*)P(lay.dec), kp, tot);
+        if (S > 0 && Ri > 0) bv_bin<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, boxLo, boxHi, cen, slots);
+        bv_decide<<<(Ti + 3) / 4, BV_BLOCK, 0, s>>>(Ti, tasks, slots, dec, kp, tot);
         if (S > 0 && Ri > 0) {
-            bv_median_bounds<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, (const BvDecision*)P(lay.dec), (const float4*)P(lay.boxLo),
-                                                      (const float4*)P(lay.boxHi), slots);
-            bv_median_finish<<<nbT, BV_BLOCK, 0, s>>>(Ti, tasks, slots, (BvDecision*)P(lay.dec), kp, tot);
+            bv_median_bounds<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, dec, boxLo, boxHi, slots);
+            bv_median_finish<<<nbT, BV_BLOCK, 0, s>>>(Ti, tasks, slots, dec, kp, tot);
         }
-        bv_task_scan_local<<<nbT, BV_BLOCK, 0, s>>>(Ti, tasks, (const BvDecision*)P(lay.dec), (U4*)P(lay.tLocal), (U4*)P(lay.tBlocks));
-        scan_block_sums<BV_BLOCK, U4><<<1, BV_BLOCK, 0, s>>>(nbT, (U4*)P(lay.tBlocks), (U4*)P(lay.tBlocks), &tot->t);
-        bv_task_emit<<<nbT, BV_BLOCK, 0, s>>>(Ti, tasks, (const BvDecision*)P(lay.dec), (const U4*)P(lay.tLocal), (const U4*)P(lay.tBlocks),
-                                              (int)innerBase, (int)rowBase, (int)nodeCap, (int)rowCap, (int*)d_nodes, (uint4*)d_woop, d_idx,
-                                              (BvTask*)P(lay.tasks[nxt]), (BvPlace*)P(lay.place), tot);
+        bv_task_scan_local<<<nbT, BV_BLOCK, 0, s>>>(Ti, tasks, dec, tLocal, tBlocks);
+        scan_block_sums<BV_BLOCK, U4><<<1, BV_BLOCK, 0, s>>>(nbT, tBlocks, tBlocks, &tot->t);
+        bv_task_emit<<<nbT, BV_BLOCK, 0, s>>>(Ti, tasks, dec, tLocal, tBlocks, (int)lv.innerBase, (int)lv.rowBase, (int)nodeCap, (int)rowCap,
+                                              (int*)d_nodes, (uint4*)d_woop, d_idx, next, place, tot);
         if (Ri > 0) {
-            bv_ref_scan_local<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, (const BvDecision*)P(lay.dec), cen,
-                                                       (unsigned int*)P(lay.rLocal), (unsigned int*)P(lay.rBlocks));
-            scan_block_sums<BV_BLOCK, unsigned int><<<1, BV_BLOCK, 0, s>>>(nbR, (unsigned int*)P(lay.rBlocks), (unsigned int*)P(lay.rBlocks),
-                                                                          (unsigned int*)P(lay.rBlocks) + nbR);
-            bv_ref_scatter<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, (const BvDecision*)P(lay.dec), (const BvPlace*)P(lay.place), cen,
-                                                    (const unsigned int*)P(lay.rLocal), (const unsigned int*)P(lay.rBlocks),
-                                                    (int*)P(lay.refs[nxt]), (int*)P(lay.taskOf[nxt]), (int*)P(lay.leafRow), tot);
+            bv_ref_scan_local<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, dec, cen, rLocal, rBlocks);
+            scan_block_sums<BV_BLOCK, unsigned int><<<1, BV_BLOCK, 0, s>>>(nbR, rBlocks, rBlocks, rBlocks + nbR);
+            bv_ref_scatter<<<nbR, BV_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, dec, place, cen, rLocal, rBlocks, nextRefs, nextTaskOf,
+                                                    at<int>(base, lay.leafRow), tot);
         }
         NTR_HIP(hipGetLastError());
-        BvTotals h;
-        NTR_HIP(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        const int64_t inner = h.t.x;
-        // checked before the error word: bv_task_emit writes no node at or beyond the bound and flags the level instead
-        if (innerBase + inner > kMaxNodes) return node_overflow_error("ntr_persistent_bvh_build", level, innerBase + inner);
+        if (const int rc = read_totals(&h, tot, s)) return rc;
+        if (const int rc = lv.check_nodes("ntr_persistent_bvh_build", h.t.x)) return rc;
         if (h.err)
-            return set_error(NTR_ERR_LAYOUT, "ntr_persistent_bvh_build: internal check failed: error 0x%x at level %d", h.err, level);
-        res->numLevels = level + 1;
-        res->numLeaves += (int32_t)(T - inner);
-        if (inner) res->maxDepth = level + 1;
-        innerBase += inner;
-        rowBase += h.t.y;
-        median = h.median;
-        costLeaves = h.costLeaves;
-        depthLeaves = h.depthLeaves;
-        T = 2 * inner;
+            return set_error(NTR_ERR_LAYOUT, "ntr_persistent_bvh_build: internal check failed: error 0x%x at level %d", h.err, lv.level);
+        lv.advance(h.t.x, h.t.y);
         R = h.t.z;
         S = h.t.w;
-        cur = nxt;
-        level++;
     }
     ev.mark(2);
-    emit_leaf_rows<BV_BLOCK><<<nbN, BV_BLOCK, 0, s>>>(n, d_tri, d_pos, (const unsigned char*)nullptr, (const int*)P(lay.leafRow), (int)rowCap,
-                                                      (float4*)d_woop, d_idx, &((BvTotals*)P(lay.totals))->err, 4u);
+    BvTotals* tot = at<BvTotals>(base, lay.totals);
+    emit_leaf_rows<BV_BLOCK><<<nbN, BV_BLOCK, 0, s>>>(n, d_tri, d_pos, (const unsigned char*)nullptr, at<int>(base, lay.leafRow), (int)rowCap,
+                                                      (float4*)d_woop, d_idx, &tot->err, 4u);
     NTR_HIP(hipGetLastError());
     ev.mark(3);
-    BvTotals h;
-    NTR_HIP(hipMemcpyAsync(&h, P(lay.totals), sizeof(h), hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
+    if (const int rc = read_totals(&h, tot, s)) return rc;
     if (h.err) return set_error(NTR_ERR_LAYOUT, "ntr_persistent_bvh_build: internal check failed: error 0x%x in the leaf emit", h.err);
 
-    res->numNodes = (int32_t)innerBase;
-    res->medianFallbacks = (int32_t)median;
-    res->costLeaves = (int32_t)costLeaves;
-    res->depthLeaves = (int32_t)depthLeaves;
-    res->nodesBytes = innerBase * 64;
-    res->triWoopBytes = rowBase * 16;
-    res->triIndexBytes = rowBase * 4;
+    fill_bvh_result(res, lv);
+    res->medianFallbacks = (int32_t)h.median;   // counted over the whole build
+    res->costLeaves = (int32_t)h.costLeaves;
+    res->depthLeaves = (int32_t)h.depthLeaves;
     res->prepMs = ev.ms(0, 1);
     res->levelsMs = ev.ms(1, 2);
     res->emitMs = ev.ms(2, 3);
@@ -608,9 +568,9 @@ int ntr_persistent_bvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int3
 {
     if (!result) return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_build: null result");
     memset(result, 0, sizeof(*result));
-    if (numTris < 1 || numTris >= (1 << 28) || numVerts < 1 || !d_triVtxIndex || !d_vtxPos || !sceneMin || !sceneMax)
-        return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_build: bad geometry arguments (1 <= numTris < 2^28, numVerts >= 1, "
-                         "non-null buffers and scene box)");
+    if (const int rc = check_build_geometry("ntr_persistent_bvh_build", numTris, numVerts, d_triVtxIndex, d_vtxPos, sceneMin && sceneMax,
+                                            " and scene box"))
+        return rc;
     NtrPersistentBvhParams p;
     ntr_persistent_bvh_params_default(&p);
     if (params) p = *params;
@@ -632,21 +592,10 @@ int ntr_persistent_bvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int3
                                            triIndexCapacity, &nodeCap, &rowCap))
         return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int rc = bv_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, sceneMin, sceneMax, p, d_nodes, nodeCap, d_triWoop, rowCap, d_triIndex,
-                            result, s);
-    if (rc != NTR_OK) {
-        (void)hipStreamSynchronize(s);
-        const NtrPersistentBvhResult zero = {};
-        *result = zero;
-    }
-    return rc;
+    return finish_build(bv_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, sceneMin, sceneMax, p, d_nodes, nodeCap, d_triWoop, rowCap,
+                                 d_triIndex, result, s), result, s);
 }
 
-int ntr_persistent_bvh_scratch_bytes(int64_t* bytes)
-{
-    if (!bytes) return set_error(NTR_ERR_INVALID, "ntr_persistent_bvh_scratch_bytes: null");
-    *bytes = (int64_t)g_bvPool.held();
-    return NTR_OK;
-}
+int ntr_persistent_bvh_scratch_bytes(int64_t* bytes) { return pool_bytes("ntr_persistent_bvh_scratch_bytes", g_bvPool, bytes); }
 
 }  // extern "C"

@@ -67,6 +67,15 @@ inline int check_nodes_bytes(const char* fn, const char* what, int64_t nodesByte
     return NTR_OK;
 }
 
+// The mesh a build is handed.  An entry point with further pointers passes whether they are there and how its message names them.
+inline int check_build_geometry(const char* fn, int32_t numTris, int32_t numVerts, const void* d_triVtxIndex, const void* d_vtxPos,
+                                bool moreThere = true, const char* more = "")
+{
+    if (numTris < 1 || numTris >= (1 << 28) || numVerts < 1 || !d_triVtxIndex || !d_vtxPos || !moreThere)
+        return set_error(NTR_ERR_INVALID, "%s: bad geometry arguments (1 <= numTris < 2^28, numVerts >= 1, non-null buffers%s)", fn, more);
+    return NTR_OK;
+}
+
 // The output buffers of a build against ntr_lbvh_capacity(numTris); *nodeCap and *rowCap (or null): what the kernels may index
 inline int check_build_outputs(const char* fn, int32_t numTris, const void* d_nodes, int64_t nodesCapacity, const void* d_triWoop,
                                int64_t triWoopCapacity, const void* d_triIndex, int64_t triIndexCapacity, int64_t* nodeCap,

@@ -2,6 +2,7 @@
 // bvh_refit_, bvh_optimize_, bvh_reorder_kernels.hip, bvh_utils.hip) and the ray sort (rayops_kernels.hip): workgroup scans and the four-counter
 // value the level loops scan, wave folds, the order-preserving float encoding with its min / max, a box as six words merged by integer
 // max, box areas, a triangle's checked indices and box, the leaf rows' emit kernel.  The LBVH keeps its own tuned scans (radix_sort.h).
+// The level loop's shared parts: level_build.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>

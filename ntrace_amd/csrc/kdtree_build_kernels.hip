@@ -19,6 +19,7 @@
 //   end             the staged node and index arrays are copied into the tree's own buffers at their exact sizes
 // Phases hand data over only at kernel boundaries.  The host reads one 32-byte record per level (the level's totals and the
 // error word) to size the next level; nothing else comes back until the build ends.
+// The plane table, that read-back (read_totals) and the level's bookkeeping (LevelState) are level_build.h's.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
@@ -32,23 +33,15 @@
 #include <new>
 
 #include "ntr_internal.h"
-#include "device_prims.h"
-#include "device_scratch.h"
+#include "level_build.h"
 #include "kdtree_kernels.h"
 #include "woop_rows.h"
 
 namespace ntr {
 namespace {
 
-constexpr int KD_PLANES = 32;
-constexpr int KD_PER_AXIS = (KD_PLANES + 2) / 3;   // 11: x and y get 11 planes, z gets 10
-constexpr float KD_EPS = 1e-8f;                    // rt_common.cuh:37
 constexpr int KD_EMPTY = (int)0x80000000;
 constexpr int KD_BLOCK = 256;
-
-// rpos = (float)(1 + k) / (float)(planesPerAxis + 1) (rt_common.cu:1013), folded by the compiler with IEEE rounding
-__constant__ float kRpos[KD_PER_AXIS] = {1.0f / 12.0f, 2.0f / 12.0f, 3.0f / 12.0f, 4.0f / 12.0f, 5.0f / 12.0f, 6.0f / 12.0f,
-                                         7.0f / 12.0f, 8.0f / 12.0f, 9.0f / 12.0f, 10.0f / 12.0f, 11.0f / 12.0f};
 
 struct KdTask {         // 48 B
     float lo[3], hi[3];
@@ -61,19 +54,13 @@ struct KdDecision {     // 32 B
 struct KdPlace {        // a task's global offsets after the task scan
     int childTask, childRef, leafOff, nodeIdx;
 };
-struct KdTotals {       // the per-level read-back
-    U4 t;               // inner nodes, leaf index entries, next level's references, non-empty leaves of this level
-    unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child (never expected)
+struct KdTotals : LevelTotals {   // t.z: next level's references, t.w: non-empty leaves of this level; err bit 2 is never set
     unsigned int pad[3];
 };
 struct KdParams {
     int triLimit, failureCount, maxDepth, level;
     float ci, ct, failRq, pad;
 };
-
-
-// findPlaneAABB (rt_common.cu:1007-1030): pos = mn + (mx - mn) * rpos, two roundings
-__device__ __forceinline__ float plane_pos(float mn, float mx, int kk) { return mn + (mx - mn) * kRpos[kk]; }
 
 // ---- once per build ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(KD_BLOCK) void kd_prep(int n, const int* __restrict__ tri, int numVerts, const float* __restrict__ pos,
@@ -143,12 +130,12 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_count(int R, const int* __restric
             const float4 bl = boxLo[id], bh = boxHi[id];
             const float tmin[3] = {bl.x, bl.y, bl.z}, tmax[3] = {bh.x, bh.y, bh.z};
 #pragma unroll
-            for (int k = 0; k < KD_PLANES; k++) {
-                const int a = k / KD_PER_AXIS;
-                const float p = plane_pos(lo[a], hi[a], k % KD_PER_AXIS);
+            for (int k = 0; k < kPlanes; k++) {
+                const int a = k / kPlanesPerAxis;
+                const float p = plane_pos(lo[a], hi[a], k % kPlanesPerAxis);
                 // getPlanePosition over the triangle's extent: left iff p - min > -EPS, right iff p - max < EPS
-                bits |= (unsigned long long)((p - tmin[a]) > -KD_EPS) << (2 * k);
-                bits |= (unsigned long long)((p - tmax[a]) < KD_EPS) << (2 * k + 1);
+                bits |= (unsigned long long)((p - tmin[a]) > -kPlaneEps) << (2 * k);
+                bits |= (unsigned long long)((p - tmax[a]) < kPlaneEps) << (2 * k + 1);
             }
         }
     }
@@ -184,9 +171,9 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_decide(int T, const KdTask* __res
     unsigned long long key = ~0ull;
     float p = 0.f, s = 0.f;
     int nL = 0, nR = 0;
-    if (lane < KD_PLANES) {
-        const int a = lane / KD_PER_AXIS;
-        p = plane_pos(sel3(tk.lo, a), sel3(tk.hi, a), lane - a * KD_PER_AXIS);
+    if (lane < kPlanes) {
+        const int a = lane / kPlanesPerAxis;
+        p = plane_pos(sel3(tk.lo, a), sel3(tk.hi, a), lane - a * kPlanesPerAxis);
         float l0 = dx, l1 = dy, l2 = dz, r0 = dx, r1 = dy, r2 = dz;   // areaAABBX/Y/Z (rt_common.cu:862-905)
         if (a == 0) { l0 = p - tk.lo[0]; r0 = tk.hi[0] - p; }
         else if (a == 1) { l1 = p - tk.lo[1]; r1 = tk.hi[1] - p; }
@@ -216,7 +203,7 @@ __global__ __launch_bounds__(KD_BLOCK) void kd_decide(int T, const KdTask* __res
             if (fail > prm.failureCount) leaf = true;
         }
         const bool deep = prm.level > prm.maxDepth - 2;
-        d = KdDecision{pb, kb / KD_PER_AXIS, nLb, nRb, leaf ? 1 : 0, fail, (nLb <= prm.triLimit || deep) ? 1 : 0,
+        d = KdDecision{pb, kb / kPlanesPerAxis, nLb, nRb, leaf ? 1 : 0, fail, (nLb <= prm.triLimit || deep) ? 1 : 0,
                        (nRb <= prm.triLimit || deep) ? 1 : 0};
     }
     dec[t] = d;
@@ -293,8 +280,8 @@ __device__ __forceinline__ unsigned long long ref_bits(const KdDecision& d, cons
 {
     const float tmin = d.axis == 0 ? bl.x : (d.axis == 1 ? bl.y : bl.z);
     const float tmax = d.axis == 0 ? bh.x : (d.axis == 1 ? bh.y : bh.z);
-    const unsigned long long l = (d.split - tmin) > -KD_EPS ? 1ull : 0ull;
-    const unsigned long long r = (d.split - tmax) < KD_EPS ? 1ull : 0ull;
+    const unsigned long long l = (d.split - tmin) > -kPlaneEps ? 1ull : 0ull;
+    const unsigned long long r = (d.split - tmax) < kPlaneEps ? 1ull : 0ull;
     return l | (r << 32);
 }
 
@@ -446,28 +433,21 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
     }
     KdLayout lay((int64_t)n, caps);
     void* base = nullptr;
-    {
-        const int rc = g_kdPool.regrow(lay.off, &base, [](void*, void*) { return (int)NTR_OK; });
-        if (rc != NTR_OK) return rc;
-    }
-    auto P = [&](size_t o) { return (char*)base + o; };
-
+    if (const int rc = first_block(g_kdPool, lay.off, &base)) return rc;
     StreamEvents<4> ev(s);
     (void)ev.create();
     ev.mark(0);
-    NTR_HIP(hipMemsetAsync(P(lay.totals), 0, sizeof(KdTotals), s));
+    NTR_HIP(hipMemsetAsync(at<KdTotals>(base, lay.totals), 0, sizeof(KdTotals), s));
     const unsigned int boxInit[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    NTR_HIP(hipMemcpyAsync(P(lay.sceneBox), boxInit, sizeof(boxInit), hipMemcpyHostToDevice, s));
-    int cur = 0;
-    kd_prep<<<(n + KD_BLOCK - 1) / KD_BLOCK, KD_BLOCK, 0, s>>>(n, d_tri, numVerts, d_pos, (float4*)P(lay.boxLo), (float4*)P(lay.boxHi),
-                                                               (float4*)t->woop, (int*)P(lay.refs[cur]), (int*)P(lay.taskOf[cur]),
-                                                               (unsigned int*)P(lay.sceneBox), (KdTotals*)P(lay.totals));
+    NTR_HIP(hipMemcpyAsync(at<unsigned int>(base, lay.sceneBox), boxInit, sizeof(boxInit), hipMemcpyHostToDevice, s));
+    kd_prep<<<(n + KD_BLOCK - 1) / KD_BLOCK, KD_BLOCK, 0, s>>>(n, d_tri, numVerts, d_pos, at<float4>(base, lay.boxLo), at<float4>(base, lay.boxHi),
+                                                               (float4*)t->woop, at<int>(base, lay.refs[0]), at<int>(base, lay.taskOf[0]),
+                                                               at<unsigned int>(base, lay.sceneBox), at<KdTotals>(base, lay.totals));
     NTR_HIP(hipGetLastError());
     unsigned int box[6];
     KdTotals tot;
-    NTR_HIP(hipMemcpyAsync(box, P(lay.sceneBox), sizeof(box), hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipMemcpyAsync(&tot, P(lay.totals), sizeof(tot), hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
+    NTR_HIP(hipMemcpyAsync(box, at<unsigned int>(base, lay.sceneBox), sizeof(box), hipMemcpyDeviceToHost, s));
+    if (const int rc = read_totals(&tot, at<KdTotals>(base, lay.totals), s)) return rc;
     if (tot.err & 1u) return set_error(NTR_ERR_INVALID, "ntr_kdtree_device_build: vertex index out of range");
     for (int k = 0; k < 3; k++) {
         info.sceneMin[k] = ord_dec(box[k]);
@@ -481,15 +461,17 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
         root.refCount = n;
         root.parentSlot = -1;
         root.forced = n <= prm.triLimit ? 1 : 0;
-        NTR_HIP(hipMemcpyAsync(P(lay.tasks[cur]), &root, sizeof(root), hipMemcpyHostToDevice, s));
+        NTR_HIP(hipMemcpyAsync(at<KdTask>(base, lay.tasks[0]), &root, sizeof(root), hipMemcpyHostToDevice, s));
         NTR_HIP(hipStreamSynchronize(s));   // `root` leaves scope
     }
     ev.mark(1);
 
-    int64_t T = 1, R = n, innerBase = 0, leafBase = 0;
-    int level = 0;
+    LevelState lv;   // rowBase: the leaf index entries so far
+    int64_t R = n;
     bool rootLeaf = false;
-    while (T > 0) {
+    while (lv.T > 0) {
+        const int64_t T = lv.T, innerBase = lv.innerBase, leafBase = lv.rowBase;
+        const int level = lv.level;
         if (2 * R > KD_MAX_ENTRIES || 2 * T > KD_MAX_ENTRIES || innerBase + T > KD_MAX_NODES || leafBase + R + T > KD_MAX_ENTRIES)
             return set_error(NTR_ERR_NOMEM, "ntr_kdtree_device_build: level %d (%lld tasks, %lld references) exceeds the builder's int32 "
                              "indexing", level, (long long)T, (long long)R);
@@ -507,7 +489,7 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
             nc.idx = grown(need.idx, caps.idx, KD_MAX_ENTRIES);
             const KdLayout nl((int64_t)n, nc);
             const KdLayout ol = lay;
-            const int c0 = cur;
+            const int c0 = lv.cur;
             const int rc = g_kdPool.regrow(nl.off, &base, [&](void* from, void* to) {
                 auto cp = [&](size_t dst, size_t src, size_t bytes) {
                     return bytes ? hipMemcpyAsync((char*)to + dst, (char*)from + src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
@@ -527,70 +509,65 @@ int kd_build(NtrDeviceKdtree* t, int n, const int32_t* d_tri, int32_t numVerts, 
             caps = nc;
             lay = nl;
         }
-        const int nxt = cur ^ 1;
         const int Ti = (int)T, Ri = (int)R;
         const int nbT = (Ti + KD_BLOCK - 1) / KD_BLOCK, nbR = (Ri + KD_BLOCK - 1) / KD_BLOCK;
         KdParams kp{prm.triLimit, prm.failureCount, maxDepth, level, prm.ci, prm.ct, prm.failRq, 0.f};
-        const KdTask* tasks = (const KdTask*)P(lay.tasks[cur]);
-        NTR_HIP(hipMemsetAsync(P(lay.bins), 0, (size_t)T * 64 * 4, s));
-        if (Ri > 0)
-            kd_count<<<nbR, KD_BLOCK, 0, s>>>(Ri, (const int*)P(lay.refs[cur]), (const int*)P(lay.taskOf[cur]), tasks,
-                                              (const float4*)P(lay.boxLo), (const float4*)P(lay.boxHi), (unsigned int*)P(lay.bins));
-        kd_decide<<<(Ti + 3) / 4, KD_BLOCK, 0, s>>>(Ti, tasks, (const unsigned int*)P(lay.bins), (KdDecision*)P(lay.dec), kp);
-        kd_task_scan_local<<<nbT, KD_BLOCK, 0, s>>>(Ti, tasks, (const KdDecision*)P(lay.dec), (U4*)P(lay.tLocal), (U4*)P(lay.tBlocks));
-        scan_block_sums<KD_BLOCK, U4><<<1, KD_BLOCK, 0, s>>>(nbT, (U4*)P(lay.tBlocks), (U4*)P(lay.tBlocks), &((KdTotals*)P(lay.totals))->t);
-        kd_task_emit<<<nbT, KD_BLOCK, 0, s>>>(Ti, level, tasks, (const KdDecision*)P(lay.dec), (const U4*)P(lay.tLocal),
-                                              (const U4*)P(lay.tBlocks), (int)innerBase, (int)leafBase, info.sceneMax[0], (int*)P(lay.nodes),
-                                              (int*)P(lay.idx), (KdTask*)P(lay.tasks[nxt]), (KdPlace*)P(lay.place));
+        // resolved per level: a relayout moves the block and every array in it
+        KdTask *tasks = at<KdTask>(base, lay.tasks[lv.cur]), *next = at<KdTask>(base, lay.tasks[lv.nxt()]);
+        int *refs = at<int>(base, lay.refs[lv.cur]), *nextRefs = at<int>(base, lay.refs[lv.nxt()]);
+        int *taskOf = at<int>(base, lay.taskOf[lv.cur]), *nextTaskOf = at<int>(base, lay.taskOf[lv.nxt()]);
+        float4 *boxLo = at<float4>(base, lay.boxLo), *boxHi = at<float4>(base, lay.boxHi);
+        unsigned int* bins = at<unsigned int>(base, lay.bins);
+        KdDecision* dec = at<KdDecision>(base, lay.dec);
+        KdPlace* place = at<KdPlace>(base, lay.place);
+        U4 *tLocal = at<U4>(base, lay.tLocal), *tBlocks = at<U4>(base, lay.tBlocks);
+        unsigned long long *rLocal = at<unsigned long long>(base, lay.rLocal), *rBlocks = at<unsigned long long>(base, lay.rBlocks);
+        int *nodes = at<int>(base, lay.nodes), *idx = at<int>(base, lay.idx);
+        KdTotals* dtot = at<KdTotals>(base, lay.totals);
+        NTR_HIP(hipMemsetAsync(bins, 0, (size_t)T * 64 * 4, s));
+        if (Ri > 0) kd_count<<<nbR, KD_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, boxLo, boxHi, bins);
+        kd_decide<<<(Ti + 3) / 4, KD_BLOCK, 0, s>>>(Ti, tasks, bins, dec, kp);
+        kd_task_scan_local<<<nbT, KD_BLOCK, 0, s>>>(Ti, tasks, dec, tLocal, tBlocks);
+        scan_block_sums<KD_BLOCK, U4><<<1, KD_BLOCK, 0, s>>>(nbT, tBlocks, tBlocks, &dtot->t);
+        kd_task_emit<<<nbT, KD_BLOCK, 0, s>>>(Ti, level, tasks, dec, tLocal, tBlocks, (int)innerBase, (int)leafBase, info.sceneMax[0], nodes, idx,
+                                              next, place);
         if (Ri > 0) {
-            kd_ref_scan_local<<<nbR, KD_BLOCK, 0, s>>>(Ri, (const int*)P(lay.refs[cur]), (const int*)P(lay.taskOf[cur]),
-                                                       (const KdDecision*)P(lay.dec), (const float4*)P(lay.boxLo), (const float4*)P(lay.boxHi),
-                                                       (unsigned long long*)P(lay.rLocal), (unsigned long long*)P(lay.rBlocks));
-            scan_block_sums<KD_BLOCK, unsigned long long><<<1, KD_BLOCK, 0, s>>>(nbR, (unsigned long long*)P(lay.rBlocks),
-                                                                                (unsigned long long*)P(lay.rBlocks),
-                                                                                (unsigned long long*)P(lay.rBlocks) + nbR);
-            kd_ref_scatter<<<nbR, KD_BLOCK, 0, s>>>(Ri, (const int*)P(lay.refs[cur]), (const int*)P(lay.taskOf[cur]), tasks,
-                                                    (const KdDecision*)P(lay.dec), (const KdPlace*)P(lay.place), (const float4*)P(lay.boxLo),
-                                                    (const float4*)P(lay.boxHi), (const unsigned long long*)P(lay.rLocal),
-                                                    (const unsigned long long*)P(lay.rBlocks), (int*)P(lay.refs[nxt]), (int*)P(lay.taskOf[nxt]),
-                                                    (int)caps.refs, (int*)P(lay.idx), (int)caps.idx, (KdTotals*)P(lay.totals));
+            kd_ref_scan_local<<<nbR, KD_BLOCK, 0, s>>>(Ri, refs, taskOf, dec, boxLo, boxHi, rLocal, rBlocks);
+            scan_block_sums<KD_BLOCK, unsigned long long><<<1, KD_BLOCK, 0, s>>>(nbR, rBlocks, rBlocks, rBlocks + nbR);
+            kd_ref_scatter<<<nbR, KD_BLOCK, 0, s>>>(Ri, refs, taskOf, tasks, dec, place, boxLo, boxHi, rLocal, rBlocks, nextRefs, nextTaskOf,
+                                                    (int)caps.refs, idx, (int)caps.idx, dtot);
         }
         NTR_HIP(hipGetLastError());
-        NTR_HIP(hipMemcpyAsync(&tot, P(lay.totals), sizeof(tot), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));
+        if (const int rc = read_totals(&tot, dtot, s)) return rc;
         if (tot.err) return set_error(NTR_ERR_LAYOUT, "ntr_kdtree_device_build: internal check failed: partition error 0x%x at level %d", tot.err, level);
         const int64_t inner = tot.t.x, nonEmpty = tot.t.w;
-        info.numLevels = level + 1;
-        info.numLeafNodes += (int32_t)(T - inner);
         info.numEmptyLeaves += (int32_t)(T - inner - nonEmpty);
         info.numTriRefs += (int32_t)(tot.t.y - nonEmpty);
-        if (inner) info.maxDepth = level + 1;
         if (level == 0 && inner == 0) rootLeaf = true;
-        innerBase += inner;
-        leafBase += tot.t.y;
-        T = 2 * inner;
+        lv.advance(inner, tot.t.y);
         R = tot.t.z;
-        cur = nxt;
-        level++;
     }
+    info.numLevels = lv.level;
+    info.numLeafNodes = lv.numLeaves;
+    info.maxDepth = lv.maxDepth;
     if (rootLeaf) {
-        innerBase = 1;
+        lv.innerBase = 1;
         info.numLeafNodes = 2;
         info.numEmptyLeaves = 1;
         info.maxDepth = 1;
     }
-    info.numInnerNodes = (int32_t)innerBase;
+    info.numInnerNodes = (int32_t)lv.innerBase;
     ev.mark(2);
 
-    info.nodesBytes = innerBase * 16;
-    info.triIndexBytes = leafBase * 4;
+    info.nodesBytes = lv.innerBase * 16;
+    info.triIndexBytes = lv.rowBase * 4;
     {
         int rc = device_malloc(&t->nodes, (size_t)info.nodesBytes, "ntr_kdtree_device_build: nodes");
         if (rc == NTR_OK) rc = device_malloc((void**)&t->idx, (size_t)info.triIndexBytes, "ntr_kdtree_device_build: triIndex");
         if (rc != NTR_OK) return rc;
     }
-    NTR_HIP(hipMemcpyAsync(t->nodes, P(lay.nodes), (size_t)info.nodesBytes, hipMemcpyDeviceToDevice, s));
-    NTR_HIP(hipMemcpyAsync(t->idx, P(lay.idx), (size_t)info.triIndexBytes, hipMemcpyDeviceToDevice, s));
+    NTR_HIP(hipMemcpyAsync(t->nodes, at<char>(base, lay.nodes), (size_t)info.nodesBytes, hipMemcpyDeviceToDevice, s));
+    NTR_HIP(hipMemcpyAsync(t->idx, at<char>(base, lay.idx), (size_t)info.triIndexBytes, hipMemcpyDeviceToDevice, s));
     ev.mark(3);
     NTR_HIP(hipStreamSynchronize(s));
 
@@ -668,12 +645,7 @@ int ntr_device_kdtree_info(const NtrDeviceKdtree* t, NtrDeviceKdtreeInfo* info)
 
 void ntr_device_kdtree_free(NtrDeviceKdtree* t) { free_tree(t); }
 
-int ntr_kdtree_device_scratch_bytes(int64_t* bytes)
-{
-    if (!bytes) return set_error(NTR_ERR_INVALID, "ntr_kdtree_device_scratch_bytes: null");
-    *bytes = (int64_t)g_kdPool.held();
-    return NTR_OK;
-}
+int ntr_kdtree_device_scratch_bytes(int64_t* bytes) { return pool_bytes("ntr_kdtree_device_scratch_bytes", g_kdPool, bytes); }
 
 int ntr_device_kdtree_download(const NtrDeviceKdtree* t, void* nodes, void* triWoop, int32_t* triIndex)
 {

@@ -21,7 +21,7 @@
 //                     partition into the other buffer; the leaf row of every triangle of a task that became a leaf
 //   end             emit_leaf_rows (device_prims.h): every live triangle's three Woop rows and its triIndex entries at its leaf row
 // Box unions are exact, so any grouping of the scans gives the host's areas; every cost expression keeps the spec's order of
-// operations (the library is compiled without contraction).  The host reads one 32-byte record per level.
+// operations (the library is compiled without contraction).  The host reads one 32-byte record per level (read_totals, LevelState: level_build.h).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <limits.h>
@@ -33,9 +33,7 @@
 #include <chrono>
 
 #include "ntr_internal.h"
-#include "compact_bvh.h"
-#include "device_prims.h"
-#include "device_scratch.h"
+#include "level_build.h"
 #include "radix_sort.h"
 
 namespace ntr {
@@ -56,10 +54,7 @@ struct SwTask {         // 40 B
 struct SwDecision { int state, axis, numLeft, pad; };
 struct SwPlace { int childTask, row, nodeIdx, pad; };
 struct SwCost { float leafSah, nodeSah; };
-struct SwTotals {       // the per-level read-back
-    U4 t;               // x: inner nodes of the level, y: Woop rows of its leaves
-    unsigned int err;   // bit 0: vertex index out of range, bit 1: a partition rank outside its child or the sort's chained scan gave up,
-                        // bit 2: a node or row beyond the caller's capacity
+struct SwTotals : LevelTotals {   // err bit 1 also: a leaf row outside the buffers at the leaf emit
     unsigned int live, pad[2];
 };
 // w: a box as six words merged by integer max (box_words, device_prims.h).  flag: a segment starts here.
@@ -580,43 +575,42 @@ int sw_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
     const auto wall0 = std::chrono::steady_clock::now();
     const SwLayout lay((int64_t)n);
     void* base = nullptr;
-    {
-        const int rc = g_swPool.regrow(lay.off, &base, [](void*, void*) { return (int)NTR_OK; });
-        if (rc != NTR_OK) return rc;
-    }
-    auto P_ = [&](size_t o) { return (char*)base + o; };
+    if (const int rc = first_block(g_swPool, lay.off, &base)) return rc;
+    // the layout never changes, so every pointer is resolved once
     const int cap = n;
-    const float4* boxLo = (const float4*)P_(lay.boxLo);
-    const float4* boxHi = (const float4*)P_(lay.boxHi);
-    unsigned char* liveFlag = (unsigned char*)P_(lay.liveFlag);
-    unsigned char* side = (unsigned char*)P_(lay.side);
-    SwTotals* tot = (SwTotals*)P_(lay.totals);
-    unsigned int* misc = (unsigned int*)P_(lay.misc);
+    float4 *boxLo = at<float4>(base, lay.boxLo), *boxHi = at<float4>(base, lay.boxHi);
+    unsigned char *liveFlag = at<unsigned char>(base, lay.liveFlag), *side = at<unsigned char>(base, lay.side);
+    int *leafRow = at<int>(base, lay.leafRow), *liveIds = at<int>(base, lay.liveIds);
+    unsigned int *keys = at<unsigned int>(base, lay.keys), *hist = at<unsigned int>(base, lay.hist), *misc = at<unsigned int>(base, lay.misc);
+    unsigned int *rLocal = at<unsigned int>(base, lay.rLocal), *rBlocks = at<unsigned int>(base, lay.rBlocks);   // the live scan's too
+    unsigned int *rootWords = at<unsigned int>(base, lay.rootWords), *minSah = at<unsigned int>(base, lay.minSah);
+    unsigned int* childBox = at<unsigned int>(base, lay.childBox);
+    unsigned long long* minKey = at<unsigned long long>(base, lay.minKey);
+    SwDecision* dec = at<SwDecision>(base, lay.dec);
+    SwCost* cost = at<SwCost>(base, lay.cost);
+    SwPlace* place = at<SwPlace>(base, lay.place);
+    U4 *tLocal = at<U4>(base, lay.tLocal), *tBlocks = at<U4>(base, lay.tBlocks);
+    SwSeg* agg = at<SwSeg>(base, lay.agg);
+    float* sah = at<float>(base, lay.sah);
+    SwTotals* tot = at<SwTotals>(base, lay.totals);
 
     StreamEvents<5> ev(s);
     (void)ev.create();
     ev.mark(0);
     NTR_HIP(hipMemsetAsync(tot, 0, sizeof(SwTotals), s));
-    NTR_HIP(hipMemsetAsync(P_(lay.rootWords), 0, 32, s));
-    NTR_HIP(hipMemsetAsync(P_(lay.hist), 0, 12 * 256 * 4, s));
+    NTR_HIP(hipMemsetAsync(rootWords, 0, 32, s));
+    NTR_HIP(hipMemsetAsync(hist, 0, 12 * 256 * 4, s));
     NTR_HIP(hipMemsetAsync(misc, 0, 64, s));
-    NTR_HIP(hipMemsetAsync(P_(lay.leafRow), 0xFF, (size_t)n * 4, s));
+    NTR_HIP(hipMemsetAsync(leafRow, 0xFF, (size_t)n * 4, s));
     const int nbN = (n + SW_BLOCK - 1) / SW_BLOCK;
-    sw_prep<<<nbN, SW_BLOCK, 0, s>>>(n, d_tri, numVerts, d_pos, (float4*)P_(lay.boxLo), (float4*)P_(lay.boxHi), liveFlag,
-                                     (unsigned int*)P_(lay.rootWords), tot);
-    {
-        unsigned int* lLocal = (unsigned int*)P_(lay.rLocal);
-        unsigned int* lBlocks = (unsigned int*)P_(lay.rBlocks);
-        sw_live_scan_local<<<nbN, SW_BLOCK, 0, s>>>(n, liveFlag, lLocal, lBlocks);
-        scan_block_sums<SW_BLOCK, unsigned int><<<1, SW_BLOCK, 0, s>>>(nbN, lBlocks, lBlocks, &tot->live);
-        sw_live_scatter<<<nbN, SW_BLOCK, 0, s>>>(n, cap, liveFlag, lLocal, lBlocks, boxLo, boxHi, (int*)P_(lay.liveIds),
-                                                 (unsigned int*)P_(lay.keys));
-    }
-    sw_root<<<1, 64, 0, s>>>((const unsigned int*)P_(lay.rootWords), tot, (SwTask*)P_(lay.tasks[0]));
+    sw_prep<<<nbN, SW_BLOCK, 0, s>>>(n, d_tri, numVerts, d_pos, boxLo, boxHi, liveFlag, rootWords, tot);
+    sw_live_scan_local<<<nbN, SW_BLOCK, 0, s>>>(n, liveFlag, rLocal, rBlocks);
+    scan_block_sums<SW_BLOCK, unsigned int><<<1, SW_BLOCK, 0, s>>>(nbN, rBlocks, rBlocks, &tot->live);
+    sw_live_scatter<<<nbN, SW_BLOCK, 0, s>>>(n, cap, liveFlag, rLocal, rBlocks, boxLo, boxHi, liveIds, keys);
+    sw_root<<<1, 64, 0, s>>>(rootWords, tot, at<SwTask>(base, lay.tasks[0]));
     NTR_HIP(hipGetLastError());
     SwTotals h;
-    NTR_HIP(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
+    if (const int rc = read_totals(&h, tot, s)) return rc;
     if (h.err & 1u) return set_error(NTR_ERR_INVALID, "ntr_sah_device_build: vertex index out of range");
     const int P = (int)h.live;
     if (P < 0 || P > n) return set_error(NTR_ERR_LAYOUT, "ntr_sah_device_build: internal check failed: %d live triangles of %d", P, n);
@@ -625,48 +619,35 @@ int sw_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
     // ---- the three orders: stable from ascending ids, so ties go by triangle id -------------------------------------------------
     if (P > 0) {
         const int tiles = (P + OS_THREADS * SW_SORT_ITEMS - 1) / (OS_THREADS * SW_SORT_ITEMS);
-        unsigned long long* tileState = (unsigned long long*)P_(lay.tileState);
-        const unsigned int* hist = (const unsigned int*)P_(lay.hist);
-        sw_hist<<<std::min(SW_HIST_BLOCKS, (P + SW_BLOCK - 1) / SW_BLOCK), SW_BLOCK, 0, s>>>(P, cap, (const unsigned int*)P_(lay.keys),
-                                                                                               (unsigned int*)P_(lay.hist), tileState, tiles * 256);
+        unsigned long long* tileState = at<unsigned long long>(base, lay.tileState);
+        sw_hist<<<std::min(SW_HIST_BLOCKS, (P + SW_BLOCK - 1) / SW_BLOCK), SW_BLOCK, 0, s>>>(P, cap, keys, hist, tileState, tiles * 256);
         for (int d = 0; d < 3; d++) {
-            unsigned int* kA = (unsigned int*)P_(lay.keys) + (size_t)d * cap;
-            unsigned int* kB = (unsigned int*)P_(lay.keysTmp);
-            int* vA = (int*)P_(lay.order[0]) + (size_t)d * cap;
-            int* vB = (int*)P_(lay.order[1]) + (size_t)d * cap;
+            unsigned int *kA = keys + (size_t)d * cap, *kB = at<unsigned int>(base, lay.keysTmp);
+            int *vA = at<int>(base, lay.order[0]) + (size_t)d * cap, *vB = at<int>(base, lay.order[1]) + (size_t)d * cap;
             for (int pass = 0; pass < 4; pass++) {
                 const int gp = d * 4 + pass;   // the tile state's tags tell the twelve passes apart: it is cleared once
                 const unsigned int* kIn = (pass & 1) ? kB : kA;
                 unsigned int* kOut = (pass & 1) ? kA : kB;
-                const int* vIn = pass == 0 ? (const int*)P_(lay.liveIds) : ((pass & 1) ? vB : vA);
+                const int* vIn = pass == 0 ? liveIds : ((pass & 1) ? vB : vA);
                 int* vOut = (pass & 1) ? vA : vB;
                 onesweep_launch<SW_SORT_ITEMS, 0, false>(s, tiles, P, kIn, vIn, kOut, vOut, 1, pass * 8, gp, hist + gp * 256, tileState,
                                                          misc + gp, misc + 12);
             }
         }
-        NTR_HIP(hipMemsetAsync(P_(lay.taskOf[0]), 0, (size_t)P * 4, s));
+        NTR_HIP(hipMemsetAsync(at<int>(base, lay.taskOf[0]), 0, (size_t)P * 4, s));
     }
     NTR_HIP(hipGetLastError());
     ev.mark(2);
 
-    int64_t T = 1, innerBase = 0, rowBase = 0;
-    int level = 0, cur = 0;
+    LevelState lv;
     const int nbP = (P + SW_PB - 1) / SW_PB;
-    while (T > 0) {
-        const int nxt = cur ^ 1;
-        const int Ti = (int)T;
+    const dim3 gridP(nbP, 3);
+    while (lv.T > 0) {
+        const int Ti = (int)lv.T, level = lv.level;
         const int nbT = (Ti + SW_BLOCK - 1) / SW_BLOCK;
-        const SwTask* tasks = (const SwTask*)P_(lay.tasks[cur]);
-        const int* order = (const int*)P_(lay.order[cur]);
-        const int* taskOf = (const int*)P_(lay.taskOf[cur]);
-        SwDecision* dec = (SwDecision*)P_(lay.dec);
-        SwCost* cost = (SwCost*)P_(lay.cost);
-        unsigned int* minSah = (unsigned int*)P_(lay.minSah);
-        unsigned long long* minKey = (unsigned long long*)P_(lay.minKey);
-        unsigned int* childBox = (unsigned int*)P_(lay.childBox);
-        SwSeg* agg = (SwSeg*)P_(lay.agg);
-        float* sah = (float*)P_(lay.sah);
-        const dim3 gridP(nbP, 3);
+        SwTask *tasks = at<SwTask>(base, lay.tasks[lv.cur]), *next = at<SwTask>(base, lay.tasks[lv.nxt()]);
+        int *order = at<int>(base, lay.order[lv.cur]), *nextOrder = at<int>(base, lay.order[lv.nxt()]);
+        int *taskOf = at<int>(base, lay.taskOf[lv.cur]), *nextTaskOf = at<int>(base, lay.taskOf[lv.nxt()]);
         NTR_HIP(hipMemsetAsync(&tot->t, 0, sizeof(U4), s));
         sw_task_begin<<<nbT, SW_BLOCK, 0, s>>>(Ti, tasks, level, minLeaf, dec, cost, minSah, minKey, childBox);
         if (P > 0 && level < SW_MAX_DEPTH) {
@@ -675,60 +656,42 @@ int sw_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
             sw_sah<<<gridP, SW_PB, 0, s>>>(P, cap, order, taskOf, tasks, dec, cost, boxLo, boxHi, agg, sah, minSah);
             sw_pick<<<gridP, SW_PB, 0, s>>>(P, cap, taskOf, tasks, dec, sah, minSah, minKey);
         }
-        sw_decide_scan_local<<<nbT, SW_BLOCK, 0, s>>>(Ti, tasks, level, maxLeaf, cost, minSah, minKey, dec, (U4*)P_(lay.tLocal),
-                                                      (U4*)P_(lay.tBlocks));
-        scan_block_sums<SW_BLOCK, U4><<<1, SW_BLOCK, 0, s>>>(nbT, (U4*)P_(lay.tBlocks), (U4*)P_(lay.tBlocks), &tot->t);
+        sw_decide_scan_local<<<nbT, SW_BLOCK, 0, s>>>(Ti, tasks, level, maxLeaf, cost, minSah, minKey, dec, tLocal, tBlocks);
+        scan_block_sums<SW_BLOCK, U4><<<1, SW_BLOCK, 0, s>>>(nbT, tBlocks, tBlocks, &tot->t);
         if (P > 0) sw_mark<<<nbP, SW_PB, 0, s>>>(P, cap, order, taskOf, tasks, dec, boxLo, boxHi, side, childBox);
-        sw_task_emit<<<nbT, SW_BLOCK, 0, s>>>(Ti, tasks, dec, childBox, (const U4*)P_(lay.tLocal), (const U4*)P_(lay.tBlocks), (int)innerBase,
-                                              (int)rowBase, (int)nodeCap, (int)rowCap, (int*)d_nodes, (uint4*)d_woop, d_idx,
-                                              (SwTask*)P_(lay.tasks[nxt]), (SwPlace*)P_(lay.place), tot);
+        sw_task_emit<<<nbT, SW_BLOCK, 0, s>>>(Ti, tasks, dec, childBox, tLocal, tBlocks, (int)lv.innerBase, (int)lv.rowBase, (int)nodeCap,
+                                              (int)rowCap, (int*)d_nodes, (uint4*)d_woop, d_idx, next, place, tot);
         if (P > 0) {
-            unsigned int* rLocal = (unsigned int*)P_(lay.rLocal);
-            unsigned int* rBlocks = (unsigned int*)P_(lay.rBlocks);
             sw_ref_scan_local<<<gridP, SW_PB, 0, s>>>(P, cap, order, taskOf, dec, side, rLocal, rBlocks);
             // one scan over the three axes' sums: a rank is a difference of two entries of the same axis
             scan_block_sums<SW_SUMS, unsigned int><<<1, SW_SUMS, 0, s>>>(3 * nbP, rBlocks, rBlocks, (unsigned int*)nullptr);
-            sw_ref_scatter<<<gridP, SW_PB, 0, s>>>(P, cap, order, taskOf, tasks, dec, (const SwPlace*)P_(lay.place), side, rLocal, rBlocks,
-                                                   (int*)P_(lay.order[nxt]), (int*)P_(lay.taskOf[nxt]), (int*)P_(lay.leafRow), tot);
+            sw_ref_scatter<<<gridP, SW_PB, 0, s>>>(P, cap, order, taskOf, tasks, dec, place, side, rLocal, rBlocks, nextOrder, nextTaskOf,
+                                                   leafRow, tot);
         }
         NTR_HIP(hipGetLastError());
-        NTR_HIP(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        const int64_t inner = h.t.x;
-        if (innerBase + inner > kMaxNodes) return node_overflow_error("ntr_sah_device_build", level, innerBase + inner);
+        if (const int rc = read_totals(&h, tot, s)) return rc;
+        if (const int rc = lv.check_nodes("ntr_sah_device_build", h.t.x)) return rc;
         if (h.err & 4u)
             return set_error(NTR_ERR_OVERFLOW, "ntr_sah_device_build: level %d does not fit the output buffers (%lld inner nodes, %lld rows so "
-                             "far): splits without a winner chain nodes beyond ntr_lbvh_capacity()", level, (long long)(innerBase + inner),
-                             (long long)(rowBase + h.t.y));
+                             "far): splits without a winner chain nodes beyond ntr_lbvh_capacity()", level,
+                             (long long)(lv.innerBase + h.t.x), (long long)(lv.rowBase + h.t.y));
         if (h.err)
             return set_error(NTR_ERR_LAYOUT, "ntr_sah_device_build: internal check failed: error 0x%x at level %d", h.err, level);
-        res->numLevels = level + 1;
-        res->numLeaves += (int32_t)(T - inner);
-        if (inner) res->maxDepth = level + 1;
-        innerBase += inner;
-        rowBase += h.t.y;
-        T = 2 * inner;
-        cur = nxt;
-        level++;
+        lv.advance(h.t.x, h.t.y);
     }
     ev.mark(3);
-    emit_leaf_rows<SW_BLOCK><<<nbN, SW_BLOCK, 0, s>>>(n, d_tri, d_pos, liveFlag, (const int*)P_(lay.leafRow), (int)rowCap, (float4*)d_woop, d_idx,
-                                                      &tot->err, 2u);
+    emit_leaf_rows<SW_BLOCK><<<nbN, SW_BLOCK, 0, s>>>(n, d_tri, d_pos, liveFlag, leafRow, (int)rowCap, (float4*)d_woop, d_idx, &tot->err, 2u);
     NTR_HIP(hipGetLastError());
     ev.mark(4);
     unsigned int sortErr = 0;
-    NTR_HIP(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
     NTR_HIP(hipMemcpyAsync(&sortErr, misc + 12, 4, hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
+    if (const int rc = read_totals(&h, tot, s)) return rc;
     if (h.err || sortErr)
         return set_error(NTR_ERR_LAYOUT, "ntr_sah_device_build: internal check failed: error 0x%x in the leaf emit, 0x%x in the sort", h.err,
                          sortErr);
 
-    res->numNodes = (int32_t)innerBase;
+    fill_bvh_result(res, lv);
     res->numDropped = n - P;
-    res->nodesBytes = innerBase * 64;
-    res->triWoopBytes = rowBase * 16;
-    res->triIndexBytes = rowBase * 4;
     res->prepMs = ev.ms(0, 1);
     res->sortMs = ev.ms(1, 2);
     res->levelsMs = ev.ms(2, 3);
@@ -750,8 +713,7 @@ int ntr_sah_device_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t 
 {
     if (!result) return set_error(NTR_ERR_INVALID, "ntr_sah_device_build: null result");
     memset(result, 0, sizeof(*result));
-    if (numTris < 1 || numTris >= (1 << 28) || numVerts < 1 || !d_triVtxIndex || !d_vtxPos)
-        return set_error(NTR_ERR_INVALID, "ntr_sah_device_build: bad geometry arguments (1 <= numTris < 2^28, numVerts >= 1, non-null buffers)");
+    if (const int rc = check_build_geometry("ntr_sah_device_build", numTris, numVerts, d_triVtxIndex, d_vtxPos)) return rc;
     if (minLeafSize < 1 || maxLeafSize < minLeafSize)
         return set_error(NTR_ERR_INVALID, "ntr_sah_device_build: leaf preferences (%d, %d): 1 <= minLeafSize <= maxLeafSize", (int)minLeafSize,
                          (int)maxLeafSize);
@@ -760,21 +722,10 @@ int ntr_sah_device_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t 
                                            triIndexCapacity, &nodeCap, &rowCap))
         return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int rc = sw_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, minLeafSize, maxLeafSize, d_nodes, nodeCap, d_triWoop, rowCap, d_triIndex,
-                            result, s);
-    if (rc != NTR_OK) {
-        (void)hipStreamSynchronize(s);
-        const NtrSahDeviceResult zero = {};
-        *result = zero;
-    }
-    return rc;
+    return finish_build(sw_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, minLeafSize, maxLeafSize, d_nodes, nodeCap, d_triWoop, rowCap,
+                                 d_triIndex, result, s), result, s);
 }
 
-int ntr_sah_device_scratch_bytes(int64_t* bytes)
-{
-    if (!bytes) return set_error(NTR_ERR_INVALID, "ntr_sah_device_scratch_bytes: null");
-    *bytes = (int64_t)g_swPool.held();
-    return NTR_OK;
-}
+int ntr_sah_device_scratch_bytes(int64_t* bytes) { return pool_bytes("ntr_sah_device_scratch_bytes", g_swPool, bytes); }
 
 }  // extern "C"
