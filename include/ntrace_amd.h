@@ -596,6 +596,59 @@ NTR_API int ntr_sah_device_build(int32_t numTris, const int32_t* d_triVtxIndex, 
 /* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_sah_device_scratch_bytes(int64_t* bytes);
 
+/* On-device PLOC build (parallel locally-ordered clustering, Meister and Bittner 2018): a bottom-up tree over the LBVH's Morton order
+ * (csrc/bvh_ploc_kernels.hip).  On the CPU the rule's tree at radius 8 has SAH cost 73.1 on the 262 k atrium, where the LBVH has 99.3,
+ * HLBVH (bits 4) 72.4 and the host SAH tree 66.4; what the build costs on the device is in DESIGN.md 6j.  EXTENSION without a reference counterpart:
+ * the rule is the numpy spec tests/np_bvh_ploc.py, which the build equals byte for byte.  The tree feeds ntr_trace_bvh,
+ * ntr_bvh_validate, ntr_bvh_refit, ntr_bvh_optimize, ntr_bvh_sah_cost and ntr_bvh_reorder unchanged.
+ *   order       ntr_lbvh_build's Morton codes over sceneMin / sceneMax and its stable sort (ties by triangle id); no triangle is dropped
+ *   leaves      one triangle per leaf in sorted order: leaf p owns rows 4p .. 4p + 3 (three Woop rows, woop_rows.h, and a terminator
+ *               row of 0x80000000), link ~(4p); the triIndex entry of the first row is the triangle id, the others 0; box = min / max
+ *               of the vertices (-0 < +0), no epsilon
+ *   clusters    (box, link, height); the list starts as the leaves, height 0.  A round, while the list has n > 1 clusters:
+ *   distance    d(i, j) = fl(fl(fl(dx * dy) + fl(dy * dz)) + fl(dz * dx)) of the union box (min / max with -0 < +0), dx = fl(hi.x - lo.x)
+ *               ..., no contraction; a NaN counts as +inf
+ *   neighbour   nn[i] = the j != i with |i - j| <= radius inside the list of least key (d, k, b), k = |i - j|, b = (min(i, j) / k) & 1;
+ *               d compared as floats (+0 == -0).  The key is symmetric and no two candidates of one cluster share (k, b), so the pair
+ *               of least key is mutual: every round merges at least one pair
+ *   merge       i and j = nn[i] merge iff nn[j] == i.  Of a round's m pairs the one whose lower index has rank r (ascending, from 0)
+ *               gets node slot (n - 1 - m) + r: the last round writes slot 0, the root; N - 1 slots in all.  Child 0 is the lower-index
+ *               cluster, child 1 the upper, boxes and links as they stand; word 14 and word 15 are 0
+ *   compaction  the merged cluster takes the lower index's place (box the union, link 64 * slot, height 1 + max); the upper index
+ *               disappears; everything else keeps its relative order
+ *   N == 1      one node: child 0 an empty leaf (box (FLT_MAX, -FLT_MAX), row 0 a terminator), child 1 the triangle (rows 1..3, a
+ *               terminator at row 4), as ntr_persistent_bvh_build's one-triangle tree
+ * Once the list has at most NTR_PLOC_TAIL clusters one workgroup runs the remaining rounds out of LDS in one launch; before that a
+ * round is four launches over tiles of NTR_PLOC_TILE clusters.  Neither constant changes a byte of the result.
+ * Output: caller-owned BVHLayout_Compact buffers of at least ntr_lbvh_capacity() bytes: max(N - 1, 1) nodes, 4N rows (5 for N == 1).
+ *   The result's *Bytes are the exact extents.
+ * NTR_ERR_INVALID (before any device work): numTris < 1 or >= 2^28, numVerts < 1, a null pointer, radius outside 1..64, a scene box
+ *   with a non-finite coordinate or min > max on an axis, output buffers smaller than ntr_lbvh_capacity(); (found on the device, before
+ *   anything is written) a vertex index outside [0, numVerts).  NTR_ERR_OVERFLOW: a tree of height above 100 (inner nodes on the
+ *   longest path; the reference CPU tracer's stack, ntr_persistent_bvh_build's bound): the buffers are then not to be traced; or more
+ *   than 0x76543200 / 64 inner nodes.  NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a device: there is no CPU fallback.  NTR_ERR_NOMEM:
+ *   device memory.  NTR_ERR_LAYOUT: an internal consistency check failed (not expected).  A failed call zeroes *result.
+ * The call blocks (one 32 B read-back per four rounds before the tail).  The scratch (about 100 B per triangle) is a per-device
+ *   grow-only pool that ntr_lbvh_release_workspace returns: one build per device at a time. */
+#define NTR_PLOC_TAIL 1024   /* list length at or below which the single-workgroup tail takes over */
+#define NTR_PLOC_TILE 1024   /* clusters per workgroup of the rounds before the tail */
+typedef struct NtrPlocResult {
+    int32_t numNodes, numLeaves, numRounds, height;   /* inner nodes, leaves (N == 1: the empty one included), rounds (tail rounds
+                                                         included), inner nodes on the longest root-to-leaf path */
+    int32_t tailClusters, pad[3];          /* list length when the tail launch took over, 0 if none (N == 1) */
+    int64_t nodesBytes, triWoopBytes, triIndexBytes;   /* exact extents of what was written */
+    float   seconds;                       /* host wall clock of the whole call */
+    float   mortonMs, sortMs, roundsMs, tailMs, emitMs;   /* GPU event times: the vertex index check and its read-back (the Morton
+                                                             codes come with the sort's launches, as in ntr_hlbvh_build); codes and
+                                                             sort; the rounds before the tail; the tail; leaf clusters and Woop rows */
+} NtrPlocResult;
+NTR_API int ntr_ploc_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
+                           const float sceneMin[3], const float sceneMax[3], int32_t radius, void* d_nodes, int64_t nodesCapacity,
+                           void* d_triWoop, int64_t triWoopCapacity, int32_t* d_triIndex, int64_t triIndexCapacity, NtrPlocResult* result,
+                           void* stream);
+/* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_ploc_scratch_bytes(int64_t* bytes);
+
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by
  * the numpy spec tests/np_bvh_refit.py, not by reference lines.  It works on any Compact tree whatever built it -- ntr_sah_build

@@ -19,7 +19,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     persistent_bvh_build, persistent_bvh_scratch_bytes, PERSISTENT_BVH_DEFAULTS, SahDeviceResult,
                     sah_device_build, sah_device_scratch_bytes, BvhRefitResult, bvh_refit,
                     bvh_refit_scratch_bytes, BvhOptimizeResult, BvhSahResult, bvh_optimize, bvh_optimize_scratch_bytes, bvh_sah_cost,
-                    BvhReorderResult, bvh_reorder, bvh_reorder_scratch_bytes)
+                    BvhReorderResult, bvh_reorder, bvh_reorder_scratch_bytes,
+                    PlocResult, ploc_build, ploc_scratch_bytes, PLOC_TAIL, PLOC_TILE)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -34,4 +35,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "persistent_bvh_build", "persistent_bvh_scratch_bytes", "PERSISTENT_BVH_DEFAULTS", "SahDeviceResult",
            "sah_device_build", "sah_device_scratch_bytes", "BvhRefitResult", "bvh_refit",
            "bvh_refit_scratch_bytes", "BvhOptimizeResult", "BvhSahResult", "bvh_optimize", "bvh_optimize_scratch_bytes",
-           "bvh_sah_cost", "BvhReorderResult", "bvh_reorder", "bvh_reorder_scratch_bytes"]
+           "bvh_sah_cost", "BvhReorderResult", "bvh_reorder", "bvh_reorder_scratch_bytes",
+           "PlocResult", "ploc_build", "ploc_scratch_bytes", "PLOC_TAIL", "PLOC_TILE"]

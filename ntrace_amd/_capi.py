@@ -105,6 +105,17 @@ class SahDeviceResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class PlocResult(C.Structure):
+    _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRounds", C.c_int32), ("height", C.c_int32),
+                ("tailClusters", C.c_int32), ("pad", C.c_int32 * 3),
+                ("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
+                ("seconds", C.c_float), ("mortonMs", C.c_float), ("sortMs", C.c_float), ("roundsMs", C.c_float), ("tailMs", C.c_float),
+                ("emitMs", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class BvhRefitResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("pad", C.c_int32), ("seconds", C.c_float)]
 
@@ -252,6 +263,9 @@ SYMBOLS = [
     ("ntr_persistent_bvh_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_sah_device_build", C.c_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(SahDeviceResult), _vp]),
     ("ntr_sah_device_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_ploc_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, _vp, _i64, _vp, _i64, _vp, _i64,
+                                 C.POINTER(PlocResult), _vp]),
+    ("ntr_ploc_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
@@ -718,6 +732,28 @@ def sah_device_scratch_bytes():
     """ntr_sah_device_scratch_bytes: bytes the device SAH builder's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_sah_device_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+PLOC_TAIL, PLOC_TILE = 1024, 1024   # NTR_PLOC_TAIL, NTR_PLOC_TILE (include/ntrace_amd.h)
+
+
+def ploc_build(num_tris, d_tri, num_verts, d_pos, scene_min, scene_max, d_nodes, nodes_cap, d_woop, woop_cap, d_idx, idx_cap, radius=8,
+               stream=0):
+    """ntr_ploc_build: PLOC over the LBVH's Morton order (mutual nearest neighbours within `radius` list positions merge, round by
+    round; the rule is tests/np_bvh_ploc.py) into Compact buffers of at least lbvh_capacity() bytes.  Returns a PlocResult."""
+    res = PlocResult()
+    mn = (C.c_float * 3)(*[float(x) for x in scene_min])
+    mx = (C.c_float * 3)(*[float(x) for x in scene_max])
+    _check(lib().ntr_ploc_build(int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos), mn, mx, int(radius), _vp(d_nodes), int(nodes_cap),
+                                _vp(d_woop), int(woop_cap), _vp(d_idx), int(idx_cap), C.byref(res), _vp(stream)))
+    return res
+
+
+def ploc_scratch_bytes():
+    """ntr_ploc_scratch_bytes: bytes the PLOC builder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_ploc_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

@@ -20,7 +20,7 @@ Renderer::Renderer(const String& builder)
     m_cudaTracer->setScene(NULL);
     m_platform = Platform("GPU");
     m_platform.setLeafPreferences(1, 1);
-    m_buildParams.builder = (builder == "HLBVH" || builder == "PersistentBVH" || builder == "DeviceSAHBVH" || m_isKDTree) ? "SAHBVH" : builder;
+    m_buildParams.builder = (builder == "HLBVH" || builder == "PersistentBVH" || builder == "DeviceSAHBVH" || builder == "PLOCBVH" || m_isKDTree) ? "SAHBVH" : builder;
 }
 
 Renderer::~Renderer(void)
@@ -79,6 +79,8 @@ String Renderer::getCacheFileName(void)
     U32 hh = h;
     if (m_builder == "HLBVH" && m_hlbvhParams.hlbvh)   // an HLBVH tree is never served as an LBVH tree or the reverse
         hh = hashBits(h, 1u, (U32)m_hlbvhParams.hlbvhBits, hashString("HLBVH"));
+    if (m_builder == "PLOCBVH")                        // the rule's one parameter: a tree of another radius is another tree
+        hh = hashBits(h, (U32)CudaPLOCBuilder::DefaultRadius, hashString("PLOCBVH"));
     snprintf(name, sizeof(name), "/%08x_", hh);
     return m_cachePath + name + m_builder + ".dat";
 }
@@ -108,6 +110,8 @@ CudaAS* Renderer::getCudaBVH(void)
         m_accelStruct = new CudaPersistentBVHBuilder(m_scene, FLT_EPSILON);
     } else if (m_builder == "DeviceSAHBVH") {    // an extension: "SAHBVH"'s tree (the same platform and leaf preferences) built on the device
         m_accelStruct = new CudaSAHBVHBuilder(m_scene, m_platform);
+    } else if (m_builder == "PLOCBVH") {         // an extension: PLOC over the LBVH's Morton order, radius 8 (ntr_ploc_build)
+        m_accelStruct = new CudaPLOCBuilder(m_scene, CudaPLOCBuilder::DefaultRadius);
     } else {
         BVH bvh(m_scene, m_platform, m_buildParams);
         m_accelStruct = new CudaBVH(bvh, layout);

@@ -4,7 +4,7 @@
 // SURVEY 8(f-2)) / getTotalNumRays for the primary, AO and diffuse ray types; setShard for the multi-GPU extension; the kd-tree data
 // structure (builders "SpatialMedianKDTree" / "SAHKDTree" on the host and "PersistentKDTree" on the device: CudaKDTreeTracer over
 // getCudaKDTree, Renderer.cpp:75-76, 309-382, 415-416); the device BVH builders "HLBVH" and "PersistentBVH" (Renderer.cpp:194-267)
-// and, as an extension, "DeviceSAHBVH".
+// and, as extensions, "DeviceSAHBVH" and "PLOCBVH".
 // Out of scope: GL display, visualisation, VPL, the persistent builders' task pools and allocators, kd-tree cache files.
 #pragma once
 #include "MeshWavefrontIO.hpp"
@@ -13,6 +13,7 @@
 #include "CudaPersistentBVHBuilder.hpp"
 #include "CudaPersistentKDTreeBuilder.hpp"
 #include "CudaSAHBVHBuilder.hpp"
+#include "CudaPLOCBuilder.hpp"
 #include "HLBVHBuilder.hpp"
 #include "RayGen.hpp"
 
@@ -32,7 +33,8 @@ public:
     };
 
     // builder: "SAHBVH" (host, leaf preferences (1,1)), "HLBVH" (device LBVH), "PersistentBVH" (device binned SAH,
-    // CudaPersistentBVHBuilder), "DeviceSAHBVH" ("SAHBVH"'s tree built on the device, CudaSAHBVHBuilder), or a kd-tree: "SpatialMedianKDTree" / "SAHKDTree"
+    // CudaPersistentBVHBuilder), "DeviceSAHBVH" ("SAHBVH"'s tree built on the device, CudaSAHBVHBuilder),
+    // "PLOCBVH" (PLOC over the LBVH's Morton order at radius 8, CudaPLOCBuilder), or a kd-tree: "SpatialMedianKDTree" / "SAHKDTree"
     // (host builds) or "PersistentKDTree" (device build, CudaPersistentKDTreeBuilder), traced by CudaKDTreeTracer --
     // Renderer.builder / Renderer.dataStructure in config.conf
     explicit Renderer(const String& builder = "SAHBVH");
