@@ -649,6 +649,63 @@ NTR_API int ntr_ploc_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_
 /* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_ploc_scratch_bytes(int64_t* bytes);
 
+/* Instanced scenes: a top-level tree (TLAS) over instances of bottom-level trees (BLAS), built on the device, and a two-level trace
+ * (csrc/tlas_build_kernels.hip, csrc/trace_instanced_kernels.hip, csrc/instanced_bvh.h).  EXTENSION without a reference counterpart:
+ * the rule is the numpy spec tests/np_instanced.py, which ntr_instance_invert, ntr_tlas_build and ntr_trace_instanced equal bit for bit.
+ *   pool        three device buffers: nodes, triWoop, triIndex.  BLAS k occupies [nodesOffset, +nodesBytes) of the pool's nodes (multiples
+ *               of 64, nodesBytes >= 64) and [triWoopOffset, +triWoopBytes) of its triWoop (multiples of 16); its triIndex entries
+ *               start at entry triWoopOffset / 16.  A BLAS is byte for byte what any builder of this library wrote when it was handed
+ *               pool + offset (or what was copied there): links stay relative to its own start, its root is its node 0.  A BLAS keeps
+ *               Compact's limits (nodesBytes <= 0x76543200); each pool buffer is at most 0xFFFFFF00 bytes.
+ *   instance    objectToWorld and worldToObject, 3x4 row-major, and the index of its BLAS.  ntr_instance_invert makes the second from
+ *               the first in binary64 (cofactors over the determinant, translation -(inv * t), each result rounded once).
+ *   world box   the union of the two child boxes of the BLAS's node 0, its eight corners through objectToWorld, min / max (-0 < +0);
+ *               no padding: a hit within rounding of an instance's box surface can be culled, as in every two-level tracer
+ *   top level   the LBVH's Morton code of the world box over the union of all world boxes, a stable sort, then ntr_ploc_build's rounds
+ *               over (world box, link ~i, height 0), i the instance's index in the caller's array; N - 1 nodes, rootLink 0.
+ *               N == 1: no node, rootLink ~0
+ *   record i    64 bytes: words 0..11 worldToObject, 12 nodesOffset, 13 triWoopOffset / 16, 14 nodesBytes, 15 zero
+ *   trace       closest or any hit through both levels with one stack (16 + 88 entries) and one shrinking tmax; the ray is transformed
+ *               by worldToObject on entering an instance (origin with w = 1, direction with w = 0, not normalised: t means the same on
+ *               both levels).  GENERIC arithmetic only.  Every fetch is range checked: whatever a link or an offset holds, nothing
+ *               outside the buffers is read.  d_instanceIDs[r] receives the instance of ray r's hit, -1 for a miss.
+ * ntr_tlas_build: NTR_ERR_INVALID for numInstances < 1, a radius outside 1..64, null buffers, capacities below ntr_tlas_capacity, a
+ *   BLAS range that is misaligned, outside the pool or above the limits; (found on the device) a blas index outside [0, numBlas).
+ *   NTR_ERR_OVERFLOW: a top-level tree higher than 100.  NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a device.  A failed call zeroes
+ *   *result.  The call blocks; its scratch is a per-device pool that ntr_lbvh_release_workspace returns.
+ * ntr_trace_instanced: seconds == NULL is asynchronous on `stream` and capturable, like ntr_trace_bvh; a traversal stack overflow
+ *   sets the status word that ntr_trace_status reads. */
+typedef struct NtrBlasRange { int64_t nodesOffset, nodesBytes, triWoopOffset, triWoopBytes; } NtrBlasRange;   /* host array */
+typedef struct NtrInstance {                                                                                  /* device array, 112 B */
+    float   objectToWorld[12];
+    float   worldToObject[12];
+    int32_t blas;
+    int32_t reserved[3];
+} NtrInstance;
+typedef struct NtrTlasResult {
+    int32_t rootLink, numNodes, numRounds, height;   /* 0 (N >= 2) or ~0 (N == 1); N - 1; rounds, tail rounds included; inner nodes on the longest path */
+    int32_t tailClusters, pad[3];                    /* list length when the tail launch took over, 0 if none (N == 1) */
+    int64_t nodesBytes, recordsBytes;                /* exact extents of what was written */
+    float   sceneMin[3], sceneMax[3];                /* the union of the instances' world boxes */
+    float   seconds;                                 /* host wall clock of the whole call */
+    float   boxesMs, sortMs, clustersMs, roundsMs, tailMs;   /* GPU event times: world boxes, records and the index check's read-back;
+                                                                codes and sort; the cluster list; the rounds before the tail; the tail */
+} NtrTlasResult;
+/* host only, no device: worldToObject from objectToWorld.  NTR_ERR_INVALID: null, or a zero or non-finite determinant. */
+NTR_API int ntr_instance_invert(const float objectToWorld[12], float worldToObject[12]);
+/* max(N - 1, 1) * 64 and N * 64 bytes */
+NTR_API int ntr_tlas_capacity(int32_t numInstances, int64_t* nodesBytes, int64_t* recordsBytes);
+NTR_API int ntr_tlas_build(int32_t numInstances, const NtrInstance* d_instances, int32_t numBlas, const NtrBlasRange* blasRanges,
+                           const void* d_poolNodes, int64_t poolNodesBytes, int32_t radius, void* d_tlasNodes, int64_t tlasNodesCapacity,
+                           void* d_records, int64_t recordsCapacity, NtrTlasResult* result, void* stream);
+/* Bytes the builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_tlas_scratch_bytes(int64_t* bytes);
+NTR_API int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds /* NULL: asynchronous */,
+                                void* stream);
+
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by
  * the numpy spec tests/np_bvh_refit.py, not by reference lines.  It works on any Compact tree whatever built it -- ntr_sah_build

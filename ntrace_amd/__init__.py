@@ -20,7 +20,9 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     sah_device_build, sah_device_scratch_bytes, BvhRefitResult, bvh_refit,
                     bvh_refit_scratch_bytes, BvhOptimizeResult, BvhSahResult, bvh_optimize, bvh_optimize_scratch_bytes, bvh_sah_cost,
                     BvhReorderResult, bvh_reorder, bvh_reorder_scratch_bytes,
-                    PlocResult, ploc_build, ploc_scratch_bytes, PLOC_TAIL, PLOC_TILE)
+                    PlocResult, ploc_build, ploc_scratch_bytes, PLOC_TAIL, PLOC_TILE,
+                    INSTANCE_DTYPE, BlasRange, BlasPool, TlasResult, instance_invert, make_instances, tlas_capacity, tlas_build,
+                    tlas_scratch_bytes, trace_instanced)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -36,4 +38,6 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "sah_device_build", "sah_device_scratch_bytes", "BvhRefitResult", "bvh_refit",
            "bvh_refit_scratch_bytes", "BvhOptimizeResult", "BvhSahResult", "bvh_optimize", "bvh_optimize_scratch_bytes",
            "bvh_sah_cost", "BvhReorderResult", "bvh_reorder", "bvh_reorder_scratch_bytes",
-           "PlocResult", "ploc_build", "ploc_scratch_bytes", "PLOC_TAIL", "PLOC_TILE"]
+           "PlocResult", "ploc_build", "ploc_scratch_bytes", "PLOC_TAIL", "PLOC_TILE",
+           "INSTANCE_DTYPE", "BlasRange", "BlasPool", "TlasResult", "instance_invert", "make_instances", "tlas_capacity", "tlas_build",
+           "tlas_scratch_bytes", "trace_instanced"]

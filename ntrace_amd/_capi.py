@@ -116,6 +116,23 @@ class PlocResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+INSTANCE_DTYPE = np.dtype([("objectToWorld", "<f4", (12,)), ("worldToObject", "<f4", (12,)), ("blas", "<i4"), ("reserved", "<i4", (3,))])
+
+
+class BlasRange(C.Structure):
+    _fields_ = [("nodesOffset", C.c_int64), ("nodesBytes", C.c_int64), ("triWoopOffset", C.c_int64), ("triWoopBytes", C.c_int64)]
+
+
+class TlasResult(C.Structure):
+    _fields_ = [("rootLink", C.c_int32), ("numNodes", C.c_int32), ("numRounds", C.c_int32), ("height", C.c_int32),
+                ("tailClusters", C.c_int32), ("pad", C.c_int32 * 3), ("nodesBytes", C.c_int64), ("recordsBytes", C.c_int64),
+                ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3), ("seconds", C.c_float), ("boxesMs", C.c_float),
+                ("sortMs", C.c_float), ("clustersMs", C.c_float), ("roundsMs", C.c_float), ("tailMs", C.c_float)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.startswith("scene") else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
 class BvhRefitResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("pad", C.c_int32), ("seconds", C.c_float)]
 
@@ -266,6 +283,11 @@ SYMBOLS = [
     ("ntr_ploc_build", C.c_int, [_i32, _vp, _i32, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, _vp, _i64, _vp, _i64, _vp, _i64,
                                  C.POINTER(PlocResult), _vp]),
     ("ntr_ploc_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_instance_invert", C.c_int, [_vp, _vp]),
+    ("ntr_tlas_capacity", C.c_int, [_i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    ("ntr_tlas_build", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, C.POINTER(TlasResult), _vp]),
+    ("ntr_tlas_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_trace_instanced", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, C.POINTER(C.c_float), _vp]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
@@ -755,6 +777,89 @@ def ploc_scratch_bytes():
     v = _i64(0)
     _check(lib().ntr_ploc_scratch_bytes(C.byref(v)))
     return int(v.value)
+
+
+def instance_invert(object_to_world):
+    """ntr_instance_invert (host only): worldToObject, 12 float32, from a 3x4 row-major objectToWorld (the rule: tests/np_instanced.py)."""
+    m = np.ascontiguousarray(np.asarray(object_to_world, np.float32).reshape(12))
+    out = np.zeros(12, np.float32)
+    _check(lib().ntr_instance_invert(m.ctypes.data, out.ctypes.data))
+    return out
+
+
+def make_instances(transforms, blas):
+    """An INSTANCE_DTYPE array from objectToWorld matrices (n, 12) and BLAS indices; worldToObject by instance_invert."""
+    transforms = np.asarray(transforms, np.float32).reshape(-1, 12)
+    inst = np.zeros(transforms.shape[0], INSTANCE_DTYPE)
+    inst["objectToWorld"] = transforms
+    for i, t in enumerate(transforms):
+        inst["worldToObject"][i] = instance_invert(t)
+    inst["blas"] = np.asarray(blas, np.int32)
+    return inst
+
+
+class BlasPool:
+    """Hands out aligned offsets of a pool's three buffers and remembers the ranges.  add(nodes_bytes, woop_bytes) -> (index,
+    nodesOffset, triWoopOffset): a builder is handed pool + offset (triIndex + triWoopOffset / 4), or a finished tree is copied there."""
+
+    def __init__(self):
+        self.ranges = []
+        self.nodes_bytes = self.woop_bytes = 0
+
+    def add(self, nodes_bytes, woop_bytes):
+        nodes_bytes = (int(nodes_bytes) + 63) // 64 * 64
+        woop_bytes = (int(woop_bytes) + 15) // 16 * 16
+        r = (self.nodes_bytes, nodes_bytes, self.woop_bytes, woop_bytes)
+        self.ranges.append(r)
+        self.nodes_bytes += nodes_bytes
+        self.woop_bytes += woop_bytes
+        return len(self.ranges) - 1, r[0], r[2]
+
+    @property
+    def tri_index_bytes(self):
+        return self.woop_bytes // 4
+
+    def c_ranges(self):
+        return (BlasRange * len(self.ranges))(*[BlasRange(*r) for r in self.ranges])
+
+
+def tlas_capacity(num_instances):
+    """ntr_tlas_capacity -> (nodesBytes, recordsBytes)"""
+    a, b = _i64(0), _i64(0)
+    _check(lib().ntr_tlas_capacity(int(num_instances), C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def tlas_build(num_instances, d_instances, ranges, d_pool_nodes, pool_nodes_bytes, d_tlas_nodes, tlas_nodes_cap, d_records, records_cap,
+               radius=8, stream=0):
+    """ntr_tlas_build: the top-level tree over instances (world boxes, Morton order, ntr_ploc_build's rounds; the rule is
+    tests/np_instanced.py).  ranges: a BlasPool or a list of (nodesOffset, nodesBytes, triWoopOffset, triWoopBytes).  Returns a TlasResult."""
+    if isinstance(ranges, BlasPool):
+        ranges = ranges.ranges
+    arr = (BlasRange * max(len(ranges), 1))(*[BlasRange(*[int(x) for x in r]) for r in ranges])
+    res = TlasResult()
+    _check(lib().ntr_tlas_build(int(num_instances), _vp(d_instances), len(ranges), C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes),
+                                int(radius), _vp(d_tlas_nodes), int(tlas_nodes_cap), _vp(d_records), int(records_cap), C.byref(res), _vp(stream)))
+    return res
+
+
+def tlas_scratch_bytes():
+    """ntr_tlas_scratch_bytes: bytes the top-level builder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_tlas_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def trace_instanced(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances,
+                    d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream=0, timed=True):
+    """ntr_trace_instanced: closest or any hit through the top-level tree and the instances' trees.  timed=True returns the GPU seconds;
+    timed=False is asynchronous on `stream` (capturable) and returns None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_instanced(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes),
+                                     int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances), _vp(d_pool_nodes),
+                                     int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
+                                     C.byref(sec) if timed else None, _vp(stream)))
+    return float(sec.value) if timed else None
 
 
 def bvh_refit(d_nodes, nodes_bytes, d_woop, woop_bytes, d_idx, idx_bytes, num_tris, d_tri, num_verts, d_pos, epsilon=0.0, d_scene_box=0,

@@ -29,39 +29,18 @@
 
 #include "ntr_internal.h"
 #include "level_build.h"
+#include "ploc_rounds.h"
 
 namespace ntr {
 namespace {
 
 constexpr int PL_TILE = NTR_PLOC_TILE;   // clusters of a workgroup of the round kernels, one per thread
 constexpr int PL_TAIL = NTR_PLOC_TAIL;   // the tail workgroup's threads, one cluster each
-constexpr int PL_MAX_RADIUS = 64;
+constexpr int PL_MAX_RADIUS = kPlocMaxRadius;
 constexpr int PL_BLOCK = 256;            // per-triangle kernels
 constexpr int kRoundsPerRead = 4;
-constexpr int kMaxHeight = 100;          // the reference CPU tracer's stack (CudaBVH.cpp:701), ntr_persistent_bvh_build's bound
+constexpr int kMaxHeight = kPlocMaxHeight;
 static_assert(PL_TILE == 1024 && PL_TAIL <= 1024 && PL_TAIL >= 2, "one cluster per thread of a 1024-thread workgroup");
-
-struct U2 {
-    unsigned int x, y;   // survivors, merging pairs
-    __device__ U2 operator+(const U2& b) const { return U2{x + b.x, y + b.y}; }
-};
-
-struct PlState {          // halves [k & 1] are read by launch group k, [(k & 1) ^ 1] written
-    int n[2];             // list length
-    int rounds[2];        // rounds done
-    int cur[2];           // which cluster buffer holds the list
-    unsigned int err;     // bit 0: vertex index out of range, bit 1: a leaf row outside the buffer (emit_leaf_rows), bit 2: a node slot or
-                          // a list position outside its bounds, bit 3: a round without a merge (none of the last three is expected)
-    int height;           // the last cluster's height (the tail writes it)
-};
-static_assert(sizeof(PlState) == 32, "one 32-byte record (read_totals)");
-
-struct PlBuf {            // a list of clusters: box component c of cluster i at box[c * cap + i] (lo.x lo.y lo.z hi.x hi.y hi.z)
-    float* box;
-    int* link;
-    int* height;
-};
-struct PlBufs { PlBuf b[2]; };
 
 // ---- the rule's pieces ------------------------------------------------------------------------------------------------------------
 // d of the union of box a (registers) and the box at column j of a [6][stride] array
@@ -335,22 +314,14 @@ __global__ __launch_bounds__(PL_TAIL) void pl_tail(int k, PlState* __restrict__ 
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 struct PlLayout {
-    size_t sort, state, nn, local, blockSums, leafRow, box[2], link[2], height[2], off;
+    size_t sort, leafRow, off;
+    PlRoundsLayout rounds;
     explicit PlLayout(int64_t n)
     {
         ScratchCarver cv;
-        const int64_t nb = n / PL_TILE + 2;
         sort = cv.take(n >= 2 ? lbvh_sort_scratch_bytes((int)n) : 0);
-        state = cv.take(sizeof(PlState));
-        nn = cv.take((size_t)n * 4);
-        local = cv.take((size_t)n * sizeof(U2));
-        blockSums = cv.take((size_t)nb * sizeof(U2));
+        rounds.carve(cv, n);
         leafRow = cv.take((size_t)n * 4);
-        for (int k = 0; k < 2; k++) {
-            box[k] = cv.take((size_t)n * 24);
-            link[k] = cv.take((size_t)n * 4);
-            height[k] = cv.take((size_t)n * 4);
-        }
         off = cv.off;
     }
 };
@@ -365,12 +336,9 @@ int pl_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
     const PlLayout lay((int64_t)n);
     void* base = nullptr;
     if (const int rc = first_block(g_plPool, lay.off, &base)) return rc;
-    PlState* st = at<PlState>(base, lay.state);
-    int* nn = at<int>(base, lay.nn);
-    U2 *local = at<U2>(base, lay.local), *blockSums = at<U2>(base, lay.blockSums);
+    PlState* st = at<PlState>(base, lay.rounds.state);
     int* leafRow = at<int>(base, lay.leafRow);
-    PlBufs bufs;
-    for (int k = 0; k < 2; k++) bufs.b[k] = PlBuf{at<float>(base, lay.box[k]), at<int>(base, lay.link[k]), at<int>(base, lay.height[k])};
+    const PlBufs bufs = pl_bufs(base, lay.rounds);
 
     StreamEvents<6> ev(s);
     (void)ev.create();
@@ -412,27 +380,10 @@ int pl_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
         ev.mark(3);
 
         int k = 0, len = n;   // launch groups so far; the list length the host knows
-        while (len > PL_TAIL) {
-            const int nb = (len + PL_TILE - 1) / PL_TILE;
-            for (int r = 0; r < kRoundsPerRead; r++, k++) {
-                pl_search<<<nb, PL_TILE, 0, s>>>(k, st, bufs, n, radius, nn);
-                pl_mark<<<nb, PL_TILE, 0, s>>>(k, st, nn, local, blockSums);
-                pl_sums<<<1, PL_TILE, 0, s>>>(k, st, blockSums);
-                pl_scatter<<<nb, PL_TILE, 0, s>>>(k, st, bufs, n, nn, local, blockSums, (int*)d_nodes, (int)nodeCap);
-            }
-            NTR_HIP(hipGetLastError());
-            if (const int rc = read_totals(&h, st, s)) return rc;
-            const int now = h.n[k & 1];
-            if (h.err || now < 1 || now >= len)
-                return set_error(NTR_ERR_LAYOUT, "%s: internal check failed: error 0x%x, %d clusters after %d of round %d", fn, h.err, now, len,
-                                 h.rounds[k & 1]);
-            len = now;
-        }
+        if (const int rc = ploc_rounds(fn, base, lay.rounds, n, radius, d_nodes, (int)nodeCap, s, &k, &len)) return rc;
         ev.mark(4);
         tailClusters = len;
-        pl_tail<<<1, PL_TAIL, 0, s>>>(k, st, bufs, n, radius, (int*)d_nodes, (int)nodeCap);
-        k++;
-        NTR_HIP(hipGetLastError());
+        if (const int rc = ploc_tail(base, lay.rounds, n, radius, d_nodes, (int)nodeCap, s, &k)) return rc;
         ev.mark(5);
         unsigned int sortBad = 0;
         NTR_HIP(hipMemcpyAsync(&sortBad, sortErr, 4, hipMemcpyDeviceToHost, s));
@@ -465,6 +416,46 @@ int pl_build(int n, const int32_t* d_tri, int32_t numVerts, const float* d_pos, 
 }
 
 }  // namespace
+
+// ---- the rounds, for this file's pl_build and for ntr_tlas_build (ploc_rounds.h) ----------------------------------------------------
+int ploc_rounds(const char* fn, void* base, const PlRoundsLayout& lay, int cap, int radius, void* d_nodes, int nodeCap, hipStream_t s,
+                int* kp, int* lenp)
+{
+    PlState* st = at<PlState>(base, lay.state);
+    int* nn = at<int>(base, lay.nn);
+    U2 *local = at<U2>(base, lay.local), *blockSums = at<U2>(base, lay.blockSums);
+    const PlBufs bufs = pl_bufs(base, lay);
+    PlState h;
+    int k = *kp, len = *lenp;
+    while (len > PL_TAIL) {
+        const int nb = (len + PL_TILE - 1) / PL_TILE;
+        for (int r = 0; r < kRoundsPerRead; r++, k++) {
+            pl_search<<<nb, PL_TILE, 0, s>>>(k, st, bufs, cap, radius, nn);
+            pl_mark<<<nb, PL_TILE, 0, s>>>(k, st, nn, local, blockSums);
+            pl_sums<<<1, PL_TILE, 0, s>>>(k, st, blockSums);
+            pl_scatter<<<nb, PL_TILE, 0, s>>>(k, st, bufs, cap, nn, local, blockSums, (int*)d_nodes, nodeCap);
+        }
+        NTR_HIP(hipGetLastError());
+        if (const int rc = read_totals(&h, st, s)) return rc;
+        const int now = h.n[k & 1];
+        if (h.err || now < 1 || now >= len)
+            return set_error(NTR_ERR_LAYOUT, "%s: internal check failed: error 0x%x, %d clusters after %d of round %d", fn, h.err, now, len,
+                             h.rounds[k & 1]);
+        len = now;
+    }
+    *kp = k;
+    *lenp = len;
+    return NTR_OK;
+}
+
+int ploc_tail(void* base, const PlRoundsLayout& lay, int cap, int radius, void* d_nodes, int nodeCap, hipStream_t s, int* k)
+{
+    pl_tail<<<1, PL_TAIL, 0, s>>>(*k, at<PlState>(base, lay.state), pl_bufs(base, lay), cap, radius, (int*)d_nodes, nodeCap);
+    ++*k;
+    NTR_HIP(hipGetLastError());
+    return NTR_OK;
+}
+
 }  // namespace ntr
 
 using namespace ntr;

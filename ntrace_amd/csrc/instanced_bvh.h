@@ -1,0 +1,51 @@
+// instanced_bvh.h -- the two-level layout, stated once, for the code that builds a top-level tree (tlas_build_kernels.hip) and the kernel
+// that traverses one (trace_instanced_kernels.hip).  The rule is tests/np_instanced.py; compact_bvh.h holds the node layout both levels share.
+//   pool      three buffers (nodes, triWoop, triIndex) that hold several Compact trees (BLAS), each byte for byte what a builder wrote
+//             at pool + offset: a BLAS's links are relative to its own start, so no word is rewritten.  A pool buffer is at most
+//             kPoolMaxBytes long: the offset kNoNode (trace_lane.h) plus a 64-byte fetch then lies beyond every extent, and a lane that
+//             must read nothing is given that offset
+//   top level Compact nodes whose leaf links are ~i, i an instance; rootLink is 0, or ~0 when the one instance is the whole tree
+//   record i  16 words: 0..11 worldToObject (3x4 row-major), 12 nodesOffset in bytes, 13 triWoopOffset / 16 (rows; triIndex entries
+//             too), 14 nodesBytes, 15 zero
+//   marker    kExitMarker on the traversal stack, below an instance's entries: a positive word above kSentinel, so neither an inner
+//             link (< kSentinel), nor a leaf link (< 0), nor the sentinel
+#pragma once
+#include <stdint.h>
+
+#include "compact_bvh.h"
+
+namespace ntr {
+
+constexpr int64_t kPoolMaxBytes = 0xFFFFFF00ll;
+constexpr int kRecordWords = 16, kRecordBytes = 64;
+constexpr int kRecNodesOffset = 12, kRecRowOffset = 13, kRecNodesBytes = 14;
+constexpr int kExitMarker = kSentinel + 1;
+static_assert(kRecordBytes == kNodeBytes, "a record is fetched like a node");
+static_assert(kExitMarker > kSentinel, "the marker is neither a link nor the sentinel");
+
+// ---- host: the checks of the two entry points -----------------------------------------------------------------------------------------
+// A pool buffer's size: a multiple of `unit` in [unit, kPoolMaxBytes]
+inline int check_pool_bytes(const char* fn, const char* what, int64_t bytes, int unit)
+{
+    if (bytes < unit || (bytes % unit) != 0 || bytes > kPoolMaxBytes)
+        return set_error(NTR_ERR_INVALID, "%s: %s must be a multiple of %d in [%d, 0x%llx]", fn, what, unit, unit, (unsigned long long)kPoolMaxBytes);
+    return NTR_OK;
+}
+
+// BLAS k's range against the pool's node buffer and Compact's limits (the triWoop side has no buffer at build time: alignment and
+// the pool limit only)
+inline int check_blas_range(const char* fn, int k, const NtrBlasRange& r, int64_t poolNodesBytes)
+{
+    if (r.nodesOffset < 0 || (r.nodesOffset % kNodeBytes) != 0 || r.nodesBytes < kNodeBytes || (r.nodesBytes % kNodeBytes) != 0)
+        return set_error(NTR_ERR_INVALID, "%s: BLAS %d: nodesOffset and nodesBytes must be multiples of 64, nodesBytes at least 64", fn, k);
+    if (r.nodesBytes > kMaxNodesBytes || r.nodesOffset > poolNodesBytes - r.nodesBytes)
+        return set_error(NTR_ERR_INVALID, "%s: BLAS %d: nodes [%lld, +%lld) lie outside the pool's %lld bytes or above Compact's 0x%llx", fn, k,
+                         (long long)r.nodesOffset, (long long)r.nodesBytes, (long long)poolNodesBytes, (unsigned long long)kMaxNodesBytes);
+    if (r.triWoopOffset < 0 || (r.triWoopOffset % kRowBytes) != 0 || r.triWoopBytes < kRowBytes || (r.triWoopBytes % kRowBytes) != 0 ||
+        r.triWoopBytes > kPoolMaxBytes || r.triWoopOffset > kPoolMaxBytes - r.triWoopBytes)
+        return set_error(NTR_ERR_INVALID, "%s: BLAS %d: triWoopOffset and triWoopBytes must be multiples of 16 inside a pool of at most 0x%llx bytes",
+                         fn, k, (unsigned long long)kPoolMaxBytes);
+    return NTR_OK;
+}
+
+}  // namespace ntr

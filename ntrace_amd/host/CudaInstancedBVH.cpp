@@ -1,0 +1,83 @@
+// CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_trace_instanced (see the header).
+#include "CudaInstancedBVH.hpp"
+
+#include <cstring>
+
+namespace FW {
+
+CudaInstancedBVH::CudaInstancedBVH(void) : m_numInstances(0), m_built(false)
+{
+    std::memset(&m_result, 0, sizeof(m_result));
+}
+
+S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
+{
+    if (bvh.getLayout() != BVHLayout_Compact) fail("CudaInstancedBVH: Incorrect BVH layout!");
+    Buffer &nodes = bvh.getNodeBuffer(), &woop = bvh.getTriWoopBuffer(), &index = bvh.getTriIndexBuffer();
+    if (nodes.getSize() < 64 || nodes.getSize() % 64 || woop.getSize() < 16 || woop.getSize() % 16 || index.getSize() * 4 != woop.getSize())
+        fail("CudaInstancedBVH: not a Compact tree's buffers");
+    // the pool's sizes are multiples of 64 and 16 already: every range was one
+    NtrBlasRange r;
+    r.nodesOffset = m_poolNodes.getSize();
+    r.nodesBytes = nodes.getSize();
+    r.triWoopOffset = m_poolTriWoop.getSize();
+    r.triWoopBytes = woop.getSize();
+    if (r.nodesOffset + r.nodesBytes > 0xFFFFFF00ll || r.triWoopOffset + r.triWoopBytes > 0xFFFFFF00ll) fail("CudaInstancedBVH: the pool is full");
+    m_poolNodes.resize(r.nodesOffset + r.nodesBytes);
+    m_poolTriWoop.resize(r.triWoopOffset + r.triWoopBytes);
+    m_poolTriIndex.resize((r.triWoopOffset + r.triWoopBytes) / 4);
+    m_poolNodes.setRange(r.nodesOffset, nodes, 0, r.nodesBytes);
+    m_poolTriWoop.setRange(r.triWoopOffset, woop, 0, r.triWoopBytes);
+    m_poolTriIndex.setRange(r.triWoopOffset / 4, index, 0, r.triWoopBytes / 4);
+    m_ranges.push_back(r);
+    m_built = false;
+    return (S32)m_ranges.size() - 1;
+}
+
+void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32* blas)
+{
+    if (num < 1 || !objectToWorld || !blas) fail("CudaInstancedBVH: no instances");
+    m_instances.resizeDiscard((S64)num * sizeof(NtrInstance));
+    NtrInstance* inst = (NtrInstance*)m_instances.getMutablePtrDiscard();
+    std::memset(inst, 0, (size_t)num * sizeof(NtrInstance));
+    for (S32 i = 0; i < num; i++) {
+        std::memcpy(inst[i].objectToWorld, objectToWorld + 12 * (size_t)i, sizeof(inst[i].objectToWorld));
+        if (ntr_instance_invert(inst[i].objectToWorld, inst[i].worldToObject) != NTR_OK) fail("CudaInstancedBVH: instance %d: %s", i, ntr_last_error());
+        inst[i].blas = blas[i];
+    }
+    m_numInstances = num;
+    m_built = false;
+}
+
+void CudaInstancedBVH::build(S32 radius)
+{
+    if (m_ranges.empty() || m_numInstances < 1) fail("CudaInstancedBVH: nothing to build");
+    int64_t capN, capR;
+    if (ntr_tlas_capacity(m_numInstances, &capN, &capR) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_tlasNodes.resizeDiscard(capN);
+    m_records.resizeDiscard(capR);
+    const int rc = ntr_tlas_build(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
+                                  m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), radius, m_tlasNodes.getMutableCudaPtr(), capN,
+                                  m_records.getMutableCudaPtr(), capR, &m_result, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    if (m_result.nodesBytes) m_tlasNodes.resize(m_result.nodesBytes);   // (N == 1 has no node: the buffer keeps its one unused slot)
+    m_built = true;
+}
+
+F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs)
+{
+    const S32 numRays = rays.getSize();
+    instanceIDs.resizeDiscard((S64)numRays * sizeof(S32));
+    if (!numRays) return 0.0f;
+    if (!m_built) fail("CudaInstancedBVH: No TLAS!");
+    float seconds = 0.0f;
+    const int rc = ntr_trace_instanced(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
+                                       (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                       m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
+                                       m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                       (const int32_t*)m_poolTriIndex.getCudaPtr(), &seconds, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    return seconds;
+}
+
+}  // namespace FW

@@ -1,0 +1,215 @@
+#!/usr/bin/env python3
+"""Instanced scenes (ntr_tlas_build, ntr_trace_instanced): what the top-level build costs and what the second level costs a frame.
+
+One process; every GPU step runs under its own time limit (an alarm that ends the process, so that nothing more is started on a device
+that hung).  Every figure is the median of --reps runs after --warmup runs, timed by stream events (the calls' own seconds / phases):
+  * tlas       ntr_tlas_build over 1 025 and 65 536 instances of soup1000, split by phases (boxes, sort, clusters, rounds, tail)
+  * identity   a 1920x1080 primary batch and one 2^20-ray AO batch (made on the host from the primary hits: uniform directions, length 5)
+               through ONE identity instance of atrium(), beside ntr_trace_bvh (fermi_speculative_while_while, validated flags) on the
+               same tree and rays: the price of the second level and of GENERIC arithmetic
+  * forest     the same kind of frame through 4 096 instances of soup1000 (a 16 x 16 x 16 grid, seeded rotations)
+Prints one JSON line per part.
+
+    timeout -k 10 600 python scripts/instanced_bench.py --out instanced.json
+"""
+import argparse
+import json
+import os
+import signal
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import ntrace_amd as nt  # noqa: E402
+from ntrace_amd import scenes  # noqa: E402
+
+F = np.float32
+PHASES = ("boxesMs", "sortMs", "clustersMs", "roundsMs", "tailMs")
+KERNEL = "fermi_speculative_while_while"
+
+
+def up(a):
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0")
+
+
+def step(name, limit, fn):
+    """fn() under a time limit of its own: a step that does not come back ends the process."""
+    def expired(*_):
+        sys.stderr.write("instanced_bench: step '%s' exceeded %d s; stopping\n" % (name, limit))
+        sys.stderr.flush()
+        os._exit(124)
+    signal.signal(signal.SIGALRM, expired)
+    signal.alarm(limit)
+    try:
+        return fn()
+    finally:
+        signal.alarm(0)
+
+
+def rotations(n, rng):
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q.T
+    return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
+                     2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=1).reshape(n, 3, 3)
+
+
+def transforms(rot, translation):
+    m = np.zeros((rot.shape[0], 3, 4))
+    m[:, :, :3] = rot
+    m[:, :, 3] = translation
+    return m.astype(F).reshape(-1, 12)
+
+
+class Blas:
+    """One mesh built by ntr_ploc_build at the start of pool buffers of its own."""
+
+    def __init__(self, tri, pos, stream):
+        tri, pos = np.ascontiguousarray(tri, np.int32), np.ascontiguousarray(pos, F)
+        caps = nt.lbvh_capacity(tri.shape[0])
+        self.bufs = [torch.zeros(c, dtype=torch.uint8, device="cuda:0") for c in caps]
+        d_tri, d_pos = up(tri), up(pos)
+        r = nt.ploc_build(tri.shape[0], d_tri.data_ptr(), pos.shape[0], d_pos.data_ptr(), pos.min(axis=0), pos.max(axis=0), self.bufs[0].data_ptr(),
+                          caps[0], self.bufs[1].data_ptr(), caps[1], self.bufs[2].data_ptr(), caps[2], 8, stream)
+        self.nb, self.wb = r.nodesBytes, r.triWoopBytes
+        self.ranges = [(0, self.nb, 0, self.wb)]
+        self.flags = nt.bvh_validate(self.bufs[0].data_ptr(), self.nb, stream)
+
+
+class Tlas:
+    def __init__(self, blas, tf, stream):
+        self.blas, self.n, self.stream = blas, tf.shape[0], stream
+        self.d_inst = up(nt.make_instances(tf, np.zeros(tf.shape[0], np.int32)))
+        self.caps = nt.tlas_capacity(self.n)
+        self.d_nodes = torch.zeros(self.caps[0], dtype=torch.uint8, device="cuda:0")
+        self.d_rec = torch.zeros(self.caps[1], dtype=torch.uint8, device="cuda:0")
+        self.res = self.build()
+
+    def build(self):
+        b = self.blas
+        return nt.tlas_build(self.n, self.d_inst.data_ptr(), b.ranges, b.bufs[0].data_ptr(), b.nb, self.d_nodes.data_ptr(), self.caps[0],
+                             self.d_rec.data_ptr(), self.caps[1], 8, self.stream)
+
+    def trace(self, count, any_hit, d_rays, d_res, d_ids):
+        b, r = self.blas, self.res
+        return nt.trace_instanced(count, any_hit, d_rays.data_ptr(), d_res.data_ptr(), d_ids.data_ptr(), self.d_nodes.data_ptr(), r.nodesBytes,
+                                  r.rootLink, self.d_rec.data_ptr(), self.n, b.bufs[0].data_ptr(), b.nb, b.bufs[1].data_ptr(), b.wb,
+                                  b.bufs[2].data_ptr(), self.stream)
+
+
+def median_rate(fn, count, reps, warmup):
+    """fn() -> the launch's GPU seconds; -> dict(ms_median, mrays_per_s)."""
+    secs = [fn() for _ in range(warmup + reps)][warmup:]
+    ms = float(np.median(secs)) * 1e3
+    return {"ms_median": ms, "mrays_per_s": count / ms / 1e3, "ms_min": float(min(secs)) * 1e3, "ms_max": float(max(secs)) * 1e3}
+
+
+def host_ao_rays(rays, res, count, seed, radius=5.0):
+    """`count` occlusion rays from the hit points of a primary batch: uniform directions, tmin 1e-3, tmax radius."""
+    rng = np.random.default_rng(seed)
+    hit = np.flatnonzero(res["id"] >= 0)
+    pick = hit[rng.integers(0, hit.size, count)]
+    d = rng.normal(size=(count, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    out = np.zeros(count, nt.RAY_DTYPE)
+    for k, dk, col in zip(("ox", "oy", "oz"), ("dx", "dy", "dz"), range(3)):
+        out[k] = rays[k][pick] + res["t"][pick] * rays[dk][pick]
+        out[dk] = d[:, col].astype(F)
+    out["tmin"], out["tmax"] = F(1e-3), F(radius)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", nargs="+", default=["tlas", "identity", "forest"])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--ao-rays", type=int, default=1 << 20)
+    ap.add_argument("--limit", type=int, default=120, help="seconds a GPU step may take")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    stream = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+
+    soup = None
+    if "tlas" in args.parts or "forest" in args.parts:
+        tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
+        soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
+
+    if "tlas" in args.parts:
+        for n in (1025, 65536):
+            rng = np.random.default_rng(n)
+            tf = transforms(rotations(n, rng), rng.uniform(-25.0, 25.0, (n, 3)) * (n / 1025.0) ** (1.0 / 3.0))
+
+            def run():
+                t = Tlas(soup, tf, stream)
+                runs = [t.build() for _ in range(args.warmup + args.reps)][args.warmup:]
+                row = {"part": "tlas", "instances": n, "ms_median": float(np.median([r.seconds for r in runs])) * 1e3}
+                row.update({p: float(np.median([getattr(r, p) for r in runs])) for p in PHASES})
+                row.update(numRounds=runs[-1].numRounds, height=runs[-1].height, tailClusters=runs[-1].tailClusters,
+                           scratch_bytes=nt.tlas_scratch_bytes())
+                return row
+            emit(step("tlas %d" % n, args.limit, run))
+
+    def frame(part, t, cam, single=None):
+        """Primary batch and AO batch through Tlas t; single: the Blas to trace beside it with ntr_trace_bvh (same rays)."""
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays = up(rays)
+        d_res, d_ids = (torch.zeros(max(n, na) * b, dtype=torch.uint8, device="cuda:0") for b in (16, 4))
+        row = {"part": part, "instances": t.n, "primary_rays": n, "ao_rays": na}
+
+        def bvh(count, any_hit, d_r):
+            return nt.trace_bvh(KERNEL, count, any_hit, d_r.data_ptr(), d_res.data_ptr(), single.bufs[0].data_ptr(), single.nb,
+                                single.bufs[1].data_ptr(), single.wb, single.bufs[2].data_ptr(), bvh_flags=single.flags, stream=stream)
+        row["primary_instanced"] = step(part + " primary", args.limit, lambda: median_rate(lambda: t.trace(n, False, d_rays, d_res, d_ids), n, args.reps, args.warmup))
+        torch.cuda.synchronize()
+        res = d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE).copy()
+        row["primary_hits"] = int((res["id"] >= 0).sum())
+        if single is not None:
+            row["primary_single_level"] = step(part + " primary single", args.limit, lambda: median_rate(lambda: bvh(n, False, d_rays), n, args.reps, args.warmup))
+            torch.cuda.synchronize()
+            same = d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE)
+            row["primary_records_equal"] = bool(same.tobytes() == res.tobytes())
+        d_ao = up(host_ao_rays(rays, res, na, 7))
+        row["ao_instanced"] = step(part + " ao", args.limit, lambda: median_rate(lambda: t.trace(na, True, d_ao, d_res, d_ids), na, args.reps, args.warmup))
+        if single is not None:
+            row["ao_single_level"] = step(part + " ao single", args.limit, lambda: median_rate(lambda: bvh(na, True, d_ao), na, args.reps, args.warmup))
+        assert nt.trace_status() == 0, "traversal stack overflow"
+        return row
+
+    if "identity" in args.parts:
+        tri, pos, cam = scenes.atrium()
+        atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
+        t = step("identity tlas", args.limit, lambda: Tlas(atrium, np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F), stream))
+        row = frame("identity", t, cam, atrium)
+        row["tris"] = int(tri.shape[0])
+        emit(row)
+
+    if "forest" in args.parts:
+        rng = np.random.default_rng(4096)
+        g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+        t = step("forest tlas", args.limit, lambda: Tlas(soup, transforms(rotations(4096, rng), (g - 7.5) * 30.0), stream))
+        cam = dict(eye=(40.0, 60.0, -420.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
+        row = frame("forest", t, cam)
+        row.update(tlas_height=t.res.height, tlas_ms=t.res.seconds * 1e3)
+        emit(row)
+
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
