@@ -706,6 +706,59 @@ NTR_API int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d
                                 int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds /* NULL: asynchronous */,
                                 void* stream);
 
+/* 4-wide BVH: an out-of-place pass that turns any BVHLayout_Compact tree into 4-wide nodes, and the trace that walks them
+ * (csrc/bvh_widen_kernels.hip, csrc/trace_wide_kernels.hip, csrc/wide_bvh.h).  EXTENSION without a reference counterpart: the rule is the
+ * numpy spec tests/np_bvh_wide.py, which ntr_bvh_widen equals byte for byte and ntr_trace_wide in all four result words.  Leaves, Woop rows
+ * and triIndex are the binary tree's, unchanged: only a new node buffer is written, and the binary tree stays usable.
+ *   wide node   32 words, 128 bytes: words 0..11 the boxes of children 0 and 1 in Compact's box words, 12..15 the links of children 0..3,
+ *               16..27 the boxes of children 2 and 3 (16 + Compact's word for child k - 2), 28 the child count (2..4), 29..31 zero.
+ *               A link < 0 is a leaf (~link its first Woop row, verbatim from the binary tree), > 0 is 128 * index of a wide node, 0 an
+ *               empty slot; slot k >= count holds link 0 and a copy of slot 0's box, so every box word is a box word of the binary tree
+ *               and ntr_bvh_validate's flags for the binary tree hold for the wide one.  The buffer is a multiple of 128 bytes in
+ *               [128, 0x76543200] (the stack sentinel stays 0x76543210)
+ *   widening    a kept binary slot becomes a wide node (slot 0 is kept): its two children, of which the inner one of largest area
+ *               (fl(fl(fl(dx*dy) + fl(dy*dz)) + fl(dz*dx)); a NaN loses, ties to the lowest position) is replaced in place by its own two
+ *               children until there are four entries or no inner one; the inner entries left are kept slots.  The wide index of a kept
+ *               slot is its rank among the kept slots in ascending slot index: the root is 0 and the binary tree's node order is inherited
+ *   trace       per wide node all four slab tests as the binary tracer computes one; a child is a candidate iff its link is non-zero and
+ *               mn <= mx && mx >= tmin && mn <= tmax; candidates are visited in ascending mn, ties by ascending slot, the others pushed
+ *               farthest first; triangles, any hit, degenerate rays and the miss record as ntr_trace_bvh.  The stack is ntr_trace_bvh's
+ *               (16 + 88 entries): result->stackBound <= 104 guarantees that it never overflows
+ * KNOWN LIMIT: the records may differ from ntr_trace_bvh's on the same tree -- a rounded box test is not conservative, so a triangle
+ *   within rounding of a box surface can be reached through one tree and culled in the other, and the visiting order decides among hits
+ *   of equal t.  The spec is the definition, not the binary tracer.
+ * ntr_bvh_widen: NTR_ERR_INVALID, before any device work, for a null pointer, nodesBytes not a multiple of 64 in [64, 0x76543200], a
+ *   capacity below ntr_bvh_widen_capacity, an output range that overlaps the input, or a capturing stream (the call blocks: it reads a
+ *   level's extent back once per four levels).  NTR_ERR_OVERFLOW: more than 0x76543200 / 128 wide nodes, nothing written.  NTR_ERR_LAYOUT,
+ *   after the work: a link > 0 that names no slot was written as an empty slot; the tree is complete otherwise and *result describes it.
+ *   Every other failure zeroes *result.  A slot named by several links is kept once, and the pass ends on any input.  Nothing beyond
+ *   result->nodesBytes is written.  NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a device: there is no CPU fallback.  The scratch is a
+ *   per-device grow-only pool that ntr_lbvh_release_workspace returns.  A wide tree is not refitted or optimized: refit or optimize the
+ *   binary tree, then widen again.
+ * ntr_trace_wide: bvhFlags are the binary tree's (ntr_bvh_validate) or 0; the records are identical under any flags.  numRays == 0 ->
+ *   NTR_OK, 0 seconds.  seconds == NULL is asynchronous on `stream` and capturable, a stack overflow sets the status word that
+ *   ntr_trace_status reads; seconds != NULL is timed and blocking, NTR_ERR_OVERFLOW if a ray's stack overflowed.
+ * ntr_trace_wide_stats: the same records through an instrumented kernel, plus the counters (numInnerVisits counts wide nodes).  Blocking. */
+typedef struct NtrBvhWideResult {
+    int64_t nodesBytes;                    /* the exact extent written: 128 * numNodes */
+    int32_t numNodes, counts[3];           /* wide nodes; those with 2, 3 and 4 children */
+    int32_t numLeafLinks, height;          /* leaf links written; wide nodes on the longest root-to-leaf path */
+    int32_t stackBound;                    /* the maximum over root-to-leaf paths of the sum of (count - 1): the most entries a traversal holds */
+    float   seconds;                       /* GPU time */
+} NtrBvhWideResult;
+/* 128 * (nodesBytes / 64): a bound, not the extent */
+NTR_API int ntr_bvh_widen_capacity(int64_t nodesBytes, int64_t* wideNodesBytes);
+NTR_API int ntr_bvh_widen(const void* d_nodes, int64_t nodesBytes, void* d_wideNodes, int64_t wideCapacity, NtrBvhWideResult* result,
+                          void* stream);
+/* Bytes the pass's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_widen_scratch_bytes(int64_t* bytes);
+NTR_API int ntr_trace_wide(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, const void* d_wideNodes,
+                           int64_t wideNodesBytes, const void* d_triWoop, int64_t triWoopBytes, const int32_t* d_triIndex, uint32_t bvhFlags,
+                           void* stream, float* seconds /* NULL: asynchronous */);
+NTR_API int ntr_trace_wide_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, const void* d_wideNodes,
+                                 int64_t wideNodesBytes, const void* d_triWoop, int64_t triWoopBytes, const int32_t* d_triIndex,
+                                 uint32_t bvhFlags, void* stream, NtrTraceStats* stats);
+
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by
  * the numpy spec tests/np_bvh_refit.py, not by reference lines.  It works on any Compact tree whatever built it -- ntr_sah_build

@@ -22,7 +22,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     BvhReorderResult, bvh_reorder, bvh_reorder_scratch_bytes,
                     PlocResult, ploc_build, ploc_scratch_bytes, PLOC_TAIL, PLOC_TILE,
                     INSTANCE_DTYPE, BlasRange, BlasPool, TlasResult, instance_invert, make_instances, tlas_capacity, tlas_build,
-                    tlas_scratch_bytes, trace_instanced)
+                    tlas_scratch_bytes, trace_instanced,
+                    BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -40,4 +41,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "bvh_sah_cost", "BvhReorderResult", "bvh_reorder", "bvh_reorder_scratch_bytes",
            "PlocResult", "ploc_build", "ploc_scratch_bytes", "PLOC_TAIL", "PLOC_TILE",
            "INSTANCE_DTYPE", "BlasRange", "BlasPool", "TlasResult", "instance_invert", "make_instances", "tlas_capacity", "tlas_build",
-           "tlas_scratch_bytes", "trace_instanced"]
+           "tlas_scratch_bytes", "trace_instanced",
+           "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats"]

@@ -133,6 +133,14 @@ class TlasResult(C.Structure):
         return {k: (list(getattr(self, k)) if k.startswith("scene") else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+class BvhWideResult(C.Structure):
+    _fields_ = [("nodesBytes", C.c_int64), ("numNodes", C.c_int32), ("counts", C.c_int32 * 3), ("numLeafLinks", C.c_int32),
+                ("height", C.c_int32), ("stackBound", C.c_int32), ("seconds", C.c_float)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "counts" else getattr(self, k)) for k, _ in self._fields_}
+
+
 class BvhRefitResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("pad", C.c_int32), ("seconds", C.c_float)]
 
@@ -288,6 +296,11 @@ SYMBOLS = [
     ("ntr_tlas_build", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, C.POINTER(TlasResult), _vp]),
     ("ntr_tlas_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_trace_instanced", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, C.POINTER(C.c_float), _vp]),
+    ("ntr_bvh_widen_capacity", C.c_int, [_i64, C.POINTER(_i64)]),
+    ("ntr_bvh_widen", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhWideResult), _vp]),
+    ("ntr_bvh_widen_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_trace_wide", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp, C.POINTER(C.c_float)]),
+    ("ntr_trace_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp, C.POINTER(TraceStats)]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
@@ -860,6 +873,48 @@ def trace_instanced(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas
                                      int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
                                      C.byref(sec) if timed else None, _vp(stream)))
     return float(sec.value) if timed else None
+
+
+def bvh_widen_capacity(nodes_bytes):
+    """ntr_bvh_widen_capacity -> the bytes a wide node buffer for a Compact tree of nodes_bytes needs at most (128 per binary slot)."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_widen_capacity(int(nodes_bytes), C.byref(v)))
+    return int(v.value)
+
+
+def bvh_widen(d_nodes, nodes_bytes, d_wide_nodes, wide_capacity, stream=0):
+    """ntr_bvh_widen: any Compact tree into 4-wide nodes, out of place (an extension; the rule is tests/np_bvh_wide.py).  Leaves, Woop
+    rows and triIndex stay the binary tree's.  Returns a BvhWideResult; result.nodesBytes is what was written."""
+    res = BvhWideResult()
+    _check(lib().ntr_bvh_widen(_vp(d_nodes), int(nodes_bytes), _vp(d_wide_nodes), int(wide_capacity), C.byref(res), _vp(stream)))
+    return res
+
+
+def bvh_widen_scratch_bytes():
+    """ntr_bvh_widen_scratch_bytes: bytes the widening pass's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_widen_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def trace_wide(num_rays, any_hit, d_rays, d_results, d_wide_nodes, wide_nodes_bytes, d_woop, woop_bytes, d_tri_index, bvh_flags=0, stream=0,
+               timed=True):
+    """ntr_trace_wide: closest or any hit through a 4-wide tree (bvh_widen) over the binary tree's Woop rows and triIndex.  bvh_flags:
+    the binary tree's validated flags, or 0 -- the records are the same.  timed=True returns the GPU seconds; timed=False is
+    asynchronous on `stream` (capturable) and returns None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_wide(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_wide_nodes), int(wide_nodes_bytes),
+                                _vp(d_woop), int(woop_bytes), _vp(d_tri_index), int(bvh_flags), _vp(stream), C.byref(sec) if timed else None))
+    return float(sec.value) if timed else None
+
+
+def trace_wide_stats(num_rays, any_hit, d_rays, d_results, d_wide_nodes, wide_nodes_bytes, d_woop, woop_bytes, d_tri_index, bvh_flags=0,
+                     stream=0):
+    """ntr_trace_wide_stats: trace_wide's records through the instrumented kernel -> TraceStats (numInnerVisits counts wide nodes)."""
+    st = TraceStats()
+    _check(lib().ntr_trace_wide_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_wide_nodes), int(wide_nodes_bytes),
+                                      _vp(d_woop), int(woop_bytes), _vp(d_tri_index), int(bvh_flags), _vp(stream), C.byref(st)))
+    return st
 
 
 def bvh_refit(d_nodes, nodes_bytes, d_woop, woop_bytes, d_idx, idx_bytes, num_tris, d_tri, num_verts, d_pos, epsilon=0.0, d_scene_box=0,
