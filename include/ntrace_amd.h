@@ -706,6 +706,53 @@ NTR_API int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d
                                 int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds /* NULL: asynchronous */,
                                 void* stream);
 
+/* Many PLOC builds in one pass: every mesh of a batch becomes one BLAS of a pool, all of them in the same launches
+ * (csrc/bvh_ploc_batch_kernels.hip; it stands here, not beside ntr_ploc_build, because it fills NtrBlasRange).  ntr_ploc_build is a
+ * chain of some hundred launches and a read-back per four rounds whatever the mesh's size; a scene of a thousand small meshes pays that
+ * chain a thousand times, the batch once.  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_ploc_batch.py -- np_bvh_ploc.build per mesh, np_instanced.make_pool over the results -- which the build equals byte for byte.
+ *   layout      mesh k of n_k triangles occupies nodes [nodesOffset_k, +64 * max(n_k - 1, 1)) and rows [triWoopOffset_k, +16 * rows_k),
+ *               rows_k = 4 n_k (5 for n_k == 1), packed in mesh order without gaps: the offsets are the running sums; its triIndex
+ *               entries start at entry triWoopOffset_k / 16
+ *   bytes       those ranges hold what ntr_ploc_build writes when given d_triVtxIndex + 3 * firstTri, numTris, the same vertices, the
+ *               mesh's box, radius and the pool pointers plus the offsets: links relative to the BLAS's own start, leaf rows to its own
+ *               row base, triangle ids to its own firstTri; the one-triangle tree included.  meshResults[k] are that build's counts,
+ *               ranges[k] feeds ntr_tlas_build unchanged
+ *   meshes      may name overlapping or identical triangle ranges (two BLASes of one mesh) and need not cover the array
+ * NTR_ERR_INVALID (before any device work): a null pointer (meshResults may be NULL), numMeshes outside 1..2^20, a mesh with numTris < 1
+ *   or a range outside [0, numTrisTotal), 2^28 triangles or more in all, radius outside 1..64, a box with a non-finite coordinate or
+ *   min > max on an axis, capacities below ntr_ploc_batch_capacity, pool nodes or triWoop not 16-byte aligned, a capturing stream (the call
+ *   blocks: one 32 B read-back per four rounds); (found on the device, before anything is written to the pool) a vertex index outside
+ *   [0, numVerts) in any mesh.  NTR_ERR_OVERFLOW (before any device work): a pool extent above 0xFFFFFF00 or a mesh of more than
+ *   0x76543200 / 64 nodes; (after the work) a mesh whose tree is higher than 100 -- the message names the first such mesh; ranges,
+ *   meshResults and the pool's bytes are the rule's all the same, as with ntr_ploc_build.  NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a
+ *   device: there is no CPU fallback.  NTR_ERR_LAYOUT: an internal consistency check failed (not expected).  A failed call zeroes *result.
+ * The scratch (about 105 B per triangle and 76 B per mesh) is a per-device grow-only pool of its own that ntr_lbvh_release_workspace
+ *   returns: one build per device at a time. */
+typedef struct NtrPlocBatchMesh {      /* host array, one per mesh */
+    int32_t firstTri, numTris;         /* triangles [firstTri, +numTris) of the shared d_triVtxIndex */
+    float   sceneMin[3], sceneMax[3];  /* the box this mesh's Morton codes are taken over, as ntr_ploc_build's */
+} NtrPlocBatchMesh;
+typedef struct NtrPlocBatchMeshResult { int32_t numNodes, numLeaves, numRounds, height; } NtrPlocBatchMeshResult;  /* host array */
+typedef struct NtrPlocBatchResult {
+    int32_t numMeshes, numRounds, maxHeight, pad;       /* rounds launched = max over meshes; greatest height */
+    int64_t numTris, nodesBytes, triWoopBytes, triIndexBytes;   /* exact extents of the pool written */
+    float   seconds;                                    /* host wall clock */
+    float   checkMs, sortMs, emitMs, roundsMs;          /* GPU event times: codes, index check and its read-back; the sort; leaf clusters
+                                                           and Woop rows; the rounds */
+} NtrPlocBatchResult;
+/* host only, no device: the exact pool extents and, when ranges != NULL, the NtrBlasRange of every mesh */
+NTR_API int ntr_ploc_batch_capacity(int32_t numMeshes, const NtrPlocBatchMesh* meshes, NtrBlasRange* ranges,
+                                    int64_t* nodesBytes, int64_t* triWoopBytes, int64_t* triIndexBytes);
+NTR_API int ntr_ploc_build_batch(int32_t numMeshes, const NtrPlocBatchMesh* meshes, int32_t numTrisTotal, const int32_t* d_triVtxIndex,
+                                 int32_t numVerts, const float* d_vtxPos, int32_t radius,
+                                 void* d_poolNodes, int64_t nodesCapacity, void* d_poolTriWoop, int64_t triWoopCapacity,
+                                 int32_t* d_poolTriIndex, int64_t triIndexCapacity,
+                                 NtrBlasRange* ranges /* numMeshes, out */, NtrPlocBatchMeshResult* meshResults /* may be NULL */,
+                                 NtrPlocBatchResult* result, void* stream);
+/* Bytes the batch builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_ploc_batch_scratch_bytes(int64_t* bytes);
+
 /* 4-wide BVH: an out-of-place pass that turns any BVHLayout_Compact tree into 4-wide nodes, and the trace that walks them
  * (csrc/bvh_widen_kernels.hip, csrc/trace_wide_kernels.hip, csrc/wide_bvh.h).  EXTENSION without a reference counterpart: the rule is the
  * numpy spec tests/np_bvh_wide.py, which ntr_bvh_widen equals byte for byte and ntr_trace_wide in all four result words.  Leaves, Woop rows

@@ -123,6 +123,31 @@ class BlasRange(C.Structure):
     _fields_ = [("nodesOffset", C.c_int64), ("nodesBytes", C.c_int64), ("triWoopOffset", C.c_int64), ("triWoopBytes", C.c_int64)]
 
 
+class PlocBatchMesh(C.Structure):
+    """NtrPlocBatchMesh: triangles [firstTri, +numTris) of the shared index array and the box the mesh's Morton codes are taken over."""
+    _fields_ = [("firstTri", C.c_int32), ("numTris", C.c_int32), ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3)]
+
+    def __init__(self, first_tri=0, num_tris=0, scene_min=(0, 0, 0), scene_max=(0, 0, 0)):
+        super().__init__(int(first_tri), int(num_tris), (C.c_float * 3)(*[float(x) for x in scene_min]),
+                         (C.c_float * 3)(*[float(x) for x in scene_max]))
+
+
+class PlocBatchMeshResult(C.Structure):
+    _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRounds", C.c_int32), ("height", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PlocBatchResult(C.Structure):
+    _fields_ = [("numMeshes", C.c_int32), ("numRounds", C.c_int32), ("maxHeight", C.c_int32), ("pad", C.c_int32),
+                ("numTris", C.c_int64), ("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
+                ("seconds", C.c_float), ("checkMs", C.c_float), ("sortMs", C.c_float), ("emitMs", C.c_float), ("roundsMs", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class TlasResult(C.Structure):
     _fields_ = [("rootLink", C.c_int32), ("numNodes", C.c_int32), ("numRounds", C.c_int32), ("height", C.c_int32),
                 ("tailClusters", C.c_int32), ("pad", C.c_int32 * 3), ("nodesBytes", C.c_int64), ("recordsBytes", C.c_int64),
@@ -292,6 +317,10 @@ SYMBOLS = [
                                  C.POINTER(PlocResult), _vp]),
     ("ntr_ploc_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_instance_invert", C.c_int, [_vp, _vp]),
+    ("ntr_ploc_batch_capacity", C.c_int, [_i32, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    ("ntr_ploc_build_batch", C.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                       C.POINTER(PlocBatchResult), _vp]),
+    ("ntr_ploc_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_capacity", C.c_int, [_i32, C.POINTER(_i64), C.POINTER(_i64)]),
     ("ntr_tlas_build", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, C.POINTER(TlasResult), _vp]),
     ("ntr_tlas_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
@@ -789,6 +818,57 @@ def ploc_scratch_bytes():
     """ntr_ploc_scratch_bytes: bytes the PLOC builder's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_ploc_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def _batch_meshes(meshes):
+    """A ctypes array of PlocBatchMesh from PlocBatchMesh objects or (firstTri, numTris, sceneMin, sceneMax) tuples."""
+    if isinstance(meshes, C.Array):
+        return meshes
+    items = [m if isinstance(m, PlocBatchMesh) else PlocBatchMesh(*m) for m in meshes]
+    return (PlocBatchMesh * max(len(items), 1))(*items)
+
+
+def _range_tuples(arr, n):
+    return [tuple(r) for r in np.frombuffer(arr, np.int64).reshape(-1, 4)[:n].tolist()]
+
+
+def ploc_batch_capacity(meshes):
+    """ntr_ploc_batch_capacity (host only) -> (nodesBytes, triWoopBytes, triIndexBytes, ranges): the exact extents of the pool that
+    ploc_build_batch(meshes) writes and every mesh's (nodesOffset, nodesBytes, triWoopOffset, triWoopBytes)."""
+    n = len(meshes)
+    arr = _batch_meshes(meshes)
+    ranges = (BlasRange * max(n, 1))()
+    a, b, c = _i64(0), _i64(0), _i64(0)
+    _check(lib().ntr_ploc_batch_capacity(n, C.cast(arr, _vp), C.cast(ranges, _vp), C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value), _range_tuples(ranges, n)
+
+
+def ploc_build_batch(meshes, num_tris_total, d_tri, num_verts, d_pos, d_pool_nodes, nodes_cap, d_pool_woop, woop_cap, d_pool_idx, idx_cap,
+                     radius=8, stream=0):
+    """ntr_ploc_build_batch: every mesh of `meshes` (PlocBatchMesh objects or (firstTri, numTris, sceneMin, sceneMax) tuples over one shared
+    index array) becomes one BLAS of the pool, all in the same launches; each BLAS is byte for byte ploc_build's tree of that mesh (the
+    rule is tests/np_ploc_batch.py).  Returns (PlocBatchResult, ranges, mesh_results): ranges as tlas_build takes them, mesh_results an
+    array of PlocBatchMeshResult.  An NtrError raised after the work (a tree too high) carries .ranges and .mesh_results too."""
+    n = len(meshes)
+    arr = _batch_meshes(meshes)
+    ranges = (BlasRange * max(n, 1))()
+    per_mesh = (PlocBatchMeshResult * max(n, 1))()
+    res = PlocBatchResult()
+    try:
+        _check(lib().ntr_ploc_build_batch(n, C.cast(arr, _vp), int(num_tris_total), _vp(d_tri), int(num_verts), _vp(d_pos), int(radius),
+                                          _vp(d_pool_nodes), int(nodes_cap), _vp(d_pool_woop), int(woop_cap), _vp(d_pool_idx), int(idx_cap),
+                                          C.cast(ranges, _vp), C.cast(per_mesh, _vp), C.byref(res), _vp(stream)))
+    except NtrError as e:
+        e.ranges, e.mesh_results = _range_tuples(ranges, n), per_mesh
+        raise
+    return res, _range_tuples(ranges, n), per_mesh
+
+
+def ploc_batch_scratch_bytes():
+    """ntr_ploc_batch_scratch_bytes: bytes the batch PLOC builder's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_ploc_batch_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

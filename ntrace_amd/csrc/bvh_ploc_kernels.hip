@@ -42,49 +42,6 @@ constexpr int kRoundsPerRead = 4;
 constexpr int kMaxHeight = kPlocMaxHeight;
 static_assert(PL_TILE == 1024 && PL_TAIL <= 1024 && PL_TAIL >= 2, "one cluster per thread of a 1024-thread workgroup");
 
-// ---- the rule's pieces ------------------------------------------------------------------------------------------------------------
-// d of the union of box a (registers) and the box at column j of a [6][stride] array
-__device__ __forceinline__ float pl_distance(const float* a, const float* s, int stride, int j)
-{
-    const float ex = ord_max(a[3], s[3 * stride + j]) - ord_min(a[0], s[j]);
-    const float ey = ord_max(a[4], s[4 * stride + j]) - ord_min(a[1], s[stride + j]);
-    const float ez = ord_max(a[5], s[5 * stride + j]) - ord_min(a[2], s[2 * stride + j]);
-    const float d = __fadd_rn(__fadd_rn(__fmul_rn(ex, ey), __fmul_rn(ey, ez)), __fmul_rn(ez, ex));
-    return d != d ? INFINITY : d;
-}
-
-// nn[i]: cluster i of a list of n sits at column li of s; its candidates i - k and i + k at li - k and li + k
-__device__ __forceinline__ int pl_nearest(const float* s, int stride, int li, int i, int n, int radius)
-{
-    float a[6];
-#pragma unroll
-    for (int c = 0; c < 6; c++) a[c] = s[c * stride + li];
-    float bestD = INFINITY;
-    int bestT = INT_MAX, best = -1;
-    for (int k = 1; k <= radius; k++) {
-        const int q = i / k;   // min(i, j) / k is q - 1 for j = i - k and q for j = i + k
-        if (i - k >= 0) {
-            const float d = pl_distance(a, s, stride, li - k);
-            const int t = 2 * k + ((q - 1) & 1);
-            if (d < bestD || (d == bestD && t < bestT)) { bestD = d; bestT = t; best = i - k; }
-        }
-        if (i + k < n) {
-            const float d = pl_distance(a, s, stride, li + k);
-            const int t = 2 * k + (q & 1);
-            if (d < bestD || (d == bestD && t < bestT)) { bestD = d; bestT = t; best = i + k; }
-        }
-    }
-    return best;
-}
-
-// the node of a merging pair: child 0 the lower-index cluster, child 1 the upper, boxes and links as they stand
-__device__ __forceinline__ void pl_write_node(int* __restrict__ nodes, int slot, const float* b0, int link0, const float* b1, int link1)
-{
-    write_inner_node(nodes, slot, b0, b0 + 3, b1, b1 + 3, 0);
-    nodes[kNodeWords * (long long)slot + kLinkWord] = link0;
-    nodes[kNodeWords * (long long)slot + kLinkWord + 1] = link1;
-}
-
 // ---- before the rounds --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PL_BLOCK) void pl_check(int n, const int* __restrict__ tri, int numVerts, PlState* __restrict__ st)
 {

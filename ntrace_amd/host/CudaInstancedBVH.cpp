@@ -8,6 +8,7 @@ namespace FW {
 CudaInstancedBVH::CudaInstancedBVH(void) : m_numInstances(0), m_built(false)
 {
     std::memset(&m_result, 0, sizeof(m_result));
+    std::memset(&m_blasResult, 0, sizeof(m_blasResult));
 }
 
 S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
@@ -32,6 +33,27 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_ranges.push_back(r);
     m_built = false;
     return (S32)m_ranges.size() - 1;
+}
+
+void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes, Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, S32 radius)
+{
+    if (numMeshes < 1 || !meshes) fail("CudaInstancedBVH: no meshes");
+    std::vector<NtrBlasRange> ranges((size_t)numMeshes);
+    int64_t capN, capW, capI;
+    if (ntr_ploc_batch_capacity(numMeshes, meshes, ranges.data(), &capN, &capW, &capI) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    const S64 numTris = triVtxIndex.getSize() / (S64)(3 * sizeof(S32));
+    if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
+    m_ranges.clear();
+    m_built = false;
+    m_poolNodes.resizeDiscard(capN);
+    m_poolTriWoop.resizeDiscard(capW);
+    m_poolTriIndex.resizeDiscard(capI);
+    const int rc = ntr_ploc_build_batch(numMeshes, meshes, (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts,
+                                        (const float*)vtxPos.getCudaPtr(), radius, m_poolNodes.getMutableCudaPtr(), capN,
+                                        m_poolTriWoop.getMutableCudaPtr(), capW, (int32_t*)m_poolTriIndex.getMutableCudaPtr(), capI, ranges.data(),
+                                        NULL, &m_blasResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_ranges.swap(ranges);
 }
 
 void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32* blas)

@@ -3,6 +3,8 @@
 // DESIGN.md 6k; the rule is tests/np_instanced.py).  An extension without a reference class.
 //   addBLAS       copies a CudaBVH's three buffers to aligned offsets of the pool: a Compact tree's links are relative to its own
 //                 start, so no word is rewritten
+//   buildBLASes   builds every mesh of a batch straight into the pool by ntr_ploc_build_batch: one pass for all of them
+//                 instead of one blocking builder call and one copy per BLAS.  The pool then holds exactly these BLASes, in mesh order
 //   setInstances  objectToWorld per instance; worldToObject by ntr_instance_invert
 //   build         the TLAS and the instance records; per frame only this is redone when instances move
 //   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss)
@@ -22,6 +24,9 @@ public:
     ~CudaInstancedBVH(void) {}
 
     S32  addBLAS(CudaBVH& bvh);                                                  // -> the BLAS's index
+    // meshes: triangle ranges of triVtxIndex (Vec3i per triangle) over vtxPos (Vec3f per vertex), each with the box of its Morton codes;
+    // BLAS k is mesh k.  Replaces whatever the pool held.
+    void buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes, Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, S32 radius = DefaultRadius);
     void setInstances(S32 num, const F32* objectToWorld /* num x 12 */, const S32* blas);
     void build(S32 radius = DefaultRadius);
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs);                       // GPU seconds
@@ -30,6 +35,7 @@ public:
     S32  getNumInstances(void) const { return m_numInstances; }
     const NtrBlasRange&  getBLASRange(S32 i) const { return m_ranges[i]; }
     const NtrTlasResult& getBuildResult(void) const { return m_result; }
+    const NtrPlocBatchResult& getBLASBuildResult(void) const { return m_blasResult; }   // of the last buildBLASes (zero before)
     Buffer& getPoolNodeBuffer(void) { return m_poolNodes; }
     Buffer& getPoolTriWoopBuffer(void) { return m_poolTriWoop; }
     Buffer& getPoolTriIndexBuffer(void) { return m_poolTriIndex; }
@@ -47,6 +53,7 @@ private:
     S32           m_numInstances;
     bool          m_built;
     NtrTlasResult m_result;
+    NtrPlocBatchResult m_blasResult;
 };
 
 }  // namespace FW
