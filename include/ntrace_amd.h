@@ -753,6 +753,58 @@ NTR_API int ntr_ploc_build_batch(int32_t numMeshes, const NtrPlocBatchMesh* mesh
 /* Bytes the batch builder's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_ploc_batch_scratch_bytes(int64_t* bytes);
 
+/* Many refits in one pass: the listed BLASes of a pool are refitted to moved vertices in the same two launches
+ * (csrc/bvh_refit_batch_kernels.hip).  The pool is built once (ntr_ploc_build_batch, addBLAS); rigid motion is the TLAS
+ * rebuild; a mesh that DEFORMS keeps its triangles and moves its vertices, and this call is its update path: refit, then ntr_tlas_build
+ * from the new node-0 boxes.  ntr_bvh_refit (below) at pool + offset gives the same bytes, two launches per BLAS.  EXTENSION without a
+ * reference counterpart: the rule is the numpy spec tests/np_refit_batch.py -- np_bvh_refit.refit over every entry's slices of the pool.
+ *   entry       the BLAS's range as ntr_ploc_build_batch / addBLAS report it; its mesh, triangles [firstTri, +numTris) of the shared
+ *               d_triVtxIndex (the BLAS's triIndex entries are relative to firstTri); its epsilon, the leaf-box rule of ntr_bvh_refit
+ *               (0 for PLOC and host SAH trees, 0.001 for the LBVH's)
+ *   bytes       every entry's ranges hold what ntr_bvh_refit writes when called on pool + offset with d_triVtxIndex + 3 * firstTri,
+ *               numTris and the entry's epsilon.  Every other byte of the pool is untouched, those inside a listed range that
+ *               ntr_bvh_refit leaves alone included (links, terminators, triIndex, unreached slots)
+ *   entries     any subset of the pool's BLASes in any order; two entries may name the same or overlapping triangles; two entries whose
+ *               node ranges or row ranges overlap are refused (two threads would refit one tree)
+ *   d_poolTriIndex  one entry per pool row (poolTriWoopBytes / 4 bytes), as the pool's builders leave it
+ *   d_blasBoxes optional, 6 floats per entry in entry order, min.xyz max.xyz: the union of the two boxes of the BLAS's node 0
+ *   lanesPerLeaf  1, 4 or 8, chosen once per call from the selection's mean leaf size by ntr_bvh_refit's thresholds: speed only
+ * With result == NULL the call is asynchronous on `stream`: two launches, no read-back, no memset.  With result != NULL it blocks and
+ * reads the counts and the GPU time back.  A malformed tree is never followed (the errors are ntr_bvh_refit's): the blocking form
+ * returns NTR_ERR_LAYOUT, fills *result all the same, and names the lowest bad entry in firstBadEntry and the message; every other
+ * entry has been refitted completely, since entries share no node.  With result == NULL such a part is skipped silently.
+ * The device's entry table (32 B per entry and a running sum) and the topology arrays (8 B per listed node slot, 16 KB of counters)
+ * live in a per-device grow-only pool of its own that ntr_lbvh_release_workspace returns.  The table is uploaded only when it differs
+ * from the one the previous call on this device uploaded (that call then waits for its upload; a frame loop over one selection pays
+ * it once).  A captured call uploads nothing and allocates nothing: it is accepted only when the last uncaptured call on this device
+ * had the same entries and the pool has not been released since, else NTR_ERR_INVALID says so.  While such a graph
+ * lives, make no call with other entries and do not release the workspace: the graph's launches read the table and the arrays in
+ * place.  One call per device at a time.
+ * NTR_ERR_INVALID (before any device work): a null pointer (d_blasBoxes and result may be null), numEntries outside 1..2^20, pool
+ * sizes that are not multiples of 64 / 16 within 0xFFFFFF00, pool pointers not 16-byte aligned, a range that is misaligned, outside
+ * the pool's extents or above the limits of ntr_tlas_build, triWoopBytes < 16, a mesh outside [0, numTrisTotal) or with numTris < 1,
+ * a negative or non-finite epsilon, overlapping or duplicate entries, numVerts < 1.  Without a device, after these checks:
+ * NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback).  Every failure but NTR_ERR_LAYOUT zeroes *result. */
+typedef struct NtrRefitBatchEntry {      /* host array, one per BLAS to refit: 48 bytes */
+    NtrBlasRange range;
+    int32_t firstTri, numTris;
+    float   epsilon;
+    int32_t pad;
+} NtrRefitBatchEntry;
+typedef struct NtrBvhRefitBatchResult {
+    int32_t numEntries, lanesPerLeaf;    /* lanesPerLeaf says which kernel ran */
+    int64_t numNodes, numLeaves, numRows;/* sums over the entries of what ntr_bvh_refit counts */
+    int32_t firstBadEntry, errBits;      /* -1 / 0, or the lowest entry whose tree is malformed and the OR of ntr_bvh_refit's error bits */
+    float   seconds, pad;                /* GPU time */
+} NtrBvhRefitBatchResult;
+NTR_API int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries,
+                                void* d_poolNodes, int64_t poolNodesBytes, void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                                const int32_t* d_poolTriIndex, int32_t numTrisTotal, const int32_t* d_triVtxIndex,
+                                int32_t numVerts, const float* d_vtxPos, float* d_blasBoxes /* may be NULL: 6 floats per entry */,
+                                NtrBvhRefitBatchResult* result /* NULL: asynchronous */, void* stream);
+/* Bytes the batch refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_refit_batch_scratch_bytes(int64_t* bytes);
+
 /* 4-wide BVH: an out-of-place pass that turns any BVHLayout_Compact tree into 4-wide nodes, and the trace that walks them
  * (csrc/bvh_widen_kernels.hip, csrc/trace_wide_kernels.hip, csrc/wide_bvh.h).  EXTENSION without a reference counterpart: the rule is the
  * numpy spec tests/np_bvh_wide.py, which ntr_bvh_widen equals byte for byte and ntr_trace_wide in all four result words.  Leaves, Woop rows

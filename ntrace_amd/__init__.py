@@ -22,6 +22,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     BvhReorderResult, bvh_reorder, bvh_reorder_scratch_bytes,
                     PlocResult, ploc_build, ploc_scratch_bytes, PLOC_TAIL, PLOC_TILE,
                     PlocBatchMesh, PlocBatchMeshResult, PlocBatchResult, ploc_batch_capacity, ploc_build_batch, ploc_batch_scratch_bytes,
+                    RefitBatchEntry, BvhRefitBatchResult, bvh_refit_batch, bvh_refit_batch_scratch_bytes,
                     INSTANCE_DTYPE, BlasRange, BlasPool, TlasResult, instance_invert, make_instances, tlas_capacity, tlas_build,
                     tlas_scratch_bytes, trace_instanced,
                     BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats)
@@ -42,6 +43,7 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "bvh_sah_cost", "BvhReorderResult", "bvh_reorder", "bvh_reorder_scratch_bytes",
            "PlocResult", "ploc_build", "ploc_scratch_bytes", "PLOC_TAIL", "PLOC_TILE",
            "PlocBatchMesh", "PlocBatchMeshResult", "PlocBatchResult", "ploc_batch_capacity", "ploc_build_batch", "ploc_batch_scratch_bytes",
+           "RefitBatchEntry", "BvhRefitBatchResult", "bvh_refit_batch", "bvh_refit_batch_scratch_bytes",
            "INSTANCE_DTYPE", "BlasRange", "BlasPool", "TlasResult", "instance_invert", "make_instances", "tlas_capacity", "tlas_build",
            "tlas_scratch_bytes", "trace_instanced",
            "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats"]

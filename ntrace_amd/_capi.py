@@ -148,6 +148,24 @@ class PlocBatchResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class RefitBatchEntry(C.Structure):
+    """NtrRefitBatchEntry: one BLAS of a pool to refit -- its range, its mesh (triangles [firstTri, +numTris) of the shared index array)
+    and the epsilon of its leaf boxes."""
+    _fields_ = [("range", BlasRange), ("firstTri", C.c_int32), ("numTris", C.c_int32), ("epsilon", C.c_float), ("pad", C.c_int32)]
+
+    def __init__(self, blas_range=(0, 0, 0, 0), first_tri=0, num_tris=0, epsilon=0.0):
+        r = blas_range if isinstance(blas_range, BlasRange) else BlasRange(*[int(x) for x in blas_range])
+        super().__init__(r, int(first_tri), int(num_tris), float(epsilon), 0)
+
+
+class BvhRefitBatchResult(C.Structure):
+    _fields_ = [("numEntries", C.c_int32), ("lanesPerLeaf", C.c_int32), ("numNodes", C.c_int64), ("numLeaves", C.c_int64),
+                ("numRows", C.c_int64), ("firstBadEntry", C.c_int32), ("errBits", C.c_int32), ("seconds", C.c_float), ("pad", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class TlasResult(C.Structure):
     _fields_ = [("rootLink", C.c_int32), ("numNodes", C.c_int32), ("numRounds", C.c_int32), ("height", C.c_int32),
                 ("tailClusters", C.c_int32), ("pad", C.c_int32 * 3), ("nodesBytes", C.c_int64), ("recordsBytes", C.c_int64),
@@ -332,6 +350,8 @@ SYMBOLS = [
     ("ntr_trace_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp, C.POINTER(TraceStats)]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(BvhRefitBatchResult), _vp]),
+    ("ntr_bvh_refit_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
     ("ntr_bvh_optimize_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_sah_cost", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhSahResult), _vp]),
@@ -1013,6 +1033,41 @@ def bvh_refit_scratch_bytes():
     """ntr_bvh_refit_scratch_bytes: bytes the refit's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_bvh_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def _refit_entries(entries):
+    """A ctypes array of RefitBatchEntry from RefitBatchEntry objects or (range, firstTri, numTris[, epsilon]) tuples."""
+    if isinstance(entries, C.Array):
+        return entries
+    items = [e if isinstance(e, RefitBatchEntry) else RefitBatchEntry(*e) for e in entries]
+    return (RefitBatchEntry * max(len(items), 1))(*items)
+
+
+def bvh_refit_batch(entries, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_idx, num_tris_total, d_tri, num_verts,
+                    d_pos, d_blas_boxes=0, stream=0, blocking=True):
+    """ntr_bvh_refit_batch: refit the listed BLASes of a pool (RefitBatchEntry objects or (range, firstTri, numTris[, epsilon]) tuples) to
+    the vertex positions at d_pos in one pass; every BLAS comes out byte for byte as bvh_refit at pool + offset leaves it (the rule is
+    tests/np_refit_batch.py).  blocking=True returns a BvhRefitBatchResult; blocking=False passes result = NULL: asynchronous on `stream`
+    and returns None.  An NtrError for a malformed tree (NTR_ERR_LAYOUT, after the work) carries .result, filled: firstBadEntry, errBits
+    and the counts."""
+    n = len(entries)
+    arr = _refit_entries(entries)
+    res = BvhRefitBatchResult() if blocking else None
+    try:
+        _check(lib().ntr_bvh_refit_batch(n, C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
+                                         _vp(d_pool_idx), int(num_tris_total), _vp(d_tri), int(num_verts), _vp(d_pos), _vp(d_blas_boxes),
+                                         C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def bvh_refit_batch_scratch_bytes():
+    """ntr_bvh_refit_batch_scratch_bytes: bytes the batch refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_refit_batch_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

@@ -9,6 +9,7 @@ CudaInstancedBVH::CudaInstancedBVH(void) : m_numInstances(0), m_built(false)
 {
     std::memset(&m_result, 0, sizeof(m_result));
     std::memset(&m_blasResult, 0, sizeof(m_blasResult));
+    std::memset(&m_refitResult, 0, sizeof(m_refitResult));
 }
 
 S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
@@ -31,6 +32,8 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_poolTriWoop.setRange(r.triWoopOffset, woop, 0, r.triWoopBytes);
     m_poolTriIndex.setRange(r.triWoopOffset / 4, index, 0, r.triWoopBytes / 4);
     m_ranges.push_back(r);
+    const Mesh none = {0, 0};
+    m_meshes.push_back(none);
     m_built = false;
     return (S32)m_ranges.size() - 1;
 }
@@ -44,6 +47,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     const S64 numTris = triVtxIndex.getSize() / (S64)(3 * sizeof(S32));
     if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
     m_ranges.clear();
+    m_meshes.clear();
     m_built = false;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
@@ -54,6 +58,38 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
                                         NULL, &m_blasResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_ranges.swap(ranges);
+    m_meshes.resize((size_t)numMeshes);
+    for (S32 k = 0; k < numMeshes; k++) {
+        m_meshes[k].firstTri = meshes[k].firstTri;
+        m_meshes[k].numTris = meshes[k].numTris;
+    }
+}
+
+void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas, S32 num, F32 epsilon)
+{
+    if (m_ranges.empty()) fail("CudaInstancedBVH: no BLASes to refit (call buildBLASes first)");
+    if (!blas) num = (S32)m_ranges.size();
+    if (num < 1) fail("CudaInstancedBVH: no BLASes selected");
+    const S64 numTris = triVtxIndex.getSize() / (S64)(3 * sizeof(S32));
+    if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
+    std::vector<NtrRefitBatchEntry> entries((size_t)num);
+    for (S32 i = 0; i < num; i++) {
+        const S32 b = blas ? blas[i] : i;
+        if (b < 0 || b >= (S32)m_ranges.size()) fail("CudaInstancedBVH: BLAS index %d outside [0, %d)", b, (S32)m_ranges.size());
+        if (m_meshes[b].numTris < 1) fail("CudaInstancedBVH: BLAS %d came through addBLAS and has no mesh here: refit its CudaBVH and add it again", b);
+        NtrRefitBatchEntry& e = entries[i];
+        e.range = m_ranges[b];
+        e.firstTri = m_meshes[b].firstTri;
+        e.numTris = m_meshes[b].numTris;
+        e.epsilon = epsilon;
+        e.pad = 0;
+    }
+    m_built = false;
+    const int rc = ntr_bvh_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
+                                       m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
+                                       (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
+                                       NULL, &m_refitResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
 }
 
 void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32* blas)

@@ -5,6 +5,10 @@
 //                 start, so no word is rewritten
 //   buildBLASes   builds every mesh of a batch straight into the pool by ntr_ploc_build_batch: one pass for all of them
 //                 instead of one blocking builder call and one copy per BLAS.  The pool then holds exactly these BLASes, in mesh order
+//   refitBLASes   after the meshes' vertices have moved (their triangles kept): refits the selected BLASes in place by
+//                 ntr_bvh_refit_batch, all in one pass.  The meshes are those buildBLASes was given, which this class
+//                 remembers; a BLAS that came through addBLAS has no mesh here and cannot be selected.  build() afterwards rebuilds the
+//                 TLAS from the new node-0 boxes; nothing else is needed
 //   setInstances  objectToWorld per instance; worldToObject by ntr_instance_invert
 //   build         the TLAS and the instance records; per frame only this is redone when instances move
 //   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss)
@@ -27,6 +31,9 @@ public:
     // meshes: triangle ranges of triVtxIndex (Vec3i per triangle) over vtxPos (Vec3f per vertex), each with the box of its Morton codes;
     // BLAS k is mesh k.  Replaces whatever the pool held.
     void buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes, Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, S32 radius = DefaultRadius);
+    // blas: num indices of BLASes to refit, each at most once (NULL: all of them); epsilon: the leaf-box rule of ntr_bvh_refit, 0 for
+    // the PLOC trees buildBLASes makes.  triVtxIndex must hold the triangles buildBLASes saw.
+    void refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas = NULL, S32 num = -1, F32 epsilon = 0.f);
     void setInstances(S32 num, const F32* objectToWorld /* num x 12 */, const S32* blas);
     void build(S32 radius = DefaultRadius);
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs);                       // GPU seconds
@@ -36,6 +43,7 @@ public:
     const NtrBlasRange&  getBLASRange(S32 i) const { return m_ranges[i]; }
     const NtrTlasResult& getBuildResult(void) const { return m_result; }
     const NtrPlocBatchResult& getBLASBuildResult(void) const { return m_blasResult; }   // of the last buildBLASes (zero before)
+    const NtrBvhRefitBatchResult& getBLASRefitResult(void) const { return m_refitResult; }   // of the last refitBLASes (zero before)
     Buffer& getPoolNodeBuffer(void) { return m_poolNodes; }
     Buffer& getPoolTriWoopBuffer(void) { return m_poolTriWoop; }
     Buffer& getPoolTriIndexBuffer(void) { return m_poolTriIndex; }
@@ -47,13 +55,16 @@ private:
     CudaInstancedBVH(const CudaInstancedBVH&);
     CudaInstancedBVH& operator=(const CudaInstancedBVH&);
 
+    struct Mesh { S32 firstTri, numTris; };                                      // numTris 0: an addBLAS tree, no mesh
     std::vector<NtrBlasRange> m_ranges;
+    std::vector<Mesh>         m_meshes;                                          // per BLAS, as m_ranges
     Buffer        m_poolNodes, m_poolTriWoop, m_poolTriIndex;
     Buffer        m_instances, m_tlasNodes, m_records;
     S32           m_numInstances;
     bool          m_built;
     NtrTlasResult m_result;
     NtrPlocBatchResult m_blasResult;
+    NtrBvhRefitBatchResult m_refitResult;
 };
 
 }  // namespace FW
