@@ -706,6 +706,55 @@ NTR_API int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d
                                 int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds /* NULL: asynchronous */,
                                 void* stream);
 
+/* Refit of a top-level tree: the TLAS keeps its topology and gets its instance records and every box again, from the current
+ * instances and the pool's current node-0 boxes, in two launches (csrc/tlas_refit_kernels.hip).  It is the update path
+ * of a frame whose instances moved rigidly or whose BLASes were refitted (ntr_bvh_refit_batch); ntr_tlas_build, a blocking chain of
+ * some dozens of launches, restores the tree's quality every so many frames.  EXTENSION without a reference counterpart: the rule is
+ * the numpy spec tests/np_tlas_refit.py, which the device equals byte for byte.
+ *   input       the node buffer, rootLink and record buffer ntr_tlas_build filled for the same number of instances (or any buffers
+ *               of that layout); d_instances as for ntr_tlas_build (here 16-byte aligned), with new transforms and, where an instance
+ *               switched its BLAS (a level of detail), a new blas index
+ *   record i    ntr_tlas_build's record of the current instance i
+ *   boxes       the box of a child ~i is instance i's world box as ntr_tlas_build forms it; the box of an inner child is the union of
+ *               the two boxes in that child's node (-0 < +0).  PLOC forms a cluster's box by the same union, so the refit of a fresh
+ *               build with unchanged instances changes no byte
+ *   untouched   words 12..15 of every node, every node slot no link reaches, everything beyond the extents
+ *   d_sceneBox  optional, 6 floats, min.xyz max.xyz: the union of node 0's two boxes (N == 1: instance 0's box)
+ *   counts      numNodes: 1 + the links that name a slot; numLeaves: the leaf links (N == 1: 0 and 1, the root link)
+ * With result == NULL the call is asynchronous on `stream` and capturable: two launches (one for N == 1), no read-back, no memset; the
+ * first launch clears the arrival counters.  With result != NULL it blocks and reads the counts, the error bits, the scene box and the
+ * GPU time back.  A bad part is never followed, and nothing outside the buffers is read or written whatever a link, an index or a
+ * record holds: an instance whose blas index lies outside [0, numBlas) keeps its record and its leaf box, a link > 0 that names no slot
+ * and a leaf link ~i with i >= numInstances are skipped; the boxes of the ancestors of such a place stay as they were (a box is
+ * rewritten exactly where everything below it is well formed), and everything else is refitted completely.  The blocking form then
+ * returns NTR_ERR_INVALID (bit 1, ntr_tlas_build's "blas index" message) or NTR_ERR_LAYOUT (bits 2, 4) with *result filled, sceneMin /
+ * sceneMax zero where the root was not refitted; the asynchronous form skips such a part silently.  Slots that only a bad link named
+ * are out of the rule: they may be refitted among themselves.
+ * The scratch -- 8 B per node slot (parent word, arrival counter), 16 B per BLAS (the range table), 16 KB of counters -- is a per-device
+ * grow-only pool of its own that ntr_lbvh_release_workspace returns.  The range table is uploaded only when it differs from the one
+ * the previous call on this device uploaded (that call then waits for its upload; a frame loop over one pool pays it once).  A captured
+ * call uploads nothing and allocates nothing: it is accepted only when the last uncaptured call on this device had the same ranges and
+ * instance count and the pool has not been released since, else NTR_ERR_INVALID says so.  While such a graph lives, make no call with
+ * other ranges and do not release the workspace.  One call per device at a time.
+ * NTR_ERR_INVALID (before any device work; *result zeroed): a null pointer (d_sceneBox and result may be null, d_tlasNodes only when
+ * numInstances == 1), numInstances < 1 or numInstances - 1 above Compact's node limit, numBlas < 1, tlasNodesBytes other than
+ * 64 * (numInstances - 1), rootLink other than 0 (N >= 2) or ~0 (N == 1), recordsCapacity < 64 * numInstances, buffers not 16-byte
+ * aligned, a pool size or BLAS range that ntr_tlas_build refuses, a captured call with a result.  Without a device, after these
+ * checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrTlasRefitResult {
+    int32_t numNodes, numLeaves;        /* reached node slots; leaf links of reached slots (== numInstances for a tree ntr_tlas_build made) */
+    int32_t errBits, pad;               /* 0, or: 1 an instance's blas index outside [0, numBlas); 2 a link > 0 that names no slot;
+                                           4 a leaf link ~i with i >= numInstances */
+    float   sceneMin[3], sceneMax[3];
+    float   seconds, pad2;              /* GPU time */
+} NtrTlasRefitResult;
+NTR_API int ntr_tlas_refit(int32_t numInstances, const NtrInstance* d_instances, int32_t numBlas, const NtrBlasRange* blasRanges,
+                           const void* d_poolNodes, int64_t poolNodesBytes, void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink,
+                           void* d_records, int64_t recordsCapacity, float* d_sceneBox /* may be NULL: 6 floats */,
+                           NtrTlasRefitResult* result /* NULL: asynchronous */, void* stream);
+/* Bytes the TLAS refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_tlas_refit_scratch_bytes(int64_t* bytes);
+
 /* Many PLOC builds in one pass: every mesh of a batch becomes one BLAS of a pool, all of them in the same launches
  * (csrc/bvh_ploc_batch_kernels.hip; it stands here, not beside ntr_ploc_build, because it fills NtrBlasRange).  ntr_ploc_build is a
  * chain of some hundred launches and a read-back per four rounds whatever the mesh's size; a scene of a thousand small meshes pays that
@@ -755,8 +804,8 @@ NTR_API int ntr_ploc_batch_scratch_bytes(int64_t* bytes);
 
 /* Many refits in one pass: the listed BLASes of a pool are refitted to moved vertices in the same two launches
  * (csrc/bvh_refit_batch_kernels.hip).  The pool is built once (ntr_ploc_build_batch, addBLAS); rigid motion is the TLAS
- * rebuild; a mesh that DEFORMS keeps its triangles and moves its vertices, and this call is its update path: refit, then ntr_tlas_build
- * from the new node-0 boxes.  ntr_bvh_refit (below) at pool + offset gives the same bytes, two launches per BLAS.  EXTENSION without a
+ * rebuild or refit; a mesh that DEFORMS keeps its triangles and moves its vertices, and this call is its update path: refit, then
+ * ntr_tlas_refit (or ntr_tlas_build) from the new node-0 boxes.  ntr_bvh_refit (below) at pool + offset gives the same bytes, two launches per BLAS.  EXTENSION without a
  * reference counterpart: the rule is the numpy spec tests/np_refit_batch.py -- np_bvh_refit.refit over every entry's slices of the pool.
  *   entry       the BLAS's range as ntr_ploc_build_batch / addBLAS report it; its mesh, triangles [firstTri, +numTris) of the shared
  *               d_triVtxIndex (the BLAS's triIndex entries are relative to firstTri); its epsilon, the leaf-box rule of ntr_bvh_refit

@@ -24,7 +24,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     PlocBatchMesh, PlocBatchMeshResult, PlocBatchResult, ploc_batch_capacity, ploc_build_batch, ploc_batch_scratch_bytes,
                     RefitBatchEntry, BvhRefitBatchResult, bvh_refit_batch, bvh_refit_batch_scratch_bytes,
                     INSTANCE_DTYPE, BlasRange, BlasPool, TlasResult, instance_invert, make_instances, tlas_capacity, tlas_build,
-                    tlas_scratch_bytes, trace_instanced,
+                    tlas_scratch_bytes, trace_instanced, TlasRefitResult, tlas_refit, tlas_refit_scratch_bytes,
                     BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats)
 
 BVHLayout_Compact = 4
@@ -45,5 +45,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "PlocBatchMesh", "PlocBatchMeshResult", "PlocBatchResult", "ploc_batch_capacity", "ploc_build_batch", "ploc_batch_scratch_bytes",
            "RefitBatchEntry", "BvhRefitBatchResult", "bvh_refit_batch", "bvh_refit_batch_scratch_bytes",
            "INSTANCE_DTYPE", "BlasRange", "BlasPool", "TlasResult", "instance_invert", "make_instances", "tlas_capacity", "tlas_build",
-           "tlas_scratch_bytes", "trace_instanced",
+           "tlas_scratch_bytes", "trace_instanced", "TlasRefitResult", "tlas_refit", "tlas_refit_scratch_bytes",
            "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats"]

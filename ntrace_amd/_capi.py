@@ -176,6 +176,14 @@ class TlasResult(C.Structure):
         return {k: (list(getattr(self, k)) if k.startswith("scene") else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+class TlasRefitResult(C.Structure):
+    _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("errBits", C.c_int32), ("pad", C.c_int32),
+                ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3), ("seconds", C.c_float), ("pad2", C.c_float)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.startswith("scene") else getattr(self, k)) for k, _ in self._fields_ if not k.startswith("pad")}
+
+
 class BvhWideResult(C.Structure):
     _fields_ = [("nodesBytes", C.c_int64), ("numNodes", C.c_int32), ("counts", C.c_int32 * 3), ("numLeafLinks", C.c_int32),
                 ("height", C.c_int32), ("stackBound", C.c_int32), ("seconds", C.c_float)]
@@ -342,6 +350,8 @@ SYMBOLS = [
     ("ntr_tlas_capacity", C.c_int, [_i32, C.POINTER(_i64), C.POINTER(_i64)]),
     ("ntr_tlas_build", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, C.POINTER(TlasResult), _vp]),
     ("ntr_tlas_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_tlas_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
+    ("ntr_tlas_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_trace_instanced", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, C.POINTER(C.c_float), _vp]),
     ("ntr_bvh_widen_capacity", C.c_int, [_i64, C.POINTER(_i64)]),
     ("ntr_bvh_widen", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhWideResult), _vp]),
@@ -960,6 +970,33 @@ def tlas_scratch_bytes():
     """ntr_tlas_scratch_bytes: bytes the top-level builder's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_tlas_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def tlas_refit(num_instances, d_instances, ranges, d_pool_nodes, pool_nodes_bytes, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+               records_cap, d_scene_box=0, stream=0, blocking=True):
+    """ntr_tlas_refit: keep a top-level tree's topology and rewrite its instance records and every box from the current instances and the
+    pool's current node-0 boxes (an extension; the rule is tests/np_tlas_refit.py).  ranges as for tlas_build.  blocking=True returns a
+    TlasRefitResult; blocking=False passes result = NULL: asynchronous on `stream` (capturable) and returns None.  An NtrError raised
+    after the device work (a bad blas index, a malformed tree) carries .result, filled: errBits and the counts."""
+    if isinstance(ranges, BlasPool):
+        ranges = ranges.ranges
+    arr = (BlasRange * max(len(ranges), 1))(*[BlasRange(*[int(x) for x in r]) for r in ranges])
+    res = TlasRefitResult() if blocking else None
+    try:
+        _check(lib().ntr_tlas_refit(int(num_instances), _vp(d_instances), len(ranges), C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes),
+                                    _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(records_cap), _vp(d_scene_box),
+                                    C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def tlas_refit_scratch_bytes():
+    """ntr_tlas_refit_scratch_bytes: bytes the TLAS refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_tlas_refit_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

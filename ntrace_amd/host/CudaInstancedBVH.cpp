@@ -1,15 +1,17 @@
-// CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_trace_instanced (see the header).
+// CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
+// (see the header).
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
 
 namespace FW {
 
-CudaInstancedBVH::CudaInstancedBVH(void) : m_numInstances(0), m_built(false)
+CudaInstancedBVH::CudaInstancedBVH(void) : m_numInstances(0), m_built(false), m_topology(false)
 {
     std::memset(&m_result, 0, sizeof(m_result));
     std::memset(&m_blasResult, 0, sizeof(m_blasResult));
     std::memset(&m_refitResult, 0, sizeof(m_refitResult));
+    std::memset(&m_tlasRefitResult, 0, sizeof(m_tlasRefitResult));
 }
 
 S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
@@ -34,7 +36,7 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_ranges.push_back(r);
     const Mesh none = {0, 0};
     m_meshes.push_back(none);
-    m_built = false;
+    m_built = m_topology = false;
     return (S32)m_ranges.size() - 1;
 }
 
@@ -48,7 +50,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
     m_ranges.clear();
     m_meshes.clear();
-    m_built = false;
+    m_built = m_topology = false;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
     m_poolTriIndex.resizeDiscard(capI);
@@ -103,6 +105,7 @@ void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32
         if (ntr_instance_invert(inst[i].objectToWorld, inst[i].worldToObject) != NTR_OK) fail("CudaInstancedBVH: instance %d: %s", i, ntr_last_error());
         inst[i].blas = blas[i];
     }
+    if (num != m_numInstances) m_topology = false;   // an unchanged count keeps the TLAS's topology for refit()
     m_numInstances = num;
     m_built = false;
 }
@@ -112,6 +115,7 @@ void CudaInstancedBVH::build(S32 radius)
     if (m_ranges.empty() || m_numInstances < 1) fail("CudaInstancedBVH: nothing to build");
     int64_t capN, capR;
     if (ntr_tlas_capacity(m_numInstances, &capN, &capR) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_built = m_topology = false;
     m_tlasNodes.resizeDiscard(capN);
     m_records.resizeDiscard(capR);
     const int rc = ntr_tlas_build(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
@@ -119,6 +123,25 @@ void CudaInstancedBVH::build(S32 radius)
                                   m_records.getMutableCudaPtr(), capR, &m_result, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     if (m_result.nodesBytes) m_tlasNodes.resize(m_result.nodesBytes);   // (N == 1 has no node: the buffer keeps its one unused slot)
+    m_built = m_topology = true;
+}
+
+void CudaInstancedBVH::refit(void)
+{
+    if (!m_topology || m_numInstances < 1)
+        fail("CudaInstancedBVH: no TLAS to refit: call build() first, and again after the instance count or the BLASes have changed");
+    const int rc = ntr_tlas_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
+                                  m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL,
+                                  m_result.nodesBytes, m_result.rootLink, m_records.getMutableCudaPtr(), m_records.getSize(), NULL,
+                                  &m_tlasRefitResult, NULL);
+    if (rc != NTR_OK) {
+        m_built = false;                         // a part of the tree kept stale boxes
+        fail("CudaInstancedBVH: %s", ntr_last_error());
+    }
+    for (int a = 0; a < 3; a++) {
+        m_result.sceneMin[a] = m_tlasRefitResult.sceneMin[a];
+        m_result.sceneMax[a] = m_tlasRefitResult.sceneMax[a];
+    }
     m_built = true;
 }
 

@@ -7,10 +7,16 @@
 //                 instead of one blocking builder call and one copy per BLAS.  The pool then holds exactly these BLASes, in mesh order
 //   refitBLASes   after the meshes' vertices have moved (their triangles kept): refits the selected BLASes in place by
 //                 ntr_bvh_refit_batch, all in one pass.  The meshes are those buildBLASes was given, which this class
-//                 remembers; a BLAS that came through addBLAS has no mesh here and cannot be selected.  build() afterwards rebuilds the
-//                 TLAS from the new node-0 boxes; nothing else is needed
-//   setInstances  objectToWorld per instance; worldToObject by ntr_instance_invert
-//   build         the TLAS and the instance records; per frame only this is redone when instances move
+//                 remembers; a BLAS that came through addBLAS has no mesh here and cannot be selected.  refit() (or build()) afterwards
+//                 brings the TLAS to the new node-0 boxes; nothing else is needed
+//   setInstances  objectToWorld per instance; worldToObject by ntr_instance_invert.  With an unchanged count the TLAS built before stays
+//                 usable for refit()
+//   build         the TLAS and the instance records, from scratch: a blocking chain of launches (ntr_tlas_build)
+//   refit         keeps the topology of the last build() and rewrites the records and every box from the current instances and the
+//                 pool's current node-0 boxes in two launches (ntr_tlas_refit).  Needs a build() with the same instance
+//                 count; a changed count, addBLAS and buildBLASes invalidate it as they invalidate build().  The frame loop of a moving,
+//                 deforming scene is refitBLASes -> setInstances -> refit -> traceBatch, with build() every so many frames: a refit
+//                 keeps the tree the old positions suggested, and its boxes overlap more the further the instances travel
 //   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss)
 #pragma once
 #include <vector>
@@ -36,6 +42,7 @@ public:
     void refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas = NULL, S32 num = -1, F32 epsilon = 0.f);
     void setInstances(S32 num, const F32* objectToWorld /* num x 12 */, const S32* blas);
     void build(S32 radius = DefaultRadius);
+    void refit(void);
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs);                       // GPU seconds
 
     S32  getNumBLAS(void) const { return (S32)m_ranges.size(); }
@@ -44,6 +51,7 @@ public:
     const NtrTlasResult& getBuildResult(void) const { return m_result; }
     const NtrPlocBatchResult& getBLASBuildResult(void) const { return m_blasResult; }   // of the last buildBLASes (zero before)
     const NtrBvhRefitBatchResult& getBLASRefitResult(void) const { return m_refitResult; }   // of the last refitBLASes (zero before)
+    const NtrTlasRefitResult& getRefitResult(void) const { return m_tlasRefitResult; }       // of the last refit (zero before)
     Buffer& getPoolNodeBuffer(void) { return m_poolNodes; }
     Buffer& getPoolTriWoopBuffer(void) { return m_poolTriWoop; }
     Buffer& getPoolTriIndexBuffer(void) { return m_poolTriIndex; }
@@ -61,10 +69,12 @@ private:
     Buffer        m_poolNodes, m_poolTriWoop, m_poolTriIndex;
     Buffer        m_instances, m_tlasNodes, m_records;
     S32           m_numInstances;
-    bool          m_built;
+    bool          m_built;                                                       // the TLAS is current: traceBatch may run
+    bool          m_topology;                                                    // a TLAS of m_numInstances leaves over these BLASes exists: refit may run
     NtrTlasResult m_result;
     NtrPlocBatchResult m_blasResult;
     NtrBvhRefitBatchResult m_refitResult;
+    NtrTlasRefitResult m_tlasRefitResult;
 };
 
 }  // namespace FW
