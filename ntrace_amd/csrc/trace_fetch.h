@@ -102,7 +102,9 @@ struct UnifiedBufs {
     unsigned int dN, dW;    // nodes - base, woop - base
     unsigned int limNode;   // largest inner-node offset whose 64 bytes lie inside the node buffer (below the sentinel: `node <= limNode` implies inner)
     int limTri;             // smallest (most negative) triangle cursor ~index whose 64 bytes lie inside triWoop
+    unsigned int oddBase, oddSpan;   // limNode < (unsigned)node < (unsigned)limTri, as node - oddBase < oddSpan: neither of the two (the sentinel included)
 };
+template <bool TRIM = false>   // TRIM: the bodies whose fetch asks for its end-of-buffer lanes with one range test (unified_fetch<.., TRIM>)
 __device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
 {
     UnifiedBufs u;
@@ -118,6 +120,8 @@ __device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
     u.dN = (unsigned int)(an - lo); u.dW = (unsigned int)(aw - lo);
     u.limNode = p.nodesBytes - kFetchBytes;
     u.limTri = leaf_link((int)((p.woopBytes - kFetchBytes) >> kRowShift));
+    u.oddBase = u.limNode + 1u; u.oddSpan = (unsigned)u.limTri - u.oddBase;
+    if (TRIM) asm volatile("" : "+s"(u.oddBase), "+s"(u.oddSpan));   // (two numbers of their own: seen through, the range test is folded back into flatOk's compares and their 0 / 1 VGPR)
     return u;
 }
 
@@ -130,8 +134,11 @@ __device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
 // 85 VGPRs, five waves per SIMD; scripts/studies/rejected_patches/two_rays_per_lane.patch, EXPERIMENTS.md).
 // unified_fetch: one 64-byte fetch per lane from its own buffer -- the node of a lane at an inner node, the triangle (48 B + the following
 // word) of a lane at a leaf.  Issues the loads and, apart from the rare end-of-buffer lanes, does not wait for them.
-template <bool FLAT>
-__device__ __forceinline__ void unified_fetch(const UnifiedBufs& ub, int node, float4& a, float4& b, float4& c, float4& d)
+// `live`: the wave's lanes that hold a node or a triangle cursor (node != kSentinel), as the loop's own ballot has them.
+// TRIM (the per-ray bodies): the end-of-buffer test as one unsigned compare per kind and one range test for "neither", the masks formed
+// as SGPR pairs.  The persistent kernels keep the earlier form: the two scalars more cost them scalar spills.
+template <bool FLAT, bool TRIM = false>
+__device__ __forceinline__ void unified_fetch(const UnifiedBufs& ub, int node, unsigned long long live, float4& a, float4& b, float4& c, float4& d)
 {
     const bool inner = (unsigned)node < (unsigned)kSentinel;
     const bool atTri = node < 0;
@@ -139,7 +146,9 @@ __device__ __forceinline__ void unified_fetch(const UnifiedBufs& ub, int node, f
     if (FLAT) {
         asm volatile("" : "=v"(a.x), "=v"(a.y), "=v"(a.z), "=v"(a.w), "=v"(b.x), "=v"(b.y), "=v"(b.z), "=v"(b.w));   // defined, whatever the lane
         asm volatile("" : "=v"(c.x), "=v"(c.y), "=v"(c.z), "=v"(c.w), "=v"(d.x), "=v"(d.y), "=v"(d.z), "=v"(d.w));
-        const bool okNode = (unsigned)node <= ub.limNode, okTri = atTri && node >= ub.limTri;   // (extents are >= 64 here)
+        // one unsigned compare per kind (extents are >= 64 here, so limTri < 0: as unsigned numbers the cursors from limTri up are the
+        // negative ones >= limTri, and limNode lies below the sentinel)
+        const bool okNode = (unsigned)node <= ub.limNode, okTri = TRIM ? (unsigned)node >= (unsigned)ub.limTri : atTri && node >= ub.limTri;
         const bool flatOk = okNode || okTri;
         const unsigned int cofs = okNode ? ub.dN + (unsigned)node : ub.dW + ((unsigned)leaf_row(node) << kRowShift);   // from the scalar base: a 32-bit offset
         if (flatOk) {   // (global address space spelled out: the base comes out of integer arithmetic, and a generic pointer would be a flat_load)
@@ -148,9 +157,18 @@ __device__ __forceinline__ void unified_fetch(const UnifiedBufs& ub, int node, f
             const u32x4 qa = q[0], qb = q[1], qc = q[2], qd = q[3];
             a = as_f4(qa); b = as_f4(qb); c = as_f4(qc); d = as_f4(qd);
         }
-        const unsigned long long odd = __ballot((inner || atTri) && !flatOk);
-        if (odd != 0ull)   // rare: range-checked descriptor loads, into the same registers, for the lanes at the very end of a buffer
-            fetch64_two_buffers_into(ub.rNodes, ub.rWoop, inner ? node : leaf_row(node) * kRowBytes, __ballot(inner && !flatOk), __ballot(atTri && !flatOk), a, b, c, d);
+        if (TRIM) {
+            // masks stay masks: the ballot of a compare that has no other use is the compare's own SGPR pair (of a predicate that also steers
+            // lanes, like flatOk, hipcc makes a 0 / 1 VGPR and compares that) -- so "neither" is asked once more, as one range test
+            const unsigned long long odd = live & __builtin_amdgcn_ballot_w64((unsigned)node - ub.oddBase < ub.oddSpan);
+            if (__builtin_expect(odd != 0ull, 0))   // rare: range-checked descriptor loads, into the same registers, for the lanes at the very end of a buffer
+                fetch64_two_buffers_into(ub.rNodes, ub.rWoop, inner ? node : leaf_row(node) * kRowBytes, odd & __builtin_amdgcn_ballot_w64(inner),
+                                         odd & __builtin_amdgcn_ballot_w64(atTri), a, b, c, d);
+        } else {
+            const unsigned long long odd = __ballot((inner || atTri) && !flatOk);
+            if (odd != 0ull)   // rare: range-checked descriptor loads, into the same registers, for the lanes at the very end of a buffer
+                fetch64_two_buffers_into(ub.rNodes, ub.rWoop, inner ? node : leaf_row(node) * kRowBytes, __ballot(inner && !flatOk), __ballot(atTri && !flatOk), a, b, c, d);
+        }
     } else {
         const int ofs = inner ? node : leaf_row(node) * kRowBytes;   // four loads under the inner lanes' mask and four under the triangle lanes' mask into the SAME registers, one wait
         fetch64_two_buffers(ub.rNodes, ub.rWoop, ofs, __ballot(inner), __ballot(atTri), a, b, c, d);

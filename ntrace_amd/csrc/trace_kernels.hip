@@ -95,7 +95,10 @@ __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int&
 // reference IS the index of its first triangle; advancing one triangle subtracts 3).
 // SLICED (persistent kernels): the loop also ends after `slice` iterations (`slice` counts down: the caller posts the dequeue of the wave's
 // next chunk, or -- drain phase -- looks at the wave's lanes again: split_settle / split_donate, trace_split.h).
-template <bool FAST, bool FLAT, int OCT = 8, bool PROLOGUE = false, bool SLICED = false>
+// TRIM (the per-ray bodies): the loop's upkeep in its cheaper forms -- the fetch's end-of-buffer test (unified_fetch<.., TRIM>), the fetched
+// rows kept as the tuples the loads wrote (keep_row) and the straight-line pop (stack_pop_flat).  Same steps, same stack content.  The
+// persistent kernels keep the earlier forms: they have no scalar register to give (EXPERIMENTS.md).
+template <bool FAST, bool FLAT, int OCT = 8, bool PROLOGUE = false, bool SLICED = false, bool TRIM = false>
 __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs& r, int& node, LaneStack& st,
                                                  int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
                                                  unsigned int* status, bool poolEmpty, int fetchThreshold, int* slice = nullptr)
@@ -108,9 +111,10 @@ __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs&
         if (!poolEmpty && __popcll(live) < fetchThreshold) break;
         if (SLICED && --*slice < 0) break;
         float4 a, b, c, d;
-        unified_fetch<FLAT>(ub, node, a, b, c, d);
-        if (FLAT) { keep(a); keep(b); keep(c); keep(d); }
-        unified_advance<FAST, OCT>(a, b, c, d, r, node, st, spill, anyHit, hitAddr, hitU, hitV, status);
+        unified_fetch<FLAT, TRIM>(ub, node, live, a, b, c, d);
+        if (FLAT && TRIM) { keep_row(a); keep_row(b); keep_row(c); keep_row(d); }
+        else if (FLAT) { keep(a); keep(b); keep(c); keep(d); }
+        unified_advance<FAST, OCT, LDS_DEPTH, TRIM>(a, b, c, d, r, node, st, spill, anyHit, hitAddr, hitU, hitV, status);
     }
 }
 // A lane of a ray pool (the persistent kernels' refill, minipool_body) starts ray rayIdx at the root.  Returns whether the ray qualifies for the FAST path.
@@ -200,8 +204,8 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
             oct = (sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0);
     }
     if (UNIFIED) {
-        const UnifiedBufs ub = unified_bufs(p);
-#define NTR_UNIFIED_OCT(O) traverse_unified<true, FLATF, O, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0)
+        const UnifiedBufs ub = unified_bufs<true>(p);
+#define NTR_UNIFIED_OCT(O) traverse_unified<true, FLATF, O, true, false, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0)
         if (oct < 8) {
             switch (oct) {
                 case 0: NTR_UNIFIED_OCT(0); break;
@@ -215,8 +219,8 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
             }
         }
 #undef NTR_UNIFIED_OCT
-        else if (fastWave) traverse_unified<true, FLATF, 8, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
-        else traverse_unified<false, FLATF, 8, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
+        else if (fastWave) traverse_unified<true, FLATF, 8, true, false, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
+        else traverse_unified<false, FLATF, 8, true, false, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
     } else if (fastWave) traverse<true, STATS, false>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow);
     else traverse<false, STATS, false>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow);
 
@@ -512,7 +516,7 @@ __device__ __forceinline__ void minipool_body(const TraceParams& p, unsigned int
     int poolEnd = min(poolNext + 64, p.numRays);
     const bool anyHit = p.anyHit != 0;
     const bool bvhFast = (p.bvhFlags & NTR_BVH_FASTDIV) != 0;
-    const UnifiedBufs ub = unified_bufs(p);
+    const UnifiedBufs ub = unified_bufs<true>(p);
 
     unsigned long long tl0 = 0;
     if (p.cost) tl0 = __builtin_amdgcn_s_memrealtime();
@@ -547,8 +551,8 @@ __device__ __forceinline__ void minipool_body(const TraceParams& p, unsigned int
         const bool poolEmpty = poolNext >= poolEnd && chunk + 1u >= chunkEnd;
         // ---- unified-step traversal until every lane is done, or (rays left in the pool) until enough lanes are free to be worth a refill --
         const bool fastWave = bvhFast && __ballot(node != kSentinel && !nice) == 0ull;
-        if (fastWave) traverse_unified<true, FLATF, 8, false>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
-        else traverse_unified<false, FLATF, 8, false>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
+        if (fastWave) traverse_unified<true, FLATF, 8, false, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
+        else traverse_unified<false, FLATF, 8, false, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
         // ---- retire finished rays -------------------------------------------------------------------------------------------------
         if (rayIdx >= 0 && node == kSentinel) {
             store_result(p.results, p.triIndex, rayIdx, hitAddr, r.tmax, hitU, hitV);

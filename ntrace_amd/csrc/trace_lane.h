@@ -169,10 +169,31 @@ __device__ __forceinline__ int stack_pop(LaneStack& st, int (&spill)[SPILL_DEPTH
     return r;
 }
 
+// The per-ray bodies' pop (unified_advance<.., TRIM = true>): ONE LDS read in straight-line code, of the entry clamped into the LDS part,
+// and the scratch entry fetched over it in the rare lanes that are deep -- an exec-mask level and half a dozen scalar instructions per
+// site less than stack_pop's nested LDS / scratch select, in every step, whether or not a lane pops (EXPERIMENTS.md).  An empty stack needs no third source for `tos`: sp == 0 implies tos == kSentinel
+// (stack_reset sets it, a push at sp == 0 stores it into entry 0, and the pop that returns to sp == 0 reads it back; the drain phase of
+// the persistent kernels, which plants sentinels inside a stack, does not use this form), so the pop of the sentinel leaves `tos` as it is.
+template <int LD = LDS_DEPTH>
+__device__ __forceinline__ int stack_pop_flat(LaneStack& st, int (&spill)[SPILL_DEPTH])
+{
+    const int r = st.tos;
+    if (st.sp > 0) {
+        st.sp--;
+        int v = st.lds[min(st.sp, LD - 1) * 64];
+        if (__builtin_expect(st.sp >= LD, 0)) v = spill[st.sp - LD];
+        st.tos = v;
+    }
+    return r;
+}
+
 // Keeps a loaded value live at this point so that hipcc cannot sink its load into a later
 // conditional block (which would turn one memory round trip per node into two).
 __device__ __forceinline__ void keep(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 __device__ __forceinline__ void keep(unsigned int& v) { asm volatile("" : "+v"(v)); }
+// ... the four words of a row as the register tuple the load wrote (kept word by word, hipcc renames five of the sixteen fetched registers
+// with v_mov after the wait)
+__device__ __forceinline__ void keep_row(float4& v) { u32x4 t = as_u4(v); asm volatile("" : "+v"(t)); v = as_f4(t); }
 
 // rank of this lane among the lanes of m: the set bits of m below it (wave64 prefix popcount)
 __device__ __forceinline__ int lane_rank(unsigned long long m)
@@ -207,7 +228,7 @@ __device__ __forceinline__ void store_result(NtrRayResult* __restrict__ results,
 }
 
 // one inner node of trace<BVHLayout_Compact> (CudaBVH.cpp:721-775): both child boxes, nearer child first (ties -> child 0), the other pushed
-template <bool FAST, int OCT, int LD = LDS_DEPTH>
+template <bool FAST, int OCT, int LD = LDS_DEPTH, bool TRIM = false>
 __device__ __forceinline__ void inner_advance(const float4& a, const float4& b, const float4& c, const float4& d, const RayRegs& r, int& node,
                                               LaneStack& st, int (&spill)[SPILL_DEPTH], unsigned int* status)
 {
@@ -219,7 +240,7 @@ __device__ __forceinline__ void inner_advance(const float4& a, const float4& b, 
     const bool swp = i1 && (!i0 || mn0 > mn1);  // visit c1 first (ties -> c0, CudaBVH.cpp:761)
     const int nearC = swp ? c1 : c0, farC = swp ? c0 : c1;
     if (i0 && i1) stack_push<LD>(st, spill, farC, status);
-    node = (i0 || i1) ? nearC : stack_pop<LD>(st, spill);
+    node = (i0 || i1) ? nearC : TRIM ? stack_pop_flat<LD>(st, spill) : stack_pop<LD>(st, spill);
 }
 
 // One inner-node step of trace<BVHLayout_Compact> (CudaBVH.cpp:721-775).  Executed by the whole
@@ -291,8 +312,8 @@ __device__ __forceinline__ bool leaf_step(Rsrc woop, RayRegs& r, int leaf, bool 
 }
 
 // unified_advance: the lane's ray takes the step its 64 bytes allow -- one inner node (trace<BVHLayout_Compact>, CudaBVH.cpp:721-775) or one
-// triangle (intersectTriangles + updateHit, CudaBVH.cpp:1084-1126, 1183-1225).
-template <bool FAST, int OCT, int LD = LDS_DEPTH>
+// triangle (intersectTriangles + updateHit, CudaBVH.cpp:1084-1126, 1183-1225).  TRIM: the per-ray bodies' pop (stack_pop_flat).
+template <bool FAST, int OCT, int LD = LDS_DEPTH, bool TRIM = false>
 __device__ __forceinline__ void unified_advance(const float4& a, const float4& b, const float4& c, const float4& d, RayRegs& r, int& node,
                                                 LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
                                                 unsigned int* status)
@@ -300,7 +321,7 @@ __device__ __forceinline__ void unified_advance(const float4& a, const float4& b
     const bool inner = (unsigned)node < (unsigned)kSentinel;
     const bool atTri = node < 0;
     if (inner) {
-        inner_advance<FAST, OCT, LD>(a, b, c, d, r, node, st, spill, status);
+        inner_advance<FAST, OCT, LD, TRIM>(a, b, c, d, r, node, st, spill, status);
     } else if (atTri) {
         bool leafDone = __float_as_uint(a.x) == kLeafTerm;   // terminator: an empty leaf
         if (!leafDone) {
@@ -313,7 +334,7 @@ __device__ __forceinline__ void unified_advance(const float4& a, const float4& b
             else if (__float_as_uint(d.x) == kLeafTerm) leafDone = true;   // the terminator came with this triangle
             else node -= kTriRows;
         }
-        if (leafDone) node = stack_pop<LD>(st, spill);
+        if (leafDone) node = TRIM ? stack_pop_flat<LD>(st, spill) : stack_pop<LD>(st, spill);
     }
 }
 
