@@ -365,6 +365,12 @@ static void tunables_load_locked()
     t.lbvhSortItems = env_int("NTR_LBVH_SORT_ITEMS", 0);   // keys per thread of a one-sweep tile (8 / 16 / 24 / 32; 0 = by size)
     t.lbvhAggStaged = env_int("NTR_LBVH_AGG_STAGED", -1);  // bottom-up emit in two launches: -1 = from 2^20 triangles, 0 / 1 = never / always
     if (t.chunk < 1) t.chunk = 1;
+    // a refill threshold above the wave size asks a FULL wave for a refill: the loops leave their traversal for it before any lane has
+    // stepped and, with no lane free to take a ray, come straight back -- for ever (trace_kernels.hip: traverse / traverse_unified,
+    // `popcount(live) < fetchThreshold` while the pool holds rays).  64 already means "refill as soon as one lane is free".
+    if (t.fetchThreshold > 64) t.fetchThreshold = 64;
+    if (t.minipoolThreshold > 64) t.minipoolThreshold = 64;
+    if (t.blocksPerCU < 1) t.blocksPerCU = 1;   // (a persistent grid of no workgroups is no launch)
     g_tun = t;
     g_tunLoaded = true;
 }
