@@ -408,6 +408,19 @@ NTR_API int ntr_raygen_ao(NtrRay* d_outRays, int32_t* d_outIDToSlot, int32_t* d_
                           const float* d_triNormals, int32_t firstInputSlot, int32_t numInputRays,
                           int32_t numSamples, float maxDist, uint32_t kernelSeed, void* stream);
 
+/* ntr_raygen_ao over per-ray normals: the AO / diffuse generator of a batch whose hits have no table of triangle normals to index,
+ * the two-level hits of an instanced scene (ntr_instanced_hit_attributes below writes d_rayNormals).  EXTENSION without a reference
+ * counterpart; it is ntr_raygen_ao in every respect -- the same kernel body (csrc/raygen_kernels.hip), the same seeds, slots and
+ * outputs -- except where the normal comes from: input slot s uses d_rayNormals[4s .. 4s+2].  An input with id == -1 OR a normal whose
+ * fourth word is zero (+0 or -0: no normal could be formed) is a missed input: normal (1, 0, 0), degenerate rays with tmax = -1.  With
+ * d_rayNormals[4s..] = (d_triNormals[3 id_s ..], 1) the output equals ntr_raygen_ao's bit for bit.  With maxDist = the camera's far
+ * plane and closest hit this is the diffuse batch, as for ntr_raygen_ao.  Asynchronous on `stream` and capturable.
+ * NTR_ERR_INVALID: a negative count or slot, a null buffer (when there is a ray to make), d_rayNormals not 16-byte aligned. */
+NTR_API int ntr_raygen_ao_normals(NtrRay* d_outRays, int32_t* d_outIDToSlot, int32_t* d_outSlotToID, const NtrRay* d_inRays,
+                                  const NtrRayResult* d_inResults, const float* d_rayNormals /* 4 floats per input slot */,
+                                  int32_t firstInputSlot, int32_t numInputRays, int32_t numSamples, float maxDist,
+                                  uint32_t kernelSeed, void* stream);
+
 /* rayGenShadowKernel (src/rt/ray/RayGenKernels.cu:240-301; RayGen::shadow, RayGen.cpp:114-150): numSamples rays per input ray
  * [firstInputSlot, +numInputRays) from its hit point (backed off 1e-2 along the ray) towards quasi-random points of the cube of
  * half-edge lightRadius around lightPos; tmax = the distance to that point, rays of missed inputs are degenerate (tmax = -1).
@@ -853,6 +866,48 @@ NTR_API int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* en
                                 NtrBvhRefitBatchResult* result /* NULL: asynchronous */, void* stream);
 /* Bytes the batch refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_bvh_refit_batch_scratch_bytes(int64_t* bytes);
+
+/* Instanced frames: what a two-level hit needs before anything indexes by triangle, in one launch with a thread per ray
+ * (csrc/instanced_attr_kernels.hip).  ntr_trace_instanced leaves (id, t, u, v) and an instance id per ray; that id is the
+ * BLAS's own triangle id, relative to its mesh's firstTri.  This call turns it into the pool triangle g -- so that ntr_reconstruct,
+ * ntr_count_hits and ntr_secondary_block_costs work unchanged over d_outResults, with tables per pool triangle -- and forms the hit
+ * triangle's world-space geometric normal from the CURRENT vertices, which ntr_raygen_ao_normals (above) takes: primary -> two-level
+ * trace -> attributes -> AO or diffuse rays -> two-level trace -> ntr_reconstruct, all on one stream or in one graph, after
+ * ntr_bvh_refit_batch and ntr_tlas_refit when the frame moved.  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_frame.py, which the device equals in every word.  Binary32 throughout, every operation rounded once.
+ *   resolved    ray r is resolved iff id = d_results[r].id != -1, i = d_instanceIDs[r] in [0, numInstances), b = d_instances[i].blas in
+ *               [0, numBlas), id in [0, d_blasTris[b].numTris), g = d_blasTris[b].firstTri + id in [0, numTrisTotal), and the three
+ *               vertex indices of triangle g in [0, numVerts).  No read happens before its index is checked: whatever the records,
+ *               the instances, the table and the index array hold, nothing outside the buffers is read
+ *   d_outResults[r]  d_results[r] with id replaced by g when resolved and by -1 otherwise; t and the two pad words verbatim
+ *   normal      e1 = v[b] - v[a], e2 = v[c] - v[a]; n_o = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x)
+ *               (Scene.cpp:112's cross product); with W the instance's worldToObject, n_w.k = (W[0][k] n_o.x + W[1][k] n_o.y) +
+ *               W[2][k] n_o.z -- the transpose of W's linear part, so the inverse transpose of objectToWorld;
+ *               l2 = (n_w.x n_w.x + n_w.y n_w.y) + n_w.z n_w.z.  A resolved ray whose l2 is finite and > 0 gets inv = 1.0f / sqrtf(l2)
+ *               and d_normals[4r ..] = (n_w.x inv, n_w.y inv, n_w.z inv, 1.0f); every other ray gets (0, 0, 0, 0)
+ *   orientation the normal follows the OBJECT's winding: under a mirroring instance (negative determinant) it is the world triangle's
+ *               geometric normal negated.  The AO generator turns the normal against the ray anyway
+ *   colours     the caller's per-triangle tables are per POOL triangle and in object space: two instances of one BLAS share a
+ *               triangle's colours, however they are turned (colour tables lit per instance are out of scope)
+ *   d_blasTris  BLAS k is triangles [firstTri, +numTris) of d_triVtxIndex, the meshes ntr_ploc_build_batch was given; numTris 0 (a
+ *               tree whose mesh is not known) resolves none of its hits
+ * One 16-byte store per output per ray; d_outResults may equal d_results (in place); either output may be NULL, not both.  The call is
+ * asynchronous on `stream` and capturable; it allocates nothing and reads nothing back.  numRays == 0 returns NTR_OK.
+ * NTR_ERR_INVALID (before any device work): numRays < 0, a null geom or a null pointer inside it, a count < 1, null d_results or
+ * d_instanceIDs, both outputs null, d_results, d_outResults, d_normals or d_instances not 16-byte aligned (d_blasTris: 8).  Without a
+ * device, after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrBlasTris { int32_t firstTri, numTris; } NtrBlasTris;        /* device array, one per BLAS */
+typedef struct NtrInstancedGeometry {                                         /* host struct of device pointers */
+    int32_t numInstances, numBlas, numTrisTotal, numVerts;
+    const NtrInstance* d_instances;    /* as ntr_tlas_build / ntr_tlas_refit take them */
+    const NtrBlasTris* d_blasTris;     /* BLAS k is triangles [firstTri, +numTris) of d_triVtxIndex (ntr_ploc_build_batch's meshes) */
+    const int32_t*     d_triVtxIndex;  /* 3 per triangle: the arrays ntr_ploc_build_batch / ntr_bvh_refit_batch were given */
+    const float*       d_vtxPos;       /* 3 per vertex, the CURRENT positions */
+} NtrInstancedGeometry;
+NTR_API int ntr_instanced_hit_attributes(int32_t numRays, const NtrRayResult* d_results, const int32_t* d_instanceIDs,
+                                         const NtrInstancedGeometry* geom,
+                                         NtrRayResult* d_outResults /* may be NULL; may equal d_results */,
+                                         float* d_normals /* may be NULL; 4 floats per ray */, void* stream);
 
 /* 4-wide BVH: an out-of-place pass that turns any BVHLayout_Compact tree into 4-wide nodes, and the trace that walks them
  * (csrc/bvh_widen_kernels.hip, csrc/trace_wide_kernels.hip, csrc/wide_bvh.h).  EXTENSION without a reference counterpart: the rule is the

@@ -166,6 +166,25 @@ class BvhRefitBatchResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class BlasTris(C.Structure):
+    """NtrBlasTris: BLAS k of a pool is triangles [firstTri, +numTris) of the shared index array (a device array, one per BLAS)."""
+    _fields_ = [("firstTri", C.c_int32), ("numTris", C.c_int32)]
+
+
+BLAS_TRIS_DTYPE = np.dtype([("firstTri", "<i4"), ("numTris", "<i4")])
+
+
+class InstancedGeometry(C.Structure):
+    """NtrInstancedGeometry: a host struct of device pointers -- the instances, the BLASes' triangle ranges, the index array and the
+    CURRENT vertex positions."""
+    _fields_ = [("numInstances", C.c_int32), ("numBlas", C.c_int32), ("numTrisTotal", C.c_int32), ("numVerts", C.c_int32),
+                ("d_instances", C.c_void_p), ("d_blasTris", C.c_void_p), ("d_triVtxIndex", C.c_void_p), ("d_vtxPos", C.c_void_p)]
+
+    def __init__(self, num_instances=0, num_blas=0, num_tris_total=0, num_verts=0, d_instances=0, d_blas_tris=0, d_tri=0, d_pos=0):
+        super().__init__(int(num_instances), int(num_blas), int(num_tris_total), int(num_verts), int(d_instances) or None,
+                         int(d_blas_tris) or None, int(d_tri) or None, int(d_pos) or None)
+
+
 class TlasResult(C.Structure):
     _fields_ = [("rootLink", C.c_int32), ("numNodes", C.c_int32), ("numRounds", C.c_int32), ("height", C.c_int32),
                 ("tailClusters", C.c_int32), ("pad", C.c_int32 * 3), ("nodesBytes", C.c_int64), ("recordsBytes", C.c_int64),
@@ -305,6 +324,7 @@ SYMBOLS = [
     ("ntr_raygen_primary", C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i32, _i32,
                                      C.c_float, _u32, _vp]),
     ("ntr_raygen_ao", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _u32, _vp]),
+    ("ntr_raygen_ao_normals", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _u32, _vp]),
     ("ntr_raygen_shadow", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(C.c_float * 3), C.c_float, _u32, _vp]),
     ("ntr_count_hits", C.c_int, [_vp, _i32, C.POINTER(_i32), _vp]),
     ("ntr_lbvh_capacity", C.c_int, [_i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
@@ -353,6 +373,7 @@ SYMBOLS = [
     ("ntr_tlas_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
     ("ntr_tlas_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_trace_instanced", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, C.POINTER(C.c_float), _vp]),
+    ("ntr_instanced_hit_attributes", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), _vp, _vp, _vp]),
     ("ntr_bvh_widen_capacity", C.c_int, [_i64, C.POINTER(_i64)]),
     ("ntr_bvh_widen", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhWideResult), _vp]),
     ("ntr_bvh_widen_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
@@ -718,6 +739,15 @@ def raygen_ao(d_out_rays, d_out_id_to_slot, d_out_slot_to_id, d_in_rays, d_in_re
                                int(num_samples), float(max_dist), int(kernel_seed), _vp(stream)))
 
 
+def raygen_ao_normals(d_out_rays, d_out_id_to_slot, d_out_slot_to_id, d_in_rays, d_in_results, d_ray_normals, first_input_slot,
+                      num_input_rays, num_samples, max_dist, kernel_seed=0, stream=0):
+    """ntr_raygen_ao_normals: raygen_ao over per-ray normals (4 floats per input slot, as instanced_hit_attributes writes them); a
+    fourth word of zero is a missed input.  Asynchronous on `stream` and capturable."""
+    _check(lib().ntr_raygen_ao_normals(_vp(d_out_rays), _vp(d_out_id_to_slot), _vp(d_out_slot_to_id), _vp(d_in_rays),
+                                       _vp(d_in_results), _vp(d_ray_normals), int(first_input_slot), int(num_input_rays),
+                                       int(num_samples), float(max_dist), int(kernel_seed), _vp(stream)))
+
+
 def raygen_shadow(d_out_rays, d_out_id_to_slot, d_out_slot_to_id, d_in_rays, d_in_results, first_input_slot, num_input_rays, num_samples,
                   light_pos, light_radius, kernel_seed=0, stream=0):
     lp = (C.c_float * 3)(*[float(x) for x in light_pos])
@@ -1010,6 +1040,15 @@ def trace_instanced(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas
                                      int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
                                      C.byref(sec) if timed else None, _vp(stream)))
     return float(sec.value) if timed else None
+
+
+def instanced_hit_attributes(num_rays, d_results, d_instance_ids, geom, d_out_results=0, d_normals=0, stream=0):
+    """ntr_instanced_hit_attributes: per ray of a two-level trace, the record with the pool triangle g = firstTri + id in place of the
+    BLAS's own id (d_out_results; may be d_results) and the world-space geometric normal of the hit triangle from the current vertices
+    (d_normals, 4 floats per ray); the rule is tests/np_instanced_frame.py.  geom: an InstancedGeometry (None passes NULL).
+    Asynchronous on `stream` and capturable."""
+    _check(lib().ntr_instanced_hit_attributes(int(num_rays), _vp(d_results), _vp(d_instance_ids), C.byref(geom) if geom is not None else None,
+                                              _vp(d_out_results), _vp(d_normals), _vp(stream)))
 
 
 def bvh_widen_capacity(nodes_bytes):

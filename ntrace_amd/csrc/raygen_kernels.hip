@@ -3,6 +3,7 @@
 //   rayGenAOKernel       src/rt/ray/RayGenKernels.cu:129-236  (AO and, with maxDist = camera
 //                        far + closest hit, the diffuse rays of Renderer.cpp:533-537)
 //   PixelTable           src/rt/ray/PixelTable.cpp:57-143      (host, uploaded once)
+//   raygen_ao_normals    the AO kernel's body over per-ray normals (an extension: ntr_raygen_ao_normals)
 // The reference compiles these with -use_fast_math, so its own bits are not reproducible
 // across GPUs; parity for the tracer is defined on identical ray buffers.  These kernels
 // use the precise libm forms and are tested against a numpy restatement to 1e-5.
@@ -64,11 +65,13 @@ __global__ __launch_bounds__(256) void raygen_primary_kernel(NtrRay* __restrict_
     out[1] = make_float4(dx * inv, dy * inv, dz * inv, maxDist);
 }
 
-__global__ __launch_bounds__(256) void raygen_ao_kernel(NtrRay* __restrict__ outRays, int32_t* __restrict__ outIDToSlot,
-                                                        int32_t* __restrict__ outSlotToID, const NtrRay* __restrict__ inRays,
-                                                        const NtrRayResult* __restrict__ inResults,
-                                                        const float* __restrict__ normals, int firstInputSlot,
-                                                        int numInputRays, int numSamples, float maxDist, uint32_t randomSeed)
+// The AO generator's body, stated once: raygen_ao_kernel and raygen_ao_normals_kernel differ only in fetch(inSlot, tri, nx, ny, nz),
+// which fills the normal of a hit input and returns false for an input to be treated as missed (normal (1, 0, 0), tmax = -1).
+template <class FetchNormal>
+__device__ __forceinline__ void raygen_ao_body(NtrRay* __restrict__ outRays, int32_t* __restrict__ outIDToSlot, int32_t* __restrict__ outSlotToID,
+                                               const NtrRay* __restrict__ inRays, const NtrRayResult* __restrict__ inResults,
+                                               int firstInputSlot, int numInputRays, int numSamples, float maxDist, uint32_t randomSeed,
+                                               FetchNormal fetch)
 {
     const int taskIdx = blockIdx.x * blockDim.x + threadIdx.x;
     if (taskIdx >= numInputRays) return;
@@ -82,9 +85,8 @@ __global__ __launch_bounds__(256) void raygen_ao_kernel(NtrRay* __restrict__ out
     const float back = fmaxf(__int_as_float(res.y) - 1.0e-4f, 0.0f);
     const float px = ro.x + rd.x * back, py = ro.y + rd.y * back, pz = ro.z + rd.z * back;
 
-    const int tri = res.x;
     float nx = 1.0f, ny = 0.0f, nz = 0.0f;
-    if (tri != -1) { nx = normals[3 * tri + 0]; ny = normals[3 * tri + 1]; nz = normals[3 * tri + 2]; }
+    const bool hit = fetch(inSlot, res.x, nx, ny, nz);
     if (nx * rd.x + ny * rd.y + nz * rd.z > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
 
     // perpendicular frame (:164-175)
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(256) void raygen_ao_kernel(NtrRay* __restrict__ out
     const float t0x = ux * ca + bx * sa, t0y = uy * ca + by * sa, t0z = uz * ca + bz * sa;
     const float t1x = ux * -sa + bx * ca, t1y = uy * -sa + by * ca, t1z = uz * -sa + bz * ca;
 
-    const float tmax = (tri == -1) ? -1.0f : maxDist;
+    const float tmax = hit ? maxDist : -1.0f;
     for (int i = 0; i < numSamples; i++) {
         // Halton(2,3) (:196-218)
         float x = 0.0f, xadd = 1.0f;
@@ -136,6 +138,36 @@ __global__ __launch_bounds__(256) void raygen_ao_kernel(NtrRay* __restrict__ out
         outIDToSlot[outSlot + i] = outSlot + i;
         outSlotToID[outSlot + i] = outSlot + i;
     }
+}
+
+// rayGenAOKernel: the normal is the hit triangle's entry of a table of 3 floats per scene triangle
+__global__ __launch_bounds__(256) void raygen_ao_kernel(NtrRay* __restrict__ outRays, int32_t* __restrict__ outIDToSlot,
+                                                        int32_t* __restrict__ outSlotToID, const NtrRay* __restrict__ inRays,
+                                                        const NtrRayResult* __restrict__ inResults,
+                                                        const float* __restrict__ normals, int firstInputSlot,
+                                                        int numInputRays, int numSamples, float maxDist, uint32_t randomSeed)
+{
+    raygen_ao_body(outRays, outIDToSlot, outSlotToID, inRays, inResults, firstInputSlot, numInputRays, numSamples, maxDist, randomSeed,
+                   [&](int, int tri, float& nx, float& ny, float& nz) {
+                       if (tri != -1) { nx = normals[3 * tri + 0]; ny = normals[3 * tri + 1]; nz = normals[3 * tri + 2]; }
+                       return tri != -1;
+                   });
+}
+
+// ntr_raygen_ao_normals: the normal is the input slot's own, 4 floats, one 16-byte load; a fourth word of zero says there is none
+__global__ __launch_bounds__(256) void raygen_ao_normals_kernel(NtrRay* __restrict__ outRays, int32_t* __restrict__ outIDToSlot,
+                                                                int32_t* __restrict__ outSlotToID, const NtrRay* __restrict__ inRays,
+                                                                const NtrRayResult* __restrict__ inResults,
+                                                                const float4* __restrict__ rayNormals, int firstInputSlot,
+                                                                int numInputRays, int numSamples, float maxDist, uint32_t randomSeed)
+{
+    raygen_ao_body(outRays, outIDToSlot, outSlotToID, inRays, inResults, firstInputSlot, numInputRays, numSamples, maxDist, randomSeed,
+                   [&](int inSlot, int tri, float& nx, float& ny, float& nz) {
+                       const float4 n = rayNormals[inSlot];
+                       const bool hit = tri != -1 && n.w != 0.0f;
+                       if (hit) { nx = n.x; ny = n.y; nz = n.z; }
+                       return hit;
+                   });
 }
 
 // countHitsKernel (src/rt/cuda/RendererKernels.cu:174-226): number of rays with id >= 0 (:193).
@@ -275,6 +307,22 @@ int ntr_raygen_ao(NtrRay* d_outRays, int32_t* d_outIDToSlot, int32_t* d_outSlotT
     hipLaunchKernelGGL(raygen_ao_kernel, dim3((numInputRays + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_outRays,
                        d_outIDToSlot, d_outSlotToID, d_inRays, d_inResults, d_triNormals, firstInputSlot, numInputRays,
                        numSamples, maxDist, kernelSeed);
+    NTR_HIP(hipGetLastError());
+    return NTR_OK;
+}
+
+int ntr_raygen_ao_normals(NtrRay* d_outRays, int32_t* d_outIDToSlot, int32_t* d_outSlotToID, const NtrRay* d_inRays,
+                          const NtrRayResult* d_inResults, const float* d_rayNormals, int32_t firstInputSlot,
+                          int32_t numInputRays, int32_t numSamples, float maxDist, uint32_t kernelSeed, void* stream)
+{
+    if (numInputRays < 0 || numSamples < 0 || firstInputSlot < 0) return set_error(NTR_ERR_INVALID, "ntr_raygen_ao_normals: negative count");
+    if (numInputRays == 0 || numSamples == 0) return NTR_OK;
+    if (!d_outRays || !d_outIDToSlot || !d_outSlotToID || !d_inRays || !d_inResults || !d_rayNormals)
+        return set_error(NTR_ERR_INVALID, "ntr_raygen_ao_normals: null buffer");
+    if ((uintptr_t)d_rayNormals & 15u) return set_error(NTR_ERR_INVALID, "ntr_raygen_ao_normals: d_rayNormals must be 16-byte aligned");
+    hipLaunchKernelGGL(raygen_ao_normals_kernel, dim3((numInputRays + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_outRays,
+                       d_outIDToSlot, d_outSlotToID, d_inRays, d_inResults, reinterpret_cast<const float4*>(d_rayNormals), firstInputSlot,
+                       numInputRays, numSamples, maxDist, kernelSeed);
     NTR_HIP(hipGetLastError());
     return NTR_OK;
 }

@@ -6,7 +6,7 @@
 
 namespace FW {
 
-CudaInstancedBVH::CudaInstancedBVH(void) : m_numInstances(0), m_built(false), m_topology(false)
+CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false)
 {
     std::memset(&m_result, 0, sizeof(m_result));
     std::memset(&m_blasResult, 0, sizeof(m_blasResult));
@@ -36,7 +36,7 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_ranges.push_back(r);
     const Mesh none = {0, 0};
     m_meshes.push_back(none);
-    m_built = m_topology = false;
+    m_built = m_topology = m_blasTrisCurrent = false;
     return (S32)m_ranges.size() - 1;
 }
 
@@ -50,7 +50,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
     m_ranges.clear();
     m_meshes.clear();
-    m_built = m_topology = false;
+    m_built = m_topology = m_blasTrisCurrent = false;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
     m_poolTriIndex.resizeDiscard(capI);
@@ -65,6 +65,24 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
         m_meshes[k].firstTri = meshes[k].firstTri;
         m_meshes[k].numTris = meshes[k].numTris;
     }
+}
+
+Buffer& CudaInstancedBVH::getBLASTrisBuffer(void)
+{
+    if (!m_blasTrisCurrent) {
+        static_assert(sizeof(Mesh) == sizeof(NtrBlasTris), "Mesh is NtrBlasTris");
+        m_blasTris.resizeDiscard((S64)m_meshes.size() * sizeof(NtrBlasTris));
+        if (!m_meshes.empty()) m_blasTris.set(m_meshes.data(), (S64)m_meshes.size() * sizeof(NtrBlasTris));
+        m_blasTrisCurrent = true;
+    }
+    return m_blasTris;
+}
+
+S32 CudaInstancedBVH::getFirstMeshlessBLAS(void) const
+{
+    for (size_t k = 0; k < m_meshes.size(); k++)
+        if (m_meshes[k].numTris < 1) return (S32)k;
+    return -1;
 }
 
 void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas, S32 num, F32 epsilon)

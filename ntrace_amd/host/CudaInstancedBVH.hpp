@@ -18,6 +18,12 @@
 //                 deforming scene is refitBLASes -> setInstances -> refit -> traceBatch, with build() every so many frames: a refit
 //                 keeps the tree the old positions suggested, and its boxes overlap more the further the instances travel
 //   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss)
+//   getBLASTrisBuffer  NtrBlasTris per BLAS, on the device: the meshes buildBLASes remembers, which ntr_instanced_hit_attributes needs
+//                 to turn a two-level hit's id into a pool triangle.  A BLAS that came through addBLAS has numTris 0:
+//                 its hits resolve to -1
+// Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
+// primary, AO and diffuse frames.  The frame loop of a moving, deforming scene becomes
+//   refitBLASes -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch / traceBatch / updateResult per batch
 #pragma once
 #include <vector>
 
@@ -45,6 +51,10 @@ public:
     void refit(void);
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs);                       // GPU seconds
 
+    Buffer& getBLASTrisBuffer(void);                                             // NtrBlasTris per BLAS (numTris 0: an addBLAS tree)
+    bool isBuilt(void) const { return m_built; }                                 // the TLAS is current: traceBatch may run
+    S32  getFirstMeshlessBLAS(void) const;                                       // the first addBLAS tree of the pool, -1 if none
+
     S32  getNumBLAS(void) const { return (S32)m_ranges.size(); }
     S32  getNumInstances(void) const { return m_numInstances; }
     const NtrBlasRange&  getBLASRange(S32 i) const { return m_ranges[i]; }
@@ -68,6 +78,8 @@ private:
     std::vector<Mesh>         m_meshes;                                          // per BLAS, as m_ranges
     Buffer        m_poolNodes, m_poolTriWoop, m_poolTriIndex;
     Buffer        m_instances, m_tlasNodes, m_records;
+    Buffer        m_blasTris;                                                    // filled from m_meshes on demand
+    bool          m_blasTrisCurrent;
     S32           m_numInstances;
     bool          m_built;                                                       // the TLAS is current: traceBatch may run
     bool          m_topology;                                                    // a TLAS of m_numInstances leaves over these BLASes exists: refit may run

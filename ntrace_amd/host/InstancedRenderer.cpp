@@ -1,0 +1,141 @@
+// InstancedRenderer.cpp -- Renderer's batching over a CudaInstancedBVH: every traced batch goes through ntr_instanced_hit_attributes
+// before ntr_raygen_ao_normals, ntr_count_hits or ntr_reconstruct sees it (see the header).
+#include "InstancedRenderer.hpp"
+
+namespace FW {
+
+InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
+    : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
+      m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
+{
+}
+
+void InstancedRenderer::setGeometry(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos)
+{
+    if (triVtxIndex.getSize() < (S64)(3 * sizeof(S32)) || numVerts < 1 || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32)))
+        fail("InstancedRenderer::setGeometry: bad mesh buffers");
+    m_triVtxIndex = &triVtxIndex;
+    m_vtxPos = &vtxPos;
+    m_numVerts = numVerts;
+}
+
+void InstancedRenderer::setParams(RayType rayType, F32 aoRadius, S32 numSamples)
+{
+    if (rayType < RayType_Primary || rayType >= RayType_Max || numSamples < 1) fail("InstancedRenderer::setParams: bad ray type or sample count");
+    m_rayType = rayType;
+    m_aoRadius = aoRadius;
+    m_numSamples = numSamples;
+}
+
+// the batch's records with pool triangle ids and, for a batch that secondary rays start from, the world-space normals
+void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals)
+{
+    const S32 n = rays.getSize();
+    resolved.resizeDiscard((S64)n * sizeof(NtrRayResult));
+    if (normals) normals->resizeDiscard((S64)n * (S64)(4 * sizeof(F32)));
+    if (!n) return;
+    NtrInstancedGeometry g;
+    g.numInstances = m_bvh.getNumInstances();
+    g.numBlas = m_bvh.getNumBLAS();
+    g.numTrisTotal = (int32_t)(m_triVtxIndex->getSize() / (S64)(3 * sizeof(S32)));
+    g.numVerts = m_numVerts;
+    g.d_instances = (const NtrInstance*)m_bvh.getInstanceBuffer().getCudaPtr();
+    g.d_blasTris = (const NtrBlasTris*)m_bvh.getBLASTrisBuffer().getCudaPtr();
+    g.d_triVtxIndex = (const int32_t*)m_triVtxIndex->getCudaPtr();
+    g.d_vtxPos = (const float*)m_vtxPos->getCudaPtr();
+    const int rc = ntr_instanced_hit_attributes(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(), &g,
+                                                (NtrRayResult*)resolved.getMutableCudaPtr(), normals ? (float*)normals->getMutableCudaPtr() : NULL,
+                                                NULL);
+    if (rc != NTR_OK) fail("InstancedRenderer: %s", ntr_last_error());
+}
+
+void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
+{
+    if (!m_triVtxIndex)
+        fail("InstancedRenderer: no geometry: call setGeometry() with the index and vertex buffers CudaInstancedBVH::buildBLASes was given");
+    const S32 meshless = m_bvh.getFirstMeshlessBLAS();
+    if (meshless >= 0)
+        fail("InstancedRenderer: BLAS %d came through addBLAS and has no mesh here, so its hits cannot be resolved: build the pool with "
+             "CudaInstancedBVH::buildBLASes", meshless);
+    if (!m_bvh.isBuilt())
+        fail("InstancedRenderer: the TLAS is not current: call build() or refit() on the CudaInstancedBVH (after buildBLASes / refitBLASes and "
+             "setInstances) before beginFrame");
+    if (w < 1 || h < 1) fail("InstancedRenderer::beginFrame: bad frame size");
+    m_raygen.primary(m_primaryRays, camera.position, camera.nscreenToWorld, w, h, camera.cameraFar, 0);
+    if (m_rayType != RayType_Primary) {   // Renderer.cpp:482-488
+        m_bvh.traceBatch(m_primaryRays, m_primaryIDs);
+        resolve(m_primaryRays, m_primaryIDs, m_primaryResolved, &m_primaryNormals);
+    }
+    m_cameraFar = camera.cameraFar;
+    m_newBatch = true;
+    m_batchRays = NULL;
+    m_batchResolved = NULL;
+    m_batchStart = 0;
+}
+
+bool InstancedRenderer::nextBatch(void)
+{
+    if (m_batchRays) m_batchStart += m_batchRays->getSize();
+    m_batchRays = NULL;
+    m_batchResolved = NULL;
+    switch (m_rayType) {
+    case RayType_Primary:
+        if (!m_newBatch) return false;
+        m_newBatch = false;
+        m_batchRays = &m_primaryRays;
+        m_batchResolved = &m_primaryResolved;
+        break;
+    case RayType_AO:
+        if (!m_raygen.aoNormals(m_secondaryRays, m_primaryRays, m_primaryNormals, m_numSamples, m_aoRadius, m_newBatch, 0)) return false;
+        m_batchRays = &m_secondaryRays;
+        m_batchResolved = &m_secondaryResolved;
+        break;
+    case RayType_Diffuse:
+        if (!m_raygen.aoNormals(m_secondaryRays, m_primaryRays, m_primaryNormals, m_numSamples, m_cameraFar, m_newBatch, 0)) return false;
+        m_secondaryRays.setNeedClosestHit(true);
+        m_batchRays = &m_secondaryRays;
+        m_batchResolved = &m_secondaryResolved;
+        break;
+    default:
+        return false;
+    }
+    return true;
+}
+
+F32 InstancedRenderer::traceBatch(void)
+{
+    if (!m_batchRays) fail("InstancedRenderer::traceBatch: no batch");
+    const bool primary = m_batchRays == &m_primaryRays;
+    Buffer& ids = primary ? m_primaryIDs : m_secondaryIDs;
+    const F32 sec = m_bvh.traceBatch(*m_batchRays, ids);
+    resolve(*m_batchRays, ids, *m_batchResolved, primary ? &m_primaryNormals : NULL);
+    return sec;
+}
+
+void InstancedRenderer::updateResult(Buffer& pixels, Buffer& triMaterialColor, Buffer& triShadedColor)
+{
+    if (!m_batchRays) fail("InstancedRenderer::updateResult: no batch");
+    if (m_batchResolved->getSize() != (S64)m_batchRays->getSize() * (S64)sizeof(NtrRayResult) ||
+        m_primaryResolved.getSize() != (S64)m_primaryRays.getSize() * (S64)sizeof(NtrRayResult))
+        fail("InstancedRenderer::updateResult: the batch has not been traced: call traceBatch() first");
+    const int perPrimary = (m_rayType == RayType_Primary) ? 1 : m_numSamples;
+    const int rc = ntr_reconstruct((int)m_rayType, perPrimary, m_batchStart / perPrimary, m_batchRays->getSize() / perPrimary,
+                                   (const int32_t*)m_primaryRays.getSlotToIDBuffer().getCudaPtr(),
+                                   (const NtrRayResult*)m_primaryResolved.getCudaPtr(),
+                                   (const int32_t*)m_batchRays->getIDToSlotBuffer().getCudaPtr(),
+                                   (const NtrRayResult*)m_batchResolved->getCudaPtr(), (const uint32_t*)triMaterialColor.getCudaPtr(),
+                                   (const uint32_t*)triShadedColor.getCudaPtr(), (uint32_t*)pixels.getMutableCudaPtr(), NULL);
+    if (rc != NTR_OK) fail("InstancedRenderer::updateResult: %s", ntr_last_error());
+    if (ntr_stream_synchronize(NULL) != NTR_OK) fail("InstancedRenderer::updateResult: %s", ntr_last_error());
+}
+
+int InstancedRenderer::getTotalNumRays(void)
+{
+    if (m_rayType == RayType_Primary) return m_primaryRays.getSize();
+    int32_t hits = 0;
+    if (ntr_count_hits((const NtrRayResult*)m_primaryResolved.getCudaPtr(), m_primaryRays.getSize(), &hits, NULL) != NTR_OK)
+        fail("InstancedRenderer: %s", ntr_last_error());
+    return hits * m_numSamples;
+}
+
+}  // namespace FW

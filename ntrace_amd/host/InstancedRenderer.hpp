@@ -1,0 +1,67 @@
+// InstancedRenderer.hpp -- frames of an instanced scene: Renderer's batching (src/rt/cuda/Renderer.cpp:405-497, 501-579, 583-659,
+// 676-710) for the primary, AO and diffuse ray types over a CudaInstancedBVH and the meshes its BLASes were built from.  An extension
+// without a reference class.
+//   setGeometry   the index and vertex buffers CudaInstancedBVH::buildBLASes / refitBLASes were given; the vertex buffer holds the
+//                 CURRENT positions whenever a batch is traced (the buffers are borrowed, not copied)
+//   setParams     the ray type, the AO radius and the samples per primary hit
+//   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
+//                 diffuse frames the primary rays are traced and resolved at once
+//   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
+//                 ntr_instanced_hit_attributes before anything indexes by triangle: the records updateResult and getTotalNumRays
+//                 read name POOL triangles (the caller's colour tables are per pool triangle, in object space), and the AO and diffuse
+//                 rays start from the world-space normals of the current vertices (ntr_raygen_ao_normals)
+// beginFrame fails, and says what to do, when there is no geometry, when the CudaInstancedBVH's TLAS is not current (build() or refit()
+// after setInstances / refitBLASes), and when the pool holds a tree that came through addBLAS (its mesh is not known here).
+// No kd-tree, no shard, no cache and no dispatch hints; Renderer itself is untouched.
+#pragma once
+#include "CudaInstancedBVH.hpp"
+#include "RayGen.hpp"
+
+namespace FW {
+
+class InstancedRenderer {
+public:
+    enum RayType { RayType_Primary = 0, RayType_AO, RayType_Diffuse, RayType_Max };   // Renderer::RayType's values: ntr_reconstruct's rayType
+
+    explicit InstancedRenderer(CudaInstancedBVH& bvh);
+
+    void setGeometry(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos);
+    void setParams(RayType rayType, F32 aoRadius, S32 numSamples);
+
+    void beginFrame(const CameraView& camera, S32 w, S32 h);
+    bool nextBatch(void);
+    F32  traceBatch(void);       // the two-level trace's GPU seconds
+    int  getTotalNumRays(void);  // for the selected ray type, excluding degenerates
+    void updateResult(Buffer& pixels, Buffer& triMaterialColor, Buffer& triShadedColor);   // colours per pool triangle
+
+    RayGen&    getRayGen(void) { return m_raygen; }
+    RayBuffer& getPrimaryRays(void) { return m_primaryRays; }
+    RayBuffer* getBatchRays(void) { return m_batchRays; }
+    Buffer&    getPrimaryResolvedBuffer(void) { return m_primaryResolved; }   // NtrRayResult per primary slot, ids of pool triangles
+    Buffer&    getPrimaryNormalBuffer(void) { return m_primaryNormals; }      // 4 floats per primary slot
+    Buffer&    getBatchResolvedBuffer(void) { return *m_batchResolved; }      // NtrRayResult per slot of the current batch
+
+private:
+    void resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals);
+    InstancedRenderer(const InstancedRenderer&);
+    InstancedRenderer& operator=(const InstancedRenderer&);
+
+    CudaInstancedBVH& m_bvh;
+    Buffer*    m_triVtxIndex;
+    Buffer*    m_vtxPos;
+    S32        m_numVerts;
+    RayType    m_rayType;
+    F32        m_aoRadius;
+    S32        m_numSamples;
+    RayGen     m_raygen;
+    F32        m_cameraFar;
+    RayBuffer  m_primaryRays, m_secondaryRays;
+    Buffer     m_primaryIDs, m_secondaryIDs;             // S32 per slot: the instance of the hit
+    Buffer     m_primaryResolved, m_primaryNormals, m_secondaryResolved;
+    bool       m_newBatch;
+    RayBuffer* m_batchRays;
+    Buffer*    m_batchResolved;
+    S32        m_batchStart;
+};
+
+}  // namespace FW

@@ -50,6 +50,21 @@ bool RayGen::ao(RayBuffer& orays, RayBuffer& irays, Scene& scene, int numSamples
     return true;
 }
 
+bool RayGen::aoNormals(RayBuffer& orays, RayBuffer& irays, Buffer& normals, int numSamples, float maxDist, bool& newBatch, U32 randomSeed)
+{
+    if (normals.getSize() < (S64)irays.getSize() * (S64)(4 * sizeof(F32))) fail("RayGen::aoNormals: fewer than 4 floats per input ray");
+    S32 lo, hi;
+    if (!batching(irays.getSize(), numSamples, m_aoStartIdx, newBatch, lo, hi)) return false;
+    orays.resize((hi - lo) * numSamples);
+    orays.setNeedClosestHit(false);
+    check(ntr_raygen_ao_normals((NtrRay*)orays.getRayBuffer().getMutableCudaPtr(), (int32_t*)orays.getIDToSlotBuffer().getMutableCudaPtr(),
+                                (int32_t*)orays.getSlotToIDBuffer().getMutableCudaPtr(), (const NtrRay*)irays.getRayBuffer().getCudaPtr(),
+                                (const NtrRayResult*)irays.getResultBuffer().getCudaPtr(), (const float*)normals.getCudaPtr(), lo, hi - lo,
+                                numSamples, maxDist, Random(randomSeed).getU32() /* as ao() */, NULL), "ntr_raygen_ao_normals");
+    check(ntr_stream_synchronize(NULL), "sync");
+    return true;
+}
+
 bool RayGen::shadow(RayBuffer& orays, RayBuffer& irays, int numSamples, const Vec3f& lightPos, float lightRadius, bool& newBatch, U32 randomSeed)
 {
     S32 lo, hi;

@@ -44,6 +44,9 @@ public:
     void primary(RayBuffer& orays, const Vec3f& origin, const Mat4f& nscreenToWorld, S32 w, S32 h, float maxDist, U32 randomSeed = 0);
     // RayGen::ao (RayGen.cpp:198-232): false when all input rays have been consumed
     bool ao(RayBuffer& orays, RayBuffer& irays, Scene& scene, int numSamples, float maxDist, bool& newBatch, U32 randomSeed = 0);
+    // ao over per-ray normals (ntr_raygen_ao_normals; no counterpart in the reference): normals holds 4 floats per slot of irays, as
+    // ntr_instanced_hit_attributes writes them; batching() exactly as ao()
+    bool aoNormals(RayBuffer& orays, RayBuffer& irays, Buffer& normals, int numSamples, float maxDist, bool& newBatch, U32 randomSeed = 0);
     // RayGen::shadow (src/rt/ray/RayGen.cpp:114-150): numSamples any-hit rays per input ray towards the area light
     bool shadow(RayBuffer& orays, RayBuffer& irays, int numSamples, const Vec3f& lightPos, float lightRadius, bool& newBatch, U32 randomSeed = 0);
 

@@ -8,6 +8,10 @@ that hung).  Every figure is the median of --reps runs after --warmup runs, time
                through ONE identity instance of atrium(), beside ntr_trace_bvh (fermi_speculative_while_while, validated flags) on the
                same tree and rays: the price of the second level and of GENERIC arithmetic
   * forest     the same kind of frame through 4 096 instances of soup1000 (a 16 x 16 x 16 grid, seeded rotations)
+Each frame part also makes its AO batch on the device, beside the host-made one: ntr_instanced_hit_attributes over the primary hits, then
+ntr_raygen_ao_normals with --ao-samples rays per primary ray (length 5), timed together and apart by stream events (attr_aogen_ms,
+attr_ms, aogen_ms), and traced (ao_device_instanced).  The identity part times ntr_raygen_ao over the single-level records of the same
+frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they were.
 Prints one JSON line per part.
 
     timeout -k 10 600 python scripts/instanced_bench.py --out instanced.json
@@ -71,9 +75,11 @@ class Blas:
 
     def __init__(self, tri, pos, stream):
         tri, pos = np.ascontiguousarray(tri, np.int32), np.ascontiguousarray(pos, F)
+        self.tri, self.pos = tri, pos
         caps = nt.lbvh_capacity(tri.shape[0])
         self.bufs = [torch.zeros(c, dtype=torch.uint8, device="cuda:0") for c in caps]
         d_tri, d_pos = up(tri), up(pos)
+        self.d_tri, self.d_pos, self.d_blas_tris = d_tri, d_pos, up(np.array([(0, tri.shape[0])], np.int32))
         r = nt.ploc_build(tri.shape[0], d_tri.data_ptr(), pos.shape[0], d_pos.data_ptr(), pos.min(axis=0), pos.max(axis=0), self.bufs[0].data_ptr(),
                           caps[0], self.bufs[1].data_ptr(), caps[1], self.bufs[2].data_ptr(), caps[2], 8, stream)
         self.nb, self.wb = r.nodesBytes, r.triWoopBytes
@@ -95,6 +101,11 @@ class Tlas:
         return nt.tlas_build(self.n, self.d_inst.data_ptr(), b.ranges, b.bufs[0].data_ptr(), b.nb, self.d_nodes.data_ptr(), self.caps[0],
                              self.d_rec.data_ptr(), self.caps[1], 8, self.stream)
 
+    def geometry(self):
+        b = self.blas
+        return nt.InstancedGeometry(self.n, 1, b.tri.shape[0], b.pos.shape[0], self.d_inst.data_ptr(), b.d_blas_tris.data_ptr(),
+                                    b.d_tri.data_ptr(), b.d_pos.data_ptr())
+
     def trace(self, count, any_hit, d_rays, d_res, d_ids):
         b, r = self.blas, self.res
         return nt.trace_instanced(count, any_hit, d_rays.data_ptr(), d_res.data_ptr(), d_ids.data_ptr(), self.d_nodes.data_ptr(), r.nodesBytes,
@@ -107,6 +118,19 @@ def median_rate(fn, count, reps, warmup):
     secs = [fn() for _ in range(warmup + reps)][warmup:]
     ms = float(np.median(secs)) * 1e3
     return {"ms_median": ms, "mrays_per_s": count / ms / 1e3, "ms_min": float(min(secs)) * 1e3, "ms_max": float(max(secs)) * 1e3}
+
+
+def median_event_ms(fn, reps, warmup):
+    """fn() launches on the current stream; -> the median GPU milliseconds between two events around it."""
+    ms = []
+    for _ in range(warmup + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms[warmup:]))
 
 
 def host_ao_rays(rays, res, count, seed, radius=5.0):
@@ -132,6 +156,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--ao-rays", type=int, default=1 << 20)
+    ap.add_argument("--ao-samples", type=int, default=8, help="rays per primary ray of the device-made AO batch")
     ap.add_argument("--limit", type=int, default=120, help="seconds a GPU step may take")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -186,6 +211,36 @@ def main():
         row["ao_instanced"] = step(part + " ao", args.limit, lambda: median_rate(lambda: t.trace(na, True, d_ao, d_res, d_ids), na, args.reps, args.warmup))
         if single is not None:
             row["ao_single_level"] = step(part + " ao single", args.limit, lambda: median_rate(lambda: bvh(na, True, d_ao), na, args.reps, args.warmup))
+        # the device-made AO batch: attributes of the two-level primary hits, then the generator over their normals
+        ns, nd = args.ao_samples, n * args.ao_samples
+        row.update(ao_samples=ns, ao_device_rays=nd)
+        t.trace(n, False, d_rays, d_res, d_ids)
+        geom = t.geometry()
+        d_out, d_nrm = (torch.zeros(n * 16, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+        d_drays = torch.zeros(nd * 32, dtype=torch.uint8, device="cuda:0")
+        d_i2s, d_s2i, d_dids = (torch.zeros(nd * 4, dtype=torch.uint8, device="cuda:0") for _ in range(3))
+        d_dres = torch.zeros(nd * 16, dtype=torch.uint8, device="cuda:0")
+
+        def attr():
+            nt.instanced_hit_attributes(n, d_res.data_ptr(), d_ids.data_ptr(), geom, d_out.data_ptr(), d_nrm.data_ptr(), stream)
+
+        def aogen():
+            nt.raygen_ao_normals(d_drays.data_ptr(), d_i2s.data_ptr(), d_s2i.data_ptr(), d_rays.data_ptr(), d_out.data_ptr(), d_nrm.data_ptr(), 0, n,
+                                 ns, 5.0, 0x2545f491, stream)
+        row["attr_aogen_ms"] = step(part + " attributes + ao generation", args.limit, lambda: median_event_ms(lambda: (attr(), aogen()), args.reps, args.warmup))
+        row["attr_ms"] = step(part + " attributes", args.limit, lambda: median_event_ms(attr, args.reps, args.warmup))
+        row["aogen_ms"] = step(part + " ao generation", args.limit, lambda: median_event_ms(aogen, args.reps, args.warmup))
+        row["ao_device_instanced"] = step(part + " device ao", args.limit, lambda: median_rate(lambda: t.trace(nd, True, d_drays, d_dres, d_dids), nd, args.reps, args.warmup))
+        row["resolved_hits"] = nt.count_hits(d_out.data_ptr(), n, stream)
+        if single is not None:
+            # ntr_raygen_ao over the single-level records of the same frame: the table of triangle normals the two-level hits cannot use
+            d_tn = up(scenes.tri_normals(single.tri, single.pos))
+            bvh(n, False, d_rays)
+
+            def single_gen():
+                nt.raygen_ao(d_drays.data_ptr(), d_i2s.data_ptr(), d_s2i.data_ptr(), d_rays.data_ptr(), d_res.data_ptr(), d_tn.data_ptr(), 0, n, ns,
+                             5.0, 0x2545f491, stream)
+            row["raygen_ao_single_ms"] = step(part + " single-level ao generation", args.limit, lambda: median_event_ms(single_gen, args.reps, args.warmup))
         assert nt.trace_status() == 0, "traversal stack overflow"
         return row
 
