@@ -719,6 +719,60 @@ NTR_API int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d
                                 int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds /* NULL: asynchronous */,
                                 void* stream);
 
+/* Instance visibility and counters of the two-level trace (csrc/trace_instanced_kernels.hip).  EXTENSION; the rule is the
+ * numpy spec tests/np_instanced_masked.py: ntr_trace_instanced's rule with one change to the step "top level, link ~i".
+ *   masks       ray r carries m_r = d_rayMasks[r] when per-ray masks are given, else rayMask; instance i carries M_i =
+ *               d_instanceMasks[i] when instance masks are given, else 0xFFFFFFFF.  All 32 bits are mask bits.
+ *   entering    if (M_i & m_r) != 0 the ray enters instance i exactly as in ntr_trace_instanced.  Otherwise the step is a pop: no exit
+ *               marker is pushed, the ray is not transformed, tmax, the hit and the instance id are untouched.  A ray with m_r == 0
+ *               still walks the top level and ends as a miss.  A link ~i with i >= numInstances is popped and its mask is never read.
+ *   tree        visibility is not geometry: NtrInstance, the 64-byte record, ntr_tlas_build and ntr_tlas_refit know nothing of the
+ *               masks, which live in an array of their own; a build or a refit neither needs nor erases them.
+ *   counters    summed over the rays of a launch, a step being one iteration of a ray in the spec's loop; one ray is traced by one lane
+ *               with no sharing, so they are deterministic and equal the spec's exactly.  An entering step whose index is outside
+ *               [0, numInstances) or that finds no room for the marker counts as neither an entry nor a masked step.
+ *   bytes       the algorithmic bytes of a launch are
+ *                 52 numRays + 64 (numTopInnerVisits + numInstanceEntries + numInnerVisits) + 32 numInstanceEntries + 48 numTriTests
+ *                 + 16 numLeafVisits + 4 numHits
+ *               (the ray, the record and the instance id; the 64-byte fetches; the world ray reloaded on leaving; triangles;
+ *               terminators; the index remap), plus 4 (numInstanceEntries + numInstancesMasked) when instance masks are given and
+ *               4 numRays when per-ray masks are given.
+ * ntr_trace_instanced_masked: seconds == NULL is asynchronous on `stream` and capturable, like ntr_trace_instanced; the call allocates
+ *   nothing and reads nothing back.  With vis == NULL -- or a vis that can refuse nothing: no arrays and rayMask 0xFFFFFFFF -- it launches
+ *   the very kernel ntr_trace_instanced launches.  The mask arrays are read by the launch: a captured launch reads their contents at
+ *   replay time, and rewriting them between replays is the intended way to change visibility.  Every mask read is range checked.
+ * ntr_trace_instanced_stats: the same records through an instrumented variant of the kernel, plus the counters.  It blocks, is refused
+ *   with NTR_ERR_INVALID on a capturing stream and is not a timed path.
+ * Errors: NTR_ERR_INVALID before any device work for everything ntr_trace_instanced refuses, a mask pointer that is not 4-byte aligned
+ *   and a null stats; numRays == 0 returns NTR_OK with the stats zeroed; without a device, after these checks, NTR_ERR_NO_DEVICE /
+ *   NTR_ERR_HIP. */
+typedef struct NtrInstanceVisibility {      /* host struct of device pointers */
+    const uint32_t* d_instanceMasks;        /* numInstances words, or NULL: every instance 0xFFFFFFFF */
+    const uint32_t* d_rayMasks;             /* numRays words, or NULL: every ray has rayMask */
+    uint32_t rayMask, pad;
+} NtrInstanceVisibility;
+typedef struct NtrInstancedTraceStats {
+    int64_t numRays;              /* rays of the launch */
+    int64_t numTopInnerVisits;    /* inner steps on the top level */
+    int64_t numInstanceEntries;   /* entering steps that entered */
+    int64_t numInstancesMasked;   /* entering steps the masks refused */
+    int64_t numInnerVisits;       /* inner steps inside instances */
+    int64_t numTriTests;          /* rows tested that are not a terminator */
+    int64_t numLeafVisits;        /* terminator rows read */
+    int64_t numHits;              /* rays whose record has id != -1 */
+} NtrInstancedTraceStats;
+NTR_API int ntr_trace_instanced_masked(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                       const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                       int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                       int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                       const NtrInstanceVisibility* vis /* NULL: no masks */, float* seconds /* NULL: asynchronous */,
+                                       void* stream);
+NTR_API int ntr_trace_instanced_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                      const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                      int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                      int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                      const NtrInstanceVisibility* vis /* may be NULL */, NtrInstancedTraceStats* stats, void* stream);
+
 /* Refit of a top-level tree: the TLAS keeps its topology and gets its instance records and every box again, from the current
  * instances and the pool's current node-0 boxes, in two launches (csrc/tlas_refit_kernels.hip).  It is the update path
  * of a frame whose instances moved rigidly or whose BLASes were refitted (ntr_bvh_refit_batch); ntr_tlas_build, a blocking chain of

@@ -24,7 +24,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     PlocBatchMesh, PlocBatchMeshResult, PlocBatchResult, ploc_batch_capacity, ploc_build_batch, ploc_batch_scratch_bytes,
                     RefitBatchEntry, BvhRefitBatchResult, bvh_refit_batch, bvh_refit_batch_scratch_bytes,
                     INSTANCE_DTYPE, BlasRange, BlasPool, TlasResult, instance_invert, make_instances, tlas_capacity, tlas_build,
-                    tlas_scratch_bytes, trace_instanced, TlasRefitResult, tlas_refit, tlas_refit_scratch_bytes,
+                    tlas_scratch_bytes, trace_instanced, InstanceVisibility, InstancedTraceStats,
+                    trace_instanced_masked, trace_instanced_stats, TlasRefitResult, tlas_refit, tlas_refit_scratch_bytes,
                     BlasTris, BLAS_TRIS_DTYPE, InstancedGeometry, instanced_hit_attributes, raygen_ao_normals,
                     BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats)
 
@@ -46,6 +47,7 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "PlocBatchMesh", "PlocBatchMeshResult", "PlocBatchResult", "ploc_batch_capacity", "ploc_build_batch", "ploc_batch_scratch_bytes",
            "RefitBatchEntry", "BvhRefitBatchResult", "bvh_refit_batch", "bvh_refit_batch_scratch_bytes",
            "INSTANCE_DTYPE", "BlasRange", "BlasPool", "TlasResult", "instance_invert", "make_instances", "tlas_capacity", "tlas_build",
-           "tlas_scratch_bytes", "trace_instanced", "TlasRefitResult", "tlas_refit", "tlas_refit_scratch_bytes",
+           "tlas_scratch_bytes", "trace_instanced", "InstanceVisibility", "InstancedTraceStats",
+           "trace_instanced_masked", "trace_instanced_stats", "TlasRefitResult", "tlas_refit", "tlas_refit_scratch_bytes",
            "BlasTris", "BLAS_TRIS_DTYPE", "InstancedGeometry", "instanced_hit_attributes", "raygen_ao_normals",
            "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats"]

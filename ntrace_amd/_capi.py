@@ -40,6 +40,35 @@ class TraceStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class InstanceVisibility(C.Structure):
+    """NtrInstanceVisibility: device pointers of the instance masks (num_instances uint32 words, 0: every instance 0xFFFFFFFF) and of
+    the per-ray masks (num_rays words, 0: every ray has ray_mask)."""
+    _fields_ = [("d_instanceMasks", C.c_void_p), ("d_rayMasks", C.c_void_p), ("rayMask", C.c_uint32), ("pad", C.c_uint32)]
+
+    def __init__(self, d_instance_masks=0, d_ray_masks=0, ray_mask=0xFFFFFFFF):
+        super().__init__(int(d_instance_masks) or None, int(d_ray_masks) or None, int(ray_mask) & 0xFFFFFFFF, 0)
+
+
+class InstancedTraceStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("numRays", "numTopInnerVisits", "numInstanceEntries", "numInstancesMasked", "numInnerVisits",
+                                         "numTriTests", "numLeafVisits", "numHits")]
+
+    def algorithmic_bytes(self, instance_masks=False, ray_masks=False):
+        """include/ntrace_amd.h, DESIGN.md 6q: 52 B per ray (the ray, the record, the instance id), 64 B per top-level node, instance
+        record and bottom-level node fetched, 32 B per entry for the world ray reloaded on leaving, 48 B per triangle tested, 16 B per
+        terminator, 4 B index remap per hit; with instance masks 4 B per entering step that asked one, with per-ray masks 4 B per ray."""
+        n = (52 * self.numRays + 64 * (self.numTopInnerVisits + self.numInstanceEntries + self.numInnerVisits) + 32 * self.numInstanceEntries
+             + 48 * self.numTriTests + 16 * self.numLeafVisits + 4 * self.numHits)
+        if instance_masks:
+            n += 4 * (self.numInstanceEntries + self.numInstancesMasked)
+        if ray_masks:
+            n += 4 * self.numRays
+        return n
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class LbvhResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numLevels", C.c_int32), ("pad", C.c_int32),
                 ("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
@@ -373,6 +402,10 @@ SYMBOLS = [
     ("ntr_tlas_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
     ("ntr_tlas_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_trace_instanced", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_masked", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                             C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                            C.POINTER(InstanceVisibility), C.POINTER(InstancedTraceStats), _vp]),
     ("ntr_instanced_hit_attributes", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), _vp, _vp, _vp]),
     ("ntr_bvh_widen_capacity", C.c_int, [_i64, C.POINTER(_i64)]),
     ("ntr_bvh_widen", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhWideResult), _vp]),
@@ -1040,6 +1073,33 @@ def trace_instanced(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas
                                      int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
                                      C.byref(sec) if timed else None, _vp(stream)))
     return float(sec.value) if timed else None
+
+
+def trace_instanced_masked(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                           num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0,
+                           timed=True):
+    """ntr_trace_instanced_masked: trace_instanced with instance visibility (the rule is tests/np_instanced_masked.py).  vis: an
+    InstanceVisibility, or None (NULL: no masks, the unmasked kernel).  timed=True returns the GPU seconds; timed=False is asynchronous
+    on `stream` (capturable; the mask arrays are read at replay time) and returns None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_instanced_masked(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
+                                            _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances),
+                                            _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
+                                            _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
+                                            C.byref(sec) if timed else None, _vp(stream)))
+    return float(sec.value) if timed else None
+
+
+def trace_instanced_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                          num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0):
+    """ntr_trace_instanced_stats: trace_instanced_masked's records through the instrumented kernel -> InstancedTraceStats.  Blocks; not
+    a timed path; refused on a capturing stream."""
+    st = InstancedTraceStats()
+    _check(lib().ntr_trace_instanced_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
+                                           _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances),
+                                           _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
+                                           _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None, C.byref(st), _vp(stream)))
+    return st
 
 
 def instanced_hit_attributes(num_rays, d_results, d_instance_ids, geom, d_out_results=0, d_normals=0, stream=0):

@@ -1,0 +1,151 @@
+// trace_instanced_body.h -- the two-level trace's kernel, stated once: trace_instanced_kernels.hip (the unmasked kernel) and
+// trace_instanced_masked_kernels.hip (the masked and the instrumented one) include this text once per variant, after
+// trace_instanced_kernels.h, with
+//   NTR_TI_KERNEL   the kernel's name
+//   NTR_TI_PARAMS   its parameters: InstancedParams p, and for the masked variants InstancedExtras x
+//   NTR_TI_MASKED   1: the entering step asks the masks (x.instMasks, x.rayMasks, x.rayMask)
+//   NTR_TI_STATS    1: per-lane counters, summed into x.stats at the end
+// An include and not a function template because the unmasked variant must stay the kernel it was, instruction for instruction
+// (scripts/kernel_isa_diff.sh): with the loop in a __forceinline__ function that the kernels call, hipcc orders its passes differently and
+// allocates other registers, and every such change would have to be measured again.  No include guard: the text is meant
+// to repeat.
+__global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
+{
+    constexpr bool MASKED = NTR_TI_MASKED, STATS = NTR_TI_STATS;
+#if !NTR_TI_MASKED
+    const InstancedExtras x{};   // (never read: every use is under MASKED or STATS)
+#endif
+    __shared__ int s_stack[LDS_DEPTH][64];   // [entry][lane]
+    const int lane = threadIdx.x;
+    const int rayIdx = blockIdx.x * 64 + lane;
+    const bool valid = rayIdx < p.numRays;
+    const float4* rays4 = reinterpret_cast<const float4*>(p.rays);
+    const u32x4 rTlas = rsrc_words(p.tlas, p.tlasBytes), rRec = rsrc_words(p.records, p.recordsBytes),
+                rNodes = rsrc_words(p.poolNodes, p.poolNodesBytes), rWoop = rsrc_words(p.poolWoop, p.poolWoopBytes);
+    const bool anyHit = p.anyHit != 0;
+    u32x4 rMasks = rTlas;
+    unsigned int rayMask = 0xFFFFFFFFu;   // m_r
+    bool instMasks = false;               // wave-uniform: without instance masks no entering step loads a word
+    if (MASKED) {
+        rMasks = rsrc_words(x.instMasks, x.instMasksBytes);
+        instMasks = x.instMasks != nullptr;
+        rayMask = x.rayMasks ? x.rayMasks[valid ? rayIdx : 0] : x.rayMask;
+    }
+    InstancedLaneStats ls = {0u, 0u, 0u, 0u, 0u, 0u};
+
+    RayRegs r;   // the current form: the world ray on the top level, the object ray inside an instance
+    {
+        const float4 o = rays4[(valid ? rayIdx : 0) * 2 + 0], d = rays4[(valid ? rayIdx : 0) * 2 + 1];
+        r.ox = o.x; r.oy = o.y; r.oz = o.z; r.tmin = o.w;
+        r.dx = d.x; r.dy = d.y; r.dz = d.z; r.tmax = d.w;
+        r.rx = r.ry = r.rz = 0.0f;   // (the FAST path's reciprocals: unused)
+    }
+    LaneStack st;
+    int spill[SPILL_DEPTH];
+    st.lds = (lds_int*)&s_stack[0][lane];
+    stack_reset(st);
+
+    int hitAddr = -1, hitInst = -1;   // the hit's row in the pool's triWoop and its instance
+    float hitU = 0.0f, hitV = 0.0f;
+    int inst = -1;                    // >= 0: inside that instance
+    unsigned int nodesOffset = 0u, rowOffset = 0u;
+    // a degenerate ray (Ray::degenerate, Util.hpp:65) is a miss without traversal
+    int node = (valid && r.tmin < r.tmax) ? p.rootLink : kSentinel;
+
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
+    for (;;) {
+        if (__ballot(node != kSentinel) == 0ull) break;
+        const bool top = inst < 0;
+        const bool inner = (unsigned)node < (unsigned)kSentinel;
+        const bool neg = node < 0;
+        int ofs = kNoNode;
+        if (top) {
+            if (inner) ofs = node;
+            else if (neg && (unsigned)~node < (unsigned)p.numInstances) ofs = ~node * kRecordBytes;
+        } else if (inner) {
+            const unsigned int o = nodesOffset + (unsigned)node;
+            if (o >= nodesOffset) ofs = (int)o;                       // (a sum that wraps reads nothing)
+        } else if (neg) {
+            const unsigned int row = rowOffset + (unsigned)~node;
+            if (row < (unsigned)(kPoolMaxBytes >> kRowShift)) ofs = (int)(row << kRowShift);
+        }
+        unsigned int instMask = 0xFFFFFFFFu;   // M_i of an entering lane
+        if (MASKED) {
+            // the word of record ofs / 64 lies at ofs / 16; an entering lane whose index is out of range holds kNoNode, and kNoNode / 16 =
+            // 0x0FFFFFF0 is at or beyond the end of any mask array (4 * numInstances <= kPoolMaxBytes / 16): it reads 0 and touches nothing
+            const unsigned long long enter = __ballot(top && neg);
+            fetch64_four_buffers_and_word(rTlas, rRec, rNodes, rWoop, rMasks, ofs, (int)((unsigned)ofs >> 4), __ballot(top && inner), enter,
+                                          __ballot(!top && inner), __ballot(!top && neg), instMasks ? enter : 0ull, a, b, c, d, instMask);
+        } else {
+            fetch64_four_buffers(rTlas, rRec, rNodes, rWoop, ofs, __ballot(top && inner), __ballot(top && neg), __ballot(!top && inner),
+                                 __ballot(!top && neg), a, b, c, d);
+        }
+        if (node == kSentinel) {
+            // done: waits for the wave
+        } else if (!inner && !neg) {
+            // a positive word above the sentinel: the exit marker.  Leaving: the world ray again (tmin and the shrunk tmax stay)
+            if (node == kExitMarker) {
+                const float4 o = rays4[rayIdx * 2 + 0], dd = rays4[rayIdx * 2 + 1];
+                r.ox = o.x; r.oy = o.y; r.oz = o.z;
+                r.dx = dd.x; r.dy = dd.y; r.dz = dd.z;
+                inst = -1;
+            }
+            node = stack_pop(st, spill);   // (any other such word is no link: it is dropped)
+        } else if (top && inner) {
+            if (STATS) ls.topInner++;
+            inner_advance<false, 8>(a, b, c, d, r, node, st, spill, p.status);
+        } else if (top) {
+            // entering instance ~node: its record is worldToObject (a, b, c) and nodesOffset, row offset, nodesBytes (d)
+            const int idx = ~node;
+            if ((unsigned)idx >= (unsigned)p.numInstances) {
+                node = stack_pop(st, spill);
+            } else if (MASKED && (instMask & rayMask) == 0u) {
+                if (STATS) ls.masked++;
+                node = stack_pop(st, spill);         // refused: no marker, no transform; the fetched record is dropped
+            } else if (st.sp >= LDS_DEPTH + SPILL_DEPTH) {
+                atomicOr(p.status, NTR_STATUS_STACK_OVERFLOW);   // no room for the marker: the instance is not entered
+                node = stack_pop(st, spill);
+            } else {
+                stack_push(st, spill, kExitMarker, p.status);
+                const float ox = dot4(a, r.ox, r.oy, r.oz, 1.0f), oy = dot4(b, r.ox, r.oy, r.oz, 1.0f), oz = dot4(c, r.ox, r.oy, r.oz, 1.0f);
+                const float dx = dot4(a, r.dx, r.dy, r.dz, 0.0f), dy = dot4(b, r.dx, r.dy, r.dz, 0.0f), dz = dot4(c, r.dx, r.dy, r.dz, 0.0f);
+                r.ox = ox; r.oy = oy; r.oz = oz;
+                r.dx = dx; r.dy = dy; r.dz = dz;
+                nodesOffset = __float_as_uint(d.x);
+                rowOffset = __float_as_uint(d.y);
+                inst = idx;
+                node = 0;
+                if (STATS) ls.entries++;
+            }
+        } else {
+            int row = -1;   // the BLAS's own row of a hit this step accepts
+            if (STATS) {
+                // counted at the call site, from the row just fetched: a triangle test unless word 0 is the terminator; a terminator read for
+                // the row itself or for the word that came with a triangle -- unless an any-hit ray ended on that triangle
+                const bool term = __float_as_uint(a.x) == kLeafTerm;
+                if (inner) ls.inner++;
+                else if (!term) ls.tris++;
+                unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
+                if (!inner && (term || (!(anyHit && row >= 0) && __float_as_uint(d.x) == kLeafTerm))) ls.leaves++;
+            } else {
+                unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
+            }
+            if (row >= 0) {
+                hitAddr = (int)(rowOffset + (unsigned)row);
+                hitInst = inst;
+            }
+        }
+    }
+    if (!valid) return;
+    store_result(p.results, p.triIndex, rayIdx, hitAddr, r.tmax, hitU, hitV);
+    p.instanceIDs[rayIdx] = hitInst;
+    if (STATS) {   // diagnostics variant only: plain per-lane atomics
+        atomicAdd(&x.stats[0], (unsigned long long)ls.topInner);
+        atomicAdd(&x.stats[1], (unsigned long long)ls.entries);
+        atomicAdd(&x.stats[2], (unsigned long long)ls.masked);
+        atomicAdd(&x.stats[3], (unsigned long long)ls.inner);
+        atomicAdd(&x.stats[4], (unsigned long long)ls.tris);
+        atomicAdd(&x.stats[5], (unsigned long long)ls.leaves);
+        atomicAdd(&x.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
+    }
+}

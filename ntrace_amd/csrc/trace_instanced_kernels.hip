@@ -13,167 +13,48 @@
 // Fetches go through four wave-uniform range-checked descriptors (fetch64_four_buffers: the shape of fetch64_two_buffers): whatever a
 // link or an offset holds, a lane reads zeros and never faults.  Per lane beyond the single-level loop: nodesOffset, the row offset
 // and the instance index, which also says which level the lane is on (-1: the top level).
+// The loop is stated once (trace_instanced_body.h) and instantiated three ways (the rule is tests/np_instanced_masked.py),
+// the first here and the other two in trace_instanced_masked_kernels.hip (trace_instanced_kernels.h: why two units):
+//   trace_instanced          unmasked: ntr_trace_instanced, and ntr_trace_instanced_masked when no mask can refuse anything
+//   trace_instanced_masked   visibility: the ray's mask m_r is loaded once beside the ray; a lane that enters instance i reads M_i through a
+//                            fifth descriptor over 4 * numInstances bytes, in the same fetch and the same wait as the record, and pops when
+//                            (M_i & m_r) == 0 -- no marker, no transform, the record dropped.  Without instance masks the group of that
+//                            load has an empty mask and is skipped by its scalar branch
+//   trace_instanced_stats    the masked loop with per-lane counters, added once at the end (ntr_trace_instanced_stats; not a timed path)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "ntr_internal.h"
 #include "instanced_bvh.h"
 #include "device_scratch.h"
 #include "sched_state.h"
 #include "trace_lane.h"
+#include "trace_instanced_kernels.h"
 
 namespace ntr {
 namespace {
 
-struct InstancedParams {
-    int32_t numRays, anyHit;
-    const NtrRay* rays;
-    NtrRayResult* results;
-    int32_t* instanceIDs;
-    const void *tlas, *records, *poolNodes, *poolWoop;
-    uint32_t tlasBytes, recordsBytes, poolNodesBytes, poolWoopBytes;   // descriptor ranges (out-of-range loads return 0)
-    const int32_t* triIndex;
-    int32_t rootLink, numInstances;
-    unsigned int* status;   // sticky error bits
-};
+#define NTR_TI_KERNEL trace_instanced
+#define NTR_TI_PARAMS InstancedParams p
+#define NTR_TI_MASKED 0
+#define NTR_TI_STATS 0
+#include "trace_instanced_body.h"
+#undef NTR_TI_KERNEL
+#undef NTR_TI_PARAMS
+#undef NTR_TI_MASKED
+#undef NTR_TI_STATS
 
-// Lanes of mask k fetch 64 B at byte offset `ofs` of buffer k (range-checked: beyond the extent a load returns 0 and touches no memory),
-// all into the same registers; a buffer whose mask is empty is skipped by a scalar branch; the other lanes keep what a..d held.
-#define NTR_FETCH64_GROUP(R, M, L)                                          \
-    "s_and_b64 exec, %[sav], %[" M "]\n\t"                                  \
-    "s_cbranch_execz .Lcs_fetch" L "%=\n\t"                                 \
-    "buffer_load_dwordx4 %[a], %[ofs], %[" R "], 0 offen\n\t"               \
-    "buffer_load_dwordx4 %[b], %[ofs], %[" R "], 0 offen offset:16\n\t"     \
-    "buffer_load_dwordx4 %[c], %[ofs], %[" R "], 0 offen offset:32\n\t"     \
-    "buffer_load_dwordx4 %[d], %[ofs], %[" R "], 0 offen offset:48\n\t"     \
-    ".Lcs_fetch" L "%=:\n\t"
-__device__ __forceinline__ void fetch64_four_buffers(u32x4 r0, u32x4 r1, u32x4 r2, u32x4 r3, int ofs, unsigned long long m0,
-                                                     unsigned long long m1, unsigned long long m2, unsigned long long m3, float4& a, float4& b,
-                                                     float4& c, float4& d)
+// The three entry points' one body.  vis == NULL, or a vis that can refuse nothing (no arrays and rayMask all ones), launches the unmasked
+// kernel; stats != NULL launches the instrumented one and reads the counters back.
+int trace_instanced_impl(const char* fn, int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                         const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records, int32_t numInstances,
+                         const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                         const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis, float* seconds, void* stream,
+                         NtrInstancedTraceStats* stats)
 {
-    u32x4 va = as_u4(a), vb = as_u4(b), vc = as_u4(c), vd = as_u4(d);
-    unsigned long long sav;
-    asm volatile("s_mov_b64 %[sav], exec\n\t"
-                 NTR_FETCH64_GROUP("r0", "m0", "a")
-                 NTR_FETCH64_GROUP("r1", "m1", "b")
-                 NTR_FETCH64_GROUP("r2", "m2", "c")
-                 NTR_FETCH64_GROUP("r3", "m3", "d")
-                 "s_mov_b64 exec, %[sav]\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : [a] "+v"(va), [b] "+v"(vb), [c] "+v"(vc), [d] "+v"(vd), [sav] "=&s"(sav)
-                 : [ofs] "v"(ofs), [r0] "s"(r0), [r1] "s"(r1), [r2] "s"(r2), [r3] "s"(r3), [m0] "s"(m0), [m1] "s"(m1), [m2] "s"(m2), [m3] "s"(m3)
-                 : "memory", "scc");   // (s_and_b64 writes SCC)
-    a = as_f4(va); b = as_f4(vb); c = as_f4(vc); d = as_f4(vd);
-}
-#undef NTR_FETCH64_GROUP
-
-__global__ __launch_bounds__(64) void trace_instanced(InstancedParams p)
-{
-    __shared__ int s_stack[LDS_DEPTH][64];   // [entry][lane]
-    const int lane = threadIdx.x;
-    const int rayIdx = blockIdx.x * 64 + lane;
-    const bool valid = rayIdx < p.numRays;
-    const float4* rays4 = reinterpret_cast<const float4*>(p.rays);
-    const u32x4 rTlas = rsrc_words(p.tlas, p.tlasBytes), rRec = rsrc_words(p.records, p.recordsBytes),
-                rNodes = rsrc_words(p.poolNodes, p.poolNodesBytes), rWoop = rsrc_words(p.poolWoop, p.poolWoopBytes);
-    const bool anyHit = p.anyHit != 0;
-
-    RayRegs r;   // the current form: the world ray on the top level, the object ray inside an instance
-    {
-        const float4 o = rays4[(valid ? rayIdx : 0) * 2 + 0], d = rays4[(valid ? rayIdx : 0) * 2 + 1];
-        r.ox = o.x; r.oy = o.y; r.oz = o.z; r.tmin = o.w;
-        r.dx = d.x; r.dy = d.y; r.dz = d.z; r.tmax = d.w;
-        r.rx = r.ry = r.rz = 0.0f;   // (the FAST path's reciprocals: unused)
-    }
-    LaneStack st;
-    int spill[SPILL_DEPTH];
-    st.lds = (lds_int*)&s_stack[0][lane];
-    stack_reset(st);
-
-    int hitAddr = -1, hitInst = -1;   // the hit's row in the pool's triWoop and its instance
-    float hitU = 0.0f, hitV = 0.0f;
-    int inst = -1;                    // >= 0: inside that instance
-    unsigned int nodesOffset = 0u, rowOffset = 0u;
-    // a degenerate ray (Ray::degenerate, Util.hpp:65) is a miss without traversal
-    int node = (valid && r.tmin < r.tmax) ? p.rootLink : kSentinel;
-
-    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
-    for (;;) {
-        if (__ballot(node != kSentinel) == 0ull) break;
-        const bool top = inst < 0;
-        const bool inner = (unsigned)node < (unsigned)kSentinel;
-        const bool neg = node < 0;
-        int ofs = kNoNode;
-        if (top) {
-            if (inner) ofs = node;
-            else if (neg && (unsigned)~node < (unsigned)p.numInstances) ofs = ~node * kRecordBytes;
-        } else if (inner) {
-            const unsigned int o = nodesOffset + (unsigned)node;
-            if (o >= nodesOffset) ofs = (int)o;                       // (a sum that wraps reads nothing)
-        } else if (neg) {
-            const unsigned int row = rowOffset + (unsigned)~node;
-            if (row < (unsigned)(kPoolMaxBytes >> kRowShift)) ofs = (int)(row << kRowShift);
-        }
-        fetch64_four_buffers(rTlas, rRec, rNodes, rWoop, ofs, __ballot(top && inner), __ballot(top && neg), __ballot(!top && inner),
-                             __ballot(!top && neg), a, b, c, d);
-        if (node == kSentinel) {
-            // done: waits for the wave
-        } else if (!inner && !neg) {
-            // a positive word above the sentinel: the exit marker.  Leaving: the world ray again (tmin and the shrunk tmax stay)
-            if (node == kExitMarker) {
-                const float4 o = rays4[rayIdx * 2 + 0], dd = rays4[rayIdx * 2 + 1];
-                r.ox = o.x; r.oy = o.y; r.oz = o.z;
-                r.dx = dd.x; r.dy = dd.y; r.dz = dd.z;
-                inst = -1;
-            }
-            node = stack_pop(st, spill);   // (any other such word is no link: it is dropped)
-        } else if (top && inner) {
-            inner_advance<false, 8>(a, b, c, d, r, node, st, spill, p.status);
-        } else if (top) {
-            // entering instance ~node: its record is worldToObject (a, b, c) and nodesOffset, row offset, nodesBytes (d)
-            const int idx = ~node;
-            if ((unsigned)idx >= (unsigned)p.numInstances) {
-                node = stack_pop(st, spill);
-            } else if (st.sp >= LDS_DEPTH + SPILL_DEPTH) {
-                atomicOr(p.status, NTR_STATUS_STACK_OVERFLOW);   // no room for the marker: the instance is not entered
-                node = stack_pop(st, spill);
-            } else {
-                stack_push(st, spill, kExitMarker, p.status);
-                const float ox = dot4(a, r.ox, r.oy, r.oz, 1.0f), oy = dot4(b, r.ox, r.oy, r.oz, 1.0f), oz = dot4(c, r.ox, r.oy, r.oz, 1.0f);
-                const float dx = dot4(a, r.dx, r.dy, r.dz, 0.0f), dy = dot4(b, r.dx, r.dy, r.dz, 0.0f), dz = dot4(c, r.dx, r.dy, r.dz, 0.0f);
-                r.ox = ox; r.oy = oy; r.oz = oz;
-                r.dx = dx; r.dy = dy; r.dz = dz;
-                nodesOffset = __float_as_uint(d.x);
-                rowOffset = __float_as_uint(d.y);
-                inst = idx;
-                node = 0;
-            }
-        } else {
-            int row = -1;   // the BLAS's own row of a hit this step accepts
-            unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
-            if (row >= 0) {
-                hitAddr = (int)(rowOffset + (unsigned)row);
-                hitInst = inst;
-            }
-        }
-    }
-    if (!valid) return;
-    store_result(p.results, p.triIndex, rayIdx, hitAddr, r.tmax, hitU, hitV);
-    p.instanceIDs[rayIdx] = hitInst;
-}
-
-}  // namespace
-}  // namespace ntr
-
-using namespace ntr;
-
-extern "C" int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
-                                   const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
-                                   int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
-                                   int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds, void* stream)
-{
-    const char* fn = "ntr_trace_instanced";
     if (seconds) *seconds = 0.0f;
+    if (stats) memset(stats, 0, sizeof(*stats));
     if (numRays < 0) return set_error(NTR_ERR_INVALID, "%s: numRays < 0", fn);
     if (numRays == 0) return NTR_OK;
     if (!d_rays || !d_results || !d_instanceIDs) return set_error(NTR_ERR_INVALID, "%s: null ray, result or instance id buffer", fn);
@@ -186,16 +67,27 @@ extern "C" int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay
                          (unsigned long long)kMaxNodesBytes);
     if (const int rc = check_pool_bytes(fn, "poolNodesBytes", poolNodesBytes, kNodeBytes)) return rc;
     if (const int rc = check_pool_bytes(fn, "poolTriWoopBytes", poolTriWoopBytes, kRowBytes)) return rc;
+    if (vis && ((((uintptr_t)vis->d_instanceMasks) | ((uintptr_t)vis->d_rayMasks)) & 3u) != 0)
+        return set_error(NTR_ERR_INVALID, "%s: a mask array must be 4-byte aligned", fn);
 
     DeviceState* ds = nullptr;
     if (const int rc = current_device_state_ready(&ds)) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (stats && stream_is_capturing(s)) return set_error(NTR_ERR_INVALID, "%s: the call reads its counters back and cannot be captured", fn);
     InstancedParams p{};
     p.numRays = numRays; p.anyHit = anyHit ? 1 : 0; p.rays = d_rays; p.results = d_results; p.instanceIDs = d_instanceIDs;
     p.tlas = d_tlasNodes; p.records = d_records; p.poolNodes = d_poolNodes; p.poolWoop = d_poolTriWoop;
     p.tlasBytes = d_tlasNodes ? (uint32_t)tlasNodesBytes : 0u; p.recordsBytes = (uint32_t)((int64_t)numInstances * kRecordBytes);
     p.poolNodesBytes = (uint32_t)poolNodesBytes; p.poolWoopBytes = (uint32_t)poolTriWoopBytes;
     p.triIndex = d_poolTriIndex; p.rootLink = rootLink; p.numInstances = numInstances; p.status = ds->status;
+    InstancedExtras x{};
+    x.rayMask = 0xFFFFFFFFu;
+    if (vis) {
+        x.instMasks = vis->d_instanceMasks; x.instMasksBytes = vis->d_instanceMasks ? (uint32_t)((int64_t)numInstances * 4) : 0u;
+        x.rayMasks = vis->d_rayMasks; x.rayMask = vis->rayMask;
+    }
+    x.stats = ds->stats;
+    const bool masked = x.instMasks || x.rayMasks || x.rayMask != 0xFFFFFFFFu;
 
     StreamEvents<2> ev(s);   // the timed bracket
     if (seconds) {
@@ -203,7 +95,15 @@ extern "C" int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay
         NTR_HIP(hipStreamSynchronize(s));
         NTR_HIP(ev.record(0));
     }
-    trace_instanced<<<(numRays + 63) / 64, 64, 0, s>>>(p);
+    const dim3 grid((numRays + 63) / 64), block(64);
+    if (stats) {
+        NTR_HIP(hipMemsetAsync(ds->stats, 0, 7 * sizeof(unsigned long long), s));
+        launch_trace_instanced_variant(true, grid.x, s, &p, &x);
+    } else if (masked) {
+        launch_trace_instanced_variant(false, grid.x, s, &p, &x);
+    } else {
+        hipLaunchKernelGGL(trace_instanced, grid, block, 0, s, p);
+    }
     NTR_HIP(hipGetLastError());
     if (seconds) {
         NTR_HIP(ev.record(1));
@@ -214,5 +114,52 @@ extern "C" int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay
         if (const int rc = status_fetch(ds, s, &bits)) return rc;
         if (bits & NTR_STATUS_STACK_OVERFLOW) return set_error(NTR_ERR_OVERFLOW, "%s: traversal stack overflow", fn);
     }
+    if (stats) {
+        unsigned long long h[7];
+        NTR_HIP(hipMemcpyAsync(h, ds->stats, sizeof(h), hipMemcpyDeviceToHost, s));
+        NTR_HIP(hipStreamSynchronize(s));
+        stats->numRays = numRays;
+        stats->numTopInnerVisits = (int64_t)h[0]; stats->numInstanceEntries = (int64_t)h[1]; stats->numInstancesMasked = (int64_t)h[2];
+        stats->numInnerVisits = (int64_t)h[3]; stats->numTriTests = (int64_t)h[4]; stats->numLeafVisits = (int64_t)h[5];
+        stats->numHits = (int64_t)h[6];
+    }
     return NTR_OK;
+}
+
+}  // namespace
+}  // namespace ntr
+
+using namespace ntr;
+
+extern "C" int ntr_trace_instanced(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                   const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                   int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                   int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, float* seconds, void* stream)
+{
+    return trace_instanced_impl("ntr_trace_instanced", numRays, anyHit, d_rays, d_results, d_instanceIDs, d_tlasNodes, tlasNodesBytes, rootLink,
+                                d_records, numInstances, d_poolNodes, poolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex, nullptr,
+                                seconds, stream, nullptr);
+}
+
+extern "C" int ntr_trace_instanced_masked(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                          const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                          int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                          int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis,
+                                          float* seconds, void* stream)
+{
+    return trace_instanced_impl("ntr_trace_instanced_masked", numRays, anyHit, d_rays, d_results, d_instanceIDs, d_tlasNodes, tlasNodesBytes,
+                                rootLink, d_records, numInstances, d_poolNodes, poolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex,
+                                vis, seconds, stream, nullptr);
+}
+
+extern "C" int ntr_trace_instanced_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                         const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                         int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                         int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis,
+                                         NtrInstancedTraceStats* stats, void* stream)
+{
+    if (!stats) return set_error(NTR_ERR_INVALID, "ntr_trace_instanced_stats: null stats");
+    return trace_instanced_impl("ntr_trace_instanced_stats", numRays, anyHit, d_rays, d_results, d_instanceIDs, d_tlasNodes, tlasNodesBytes,
+                                rootLink, d_records, numInstances, d_poolNodes, poolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex,
+                                vis, nullptr, stream, stats);
 }

@@ -1,5 +1,5 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
-// (see the header).
+// and ntr_trace_instanced_masked (see the header).
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
@@ -123,9 +123,20 @@ void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32
         if (ntr_instance_invert(inst[i].objectToWorld, inst[i].worldToObject) != NTR_OK) fail("CudaInstancedBVH: instance %d: %s", i, ntr_last_error());
         inst[i].blas = blas[i];
     }
-    if (num != m_numInstances) m_topology = false;   // an unchanged count keeps the TLAS's topology for refit()
+    if (num != m_numInstances) {
+        m_topology = false;                          // an unchanged count keeps the TLAS's topology for refit() ...
+        m_instanceMasks.resizeDiscard(0);            // ... and the instance masks: with another count they would name other instances
+    }
     m_numInstances = num;
     m_built = false;
+}
+
+void CudaInstancedBVH::setInstanceMasks(const U32* masks)
+{
+    if (m_numInstances < 1) fail("CudaInstancedBVH: no instances to mask (call setInstances first)");
+    if (!masks) { m_instanceMasks.resizeDiscard(0); return; }
+    m_instanceMasks.resizeDiscard((S64)m_numInstances * sizeof(U32));
+    m_instanceMasks.set(masks, (S64)m_numInstances * sizeof(U32));   // the TLAS knows nothing of visibility: m_built stays
 }
 
 void CudaInstancedBVH::build(S32 radius)
@@ -163,18 +174,33 @@ void CudaInstancedBVH::refit(void)
     m_built = true;
 }
 
-F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs)
+F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
 {
     const S32 numRays = rays.getSize();
     instanceIDs.resizeDiscard((S64)numRays * sizeof(S32));
     if (!numRays) return 0.0f;
     if (!m_built) fail("CudaInstancedBVH: No TLAS!");
     float seconds = 0.0f;
-    const int rc = ntr_trace_instanced(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
-                                       (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                       m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
-                                       m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                       (const int32_t*)m_poolTriIndex.getCudaPtr(), &seconds, NULL);
+    const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
+    int rc;
+    if (!masks && rayMask == 0xFFFFFFFFu) {
+        rc = ntr_trace_instanced(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
+                                 (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                 m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
+                                 m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                 (const int32_t*)m_poolTriIndex.getCudaPtr(), &seconds, NULL);
+    } else {
+        NtrInstanceVisibility vis;
+        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
+        vis.d_rayMasks = NULL;
+        vis.rayMask = rayMask;
+        vis.pad = 0;
+        rc = ntr_trace_instanced_masked(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
+                                        (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                        m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
+                                        m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                        (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
+    }
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     return seconds;
 }

@@ -17,7 +17,12 @@
 //                 count; a changed count, addBLAS and buildBLASes invalidate it as they invalidate build().  The frame loop of a moving,
 //                 deforming scene is refitBLASes -> setInstances -> refit -> traceBatch, with build() every so many frames: a refit
 //                 keeps the tree the old positions suggested, and its boxes overlap more the further the instances travel
-//   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss)
+//   setInstanceMasks  one 32-bit visibility mask per instance; NULL: all visible again.  Visibility is not geometry: the
+//                 TLAS is not touched and isBuilt() stays as it was.  Fails before setInstances; a later setInstances with another
+//                 count drops the masks back to all visible, one with the same count keeps them
+//   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss).  A ray enters
+//                 instance i only if (mask_i & rayMask) != 0 (ntr_trace_instanced_masked); with no masks set and the default ray mask
+//                 the call is ntr_trace_instanced's
 //   getBLASTrisBuffer  NtrBlasTris per BLAS, on the device: the meshes buildBLASes remembers, which ntr_instanced_hit_attributes needs
 //                 to turn a two-level hit's id into a pool triangle.  A BLAS that came through addBLAS has numTris 0:
 //                 its hits resolve to -1
@@ -49,8 +54,10 @@ public:
     void setInstances(S32 num, const F32* objectToWorld /* num x 12 */, const S32* blas);
     void build(S32 radius = DefaultRadius);
     void refit(void);
-    F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs);                       // GPU seconds
+    void setInstanceMasks(const U32* masks /* getNumInstances() words; NULL: all visible */);
+    F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask = 0xFFFFFFFFu);   // GPU seconds
 
+    Buffer& getInstanceMaskBuffer(void) { return m_instanceMasks; }              // U32 per instance; empty: all visible
     Buffer& getBLASTrisBuffer(void);                                             // NtrBlasTris per BLAS (numTris 0: an addBLAS tree)
     bool isBuilt(void) const { return m_built; }                                 // the TLAS is current: traceBatch may run
     S32  getFirstMeshlessBLAS(void) const;                                       // the first addBLAS tree of the pool, -1 if none
@@ -78,6 +85,7 @@ private:
     std::vector<Mesh>         m_meshes;                                          // per BLAS, as m_ranges
     Buffer        m_poolNodes, m_poolTriWoop, m_poolTriIndex;
     Buffer        m_instances, m_tlasNodes, m_records;
+    Buffer        m_instanceMasks;                                               // empty: no masks
     Buffer        m_blasTris;                                                    // filled from m_meshes on demand
     bool          m_blasTrisCurrent;
     S32           m_numInstances;

@@ -6,6 +6,7 @@ namespace FW {
 
 InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
     : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
+      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu),
       m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
 {
 }
@@ -25,6 +26,12 @@ void InstancedRenderer::setParams(RayType rayType, F32 aoRadius, S32 numSamples)
     m_rayType = rayType;
     m_aoRadius = aoRadius;
     m_numSamples = numSamples;
+}
+
+void InstancedRenderer::setRayMasks(U32 primaryMask, U32 secondaryMask)
+{
+    m_primaryMask = primaryMask;
+    m_secondaryMask = secondaryMask;
 }
 
 // the batch's records with pool triangle ids and, for a batch that secondary rays start from, the world-space normals
@@ -63,7 +70,7 @@ void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
     if (w < 1 || h < 1) fail("InstancedRenderer::beginFrame: bad frame size");
     m_raygen.primary(m_primaryRays, camera.position, camera.nscreenToWorld, w, h, camera.cameraFar, 0);
     if (m_rayType != RayType_Primary) {   // Renderer.cpp:482-488
-        m_bvh.traceBatch(m_primaryRays, m_primaryIDs);
+        m_bvh.traceBatch(m_primaryRays, m_primaryIDs, m_primaryMask);
         resolve(m_primaryRays, m_primaryIDs, m_primaryResolved, &m_primaryNormals);
     }
     m_cameraFar = camera.cameraFar;
@@ -107,7 +114,7 @@ F32 InstancedRenderer::traceBatch(void)
     if (!m_batchRays) fail("InstancedRenderer::traceBatch: no batch");
     const bool primary = m_batchRays == &m_primaryRays;
     Buffer& ids = primary ? m_primaryIDs : m_secondaryIDs;
-    const F32 sec = m_bvh.traceBatch(*m_batchRays, ids);
+    const F32 sec = m_bvh.traceBatch(*m_batchRays, ids, primary ? m_primaryMask : m_secondaryMask);
     resolve(*m_batchRays, ids, *m_batchResolved, primary ? &m_primaryNormals : NULL);
     return sec;
 }

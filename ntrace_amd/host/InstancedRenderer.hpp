@@ -4,6 +4,9 @@
 //   setGeometry   the index and vertex buffers CudaInstancedBVH::buildBLASes / refitBLASes were given; the vertex buffer holds the
 //                 CURRENT positions whenever a batch is traced (the buffers are borrowed, not copied)
 //   setParams     the ray type, the AO radius and the samples per primary hit
+//   setRayMasks   the ray masks of CudaInstancedBVH::traceBatch: primary batches are traced with the first, AO and diffuse
+//                 batches with the second; both default to all ones.  Nothing else in the frame changes: a masked-out primary hit is a
+//                 miss, and ntr_instanced_hit_attributes resolves it as one
 //   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
 //                 diffuse frames the primary rays are traced and resolved at once
 //   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
@@ -27,6 +30,7 @@ public:
 
     void setGeometry(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos);
     void setParams(RayType rayType, F32 aoRadius, S32 numSamples);
+    void setRayMasks(U32 primaryMask = 0xFFFFFFFFu, U32 secondaryMask = 0xFFFFFFFFu);
 
     void beginFrame(const CameraView& camera, S32 w, S32 h);
     bool nextBatch(void);
@@ -53,6 +57,7 @@ private:
     RayType    m_rayType;
     F32        m_aoRadius;
     S32        m_numSamples;
+    U32        m_primaryMask, m_secondaryMask;
     RayGen     m_raygen;
     F32        m_cameraFar;
     RayBuffer  m_primaryRays, m_secondaryRays;

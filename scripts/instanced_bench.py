@@ -12,6 +12,11 @@ Each frame part also makes its AO batch on the device, beside the host-made one:
 ntr_raygen_ao_normals with --ao-samples rays per primary ray (length 5), timed together and apart by stream events (attr_aogen_ms,
 attr_ms, aogen_ms), and traced (ao_device_instanced).  The identity part times ntr_raygen_ao over the single-level records of the same
 frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they were.
+  * masks      (not in the default parts) instance visibility and the counters of the two-level trace over the identity and the forest
+               frame: per batch (primary closest hit, host-made AO any hit) the counters of ntr_trace_instanced_stats, the algorithmic
+               bytes and their fraction of 8 TB/s at the measured time, and three launches timed: the unmasked launch, the masked
+               launch with everything visible (an instance mask array of all ones) and, for the AO batch, the masked launch with
+               every second instance hidden from it (odd instances carry mask 1, even ones 3; the AO rays carry 2)
 Prints one JSON line per part.
 
     timeout -k 10 600 python scripts/instanced_bench.py --out instanced.json
@@ -35,6 +40,7 @@ from ntrace_amd import scenes  # noqa: E402
 F = np.float32
 PHASES = ("boxesMs", "sortMs", "clustersMs", "roundsMs", "tailMs")
 KERNEL = "fermi_speculative_while_while"
+PEAK_BYTES_PER_S = 8e12   # the HBM figure the roofline fractions are taken of
 
 
 def up(a):
@@ -106,6 +112,17 @@ class Tlas:
         return nt.InstancedGeometry(self.n, 1, b.tri.shape[0], b.pos.shape[0], self.d_inst.data_ptr(), b.d_blas_tris.data_ptr(),
                                     b.d_tri.data_ptr(), b.d_pos.data_ptr())
 
+    def args(self, count, any_hit, d_rays, d_res, d_ids):
+        b, r = self.blas, self.res
+        return (count, any_hit, d_rays.data_ptr(), d_res.data_ptr(), d_ids.data_ptr(), self.d_nodes.data_ptr(), r.nodesBytes, r.rootLink,
+                self.d_rec.data_ptr(), self.n, b.bufs[0].data_ptr(), b.nb, b.bufs[1].data_ptr(), b.wb, b.bufs[2].data_ptr())
+
+    def trace_masked(self, count, any_hit, d_rays, d_res, d_ids, vis):
+        return nt.trace_instanced_masked(*self.args(count, any_hit, d_rays, d_res, d_ids), vis=vis, stream=self.stream)
+
+    def stats(self, count, any_hit, d_rays, d_res, d_ids, vis):
+        return nt.trace_instanced_stats(*self.args(count, any_hit, d_rays, d_res, d_ids), vis=vis, stream=self.stream)
+
     def trace(self, count, any_hit, d_rays, d_res, d_ids):
         b, r = self.blas, self.res
         return nt.trace_instanced(count, any_hit, d_rays.data_ptr(), d_res.data_ptr(), d_ids.data_ptr(), self.d_nodes.data_ptr(), r.nodesBytes,
@@ -168,7 +185,7 @@ def main():
         rows.append(row)
 
     soup = None
-    if "tlas" in args.parts or "forest" in args.parts:
+    if "tlas" in args.parts or "forest" in args.parts or "masks" in args.parts:
         tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
         soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
 
@@ -244,22 +261,67 @@ def main():
         assert nt.trace_status() == 0, "traversal stack overflow"
         return row
 
-    if "identity" in args.parts:
+    def masks_frame(frame_name, t, cam):
+        """The counters, the algorithmic bytes and the three timed launches of the part `masks` over one frame."""
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays = up(rays)
+        d_res, d_ids = (torch.zeros(max(n, na) * b, dtype=torch.uint8, device="cuda:0") for b in (16, 4))
+        row = {"part": "masks", "frame": frame_name, "instances": t.n, "primary_rays": n, "ao_rays": na, "peak_bytes_per_s": PEAK_BYTES_PER_S}
+        t.trace(n, False, d_rays, d_res, d_ids)
+        torch.cuda.synchronize()
+        res = d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE).copy()
+        d_ao = up(host_ao_rays(rays, res, na, 7))
+        d_ones = up(np.full(t.n, 0xFFFFFFFF, np.uint32))
+        d_half = up(np.where(np.arange(t.n) % 2 == 0, 3, 1).astype(np.uint32))
+        visible = nt.InstanceVisibility(d_ones.data_ptr(), 0, 0xFFFFFFFF)
+        half = nt.InstanceVisibility(d_half.data_ptr(), 0, 2)
+        row["instances_hidden_from_ao"] = int(t.n // 2)
+
+        def launch(name, count, any_hit, d_r, vis):
+            """One launch kind of one batch: its counters, then its time, then the bytes over the time."""
+            st = step("%s %s counters" % (frame_name, name), args.limit, lambda: t.stats(count, any_hit, d_r, d_res, d_ids, vis))
+            if vis is None:
+                fn = lambda: t.trace(count, any_hit, d_r, d_res, d_ids)   # noqa: E731
+            else:
+                fn = lambda: t.trace_masked(count, any_hit, d_r, d_res, d_ids, vis)   # noqa: E731
+            out = step("%s %s" % (frame_name, name), args.limit, lambda: median_rate(fn, count, args.reps, args.warmup))
+            out["counters"] = st.as_dict()
+            out["algorithmic_bytes"] = int(st.algorithmic_bytes(instance_masks=vis is not None))
+            out["fraction_of_peak"] = out["algorithmic_bytes"] / (out["ms_median"] * 1e-3) / PEAK_BYTES_PER_S
+            return out
+        row["primary_unmasked"] = launch("primary unmasked", n, False, d_rays, None)
+        row["primary_masked_all_visible"] = launch("primary masked, all visible", n, False, d_rays, visible)
+        row["ao_unmasked"] = launch("ao unmasked", na, True, d_ao, None)
+        row["ao_masked_all_visible"] = launch("ao masked, all visible", na, True, d_ao, visible)
+        row["ao_masked_half_hidden"] = launch("ao masked, every second instance hidden", na, True, d_ao, half)
+        for k in ("primary", "ao"):
+            row[k + "_masked_over_unmasked"] = row[k + "_masked_all_visible"]["ms_median"] / row[k + "_unmasked"]["ms_median"]
+        assert nt.trace_status() == 0, "traversal stack overflow"
+        return row
+
+    if "identity" in args.parts or "masks" in args.parts:
         tri, pos, cam = scenes.atrium()
         atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
         t = step("identity tlas", args.limit, lambda: Tlas(atrium, np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F), stream))
-        row = frame("identity", t, cam, atrium)
-        row["tris"] = int(tri.shape[0])
-        emit(row)
+        if "identity" in args.parts:
+            row = frame("identity", t, cam, atrium)
+            row["tris"] = int(tri.shape[0])
+            emit(row)
+        if "masks" in args.parts:
+            emit(masks_frame("identity", t, cam))
 
-    if "forest" in args.parts:
+    if "forest" in args.parts or "masks" in args.parts:
         rng = np.random.default_rng(4096)
         g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
         t = step("forest tlas", args.limit, lambda: Tlas(soup, transforms(rotations(4096, rng), (g - 7.5) * 30.0), stream))
         cam = dict(eye=(40.0, 60.0, -420.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
-        row = frame("forest", t, cam)
-        row.update(tlas_height=t.res.height, tlas_ms=t.res.seconds * 1e3)
-        emit(row)
+        if "forest" in args.parts:
+            row = frame("forest", t, cam)
+            row.update(tlas_height=t.res.height, tlas_ms=t.res.seconds * 1e3)
+            emit(row)
+        if "masks" in args.parts:
+            emit(masks_frame("forest", t, cam))
 
     if args.out:
         with open(args.out, "w") as f:
