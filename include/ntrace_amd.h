@@ -385,6 +385,10 @@ NTR_API int ntr_selftest_division(const float* d_x, int32_t nx, const float* d_d
  * scripts/studies/div_one_correction_check.py checks in exact integer arithmetic), as x = X 2^(xExp + i - 23), d = +-D 2^(dExp + j - 23),
  * i, j = 0..3.  pairs = quotients tested, mismatches = FAST differs from `/` (must be 0).  Diagnostic, blocking. */
 NTR_API int ntr_selftest_division_hard(int32_t xExp, int32_t dExp, uint64_t* pairs, uint64_t* mismatches, void* stream);
+/* Device self test of the FAST path's admission test: counts the rays of d_rays on which the integer form the trace kernels run (ray_class,
+ * trace_lane.h) and the rule's float ranges (directions 2^-40 <= |d| <= 2^20, origins 2^-36 <= |o| < 2^55, a zero origin component only
+ * with NTR_BVH_NOTINY in bvhFlags) disagree (must be 0 for every bit pattern).  Diagnostic, blocking. */
+NTR_API int ntr_selftest_ray_class(const NtrRay* d_rays, int32_t numRays, uint32_t bvhFlags, uint32_t* mismatches, void* stream);
 
 /* ---- ray production (callers of the hot path) -------- */
 

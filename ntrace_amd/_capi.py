@@ -346,6 +346,7 @@ SYMBOLS = [
     ("ntr_bvh_leaf_depths", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, C.POINTER(_i32), _vp]),
     ("ntr_selftest_division", C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_u32), _vp]),
     ("ntr_selftest_division_hard", C.c_int, [_i32, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp]),
+    ("ntr_selftest_ray_class", C.c_int, [_vp, _i32, _u32, C.POINTER(_u32), _vp]),
     ("ntr_trace_bvh_stats", C.c_int, [C.c_char_p, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _u32, _vp,
                                       C.POINTER(TraceStats)]),
     ("ntr_bvh_validate", C.c_int, [_vp, _i64, C.POINTER(_u32), _vp]),
@@ -736,6 +737,13 @@ def selftest_division_hard(x_exp, d_exp, stream=0):
     n, m = C.c_uint64(0), C.c_uint64(0)
     _check(lib().ntr_selftest_division_hard(int(x_exp), int(d_exp), C.byref(n), C.byref(m), _vp(stream)))
     return int(n.value), int(m.value)
+
+
+def selftest_ray_class(d_rays, num_rays, bvh_flags, stream=0):
+    """rays on which the kernels' integer FAST-path admission test (ray_class) differs from the rule's float ranges (ntr_selftest_ray_class)"""
+    m = _u32(0)
+    _check(lib().ntr_selftest_ray_class(_vp(d_rays), int(num_rays), int(bvh_flags), C.byref(m), _vp(stream)))
+    return int(m.value)
 
 
 def trace_bvh_stats(kernel, num_rays, any_hit, d_rays, d_results, d_nodes, nodes_bytes, d_woop, woop_bytes,

@@ -106,6 +106,26 @@ struct TraceLaunch {
     PredictScratch* predScratch = nullptr;   // non-null: the dispatch order is predicted before the launch
 };
 
+// The launch constants of the per-ray bodies (TraceParams::k): everything a wave would derive from the launch's arguments alone.
+static void trace_fill_consts(TraceParams& p)
+{
+    TraceConsts& k = p.k;
+    const unsigned long long an = (unsigned long long)p.nodes, aw = (unsigned long long)p.woop, lo = an < aw ? an : aw;
+    k.base = (const char*)lo;
+    k.dN = (uint32_t)(an - lo); k.dW = (uint32_t)(aw - lo);
+    k.limNode = p.nodesBytes - (uint32_t)kNodeBytes;
+    k.limTri = leaf_link((int)((p.woopBytes - (uint32_t)kNodeBytes) >> kRowShift));
+    k.oddBase = k.limNode + 1u; k.oddSpan = (uint32_t)k.limTri - k.oddBase;
+    // descriptor words: base, base_hi (stride 0), extent in bytes, flags (what make_rsrc builds)
+    k.rNodes[0] = (uint32_t)an; k.rNodes[1] = (uint32_t)(an >> 32) & 0xFFFFu; k.rNodes[2] = p.nodesBytes; k.rNodes[3] = 0x00020000u;
+    k.rWoop[0] = (uint32_t)aw; k.rWoop[1] = (uint32_t)(aw >> 32) & 0xFFFFu; k.rWoop[2] = p.woopBytes; k.rWoop[3] = 0x00020000u;
+    k.descentLim = !p.certainDescent ? 0u : k.limNode < (uint32_t)kSentinel ? k.limNode : (uint32_t)kSentinel - 1u;
+    const bool ordered = (p.bvhFlags & NTR_BVH_ORDERED) != 0;
+    k.switches = ((p.bvhFlags & NTR_BVH_FASTDIV) ? NTR_K_FAST : 0u) | ((p.bvhFlags & NTR_BVH_NOTINY) ? NTR_K_ZERO_ORIGIN : 0u) |
+                 ((p.octant && ordered) ? NTR_K_OCTANT : 0u) | ((p.certainSteps && ordered) ? NTR_K_CERTAIN : 0u) |
+                 ((p.uniformPrologue && (an & (unsigned long long)(kNodeBytes - 1)) == 0ull) ? NTR_K_PROLOGUE : 0u);
+}
+
 // Binds the run-time state the plan asks for -- hint, prediction scratch, pool counters -- and derives both sides' parameters from L->p.
 static int bind_trace(DeviceState* ds, const Tunables& tun, const TracePlan& pl, bool capturing, int64_t nodesBytes, hipStream_t s,
                       NtrSchedHint* hint, TraceLaunch* L)
@@ -190,6 +210,8 @@ static int bind_trace(DeviceState* ds, const Tunables& tun, const TracePlan& pl,
         p.routeSkip = NTR_ROUTE_SKIP_INCOHERENT;
         if (variant == NTR_VARIANT_PERSISTENT) { p.fetchThreshold = pl.perrayFetchThreshold; p.poolKConst = 1; }
     }
+    trace_fill_consts(p);
+    trace_fill_consts(pp);
     return NTR_OK;
 }
 
@@ -688,6 +710,23 @@ int ntr_selftest_division(const float* d_x, int32_t nx, const float* d_d, int32_
     NTR_HIP(hipMemcpyAsync(&m, d_m, sizeof(m), hipMemcpyDeviceToHost, s));
     NTR_HIP(hipStreamSynchronize(s));
     NTR_HIP(hipFree(d_m));
+    *mismatches = m;
+    return NTR_OK;
+}
+
+int ntr_selftest_ray_class(const NtrRay* d_rays, int32_t numRays, uint32_t bvhFlags, uint32_t* mismatches, void* stream)
+{
+    if (!mismatches || !d_rays || numRays <= 0) return set_error(NTR_ERR_INVALID, "ntr_selftest_ray_class: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned int* d_m = nullptr;
+    NTR_HIP(hipMalloc((void**)&d_m, sizeof(unsigned int)));
+    hipError_t e = hipMemsetAsync(d_m, 0, sizeof(unsigned int), s);
+    if (e == hipSuccess) e = ntr_launch_selftest_ray_class(d_rays, numRays, bvhFlags, d_m, s);
+    unsigned int m = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&m, d_m, sizeof(m), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_m);
+    if (e != hipSuccess) return hip_fail(e, "ntr_selftest_ray_class");
     *mismatches = m;
     return NTR_OK;
 }

@@ -1,10 +1,13 @@
 // selftest_kernels.hip -- device self tests of the FAST slab path's exact division (trace_arith.h): FAST == the hardware's correctly
 // rounded `/`, bit for bit.  ntr_selftest_division / ntr_selftest_division_hard in the C-ABI (tests/test_trace_gpu.py).
+// ... and of the FAST path's admission test: ray_class, the integer form the kernels run, against the rule as the float ranges state it
+// (trace_lane.h).  ntr_selftest_ray_class (tests/test_wave_setup_gpu.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "trace_kernels.h"
 #include "trace_arith.h"
+#include "trace_lane.h"
 
 namespace ntr {
 
@@ -75,7 +78,26 @@ __global__ __launch_bounds__(256) void selftest_division_hard_kernel(int xe0, in
     if (bad) atomicAdd(&counts[1], bad);
 }
 
+// mismatches += the rays on which ray_class (<= kNiceMax) and ray_is_nice disagree, for the BVH flags given (NTR_BVH_NOTINY matters)
+__global__ __launch_bounds__(256) void selftest_ray_class_kernel(const NtrRay* __restrict__ rays, int numRays, uint32_t bvhFlags,
+                                                                 unsigned int* __restrict__ mismatches)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= numRays) return;
+    const float4 o = reinterpret_cast<const float4*>(rays)[i * 2 + 0], d = reinterpret_cast<const float4*>(rays)[i * 2 + 1];
+    RayRegs r = {o.x, o.y, o.z, o.w, d.x, d.y, d.z, d.w, 0.0f, 0.0f, 0.0f};
+    const bool rule = ray_is_nice(r, bvhFlags);
+    const bool fast = ray_class(r, nice_zero_word(bvhFlags)) <= kNiceMax;
+    if (rule != fast) atomicAdd(mismatches, 1u);
+}
+
 }  // namespace ntr
+
+extern "C" hipError_t ntr_launch_selftest_ray_class(const NtrRay* d_rays, int numRays, uint32_t bvhFlags, unsigned int* d_mismatches, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ntr::selftest_ray_class_kernel, dim3((numRays + 255) / 256), dim3(256), 0, stream, d_rays, numRays, bvhFlags, d_mismatches);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t ntr_launch_selftest_division(const float* d_x, const float* d_d, int nx, int nd,
                                                    unsigned int* d_mismatches, hipStream_t stream)

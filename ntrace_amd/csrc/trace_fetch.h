@@ -1,6 +1,8 @@
 // trace_fetch.h -- how 64 bytes reach a lane of the BVH traversal kernels (trace_kernels.hip): buffer loads through wave-uniform resource
 // descriptors, the masked two-buffer fetch, and the unified-step loop's one fetch per lane and iteration (flat or through descriptors).
 // A node is 64 bytes and so is a Woop triangle with the word that follows it (compact_bvh.h): one fetch serves either.
+// The fetch's wave-uniform operands (UnifiedBufs) are derived from the launch's arguments: by the host, once, for the per-ray bodies
+// (TraceConsts; unified_bufs<TRIM = true> copies), per wave in the persistent kernels (unified_bufs<false>, the same arithmetic).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,6 +105,7 @@ struct UnifiedBufs {
     unsigned int limNode;   // largest inner-node offset whose 64 bytes lie inside the node buffer (below the sentinel: `node <= limNode` implies inner)
     int limTri;             // smallest (most negative) triangle cursor ~index whose 64 bytes lie inside triWoop
     unsigned int oddBase, oddSpan;   // limNode < (unsigned)node < (unsigned)limTri, as node - oddBase < oddSpan: neither of the two (the sentinel included)
+    unsigned int descentLim;         // TRIM bodies: TraceConsts::descentLim (the persistent kernels' prologue forms its own)
 };
 template <bool TRIM = false>   // TRIM: the bodies whose fetch asks for its end-of-buffer lanes with one range test (unified_fetch<.., TRIM>)
 __device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
@@ -110,6 +113,16 @@ __device__ __forceinline__ UnifiedBufs unified_bufs(const TraceParams& p)
     UnifiedBufs u;
     u.nodes = (const char*)p.nodes; u.woop = (const char*)p.woop;
     u.nodesBytes = p.nodesBytes; u.woopBytes = p.woopBytes;
+    if (TRIM) {   // the per-ray bodies: the host's values (TraceParams::k), copied
+        const TraceConsts& k = p.k;
+        u.rNodes = u32x4{k.rNodes[0], k.rNodes[1], k.rNodes[2], k.rNodes[3]}; u.rWoop = u32x4{k.rWoop[0], k.rWoop[1], k.rWoop[2], k.rWoop[3]};
+        u.uniformPrologue = (k.switches & NTR_K_PROLOGUE) != 0u;
+        u.certainSteps = (k.switches & NTR_K_CERTAIN) != 0u;
+        u.certainDescent = k.descentLim != 0u;
+        u.base = k.base; u.dN = k.dN; u.dW = k.dW; u.limNode = k.limNode; u.limTri = k.limTri;
+        u.oddBase = k.oddBase; u.oddSpan = k.oddSpan; u.descentLim = k.descentLim;
+        return u;
+    }
     u.rNodes = rsrc_words(p.nodes, p.nodesBytes); u.rWoop = rsrc_words(p.woop, p.woopBytes);
     u.uniformPrologue = p.uniformPrologue != 0;
     u.certainSteps = p.certainSteps != 0 && (p.bvhFlags & NTR_BVH_ORDERED) != 0;

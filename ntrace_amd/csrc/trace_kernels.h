@@ -1,4 +1,5 @@
-// trace_kernels.h -- launch contract between ntr_api.cpp and trace_kernels.hip.
+// trace_kernels.h -- launch contract between ntr_api.cpp and trace_kernels.hip: the launch's arguments (TraceParams) and what the host
+// derives from them once per launch for the per-ray bodies (TraceConsts).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,6 +42,25 @@
 
 
 namespace ntr {
+
+// What a wave of the per-ray bodies would otherwise derive from the launch's arguments before its first step: the same in every wave of a
+// launch, so the host forms it once (trace_fill_consts, ntr_api.cpp: the one place that holds the arithmetic; called from bind_trace for
+// both sides) and unified_bufs<TRIM = true> and the prologue only copy.  The persistent kernels derive their own (no scalar register to give).
+#define NTR_K_FAST 1u          // NTR_BVH_FASTDIV: a wave of nice rays may run the FAST slab test
+#define NTR_K_ZERO_ORIGIN 2u   // NTR_BVH_NOTINY: a zero origin component is nice
+#define NTR_K_OCTANT 4u        // octant && NTR_BVH_ORDERED: the octant vote is allowed
+#define NTR_K_CERTAIN 8u       // certainSteps && NTR_BVH_ORDERED
+#define NTR_K_PROLOGUE 16u     // uniformPrologue && the node buffer is 64-byte aligned (s_load_dwordx16)
+struct TraceConsts {
+    const char* base;            // the lower of nodes / woop (flat fetch)
+    uint32_t dN, dW;             // nodes - base, woop - base
+    uint32_t limNode;            // largest inner-node offset whose 64 bytes lie inside the node buffer
+    int32_t limTri;              // smallest triangle cursor whose 64 bytes lie inside triWoop
+    uint32_t oddBase, oddSpan;   // node - oddBase < oddSpan: neither of the two
+    uint32_t rNodes[4], rWoop[4];   // the two buffer descriptors' words
+    uint32_t descentLim;         // carried certain descent: a child word c is the wave's next scalar node when 1 <= c <= descentLim (0 = off)
+    uint32_t switches;           // NTR_K_*
+};
 
 struct TraceParams {
     int32_t numRays;
@@ -87,6 +107,7 @@ struct TraceParams {
     int32_t routeSkip;          // batch routing by the device's coherence word (*poolK; ntr_api.cpp launches BOTH bodies for such a batch): 0 = none,
                                 // NTR_ROUTE_SKIP_COHERENT = this launch leaves at once when the word says coherent (the persistent bodies),
                                 // NTR_ROUTE_SKIP_INCOHERENT = ... when it says incoherent (the per-ray body)
+    TraceConsts k;              // derived from the fields above: trace_fill_consts
 };
 
 }  // namespace ntr
@@ -125,3 +146,4 @@ extern "C" hipError_t ntr_launch_identity_order(unsigned int* d_order, int numBl
 extern "C" hipError_t ntr_launch_selftest_division(const float* d_x, const float* d_d, int nx, int nd,
                                                    unsigned int* d_mismatches, hipStream_t stream);
 extern "C" hipError_t ntr_launch_selftest_division_hard(int xe0, int de0, unsigned long long* d_counts, hipStream_t stream);
+extern "C" hipError_t ntr_launch_selftest_ray_class(const NtrRay* d_rays, int numRays, uint32_t bvhFlags, unsigned int* d_mismatches, hipStream_t stream);

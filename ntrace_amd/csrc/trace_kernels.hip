@@ -26,6 +26,15 @@
 // The traversal stack lives in LDS ([entry][lane], conflict-free), spilling to scratch
 // beyond LDS_DEPTH.  No MFMA: there is no dense contraction on this path.
 //
+// WHAT IS COMPUTED WHERE.  Everything that is a function of the launch's arguments alone -- the flat fetch's base and offsets, the limits of
+// the end-of-buffer tests, the two descriptors, the descent limit and the combined switches -- is formed once on the host (TraceConsts,
+// trace_kernels.h; trace_fill_consts, ntr_api.cpp) and copied by the per-ray bodies (unified_bufs<TRIM>, the prologue's HOSTK form); the
+// persistent kernels derive their own.  Per wave: a fresh wave of perray_body votes with ballots of compares that have no other use,
+// masked by its live lanes on the scalar side -- on the FAST path with ray_class (the rule's ranges as integer arithmetic, trace_lane.h), on
+// the octant with three sign ballots, and on the triangle step with wave_may_quirk: a wave without tmax = +inf runs the loop instances
+// whose triangle_step<QUIRK = false> writes nothing on a miss, a wave with it the general FAST (or GENERIC) loop in the reference's form.
+// minipool_body takes the last vote again after every refill; its refills and the persistent kernels' ask ray_is_nice per ray.
+//
 // SCHEDULING (never a ray's own visiting order, hence never a hit record or a counter):
 //   * a wave leaves its inner-node loop early when few lanes still hold an inner node (leafSwitchBelow);
 //   * trace_bvh_perray maps workgroup i to ray block order[i] when an order is given -- predicted
@@ -98,12 +107,13 @@ __device__ __forceinline__ void traverse(Rsrc nodes, Rsrc woop, RayRegs& r, int&
 // TRIM (the per-ray bodies): the loop's upkeep in its cheaper forms -- the fetch's end-of-buffer test (unified_fetch<.., TRIM>), the fetched
 // rows kept as the tuples the loads wrote (keep_row) and the straight-line pop (stack_pop_flat).  Same steps, same stack content.  The
 // persistent kernels keep the earlier forms: they have no scalar register to give (EXPERIMENTS.md).
-template <bool FAST, bool FLAT, int OCT = 8, bool PROLOGUE = false, bool SLICED = false, bool TRIM = false>
+// QUIRK = false (the per-ray bodies, a wave without tmax = +inf): triangle_step's form in which a miss writes nothing (trace_lane.h).
+template <bool FAST, bool FLAT, int OCT = 8, bool PROLOGUE = false, bool SLICED = false, bool TRIM = false, bool QUIRK = true>
 __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs& r, int& node, LaneStack& st,
                                                  int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
                                                  unsigned int* status, bool poolEmpty, int fetchThreshold, int* slice = nullptr)
 {
-    if (PROLOGUE && ub.uniformPrologue) uniform_prologue<FAST, OCT, true>(ub, r, node, st, spill, status);   // (PROLOGUE: the per-ray kernels)
+    if (PROLOGUE && ub.uniformPrologue) uniform_prologue<FAST, OCT, true, TRIM>(ub, r, node, st, spill, status);   // (PROLOGUE: the per-ray kernels)
     for (;;) {
         const unsigned long long live = __ballot(node != kSentinel);
         if (live == 0ull) break;
@@ -114,10 +124,11 @@ __device__ __forceinline__ void traverse_unified(const UnifiedBufs& ub, RayRegs&
         unified_fetch<FLAT, TRIM>(ub, node, live, a, b, c, d);
         if (FLAT && TRIM) { keep_row(a); keep_row(b); keep_row(c); keep_row(d); }
         else if (FLAT) { keep(a); keep(b); keep(c); keep(d); }
-        unified_advance<FAST, OCT, LDS_DEPTH, TRIM>(a, b, c, d, r, node, st, spill, anyHit, hitAddr, hitU, hitV, status);
+        unified_advance<FAST, OCT, LDS_DEPTH, TRIM, QUIRK>(a, b, c, d, r, node, st, spill, anyHit, hitAddr, hitU, hitV, status);
     }
 }
 // A lane of a ray pool (the persistent kernels' refill, minipool_body) starts ray rayIdx at the root.  Returns whether the ray qualifies for the FAST path.
+// (the rule in its float form: ray_class, the fresh waves' form, costs the persistent kernels two or three VGPRs and the mini kernel its 60th)
 __device__ __forceinline__ bool start_ray(const TraceParams& p, int rayIdx, RayRegs& r, int& node, LaneStack& st,
                                           int& hitAddr, float& hitU, float& hitV)
 {
@@ -175,37 +186,50 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
     const int rayIdx = block * 256 + part * (WAVES * 64) + threadIdx.x;
     const bool valid = rayIdx < p.numRays;
     const Rsrc nodes = make_rsrc(p.nodes, p.nodesBytes), woop = make_rsrc(p.woop, p.woopBytes);
+    // The launch's scalars and the lane's stack stand in front of the ray's loads.  (Measured, not reasoned: with the loads issued first and
+    // the scalars behind them, as the loads' latency suggests, the AO launches are 0.5 % slower, and with the scalars formed where the loops
+    // are entered the frame gains nothing from the trims below: EXPERIMENTS.md, wave set-up.)
+    UnifiedBufs ub;
+    if (UNIFIED) ub = unified_bufs<true>(p);
 
     unsigned long long tl0 = 0;
     if (p.cost) tl0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz; scheduling feedback
 
-    RayRegs r;
-    load_ray(p.rays, valid ? rayIdx : 0, r);
     LaneStack st;
     int spill[SPILL_DEPTH];
     st.lds = (lds_int*)&s_stack[wave][0][lane];
     stack_reset(st);
+    RayRegs r;
+    load_ray(p.rays, valid ? rayIdx : 0, r);
 
     int hitAddr = -1;
     float hitU = 0.0f, hitV = 0.0f;
     // No triangle can be accepted unless tmin < tmax (t>tmin && t<tmax), so a
     // degenerate ray (Ray::degenerate, Util.hpp:65) is a miss without traversal.
-    int node = (valid && r.tmin < r.tmax) ? 0 : kSentinel;
+    const bool live = valid && r.tmin < r.tmax;
+    int node = live ? 0 : kSentinel;
     LaneStats ls = {0u, 0u, 0u};
+    // the wave's live lanes, once: the votes below are ballots of compares that have no other use, masked on the scalar side (of a predicate
+    // that also steers lanes hipcc makes a 0 / 1 VGPR and a second compare), so a dead lane -- a degenerate ray, an index past numRays -- has no say
+    const unsigned long long liveMask = __builtin_amdgcn_ballot_w64(live);
 
-    const bool fastWave = (p.bvhFlags & NTR_BVH_FASTDIV) && __ballot(node != kSentinel && !ray_is_nice(r, p.bvhFlags)) == 0ull;
+    // the launch's switches as the host combined them (TraceConsts)
+    const bool fastAllowed = (p.k.switches & NTR_K_FAST) != 0u, octantAllowed = (p.k.switches & NTR_K_OCTANT) != 0u;
+    const unsigned int zeroWord = (p.k.switches & NTR_K_ZERO_ORIGIN) ? kPosZero : (kPosZero | 1u);
+    const bool fastWave = fastAllowed && (liveMask & __builtin_amdgcn_ballot_w64(ray_class(r, zeroWord) > kNiceMax)) == 0ull;
     // direction signs shared by every live ray of the wave (a primary wave is an 8 x 8 pixel tile): the octant's own slab test
-    int oct = 8;
-    if (UNIFIED && fastWave && p.octant && (p.bvhFlags & NTR_BVH_ORDERED)) {
-        const unsigned long long liveMask = __ballot(node != kSentinel);
-        const unsigned long long sx = __ballot(node != kSentinel && r.dx < 0.0f), sy = __ballot(node != kSentinel && r.dy < 0.0f),
-                                 sz = __ballot(node != kSentinel && r.dz < 0.0f);
+    // (a wave that holds tmax = +inf keeps the general FAST loop, whose triangle step records the reference's missed test: triangle_step)
+    int oct = wave_may_quirk(r) ? 9 : 8;   // 9: the general FAST loop with the reference's triangle step, no octant vote
+    // Three sign ballots of compares that have no other use, masked by the live lanes on the scalar side; nothing of it runs unless the wave is
+    // FAST and the launch allows the vote.
+    if (UNIFIED && fastWave && __builtin_expect(oct == 8, 1) && octantAllowed) {
+        const unsigned long long sx = liveMask & __builtin_amdgcn_ballot_w64(r.dx < 0.0f), sy = liveMask & __builtin_amdgcn_ballot_w64(r.dy < 0.0f),
+                                 sz = liveMask & __builtin_amdgcn_ballot_w64(r.dz < 0.0f);
         if ((sx == 0ull || sx == liveMask) && (sy == 0ull || sy == liveMask) && (sz == 0ull || sz == liveMask))
             oct = (sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0);
     }
     if (UNIFIED) {
-        const UnifiedBufs ub = unified_bufs<true>(p);
-#define NTR_UNIFIED_OCT(O) traverse_unified<true, FLATF, O, true, false, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0)
+#define NTR_UNIFIED_OCT(O) traverse_unified<true, FLATF, O, true, false, true, false>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0)
         if (oct < 8) {
             switch (oct) {
                 case 0: NTR_UNIFIED_OCT(0); break;
@@ -219,6 +243,7 @@ __device__ __forceinline__ void perray_body(const TraceParams& p)
             }
         }
 #undef NTR_UNIFIED_OCT
+        else if (__builtin_expect(fastWave && oct == 8, 1)) traverse_unified<true, FLATF, 8, true, false, true, false>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
         else if (fastWave) traverse_unified<true, FLATF, 8, true, false, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
         else traverse_unified<false, FLATF, 8, true, false, true>(ub, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, p.status, true, 0);
     } else if (fastWave) traverse<true, STATS, false>(nodes, woop, r, node, st, spill, p.anyHit != 0, hitAddr, hitU, hitV, ls, p.status, true, 0, p.leafSwitchBelow);
@@ -551,7 +576,8 @@ __device__ __forceinline__ void minipool_body(const TraceParams& p, unsigned int
         const bool poolEmpty = poolNext >= poolEnd && chunk + 1u >= chunkEnd;
         // ---- unified-step traversal until every lane is done, or (rays left in the pool) until enough lanes are free to be worth a refill --
         const bool fastWave = bvhFast && __ballot(node != kSentinel && !nice) == 0ull;
-        if (fastWave) traverse_unified<true, FLATF, 8, false, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
+        if (fastWave && !wave_may_quirk(r)) traverse_unified<true, FLATF, 8, false, false, true, false>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
+        else if (fastWave) traverse_unified<true, FLATF, 8, false, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
         else traverse_unified<false, FLATF, 8, false, false, true>(ub, r, node, st, spill, anyHit, hitAddr, hitU, hitV, p.status, poolEmpty, p.fetchThreshold);
         // ---- retire finished rays -------------------------------------------------------------------------------------------------
         if (rayIdx >= 0 && node == kSentinel) {

@@ -28,6 +28,10 @@
 //            No NaN/inf can arise in the range either, so v_min3/v_max3 equal the select-form
 //            folds up to the sign of zero, which no later comparison can observe.
 //   ntr_selftest_division() / ntr_selftest_division_hard() check FAST == GENERIC bit for bit on the device.
+// Who may take FAST is stated twice: ray_is_nice, the rule in float compares (the pools' refills, the wide and instanced traces), and
+// ray_class, the same ranges as integer arithmetic on the words with one compare at the end (a fresh wave's vote in perray_body);
+// ntr_selftest_ray_class holds the second against the first.  triangle_step<QUIRK> likewise has the reference's form and, for waves in
+// which no lane holds tmax = +inf (wave_may_quirk), the form in which a miss writes nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,11 +70,36 @@ __device__ __forceinline__ bool nice_pos(float v, bool zeroOk)
     const float a = fabsf(v);
     return (a >= 0x1p-36f && a < 0x1p55f) || (zeroOk && v == 0.0f);
 }
+// THE RULE, as the ranges above state it: what the pools' refills ask per ray (start_ray), and what the device self test
+// ntr_selftest_ray_class holds ray_class against.
 __device__ __forceinline__ bool ray_is_nice(const RayRegs& r, uint32_t bvhFlags)
 {
     const bool zeroOk = (bvhFlags & NTR_BVH_NOTINY) != 0;
     return nice_dir(r.dx) && nice_dir(r.dy) && nice_dir(r.dz) && nice_pos(r.ox, zeroOk) && nice_pos(r.oy, zeroOk) &&
            nice_pos(r.oz, zeroOk);
+}
+// What a fresh wave of the per-ray kernels votes with (perray_body): the rule as integer arithmetic on the six words, straight-line, one number per ray.  As floats the twelve range
+// compares fold through five exec-mask levels, ~62 instructions of every wave's set-up; here it is 17 VALU and the wave's vote is ONE
+// compare whose only use is the ballot (EXPERIMENTS.md).
+// Non-negative floats order like their bit patterns, so with s = word << 1 (the sign shifted out; s is even) a magnitude range [lo, hi] is
+// s - 2 lo <= 2 (hi - lo) in unsigned arithmetic: below the range the difference wraps to at least 2^32 - 2 lo, which is above every
+// bound used here; infinities and NaN (s >= 0xFF000000) land above the bounds as well, denormals and zeros (s < 2^24) below the range.
+//   direction  2^-40 <= |d| <= 2^20:  wd = s - 0x57000000 <= 0x3C000000    (both ends included)
+//   position   2^-36 <= |o| <  2^55:  wp = s - 0x5B000000 <= 0x5AFFFFFE    (2^55 itself, wp = 0x5B000000, excluded: wp is even)
+//   +0 / -0 position (s = 0, wp = kPosZero) passes under NTR_BVH_NOTINY only: wp == zeroWord ? 0 : wp, where zeroWord is kPosZero with the
+//   flag and the odd kPosZero | 1, which no wp equals, without it.
+// The class is the largest of the three wp and of the largest wd moved up by kDirPad = 0x5AFFFFFE - 0x3C000000 with a SATURATING add (a
+// wrapped wd stays large): nice <=> class <= kNiceMax, for every bit pattern of every component.
+static constexpr unsigned int kDirLo2 = 0x57000000u, kDirSpan2 = 0x3C000000u, kPosLo2 = 0x5B000000u, kNiceMax = 0x5AFFFFFEu;
+static constexpr unsigned int kDirPad = kNiceMax - kDirSpan2, kPosZero = 0u - kPosLo2;
+__device__ __forceinline__ unsigned int nice_zero_word(uint32_t bvhFlags) { return (bvhFlags & NTR_BVH_NOTINY) ? kPosZero : (kPosZero | 1u); }
+__device__ __forceinline__ unsigned int ray_class(const RayRegs& r, unsigned int zeroWord)
+{
+    const unsigned int dx = (__float_as_uint(r.dx) << 1) - kDirLo2, dy = (__float_as_uint(r.dy) << 1) - kDirLo2, dz = (__float_as_uint(r.dz) << 1) - kDirLo2;
+    unsigned int px = (__float_as_uint(r.ox) << 1) - kPosLo2, py = (__float_as_uint(r.oy) << 1) - kPosLo2, pz = (__float_as_uint(r.oz) << 1) - kPosLo2;
+    px = px == zeroWord ? 0u : px; py = py == zeroWord ? 0u : py; pz = pz == zeroWord ? 0u : pz;
+    const unsigned int d = max(max(dx, dy), dz), p = max(max(px, py), pz);
+    return max(p, __builtin_elementwise_add_sat(d, kDirPad));
 }
 // Intersect::RayBox for BOTH children of a node (Util.cpp:34-46).  The FAST form evaluates
 // the twelve quotients stage by stage (all q0, then all e1, ...) so that consecutive
@@ -260,11 +289,33 @@ __device__ __forceinline__ void inner_step(Rsrc nodes, bool inner, const RayRegs
 
 // One triangle of a leaf: Intersect::RayTriangleWoop (Util.cpp:99-127) on its rows z, u4, v4 and updateHit (CudaBVH.cpp:1183-1225).
 // Returns true when the hit is accepted: r.tmax, hitU and hitV are then its, and the caller records the triangle's row.
+// The reference returns (t, u, v) for an accepted test and (FW_F32_MAX, 0, 0) for a missed one, and updateHit re-tests the returned t against
+// (tmin, tmax) (CudaBVH.cpp:1200).  What that comes to, for every input:
+//   accepted test: the returned t already passed t > tmin && t < tmax, so the re-test holds and the record is (t, u, v);
+//   missed test:   the re-test is FLT_MAX > tmin && FLT_MAX < tmax.  FLT_MAX is the largest finite float, so the second half holds for
+//                  tmax = +inf alone (a NaN on either side fails its compare): the missed test is then RECORDED at t = FLT_MAX, u = v = 0
+//                  (the reference's quirk); for every other tmax nothing is recorded and ray and hit stay as they are.
+// QUIRK = true states that as the reference does -- the miss values materialised, merged at the three exits and re-tested -- and is right for
+// every ray.  QUIRK = false (the per-ray bodies, for a wave in which NO lane holds tmax = +inf: wave_may_quirk below) is the same function on
+// those rays with the second case gone: a miss writes nothing, the accepted test writes its three values where it is accepted.  tmax only
+// shrinks during a traversal (an accepted t is < tmax), so a wave that starts without +inf stays without.
+template <bool QUIRK = true>
 __device__ __forceinline__ bool triangle_step(const float4& z, const float4& u4, const float4& v4, RayRegs& r, float& hitU, float& hitV)
 {
     const float Oz = z.w - r.ox * z.x - r.oy * z.y - r.oz * z.z;
     const float ooDz = 1.0f / dot4(z, r.dx, r.dy, r.dz, 0.0f);
     const float t = Oz * ooDz;
+    if (!QUIRK) {
+        bool hit = false;
+        if (t > r.tmin && t < r.tmax) {
+            const float u = dot4(u4, r.ox, r.oy, r.oz, 1.0f) + t * dot4(u4, r.dx, r.dy, r.dz, 0.0f);
+            if (u >= 0.0f) {
+                const float v = dot4(v4, r.ox, r.oy, r.oz, 1.0f) + t * dot4(v4, r.dx, r.dy, r.dz, 0.0f);
+                if (v >= 0.0f && (u + v) <= 1.0f) { r.tmax = t; hitU = u; hitV = v; hit = true; }
+            }
+        }
+        return hit;
+    }
     float tt = FLT_MAX, uu = 0.0f, vv = 0.0f;  // miss -> bary[2] = FW_F32_MAX
     if (t > r.tmin && t < r.tmax) {
         const float u = dot4(u4, r.ox, r.oy, r.oz, 1.0f) + t * dot4(u4, r.dx, r.dy, r.dz, 0.0f);
@@ -279,6 +330,9 @@ __device__ __forceinline__ bool triangle_step(const float4& z, const float4& u4,
     if (hit) { r.tmax = tt; hitU = uu; hitV = vv; }
     return hit;
 }
+// Whether some lane of the wave holds tmax = +inf (the one value at which a missed test is recorded): such a wave runs the QUIRK = true loop.
+// Every lane votes, whatever it holds -- a finished or unused lane can only make the answer the careful one.
+__device__ __forceinline__ bool wave_may_quirk(const RayRegs& r) { return __builtin_amdgcn_ballot_w64(!(r.tmax <= FLT_MAX)) != 0ull; }
 
 // intersectTriangles<BVHLayout_Compact> + updateHit (CudaBVH.cpp:1084-1126, 1183-1225).
 // Returns true when an any-hit ray terminates.
@@ -312,8 +366,8 @@ __device__ __forceinline__ bool leaf_step(Rsrc woop, RayRegs& r, int leaf, bool 
 }
 
 // unified_advance: the lane's ray takes the step its 64 bytes allow -- one inner node (trace<BVHLayout_Compact>, CudaBVH.cpp:721-775) or one
-// triangle (intersectTriangles + updateHit, CudaBVH.cpp:1084-1126, 1183-1225).  TRIM: the per-ray bodies' pop (stack_pop_flat).
-template <bool FAST, int OCT, int LD = LDS_DEPTH, bool TRIM = false>
+// triangle (intersectTriangles + updateHit, CudaBVH.cpp:1084-1126, 1183-1225).  TRIM: the per-ray bodies' pop (stack_pop_flat).  QUIRK: triangle_step's.
+template <bool FAST, int OCT, int LD = LDS_DEPTH, bool TRIM = false, bool QUIRK = true>
 __device__ __forceinline__ void unified_advance(const float4& a, const float4& b, const float4& c, const float4& d, RayRegs& r, int& node,
                                                 LaneStack& st, int (&spill)[SPILL_DEPTH], bool anyHit, int& hitAddr, float& hitU, float& hitV,
                                                 unsigned int* status)
@@ -326,7 +380,7 @@ __device__ __forceinline__ void unified_advance(const float4& a, const float4& b
         bool leafDone = __float_as_uint(a.x) == kLeafTerm;   // terminator: an empty leaf
         if (!leafDone) {
             bool terminated = false;
-            if (triangle_step(a, b, c, r, hitU, hitV)) {
+            if (triangle_step<QUIRK>(a, b, c, r, hitU, hitV)) {
                 hitAddr = leaf_row(node);
                 terminated = anyHit;
             }

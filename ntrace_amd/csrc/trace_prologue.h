@@ -1,5 +1,7 @@
 // trace_prologue.h -- the wave-uniform prologue of the BVH traversal kernels (trace_kernels.hip): the top of the tree through the scalar
 // cache while every live lane of a wave holds the same inner node, and the certain steps that skip the exact slab test there.
+// Its preconditions (the node buffer's 64-byte alignment, certainSteps with NTR_BVH_ORDERED) and the descent limit reach the per-ray bodies
+// combined by the host (HOSTK: TraceConsts::switches, descentLim); the persistent kernels' fresh waves check and form them here.
 #pragma once
 #include "trace_lane.h"
 
@@ -169,11 +171,12 @@ __device__ __forceinline__ void take_children(int& node, int c0, int c1, unsigne
         : [m0] "s"(m0), [m1] "s"(m1), [c0] "s"(c0), [c1] "s"(c1));
 }
 
-template <bool FAST, int OCT, bool CERTAIN = false>
+// HOSTK (the per-ray bodies): the preconditions come checked and the descent limit formed by the host (TraceConsts).
+template <bool FAST, int OCT, bool CERTAIN = false, bool HOSTK = false>
 __device__ __forceinline__ void uniform_prologue(const UnifiedBufs& ub, const RayRegs& r, int& node, LaneStack& st, int (&spill)[SPILL_DEPTH],
                                                  unsigned int* status)
 {
-    if ((reinterpret_cast<unsigned long long>(ub.nodes) & (unsigned long long)(kNodeBytes - 1)) != 0ull) return;   // (s_load_dwordx16 wants the record 64-byte aligned)
+    if (!HOSTK && (reinterpret_cast<unsigned long long>(ub.nodes) & (unsigned long long)(kNodeBytes - 1)) != 0ull) return;   // (s_load_dwordx16 wants the record 64-byte aligned; HOSTK: part of ub.uniformPrologue)
     // certain steps: wave-uniform preconditions, checked once (FAST is the caller's fastWave)
     bool tryCertain = false;
     int uncertain = 0;
@@ -189,15 +192,15 @@ __device__ __forceinline__ void uniform_prologue(const UnifiedBufs& ub, const Ra
     }
     // carried certain descent: a child word c is the wave's next scalar node when 1 <= c <= descentLim -- an inner node whose 64 bytes lie
     // inside the buffer (the test of the loop top below; 0, the root, is no child of a well-formed tree and goes through the lanes); 0 = off
-    unsigned int descentLim = !ub.certainDescent ? 0u : ub.nodesBytes - (unsigned)kNodeBytes < (unsigned)kSentinel ? ub.nodesBytes - (unsigned)kNodeBytes : (unsigned)kSentinel - 1u;
-    asm volatile("" : "+s"(descentLim));   // (one number to compare with: left to see through it, the compiler tests the switch again on every step)
+    unsigned int descentLim = HOSTK ? ub.descentLim : !ub.certainDescent ? 0u : ub.nodesBytes - (unsigned)kNodeBytes < (unsigned)kSentinel ? ub.nodesBytes - (unsigned)kNodeBytes : (unsigned)kSentinel - 1u;
+    if (!HOSTK) asm volatile("" : "+s"(descentLim));   // (one number to compare with: left to see through it, the compiler tests the switch again on every step)
     for (;;) {
         const bool live = node != kSentinel;
         const unsigned long long liveMask = __ballot(live);
         if (liveMask == 0ull) return;
         const int unode = __builtin_amdgcn_readlane(node, (int)__builtin_ctzll(liveMask));   // the first live lane's node: a scalar
         if (__ballot(live && node != unode) != 0ull) return;                                  // the lanes disagree: the general loop from here on
-        if ((unsigned)unode >= (unsigned)kSentinel || (unsigned)unode > ub.nodesBytes - (unsigned)kNodeBytes) return;   // a leaf (or a malformed offset): likewise
+        if ((unsigned)unode >= (unsigned)kSentinel || (unsigned)unode > (HOSTK ? ub.limNode : ub.nodesBytes - (unsigned)kNodeBytes)) return;   // a leaf (or a malformed offset): likewise
         unsigned int snode = (unsigned)unode;   // the wave's node while it is a scalar (carried certain descent)
         f32x4 A, B, C, D;
         if (CERTAIN && FAST && tryCertain) {
