@@ -1020,6 +1020,80 @@ NTR_API int ntr_trace_wide_stats(int32_t numRays, int32_t anyHit, const NtrRay* 
                                  int64_t wideNodesBytes, const void* d_triWoop, int64_t triWoopBytes, const int32_t* d_triIndex,
                                  uint32_t bvhFlags, void* stream, NtrTraceStats* stats);
 
+/* Two-level trace over 4-wide trees: the pool and the top-level tree of an instanced scene widened, and the trace that walks them
+ * (csrc/instanced_widen_kernels.hip, csrc/trace_instanced_wide_kernels.hip, csrc/instanced_wide_bvh.h).  EXTENSION without a
+ * reference counterpart: the rule is the numpy spec tests/np_instanced_wide.py, which ntr_pool_widen and ntr_tlas_widen equal byte for
+ * byte and ntr_trace_instanced_wide in all four result words, the instance id and every counter.  The binary pool, top-level tree and
+ * records are only read and stay usable; the pool's triWoop and triIndex serve both paths.
+ *   wide pool   one more node buffer: wide BLAS k is byte for byte what ntr_bvh_widen writes for binary BLAS k when handed
+ *               pool + nodesOffset_k, placed at the sum of the exact wide extents of the BLASes before it (multiples of 128, no gaps);
+ *               links stay relative to the BLAS's own start.  At most 0xFFFFFF00 bytes
+ *   wide TLAS   ntr_bvh_widen applied to the top-level node buffer; leaf links ~i pass through verbatim.  N == 1: no node, rootLink ~0
+ *   record i    64 bytes: words 0..11 worldToObject, 12 the wide BLAS's offset in the wide pool, 13 triWoopOffset / 16, 14 the wide
+ *               BLAS's extent, 15 zero.  An instance whose blas index lies outside [0, numBlas) gets offset and extent 0: a wide node
+ *               inside an instance is fetched only below the extent, so nothing of such an instance is ever read
+ *   trace       ntr_trace_instanced_masked's rule with both inner steps replaced by ntr_trace_wide's wide-node step (four slab tests; a
+ *               candidate iff its link is non-zero and mn <= mx && mx >= tmin && mn <= tmax; ascending (mn, slot), the others pushed
+ *               farthest first).  Entering, masks, the exit marker, triangles, any hit, the miss record, degenerate rays and the 16 + 88
+ *               stack are unchanged.  GENERIC arithmetic only; every fetch is range checked
+ *   bytes       52 numRays + 112 (numTopInnerVisits + numInnerVisits) + 64 numInstanceEntries + 32 numInstanceEntries + 48 numTriTests
+ *               + 16 numLeafVisits + 4 numHits, plus the two mask terms of ntr_trace_instanced_stats (112: a wide node's seven fetched rows)
+ * KNOWN LIMIT, ntr_trace_wide's: the records may differ from the binary two-level trace's on the same scene.  The spec is the definition.
+ * ntr_pool_widen_capacity: host only; the sum of ntr_bvh_widen_capacity over the ranges (a bound, not the extent).
+ * ntr_pool_widen: a loop of ntr_bvh_widen, one BLAS after the other (a batched pass is future work: the loop pays the pass's launches
+ *   and read-backs per BLAS).  It blocks and is refused on a capturing stream.  wideRanges[k] receives BLAS k's offset, extent, node
+ *   count and stackBound; *result the total extent (nodesBytes), the sums of numNodes, counts and numLeafLinks, the largest height and
+ *   stackBound of any BLAS, and the summed GPU time.  NTR_ERR_INVALID before any device work for numBlas < 1, null pointers, a pool size
+ *   or BLAS range that ntr_tlas_build refuses, a capacity below ntr_pool_widen_capacity, an output that overlaps the pool.
+ *   NTR_ERR_OVERFLOW: the wide pool would exceed 0xFFFFFF00 bytes.  NTR_ERR_LAYOUT, after the work, as ntr_bvh_widen reports it.
+ * ntr_tlas_widen: widens the top-level tree (skipped when rootLink < 0, the one-instance tree) and writes the wide records from
+ *   d_instances in one element-wise launch.  result->stackBound = the wide TLAS's bound + 1 (the exit marker) + the largest
+ *   wideRanges[k].stackBound: <= 104 guarantees that the trace's stack never overflows.  It blocks and is refused on a capturing
+ *   stream.  After ntr_tlas_refit or ntr_bvh_refit_batch the caller widens again: wide trees are not refitted in place.
+ *   NTR_ERR_INVALID before any device work for numInstances < 1, null or misaligned (16 B) buffers, a rootLink that is neither 0 nor an
+ *   instance's link, a top-level buffer that ntr_bvh_widen refuses, capacities below ntr_bvh_widen_capacity / 64 * numInstances, a
+ *   triWoopOffset that is no multiple of 16 inside the pool limit, a wide range that is not multiples of 128 inside the pool limit.
+ * ntr_trace_instanced_wide: ntr_trace_instanced_masked's arguments with the wide top-level tree, wide records and wide pool nodes in
+ *   place of the binary ones.  vis may be NULL; vis == NULL or a vis that can refuse nothing launches the unmasked kernel.
+ *   seconds == NULL is asynchronous on `stream` and capturable; the call allocates nothing and reads nothing back.  A wide buffer that
+ *   is not a multiple of 128 is refused with NTR_ERR_INVALID, like everything ntr_trace_instanced_masked refuses.
+ * ntr_trace_instanced_wide_stats: the same records through an instrumented variant, plus the counters (numTopInnerVisits and
+ *   numInnerVisits count wide nodes).  It blocks and is refused on a capturing stream.
+ * Without a device, after the argument checks, NTR_ERR_NO_DEVICE / NTR_ERR_HIP.  The calls hold no scratch pool of their own: the BLAS
+ *   table lives in ntr_bvh_widen's pool, which ntr_lbvh_release_workspace returns. */
+typedef struct NtrWideBlasRange {        /* host array */
+    int64_t nodesOffset, nodesBytes;     /* wide BLAS k's place in the wide pool: multiples of 128 */
+    int32_t numNodes, stackBound;        /* NtrBvhWideResult's of that BLAS */
+} NtrWideBlasRange;
+typedef struct NtrTlasWideResult {
+    int64_t nodesBytes, recordsBytes;      /* exact extents written: 128 * numNodes (0 for one instance), 64 * numInstances */
+    int32_t numNodes, counts[3];           /* wide top-level nodes; those with 2, 3 and 4 children */
+    int32_t numLeafLinks, height;          /* instance links written; wide nodes on the longest path of the top level */
+    int32_t tlasStackBound, stackBound;    /* the top level's own bound; that + 1 + the largest BLAS bound: the most entries a trace holds */
+    float   seconds;                       /* GPU time: the widening pass and the record launch */
+    int32_t pad;
+} NtrTlasWideResult;
+NTR_API int ntr_pool_widen_capacity(int32_t numBlas, const NtrBlasRange* blasRanges, int64_t* widePoolNodesBytes);
+NTR_API int ntr_pool_widen(int32_t numBlas, const NtrBlasRange* blasRanges, const void* d_poolNodes, int64_t poolNodesBytes,
+                           void* d_widePoolNodes, int64_t capacity, NtrWideBlasRange* wideRanges /* numBlas, host out */,
+                           NtrBvhWideResult* result, void* stream);
+NTR_API int ntr_tlas_widen(int32_t numInstances, const NtrInstance* d_instances, const void* d_tlasNodes, int64_t tlasNodesBytes,
+                           int32_t rootLink, int32_t numBlas, const NtrBlasRange* blasRanges, const NtrWideBlasRange* wideRanges,
+                           void* d_wideTlasNodes, int64_t capacity, void* d_wideRecords, int64_t recordsCapacity, NtrTlasWideResult* result,
+                           void* stream);
+NTR_API int ntr_trace_instanced_wide(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                     const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink, const void* d_wideRecords,
+                                     int32_t numInstances, const void* d_widePoolNodes, int64_t widePoolNodesBytes, const void* d_poolTriWoop,
+                                     int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                     const NtrInstanceVisibility* vis /* NULL: no masks */, float* seconds /* NULL: asynchronous */,
+                                     void* stream);
+NTR_API int ntr_trace_instanced_wide_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                           int32_t* d_instanceIDs, const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink,
+                                           const void* d_wideRecords, int32_t numInstances, const void* d_widePoolNodes,
+                                           int64_t widePoolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                                           const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* may be NULL */,
+                                           NtrInstancedTraceStats* stats, void* stream);
+
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by
  * the numpy spec tests/np_bvh_refit.py, not by reference lines.  It works on any Compact tree whatever built it -- ntr_sah_build

@@ -27,7 +27,9 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     tlas_scratch_bytes, trace_instanced, InstanceVisibility, InstancedTraceStats,
                     trace_instanced_masked, trace_instanced_stats, TlasRefitResult, tlas_refit, tlas_refit_scratch_bytes,
                     BlasTris, BLAS_TRIS_DTYPE, InstancedGeometry, instanced_hit_attributes, raygen_ao_normals,
-                    BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats)
+                    BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats,
+                    WideBlasRange, TlasWideResult, InstancedWideTraceStats, pool_widen_capacity, pool_widen, tlas_widen,
+                    trace_instanced_wide, trace_instanced_wide_stats)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -50,4 +52,6 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "tlas_scratch_bytes", "trace_instanced", "InstanceVisibility", "InstancedTraceStats",
            "trace_instanced_masked", "trace_instanced_stats", "TlasRefitResult", "tlas_refit", "tlas_refit_scratch_bytes",
            "BlasTris", "BLAS_TRIS_DTYPE", "InstancedGeometry", "instanced_hit_attributes", "raygen_ao_normals",
-           "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats"]
+           "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats",
+           "WideBlasRange", "TlasWideResult", "InstancedWideTraceStats", "pool_widen_capacity", "pool_widen", "tlas_widen",
+           "trace_instanced_wide", "trace_instanced_wide_stats"]

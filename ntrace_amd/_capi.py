@@ -240,6 +240,35 @@ class BvhWideResult(C.Structure):
         return {k: (list(getattr(self, k)) if k == "counts" else getattr(self, k)) for k, _ in self._fields_}
 
 
+class WideBlasRange(C.Structure):
+    """NtrWideBlasRange: wide BLAS k's place in the wide pool, its node count and its stackBound (pool_widen fills them)."""
+    _fields_ = [("nodesOffset", C.c_int64), ("nodesBytes", C.c_int64), ("numNodes", C.c_int32), ("stackBound", C.c_int32)]
+
+
+class TlasWideResult(C.Structure):
+    _fields_ = [("nodesBytes", C.c_int64), ("recordsBytes", C.c_int64), ("numNodes", C.c_int32), ("counts", C.c_int32 * 3),
+                ("numLeafLinks", C.c_int32), ("height", C.c_int32), ("tlasStackBound", C.c_int32), ("stackBound", C.c_int32),
+                ("seconds", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "counts" else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class InstancedWideTraceStats(InstancedTraceStats):
+    """NtrInstancedTraceStats of the wide two-level trace: numTopInnerVisits and numInnerVisits count wide nodes."""
+
+    def algorithmic_bytes(self, instance_masks=False, ray_masks=False):
+        """include/ntrace_amd.h, DESIGN.md 6r: as InstancedTraceStats.algorithmic_bytes, with 112 B (seven fetched rows) per wide node of
+        either level and 64 B per instance record."""
+        n = (52 * self.numRays + 112 * (self.numTopInnerVisits + self.numInnerVisits) + 64 * self.numInstanceEntries
+             + 32 * self.numInstanceEntries + 48 * self.numTriTests + 16 * self.numLeafVisits + 4 * self.numHits)
+        if instance_masks:
+            n += 4 * (self.numInstanceEntries + self.numInstancesMasked)
+        if ray_masks:
+            n += 4 * self.numRays
+        return n
+
+
 class BvhRefitResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numRows", C.c_int32), ("pad", C.c_int32), ("seconds", C.c_float)]
 
@@ -413,6 +442,13 @@ SYMBOLS = [
     ("ntr_bvh_widen_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_trace_wide", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp, C.POINTER(C.c_float)]),
     ("ntr_trace_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp, C.POINTER(TraceStats)]),
+    ("ntr_pool_widen_capacity", C.c_int, [_i32, _vp, C.POINTER(_i64)]),
+    ("ntr_pool_widen", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(BvhWideResult), _vp]),
+    ("ntr_tlas_widen", C.c_int, [_i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, C.POINTER(TlasWideResult), _vp]),
+    ("ntr_trace_instanced_wide", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                           C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                 C.POINTER(InstanceVisibility), C.POINTER(InstancedWideTraceStats), _vp]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(BvhRefitBatchResult), _vp]),
@@ -1158,6 +1194,80 @@ def trace_wide_stats(num_rays, any_hit, d_rays, d_results, d_wide_nodes, wide_no
     st = TraceStats()
     _check(lib().ntr_trace_wide_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_wide_nodes), int(wide_nodes_bytes),
                                       _vp(d_woop), int(woop_bytes), _vp(d_tri_index), int(bvh_flags), _vp(stream), C.byref(st)))
+    return st
+
+
+def _blas_ranges(ranges):
+    if isinstance(ranges, BlasPool):
+        ranges = ranges.ranges
+    return (BlasRange * max(len(ranges), 1))(*[BlasRange(*[int(x) for x in r]) for r in ranges]), len(ranges)
+
+
+def _wide_ranges(wide_ranges):
+    """a list of (nodesOffset, nodesBytes, numNodes, stackBound) -> the C array"""
+    return (WideBlasRange * max(len(wide_ranges), 1))(*[WideBlasRange(*[int(x) for x in r]) for r in wide_ranges])
+
+
+def pool_widen_capacity(ranges):
+    """ntr_pool_widen_capacity -> the bytes a wide pool for these BLAS ranges needs at most (the sum of bvh_widen_capacity)."""
+    arr, n = _blas_ranges(ranges)
+    v = _i64(0)
+    _check(lib().ntr_pool_widen_capacity(n, C.cast(arr, _vp), C.byref(v)))
+    return int(v.value)
+
+
+def pool_widen(ranges, d_pool_nodes, pool_nodes_bytes, d_wide_pool_nodes, capacity, stream=0):
+    """ntr_pool_widen: every BLAS of a pool into 4-wide nodes, BLAS k at the sum of the exact extents before it (an extension; the rule
+    is tests/np_instanced_wide.py).  ranges as for tlas_build.  -> (wide_ranges, BvhWideResult): a list of (nodesOffset, nodesBytes,
+    numNodes, stackBound) per BLAS, and the pool's totals (nodesBytes is the wide pool's extent, stackBound the largest of any BLAS)."""
+    arr, n = _blas_ranges(ranges)
+    out = (WideBlasRange * max(n, 1))()
+    res = BvhWideResult()
+    _check(lib().ntr_pool_widen(n, C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_wide_pool_nodes), int(capacity),
+                                C.cast(out, _vp), C.byref(res), _vp(stream)))
+    return [(int(w.nodesOffset), int(w.nodesBytes), int(w.numNodes), int(w.stackBound)) for w in out[:n]], res
+
+
+def tlas_widen(num_instances, d_instances, d_tlas_nodes, tlas_nodes_bytes, root_link, ranges, wide_ranges, d_wide_tlas_nodes, capacity,
+               d_wide_records, records_cap, stream=0):
+    """ntr_tlas_widen: the top-level tree into 4-wide nodes (none for one instance) and the wide instance records.  ranges as for
+    tlas_build, wide_ranges as pool_widen returned them.  -> TlasWideResult; stackBound <= 104 guarantees that
+    trace_instanced_wide's stack never overflows."""
+    arr, n = _blas_ranges(ranges)
+    warr = _wide_ranges(wide_ranges)
+    res = TlasWideResult()
+    _check(lib().ntr_tlas_widen(int(num_instances), _vp(d_instances), _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), n,
+                                C.cast(arr, _vp), C.cast(warr, _vp), _vp(d_wide_tlas_nodes), int(capacity), _vp(d_wide_records),
+                                int(records_cap), C.byref(res), _vp(stream)))
+    return res
+
+
+def trace_instanced_wide(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
+                         d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                         d_pool_tri_index, vis=None, stream=0, timed=True):
+    """ntr_trace_instanced_wide: trace_instanced_masked over 4-wide trees (tlas_widen, pool_widen); the rule is
+    tests/np_instanced_wide.py.  vis: an InstanceVisibility or None.  timed=True returns the GPU seconds; timed=False is asynchronous on
+    `stream` (capturable) and returns None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_instanced_wide(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
+                                          _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), int(root_link), _vp(d_wide_records),
+                                          int(num_instances), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes), _vp(d_pool_woop),
+                                          int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
+                                          C.byref(sec) if timed else None, _vp(stream)))
+    return float(sec.value) if timed else None
+
+
+def trace_instanced_wide_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
+                               d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                               d_pool_tri_index, vis=None, stream=0):
+    """ntr_trace_instanced_wide_stats: trace_instanced_wide's records through the instrumented kernel -> InstancedWideTraceStats
+    (numTopInnerVisits and numInnerVisits count wide nodes).  Blocks; refused on a capturing stream."""
+    st = InstancedWideTraceStats()
+    _check(lib().ntr_trace_instanced_wide_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
+                                                _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), int(root_link), _vp(d_wide_records),
+                                                int(num_instances), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes), _vp(d_pool_woop),
+                                                int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
+                                                C.byref(st), _vp(stream)))
     return st
 
 

@@ -233,6 +233,10 @@ bool wd_ranges_overlap(const void* a, int64_t an, const void* b, int64_t bn)
 }
 
 }  // namespace
+
+// instanced_wide_bvh.h: the pool and TLAS widening keep their BLAS table in this pass's pool
+int widen_scratch_reserve(size_t bytes, void** out) { return g_wdPool.reserve(bytes, out); }
+
 }  // namespace ntr
 
 using namespace ntr;

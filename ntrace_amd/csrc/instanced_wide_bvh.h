@@ -1,0 +1,36 @@
+// instanced_wide_bvh.h -- the two-level layout over 4-wide trees, stated once, for the code that widens a pool and a top-level tree
+// (instanced_widen_kernels.hip) and the kernel that traverses them (trace_instanced_wide_kernels.hip).  It joins instanced_bvh.h (pool,
+// top level, record, exit marker) and wide_bvh.h (the 128-byte node); the rule is tests/np_instanced_wide.py.
+//   wide pool   ONE more node buffer beside the pool; the pool's triWoop and triIndex are used unchanged.  Wide BLAS k is byte for byte
+//               what ntr_bvh_widen writes for binary BLAS k when handed pool + nodesOffset_k, and lies at the sum of the exact wide
+//               extents (NtrBvhWideResult::nodesBytes) of the BLASes before it: every offset is a multiple of 128, there are no gaps, and
+//               links stay relative to the BLAS's own start.  The buffer is at most kPoolMaxBytes long
+//   wide TLAS   ntr_bvh_widen applied to the top-level node buffer; leaf links ~i pass through verbatim.  N == 1: no node, rootLink ~0
+//   record i    16 words: 0..11 worldToObject, 12 the wide BLAS's offset in the wide pool, 13 triWoopOffset / 16 (as the binary record),
+//               14 the wide BLAS's extent, 15 zero.  An instance whose blas index lies outside [0, numBlas) gets offset, row offset and
+//               extent 0: a lane inside an instance fetches a wide node only below the extent, so nothing of such an instance is read
+//   marker      kExitMarker, as in instanced_bvh.h
+#pragma once
+#include <stdint.h>
+
+#include "instanced_bvh.h"
+#include "wide_bvh.h"
+
+namespace ntr {
+
+constexpr int kWideRecOffset = 12, kWideRecRowOffset = 13, kWideRecExtent = 14;
+static_assert(kPoolMaxBytes % kWideBytes == 0, "a wide pool of the largest size is a whole number of wide nodes");
+
+// bvh_widen_kernels.hip: `bytes` of the widening pass's per-device scratch pool (the pass is blocking, so between two passes the pool
+// is idle: the pool and TLAS widening keep their BLAS table there and add no pool of their own)
+int widen_scratch_reserve(size_t bytes, void** out);
+
+// A wide pool's size: a multiple of 128 in [128, kPoolMaxBytes]
+inline int check_wide_pool_bytes(const char* fn, const char* what, int64_t bytes)
+{
+    if (bytes < kWideBytes || (bytes % kWideBytes) != 0 || bytes > kPoolMaxBytes)
+        return set_error(NTR_ERR_INVALID, "%s: %s must be a multiple of 128 in [128, 0x%llx]", fn, what, (unsigned long long)kPoolMaxBytes);
+    return NTR_OK;
+}
+
+}  // namespace ntr

@@ -1,13 +1,16 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
-// and ntr_trace_instanced_masked (see the header).
+// and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen / ntr_tlas_widen / ntr_trace_instanced_wide (see the header).
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
 
 namespace FW {
 
-CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false)
+CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false),
+                                           m_widePool(false), m_wideTlas(false), m_traceWide(false)
 {
+    std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
+    std::memset(&m_wideResult, 0, sizeof(m_wideResult));
     std::memset(&m_result, 0, sizeof(m_result));
     std::memset(&m_blasResult, 0, sizeof(m_blasResult));
     std::memset(&m_refitResult, 0, sizeof(m_refitResult));
@@ -37,6 +40,7 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     const Mesh none = {0, 0};
     m_meshes.push_back(none);
     m_built = m_topology = m_blasTrisCurrent = false;
+    m_widePool = m_wideTlas = false;
     return (S32)m_ranges.size() - 1;
 }
 
@@ -51,6 +55,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     m_ranges.clear();
     m_meshes.clear();
     m_built = m_topology = m_blasTrisCurrent = false;
+    m_widePool = m_wideTlas = false;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
     m_poolTriIndex.resizeDiscard(capI);
@@ -105,6 +110,7 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
         e.pad = 0;
     }
     m_built = false;
+    m_widePool = m_wideTlas = false;             // wide trees are not refitted in place: widen() again
     const int rc = ntr_bvh_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
                                        m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
                                        (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
@@ -145,6 +151,7 @@ void CudaInstancedBVH::build(S32 radius)
     int64_t capN, capR;
     if (ntr_tlas_capacity(m_numInstances, &capN, &capR) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_built = m_topology = false;
+    m_wideTlas = false;
     m_tlasNodes.resizeDiscard(capN);
     m_records.resizeDiscard(capR);
     const int rc = ntr_tlas_build(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
@@ -159,6 +166,7 @@ void CudaInstancedBVH::refit(void)
 {
     if (!m_topology || m_numInstances < 1)
         fail("CudaInstancedBVH: no TLAS to refit: call build() first, and again after the instance count or the BLASes have changed");
+    m_wideTlas = false;
     const int rc = ntr_tlas_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
                                   m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL,
                                   m_result.nodesBytes, m_result.rootLink, m_records.getMutableCudaPtr(), m_records.getSize(), NULL,
@@ -174,6 +182,33 @@ void CudaInstancedBVH::refit(void)
     m_built = true;
 }
 
+void CudaInstancedBVH::widen(void)
+{
+    if (!m_built) fail("CudaInstancedBVH: no TLAS to widen: call build() or refit() first");
+    const int32_t numBlas = (int32_t)m_ranges.size();
+    if (!m_widePool) {
+        int64_t cap = 0;
+        if (ntr_pool_widen_capacity(numBlas, m_ranges.data(), &cap) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+        m_wideRanges.assign((size_t)numBlas, NtrWideBlasRange());
+        m_widePoolNodes.resizeDiscard(cap);
+        if (ntr_pool_widen(numBlas, m_ranges.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_widePoolNodes.getMutableCudaPtr(), cap,
+                           m_wideRanges.data(), &m_widePoolResult, NULL) != NTR_OK)
+            fail("CudaInstancedBVH: %s", ntr_last_error());
+        m_widePool = true;
+    }
+    m_wideTlas = false;
+    int64_t capT = 0;
+    if (m_result.rootLink == 0 && ntr_bvh_widen_capacity(m_result.nodesBytes, &capT) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_wideTlasNodes.resizeDiscard(capT ? capT : 128);
+    m_wideRecords.resizeDiscard((S64)m_numInstances * 64);
+    const int rc = ntr_tlas_widen(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), m_result.rootLink == 0 ? m_tlasNodes.getCudaPtr() : NULL,
+                                  m_result.nodesBytes, m_result.rootLink, numBlas, m_ranges.data(), m_wideRanges.data(),
+                                  m_result.rootLink == 0 ? m_wideTlasNodes.getMutableCudaPtr() : NULL, capT, m_wideRecords.getMutableCudaPtr(),
+                                  m_wideRecords.getSize(), &m_wideResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_wideTlas = true;
+}
+
 F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
 {
     const S32 numRays = rays.getSize();
@@ -183,7 +218,19 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     float seconds = 0.0f;
     const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
     int rc;
-    if (!masks && rayMask == 0xFFFFFFFFu) {
+    if (m_traceWide && isWide()) {
+        NtrInstanceVisibility vis;
+        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
+        vis.d_rayMasks = NULL;
+        vis.rayMask = rayMask;
+        vis.pad = 0;
+        rc = ntr_trace_instanced_wide(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
+                                      (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                      m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes, m_result.rootLink,
+                                      m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
+                                      m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis,
+                                      &seconds, NULL);
+    } else if (!masks && rayMask == 0xFFFFFFFFu) {
         rc = ntr_trace_instanced(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
                                  (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
                                  m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,

@@ -23,6 +23,13 @@
 //   traceBatch    closest hit or any hit as the RayBuffer asks; instanceIDs receives one S32 per ray (-1: a miss).  A ray enters
 //                 instance i only if (mask_i & rayMask) != 0 (ntr_trace_instanced_masked); with no masks set and the default ray mask
 //                 the call is ntr_trace_instanced's
+//   widen          valid once isBuilt(): widens the pool into a second node buffer if the pool changed since the last widen()
+//                 (ntr_pool_widen), and the TLAS and the records always (ntr_tlas_widen).  build() and refit() drop the wide TLAS;
+//                 refitBLASes, buildBLASes and addBLAS drop the wide pool too: widen again after them.  The binary pool, TLAS and
+//                 records stay what they are
+//   setTraceWide  traceBatch takes the wide path (ntr_trace_instanced_wide) when isWide() and this was set; default false, so nothing
+//                 changes for existing callers.  The records may differ from the binary path's in rays within rounding of a box
+//                 surface (the spec tests/np_instanced_wide.py states the limit)
 //   getBLASTrisBuffer  NtrBlasTris per BLAS, on the device: the meshes buildBLASes remembers, which ntr_instanced_hit_attributes needs
 //                 to turn a two-level hit's id into a pool triangle.  A BLAS that came through addBLAS has numTris 0:
 //                 its hits resolve to -1
@@ -56,6 +63,16 @@ public:
     void refit(void);
     void setInstanceMasks(const U32* masks /* getNumInstances() words; NULL: all visible */);
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask = 0xFFFFFFFFu);   // GPU seconds
+    void widen(void);
+    void setTraceWide(bool on) { m_traceWide = on; }
+    bool getTraceWide(void) const { return m_traceWide; }
+    bool isWide(void) const { return m_built && m_widePool && m_wideTlas; }      // the wide pool, TLAS and records are current
+    bool isWidePoolCurrent(void) const { return m_widePool; }
+    const NtrTlasWideResult& getWideResult(void) const { return m_wideResult; }            // of the last widen() (zero before)
+    const NtrBvhWideResult&  getWidePoolResult(void) const { return m_widePoolResult; }    // of the last pool widening (zero before)
+    Buffer& getWidePoolNodeBuffer(void) { return m_widePoolNodes; }
+    Buffer& getWideTLASNodeBuffer(void) { return m_wideTlasNodes; }
+    Buffer& getWideRecordBuffer(void) { return m_wideRecords; }
 
     Buffer& getInstanceMaskBuffer(void) { return m_instanceMasks; }              // U32 per instance; empty: all visible
     Buffer& getBLASTrisBuffer(void);                                             // NtrBlasTris per BLAS (numTris 0: an addBLAS tree)
@@ -95,6 +112,12 @@ private:
     NtrPlocBatchResult m_blasResult;
     NtrBvhRefitBatchResult m_refitResult;
     NtrTlasRefitResult m_tlasRefitResult;
+    // the wide path (widen): a second node buffer beside the pool, a wide TLAS and wide records
+    std::vector<NtrWideBlasRange> m_wideRanges;
+    Buffer        m_widePoolNodes, m_wideTlasNodes, m_wideRecords;
+    bool          m_widePool, m_wideTlas, m_traceWide;
+    NtrBvhWideResult  m_widePoolResult;
+    NtrTlasWideResult m_wideResult;
 };
 
 }  // namespace FW

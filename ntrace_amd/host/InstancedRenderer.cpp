@@ -6,7 +6,7 @@ namespace FW {
 
 InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
     : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
-      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu),
+      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false),
       m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
 {
 }
@@ -32,6 +32,17 @@ void InstancedRenderer::setRayMasks(U32 primaryMask, U32 secondaryMask)
 {
     m_primaryMask = primaryMask;
     m_secondaryMask = secondaryMask;
+}
+
+F32 InstancedRenderer::trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
+{
+    struct Restore {   // the caller's flag comes back on every path: traceBatch fails by throwing
+        CudaInstancedBVH& bvh;
+        bool was;
+        ~Restore() { bvh.setTraceWide(was); }
+    } restore = {m_bvh, m_bvh.getTraceWide()};
+    m_bvh.setTraceWide(m_wide);
+    return m_bvh.traceBatch(rays, instanceIDs, rayMask);
 }
 
 // the batch's records with pool triangle ids and, for a batch that secondary rays start from, the world-space normals
@@ -68,9 +79,10 @@ void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
         fail("InstancedRenderer: the TLAS is not current: call build() or refit() on the CudaInstancedBVH (after buildBLASes / refitBLASes and "
              "setInstances) before beginFrame");
     if (w < 1 || h < 1) fail("InstancedRenderer::beginFrame: bad frame size");
+    if (m_wide && !m_bvh.isWide()) m_bvh.widen();   // after each build() / refit() of the frame loop
     m_raygen.primary(m_primaryRays, camera.position, camera.nscreenToWorld, w, h, camera.cameraFar, 0);
     if (m_rayType != RayType_Primary) {   // Renderer.cpp:482-488
-        m_bvh.traceBatch(m_primaryRays, m_primaryIDs, m_primaryMask);
+        trace(m_primaryRays, m_primaryIDs, m_primaryMask);
         resolve(m_primaryRays, m_primaryIDs, m_primaryResolved, &m_primaryNormals);
     }
     m_cameraFar = camera.cameraFar;
@@ -114,7 +126,7 @@ F32 InstancedRenderer::traceBatch(void)
     if (!m_batchRays) fail("InstancedRenderer::traceBatch: no batch");
     const bool primary = m_batchRays == &m_primaryRays;
     Buffer& ids = primary ? m_primaryIDs : m_secondaryIDs;
-    const F32 sec = m_bvh.traceBatch(*m_batchRays, ids, primary ? m_primaryMask : m_secondaryMask);
+    const F32 sec = trace(*m_batchRays, ids, primary ? m_primaryMask : m_secondaryMask);
     resolve(*m_batchRays, ids, *m_batchResolved, primary ? &m_primaryNormals : NULL);
     return sec;
 }

@@ -7,6 +7,10 @@
 //   setRayMasks   the ray masks of CudaInstancedBVH::traceBatch: primary batches are traced with the first, AO and diffuse
 //                 batches with the second; both default to all ones.  Nothing else in the frame changes: a masked-out primary hit is a
 //                 miss, and ntr_instanced_hit_attributes resolves it as one
+//   setWide       trace every batch of the frame over the 4-wide trees (CudaInstancedBVH::widen); default false.  beginFrame
+//                 widens when the CudaInstancedBVH is not wide -- that is, after each build() / refit() of the frame loop -- and the
+//                 batches are traced with setTraceWide(true), which is put back after each trace.  Nothing else of the frame changes:
+//                 the hit attributes, the AO rays and the reconstruction read the binary geometry, which the wide path keeps
 //   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
 //                 diffuse frames the primary rays are traced and resolved at once
 //   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
@@ -31,6 +35,8 @@ public:
     void setGeometry(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos);
     void setParams(RayType rayType, F32 aoRadius, S32 numSamples);
     void setRayMasks(U32 primaryMask = 0xFFFFFFFFu, U32 secondaryMask = 0xFFFFFFFFu);
+    void setWide(bool on) { m_wide = on; }
+    bool getWide(void) const { return m_wide; }
 
     void beginFrame(const CameraView& camera, S32 w, S32 h);
     bool nextBatch(void);
@@ -47,6 +53,7 @@ public:
 
 private:
     void resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals);
+    F32  trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask);   // the CudaInstancedBVH's traceBatch, wide when setWide asked for it
     InstancedRenderer(const InstancedRenderer&);
     InstancedRenderer& operator=(const InstancedRenderer&);
 
@@ -58,6 +65,7 @@ private:
     F32        m_aoRadius;
     S32        m_numSamples;
     U32        m_primaryMask, m_secondaryMask;
+    bool       m_wide;
     RayGen     m_raygen;
     F32        m_cameraFar;
     RayBuffer  m_primaryRays, m_secondaryRays;

@@ -17,6 +17,15 @@ frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they we
                bytes and their fraction of 8 TB/s at the measured time, and three launches timed: the unmasked launch, the masked
                launch with everything visible (an instance mask array of all ones) and, for the AO batch, the masked launch with
                every second instance hidden from it (odd instances carry mask 1, even ones 3; the AO rays carry 2)
+  * wide       (not in the default parts) the two-level trace over 4-wide trees (ntr_pool_widen, ntr_tlas_widen,
+               ntr_trace_instanced_wide) beside the binary one, over the identity and the forest frame: per batch (primary
+               closest hit, host-made AO any hit) the binary launch and the wide launch ALTERNATED in this process, each timed by its own
+               stream events (median, min, max); per ray the counters of both stats calls (top-level nodes, entries, bottom-level nodes,
+               triangle tests), the algorithmic bytes over the median as a fraction of 8 TB/s, and how many records differ between the
+               two paths (the spec's known limit, reported and not asserted).  Then what widening costs: the frame's own pool and TLAS,
+               and ntr_pool_widen's loop over a pool of 1 024 BLASes of 1 000 triangles each (built by ntr_ploc_build_batch)
+  * wide_sweep (not in the default parts) the primary batch of `wide` over k x k x k grids of soup1000 for k = 1, 2, 4, 8, 16 (the last is
+               the forest), the camera moved back with the grid: where in instance count the wide path starts to pay
 Prints one JSON line per part.
 
     timeout -k 10 600 python scripts/instanced_bench.py --out instanced.json
@@ -26,6 +35,7 @@ import json
 import os
 import signal
 import sys
+import time
 
 import numpy as np
 
@@ -123,6 +133,34 @@ class Tlas:
     def stats(self, count, any_hit, d_rays, d_res, d_ids, vis):
         return nt.trace_instanced_stats(*self.args(count, any_hit, d_rays, d_res, d_ids), vis=vis, stream=self.stream)
 
+    def widen(self, reps=1):
+        """The wide pool, TLAS and records of this scene; -> (the pool's BvhWideResult runs, the TLAS's TlasWideResult runs)."""
+        b, r = self.blas, self.res
+        cap = nt.pool_widen_capacity(b.ranges)
+        self.d_wpool = torch.zeros(cap, dtype=torch.uint8, device="cuda:0")
+        tcap = nt.bvh_widen_capacity(r.nodesBytes) if r.rootLink == 0 else 0
+        self.d_wtlas = torch.zeros(max(tcap, 128), dtype=torch.uint8, device="cuda:0")
+        self.d_wrec = torch.zeros(64 * self.n, dtype=torch.uint8, device="cuda:0")
+        pools, tops = [], []
+        for _ in range(reps):
+            self.wide_ranges, p = nt.pool_widen(b.ranges, b.bufs[0].data_ptr(), b.nb, self.d_wpool.data_ptr(), cap, self.stream)
+            pools.append(p)
+            tops.append(nt.tlas_widen(self.n, self.d_inst.data_ptr(), self.d_nodes.data_ptr(), r.nodesBytes, r.rootLink, b.ranges, self.wide_ranges,
+                                      self.d_wtlas.data_ptr(), tcap, self.d_wrec.data_ptr(), 64 * self.n, self.stream))
+        self.wpool_res, self.wtlas_res = pools[-1], tops[-1]
+        return pools, tops
+
+    def wide_args(self, count, any_hit, d_rays, d_res, d_ids):
+        b, r = self.blas, self.res
+        return (count, any_hit, d_rays.data_ptr(), d_res.data_ptr(), d_ids.data_ptr(), self.d_wtlas.data_ptr(), self.wtlas_res.nodesBytes, r.rootLink,
+                self.d_wrec.data_ptr(), self.n, self.d_wpool.data_ptr(), self.wpool_res.nodesBytes, b.bufs[1].data_ptr(), b.wb, b.bufs[2].data_ptr())
+
+    def trace_wide(self, count, any_hit, d_rays, d_res, d_ids):
+        return nt.trace_instanced_wide(*self.wide_args(count, any_hit, d_rays, d_res, d_ids), stream=self.stream)
+
+    def stats_wide(self, count, any_hit, d_rays, d_res, d_ids):
+        return nt.trace_instanced_wide_stats(*self.wide_args(count, any_hit, d_rays, d_res, d_ids), stream=self.stream)
+
     def trace(self, count, any_hit, d_rays, d_res, d_ids):
         b, r = self.blas, self.res
         return nt.trace_instanced(count, any_hit, d_rays.data_ptr(), d_res.data_ptr(), d_ids.data_ptr(), self.d_nodes.data_ptr(), r.nodesBytes,
@@ -185,7 +223,7 @@ def main():
         rows.append(row)
 
     soup = None
-    if "tlas" in args.parts or "forest" in args.parts or "masks" in args.parts:
+    if "tlas" in args.parts or "forest" in args.parts or "masks" in args.parts or "wide" in args.parts or "wide_sweep" in args.parts:
         tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
         soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
 
@@ -300,7 +338,90 @@ def main():
         assert nt.trace_status() == 0, "traversal stack overflow"
         return row
 
-    if "identity" in args.parts or "masks" in args.parts:
+    def rate(secs, count):
+        ms = float(np.median(secs)) * 1e3
+        return {"ms_median": ms, "mrays_per_s": count / ms / 1e3, "ms_min": float(min(secs)) * 1e3, "ms_max": float(max(secs)) * 1e3}
+
+    def wide_frame(frame_name, t, cam):
+        """The part `wide` over one frame: binary and wide launches alternated, their counters, bytes and differing records."""
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays, d_res, d_ids, d_wres, d_wids = step(frame_name + " buffers", args.limit, lambda: [up(rays)] + [
+            torch.zeros(max(n, na) * b, dtype=torch.uint8, device="cuda:0") for b in (16, 4, 16, 4)])
+        row = {"part": "wide", "frame": frame_name, "instances": t.n, "primary_rays": n, "ao_rays": na, "peak_bytes_per_s": PEAK_BYTES_PER_S}
+        pools, tops = step(frame_name + " widening", args.limit, lambda: t.widen(args.warmup + args.reps))
+        row["pool_widen_ms"] = float(np.median([p.seconds for p in pools[args.warmup:]])) * 1e3
+        row["tlas_widen_ms"] = float(np.median([w.seconds for w in tops[args.warmup:]])) * 1e3
+        row.update(wide_pool_bytes=int(t.wpool_res.nodesBytes), binary_pool_bytes=int(t.blas.nb), wide_tlas_bytes=int(t.wtlas_res.nodesBytes),
+                   binary_tlas_bytes=int(t.res.nodesBytes), stack_bound=int(t.wtlas_res.stackBound), wide_tlas_counts=list(t.wtlas_res.counts),
+                   wide_pool_counts=list(t.wpool_res.counts))
+        def first_primary():
+            t.trace(n, False, d_rays, d_res, d_ids)
+            torch.cuda.synchronize()
+            return d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE).copy()
+        res = step(frame_name + " primary for the ao rays", args.limit, first_primary)
+        d_ao = step(frame_name + " ao upload", args.limit, lambda: up(host_ao_rays(rays, res, na, 7)))
+
+        def batch(name, count, any_hit, d_r):
+            def run():
+                b_secs, w_secs = [], []
+                for _ in range(args.warmup + args.reps):      # alternated: binary, wide, binary, wide, ...
+                    b_secs.append(t.trace(count, any_hit, d_r, d_res, d_ids))
+                    w_secs.append(t.trace_wide(count, any_hit, d_r, d_wres, d_wids))
+                torch.cuda.synchronize()                      # (the read-backs of both paths' last records: under the step's limit too)
+                back = (d_res.cpu().numpy()[:16 * count].reshape(-1, 16), d_wres.cpu().numpy()[:16 * count].reshape(-1, 16),
+                        d_ids.cpu().numpy()[:4 * count].reshape(-1, 4), d_wids.cpu().numpy()[:4 * count].reshape(-1, 4))
+                return b_secs[args.warmup:], w_secs[args.warmup:], back
+            b_secs, w_secs, (rb, rw, ib, iw) = step("%s %s" % (frame_name, name), args.limit, run)
+            out = {"binary": rate(b_secs, count), "wide": rate(w_secs, count),
+                   "records_differ": int(((rb != rw).any(axis=1) | (ib != iw).any(axis=1)).sum()),
+                   "hit_status_differs": int(((rb[:, :4].view(np.int32)[:, 0] >= 0) != (rw[:, :4].view(np.int32)[:, 0] >= 0)).sum())}
+            for key, st in (("binary", step("%s %s binary counters" % (frame_name, name), args.limit, lambda: t.stats(count, any_hit, d_r, d_res, d_ids, None))),
+                            ("wide", step("%s %s wide counters" % (frame_name, name), args.limit, lambda: t.stats_wide(count, any_hit, d_r, d_wres, d_wids)))):
+                c = st.as_dict()
+                out[key]["counters"] = c
+                out[key]["per_ray"] = {"top_nodes": c["numTopInnerVisits"] / count, "entries": c["numInstanceEntries"] / count,
+                                       "bottom_nodes": c["numInnerVisits"] / count, "tri_tests": c["numTriTests"] / count}
+                out[key]["algorithmic_bytes"] = int(st.algorithmic_bytes())
+                out[key]["fraction_of_peak"] = out[key]["algorithmic_bytes"] / (out[key]["ms_median"] * 1e-3) / PEAK_BYTES_PER_S
+            out["wide_over_binary"] = out["wide"]["ms_median"] / out["binary"]["ms_median"]
+            return out
+        row["primary"] = batch("primary", n, False, d_rays)
+        row["ao"] = batch("ao", na, True, d_ao)
+        assert nt.trace_status() == 0, "traversal stack overflow"
+        return row
+
+    def wide_pool_loop(num_blas=1024):
+        """ntr_pool_widen over a pool of num_blas BLASes of soup1000's triangles each: what the unbatched loop costs."""
+        tri, pos = soup.tri, soup.pos
+        nt_, nv = tri.shape[0], pos.shape[0]
+        k = np.arange(num_blas)
+        all_tri = (tri[None, :, :] + (k * nv)[:, None, None]).reshape(-1, 3).astype(np.int32)
+        all_pos = np.tile(pos, (num_blas, 1)).astype(F)
+        mn, mx = pos.min(axis=0), pos.max(axis=0)
+        meshes = [(int(i * nt_), int(nt_), mn, mx) for i in k]
+        cn, cw, ci, _ = nt.ploc_batch_capacity(meshes)
+        d_tri, d_pos = up(all_tri), up(all_pos)
+        bufs = [torch.zeros(c, dtype=torch.uint8, device="cuda:0") for c in (cn, cw, ci)]
+        out = nt.ploc_build_batch(meshes, all_tri.shape[0], d_tri.data_ptr(), all_pos.shape[0], d_pos.data_ptr(), bufs[0].data_ptr(), cn,
+                                  bufs[1].data_ptr(), cw, bufs[2].data_ptr(), ci, 8, stream)
+        ranges = out[1]
+        cap = nt.pool_widen_capacity(ranges)
+        d_wide = torch.zeros(cap, dtype=torch.uint8, device="cuda:0")
+        gpu, wall = [], []
+        for _ in range(args.warmup + args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, r = nt.pool_widen(ranges, bufs[0].data_ptr(), cn, d_wide.data_ptr(), cap, stream)
+            wall.append(time.perf_counter() - t0)
+            gpu.append(r.seconds)
+        gpu, wall = gpu[args.warmup:], wall[args.warmup:]
+        return {"part": "wide", "frame": "pool_widen_loop", "blases": num_blas, "tris_per_blas": int(nt_), "binary_pool_bytes": int(cn),
+                "wide_pool_bytes": int(r.nodesBytes), "gpu_ms_median": float(np.median(gpu)) * 1e3, "gpu_ms_min": float(min(gpu)) * 1e3,
+                "gpu_ms_max": float(max(gpu)) * 1e3, "wall_ms_median": float(np.median(wall)) * 1e3, "wall_ms_min": float(min(wall)) * 1e3,
+                "wall_ms_max": float(max(wall)) * 1e3, "wall_us_per_blas": float(np.median(wall)) * 1e6 / num_blas}
+
+    if "identity" in args.parts or "masks" in args.parts or "wide" in args.parts:
         tri, pos, cam = scenes.atrium()
         atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
         t = step("identity tlas", args.limit, lambda: Tlas(atrium, np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F), stream))
@@ -310,8 +431,10 @@ def main():
             emit(row)
         if "masks" in args.parts:
             emit(masks_frame("identity", t, cam))
+        if "wide" in args.parts:
+            emit(wide_frame("identity", t, cam))
 
-    if "forest" in args.parts or "masks" in args.parts:
+    if "forest" in args.parts or "masks" in args.parts or "wide" in args.parts:
         rng = np.random.default_rng(4096)
         g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
         t = step("forest tlas", args.limit, lambda: Tlas(soup, transforms(rotations(4096, rng), (g - 7.5) * 30.0), stream))
@@ -322,6 +445,38 @@ def main():
             emit(row)
         if "masks" in args.parts:
             emit(masks_frame("forest", t, cam))
+        if "wide" in args.parts:
+            emit(wide_frame("forest", t, cam))
+            emit(step("pool widen loop", args.limit, wide_pool_loop))
+
+    if "wide_sweep" in args.parts:
+        for k in (1, 2, 4, 8, 16):
+            rng = np.random.default_rng(4096)
+            g = np.stack(np.meshgrid(*[np.arange(k)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+            t = step("sweep tlas %d" % k, args.limit, lambda: Tlas(soup, transforms(rotations(k ** 3, rng), (g - (k - 1) / 2.0) * 30.0), stream))
+            f = (30.0 * k + 40.0) / 520.0                     # the forest's camera, moved back with the grid's extent
+            cam = dict(eye=(40.0 * f, 60.0 * f, -420.0 * f), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
+            rays, _ = scenes.primary_rays(cam, args.width, args.height)
+            n = rays.shape[0]
+            d_rays, d_res, d_ids, d_wres, d_wids = step("sweep buffers %d" % k, args.limit, lambda: [up(rays)] + [
+                torch.zeros(n * b, dtype=torch.uint8, device="cuda:0") for b in (16, 4, 16, 4)])
+            step("sweep widening %d" % k, args.limit, lambda: t.widen())
+
+            def run():
+                b_secs, w_secs = [], []
+                for _ in range(args.warmup + args.reps):      # alternated
+                    b_secs.append(t.trace(n, False, d_rays, d_res, d_ids))
+                    w_secs.append(t.trace_wide(n, False, d_rays, d_wres, d_wids))
+                return b_secs[args.warmup:], w_secs[args.warmup:]
+            b_secs, w_secs = step("sweep %d" % k, args.limit, run)
+            sb = step("sweep %d binary counters" % k, args.limit, lambda: t.stats(n, False, d_rays, d_res, d_ids, None)).as_dict()
+            sw = step("sweep %d wide counters" % k, args.limit, lambda: t.stats_wide(n, False, d_rays, d_wres, d_wids)).as_dict()
+            fetches = lambda c: (c["numTopInnerVisits"] + c["numInstanceEntries"] + c["numInnerVisits"]) / n   # noqa: E731
+            row = {"part": "wide_sweep", "instances": k ** 3, "primary_rays": n, "hits": sb["numHits"], "binary": rate(b_secs, n), "wide": rate(w_secs, n),
+                   "binary_fetches_per_ray": fetches(sb), "wide_fetches_per_ray": fetches(sw)}
+            row["wide_over_binary"] = row["wide"]["ms_median"] / row["binary"]["ms_median"]
+            assert nt.trace_status() == 0, "traversal stack overflow"
+            emit(row)
 
     if args.out:
         with open(args.out, "w") as f:
