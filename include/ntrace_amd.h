@@ -994,8 +994,8 @@ NTR_API int ntr_instanced_hit_attributes(int32_t numRays, const NtrRayResult* d_
  *   after the work: a link > 0 that names no slot was written as an empty slot; the tree is complete otherwise and *result describes it.
  *   Every other failure zeroes *result.  A slot named by several links is kept once, and the pass ends on any input.  Nothing beyond
  *   result->nodesBytes is written.  NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a device: there is no CPU fallback.  The scratch is a
- *   per-device grow-only pool that ntr_lbvh_release_workspace returns.  A wide tree is not refitted or optimized: refit or optimize the
- *   binary tree, then widen again.
+ *   per-device grow-only pool that ntr_lbvh_release_workspace returns.  A wide tree is refitted in place by a one-entry
+ *   ntr_pool_wide_refit (below); it is not optimized: optimize the binary tree, then widen again.
  * ntr_trace_wide: bvhFlags are the binary tree's (ntr_bvh_validate) or 0; the records are identical under any flags.  numRays == 0 ->
  *   NTR_OK, 0 seconds.  seconds == NULL is asynchronous on `stream` and capturable, a stack overflow sets the status word that
  *   ntr_trace_status reads; seconds != NULL is timed and blocking, NTR_ERR_OVERFLOW if a ray's stack overflowed.
@@ -1049,7 +1049,8 @@ NTR_API int ntr_trace_wide_stats(int32_t numRays, int32_t anyHit, const NtrRay* 
  * ntr_tlas_widen: widens the top-level tree (skipped when rootLink < 0, the one-instance tree) and writes the wide records from
  *   d_instances in one element-wise launch.  result->stackBound = the wide TLAS's bound + 1 (the exit marker) + the largest
  *   wideRanges[k].stackBound: <= 104 guarantees that the trace's stack never overflows.  It blocks and is refused on a capturing
- *   stream.  After ntr_tlas_refit or ntr_bvh_refit_batch the caller widens again: wide trees are not refitted in place.
+ *   stream.  After ntr_tlas_refit or ntr_bvh_refit_batch the caller widens again, or refits the wide trees in place
+ *   (ntr_pool_wide_refit, ntr_tlas_wide_refit, below), which keeps their topology and can be captured.
  *   NTR_ERR_INVALID before any device work for numInstances < 1, null or misaligned (16 B) buffers, a rootLink that is neither 0 nor an
  *   instance's link, a top-level buffer that ntr_bvh_widen refuses, capacities below ntr_bvh_widen_capacity / 64 * numInstances, a
  *   triWoopOffset that is no multiple of 16 inside the pool limit, a wide range that is not multiples of 128 inside the pool limit.
@@ -1093,6 +1094,75 @@ NTR_API int ntr_trace_instanced_wide_stats(int32_t numRays, int32_t anyHit, cons
                                            int64_t widePoolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
                                            const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* may be NULL */,
                                            NtrInstancedTraceStats* stats, void* stream);
+
+/* In-place refit of 4-wide trees: the update path of an animated instanced frame for the wide two-level trace
+ * (csrc/wide_refit_batch_kernels.hip, csrc/tlas_wide_refit_kernels.hip, csrc/wide_climb.h).  ntr_pool_widen and
+ * ntr_tlas_widen block, read back and may change a wide tree's topology from frame to frame; these two calls keep the wide topology
+ * and rewrite every box in place, asynchronously and capturably, the pool's BLASes in one pass.  EXTENSION without a reference
+ * counterpart: the rule is the numpy spec tests/np_wide_refit.py, which the device equals byte for byte.
+ *   leaf box     slot k < count with link < 0: ntr_bvh_refit's leaf rule over the leaf's triangles and the entry's epsilon; a leaf
+ *                without rows keeps its box
+ *   inner box    slot k < count with link > 0: the union, in the integer order, of slots 0..count-1 of the wide node it names
+ *   empty slot   link 0 below count: keeps its box and takes part in its node's union
+ *   padding      slot k >= count: a copy of slot 0's new box (ntr_bvh_widen's invariant)
+ *   not written  words 12..15 and 28..31 of every wide node, wide nodes no link reaches, terminators, triIndex; the Woop rows unless
+ *                rewriteRows
+ *   equal to     the boxes of the refitted binary tree at the slots' sources: after ntr_bvh_refit_batch (or with rewriteRows = 1) the
+ *                wide tree is what ntr_bvh_widen's expansion of the OLD binary boxes selects from the NEW binary boxes.  A fresh
+ *                widening of the refitted binary tree may choose another topology (areas changed): both are valid wide trees
+ * ntr_pool_wide_refit: an entry is a wide BLAS's range (NtrWideBlasRange's offset and extent), the BLAS's row range (NtrBlasRange's),
+ *   its mesh and its epsilon, as NtrRefitBatchEntry's.  rewriteRows = 1 also rewrites the Woop rows of every leaf, bit for bit as
+ *   ntr_bvh_refit_batch does: the all-wide path of a caller that traces wide only (no binary refit; ntr_tlas_wide_refit then takes the
+ *   boxes from the wide roots).  rewriteRows = 0 only reads the rows: for a caller that has just run ntr_bvh_refit_batch over the same
+ *   selection.  d_blasBoxes: optional, 6 floats per entry in entry order, min.xyz max.xyz, the union of the root's slots -- equal to
+ *   ntr_bvh_refit_batch's.  lanesPerLeaf is chosen by ntr_bvh_refit's thresholds from numTris / max(rows - 3 numTris, 1) summed over
+ *   the entries (a leaf is a terminator row): speed only.  A single-level wide tree (ntr_bvh_widen) is refitted as a one-entry pool.
+ * ntr_tlas_wide_refit: writes wide record i from the current d_instances[i] as ntr_tlas_widen does, forms the box of a leaf ~i from
+ *   the union of the root slots of instance i's wide BLAS (the pool's node 0 is not read) through objectToWorld as ntr_tlas_refit
+ *   does, and climbs.  N == 1: no node, rootLink ~0, wideTlasNodesBytes 0; record 0 and the scene box.
+ * Both follow ntr_bvh_refit_batch and ntr_tlas_refit point for point: result == NULL is asynchronous on `stream` (two launches, no
+ * read-back, no memset, capturable); result != NULL blocks, reads counts, error bits and GPU time back and is refused on a capturing
+ * stream.  A malformed part is never followed and nothing outside the buffers is read or written, whatever the wide buffers hold: the
+ * blocking form returns NTR_ERR_LAYOUT after the work with *result filled (error bits as ntr_bvh_refit's / ntr_tlas_refit's; bit 1 of
+ * the pool and bit 2 of the top level also cover a link that is no multiple of 128 or lies outside the tree, a node named by two links
+ * and a count word outside 2..4; NTR_ERR_INVALID for a blas index out of range, as ntr_tlas_refit), every other entry has been
+ * refitted completely; the asynchronous form skips such a part silently.  The scratch (8 B per listed wide node, the entry or range
+ * table, 16 KB of counters) is a per-device grow-only pool of each call's own that ntr_lbvh_release_workspace returns.  Tables are
+ * uploaded only when they differ from the last uncaptured call's; a captured call is accepted only when the last uncaptured call had
+ * the same table (and the same instance count and extent) and the pool has not been released since, else NTR_ERR_INVALID says so.  One
+ * call per device at a time.
+ * NTR_ERR_INVALID (before any device work): null pointers (d_blasBoxes, d_sceneBox, result may be null; d_wideTlasNodes for N == 1),
+ * numEntries outside 1..2^20, sizes that are not multiples of 128 / 16 / 64 within the pool limits, pointers not 16-byte aligned, a
+ * range that is misaligned or outside the extents, entries whose wide ranges or row ranges overlap, a mesh outside [0, numTrisTotal), a
+ * negative or non-finite epsilon, a rewriteRows other than 0 or 1, a rootLink that is neither 0 nor ~0 as N requires,
+ * wideTlasNodesBytes that is no multiple of 128 (0 only for N == 1), recordsCapacity < 64 * numInstances.  Without a device, after
+ * these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrWideRefitEntry {            /* host array, one per wide BLAS to refit: 48 bytes */
+    int64_t wideNodesOffset, wideNodesBytes;  /* NtrWideBlasRange's of that BLAS */
+    int64_t triWoopOffset, triWoopBytes;      /* NtrBlasRange's of that BLAS */
+    int32_t firstTri, numTris;
+    float   epsilon;
+    int32_t pad;
+} NtrWideRefitEntry;
+typedef struct NtrWideRefitResult {
+    int32_t numEntries, lanesPerLeaf;         /* lanesPerLeaf says which kernel ran */
+    int64_t numNodes, numLeafLinks, numRows;  /* sums over the entries: wide nodes, negative links, rows (terminators included) */
+    int32_t firstBadEntry, errBits;           /* -1 / 0, or the lowest entry whose tree is malformed and the OR of the error bits */
+    float   seconds, pad;                     /* GPU time */
+} NtrWideRefitResult;
+NTR_API int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, void* d_widePoolNodes, int64_t widePoolNodesBytes,
+                                void* d_poolTriWoop, int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, int32_t numTrisTotal,
+                                const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos, int32_t rewriteRows,
+                                float* d_blasBoxes /* may be NULL */, NtrWideRefitResult* result /* NULL: asynchronous */, void* stream);
+/* Bytes the wide pool refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_pool_wide_refit_scratch_bytes(int64_t* bytes);
+NTR_API int ntr_tlas_wide_refit(int32_t numInstances, const NtrInstance* d_instances, int32_t numBlas, const NtrBlasRange* blasRanges,
+                                const NtrWideBlasRange* wideRanges, const void* d_widePoolNodes, int64_t widePoolNodesBytes,
+                                void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink, void* d_wideRecords,
+                                int64_t recordsCapacity, float* d_sceneBox /* may be NULL */,
+                                NtrTlasRefitResult* result /* NULL: asynchronous */, void* stream);
+/* Bytes the wide top-level refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_tlas_wide_refit_scratch_bytes(int64_t* bytes);
 
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by

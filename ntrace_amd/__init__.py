@@ -29,7 +29,9 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     BlasTris, BLAS_TRIS_DTYPE, InstancedGeometry, instanced_hit_attributes, raygen_ao_normals,
                     BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats,
                     WideBlasRange, TlasWideResult, InstancedWideTraceStats, pool_widen_capacity, pool_widen, tlas_widen,
-                    trace_instanced_wide, trace_instanced_wide_stats)
+                    trace_instanced_wide, trace_instanced_wide_stats,
+                    WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
+                    tlas_wide_refit_scratch_bytes)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -54,4 +56,6 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "BlasTris", "BLAS_TRIS_DTYPE", "InstancedGeometry", "instanced_hit_attributes", "raygen_ao_normals",
            "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats",
            "WideBlasRange", "TlasWideResult", "InstancedWideTraceStats", "pool_widen_capacity", "pool_widen", "tlas_widen",
-           "trace_instanced_wide", "trace_instanced_wide_stats"]
+           "trace_instanced_wide", "trace_instanced_wide_stats",
+           "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",
+           "tlas_wide_refit_scratch_bytes"]

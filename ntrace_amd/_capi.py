@@ -254,6 +254,25 @@ class TlasWideResult(C.Structure):
         return {k: (list(getattr(self, k)) if k == "counts" else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+class WideRefitEntry(C.Structure):
+    """NtrWideRefitEntry: one wide BLAS of a wide pool to refit -- its wide range (pool_widen's), its row range (the BLAS's), its mesh
+    and the epsilon of its leaf boxes."""
+    _fields_ = [("wideNodesOffset", C.c_int64), ("wideNodesBytes", C.c_int64), ("triWoopOffset", C.c_int64), ("triWoopBytes", C.c_int64),
+                ("firstTri", C.c_int32), ("numTris", C.c_int32), ("epsilon", C.c_float), ("pad", C.c_int32)]
+
+    def __init__(self, wide_nodes_offset=0, wide_nodes_bytes=0, tri_woop_offset=0, tri_woop_bytes=0, first_tri=0, num_tris=0, epsilon=0.0):
+        super().__init__(int(wide_nodes_offset), int(wide_nodes_bytes), int(tri_woop_offset), int(tri_woop_bytes), int(first_tri),
+                         int(num_tris), float(epsilon), 0)
+
+
+class WideRefitResult(C.Structure):
+    _fields_ = [("numEntries", C.c_int32), ("lanesPerLeaf", C.c_int32), ("numNodes", C.c_int64), ("numLeafLinks", C.c_int64),
+                ("numRows", C.c_int64), ("firstBadEntry", C.c_int32), ("errBits", C.c_int32), ("seconds", C.c_float), ("pad", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class InstancedWideTraceStats(InstancedTraceStats):
     """NtrInstancedTraceStats of the wide two-level trace: numTopInnerVisits and numInnerVisits count wide nodes."""
 
@@ -449,6 +468,10 @@ SYMBOLS = [
                                            C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
     ("ntr_trace_instanced_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                                  C.POINTER(InstanceVisibility), C.POINTER(InstancedWideTraceStats), _vp]),
+    ("ntr_pool_wide_refit", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.POINTER(WideRefitResult), _vp]),
+    ("ntr_pool_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_tlas_wide_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
+    ("ntr_tlas_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(BvhRefitBatchResult), _vp]),
@@ -1269,6 +1292,71 @@ def trace_instanced_wide_stats(num_rays, any_hit, d_rays, d_results, d_instance_
                                                 int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
                                                 C.byref(st), _vp(stream)))
     return st
+
+
+def _wide_refit_entries(entries):
+    """A ctypes array of WideRefitEntry from WideRefitEntry objects or (wideNodesOffset, wideNodesBytes, triWoopOffset, triWoopBytes,
+    firstTri, numTris[, epsilon]) tuples."""
+    if isinstance(entries, C.Array):
+        return entries
+    items = [e if isinstance(e, WideRefitEntry) else WideRefitEntry(*e) for e in entries]
+    return (WideRefitEntry * max(len(items), 1))(*items)
+
+
+def pool_wide_refit(entries, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_idx, num_tris_total, d_tri,
+                    num_verts, d_pos, rewrite_rows=True, d_blas_boxes=0, stream=0, blocking=True):
+    """ntr_pool_wide_refit: refit the listed wide BLASes of a wide pool (WideRefitEntry objects or (wideNodesOffset, wideNodesBytes,
+    triWoopOffset, triWoopBytes, firstTri, numTris[, epsilon]) tuples) in place to the vertex positions at d_pos, keeping their topology
+    (an extension; the rule is tests/np_wide_refit.py).  rewrite_rows=True also rewrites the leaves' Woop rows, as bvh_refit_batch does;
+    False only reads them (after a bvh_refit_batch over the same selection).  blocking=True returns a WideRefitResult; blocking=False
+    passes result = NULL: asynchronous on `stream` (capturable) and returns None.  An NtrError for a malformed tree (NTR_ERR_LAYOUT, after
+    the work) carries .result, filled: firstBadEntry, errBits and the counts."""
+    n = len(entries)
+    arr = _wide_refit_entries(entries)
+    res = WideRefitResult() if blocking else None
+    try:
+        _check(lib().ntr_pool_wide_refit(n, C.cast(arr, _vp), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes), _vp(d_pool_woop),
+                                         int(pool_woop_bytes), _vp(d_pool_idx), int(num_tris_total), _vp(d_tri), int(num_verts), _vp(d_pos),
+                                         int(rewrite_rows), _vp(d_blas_boxes), C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def pool_wide_refit_scratch_bytes():
+    """ntr_pool_wide_refit_scratch_bytes: bytes the wide pool refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_pool_wide_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def tlas_wide_refit(num_instances, d_instances, ranges, wide_ranges, d_wide_pool_nodes, wide_pool_nodes_bytes, d_wide_tlas_nodes,
+                    wide_tlas_nodes_bytes, root_link, d_wide_records, records_cap, d_scene_box=0, stream=0, blocking=True):
+    """ntr_tlas_wide_refit: keep a wide top-level tree's topology and rewrite its wide records and every box from the current instances
+    and the current roots of the wide pool's BLASes (an extension; the rule is tests/np_wide_refit.py).  ranges as for tlas_build,
+    wide_ranges as pool_widen returned them.  blocking=True returns a TlasRefitResult; blocking=False passes result = NULL: asynchronous
+    on `stream` (capturable) and returns None.  An NtrError raised after the device work (a bad blas index, a malformed tree) carries
+    .result, filled: errBits and the counts."""
+    arr, n = _blas_ranges(ranges)
+    warr = _wide_ranges(wide_ranges)
+    res = TlasRefitResult() if blocking else None
+    try:
+        _check(lib().ntr_tlas_wide_refit(int(num_instances), _vp(d_instances), n, C.cast(arr, _vp), C.cast(warr, _vp), _vp(d_wide_pool_nodes),
+                                         int(wide_pool_nodes_bytes), _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), int(root_link),
+                                         _vp(d_wide_records), int(records_cap), _vp(d_scene_box), C.byref(res) if blocking else None,
+                                         _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def tlas_wide_refit_scratch_bytes():
+    """ntr_tlas_wide_refit_scratch_bytes: bytes the wide top-level refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_tlas_wide_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
 
 
 def bvh_refit(d_nodes, nodes_bytes, d_woop, woop_bytes, d_idx, idx_bytes, num_tris, d_tri, num_verts, d_pos, epsilon=0.0, d_scene_box=0,

@@ -1,6 +1,7 @@
 // bvh_refit_leaf.h -- the refit's leaf pass as functions of one tree's pointers: the walk over a leaf's row groups to the terminator, the
 // Woop rows, the integer-order fold of the box, and epsilon, the box's publish and the climb (bvh_climb.h).  The rule is
-// tests/np_bvh_refit.py.  Used by the kernel that refits many BLASes of a pool (bvh_refit_batch_kernels.hip).  refit_climb of
+// tests/np_bvh_refit.py.  Used by the kernels that refit many BLASes of a pool
+// (bvh_refit_batch_kernels.hip) and many wide BLASes of a wide pool (wide_refit_batch_kernels.hip: refit_leaf_rows only).  refit_climb of
 // bvh_refit_kernels.hip holds the same statements inline and does NOT include this header: built over these functions its three
 // instances came out with other code than before (block layout and register assignment; scripts/kernel_isa_diff.sh), so that file was
 // left as it was.  A change to the leaf rule is made in both places; tests/test_refit_batch_gpu.py compares the two
@@ -45,8 +46,10 @@ __device__ __forceinline__ void rf_acquire_box(const int* nodes, int node, int k
 // on it): lane `sub` takes the row groups sub, sub + G, ... of the leaf, so that a leaf's index -> vertex gathers are in flight
 // together; the lanes find the terminator by a ballot and fold their boxes by shuffles.  `link` is the leaf's (< 0), uniform within
 // the group, whose first lane of the wave is groupShift.  Afterwards lo / hi hold the group's box as ord_enc words in every lane of
-// the group (lo > hi: no triangle was folded); err and rows are the lane's own.
-template <int G>
+// the group (lo > hi: no triangle was folded); err and rows are the lane's own.  REWRITE false (the wide refit that follows a binary one,
+// wide_refit_batch_kernels.hip, whose rows are current already) only reads the rows, to find the terminator and triIndex: that instance
+// holds no store to woop.
+template <int G, bool REWRITE = true>
 __device__ __forceinline__ void refit_leaf_rows(int link, int sub, int groupShift, int numRows, float4* woop,
                                                 const int* triIndex, int numTris, const int* tri, int numVerts,
                                                 const float* pos, unsigned int& err, unsigned int& rows,
@@ -79,11 +82,13 @@ __device__ __forceinline__ void refit_leaf_rows(int link, int sub, int groupShif
                         v[3 + q] = pos[3 * (size_t)i1 + q];
                         v[6 + q] = pos[3 * (size_t)i2 + q];
                     }
-                    float4 w0, w1, w2;
-                    woop_rows_verts(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], w0, w1, w2);
-                    woop[r] = w0;
-                    woop[r + 1] = w1;
-                    woop[r + 2] = w2;
+                    if (REWRITE) {
+                        float4 w0, w1, w2;
+                        woop_rows_verts(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], w0, w1, w2);
+                        woop[r] = w0;
+                        woop[r + 1] = w1;
+                        woop[r + 2] = w2;
+                    }
                     rows += 3;
 #pragma unroll
                     for (int q = 0; q < 3; q++) {

@@ -11,6 +11,7 @@
 //               extent 0: a lane inside an instance fetches a wide node only below the extent, so nothing of such an instance is read
 //   marker      kExitMarker, as in instanced_bvh.h
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "instanced_bvh.h"
@@ -20,6 +21,21 @@ namespace ntr {
 
 constexpr int kWideRecOffset = 12, kWideRecRowOffset = 13, kWideRecExtent = 14;
 static_assert(kPoolMaxBytes % kWideBytes == 0, "a wide pool of the largest size is a whole number of wide nodes");
+
+// Wide record i from the current instance i: table[b] is (wide offset, triWoopOffset / 16, wide extent, 0) of BLAS b.  For the record
+// launch of ntr_tlas_widen and the prepare launch of ntr_tlas_wide_refit
+__device__ __forceinline__ void wide_write_record(const NtrInstance* __restrict__ inst, int i, int numBlas, const uint4* __restrict__ table,
+                                                  uint4* __restrict__ records)
+{
+    const int b = inst[i].blas;
+    const uint4 range = (b >= 0 && b < numBlas) ? table[b] : make_uint4(0u, 0u, 0u, 0u);   // wide offset, row offset, wide extent, 0
+    const uint32_t* inv = reinterpret_cast<const uint32_t*>(inst[i].worldToObject);
+    uint4* rec = records + 4 * (size_t)i;
+    rec[0] = make_uint4(inv[0], inv[1], inv[2], inv[3]);
+    rec[1] = make_uint4(inv[4], inv[5], inv[6], inv[7]);
+    rec[2] = make_uint4(inv[8], inv[9], inv[10], inv[11]);
+    rec[3] = make_uint4(range.x, range.y, range.z, 0u);
+}
 
 // bvh_widen_kernels.hip: `bytes` of the widening pass's per-device scratch pool (the pass is blocking, so between two passes the pool
 // is idle: the pool and TLAS widening keep their BLAS table there and add no pool of their own)

@@ -26,14 +26,7 @@ __global__ __launch_bounds__(IW_BLOCK) void iw_records(int n, const NtrInstance*
 {
     const int i = blockIdx.x * IW_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const int b = inst[i].blas;
-    const uint4 range = (b >= 0 && b < numBlas) ? table[b] : make_uint4(0u, 0u, 0u, 0u);   // wide offset, row offset, wide extent, 0
-    const uint32_t* inv = reinterpret_cast<const uint32_t*>(inst[i].worldToObject);
-    uint4* rec = records + 4 * (size_t)i;
-    rec[0] = make_uint4(inv[0], inv[1], inv[2], inv[3]);
-    rec[1] = make_uint4(inv[4], inv[5], inv[6], inv[7]);
-    rec[2] = make_uint4(inv[8], inv[9], inv[10], inv[11]);
-    rec[3] = make_uint4(range.x, range.y, range.z, 0u);
+    wide_write_record(inst, i, numBlas, table, records);
 }
 
 bool iw_ranges_overlap(const void* a, int64_t an, const void* b, int64_t bn)

@@ -8,7 +8,8 @@
 //   tlr_climb     one thread per child slot: a leaf link ~i forms instance i's world box (tlr_world_box), publishes it into the node
 //                 and runs the climb of bvh_climb.h with the integer-order union
 //   tlr_single    N == 1 has no node: record 0 and the scene box in one small launch
-// tlr_world_box holds the statements of tl_boxes (tlas_build_kernels.hip), which does NOT call it: built over a shared function tl_boxes
+// tlr_world_box (tlas_world_box.h: the wide top-level refit shares it) holds the statements of tl_boxes (tlas_build_kernels.hip), which
+// does NOT call it: built over a shared function tl_boxes
 // came out with other code than before (the operands of twelve additions commuted; scripts/kernel_isa_diff.sh), so that file was left
 // as it was.  A change to the world-box rule is made in both places; tests/test_tlas_refit_gpu.py demands that the refit
 // of a fresh build changes no byte at every size it runs.
@@ -31,6 +32,7 @@
 #include "device_scratch.h"
 #include "instanced_bvh.h"
 #include "level_build.h"
+#include "tlas_world_box.h"
 
 namespace ntr {
 namespace {
@@ -48,36 +50,6 @@ struct TlrStats {
 static_assert(sizeof(TlrStats) == 64, "TlrStats must be 64 bytes");
 
 DeviceScratchPool g_tlrPool;
-
-// xform's component (np_instanced.py): r = 0; r += a0 * x; r += a1 * y; r += a2 * z; r += a3 * w
-__device__ __forceinline__ float tlr_dot4(const float* a, float x, float y, float z, float w)
-{
-    float r = 0.0f;
-    r += a[0] * x;
-    r += a[1] * y;
-    r += a[2] * z;
-    r += a[3] * w;
-    return r;
-}
-
-// np_instanced.instance_box: n0, n1, nz are the first three float4 of the BLAS's node 0, m is objectToWorld
-__device__ __forceinline__ void tlr_world_box(const float4& n0, const float4& n1, const float4& nz, const float (&m)[12], float (&wlo)[3],
-                                              float (&whi)[3])
-{
-    // the object box: the union of node 0's child boxes (an empty child, (FLT_MAX, -FLT_MAX), drops out by itself)
-    const float lo[3] = {ord_min(n0.x, n1.x), ord_min(n0.z, n1.z), ord_min(nz.x, nz.z)};
-    const float hi[3] = {ord_max(n0.y, n1.y), ord_max(n0.w, n1.w), ord_max(nz.y, nz.w)};
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        const float x = (c & 1) ? hi[0] : lo[0], y = (c & 2) ? hi[1] : lo[1], z = (c & 4) ? hi[2] : lo[2];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const float p = tlr_dot4(m + 4 * r, x, y, z, 1.0f);
-            wlo[r] = c == 0 ? p : ord_min(wlo[r], p);
-            whi[r] = c == 0 ? p : ord_max(whi[r], p);
-        }
-    }
-}
 
 // Record i (instanced_bvh.h) of an instance whose blas index the caller has checked; range is the table's entry of its BLAS
 __device__ __forceinline__ void tlr_write_record(const NtrInstance* __restrict__ inst, int i, const uint4 range, uint4* __restrict__ records)

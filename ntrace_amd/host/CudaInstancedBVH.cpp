@@ -1,5 +1,6 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
-// and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen / ntr_tlas_widen / ntr_trace_instanced_wide (see the header).
+// and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
+// ntr_trace_instanced_wide (see the header).
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
@@ -7,10 +8,12 @@
 namespace FW {
 
 CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false),
-                                           m_widePool(false), m_wideTlas(false), m_traceWide(false)
+                                           m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false)
 {
     std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
     std::memset(&m_wideResult, 0, sizeof(m_wideResult));
+    std::memset(&m_wideBlasRefitResult, 0, sizeof(m_wideBlasRefitResult));
+    std::memset(&m_wideTlasRefitResult, 0, sizeof(m_wideTlasRefitResult));
     std::memset(&m_result, 0, sizeof(m_result));
     std::memset(&m_blasResult, 0, sizeof(m_blasResult));
     std::memset(&m_refitResult, 0, sizeof(m_refitResult));
@@ -39,7 +42,7 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_ranges.push_back(r);
     const Mesh none = {0, 0};
     m_meshes.push_back(none);
-    m_built = m_topology = m_blasTrisCurrent = false;
+    m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
     return (S32)m_ranges.size() - 1;
 }
@@ -54,7 +57,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
     m_ranges.clear();
     m_meshes.clear();
-    m_built = m_topology = m_blasTrisCurrent = false;
+    m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
@@ -110,7 +113,7 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
         e.pad = 0;
     }
     m_built = false;
-    m_widePool = m_wideTlas = false;             // wide trees are not refitted in place: widen() again
+    m_widePool = m_wideTlas = false;             // this method refits the binary pool only: widen() again, or call refitBLASesWide
     const int rc = ntr_bvh_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
                                        m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
                                        (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
@@ -130,7 +133,7 @@ void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32
         inst[i].blas = blas[i];
     }
     if (num != m_numInstances) {
-        m_topology = false;                          // an unchanged count keeps the TLAS's topology for refit() ...
+        m_topology = m_wideTopology = false;         // an unchanged count keeps the TLAS's topology for refit() ...
         m_instanceMasks.resizeDiscard(0);            // ... and the instance masks: with another count they would name other instances
     }
     m_numInstances = num;
@@ -150,7 +153,7 @@ void CudaInstancedBVH::build(S32 radius)
     if (m_ranges.empty() || m_numInstances < 1) fail("CudaInstancedBVH: nothing to build");
     int64_t capN, capR;
     if (ntr_tlas_capacity(m_numInstances, &capN, &capR) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
-    m_built = m_topology = false;
+    m_built = m_topology = m_wideTopology = false;
     m_wideTlas = false;
     m_tlasNodes.resizeDiscard(capN);
     m_records.resizeDiscard(capR);
@@ -205,6 +208,48 @@ void CudaInstancedBVH::widen(void)
                                   m_result.nodesBytes, m_result.rootLink, numBlas, m_ranges.data(), m_wideRanges.data(),
                                   m_result.rootLink == 0 ? m_wideTlasNodes.getMutableCudaPtr() : NULL, capT, m_wideRecords.getMutableCudaPtr(),
                                   m_wideRecords.getSize(), &m_wideResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_wideTlas = m_wideTopology = true;
+}
+
+void CudaInstancedBVH::refitBLASesWide(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas, S32 num, F32 epsilon)
+{
+    if (!m_widePool) fail("CudaInstancedBVH: no current wide pool to refit: call widen() first, and again after refitBLASes, buildBLASes or addBLAS");
+    if (!blas) num = (S32)m_ranges.size();
+    refitBLASes(triVtxIndex, numVerts, vtxPos, blas, num, epsilon);   // the binary pool stays current; the selection is checked there
+    std::vector<NtrWideRefitEntry> entries((size_t)num);
+    for (S32 i = 0; i < num; i++) {
+        const S32 b = blas ? blas[i] : i;
+        NtrWideRefitEntry& e = entries[i];
+        e.wideNodesOffset = m_wideRanges[b].nodesOffset;
+        e.wideNodesBytes = m_wideRanges[b].nodesBytes;
+        e.triWoopOffset = m_ranges[b].triWoopOffset;
+        e.triWoopBytes = m_ranges[b].triWoopBytes;
+        e.firstTri = m_meshes[b].firstTri;
+        e.numTris = m_meshes[b].numTris;
+        e.epsilon = epsilon;
+        e.pad = 0;
+    }
+    const S64 numTris = triVtxIndex.getSize() / (S64)(3 * sizeof(S32));
+    const int rc = ntr_pool_wide_refit(num, entries.data(), m_widePoolNodes.getMutableCudaPtr(), m_widePoolResult.nodesBytes,
+                                       m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
+                                       (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
+                                       0 /* the binary refit has written the rows */, NULL, &m_wideBlasRefitResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_widePool = true;                           // (refitBLASes dropped it: the wide boxes are the new ones again)
+}
+
+void CudaInstancedBVH::refitWide(void)
+{
+    if (!m_topology || !m_wideTopology || m_numInstances < 1)
+        fail("CudaInstancedBVH: no wide TLAS to refit: call build() and widen() first, and again after the instance count or the BLASes have changed");
+    if (!m_widePool) fail("CudaInstancedBVH: the wide pool is not current: call refitBLASesWide() in place of refitBLASes(), or widen()");
+    refit();                                     // the binary TLAS and records stay current
+    const int rc = ntr_tlas_wide_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
+                                       m_wideRanges.data(), m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
+                                       m_wideResult.nodesBytes ? m_wideTlasNodes.getMutableCudaPtr() : NULL, m_wideResult.nodesBytes,
+                                       m_result.rootLink, m_wideRecords.getMutableCudaPtr(), m_wideRecords.getSize(), NULL,
+                                       &m_wideTlasRefitResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_wideTlas = true;
 }

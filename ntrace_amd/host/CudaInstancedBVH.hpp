@@ -27,6 +27,13 @@
 //                 (ntr_pool_widen), and the TLAS and the records always (ntr_tlas_widen).  build() and refit() drop the wide TLAS;
 //                 refitBLASes, buildBLASes and addBLAS drop the wide pool too: widen again after them.  The binary pool, TLAS and
 //                 records stay what they are
+//   refitBLASesWide   refitBLASes, then the same selection of the wide pool in place by ntr_pool_wide_refit (rewriteRows 0:
+//                 the binary refit has just written the rows).  Needs isWidePoolCurrent() on entry and keeps it: the wide BLASes keep
+//                 the topology of the last pool widening.  The TLAS flags fall as after refitBLASes
+//   refitWide     refit(), then the wide TLAS and the wide records in place by ntr_tlas_wide_refit.  Needs a build() and a widen() with
+//                 the current instance count since, and a current wide pool; afterwards isBuilt() && isWide().  The frame loop of a
+//                 moving, deforming scene on the wide path is refitBLASesWide -> setInstances -> refitWide -> traceBatch, with
+//                 build() + widen() every so many frames; none of its steps reads anything back but the results
 //   setTraceWide  traceBatch takes the wide path (ntr_trace_instanced_wide) when isWide() and this was set; default false, so nothing
 //                 changes for existing callers.  The records may differ from the binary path's in rays within rounding of a box
 //                 surface (the spec tests/np_instanced_wide.py states the limit)
@@ -64,12 +71,16 @@ public:
     void setInstanceMasks(const U32* masks /* getNumInstances() words; NULL: all visible */);
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask = 0xFFFFFFFFu);   // GPU seconds
     void widen(void);
+    void refitBLASesWide(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas = NULL, S32 num = 0, F32 epsilon = 0.0f);
+    void refitWide(void);
     void setTraceWide(bool on) { m_traceWide = on; }
     bool getTraceWide(void) const { return m_traceWide; }
     bool isWide(void) const { return m_built && m_widePool && m_wideTlas; }      // the wide pool, TLAS and records are current
     bool isWidePoolCurrent(void) const { return m_widePool; }
     const NtrTlasWideResult& getWideResult(void) const { return m_wideResult; }            // of the last widen() (zero before)
     const NtrBvhWideResult&  getWidePoolResult(void) const { return m_widePoolResult; }    // of the last pool widening (zero before)
+    const NtrWideRefitResult& getWideBLASRefitResult(void) const { return m_wideBlasRefitResult; }   // of the last refitBLASesWide (zero before)
+    const NtrTlasRefitResult& getWideRefitResult(void) const { return m_wideTlasRefitResult; }       // of the last refitWide (zero before)
     Buffer& getWidePoolNodeBuffer(void) { return m_widePoolNodes; }
     Buffer& getWideTLASNodeBuffer(void) { return m_wideTlasNodes; }
     Buffer& getWideRecordBuffer(void) { return m_wideRecords; }
@@ -108,6 +119,7 @@ private:
     S32           m_numInstances;
     bool          m_built;                                                       // the TLAS is current: traceBatch may run
     bool          m_topology;                                                    // a TLAS of m_numInstances leaves over these BLASes exists: refit may run
+    bool          m_wideTopology;                                                // ... and widen() has widened it since that build(): refitWide may run
     NtrTlasResult m_result;
     NtrPlocBatchResult m_blasResult;
     NtrBvhRefitBatchResult m_refitResult;
@@ -118,6 +130,8 @@ private:
     bool          m_widePool, m_wideTlas, m_traceWide;
     NtrBvhWideResult  m_widePoolResult;
     NtrTlasWideResult m_wideResult;
+    NtrWideRefitResult m_wideBlasRefitResult;
+    NtrTlasRefitResult m_wideTlasRefitResult;
 };
 
 }  // namespace FW

@@ -4,7 +4,8 @@
 //                     outlive this object and keep its buffers)
 //   build             widens the Compact tree on the device; refuses (FW::fail) without a device: there is no CPU fallback
 //   traceBatch        closest hit or any hit as the RayBuffer asks, with the binary tree's validated flags
-// A wide tree is not refitted or optimized: refit or optimize the CudaBVH, then build() again.
+// This class does not refit or optimize its wide tree: refit or optimize the CudaBVH, then build() again (at the C ABI a one-entry
+// ntr_pool_wide_refit refits a single-level wide tree in place).
 #pragma once
 #include "CudaBVH.hpp"
 #include "RayBuffer.hpp"
