@@ -1040,8 +1040,9 @@ NTR_API int ntr_trace_wide_stats(int32_t numRays, int32_t anyHit, const NtrRay* 
  *               + 16 numLeafVisits + 4 numHits, plus the two mask terms of ntr_trace_instanced_stats (112: a wide node's seven fetched rows)
  * KNOWN LIMIT, ntr_trace_wide's: the records may differ from the binary two-level trace's on the same scene.  The spec is the definition.
  * ntr_pool_widen_capacity: host only; the sum of ntr_bvh_widen_capacity over the ranges (a bound, not the extent).
- * ntr_pool_widen: a loop of ntr_bvh_widen, one BLAS after the other (a batched pass is future work: the loop pays the pass's launches
- *   and read-backs per BLAS).  It blocks and is refused on a capturing stream.  wideRanges[k] receives BLAS k's offset, extent, node
+ * ntr_pool_widen: a loop of ntr_bvh_widen, one BLAS after the other (the loop pays the pass's launches and read-backs per BLAS;
+ *   ntr_pool_widen_batch, below, is the batched pass and writes the same bytes).  It blocks and is refused on a capturing stream.
+ *   wideRanges[k] receives BLAS k's offset, extent, node
  *   count and stackBound; *result the total extent (nodesBytes), the sums of numNodes, counts and numLeafLinks, the largest height and
  *   stackBound of any BLAS, and the summed GPU time.  NTR_ERR_INVALID before any device work for numBlas < 1, null pointers, a pool size
  *   or BLAS range that ntr_tlas_build refuses, a capacity below ntr_pool_widen_capacity, an output that overlaps the pool.
@@ -1078,6 +1079,27 @@ NTR_API int ntr_pool_widen_capacity(int32_t numBlas, const NtrBlasRange* blasRan
 NTR_API int ntr_pool_widen(int32_t numBlas, const NtrBlasRange* blasRanges, const void* d_poolNodes, int64_t poolNodesBytes,
                            void* d_widePoolNodes, int64_t capacity, NtrWideBlasRange* wideRanges /* numBlas, host out */,
                            NtrBvhWideResult* result, void* stream);
+/* ntr_pool_widen_batch: ntr_pool_widen's arguments and outputs, every BLAS in one pass (csrc/pool_widen_batch_kernels.hip):
+ *   the marking runs level by level over all BLASes at once, so the launches and read-backs number what one ntr_bvh_widen of the
+ *   tallest BLAS takes plus a fixed few, whatever numBlas is.  The bytes written, wideRanges and *result (but for seconds, the GPU
+ *   time of the whole pass) equal ntr_pool_widen's, that is tests/np_instanced_wide.py::widen_pool: wide BLAS k is what ntr_bvh_widen
+ *   writes for pool + nodesOffset_k, at the sum of the exact extents of BLASes 0..k-1 in k order.  blasRanges may come in any order,
+ *   alias or overlap each other and leave gaps: each is a tree of its own, and a link is judged against its own BLAS's slot count only.
+ *   NTR_ERR_INVALID before any device work for everything ntr_pool_widen refuses, in its order (a capturing stream included: the call
+ *   blocks), and for numBlas > 2^20 (wideRanges is then left untouched; every other failure zeroes it, and every failure but
+ *   NTR_ERR_LAYOUT zeroes *result).  After the checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP without a device.  NTR_ERR_OVERFLOW: the wide
+ *   pool would exceed 0xFFFFFF00 bytes, a wide BLAS would exceed 0x76543200 / 128 nodes, or the ranges list more than 0xFFFFFF00 / 64
+ *   slots in all (possible only where they alias).  STRICTER than the loop: the node counts are known before anything is emitted, so
+ *   here NOTHING is written, where ntr_pool_widen has written the BLASes before the one that overflows.  NTR_ERR_LAYOUT, after the
+ *   work: some link > 0 names no slot of its own BLAS and was written as an empty slot; every wide BLAS is complete, *result and
+ *   wideRanges are filled, and the message names the lowest such BLAS and the number of such links.  Nothing beyond result->nodesBytes
+ *   is written.  The scratch is a per-device grow-only pool of its own that ntr_lbvh_release_workspace returns; ntr_bvh_widen's pool
+ *   is not touched. */
+NTR_API int ntr_pool_widen_batch(int32_t numBlas, const NtrBlasRange* blasRanges, const void* d_poolNodes, int64_t poolNodesBytes,
+                                 void* d_widePoolNodes, int64_t capacity, NtrWideBlasRange* wideRanges /* numBlas, host out */,
+                                 NtrBvhWideResult* result, void* stream);
+/* Bytes ntr_pool_widen_batch's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_pool_widen_batch_scratch_bytes(int64_t* bytes);
 NTR_API int ntr_tlas_widen(int32_t numInstances, const NtrInstance* d_instances, const void* d_tlasNodes, int64_t tlasNodesBytes,
                            int32_t rootLink, int32_t numBlas, const NtrBlasRange* blasRanges, const NtrWideBlasRange* wideRanges,
                            void* d_wideTlasNodes, int64_t capacity, void* d_wideRecords, int64_t recordsCapacity, NtrTlasWideResult* result,

@@ -29,6 +29,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     BlasTris, BLAS_TRIS_DTYPE, InstancedGeometry, instanced_hit_attributes, raygen_ao_normals,
                     BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats,
                     WideBlasRange, TlasWideResult, InstancedWideTraceStats, pool_widen_capacity, pool_widen, tlas_widen,
+                    pool_widen_batch, pool_widen_batch_scratch_bytes,
                     trace_instanced_wide, trace_instanced_wide_stats,
                     WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
                     tlas_wide_refit_scratch_bytes)
@@ -56,6 +57,7 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "BlasTris", "BLAS_TRIS_DTYPE", "InstancedGeometry", "instanced_hit_attributes", "raygen_ao_normals",
            "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats",
            "WideBlasRange", "TlasWideResult", "InstancedWideTraceStats", "pool_widen_capacity", "pool_widen", "tlas_widen",
+           "pool_widen_batch", "pool_widen_batch_scratch_bytes",
            "trace_instanced_wide", "trace_instanced_wide_stats",
            "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",
            "tlas_wide_refit_scratch_bytes"]

@@ -463,6 +463,8 @@ SYMBOLS = [
     ("ntr_trace_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp, C.POINTER(TraceStats)]),
     ("ntr_pool_widen_capacity", C.c_int, [_i32, _vp, C.POINTER(_i64)]),
     ("ntr_pool_widen", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(BvhWideResult), _vp]),
+    ("ntr_pool_widen_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(BvhWideResult), _vp]),
+    ("ntr_pool_widen_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_widen", C.c_int, [_i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, C.POINTER(TlasWideResult), _vp]),
     ("ntr_trace_instanced_wide", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                            C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
@@ -1249,6 +1251,24 @@ def pool_widen(ranges, d_pool_nodes, pool_nodes_bytes, d_wide_pool_nodes, capaci
     _check(lib().ntr_pool_widen(n, C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_wide_pool_nodes), int(capacity),
                                 C.cast(out, _vp), C.byref(res), _vp(stream)))
     return [(int(w.nodesOffset), int(w.nodesBytes), int(w.numNodes), int(w.stackBound)) for w in out[:n]], res
+
+
+def pool_widen_batch(ranges, d_pool_nodes, pool_nodes_bytes, d_wide_pool_nodes, capacity, stream=0):
+    """ntr_pool_widen_batch: pool_widen's arguments, bytes and return value, every BLAS in one pass -- the launches and read-backs
+    follow the tallest BLAS, not the number of BLASes.  On an overflow nothing is written (stricter than pool_widen's loop)."""
+    arr, n = _blas_ranges(ranges)
+    out = (WideBlasRange * max(n, 1))()
+    res = BvhWideResult()
+    _check(lib().ntr_pool_widen_batch(n, C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_wide_pool_nodes), int(capacity),
+                                      C.cast(out, _vp), C.byref(res), _vp(stream)))
+    return [(int(w.nodesOffset), int(w.nodesBytes), int(w.numNodes), int(w.stackBound)) for w in out[:n]], res
+
+
+def pool_widen_batch_scratch_bytes():
+    """ntr_pool_widen_batch_scratch_bytes: bytes the batched pool widening's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_pool_widen_batch_scratch_bytes(C.byref(v)))
+    return int(v.value)
 
 
 def tlas_widen(num_instances, d_instances, d_tlas_nodes, tlas_nodes_bytes, root_link, ranges, wide_ranges, d_wide_tlas_nodes, capacity,

@@ -2,7 +2,8 @@
 // and the top-level tree through ntr_bvh_widen, and the wide instance records.  EXTENSION without a reference counterpart: the rule is
 // the numpy spec tests/np_instanced_wide.py; instanced_wide_bvh.h states the layout.
 //   ntr_pool_widen   a host loop of ntr_bvh_widen, BLAS k at the sum of the exact extents before it.  Not batched: every BLAS pays the
-//                    pass's launches and read-backs (DESIGN.md 6r has what that costs for 1 024 BLASes)
+//                    pass's launches and read-backs (DESIGN.md 6r has what that costs for 1 024 BLASes).  The batched pass is
+//                    ntr_pool_widen_batch (pool_widen_batch_kernels.hip), which writes the same bytes
 //   ntr_tlas_widen   ntr_bvh_widen on the top-level nodes (none for one instance), then iw_records: a thread per instance copies
 //                    worldToObject and looks its BLAS up in a table of (wide offset, row offset, wide extent) -- zeros for a blas index
 //                    outside the table.  The table lives in the widening pass's scratch pool, which is idle once the pass has returned

@@ -1,5 +1,5 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
-// and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
+// and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen_batch (ntr_pool_widen for one BLAS) / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
 // ntr_trace_instanced_wide (see the header).
 #include "CudaInstancedBVH.hpp"
 
@@ -194,9 +194,12 @@ void CudaInstancedBVH::widen(void)
         if (ntr_pool_widen_capacity(numBlas, m_ranges.data(), &cap) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
         m_wideRanges.assign((size_t)numBlas, NtrWideBlasRange());
         m_widePoolNodes.resizeDiscard(cap);
-        if (ntr_pool_widen(numBlas, m_ranges.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_widePoolNodes.getMutableCudaPtr(), cap,
-                           m_wideRanges.data(), &m_widePoolResult, NULL) != NTR_OK)
-            fail("CudaInstancedBVH: %s", ntr_last_error());
+        // the same bytes either way; the batched pass costs launches by the tallest BLAS, the loop by the number of BLASes
+        const int rc = numBlas > 1 ? ntr_pool_widen_batch(numBlas, m_ranges.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(),
+                                                          m_widePoolNodes.getMutableCudaPtr(), cap, m_wideRanges.data(), &m_widePoolResult, NULL)
+                                   : ntr_pool_widen(numBlas, m_ranges.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(),
+                                                    m_widePoolNodes.getMutableCudaPtr(), cap, m_wideRanges.data(), &m_widePoolResult, NULL);
+        if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
         m_widePool = true;
     }
     m_wideTlas = false;

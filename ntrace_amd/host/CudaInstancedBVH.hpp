@@ -24,7 +24,7 @@
 //                 instance i only if (mask_i & rayMask) != 0 (ntr_trace_instanced_masked); with no masks set and the default ray mask
 //                 the call is ntr_trace_instanced's
 //   widen          valid once isBuilt(): widens the pool into a second node buffer if the pool changed since the last widen()
-//                 (ntr_pool_widen), and the TLAS and the records always (ntr_tlas_widen).  build() and refit() drop the wide TLAS;
+//                 (ntr_pool_widen_batch; ntr_pool_widen for a pool of one BLAS: the same bytes), and the TLAS and the records always (ntr_tlas_widen).  build() and refit() drop the wide TLAS;
 //                 refitBLASes, buildBLASes and addBLAS drop the wide pool too: widen again after them.  The binary pool, TLAS and
 //                 records stay what they are
 //   refitBLASesWide   refitBLASes, then the same selection of the wide pool in place by ntr_pool_wide_refit (rewriteRows 0:

@@ -24,6 +24,12 @@ frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they we
                triangle tests), the algorithmic bytes over the median as a fraction of 8 TB/s, and how many records differ between the
                two paths (the spec's known limit, reported and not asserted).  Then what widening costs: the frame's own pool and TLAS,
                and ntr_pool_widen's loop over a pool of 1 024 BLASes of 1 000 triangles each (built by ntr_ploc_build_batch)
+  * widen_batch (not in the default parts) ntr_pool_widen_batch beside ntr_pool_widen's loop, ALTERNATED in this process, over
+               pools of 1 024 BLASes of 1 000 triangles (6r's pool), 16 384 of 64, 64 of 16 384 and one of 2^20 (the pool shapes of 6m and
+               6n), each BLAS a copy of one soup built by ntr_ploc_build_batch: GPU time (the calls' own seconds) and wall time (around the
+               entry point itself, on range arrays made once), median, min and max, and the kernel launches and read-backs each call takes -- derived from the trees' heights by the rule of
+               the two host loops (widen_counts below; every BLAS of a pool is the same tree, so the pool's height is each BLAS's).  The
+               two wide pools, the ranges and the result fields are asserted equal before anything is timed
   * wide_sweep (not in the default parts) the primary batch of `wide` over k x k x k grids of soup1000 for k = 1, 2, 4, 8, 16 (the last is
                the forest), the camera moved back with the grid: where in instance count the wide path starts to pay
 Prints one JSON line per part.
@@ -186,6 +192,20 @@ def median_event_ms(fn, reps, warmup):
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
     return float(np.median(ms[warmup:]))
+
+
+def widen_counts(height, slots, batch_entries=0):
+    """(kernel launches, read-backs) of one ntr_bvh_widen of a tree of `slots` slots and `height` wide levels -- or, with batch_entries,
+    of one ntr_pool_widen_batch whose tallest BLAS that tree is.  Both host loops launch mark + close per level, four levels at a time,
+    and read the next level's extent back after each four until it is empty.  Around that: the seed launch, the two scan launches and
+    the emit launch (the batch: the entry-table launch on top), and the read-back of the report (the batch's carries the entry table)."""
+    level, readbacks = 0, 0
+    while True:
+        level = min(level + 4, slots)
+        readbacks += 1
+        if level >= height or level >= slots:
+            break
+    return 1 + 2 * level + (4 if batch_entries else 3), readbacks + 1
 
 
 def host_ao_rays(rays, res, count, seed, radius=5.0):
@@ -420,6 +440,66 @@ def main():
                 "wide_pool_bytes": int(r.nodesBytes), "gpu_ms_median": float(np.median(gpu)) * 1e3, "gpu_ms_min": float(min(gpu)) * 1e3,
                 "gpu_ms_max": float(max(gpu)) * 1e3, "wall_ms_median": float(np.median(wall)) * 1e3, "wall_ms_min": float(min(wall)) * 1e3,
                 "wall_ms_max": float(max(wall)) * 1e3, "wall_us_per_blas": float(np.median(wall)) * 1e6 / num_blas}
+
+    def widen_batch_row(num_blas, tris_per_blas):
+        """ntr_pool_widen's loop and ntr_pool_widen_batch, alternated, over num_blas copies of one soup of tris_per_blas triangles."""
+        tri, pos = scenes.random_soup(tris_per_blas, seed=1100 + tris_per_blas, walls=False)[:2]
+        tri, pos = np.ascontiguousarray(tri, np.int32), np.ascontiguousarray(pos, F)
+        nt_, nv = tri.shape[0], pos.shape[0]
+        k = np.arange(num_blas)
+        all_tri = (tri[None, :, :] + (k * nv)[:, None, None]).reshape(-1, 3).astype(np.int32)
+        all_pos = np.tile(pos, (num_blas, 1)).astype(F)
+        mn, mx = pos.min(axis=0), pos.max(axis=0)
+        meshes = [(int(i * nt_), int(nt_), mn, mx) for i in k]
+        cn, cw, ci, _ = nt.ploc_batch_capacity(meshes)
+        d_tri, d_pos = up(all_tri), up(all_pos)
+        bufs = [torch.zeros(c, dtype=torch.uint8, device="cuda:0") for c in (cn, cw, ci)]
+        out = nt.ploc_build_batch(meshes, all_tri.shape[0], d_tri.data_ptr(), all_pos.shape[0], d_pos.data_ptr(), bufs[0].data_ptr(), cn,
+                                  bufs[1].data_ptr(), cw, bufs[2].data_ptr(), ci, 8, stream)
+        ranges = out[1]
+        cap = nt.pool_widen_capacity(ranges)
+        d_loop, d_batch = (torch.full((cap,), 0xAB, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+        calls = {"loop": lambda: nt.pool_widen(ranges, bufs[0].data_ptr(), cn, d_loop.data_ptr(), cap, stream),
+                 "batch": lambda: nt.pool_widen_batch(ranges, bufs[0].data_ptr(), cn, d_batch.data_ptr(), cap, stream)}
+        (lr, l), (br, b) = calls["loop"](), calls["batch"]()
+        torch.cuda.synchronize()
+        fields = lambda r: (r.nodesBytes, r.numNodes, list(r.counts), r.numLeafLinks, r.height, r.stackBound)   # noqa: E731
+        assert lr == br and fields(l) == fields(b), "the batch's ranges or result differ from the loop's"
+        assert torch.equal(d_loop, d_batch), "the batch's wide pool differs from the loop's"
+        # timed: the entry points themselves, on range arrays made once (the binding's list conversions are 16 384 Python objects a call)
+        import ctypes as C
+        arr = (nt.BlasRange * num_blas)(*[nt.BlasRange(*[int(x) for x in r]) for r in ranges])
+        w_out, r = (nt.WideBlasRange * num_blas)(), nt.BvhWideResult()
+        raw = {"loop": (nt.lib().ntr_pool_widen, d_loop), "batch": (nt.lib().ntr_pool_widen_batch, d_batch)}
+        gpu, wall = {"loop": [], "batch": []}, {"loop": [], "batch": []}
+        for _ in range(args.warmup + args.reps):          # alternated
+            for name in ("loop", "batch"):
+                fn, d_out = raw[name]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                rc = fn(num_blas, C.cast(arr, C.c_void_p), bufs[0].data_ptr(), cn, d_out.data_ptr(), cap, C.cast(w_out, C.c_void_p), C.byref(r),
+                        C.c_void_p(stream))
+                wall[name].append(time.perf_counter() - t0)
+                assert rc == 0, nt.lib().ntr_last_error()
+                gpu[name].append(r.seconds)
+        slots = ranges[0][1] // 64
+        one = widen_counts(b.height, slots)
+        row = {"part": "widen_batch", "blases": num_blas, "tris_per_blas": int(nt_), "slots_per_blas": int(slots), "height": int(b.height),
+               "binary_pool_bytes": int(cn), "wide_pool_bytes": int(b.nodesBytes), "bytes_equal": True,
+               "batch_scratch_bytes": nt.pool_widen_batch_scratch_bytes()}
+        for name, (launches, readbacks) in (("loop", (num_blas * one[0], num_blas * one[1])), ("batch", widen_counts(b.height, slots, num_blas))):
+            g, w = gpu[name][args.warmup:], wall[name][args.warmup:]
+            row[name] = {"gpu_ms_median": float(np.median(g)) * 1e3, "gpu_ms_min": float(min(g)) * 1e3, "gpu_ms_max": float(max(g)) * 1e3,
+                         "wall_ms_median": float(np.median(w)) * 1e3, "wall_ms_min": float(min(w)) * 1e3, "wall_ms_max": float(max(w)) * 1e3,
+                         "launches": int(launches), "readbacks": int(readbacks)}
+        row["single_widen_launches"], row["single_widen_readbacks"] = one
+        row["wall_loop_over_batch"] = row["loop"]["wall_ms_median"] / row["batch"]["wall_ms_median"]
+        return row
+
+    if "widen_batch" in args.parts:
+        for num_blas, tris_per_blas in ((1024, 1000), (16384, 64), (64, 16384), (1, 1 << 20)):
+            emit(step("widen_batch %d x %d" % (num_blas, tris_per_blas), args.limit, lambda: widen_batch_row(num_blas, tris_per_blas)))
+            nt.lbvh_release_workspace()
 
     if "identity" in args.parts or "masks" in args.parts or "wide" in args.parts:
         tri, pos, cam = scenes.atrium()
