@@ -464,7 +464,9 @@ NTR_API int ntr_lbvh_capacity(int32_t numTris, int64_t* nodesBytes, int64_t* tri
  * emit -> bottom-up refit, all on the device, into caller-owned BVHLayout_Compact buffers of at least
  * ntr_lbvh_capacity() bytes.  d_triVtxIndex: 3 ints per triangle, d_vtxPos: 3 floats per vertex
  * (Scene::getTriVtxIndexBuffer / getVtxPosBuffer), sceneMin/Max = Scene::getBBox.  Renderer passes
- * leafSize 8, epsilon 0.001 (Renderer.cpp:203-207).  Blocking. */
+ * leafSize 8, epsilon 0.001 (Renderer.cpp:203-207).  Blocking: the call reads counts back and
+ * synchronises the stream, so a stream that is being captured is refused with NTR_ERR_INVALID before
+ * anything is allocated or launched (the capture stays valid and the outputs untouched). */
 NTR_API int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
                            const float sceneMin[3], const float sceneMax[3], int32_t leafSize, float epsilon,
                            void* d_nodes, int64_t nodesCapacity, void* d_triWoop, int64_t triWoopCapacity,
@@ -487,7 +489,9 @@ typedef struct NtrHlbvhResult {
  * 0..10 (anything else is NTR_ERR_INVALID; 10 is ntr_lbvh_build).  Same Compact conventions, capacities (ntr_lbvh_capacity) and
  * stream rules as ntr_lbvh_build; Renderer's HLBVH setup is hlbvhBits 4, leafSize 8, epsilon 0.001 (Renderer.cpp:201-209).  The
  * tree equals the restatement tests/np_hlbvh.py in canonical form; its header lists the canonical choices where the reference is
- * nondeterministic or broken.  Blocking. */
+ * nondeterministic or broken.  Blocking (one read-back after the clusters, one per eight top levels, one at the end); as
+ * ntr_lbvh_build, a capturing stream is refused with NTR_ERR_INVALID before any allocation or launch.  On the cluster path
+ * (hlbvhBits < 10 and numTris > leafSize) no byte of the output buffers past the reported extents is written. */
 NTR_API int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos,
                             const float sceneMin[3], const float sceneMax[3], int32_t leafSize, float epsilon, int32_t hlbvhBits,
                             void* d_nodes, int64_t nodesCapacity, void* d_triWoop, int64_t triWoopCapacity,

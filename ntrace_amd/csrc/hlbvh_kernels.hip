@@ -543,6 +543,8 @@ int ntr_hlbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVe
         return rc;
     const int n = numTris;
     if (n >= (1 << 27)) return set_error(NTR_ERR_INVALID, "ntr_hlbvh_build: at most 2^27 - 1 triangles");
+    if (stream_is_capturing((hipStream_t)stream))
+        return set_error(NTR_ERR_INVALID, "ntr_hlbvh_build: the call reads its counts back and cannot be captured");
     // HLBVHBuilder.cpp:44-47: hlbvhBits == 10 is buildLBVH; n <= leafSize is the LBVH's single root too (canonical)
     if (hlbvhBits == 10 || n <= leafSize) {
         const int rc = ntr_lbvh_build(numTris, d_triVtxIndex, numVerts, d_vtxPos, sceneMin, sceneMax, leafSize, epsilon, d_nodes, nodesCapacity,

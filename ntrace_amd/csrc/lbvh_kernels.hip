@@ -1134,6 +1134,7 @@ int ntr_lbvh_build(int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVer
     hipStream_t s = (hipStream_t)stream;
     const int n = numTris;
     if (n >= (1 << 28)) return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: at most 2^28 - 1 triangles");
+    if (stream_is_capturing(s)) return set_error(NTR_ERR_INVALID, "ntr_lbvh_build: the call reads its counts back and cannot be captured");
     const Tunables tun = tunables();
     const int osItems = onesweep_items(n);
     const int osTiles = (n + OS_THREADS * osItems - 1) / (OS_THREADS * osItems);

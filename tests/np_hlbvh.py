@@ -46,6 +46,17 @@ from oracle import oracle
 F32 = np.float32
 FLT_MAX = F32(np.finfo(np.float32).max)
 BINS = 8
+NAN_BIN = 0            # canonical choice 1; a name of its own so that a test can show which scenes tell it from 7
+
+
+def missed_cnt_right(m):
+    """Canonical choice 2: clusters that go right when a task of m clusters misses its split."""
+    return m // 2
+
+
+def left_of_plane(bins_a, b):
+    """Plane b of an axis has bins 0..b on its left (emitTreeKernel.cu:940-1027, `bin <= split`)."""
+    return bins_a <= b
 
 
 def f2i(a):
@@ -141,7 +152,7 @@ def find_split(cl_lo, cl_hi, t_lo, t_hi):
         step = ((t_hi - t_lo) / F32(BINS)).astype(np.float32)
         q = ((mid - t_lo) / step).astype(np.float32)
     f = np.floor(q)
-    bins = np.where(q != q, 0, np.where(f >= 7, 7, np.where(f <= 0, 0, np.nan_to_num(f)))).astype(np.int64).reshape(m, 3)
+    bins = np.where(q != q, NAN_BIN, np.where(f >= 7, 7, np.where(f <= 0, 0, np.nan_to_num(f)))).astype(np.int64).reshape(m, 3)
     lo_i, hi_i = f2i(cl_lo), f2i(cl_hi)
     # bin boxes in the f2i order, empty bins +-FLT_MAX (initBins, :695-711)
     b_lo = np.full((3, BINS, 3), FLT_MAX, np.float32)
@@ -186,12 +197,13 @@ def find_split(cl_lo, cl_hi, t_lo, t_hi):
         box = (b_lo[0, b0].copy(), b_hi[0, b0].copy())
         return 0, None, box, box, bins
     a, b, bl, br = win
-    return a, bins[:, a] <= b, bl, br, bins
+    return a, left_of_plane(bins[:, a], b), bl, br, bins
 
 
 def hlbvh_build(tri, pos, bits, leaf_size=8, epsilon=0.001, bbox=None):
     """Returns dict(nodes (uint8), woop (uint8), tri_index (int32), num_inner, num_leaves, num_clusters, top_nodes, top_levels,
-    lbvh_path, structure) -- Compact buffers like oracle.lbvh_build; `structure` is the decision record used by the tests."""
+    lbvh_path, structure, decisions) -- Compact buffers like oracle.lbvh_build; `structure` is the decision record used by the tests,
+    `decisions` says per top-level task its level, its range of cluster positions and whether its split was missed."""
     tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
     pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
     n = tri.shape[0]
@@ -202,7 +214,7 @@ def hlbvh_build(tri, pos, bits, leaf_size=8, epsilon=0.001, bbox=None):
     mx = np.ascontiguousarray(mx, dtype=np.float32)
     if bits == 10 or n <= leaf_size:                  # canonical 5
         r = oracle.lbvh_build(tri, pos, leaf_size, epsilon, bbox=(mn, mx))
-        r.update(num_clusters=0, top_nodes=0, top_levels=0, lbvh_path=True, structure=None)
+        r.update(num_clusters=0, top_nodes=0, top_levels=0, lbvh_path=True, structure=None, decisions=None)
         return r
     keys, ts = morton_sorted(tri, pos, mn, mx)
     woop12 = woop_rows(tri, pos)
@@ -223,27 +235,32 @@ def hlbvh_build(tri, pos, bits, leaf_size=8, epsilon=0.001, bbox=None):
     top_levels = 0
     top_nodes = 0
     structure = []
+    decisions = []                                    # per top-level task: level, node, cluster positions [beg, end), missed, axis
     if C_ < 2:                                        # canonical 4
         bottom_roots.append((0, 0, n))
     else:
-        tasks = [(0, list(range(C_)), (mn.copy(), mx.copy()))]   # (node, clusters in order, task box)
+        # (node, clusters in order, task box, first position): a stable partition keeps a task's clusters in one range of positions
+        tasks = [(0, list(range(C_)), (mn.copy(), mx.copy()), 0)]
         while tasks:
             top_levels += 1
             nxt = []
-            for node, cls, (tlo, thi) in tasks:
+            for node, cls, (tlo, thi), beg in tasks:
                 top_nodes += 1
                 cls = np.array(cls)
                 axis, left, bl, br, _ = find_split(cl_lo[cls], cl_hi[cls], tlo, thi)
-                if left is None:
-                    cnt_r = len(cls) // 2
+                missed = left is None
+                if missed:
+                    cnt_r = missed_cnt_right(len(cls))
                     left = np.arange(len(cls)) < len(cls) - cnt_r
                 parts = (cls[left], cls[~left])
                 structure.append((node, axis, [list(map(int, p)) for p in parts]))
+                decisions.append(dict(level=top_levels - 1, node=node, beg=beg, end=beg + len(cls), missed=missed, axis=axis,
+                                      cnt_l=len(parts[0])))
                 ch = []
-                for part, box in zip(parts, (bl, br)):
+                for part, box, pbeg in zip(parts, (bl, br), (beg, beg + len(parts[0]))):
                     if len(part) > 1:
                         k = new_node()
-                        nxt.append((k, list(part), box))
+                        nxt.append((k, list(part), box, pbeg))
                         ch.append(("node", k))
                     else:
                         c = int(part[0])
@@ -364,7 +381,7 @@ def hlbvh_build(tri, pos, bits, leaf_size=8, epsilon=0.001, bbox=None):
     wb = (n * 3 + num_leaves) * 16
     return dict(nodes=out_nodes.reshape(-1).view(np.uint8).copy(), woop=woop.reshape(-1).view(np.uint8)[:wb].copy(),
                 tri_index=tidx[:n * 3 + num_leaves].copy(), num_inner=num, num_leaves=num_leaves, num_clusters=C_,
-                top_nodes=top_nodes, top_levels=top_levels, lbvh_path=False, structure=structure,
+                top_nodes=top_nodes, top_levels=top_levels, lbvh_path=False, structure=structure, decisions=decisions,
                 tri_sorted=ts, morton_sorted=keys, cluster_starts=starts, bottom_roots=bottom_roots, tree=nodes)
 
 

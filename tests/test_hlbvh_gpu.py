@@ -1,8 +1,12 @@
 """On-device HLBVH build (ntr_hlbvh_build) against the restatement tests/np_hlbvh.py, in canonical form, and traces through its trees."""
+import time
+
 import numpy as np
 import pytest
 
+import hlbvh_scenes as S
 import np_hlbvh as H
+import ray_sets
 import ntrace_amd as nt
 from ntrace_amd import scenes
 from oracle import oracle
@@ -38,10 +42,17 @@ def hash_of(t):
     return oracle.bvh_canonical_hash(t["nodes"], t["woop"], t["tri_index"])
 
 
+def assert_same_tree(got, ref, what):
+    """The canonical hash is the criterion; on a mismatch the message names the first differing node."""
+    if hash_of(got) != H.canonical_hash(ref):
+        ref_bufs = dict(nodes=ref["nodes"], woop=ref["woop"], tri_index=ref["tri_index"])
+        pytest.fail("%s: canonical hashes differ; %s" % (what, S.first_difference(got, ref_bufs) or "no node differs in the walk"))
+
+
 def check_same(tri, pos, bits, leaf_size, bbox=None):
     ref = H.hlbvh_build(tri, pos, bits, leaf_size=leaf_size, bbox=bbox)
     got = dev_build(tri, pos, bits, leaf_size, bbox=bbox)
-    assert hash_of(got) == H.canonical_hash(ref), (tri.shape[0], bits, leaf_size)
+    assert_same_tree(got, ref, (tri.shape[0], bits, leaf_size))
     r = got["res"]
     assert r.lbvh.numNodes == ref["num_inner"] and r.lbvh.numLeaves == ref["num_leaves"]
     assert r.lbvh.nodesBytes == ref["nodes"].nbytes and r.lbvh.triWoopBytes == ref["woop"].nbytes
@@ -154,3 +165,144 @@ def test_trace_parity_on_hlbvh_trees():
             assert np.array_equal(got["id"], ref["id"]), (kernel, name)
             assert np.array_equal(got["t"].view(np.uint32), ref["t"].view(np.uint32)), (kernel, name)
     assert hit.any()
+
+
+# ---- the named scenes of hlbvh_scenes.py: kernel seams and decision cases (their claims are asserted on the CPU tier) ----
+def build_scene(name):
+    tri, pos, bits, leaf_size, eps, bbox = S.scene(name)
+    return dev_build(tri, pos, bits, leaf_size, eps=eps, bbox=bbox)
+
+
+def fields(t):
+    r = t["res"]
+    return (r.numClusters, r.topLevels, r.topNodes, r.lbvh.numNodes, r.lbvh.numLeaves, r.lbvh.nodesBytes, r.lbvh.triWoopBytes,
+            r.lbvh.triIndexBytes)
+
+
+def spec_fields(ref):
+    top = (0, 0, 0) if ref["lbvh_path"] else (ref["num_clusters"], ref["top_levels"], ref["top_nodes"])
+    return top + (ref["num_inner"], ref["num_leaves"], ref["nodes"].nbytes, ref["woop"].nbytes, ref["tri_index"].nbytes)
+
+
+@pytest.mark.parametrize("name", list(S.SCENES))
+def test_named_scene_matches_restatement(name):
+    t0 = time.perf_counter()
+    ref = S.build_spec(name)      # built anew, so that the printed time is a build's and not a cache look-up's
+    t1 = time.perf_counter()
+    got = build_scene(name)
+    t2 = time.perf_counter()
+    print("%s (%s): spec %.2f s, device %.3f s" % (name, S.claim(name), t1 - t0, t2 - t1))
+    assert_same_tree(got, ref, name)
+    assert fields(got) == spec_fields(ref), name
+
+
+def test_builds_are_the_same_on_every_stream_and_after_a_release():
+    name = "cluster_box"
+    ref = S.spec(name)
+    seen = []
+    for stream in (None, torch.cuda.Stream(), torch.cuda.Stream()):
+        if stream is None:
+            t = build_scene(name)
+        else:
+            with torch.cuda.stream(stream):
+                t = build_scene(name)
+        seen.append((hash_of(t), fields(t)))
+    nt.lbvh_release_workspace()
+    t = build_scene(name)
+    seen.append((hash_of(t), fields(t)))
+    assert seen == [(H.canonical_hash(ref), spec_fields(ref))] * 4
+
+
+@pytest.mark.parametrize("name", ["part_c1025", "cluster_box", "leaf_exact"])
+def test_exact_capacity_is_enough_and_nothing_else_is_written(name):
+    """part_c1025 is the worst case of the capacity (bits 0 and leaf size 1 give n leaves and n - 1 inner nodes); the other two leave
+    real slack between the reported extents and the capacity (leaf size 4), which must keep its prefill."""
+    tri, pos, bits, leaf_size, eps, bbox = S.scene(name)
+    n = tri.shape[0]
+    ref = S.spec(name)
+    worst = name == "part_c1025"
+    assert (bits == 0 and leaf_size == 1 and ref["num_leaves"] == n and ref["num_inner"] == n - 1) == worst
+    caps = nt.lbvh_capacity(n)
+    guard, fill = 4096, 0xAB
+    d_tri, d_pos = up(tri), up(pos)
+    bufs = [torch.full((c + 2 * guard,), fill, dtype=torch.uint8, device="cuda") for c in caps]
+    ptrs = [b.data_ptr() + guard for b in bufs]
+    res = nt.hlbvh_build(n, d_tri.data_ptr(), pos.shape[0], d_pos.data_ptr(), bbox[0], bbox[1], leaf_size, eps, bits, ptrs[0], caps[0],
+                         ptrs[1], caps[1], ptrs[2], caps[2], torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    host = [b.cpu().numpy() for b in bufs]
+    ext = (res.lbvh.nodesBytes, res.lbvh.triWoopBytes, res.lbvh.triIndexBytes)
+    assert ext == (ref["nodes"].nbytes, ref["woop"].nbytes, ref["tri_index"].nbytes)
+    if worst:
+        assert ext == (64 * (n - 1), 16 * 4 * n, 4 * 4 * n)
+    else:      # at least a quarter of the node slots and a tenth of the entries stay unused
+        assert ext[0] < 0.75 * caps[0] and ext[1] < 0.9 * caps[1] and ext[2] < 0.9 * caps[2]
+    for h, c, e in zip(host, caps, ext):
+        assert e <= c
+        assert (h[:guard] == fill).all() and (h[guard + c:] == fill).all()      # nothing outside the capacity
+        assert (h[guard + e:guard + c] == fill).all()                            # nor past the reported extents (see the header)
+    got = dict(nodes=host[0][guard:guard + ext[0]], woop=host[1][guard:guard + ext[1]],
+               tri_index=host[2][guard:guard + ext[2]].copy().view(np.int32), res=res)
+    assert_same_tree(got, ref, name)
+
+
+@pytest.mark.parametrize("name", ["cluster_box", "missed_1025", "host_slivers"])
+def test_traces_through_named_trees_match_the_oracle(name):
+    tri, pos = S.scene(name)[:2]
+    t = build_scene(name)
+    assert_same_tree(t, S.spec(name), name)
+    d_nodes, d_woop, d_idx = up(t["nodes"]), up(t["woop"]), up(t["tri_index"])
+    view = nt.BvhView(d_nodes.data_ptr(), t["nodes"].nbytes, d_woop.data_ptr(), t["woop"].nbytes, d_idx.data_ptr())
+    view.validate()
+    edge = ray_sets.edge_rays()
+    rays = np.concatenate([edge, S.aimed_rays(tri, pos, 4096 - edge.shape[0], 11)])
+    assert rays.shape[0] == 4096
+    d_rays = up(rays)
+    refs = {any_hit: oracle.trace(t["nodes"], t["woop"], t["tri_index"], rays, any_hit=any_hit)[0] for any_hit in (False, True)}
+    assert (refs[False]["id"] >= 0).sum() > 500
+    for kernel in nt.KERNELS:
+        for any_hit in (False, True):
+            d_res = torch.zeros(rays.shape[0] * 16, dtype=torch.uint8, device="cuda")
+            view.trace(kernel, rays.shape[0], any_hit, d_rays.data_ptr(), d_res.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            got = d_res.cpu().numpy().view(nt.RESULT_DTYPE)
+            assert np.array_equal(got["id"], refs[any_hit]["id"]), (kernel, any_hit)
+            assert np.array_equal(got["t"].view(np.uint32), refs[any_hit]["t"].view(np.uint32)), (kernel, any_hit)
+
+
+def test_a_capturing_stream_is_refused():
+    """Both builds read counts back and synchronise: inside a capture they are refused before anything is allocated or launched, the
+    capture stays valid and replays, and the output buffers keep their prefill."""
+    tri, pos, bits, leaf_size, eps, bbox = S.scene("leaf_exact")
+    n = tri.shape[0]
+    caps = nt.lbvh_capacity(n)
+    d_tri, d_pos = up(tri), up(pos)
+    outs = [torch.full((c,), 0xAB, dtype=torch.uint8, device="cuda") for c in caps]
+    marker = torch.zeros(64, dtype=torch.uint8, device="cuda")
+    nt.lbvh_release_workspace()      # a call that got past the check would have to allocate
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    errs = []
+    with torch.cuda.graph(g, stream=s):
+        cs = torch.cuda.current_stream().cuda_stream
+        marker.fill_(7)              # the one other node of the graph
+        for call in ("hlbvh", "lbvh"):
+            args = (n, d_tri.data_ptr(), pos.shape[0], d_pos.data_ptr(), bbox[0], bbox[1], leaf_size, eps)
+            tail = (outs[0].data_ptr(), caps[0], outs[1].data_ptr(), caps[1], outs[2].data_ptr(), caps[2], cs)
+            try:
+                if call == "hlbvh":
+                    nt.hlbvh_build(*args, bits, *tail)
+                else:
+                    nt.lbvh_build(*args, *tail)
+            except nt.NtrError as e:
+                errs.append((call, e.code, "captured" in str(e)))
+    assert errs == [("hlbvh", -1, True), ("lbvh", -1, True)]
+    torch.cuda.synchronize()
+    assert int(marker.max()) == 0    # captured, not run
+    g.replay()
+    torch.cuda.synchronize()
+    assert (marker == 7).all()
+    for o in outs:
+        assert (o == 0xAB).all()
+    # and outside a capture the same arguments build
+    assert_same_tree(build_scene("leaf_exact"), S.spec("leaf_exact"), "after the capture")
