@@ -1121,6 +1121,61 @@ NTR_API int ntr_trace_instanced_wide_stats(int32_t numRays, int32_t anyHit, cons
                                            const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* may be NULL */,
                                            NtrInstancedTraceStats* stats, void* stream);
 
+/* A static world beside the instances: the seeded two-level trace (csrc/trace_instanced_seeded_kernels.hip,
+ * csrc/trace_instanced_wide_seeded_kernels.hip).  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_seeded.py, which the device equals in all four result words, the instance id and every counter.
+ * Intended use: a large static world is ONE BLAS of the pool, in its own space, and no instance.  Per batch, on one stream or in one
+ * graph: ntr_trace_bvh on that BLAS's range of the pool (nodes at d_poolNodes + nodesOffset, rows at d_poolTriWoop + triWoopOffset,
+ * indices at d_poolTriIndex + triWoopOffset / 16 -- a BLAS of a pool is byte for byte a Compact tree there) writes one record per ray;
+ * the seeded call then traces the moving instances starting from those records.  The world pays the single-level kernel's price, and
+ * the two-level kernel sees rays that are already as short as the world makes them.
+ *   seed        d_seedResults[r] is ray r's record so far, four words (id, t, w2, w3).  s_hit = (id != -1).
+ *   start       tmax0 = seed.t if s_hit, else the ray's tmax; the hit record starts as the seed's four words; the instance id starts
+ *               as seedInstance if s_hit, else -1.  !(tmin < tmax0): no traversal (the degenerate rule, applied to tmax0).  anyHit
+ *               and s_hit: no traversal.
+ *   traversal   ntr_trace_instanced_masked's (ntr_trace_instanced_wide's), unchanged, from that state: masks, exit marker, the stack
+ *               of 104, counters.  An accepted hit overwrites all four words and the instance id, as in the unseeded trace.
+ *   no hit      a ray whose traversal accepts nothing ends with the seed's four words verbatim -- w2 and w3 are not interpreted, and
+ *               a seed that is a miss keeps its own t, not the ray's -- and with seedInstance (s_hit) or -1.
+ *   seed.t      taken as it is: a NaN, an infinity or a negative t makes the ray degenerate or not by the comparison above and nothing
+ *               else.  Whatever the seed holds, nothing outside the buffers is read.
+ *   seedInstance  any int32, stored verbatim.  With the world's NtrInstance appended behind the N instances (identity both ways, blas
+ *               = the world's), seedInstance = N lets ntr_instanced_hit_attributes resolve world hits with numInstances = N + 1.
+ *   counters    ntr_trace_instanced_stats's; numHits counts the final records with id != -1.  Algorithmic bytes: the unseeded formula
+ *               + 16 numRays (the seed read).
+ * d_results may equal d_seedResults: each lane reads its own record before it writes it.  seconds == NULL is asynchronous on `stream`
+ * and capturable; the call allocates nothing and reads nothing back.  The seeded kernels are the masked loop whatever vis holds.  The
+ * _stats forms block and are refused on a capturing stream.  Errors: NTR_ERR_INVALID before any device work for everything the
+ * unseeded sibling refuses, a null d_seedResults and a d_seedResults that is not 16-byte aligned; numRays == 0 returns NTR_OK.
+ * Without a device, after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+NTR_API int ntr_trace_instanced_seeded(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                       int32_t seedInstance, NtrRayResult* d_results /* may equal d_seedResults */, int32_t* d_instanceIDs,
+                                       const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                       int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                       int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                       const NtrInstanceVisibility* vis /* NULL: no masks */, float* seconds /* NULL: asynchronous */,
+                                       void* stream);
+NTR_API int ntr_trace_instanced_seeded_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                             int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs, const void* d_tlasNodes,
+                                             int64_t tlasNodesBytes, int32_t rootLink, const void* d_records, int32_t numInstances,
+                                             const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                             int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                             const NtrInstanceVisibility* vis /* may be NULL */, NtrInstancedTraceStats* stats, void* stream);
+NTR_API int ntr_trace_instanced_wide_seeded(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                            int32_t seedInstance, NtrRayResult* d_results /* may equal d_seedResults */,
+                                            int32_t* d_instanceIDs, const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink,
+                                            const void* d_wideRecords, int32_t numInstances, const void* d_widePoolNodes,
+                                            int64_t widePoolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                                            const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* NULL: no masks */,
+                                            float* seconds /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_trace_instanced_wide_seeded_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                                  int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                                  const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink,
+                                                  const void* d_wideRecords, int32_t numInstances, const void* d_widePoolNodes,
+                                                  int64_t widePoolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                                                  const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* may be NULL */,
+                                                  NtrInstancedTraceStats* stats, void* stream);
+
 /* In-place refit of 4-wide trees: the update path of an animated instanced frame for the wide two-level trace
  * (csrc/wide_refit_batch_kernels.hip, csrc/tlas_wide_refit_kernels.hip, csrc/wide_climb.h).  ntr_pool_widen and
  * ntr_tlas_widen block, read back and may change a wide tree's topology from frame to frame; these two calls keep the wide topology

@@ -31,6 +31,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     WideBlasRange, TlasWideResult, InstancedWideTraceStats, pool_widen_capacity, pool_widen, tlas_widen,
                     pool_widen_batch, pool_widen_batch_scratch_bytes,
                     trace_instanced_wide, trace_instanced_wide_stats,
+                    trace_instanced_seeded, trace_instanced_seeded_stats, trace_instanced_wide_seeded, trace_instanced_wide_seeded_stats,
                     WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
                     tlas_wide_refit_scratch_bytes)
 
@@ -59,5 +60,6 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "WideBlasRange", "TlasWideResult", "InstancedWideTraceStats", "pool_widen_capacity", "pool_widen", "tlas_widen",
            "pool_widen_batch", "pool_widen_batch_scratch_bytes",
            "trace_instanced_wide", "trace_instanced_wide_stats",
+           "trace_instanced_seeded", "trace_instanced_seeded_stats", "trace_instanced_wide_seeded", "trace_instanced_wide_seeded_stats",
            "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",
            "tlas_wide_refit_scratch_bytes"]

@@ -470,6 +470,14 @@ SYMBOLS = [
                                            C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
     ("ntr_trace_instanced_wide_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                                  C.POINTER(InstanceVisibility), C.POINTER(InstancedWideTraceStats), _vp]),
+    ("ntr_trace_instanced_seeded", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                             C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_seeded_stats", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                   C.POINTER(InstanceVisibility), C.POINTER(InstancedTraceStats), _vp]),
+    ("ntr_trace_instanced_wide_seeded", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                  C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_wide_seeded_stats", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64,
+                                                        _vp, C.POINTER(InstanceVisibility), C.POINTER(InstancedWideTraceStats), _vp]),
     ("ntr_pool_wide_refit", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.POINTER(WideRefitResult), _vp]),
     ("ntr_pool_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_wide_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
@@ -1311,6 +1319,65 @@ def trace_instanced_wide_stats(num_rays, any_hit, d_rays, d_results, d_instance_
                                                 int(num_instances), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes), _vp(d_pool_woop),
                                                 int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
                                                 C.byref(st), _vp(stream)))
+    return st
+
+
+def _trace_seeded(fn, out, num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes,
+                  root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream):
+    _check(fn(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance), _vp(d_results), _vp(d_instance_ids),
+              _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances), _vp(d_pool_nodes),
+              int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
+              out, _vp(stream)))
+
+
+def trace_instanced_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes,
+                           root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index,
+                           vis=None, stream=0, timed=True):
+    """ntr_trace_instanced_seeded: trace_instanced_masked started from one result record per ray (the rule is
+    tests/np_instanced_seeded.py): tmax from a seed that is a hit, an any-hit ray whose seed is a hit never starts, a ray that accepts
+    nothing keeps the seed's four words and, for a hit, seed_instance.  d_results may be d_seed_results.  The intended seed is trace_bvh
+    of the world BLAS's range of the pool.  timed=True returns the GPU seconds; timed=False is asynchronous on `stream` (capturable) and
+    returns None."""
+    sec = C.c_float(0.0)
+    _trace_seeded(lib().ntr_trace_instanced_seeded, C.byref(sec) if timed else None, num_rays, any_hit, d_rays, d_seed_results, seed_instance,
+                  d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
+                  d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
+    return float(sec.value) if timed else None
+
+
+def trace_instanced_seeded_stats(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_tlas_nodes,
+                                 tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop,
+                                 pool_woop_bytes, d_pool_tri_index, vis=None, stream=0):
+    """ntr_trace_instanced_seeded_stats: trace_instanced_seeded's records through the instrumented kernel -> InstancedTraceStats (the
+    seed read adds 16 B per ray to algorithmic_bytes).  Blocks; refused on a capturing stream."""
+    st = InstancedTraceStats()
+    _trace_seeded(lib().ntr_trace_instanced_seeded_stats, C.byref(st), num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results,
+                  d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
+                  d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
+    return st
+
+
+def trace_instanced_wide_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes,
+                                wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes,
+                                d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0, timed=True):
+    """ntr_trace_instanced_wide_seeded: trace_instanced_seeded over 4-wide trees (the rule is tests/np_instanced_seeded.py, trace_wide).
+    timed=True returns the GPU seconds; timed=False is asynchronous on `stream` (capturable) and returns None."""
+    sec = C.c_float(0.0)
+    _trace_seeded(lib().ntr_trace_instanced_wide_seeded, C.byref(sec) if timed else None, num_rays, any_hit, d_rays, d_seed_results,
+                  seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances,
+                  d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
+    return float(sec.value) if timed else None
+
+
+def trace_instanced_wide_seeded_stats(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes,
+                                      wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
+                                      wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0):
+    """ntr_trace_instanced_wide_seeded_stats: trace_instanced_wide_seeded's records through the instrumented kernel ->
+    InstancedWideTraceStats.  Blocks; refused on a capturing stream."""
+    st = InstancedWideTraceStats()
+    _trace_seeded(lib().ntr_trace_instanced_wide_seeded_stats, C.byref(st), num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results,
+                  d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
+                  wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
     return st
 
 

@@ -1,6 +1,6 @@
-// trace_instanced_kernels.h -- what the two translation units of the two-level trace share: the kernels' parameters and the fetch.
+// trace_instanced_kernels.h -- what the translation units of the two-level trace share: the kernels' parameters and the fetch.
 // trace_instanced_kernels.hip holds the unmasked kernel and the entry points, trace_instanced_masked_kernels.hip the masked and the
-// instrumented kernel.  Two units because the unmasked kernel must stay the kernel it was, instruction for instruction
+// instrumented kernel, trace_instanced_seeded_kernels.hip the two seeded kernels.  Separate units because the unmasked kernel must stay the kernel it was, instruction for instruction
 // (scripts/kernel_isa_diff.sh): with further kernels in its unit hipcc compiles it differently (an integer compare where it had a class
 // test, another register allocation), and that would have to be measured again.  The types stay in an anonymous namespace, which the
 // unmasked kernel's name carries; the launcher of the other unit therefore takes them as bytes.
@@ -17,6 +17,8 @@ namespace ntr {
 // trace_instanced_masked_kernels.hip: launches trace_instanced_stats (stats) or trace_instanced_masked over `blocks` workgroups of 64.
 // params, extras: an InstancedParams and an InstancedExtras of the caller's unit.
 void launch_trace_instanced_variant(bool stats, unsigned int blocks, hipStream_t stream, const void* params, const void* extras);
+// trace_instanced_seeded_kernels.hip: launches trace_instanced_seeded_stats (stats) or trace_instanced_seeded; seed: an InstancedSeed.
+void launch_trace_instanced_seeded(bool stats, unsigned int blocks, hipStream_t stream, const void* params, const void* extras, const void* seed);
 
 namespace {
 
@@ -40,6 +42,11 @@ struct InstancedExtras {
 };
 struct InstancedLaneStats {
     unsigned int topInner, entries, masked, inner, tris, leaves;
+};
+// What the seeded kernels take beside the two: one result record per ray to start from (tests/np_instanced_seeded.py).
+struct InstancedSeed {
+    const NtrRayResult* seedResults;   // numRays records, 16-byte aligned; may be InstancedParams::results
+    int32_t seedInstance;              // the instance id of a ray that keeps a seed that is a hit
 };
 
 // Lanes of mask k fetch 64 B at byte offset `ofs` of buffer k (range-checked: beyond the extent a load returns 0 and touches no memory),

@@ -21,6 +21,8 @@
 //                            (M_i & m_r) == 0 -- no marker, no transform, the record dropped.  Without instance masks the group of that
 //                            load has an empty mask and is skipped by its scalar branch
 //   trace_instanced_stats    the masked loop with per-lane counters, added once at the end (ntr_trace_instanced_stats; not a timed path)
+// and twice more, seeded (NTR_TI_SEEDED; trace_instanced_seeded_kernels.hip; the rule is tests/np_instanced_seeded.py):
+//   trace_instanced_seeded, trace_instanced_seeded_stats   the masked and the instrumented loop started from one result record per ray
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -39,19 +41,21 @@ namespace {
 #define NTR_TI_PARAMS InstancedParams p
 #define NTR_TI_MASKED 0
 #define NTR_TI_STATS 0
+#define NTR_TI_SEEDED 0
 #include "trace_instanced_body.h"
 #undef NTR_TI_KERNEL
 #undef NTR_TI_PARAMS
 #undef NTR_TI_MASKED
 #undef NTR_TI_STATS
+#undef NTR_TI_SEEDED
 
-// The three entry points' one body.  vis == NULL, or a vis that can refuse nothing (no arrays and rayMask all ones), launches the unmasked
-// kernel; stats != NULL launches the instrumented one and reads the counters back.
+// The entry points' one body.  vis == NULL, or a vis that can refuse nothing (no arrays and rayMask all ones), launches the unmasked
+// kernel; stats != NULL launches the instrumented one and reads the counters back.  seeded: the seeded kernels (always the masked loop).
 int trace_instanced_impl(const char* fn, int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
                          const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records, int32_t numInstances,
                          const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
                          const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis, float* seconds, void* stream,
-                         NtrInstancedTraceStats* stats)
+                         NtrInstancedTraceStats* stats, bool seeded = false, const NtrRayResult* d_seedResults = nullptr, int32_t seedInstance = -1)
 {
     if (seconds) *seconds = 0.0f;
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -69,6 +73,8 @@ int trace_instanced_impl(const char* fn, int32_t numRays, int32_t anyHit, const 
     if (const int rc = check_pool_bytes(fn, "poolTriWoopBytes", poolTriWoopBytes, kRowBytes)) return rc;
     if (vis && ((((uintptr_t)vis->d_instanceMasks) | ((uintptr_t)vis->d_rayMasks)) & 3u) != 0)
         return set_error(NTR_ERR_INVALID, "%s: a mask array must be 4-byte aligned", fn);
+    if (seeded && (!d_seedResults || (((uintptr_t)d_seedResults) & 15u) != 0))
+        return set_error(NTR_ERR_INVALID, "%s: the seed records must be given and 16-byte aligned", fn);
 
     DeviceState* ds = nullptr;
     if (const int rc = current_device_state_ready(&ds)) return rc;
@@ -96,8 +102,12 @@ int trace_instanced_impl(const char* fn, int32_t numRays, int32_t anyHit, const 
         NTR_HIP(ev.record(0));
     }
     const dim3 grid((numRays + 63) / 64), block(64);
-    if (stats) {
-        NTR_HIP(hipMemsetAsync(ds->stats, 0, 7 * sizeof(unsigned long long), s));
+    if (stats) NTR_HIP(hipMemsetAsync(ds->stats, 0, 7 * sizeof(unsigned long long), s));
+    if (seeded) {
+        InstancedSeed sd{};
+        sd.seedResults = d_seedResults; sd.seedInstance = seedInstance;
+        launch_trace_instanced_seeded(stats != nullptr, grid.x, s, &p, &x, &sd);
+    } else if (stats) {
         launch_trace_instanced_variant(true, grid.x, s, &p, &x);
     } else if (masked) {
         launch_trace_instanced_variant(false, grid.x, s, &p, &x);
@@ -162,4 +172,28 @@ extern "C" int ntr_trace_instanced_stats(int32_t numRays, int32_t anyHit, const 
     return trace_instanced_impl("ntr_trace_instanced_stats", numRays, anyHit, d_rays, d_results, d_instanceIDs, d_tlasNodes, tlasNodesBytes,
                                 rootLink, d_records, numInstances, d_poolNodes, poolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex,
                                 vis, nullptr, stream, stats);
+}
+
+extern "C" int ntr_trace_instanced_seeded(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                          int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs, const void* d_tlasNodes,
+                                          int64_t tlasNodesBytes, int32_t rootLink, const void* d_records, int32_t numInstances,
+                                          const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                                          const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis, float* seconds, void* stream)
+{
+    return trace_instanced_impl("ntr_trace_instanced_seeded", numRays, anyHit, d_rays, d_results, d_instanceIDs, d_tlasNodes, tlasNodesBytes,
+                                rootLink, d_records, numInstances, d_poolNodes, poolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex,
+                                vis, seconds, stream, nullptr, true, d_seedResults, seedInstance);
+}
+
+extern "C" int ntr_trace_instanced_seeded_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                                int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs, const void* d_tlasNodes,
+                                                int64_t tlasNodesBytes, int32_t rootLink, const void* d_records, int32_t numInstances,
+                                                const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                                int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis,
+                                                NtrInstancedTraceStats* stats, void* stream)
+{
+    if (!stats) return set_error(NTR_ERR_INVALID, "ntr_trace_instanced_seeded_stats: null stats");
+    return trace_instanced_impl("ntr_trace_instanced_seeded_stats", numRays, anyHit, d_rays, d_results, d_instanceIDs, d_tlasNodes,
+                                tlasNodesBytes, rootLink, d_records, numInstances, d_poolNodes, poolNodesBytes, d_poolTriWoop, poolTriWoopBytes,
+                                d_poolTriIndex, vis, nullptr, stream, stats, true, d_seedResults, seedInstance);
 }

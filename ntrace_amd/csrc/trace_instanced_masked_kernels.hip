@@ -13,6 +13,7 @@ namespace {
 
 #define NTR_TI_PARAMS InstancedParams p, InstancedExtras x
 #define NTR_TI_MASKED 1
+#define NTR_TI_SEEDED 0
 
 #define NTR_TI_KERNEL trace_instanced_masked
 #define NTR_TI_STATS 0
@@ -28,6 +29,7 @@ namespace {
 
 #undef NTR_TI_PARAMS
 #undef NTR_TI_MASKED
+#undef NTR_TI_SEEDED
 
 }  // namespace
 

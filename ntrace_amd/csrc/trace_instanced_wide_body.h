@@ -1,22 +1,18 @@
-// trace_instanced_body.h -- the two-level trace's kernel, stated once: trace_instanced_kernels.hip (the unmasked kernel) and
-// trace_instanced_masked_kernels.hip (the masked and the instrumented one) and trace_instanced_seeded_kernels.hip (the seeded masked
-// and the seeded instrumented one, whose parameters add InstancedSeed sd) include this text once per variant, after
-// trace_instanced_kernels.h, with
-//   NTR_TI_KERNEL   the kernel's name
-//   NTR_TI_PARAMS   its parameters: InstancedParams p, and for the masked variants InstancedExtras x
-//   NTR_TI_MASKED   1: the entering step asks the masks (x.instMasks, x.rayMasks, x.rayMask)
-//   NTR_TI_STATS    1: per-lane counters, summed into x.stats at the end
-//   NTR_TI_SEEDED   1: the ray starts from a seed record (InstancedSeed sd; the rule is tests/np_instanced_seeded.py): tmax from a seed that
-//                   is a hit, no traversal for an any-hit ray whose seed is a hit, and a lane that accepts nothing stores the seed's words
-// An include and not a function template because the unmasked variant must stay the kernel it was, instruction for instruction
-// (scripts/kernel_isa_diff.sh): with the loop in a __forceinline__ function that the kernels call, hipcc orders its passes differently and
-// allocates other registers, and every such change would have to be measured again.  No include guard: the text is meant
-// to repeat.
-__global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
+// trace_instanced_wide_body.h -- the two-level trace over 4-wide trees, its kernel stated once: trace_instanced_wide_kernels.hip (the
+// three unseeded kernels) and trace_instanced_wide_seeded_kernels.hip (the seeded ones) include this text once each, after
+// trace_instanced_wide_kernels.h, with
+//   NTR_TIW_TEMPLATE   the template header: <bool MASKED, bool STATS>, or <bool STATS> for the seeded kernels (MASKED is then true)
+//   NTR_TIW_KERNEL     the kernel's name
+//   NTR_TIW_PARAMS     its parameters: InstancedWideParams p, and for the seeded kernels InstancedWideSeed sd
+//   NTR_TIW_SEEDED     1: the ray starts from a seed record (the rule is tests/np_instanced_seeded.py): tmax from a seed that is a hit,
+//                      no traversal for an any-hit ray whose seed is a hit, and a lane that accepts nothing stores the seed's words
+// An include and not a further template parameter for trace_instanced_body.h's reason: the unseeded kernels keep their names and stay,
+// instruction for instruction, what they were (scripts/kernel_isa_diff.sh).  No include guard.
+NTR_TIW_TEMPLATE
+__global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
 {
-    constexpr bool MASKED = NTR_TI_MASKED, STATS = NTR_TI_STATS;
-#if !NTR_TI_MASKED
-    const InstancedExtras x{};   // (never read: every use is under MASKED or STATS)
+#if NTR_TIW_SEEDED
+    constexpr bool MASKED = true;   // the seeded kernels are the masked loop
 #endif
     __shared__ int s_stack[LDS_DEPTH][64];   // [entry][lane]
     const int lane = threadIdx.x;
@@ -24,15 +20,15 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     const bool valid = rayIdx < p.numRays;
     const float4* rays4 = reinterpret_cast<const float4*>(p.rays);
     const u32x4 rTlas = rsrc_words(p.tlas, p.tlasBytes), rRec = rsrc_words(p.records, p.recordsBytes),
-                rNodes = rsrc_words(p.poolNodes, p.poolNodesBytes), rWoop = rsrc_words(p.poolWoop, p.poolWoopBytes);
+                rWide = rsrc_words(p.poolWide, p.poolWideBytes), rWoop = rsrc_words(p.poolWoop, p.poolWoopBytes);
     const bool anyHit = p.anyHit != 0;
     u32x4 rMasks = rTlas;
     unsigned int rayMask = 0xFFFFFFFFu;   // m_r
     bool instMasks = false;               // wave-uniform: without instance masks no entering step loads a word
     if (MASKED) {
-        rMasks = rsrc_words(x.instMasks, x.instMasksBytes);
-        instMasks = x.instMasks != nullptr;
-        rayMask = x.rayMasks ? x.rayMasks[valid ? rayIdx : 0] : x.rayMask;
+        rMasks = rsrc_words(p.instMasks, p.instMasksBytes);
+        instMasks = p.instMasks != nullptr;
+        rayMask = p.rayMasks ? p.rayMasks[valid ? rayIdx : 0] : p.rayMask;
     }
     InstancedLaneStats ls = {0u, 0u, 0u, 0u, 0u, 0u};
 
@@ -51,8 +47,8 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     int hitAddr = -1, hitInst = -1;   // the hit's row in the pool's triWoop and its instance
     float hitU = 0.0f, hitV = 0.0f;
     int inst = -1;                    // >= 0: inside that instance
-    unsigned int nodesOffset = 0u, rowOffset = 0u;
-#if NTR_TI_SEEDED
+    unsigned int wideOffset = 0u, rowOffset = 0u, extent = 0u;
+#if NTR_TIW_SEEDED
     // one coalesced 16-byte load beside the ray's: a seed that is a hit gives tmax.  Nothing of it is held through the loop: a lane that
     // accepts nothing reloads its record at the end, as the world ray is reloaded on leaving an instance
     const int4* seeds4 = reinterpret_cast<const int4*>(sd.seedResults);
@@ -71,7 +67,7 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     int node = (valid && r.tmin < r.tmax) ? p.rootLink : kSentinel;
 #endif
 
-    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a, e = a, f = a, g = a;
     for (;;) {
         if (__ballot(node != kSentinel) == 0ull) break;
         const bool top = inst < 0;
@@ -82,22 +78,21 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
             if (inner) ofs = node;
             else if (neg && (unsigned)~node < (unsigned)p.numInstances) ofs = ~node * kRecordBytes;
         } else if (inner) {
-            const unsigned int o = nodesOffset + (unsigned)node;
-            if (o >= nodesOffset) ofs = (int)o;                       // (a sum that wraps reads nothing)
+            // below the BLAS's extent only (node and extent are multiples of 128 in a well-formed tree: the whole node lies inside)
+            const unsigned int o = wideOffset + (unsigned)node;
+            if ((unsigned)node < extent && o >= wideOffset && o < (unsigned)kNoNode) ofs = (int)o;   // (a sum that wraps reads nothing)
         } else if (neg) {
             const unsigned int row = rowOffset + (unsigned)~node;
             if (row < (unsigned)(kPoolMaxBytes >> kRowShift)) ofs = (int)(row << kRowShift);
         }
         unsigned int instMask = 0xFFFFFFFFu;   // M_i of an entering lane
-        if (MASKED) {
+        {
             // the word of record ofs / 64 lies at ofs / 16; an entering lane whose index is out of range holds kNoNode, and kNoNode / 16 =
             // 0x0FFFFFF0 is at or beyond the end of any mask array (4 * numInstances <= kPoolMaxBytes / 16): it reads 0 and touches nothing
             const unsigned long long enter = __ballot(top && neg);
-            fetch64_four_buffers_and_word(rTlas, rRec, rNodes, rWoop, rMasks, ofs, (int)((unsigned)ofs >> 4), __ballot(top && inner), enter,
-                                          __ballot(!top && inner), __ballot(!top && neg), instMasks ? enter : 0ull, a, b, c, d, instMask);
-        } else {
-            fetch64_four_buffers(rTlas, rRec, rNodes, rWoop, ofs, __ballot(top && inner), __ballot(top && neg), __ballot(!top && inner),
-                                 __ballot(!top && neg), a, b, c, d);
+            fetch_two_level_wide(rTlas, rRec, rWide, rWoop, rMasks, ofs, (int)((unsigned)ofs >> 4), __ballot(top && inner), enter,
+                                 __ballot(!top && inner), __ballot(!top && neg), (MASKED && instMasks) ? enter : 0ull, a, b, c, d, e, f, g,
+                                 instMask);
         }
         if (node == kSentinel) {
             // done: waits for the wave
@@ -110,11 +105,12 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
                 inst = -1;
             }
             node = stack_pop(st, spill);   // (any other such word is no link: it is dropped)
-        } else if (top && inner) {
-            if (STATS) ls.topInner++;
-            inner_advance<false, 8>(a, b, c, d, r, node, st, spill, p.status);
+        } else if (inner) {
+            // a wide node of either level (a lane whose fetch lay beyond an extent read zeros: four links of 0, no candidate, a pop)
+            if (STATS) { if (top) ls.topInner++; else ls.inner++; }
+            wide_advance<false>(a, b, c, d, e, f, g, r, node, st, spill, p.status);
         } else if (top) {
-            // entering instance ~node: its record is worldToObject (a, b, c) and nodesOffset, row offset, nodesBytes (d)
+            // entering instance ~node: its record is worldToObject (a, b, c) and the wide offset, row offset and extent (d)
             const int idx = ~node;
             if ((unsigned)idx >= (unsigned)p.numInstances) {
                 node = stack_pop(st, spill);
@@ -130,8 +126,9 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
                 const float dx = dot4(a, r.dx, r.dy, r.dz, 0.0f), dy = dot4(b, r.dx, r.dy, r.dz, 0.0f), dz = dot4(c, r.dx, r.dy, r.dz, 0.0f);
                 r.ox = ox; r.oy = oy; r.oz = oz;
                 r.dx = dx; r.dy = dy; r.dz = dz;
-                nodesOffset = __float_as_uint(d.x);
+                wideOffset = __float_as_uint(d.x);
                 rowOffset = __float_as_uint(d.y);
+                extent = __float_as_uint(d.z);
                 inst = idx;
                 node = 0;
                 if (STATS) ls.entries++;
@@ -139,13 +136,12 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
         } else {
             int row = -1;   // the BLAS's own row of a hit this step accepts
             if (STATS) {
-                // counted at the call site, from the row just fetched: a triangle test unless word 0 is the terminator; a terminator read for
-                // the row itself or for the word that came with a triangle -- unless an any-hit ray ended on that triangle
+                // leaf_step's counters: a triangle test unless the row is a terminator; a terminator read for the row itself or for the word
+                // that came with a triangle -- unless an any-hit ray ended on that triangle
                 const bool term = __float_as_uint(a.x) == kLeafTerm;
-                if (inner) ls.inner++;
-                else if (!term) ls.tris++;
+                if (!term) ls.tris++;
                 unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
-                if (!inner && (term || (!(anyHit && row >= 0) && __float_as_uint(d.x) == kLeafTerm))) ls.leaves++;
+                if (term || (!(anyHit && row >= 0) && __float_as_uint(d.x) == kLeafTerm)) ls.leaves++;
             } else {
                 unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
             }
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
         }
     }
     if (!valid) return;
-#if NTR_TI_SEEDED
+#if NTR_TIW_SEEDED
     bool seedKept = false;   // the lane accepted nothing and its seed is a hit
     if (hitAddr < 0) {
         // the seed's four words verbatim, a miss's too (results may be the seed buffer: the lane reads its record before it writes it)
@@ -173,16 +169,16 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     p.instanceIDs[rayIdx] = hitInst;
 #endif
     if (STATS) {   // diagnostics variant only: plain per-lane atomics
-        atomicAdd(&x.stats[0], (unsigned long long)ls.topInner);
-        atomicAdd(&x.stats[1], (unsigned long long)ls.entries);
-        atomicAdd(&x.stats[2], (unsigned long long)ls.masked);
-        atomicAdd(&x.stats[3], (unsigned long long)ls.inner);
-        atomicAdd(&x.stats[4], (unsigned long long)ls.tris);
-        atomicAdd(&x.stats[5], (unsigned long long)ls.leaves);
-#if NTR_TI_SEEDED
-        atomicAdd(&x.stats[6], (unsigned long long)(seedKept || (hitAddr >= 0 && p.triIndex[hitAddr] != -1)));
+        atomicAdd(&p.stats[0], (unsigned long long)ls.topInner);
+        atomicAdd(&p.stats[1], (unsigned long long)ls.entries);
+        atomicAdd(&p.stats[2], (unsigned long long)ls.masked);
+        atomicAdd(&p.stats[3], (unsigned long long)ls.inner);
+        atomicAdd(&p.stats[4], (unsigned long long)ls.tris);
+        atomicAdd(&p.stats[5], (unsigned long long)ls.leaves);
+#if NTR_TIW_SEEDED
+        atomicAdd(&p.stats[6], (unsigned long long)(seedKept || (hitAddr >= 0 && p.triIndex[hitAddr] != -1)));
 #else
-        atomicAdd(&x.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
+        atomicAdd(&p.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
 #endif
     }
 }

@@ -1,6 +1,7 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
 // and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen_batch (ntr_pool_widen for one BLAS) / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
-// ntr_trace_instanced_wide (see the header).
+// ntr_trace_instanced_wide, and a static world over ntr_trace_bvh / ntr_trace_instanced_seeded / ntr_trace_instanced_wide_seeded (see the
+// header).
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
@@ -8,7 +9,7 @@
 namespace FW {
 
 CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false),
-                                           m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false)
+                                           m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false), m_world(-1)
 {
     std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
     std::memset(&m_wideResult, 0, sizeof(m_wideResult));
@@ -57,6 +58,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     if (numTris < 1 || numTris >= (1ll << 28) || vtxPos.getSize() < (S64)numVerts * (S64)(3 * sizeof(F32))) fail("CudaInstancedBVH: bad mesh buffers");
     m_ranges.clear();
     m_meshes.clear();
+    clearWorld();                                    // the pool is replaced: whatever BLAS the world named is gone
     m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
     m_poolNodes.resizeDiscard(capN);
@@ -124,9 +126,10 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
 void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32* blas)
 {
     if (num < 1 || !objectToWorld || !blas) fail("CudaInstancedBVH: no instances");
-    m_instances.resizeDiscard((S64)num * sizeof(NtrInstance));
+    const S32 total = num + (m_world >= 0 ? 1 : 0);  // a world's record lies behind the instances'
+    m_instances.resizeDiscard((S64)total * sizeof(NtrInstance));
     NtrInstance* inst = (NtrInstance*)m_instances.getMutablePtrDiscard();
-    std::memset(inst, 0, (size_t)num * sizeof(NtrInstance));
+    std::memset(inst, 0, (size_t)total * sizeof(NtrInstance));
     for (S32 i = 0; i < num; i++) {
         std::memcpy(inst[i].objectToWorld, objectToWorld + 12 * (size_t)i, sizeof(inst[i].objectToWorld));
         if (ntr_instance_invert(inst[i].objectToWorld, inst[i].worldToObject) != NTR_OK) fail("CudaInstancedBVH: instance %d: %s", i, ntr_last_error());
@@ -138,6 +141,35 @@ void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32
     }
     m_numInstances = num;
     m_built = false;
+    writeWorldRecord();
+}
+
+void CudaInstancedBVH::writeWorldRecord(void)
+{
+    if (m_world < 0) return;
+    NtrInstance w;
+    std::memset(&w, 0, sizeof(w));
+    w.objectToWorld[0] = w.objectToWorld[5] = w.objectToWorld[10] = 1.0f;   // identity both ways: the world's object space is world space
+    w.worldToObject[0] = w.worldToObject[5] = w.worldToObject[10] = 1.0f;
+    w.blas = m_world;
+    m_instances.resize((S64)(m_numInstances + 1) * sizeof(NtrInstance));   // keeps the instances' records
+    m_instances.setRange((S64)m_numInstances * sizeof(NtrInstance), &w, sizeof(w));
+}
+
+void CudaInstancedBVH::setWorld(S32 blas, const char* kernelName)
+{
+    if (blas < 0 || blas >= (S32)m_ranges.size()) fail("CudaInstancedBVH::setWorld: BLAS index %d outside [0, %d)", blas, (S32)m_ranges.size());
+    if (!kernelName || !kernelName[0]) fail("CudaInstancedBVH::setWorld: no kernel name");
+    m_world = blas;
+    m_worldKernel = kernelName;
+    writeWorldRecord();                              // the TLAS never sees the world: m_built stays
+}
+
+void CudaInstancedBVH::clearWorld(void)
+{
+    if (m_world < 0) return;
+    m_world = -1;
+    m_instances.resize((S64)m_numInstances * sizeof(NtrInstance));
 }
 
 void CudaInstancedBVH::setInstanceMasks(const U32* masks)
@@ -266,7 +298,35 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     float seconds = 0.0f;
     const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
     int rc;
-    if (m_traceWide && isWide()) {
+    if (m_world >= 0) {
+        // the world's single-level trace on its range of the pool, then the seeded two-level trace over its records, in place
+        const NtrBlasRange& wr = m_ranges[m_world];
+        const int32_t anyHit = rays.getNeedClosestHit() ? 0 : 1;
+        const NtrRay* d_rays = (const NtrRay*)rays.getRayBuffer().getCudaPtr();
+        NtrRayResult* d_results = (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr();
+        float worldSeconds = 0.0f;
+        rc = ntr_trace_bvh(m_worldKernel.c_str(), numRays, anyHit, d_rays, d_results, (const U8*)m_poolNodes.getCudaPtr() + wr.nodesOffset,
+                           wr.nodesBytes, (const U8*)m_poolTriWoop.getCudaPtr() + wr.triWoopOffset, wr.triWoopBytes,
+                           (const int32_t*)m_poolTriIndex.getCudaPtr() + wr.triWoopOffset / 16, BVHLayout_Compact, 0u, NULL, &worldSeconds);
+        if (rc != NTR_OK) fail("CudaInstancedBVH: the world's trace: %s", ntr_last_error());
+        NtrInstanceVisibility vis;
+        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
+        vis.d_rayMasks = NULL;
+        vis.rayMask = rayMask;
+        vis.pad = 0;
+        if (m_traceWide && isWide())
+            rc = ntr_trace_instanced_wide_seeded(numRays, anyHit, d_rays, d_results, m_numInstances, d_results,
+                                                 (int32_t*)instanceIDs.getMutableCudaPtr(), m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL,
+                                                 m_wideResult.nodesBytes, m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances,
+                                                 m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(),
+                                                 m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
+        else
+            rc = ntr_trace_instanced_seeded(numRays, anyHit, d_rays, d_results, m_numInstances, d_results, (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                            m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
+                                            m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                            (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
+        seconds += worldSeconds;
+    } else if (m_traceWide && isWide()) {
         NtrInstanceVisibility vis;
         vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
         vis.d_rayMasks = NULL;

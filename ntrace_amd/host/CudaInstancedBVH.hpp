@@ -40,10 +40,22 @@
 //   getBLASTrisBuffer  NtrBlasTris per BLAS, on the device: the meshes buildBLASes remembers, which ntr_instanced_hit_attributes needs
 //                 to turn a two-level hit's id into a pool triangle.  A BLAS that came through addBLAS has numTris 0:
 //                 its hits resolve to -1
+//   setWorld       a static world beside the instances: one BLAS of the pool, traced in its own space -- its object space
+//                 is world space -- by the single-level kernel.  It is no entry of setInstances and the TLAS never sees it: build() and
+//                 refit() cover the N instances as before.  Its instance id is getNumInstances(), and while it is set getInstanceBuffer()
+//                 carries one more NtrInstance at that index (identity both ways, blas = the world's), so that
+//                 ntr_instanced_hit_attributes with numInstances + 1 resolves world hits without change.  traceBatch then runs
+//                 ntr_trace_bvh(kernelName) on the world BLAS's range of the pool and ntr_trace_instanced_seeded (the wide form when
+//                 setTraceWide and isWide() say so) in place over its records, and returns the sum of both GPU times.  Refuses a BLAS
+//                 index outside the pool; traceBatch still needs at least one instance and a current TLAS.  buildBLASes replaces the
+//                 pool and drops the world; clearWorld drops it and the extra record
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
-// primary, AO and diffuse frames.  The frame loop of a moving, deforming scene becomes
+// primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
 //   refitBLASes -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch / traceBatch / updateResult per batch
+// and with a static world set (setWorld, once) nothing of that loop changes: the world BLAS is left out of refitBLASes' selection, the
+// instances move, and every traceBatch of the frame is the world's single-level trace followed by the seeded two-level trace.
 #pragma once
+#include <string>
 #include <vector>
 
 #include "CudaBVH.hpp"
@@ -73,6 +85,10 @@ public:
     void widen(void);
     void refitBLASesWide(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas = NULL, S32 num = 0, F32 epsilon = 0.0f);
     void refitWide(void);
+    void setWorld(S32 blas, const char* kernelName = "fermi_speculative_while_while");
+    void clearWorld(void);
+    bool hasWorld(void) const { return m_world >= 0; }
+    S32  getWorldBLAS(void) const { return m_world; }                            // -1: no world
     void setTraceWide(bool on) { m_traceWide = on; }
     bool getTraceWide(void) const { return m_traceWide; }
     bool isWide(void) const { return m_built && m_widePool && m_wideTlas; }      // the wide pool, TLAS and records are current
@@ -100,7 +116,7 @@ public:
     Buffer& getPoolNodeBuffer(void) { return m_poolNodes; }
     Buffer& getPoolTriWoopBuffer(void) { return m_poolTriWoop; }
     Buffer& getPoolTriIndexBuffer(void) { return m_poolTriIndex; }
-    Buffer& getInstanceBuffer(void) { return m_instances; }                      // NtrInstance per instance
+    Buffer& getInstanceBuffer(void) { return m_instances; }                      // NtrInstance per instance; with a world, one more: the world's
     Buffer& getTLASNodeBuffer(void) { return m_tlasNodes; }
     Buffer& getRecordBuffer(void) { return m_records; }
 
@@ -132,6 +148,10 @@ private:
     NtrTlasWideResult m_wideResult;
     NtrWideRefitResult m_wideBlasRefitResult;
     NtrTlasRefitResult m_wideTlasRefitResult;
+    // the static world (setWorld): a BLAS of the pool that seeds the two-level trace
+    void          writeWorldRecord(void);                                        // m_instances[m_numInstances], when a world is set
+    S32           m_world;                                                       // -1: none
+    std::string   m_worldKernel;
 };
 
 }  // namespace FW

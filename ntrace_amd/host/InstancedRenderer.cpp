@@ -53,7 +53,7 @@ void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& re
     if (normals) normals->resizeDiscard((S64)n * (S64)(4 * sizeof(F32)));
     if (!n) return;
     NtrInstancedGeometry g;
-    g.numInstances = m_bvh.getNumInstances();
+    g.numInstances = m_bvh.getNumInstances() + (m_bvh.hasWorld() ? 1 : 0);   // a world's hits carry instance id N: its record lies there
     g.numBlas = m_bvh.getNumBLAS();
     g.numTrisTotal = (int32_t)(m_triVtxIndex->getSize() / (S64)(3 * sizeof(S32)));
     g.numVerts = m_numVerts;

@@ -17,6 +17,10 @@
 //                 ntr_instanced_hit_attributes before anything indexes by triangle: the records updateResult and getTotalNumRays
 //                 read name POOL triangles (the caller's colour tables are per pool triangle, in object space), and the AO and diffuse
 //                 rays start from the world-space normals of the current vertices (ntr_raygen_ao_normals)
+// With a static world set on the CudaInstancedBVH (setWorld) primary, AO and diffuse frames run through its traceBatch
+// unchanged otherwise: every batch is the world's single-level trace followed by the seeded two-level trace (AO batches any-hit), world
+// hits carry instance id getNumInstances() and resolve through the one more NtrInstance the instance buffer then holds, and updateResult
+// works over pool triangles as before.
 // beginFrame fails, and says what to do, when there is no geometry, when the CudaInstancedBVH's TLAS is not current (build() or refit()
 // after setInstances / refitBLASes), and when the pool holds a tree that came through addBLAS (its mesh is not known here).
 // No kd-tree, no shard, no cache and no dispatch hints; Renderer itself is untouched.
