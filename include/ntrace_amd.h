@@ -1348,6 +1348,75 @@ typedef struct NtrBvhSahResult {
 NTR_API int ntr_bvh_sah_cost(const void* d_nodes, int64_t nodesBytes, const void* d_triWoop, int64_t triWoopBytes,
                              NtrBvhSahResult* result, void* stream);
 
+/* ntr_bvh_optimize_batch: ntr_bvh_optimize over many BLASes of a pool in one pass (csrc/bvh_optimize_batch_kernels.hip).
+ * EXTENSION without a reference counterpart; the rule is tests/np_optimize_batch.py::optimize, that is np_bvh_optimize.optimize over
+ * every entry's node slice.  After the call every listed BLAS's node range holds what ntr_bvh_optimize(pool + nodesOffset, nodesBytes,
+ * passes) writes, and every other byte of the pool is untouched.  Only nodesOffset and nodesBytes of an entry are read: leaves, Woop rows
+ * and triIndex stay as they are, so no row pointer is passed.  The entries are any subset of the pool's BLASes in any order, with gaps.
+ *   what stays valid  slot 0 of a BLAS is only ever re-split: the union of its two child boxes (min / max, exact) keeps its bits, so a
+ *                top-level tree over the pool, its records and ntr_tlas_refit's result stay valid.  A wide pool made from the BLASes
+ *                does not: re-widen it (ntr_pool_widen_batch)
+ *   host cost    every kernel covers all entries (a joint slot space: the running sum of the entries' slot counts), and a height of
+ *                treelets is one launch for all entries, so launches <= passes * (5 + H) + 2, H the greatest height of any entry in
+ *                any pass.  One read-back per pass (the tallest height and the histogram's first 1024 words; one more only for a tree
+ *                taller than that), one after the final measuring round, one more for entryResults != NULL.  result->launches and
+ *                result->readBacks report what was issued
+ *   results      entryResults[k] (may be NULL): reached slots and leaf links, the height before the first and after the last pass,
+ *                errBits.  *result (may be NULL): formed / rewritten per pass summed over the entries, the tallest heights,
+ *                firstBadEntry (-1: none; the lowest index) and the OR of the entries' errBits, seconds (GPU time of the call)
+ * The call BLOCKS and is refused on a capturing stream.  Scratch: 40 B per listed slot (56 B for ntr_bvh_sah_cost_batch, which shares
+ * the pool), 88 B per entry and two tables of as many words as the largest entry has slots, in a per-device grow-only pool of its own
+ * that ntr_lbvh_release_workspace returns.
+ * NTR_ERR_INVALID before any device work: null entries or d_poolNodes; numEntries outside 1..2^20; passes outside 1..8; poolNodesBytes
+ * not a multiple of 64 in [64, 0xFFFFFF00]; d_poolNodes not 16-byte aligned; an entry's node range misaligned, empty, outside the pool or
+ * above 0x76543200 bytes; two entries whose node ranges overlap or repeat (a BLAS is restructured once per call); a capturing stream.
+ * Without a device, after those checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP.
+ * NTR_ERR_LAYOUT, after the work, with *result and entryResults filled and every other entry optimised completely:
+ *   NTR_OPT_ERR_LINK     a child link outside its BLAS's extent: never followed, it counts as a leaf link (ntr_bvh_optimize's rule);
+ *                        a link is always judged against its own BLAS's slot count, so one that would land in a neighbour names nobody
+ *   NTR_OPT_ERR_NO_TREE  the links form no tree under the entry's slot 0 -- the bottom-up pass never completes slot 0, or slot 0 has no
+ *                        child at all, as a zero-filled slot has: the entry is left entirely unchanged in every pass (ntr_bvh_optimize
+ *                        leaves a zero-filled slot 0 unchanged too, without an error) */
+enum { NTR_OPT_ERR_LINK = 1, NTR_OPT_ERR_ROW = 2, NTR_OPT_ERR_NO_TREE = 4 };
+typedef struct NtrBvhOptimizeBatchEntry {          /* host array, one per listed BLAS: 32 bytes */
+    int32_t numNodes, numLeafLinks;                /* reached slots and the leaf links below them (0, 0 without a tree) */
+    int32_t heightBefore, heightAfter;             /* before the first pass, after the last */
+    int32_t errBits, pad[3];
+} NtrBvhOptimizeBatchEntry;
+typedef struct NtrBvhOptimizeBatchResult {
+    int32_t numEntries, passes;
+    int64_t formed[8], rewritten[8];               /* per pass, summed over the entries */
+    int32_t maxHeightBefore, maxHeightAfter;       /* the tallest entry before the first pass and after the last */
+    int32_t firstBadEntry, errBits;
+    int32_t launches, readBacks;                   /* kernel launches and blocking device-to-host copies issued */
+    float   seconds;
+    int32_t pad;
+} NtrBvhOptimizeBatchResult;
+NTR_API int ntr_bvh_optimize_batch(int32_t numEntries, const NtrBlasRange* entries, void* d_poolNodes, int64_t poolNodesBytes,
+                                   int32_t passes, NtrBvhOptimizeBatchEntry* entryResults /* numEntries, may be NULL */,
+                                   NtrBvhOptimizeBatchResult* result /* may be NULL */, void* stream);
+/* Bytes the scratch pool of ntr_bvh_optimize_batch / ntr_bvh_sah_cost_batch holds on the current device (0 after
+ * ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_optimize_batch_scratch_bytes(int64_t* bytes);
+
+/* ntr_bvh_sah_cost_batch: ntr_bvh_sah_cost of many BLASes of a pool in two launches and one read-back (same unit; the rule is
+ * tests/np_optimize_batch.py::sah_costs).  entryResults[k] equals what ntr_bvh_sah_cost returns at pool + offsets in sahCost (bit for
+ * bit), numNodes, numLeaves, numTris and height; its seconds is 0, the call's GPU time is result->seconds.  A leaf counts its rows to
+ * the terminator inside its own BLAS's row range only.  The call only reads the pool, so entries may repeat or overlap.  Blocking, not
+ * capturable.  A malformed entry counts 0 where it cannot follow (NTR_OPT_ERR_LINK, NTR_OPT_ERR_ROW) or, without a tree under its slot 0,
+ * is reported as zeros (NTR_OPT_ERR_NO_TREE); the call then returns NTR_ERR_LAYOUT with firstBadEntry, and every result is filled.
+ * NTR_ERR_INVALID before any device work: ntr_bvh_optimize_batch's cases for the nodes (but for the overlap rule), the same for the
+ * rows (poolTriWoopBytes a multiple of 16 in [16, 0xFFFFFF00], a 16-byte aligned pointer, every row range a positive multiple of 16
+ * inside it), null entryResults.  NTR_ERR_OVERFLOW: the entries list more than 0xFFFFFF00 / 64 slots in all (only where they repeat). */
+typedef struct NtrBvhSahBatchResult {
+    int32_t numEntries, firstBadEntry, errBits;
+    int32_t launches, readBacks;
+    float   seconds;
+} NtrBvhSahBatchResult;
+NTR_API int ntr_bvh_sah_cost_batch(int32_t numEntries, const NtrBlasRange* entries, const void* d_poolNodes, int64_t poolNodesBytes,
+                                   const void* d_poolTriWoop, int64_t poolTriWoopBytes, NtrBvhSahResult* entryResults /* numEntries */,
+                                   NtrBvhSahBatchResult* result /* may be NULL */, void* stream);
+
 /* On-device renumbering: copy a BVHLayout_Compact tree, whatever built, refitted or restructured it, into the node and row order of
  * the host builder (CudaBVH::createCompact, CudaBVH.cpp:594-652): a stack holding slot 0; pop a slot and, for child 0 then child 1, an
  * inner child takes the next node slot and is pushed, a leaf child takes the next rows.  So siblings share a 128-byte line, a node's

@@ -30,6 +30,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     BvhWideResult, bvh_widen_capacity, bvh_widen, bvh_widen_scratch_bytes, trace_wide, trace_wide_stats,
                     WideBlasRange, TlasWideResult, InstancedWideTraceStats, pool_widen_capacity, pool_widen, tlas_widen,
                     pool_widen_batch, pool_widen_batch_scratch_bytes,
+                    BvhOptimizeBatchEntry, BvhOptimizeBatchResult, BvhSahBatchResult, bvh_optimize_batch, bvh_optimize_batch_scratch_bytes,
+                    bvh_sah_cost_batch, OPT_ERR_LINK, OPT_ERR_ROW, OPT_ERR_NO_TREE,
                     trace_instanced_wide, trace_instanced_wide_stats,
                     trace_instanced_seeded, trace_instanced_seeded_stats, trace_instanced_wide_seeded, trace_instanced_wide_seeded_stats,
                     WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
@@ -59,6 +61,8 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "BvhWideResult", "bvh_widen_capacity", "bvh_widen", "bvh_widen_scratch_bytes", "trace_wide", "trace_wide_stats",
            "WideBlasRange", "TlasWideResult", "InstancedWideTraceStats", "pool_widen_capacity", "pool_widen", "tlas_widen",
            "pool_widen_batch", "pool_widen_batch_scratch_bytes",
+           "BvhOptimizeBatchEntry", "BvhOptimizeBatchResult", "BvhSahBatchResult", "bvh_optimize_batch", "bvh_optimize_batch_scratch_bytes",
+           "bvh_sah_cost_batch", "OPT_ERR_LINK", "OPT_ERR_ROW", "OPT_ERR_NO_TREE",
            "trace_instanced_wide", "trace_instanced_wide_stats",
            "trace_instanced_seeded", "trace_instanced_seeded_stats", "trace_instanced_wide_seeded", "trace_instanced_wide_seeded_stats",
            "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",

@@ -323,6 +323,36 @@ class BvhSahResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+OPT_ERR_LINK, OPT_ERR_ROW, OPT_ERR_NO_TREE = 1, 2, 4   # NTR_OPT_ERR_*: the errBits of the two pool calls below
+
+
+class BvhOptimizeBatchEntry(C.Structure):
+    """NtrBvhOptimizeBatchEntry: what ntr_bvh_optimize_batch found out about one listed BLAS."""
+    _fields_ = [("numNodes", C.c_int32), ("numLeafLinks", C.c_int32), ("heightBefore", C.c_int32), ("heightAfter", C.c_int32),
+                ("errBits", C.c_int32), ("pad", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class BvhOptimizeBatchResult(C.Structure):
+    _fields_ = [("numEntries", C.c_int32), ("passes", C.c_int32), ("formed", C.c_int64 * 8), ("rewritten", C.c_int64 * 8),
+                ("maxHeightBefore", C.c_int32), ("maxHeightAfter", C.c_int32), ("firstBadEntry", C.c_int32), ("errBits", C.c_int32),
+                ("launches", C.c_int32), ("readBacks", C.c_int32), ("seconds", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        n = self.passes
+        return {k: (list(getattr(self, k))[:n] if k in ("formed", "rewritten") else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class BvhSahBatchResult(C.Structure):
+    _fields_ = [("numEntries", C.c_int32), ("firstBadEntry", C.c_int32), ("errBits", C.c_int32), ("launches", C.c_int32),
+                ("readBacks", C.c_int32), ("seconds", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class _DeviceKdtreeInfo(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("nodesBytes", C.c_int64), ("triWoop", C.c_void_p),
                 ("triWoopBytes", C.c_int64), ("triIndex", C.c_void_p), ("triIndexBytes", C.c_int64),
@@ -489,6 +519,9 @@ SYMBOLS = [
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
     ("ntr_bvh_optimize_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_sah_cost", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhSahResult), _vp]),
+    ("ntr_bvh_optimize_batch", C.c_int, [_i32, _vp, _vp, _i64, _i32, _vp, C.POINTER(BvhOptimizeBatchResult), _vp]),
+    ("ntr_bvh_optimize_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_sah_cost_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(BvhSahBatchResult), _vp]),
     ("ntr_bvh_reorder", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, C.POINTER(BvhReorderResult), _vp]),
     ("ntr_bvh_reorder_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_host_kdtree_info", C.c_int, [_vp, C.POINTER(_HostKdtreeInfo)]),
@@ -1540,6 +1573,47 @@ def bvh_sah_cost(d_nodes, nodes_bytes, d_woop, woop_bytes, stream=0):
     res = BvhSahResult()
     _check(lib().ntr_bvh_sah_cost(_vp(d_nodes), int(nodes_bytes), _vp(d_woop), int(woop_bytes), C.byref(res), _vp(stream)))
     return res
+
+
+def bvh_optimize_batch(entries, d_pool_nodes, pool_nodes_bytes, passes=2, stream=0, entry_results=True):
+    """ntr_bvh_optimize_batch: bvh_optimize over the listed BLASes of a pool in one pass (an extension; the rule is
+    tests/np_optimize_batch.py).  entries: (nodesOffset, nodesBytes[, triWoopOffset, triWoopBytes]) tuples or a BlasPool -- only the
+    node part is read.  Blocks; returns (BvhOptimizeBatchResult, [BvhOptimizeBatchEntry] or None).  An NtrError raised after the work
+    (NTR_ERR_LAYOUT) carries .result and .entry_results, filled."""
+    arr, n = _blas_ranges(entries)
+    res = BvhOptimizeBatchResult()
+    per = (BvhOptimizeBatchEntry * max(n, 1))() if entry_results else None
+    try:
+        _check(lib().ntr_bvh_optimize_batch(n, C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes), int(passes),
+                                            C.cast(per, _vp) if entry_results else None, C.byref(res), _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        e.entry_results = list(per[:n]) if entry_results else None
+        raise
+    return res, (list(per[:n]) if entry_results else None)
+
+
+def bvh_optimize_batch_scratch_bytes():
+    """ntr_bvh_optimize_batch_scratch_bytes: bytes the scratch pool of bvh_optimize_batch / bvh_sah_cost_batch holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_optimize_batch_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def bvh_sah_cost_batch(entries, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, stream=0):
+    """ntr_bvh_sah_cost_batch: bvh_sah_cost of the listed BLASes of a pool in two launches (spec: tests/np_optimize_batch.py sah_costs).
+    Blocks; returns ([BvhSahResult], BvhSahBatchResult).  An NtrError raised after the work carries .result and .entry_results."""
+    arr, n = _blas_ranges(entries)
+    res = BvhSahBatchResult()
+    per = (BvhSahResult * max(n, 1))()
+    try:
+        _check(lib().ntr_bvh_sah_cost_batch(n, C.cast(arr, _vp), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop),
+                                            int(pool_woop_bytes), C.cast(per, _vp), C.byref(res), _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        e.entry_results = list(per[:n])
+        raise
+    return list(per[:n]), res
 
 
 def camera_decode(signature):

@@ -1,5 +1,5 @@
 // bvh_climb.h -- the bottom-up pass over a BVHLayout_Compact tree (compact_bvh.h): the topology step that prepares it and the climb,
-// once, for the refit (bvh_refit_kernels.hip), for the optimiser's height / SAH-cost passes (bvh_optimize_kernels.hip) and for the
+// once, for the refit (bvh_refit_kernels.hip), for the optimiser's height / SAH-cost passes (bvh_optimize_payload.h, for bvh_optimize_kernels.hip and bvh_optimize_batch_kernels.hip) and for the
 // renumbering's subtree counts (bvh_reorder_kernels.hip).
 //
 // Two launches.  The topology step, one thread per node slot, clears the slot's arrival counter and writes

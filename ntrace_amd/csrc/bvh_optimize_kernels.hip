@@ -25,6 +25,9 @@
 // computes the node's value from its two children's; the root's value, height and counts are read back.
 // A link outside the extent is never followed (it counts as a leaf link and sets an error bit), so nothing outside the caller's
 // buffer is touched; a node reached by more than two arrivals (not a tree) is owned once, so every pass ends on any input.
+// The device code of every step but the topology's lives in bvh_optimize_payload.h (the climb and what it carries) and
+// bvh_optimize_treelet.h (histogram, scan, scatter, the treelet), which bvh_optimize_batch_kernels.hip runs over the BLASes of a pool
+// (DESIGN.md 6v); the kernels here find their slot and call those bodies.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -36,26 +39,13 @@
 
 #include "ntr_internal.h"
 #include "bvh_climb.h"
+#include "bvh_optimize_payload.h"
+#include "bvh_optimize_treelet.h"
 #include "device_prims.h"
 #include "device_scratch.h"
 
 namespace ntr {
 namespace {
-
-constexpr int OP_BLOCK = 256;
-constexpr int OP_N = 7;                      // treelet size
-constexpr int OP_FULL = (1 << OP_N) - 1;
-constexpr int OP_MAX_PASSES = 8;
-constexpr int OP_STAT_SLOTS = 64;            // the rewritten-treelet counters of a pass: a workgroup adds to slot blockIdx % 64
-constexpr int OP_HIST_LDS = 1024;            // heights below this are counted in LDS first
-enum : unsigned int { OP_ERR_LINK = 1u, OP_ERR_ROW = 2u };
-
-struct OpRoot {                              // what the owner of slot 0 reports; `done` stays 0 if the climb never got there
-    unsigned int done, height, leafLinks, slots, leaves, tris, err;
-    float sah;
-    unsigned int pad[8];
-};
-static_assert(sizeof(OpRoot) == 64, "OpRoot must be 64 bytes");
 
 DeviceScratchPool g_opPool;
 
@@ -74,54 +64,7 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_topology(int numSlots, const int
     if (kind[0] == LINK_BAD || kind[1] == LINK_BAD) atomicOr(&root->err, OP_ERR_LINK);   // a malformed tree only
 }
 
-// What a child reports to its node.  SAH: three 8-byte words (value | height, leaves | triangles, slots); else one (height | leaf links).
-template <bool SAH>
-struct OpInfo {
-    unsigned int height, leafLinks, slots, leaves, tris;
-    float value;
-};
-template <bool SAH>
-__device__ __forceinline__ void op_publish(unsigned long long* info, size_t child, const OpInfo<SAH>& v)
-{
-    if (SAH) {
-        unsigned long long* p = info + 3 * child;
-        __hip_atomic_store(p, (unsigned long long)__float_as_uint(v.value) | ((unsigned long long)v.height << 32), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(p + 1, (unsigned long long)v.leaves | ((unsigned long long)v.tris << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(p + 2, (unsigned long long)v.slots, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        __hip_atomic_store(info + child, (unsigned long long)v.height | ((unsigned long long)v.leafLinks << 32), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-template <bool SAH>
-__device__ __forceinline__ void op_acquire(const unsigned long long* info, size_t child, OpInfo<SAH>& v)
-{
-    v = OpInfo<SAH>();
-    if (SAH) {
-        const unsigned long long* p = info + 3 * child;
-        const unsigned long long a = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long b = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long c = __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v.value = __uint_as_float((unsigned int)a); v.height = (unsigned int)(a >> 32);
-        v.leaves = (unsigned int)b; v.tris = (unsigned int)(b >> 32);
-        v.slots = (unsigned int)c;
-    } else {
-        const unsigned long long a = __hip_atomic_load(info + child, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v.height = (unsigned int)a; v.leafLinks = (unsigned int)(a >> 32);
-    }
-}
-
-// fminf / fmaxf of calcSAHNode pinned: the other operand for a NaN, else by the total order -0 < +0
-__device__ __forceinline__ float op_fmin(float a, float b) { return a != a ? b : (b != b ? a : ord_min(a, b)); }
-__device__ __forceinline__ float op_fmax(float a, float b) { return a != a ? b : (b != b ? a : ord_max(a, b)); }
-// 2 * ((dx*dy + dy*dz) + dz*dx), left to right (emitTreeKernel.cu:1374-1376); this file is compiled without contraction
-__device__ __forceinline__ float op_sah_area(float xi, float xa, float yi, float ya, float zi, float za)
-{
-    const float dx = xa - xi, dy = ya - yi, dz = za - zi;
-    return 2.0f * ((dx * dy + dy * dz) + dz * dx);
-}
-
+// The payload, its stores and loads and the climb of a child word are bvh_optimize_payload.h's.
 template <bool SAH>
 __global__ __launch_bounds__(OP_BLOCK) void opt_climb(int numSlots, const int* __restrict__ nodes, int numRows, const float4* __restrict__ woop,
                                                       const unsigned int* __restrict__ parent, unsigned int* __restrict__ arrive,
@@ -130,53 +73,7 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_climb(int numSlots, const int* _
 {
     const long long g = (long long)blockIdx.x * OP_BLOCK + threadIdx.x;
     if (g >= 2ll * numSlots) return;
-    int node = (int)(g >> 1), k = (int)(g & 1);
-    const int link = nodes[(size_t)node * kNodeWords + kLinkWord + k];
-    if (is_inner_link(link, numSlots)) return;   // an inner child arrives with the owner of its node
-    OpInfo<SAH> mine = OpInfo<SAH>();
-    mine.leafLinks = 1u;
-    if (SAH && link < 0) {
-        mine.leaves = 1u;
-        long long r = (long long)leaf_row(link);
-        while (r < numRows && __float_as_uint(woop[r].x) != kLeafTerm) {   // calcLeafs (emitTreeKernel.cu:1351-1359), inside the extent
-            mine.tris++;
-            r += 3;
-        }
-        if (r >= numRows) atomicOr(&root->err, OP_ERR_ROW);
-        mine.value = (float)mine.tris;
-    }
-    OpInfo<SAH> sib;
-    const auto publish = [&](int n, int ck) { op_publish<SAH>(info, 2 * (size_t)n + ck, mine); };
-    const auto acquire = [&](int n, int ck) { op_acquire<SAH>(info, 2 * (size_t)n + ck, sib); };
-    const auto merge = [&](int n, int ck) {
-        OpInfo<SAH> up = OpInfo<SAH>();
-        up.height = 1u + max(mine.height, sib.height);
-        up.leafLinks = mine.leafLinks + sib.leafLinks;
-        if (SAH) {
-            up.slots = 1u + mine.slots + sib.slots;
-            up.leaves = mine.leaves + sib.leaves;
-            up.tris = mine.tris + sib.tris;
-            const float* nf = reinterpret_cast<const float*>(nodes + (size_t)n * kNodeWords);
-            const float4 n0 = *reinterpret_cast<const float4*>(nf), n1 = *reinterpret_cast<const float4*>(nf + 4),
-                         n2 = *reinterpret_cast<const float4*>(nf + 8);
-            const float pa = op_sah_area(op_fmin(n0.x, n1.x), op_fmax(n0.y, n1.y), op_fmin(n0.z, n1.z), op_fmax(n0.w, n1.w),
-                                         op_fmin(n2.x, n2.z), op_fmax(n2.y, n2.w));
-            const float pl = op_sah_area(n0.x, n0.y, n0.z, n0.w, n2.x, n2.y);
-            const float pr = op_sah_area(n1.x, n1.y, n1.z, n1.w, n2.z, n2.w);
-            const float l = ck == 0 ? mine.value : sib.value, r = ck == 0 ? sib.value : mine.value;
-            up.value = (1.0f + (pl / pa) * l) + (pr / pa) * r;
-        } else {
-            height[n] = (int)up.height;
-            leafLinks[n] = up.leafLinks;
-        }
-        if (n == 0) {                         // the root reports to no parent
-            root->height = up.height; root->leafLinks = up.leafLinks; root->slots = up.slots; root->leaves = up.leaves;
-            root->tris = up.tris; root->sah = up.value; root->done = 1u;
-        }
-        mine = up;
-    };
-    publish(node, k);
-    climb(node, k, numSlots, nodes, parent, arrive, publish, acquire, merge);
+    op_climb_child<SAH>((int)(g >> 1), (int)(g & 1), numSlots, nodes, numRows, woop, parent, arrive, info, height, leafLinks, root, nullptr);
 }
 
 // qual[slot] = the slot's height if it roots a treelet (reached, leafLinks >= 7), else 0; hist[height] counts them.
@@ -184,30 +81,8 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_histogram(int numSlots, const in
                                                           const int* __restrict__ height, const unsigned int* __restrict__ leafLinks,
                                                           int* __restrict__ qual, unsigned int* __restrict__ hist)
 {
-    __shared__ unsigned int sh[OP_HIST_LDS];
-    for (int i = threadIdx.x; i < OP_HIST_LDS; i += OP_BLOCK) sh[i] = 0u;
-    __syncthreads();
     const int slot = blockIdx.x * OP_BLOCK + threadIdx.x;
-    if (slot < numSlots) {
-        const int h = height[slot];              // 0: nobody owned this slot in the climb
-        int q = 0;
-        if (h > 0 && leafLinks[slot] >= (unsigned int)OP_N) {
-            int n = slot;
-            for (int steps = 0; n != 0 && steps < numSlots; steps++) {
-                const unsigned int p = parent[n];
-                if (!parent_links_back(p, n, numSlots, nodes)) break;
-                n = (int)(p >> 1);
-            }
-            if (n == 0) q = h;
-        }
-        qual[slot] = q;
-        if (q > 0) {
-            if (q < OP_HIST_LDS) atomicAdd(&sh[q], 1u); else atomicAdd(&hist[q], 1u);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < OP_HIST_LDS; i += OP_BLOCK)
-        if (sh[i]) atomicAdd(&hist[i], sh[i]);
+    op_histogram_body(slot < numSlots, slot, numSlots, nodes, parent, height, leafLinks, qual + slot, hist);
 }
 
 // cursor[h] = the exclusive scan of hist[0 .. root->height]: one workgroup, which reads the height the climb has just reported, so the
@@ -215,200 +90,23 @@ __global__ __launch_bounds__(OP_BLOCK) void opt_histogram(int numSlots, const in
 __global__ __launch_bounds__(OP_BLOCK) void opt_scan(int numSlots, const OpRoot* __restrict__ root, const unsigned int* __restrict__ hist,
                                                      unsigned int* __restrict__ cursor)
 {
-    const int nb = root->done ? min((int)root->height, numSlots) + 1 : 0;
-    unsigned int carry = 0u;
-    for (int base = 0; base < nb; base += OP_BLOCK) {   // uniform
-        const int i = base + threadIdx.x;
-        unsigned int chunk;
-        const unsigned int ex = block_exclusive_scan<OP_BLOCK>(i < nb ? hist[i] : 0u, &chunk);
-        if (i < nb) cursor[i] = carry + ex;
-        carry += chunk;
-    }
+    op_scan_body(root->done ? min((int)root->height, numSlots) + 1 : 0, hist, cursor);
 }
 
-// The roots into their heights' lists; the order inside a list is immaterial (its treelets are disjoint).  A workgroup ranks its
-// roots per height in LDS and reserves one range per height: one global add per workgroup and height instead of one per root, which
-// all land on the same few words (53 us instead of a few on the 49 k-node tree).
 __global__ __launch_bounds__(OP_BLOCK) void opt_scatter(int numSlots, const int* __restrict__ qual, unsigned int* __restrict__ cursor,
                                                         int* __restrict__ list)
 {
-    __shared__ unsigned int sCount[OP_HIST_LDS], sBase[OP_HIST_LDS];
-    for (int i = threadIdx.x; i < OP_HIST_LDS; i += OP_BLOCK) sCount[i] = 0u;
-    __syncthreads();
-    const int slot = blockIdx.x * OP_BLOCK + threadIdx.x;
-    const int q = slot < numSlots ? qual[slot] : 0;
-    unsigned int rank = 0u;
-    if (q > 0 && q < OP_HIST_LDS) rank = atomicAdd(&sCount[q], 1u);
-    __syncthreads();
-    for (int i = threadIdx.x; i < OP_HIST_LDS; i += OP_BLOCK)
-        if (sCount[i]) sBase[i] = atomicAdd(&cursor[i], sCount[i]);
-    __syncthreads();
-    if (q > 0) {
-        const unsigned int at = q < OP_HIST_LDS ? sBase[q] + rank : atomicAdd(&cursor[q], 1u);
-        if (at < (unsigned int)numSlots) list[at] = slot;
-    }
+    op_scatter_body(numSlots, qual, cursor, list);
 }
 
-__device__ __forceinline__ float op_area(const unsigned int (&b)[6])   // rule 4
-{
-    const float dx = ord_dec(b[1]) - ord_dec(b[0]), dy = ord_dec(b[3]) - ord_dec(b[2]), dz = ord_dec(b[5]) - ord_dec(b[4]);
-    return (dx * dy + dy * dz) + dz * dx;
-}
-
-// One wave64 (one workgroup) per treelet; every branch around a barrier is uniform.
+// One wave64 (one workgroup) per treelet (bvh_optimize_treelet.h)
 __global__ __launch_bounds__(64) void opt_treelets(int numSlots, int* __restrict__ nodes, const int* __restrict__ roots, int count,
                                                    unsigned int* __restrict__ rewritten)
 {
-    __shared__ unsigned int sBox[OP_N][6];       // the entries' boxes, ord_enc words, lo.x hi.x lo.y hi.y lo.z hi.z
-    __shared__ int sLink[OP_N];
-    __shared__ float sArea[OP_FULL + 1], sCost[OP_FULL + 1], sOrig[OP_FULL + 1];
-    __shared__ unsigned char sChoice[OP_FULL + 1];
-    __shared__ int sSorted[OP_N - 2];            // the internal slots other than the root, ascending
-    __shared__ int sSub[OP_N - 1];               // the entries of the new inner node with preorder index i
     if ((int)blockIdx.x >= count) return;
-    const int lane = threadIdx.x;
     const int R = roots[blockIdx.x];
     if (R < 0 || R >= numSlots) return;
-
-    // ---- formation (rule 3): lane j < 6 keeps the entry masks of internal node j (node 0 = R), lane e < n entry e's link and area
-    unsigned int m0 = lane == 0 ? 1u : 0u, m1 = lane == 0 ? 2u : 0u;
-    int mySlot = R;                              // lane j: the slot of internal node j + 1
-    int pos0 = 0, pos1 = 1, from = R;
-    for (int n = 2;; n++) {
-        if (lane < 12) {
-            const int w = lane;
-            sBox[box_word_child(w) ? pos1 : pos0][box_word_comp(w)] = ord_enc(__int_as_float(nodes[(size_t)from * kNodeWords + w]));
-        } else if (lane < 14) {
-            sLink[lane == kLinkWord ? pos0 : pos1] = nodes[(size_t)from * kNodeWords + lane];
-        }
-        __syncthreads();
-        if (n == OP_N) break;
-        int myLink = 0;
-        float myArea = 0.0f;
-        if (lane < n) {
-            myLink = sLink[lane];
-            unsigned int b[6];
-#pragma unroll
-            for (int j = 0; j < 6; j++) b[j] = sBox[lane][j];
-            myArea = op_area(b);
-        }
-        const unsigned long long inner = __ballot(lane < n && is_inner_link(myLink, numSlots));
-        if (!inner) return;                      // cannot happen with leafLinks >= 7 in a tree; uniform
-        int cand = __ffsll((long long)inner) - 1;
-        float best = __shfl(myArea, cand);
-        for (int e = cand + 1; e < n; e++) {
-            const float a = __shfl(myArea, e);
-            if (((inner >> e) & 1ull) && a > best) { best = a; cand = e; }
-        }
-        from = inner_index(__shfl(myLink, cand));
-        pos0 = cand;
-        pos1 = n;
-        const unsigned int bit = 1u << cand, fresh = 1u << n;
-        if (lane < n - 1) {
-            if (m0 & bit) m0 |= fresh;
-            if (m1 & bit) m1 |= fresh;
-        } else if (lane == n - 1) {
-            m0 = bit;
-            m1 = fresh;
-        }
-        if (lane == n - 2) mySlot = from;
-        __syncthreads();                         // everybody has read the entries before the next record overwrites one
-    }
-
-    // the five internal slots in ascending order (distinct in a tree; the table starts as R so that no word of it is ever undefined)
-    if (lane < OP_N - 2) sSorted[lane] = R;
-    __syncthreads();
-    {
-        int rank = 0;
-        for (int j = 0; j < OP_N - 2; j++) {
-            const int other = __shfl(mySlot, j);
-            if (other < mySlot) rank++;
-        }
-        if (lane < OP_N - 2) sSorted[rank] = mySlot;
-    }
-
-    // ---- rule 4: the areas of subsets lane and lane + 64; rule 5's single entries
-#pragma unroll
-    for (int half = 0; half < 2; half++) {
-        const int s = lane + 64 * half;
-        unsigned int b[6] = {0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
-        for (int e = 0; e < OP_N; e++) {
-            if ((s >> e) & 1) {
-#pragma unroll
-                for (int j = 0; j < 6; j += 2) {
-                    b[j] = min(b[j], sBox[e][j]);
-                    b[j + 1] = max(b[j + 1], sBox[e][j + 1]);
-                }
-            }
-        }
-        sArea[s] = s ? op_area(b) : 0.0f;
-        sCost[s] = 0.0f;
-        sOrig[s] = 0.0f;
-        sChoice[s] = 0;
-    }
-    __syncthreads();
-
-    // ---- rule 5: subsets of size k; a lane's subsets lane and lane + 64 differ by one in size, so it has at most one per round
-    const int pc = __popc((unsigned int)lane);
-    for (int k = 2; k <= OP_N; k++) {
-        const int s = pc == k ? lane : (pc == k - 1 ? lane + 64 : 0);
-        if (s) {
-            const int low = s & -s, rest = s ^ low;
-            float best = INFINITY;
-            int bp = low;
-            for (int q = 0; q != rest; q = (q - rest) & rest) {   // the subsets of rest in ascending order, rest itself left out
-                const float v = sCost[low | q] + sCost[rest ^ q];
-                if (v < best) { best = v; bp = low | q; }
-            }
-            sCost[s] = sArea[s] + best;
-            sChoice[s] = (unsigned char)bp;
-        }
-        __syncthreads();
-    }
-
-    // ---- rule 6: the existing topology's cost, children before parents (a child is formed after its parent)
-    for (int i = OP_N - 2; i >= 0; i--) {
-        if (lane == i) sOrig[m0 | m1] = sArea[m0 | m1] + (sOrig[m0] + sOrig[m1]);
-        __syncthreads();
-    }
-    if (!(sCost[OP_FULL] < sOrig[OP_FULL])) return;   // uniform: nothing of this treelet changes
-
-    // ---- rule 7
-    if (lane == 0) {
-        sSub[0] = OP_FULL;
-        for (int i = 0; i < OP_N - 1; i++) {
-            const int s = sSub[i], p = sChoice[s], o = s ^ p;
-            const int np = __popc((unsigned int)p);
-            if (np > 1 && i + 1 < OP_N - 1) sSub[i + 1] = p;
-            if (__popc((unsigned int)o) > 1 && i + np < OP_N - 1) sSub[i + np] = o;   // i + 1 + (np - 1)
-        }
-        atomicAdd(&rewritten[blockIdx.x % OP_STAT_SLOTS], 1u);
-    }
-    __syncthreads();
-    for (int item = lane; item < 16 * (OP_N - 1); item += 64) {
-        const int i = item >> 4, w = item & 15;
-        if (w == 15) continue;                   // the fourth link word stays
-        const int s = sSub[i] & OP_FULL, p = sChoice[s], o = s ^ p;
-        const int slot = i == 0 ? R : sSorted[i - 1];
-        int word = 0;                            // w == 14: the split word, which no kernel reads
-        if (w < 12) {
-            const int q = box_word_child(w) ? o : p, j = box_word_comp(w);
-            unsigned int v = (j & 1) ? 0u : 0xFFFFFFFFu;
-            for (int e = 0; e < OP_N; e++)
-                if ((q >> e) & 1) v = (j & 1) ? max(v, sBox[e][j]) : min(v, sBox[e][j]);
-            word = __float_as_int(ord_dec(v));
-        } else if (w < 14) {
-            const int q = w == 12 ? p : o;
-            const int np = __popc((unsigned int)p);
-            if (__popc((unsigned int)q) <= 1) {
-                word = sLink[__ffs(q | (1 << (OP_N - 1))) - 1];
-            } else {
-                const int idx = w == 12 ? i + 1 : i + np;
-                word = inner_link(sSorted[min(max(idx, 1), OP_N - 2) - 1]);
-            }
-        }
-        nodes[(size_t)slot * kNodeWords + w] = word;
-    }
+    op_treelet_body(numSlots, nodes, R, rewritten);
 }
 
 struct OpLayout {

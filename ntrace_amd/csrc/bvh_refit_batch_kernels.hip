@@ -60,17 +60,6 @@ static_assert(sizeof(RbStats) == 64, "RbStats must be 64 bytes");
 
 DeviceScratchPool g_rbPool;
 
-// The entry of listed slot `slot` (< starts[numEntries]): the last e with starts[e] <= slot.  Every entry has a slot, so starts rises strictly.
-__device__ __forceinline__ int rb_entry_of(const int* __restrict__ starts, int numEntries, int slot)
-{
-    int lo = 0, hi = numEntries;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (starts[mid] <= slot) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(RB_BLOCK) void refit_batch_topology(int numEntries, int totalSlots, const int* __restrict__ starts,
                                                                  const RbEntry* __restrict__ table, const int* __restrict__ poolNodes,
                                                                  unsigned int* __restrict__ parent, unsigned int* __restrict__ arrive,
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(RB_BLOCK) void refit_batch_topology(int numEntries,
     unsigned int inner = 0, leaf = 0, err = 0;
     int e = 0;
     if (slot < totalSlots) {
-        e = rb_entry_of(starts, numEntries, slot);
+        e = joint_entry_of(starts, numEntries, slot);
         const int first = starts[e];
         const RbEntry E = table[e];
         int kind[2];
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(RB_BLOCK) void refit_batch_climb(int numEntries, in
     int e = 0, first = 0;
     RbEntry E = {};
     if (live) {
-        e = rb_entry_of(starts, numEntries, slot);
+        e = joint_entry_of(starts, numEntries, slot);
         first = starts[e];
         E = table[e];
     }
@@ -172,24 +161,6 @@ struct RbUploaded {
     std::vector<RbEntry> table;
 };
 RbUploaded g_rbUploaded[kMaxDevices];
-
-// Two ranges [off, off + len) of the same buffer overlap: found by a sort over the entries' indices, not a quadratic scan
-template <class Off, class Len>
-int rb_first_overlap(int n, Off off, Len len, int* other)
-{
-    std::vector<int> order((size_t)n);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return off(a) != off(b) ? off(a) < off(b) : a < b; });
-    int bad = -1;
-    for (int i = 1; i < n; i++) {
-        const int p = order[i - 1], q = order[i];
-        if (off(q) < off(p) + len(p)) {
-            const int hiE = std::max(p, q);
-            if (bad < 0 || hiE < bad) { bad = hiE; *other = std::min(p, q); }
-        }
-    }
-    return bad;
-}
 
 }  // namespace
 }  // namespace ntr
@@ -250,11 +221,11 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
     starts[numEntries] = (int)totalSlots;
     {
         int other = -1;
-        int bad = rb_first_overlap(numEntries, [&](int k) { return entries[k].range.nodesOffset; },
+        int bad = first_range_overlap(numEntries, [&](int k) { return entries[k].range.nodesOffset; },
                                    [&](int k) { return entries[k].range.nodesBytes; }, &other);
         if (bad >= 0)
             return set_error(NTR_ERR_INVALID, "%s: entries %d and %d overlap in the pool's nodes: a BLAS is refitted once per call", fn, other, bad);
-        bad = rb_first_overlap(numEntries, [&](int k) { return entries[k].range.triWoopOffset; },
+        bad = first_range_overlap(numEntries, [&](int k) { return entries[k].range.triWoopOffset; },
                                [&](int k) { return entries[k].range.triWoopBytes; }, &other);
         if (bad >= 0)
             return set_error(NTR_ERR_INVALID, "%s: entries %d and %d overlap in the pool's rows: a BLAS is refitted once per call", fn, other, bad);

@@ -12,6 +12,10 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
 #include "compact_bvh.h"
 
 namespace ntr {
@@ -22,6 +26,20 @@ constexpr int kRecNodesOffset = 12, kRecRowOffset = 13, kRecNodesBytes = 14;
 constexpr int kExitMarker = kSentinel + 1;
 static_assert(kRecordBytes == kNodeBytes, "a record is fetched like a node");
 static_assert(kExitMarker > kSentinel, "the marker is neither a link nor the sentinel");
+
+// ---- device: the batched passes over a pool (bvh_refit_batch_, pool_widen_batch_, bvh_optimize_batch_kernels.hip) -----------------------
+// Such a pass indexes its per-slot state by a joint slot space: entry e owns [starts[e], starts[e + 1]), the running sum of the listed
+// BLASes' slot counts.  The entry of joint slot `slot` (< starts[numEntries]) is the last e with starts[e] <= slot; every entry has a
+// slot, so starts rises strictly.  At most 20 steps over a table that a wave's lanes walk together and the L2 holds.
+__device__ __forceinline__ int joint_entry_of(const int* __restrict__ starts, int numEntries, int slot)
+{
+    int lo = 0, hi = numEntries;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (starts[mid] <= slot) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // ---- host: the checks of the two entry points -----------------------------------------------------------------------------------------
 // A pool buffer's size: a multiple of `unit` in [unit, kPoolMaxBytes]
@@ -46,6 +64,25 @@ inline int check_blas_range(const char* fn, int k, const NtrBlasRange& r, int64_
         return set_error(NTR_ERR_INVALID, "%s: BLAS %d: triWoopOffset and triWoopBytes must be multiples of 16 inside a pool of at most 0x%llx bytes",
                          fn, k, (unsigned long long)kPoolMaxBytes);
     return NTR_OK;
+}
+
+// Two of n ranges [off(k), off(k) + len(k)) of one buffer overlap: the higher index of the first such pair in index order and, in
+// *other, the lower; -1 if none.  Found by a sort over the indices, not a quadratic scan (a batch lists up to 2^20 BLASes).
+template <class Off, class Len>
+int first_range_overlap(int n, Off off, Len len, int* other)
+{
+    std::vector<int> order((size_t)n);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return off(a) != off(b) ? off(a) < off(b) : a < b; });
+    int bad = -1;
+    for (int i = 1; i < n; i++) {
+        const int p = order[i - 1], q = order[i];
+        if (off(q) < off(p) + len(p)) {
+            const int hiE = std::max(p, q);
+            if (bad < 0 || hiE < bad) { bad = hiE; *other = std::min(p, q); }
+        }
+    }
+    return bad;
 }
 
 }  // namespace ntr

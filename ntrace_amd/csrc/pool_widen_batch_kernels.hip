@@ -74,17 +74,6 @@ static_assert(sizeof(WbOut) == 16, "WbOut is 16 bytes");
 
 DeviceScratchPool g_wbPool;
 
-// The entry of joint slot s (< starts[numEntries]): the last e with starts[e] <= s.  Every entry has a slot, so starts rises strictly.
-__device__ __forceinline__ int wb_entry_of(const int* __restrict__ starts, int numEntries, int s)
-{
-    int lo = 0, hi = numEntries;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (starts[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(WB_BLOCK) void wb_seed(int numEntries, const int* __restrict__ starts, unsigned int* __restrict__ level,
                                                     unsigned int* __restrict__ queue, unsigned int* __restrict__ queueEntry,
                                                     unsigned int* __restrict__ bounds, WbReport* __restrict__ report)
@@ -172,7 +161,7 @@ __global__ __launch_bounds__(WB_BLOCK) void wb_emit(int numEntries, int totalSlo
     const int s = blockIdx.x * WB_BLOCK + threadIdx.x;
     unsigned int c2 = 0u, c3 = 0u, c4 = 0u, leaves = 0u, err = 0u, height = 0u, bound = 0u;
     // every lane has an entry, kept slot or not, so that a wave inside one entry is told by one comparison
-    const int e = wb_entry_of(starts, numEntries, s < totalSlots ? s : totalSlots - 1);
+    const int e = joint_entry_of(starts, numEntries, s < totalSlots ? s : totalSlots - 1);
     const unsigned int lv = s < totalSlots ? level[s] : 0u;
     if (lv != 0u) {
         const unsigned int w = wb_rank(rank, blockSums, s);

@@ -18,6 +18,7 @@ CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstan
     std::memset(&m_result, 0, sizeof(m_result));
     std::memset(&m_blasResult, 0, sizeof(m_blasResult));
     std::memset(&m_refitResult, 0, sizeof(m_refitResult));
+    std::memset(&m_optimizeResult, 0, sizeof(m_optimizeResult));
     std::memset(&m_tlasRefitResult, 0, sizeof(m_tlasRefitResult));
 }
 
@@ -120,6 +121,39 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
                                        m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
                                        (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
                                        NULL, &m_refitResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+}
+
+void CudaInstancedBVH::selectRanges(const S32* blas, S32 num, std::vector<NtrBlasRange>& out, const char* what) const
+{
+    if (m_ranges.empty()) fail("CudaInstancedBVH: no BLASes to %s", what);
+    if (!blas) num = (S32)m_ranges.size();
+    if (num < 1) fail("CudaInstancedBVH: no BLASes selected");
+    out.resize((size_t)num);
+    for (S32 i = 0; i < num; i++) {
+        const S32 b = blas ? blas[i] : i;
+        if (b < 0 || b >= (S32)m_ranges.size()) fail("CudaInstancedBVH: BLAS index %d outside [0, %d)", b, (S32)m_ranges.size());
+        out[(size_t)i] = m_ranges[(size_t)b];
+    }
+}
+
+void CudaInstancedBVH::optimizeBLASes(const S32* blas, S32 num, S32 passes)
+{
+    std::vector<NtrBlasRange> sel;
+    selectRanges(blas, num, sel, "optimise");
+    m_widePool = m_wideTlas = false;             // the binary pool's topology changes: widen() again (m_built stays, see the header)
+    const int rc = ntr_bvh_optimize_batch((int32_t)sel.size(), sel.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(), passes, NULL,
+                                          &m_optimizeResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+}
+
+void CudaInstancedBVH::measureBLASes(std::vector<NtrBvhSahResult>& out, const S32* blas, S32 num)
+{
+    std::vector<NtrBlasRange> sel;
+    selectRanges(blas, num, sel, "measure");
+    out.assign(sel.size(), NtrBvhSahResult());
+    const int rc = ntr_bvh_sah_cost_batch((int32_t)sel.size(), sel.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(),
+                                          m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(), out.data(), NULL, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
 }
 

@@ -15,8 +15,18 @@
 //   refit         keeps the topology of the last build() and rewrites the records and every box from the current instances and the
 //                 pool's current node-0 boxes in two launches (ntr_tlas_refit).  Needs a build() with the same instance
 //                 count; a changed count, addBLAS and buildBLASes invalidate it as they invalidate build().  The frame loop of a moving,
-//                 deforming scene is refitBLASes -> setInstances -> refit -> traceBatch, with build() every so many frames: a refit
-//                 keeps the tree the old positions suggested, and its boxes overlap more the further the instances travel
+//                 deforming scene is refitBLASes -> optimizeBLASes every so many frames -> setInstances -> refit -> traceBatch, with
+//                 build() every so many frames: a refit keeps the tree the old positions suggested, and its boxes overlap more the
+//                 further the instances travel
+//   optimizeBLASes   restructures the selected BLASes' treelets in place by ntr_bvh_optimize_batch, all in one pass: the
+//                 repair of BLASes whose refitted trees have degraded, short of buildBLASes (which replaces every BLAS and drops the
+//                 world).  It needs no mesh, so addBLAS trees may be selected.  Leaves, rows and triIndex stay.  isBuilt(), the binary
+//                 TLAS, the records and the world stay as they are: restructuring only re-splits a BLAS's slot 0 into two other parts,
+//                 and the union of the two (min / max, exact) keeps its bits, so every box the TLAS holds is still the box of its BLAS.
+//                 The wide pool is made of the binary pool's topology and is dropped with the wide TLAS, exactly as refitBLASes
+//                 drops them: widen() again.  A treelet is only ever replaced by a strictly better one, so there is nothing to decide
+//   measureBLASes ntr_bvh_sah_cost of every selected BLAS in two launches (ntr_bvh_sah_cost_batch): how good the trees are, before
+//                 and after.  Reads only
 //   setInstanceMasks  one 32-bit visibility mask per instance; NULL: all visible again.  Visibility is not geometry: the
 //                 TLAS is not touched and isBuilt() stays as it was.  Fails before setInstances; a later setInstances with another
 //                 count drops the masks back to all visible, one with the same count keeps them
@@ -51,7 +61,8 @@
 //                 pool and drops the world; clearWorld drops it and the extra record
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
-//   refitBLASes -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch / traceBatch / updateResult per batch
+//   refitBLASes -> optimizeBLASes every so many frames -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch /
+//   traceBatch / updateResult per batch
 // and with a static world set (setWorld, once) nothing of that loop changes: the world BLAS is left out of refitBLASes' selection, the
 // instances move, and every traceBatch of the frame is the world's single-level trace followed by the seeded two-level trace.
 #pragma once
@@ -77,6 +88,10 @@ public:
     // blas: num indices of BLASes to refit, each at most once (NULL: all of them); epsilon: the leaf-box rule of ntr_bvh_refit, 0 for
     // the PLOC trees buildBLASes makes.  triVtxIndex must hold the triangles buildBLASes saw.
     void refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas = NULL, S32 num = -1, F32 epsilon = 0.f);
+    // blas: num indices of BLASes, each at most once (NULL: all of them), addBLAS trees included; passes: 1..8 treelet passes.
+    void optimizeBLASes(const S32* blas = NULL, S32 num = -1, S32 passes = 2);
+    // out[i]: ntr_bvh_sah_cost of the i-th selected BLAS (its seconds is 0); a BLAS may be named more than once.
+    void measureBLASes(std::vector<NtrBvhSahResult>& out, const S32* blas = NULL, S32 num = -1);
     void setInstances(S32 num, const F32* objectToWorld /* num x 12 */, const S32* blas);
     void build(S32 radius = DefaultRadius);
     void refit(void);
@@ -112,6 +127,7 @@ public:
     const NtrTlasResult& getBuildResult(void) const { return m_result; }
     const NtrPlocBatchResult& getBLASBuildResult(void) const { return m_blasResult; }   // of the last buildBLASes (zero before)
     const NtrBvhRefitBatchResult& getBLASRefitResult(void) const { return m_refitResult; }   // of the last refitBLASes (zero before)
+    const NtrBvhOptimizeBatchResult& getBLASOptimizeResult(void) const { return m_optimizeResult; }   // of the last optimizeBLASes (zero before)
     const NtrTlasRefitResult& getRefitResult(void) const { return m_tlasRefitResult; }       // of the last refit (zero before)
     Buffer& getPoolNodeBuffer(void) { return m_poolNodes; }
     Buffer& getPoolTriWoopBuffer(void) { return m_poolTriWoop; }
@@ -139,6 +155,8 @@ private:
     NtrTlasResult m_result;
     NtrPlocBatchResult m_blasResult;
     NtrBvhRefitBatchResult m_refitResult;
+    NtrBvhOptimizeBatchResult m_optimizeResult;
+    void          selectRanges(const S32* blas, S32 num, std::vector<NtrBlasRange>& out, const char* what) const;
     NtrTlasRefitResult m_tlasRefitResult;
     // the wide path (widen): a second node buffer beside the pool, a wide TLAS and wide records
     std::vector<NtrWideBlasRange> m_wideRanges;

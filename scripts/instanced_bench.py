@@ -30,6 +30,13 @@ frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they we
                entry point itself, on range arrays made once), median, min and max, and the kernel launches and read-backs each call takes -- derived from the trees' heights by the rule of
                the two host loops (widen_counts below; every BLAS of a pool is the same tree, so the pool's height is each BLAS's).  The
                two wide pools, the ranges and the result fields are asserted equal before anything is timed
+  * optimize_batch (not in the default parts) ntr_bvh_optimize_batch beside the loop of ntr_bvh_optimize calls, ALTERNATED in this
+               process, each on a fresh copy of one pool, over widen_batch's four pool shapes at 2 passes: GPU time (the calls' own
+               seconds, summed for the loop) and wall time around the entry points, median, min and max, launches and read-backs; then
+               ntr_bvh_sah_cost_batch beside the loop of ntr_bvh_sah_cost calls the same way.  The pools and the costs are asserted equal
+  * optimize_forest (not in the default parts) the forest after its mesh has moved by 0.02, 0.1 and 0.3 of its diagonal: the primary batch
+               and an AO batch through the refitted BLAS, through the same after 1, 2 and 4 treelet passes and through a rebuilt BLAS --
+               time, node fetches per ray (ntr_trace_instanced_stats), the BLAS's SAH cost and the update's own GPU time
   * wide_sweep (not in the default parts) the primary batch of `wide` over k x k x k grids of soup1000 for k = 1, 2, 4, 8, 16 (the last is
                the forest), the camera moved back with the grid: where in instance count the wide path starts to pay
 Prints one JSON line per part.
@@ -243,7 +250,7 @@ def main():
         rows.append(row)
 
     soup = None
-    if "tlas" in args.parts or "forest" in args.parts or "masks" in args.parts or "wide" in args.parts or "wide_sweep" in args.parts:
+    if any(p in args.parts for p in ("tlas", "forest", "masks", "wide", "wide_sweep", "optimize_forest")):
         tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
         soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
 
@@ -501,6 +508,168 @@ def main():
             emit(step("widen_batch %d x %d" % (num_blas, tris_per_blas), args.limit, lambda: widen_batch_row(num_blas, tris_per_blas)))
             nt.lbvh_release_workspace()
 
+    def optimize_batch_row(num_blas, tris_per_blas, passes=2):
+        """The loop of ntr_bvh_optimize calls and ntr_bvh_optimize_batch, alternated, each on a fresh copy of one pool of num_blas copies
+        of one soup; then the loop of ntr_bvh_sah_cost calls and ntr_bvh_sah_cost_batch over the optimised pool, alternated."""
+        import ctypes as C
+        tri, pos = scenes.random_soup(tris_per_blas, seed=1100 + tris_per_blas, walls=False)[:2]
+        tri, pos = np.ascontiguousarray(tri, np.int32), np.ascontiguousarray(pos, F)
+        nt_, nv = tri.shape[0], pos.shape[0]
+        k = np.arange(num_blas)
+        all_tri = (tri[None, :, :] + (k * nv)[:, None, None]).reshape(-1, 3).astype(np.int32)
+        all_pos = np.tile(pos, (num_blas, 1)).astype(F)
+        mn, mx = pos.min(axis=0), pos.max(axis=0)
+        meshes = [(int(i * nt_), int(nt_), mn, mx) for i in k]
+        cn, cw, ci, _ = nt.ploc_batch_capacity(meshes)
+        d_tri, d_pos = up(all_tri), up(all_pos)
+        bufs = [torch.zeros(c, dtype=torch.uint8, device="cuda:0") for c in (cn, cw, ci)]
+        ranges = nt.ploc_build_batch(meshes, all_tri.shape[0], d_tri.data_ptr(), all_pos.shape[0], d_pos.data_ptr(), bufs[0].data_ptr(), cn,
+                                     bufs[1].data_ptr(), cw, bufs[2].data_ptr(), ci, 8, stream)[1]
+        L = nt.lib()
+        arr = (nt.BlasRange * num_blas)(*[nt.BlasRange(*[int(x) for x in r]) for r in ranges])
+        d_work = {"loop": bufs[0].clone(), "batch": bufs[0].clone()}
+        one, res = nt.BvhOptimizeResult(), nt.BvhOptimizeBatchResult()
+
+        def loop(d):
+            secs = 0.0
+            for no, nb, _, _ in ranges:
+                rc = L.ntr_bvh_optimize(d.data_ptr() + no, nb, passes, C.byref(one), C.c_void_p(stream))
+                assert rc == 0, L.ntr_last_error()
+                secs += one.seconds
+            return secs
+
+        def batch(d):
+            rc = L.ntr_bvh_optimize_batch(num_blas, C.cast(arr, C.c_void_p), d.data_ptr(), cn, passes, None, C.byref(res), C.c_void_p(stream))
+            assert rc == 0, L.ntr_last_error()
+            return res.seconds
+        calls = {"loop": loop, "batch": batch}
+        gpu, wall = {"loop": [], "batch": []}, {"loop": [], "batch": []}
+        for _ in range(args.warmup + args.reps):          # alternated, each on the pool as built
+            for name in ("loop", "batch"):
+                d_work[name].copy_(bufs[0])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                secs = calls[name](d_work[name])
+                wall[name].append(time.perf_counter() - t0)
+                gpu[name].append(secs)
+        torch.cuda.synchronize()
+        assert torch.equal(d_work["loop"], d_work["batch"]), "the batch's pool differs from the loop's"
+        slots = ranges[0][1] // 64
+        # what the loop issues: per BLAS and pass five launches and one per height with roots, one read-back; two launches and two
+        # read-backs at the end.  Every BLAS is the same tree, so the batch's launches are one BLAS's
+        row = {"part": "optimize_batch", "blases": num_blas, "tris_per_blas": int(nt_), "slots_per_blas": int(slots), "passes": passes,
+               "pool_bytes": int(cn), "bytes_equal": True, "height_before": int(res.maxHeightBefore), "height_after": int(res.maxHeightAfter),
+               "formed": list(res.formed)[:passes], "rewritten": list(res.rewritten)[:passes],
+               "batch_scratch_bytes": nt.bvh_optimize_batch_scratch_bytes()}
+        counts = {"loop": (num_blas * int(res.launches), num_blas * (passes + 2)), "batch": (int(res.launches), int(res.readBacks))}
+
+        def summary(name, g, w, launches, readbacks):
+            g, w = g[args.warmup:], w[args.warmup:]
+            return {"gpu_ms_median": float(np.median(g)) * 1e3, "gpu_ms_min": float(min(g)) * 1e3, "gpu_ms_max": float(max(g)) * 1e3,
+                    "wall_ms_median": float(np.median(w)) * 1e3, "wall_ms_min": float(min(w)) * 1e3, "wall_ms_max": float(max(w)) * 1e3,
+                    "launches": int(launches), "readbacks": int(readbacks)}
+        for name in ("loop", "batch"):
+            row[name] = summary(name, gpu[name], wall[name], *counts[name])
+        row["wall_loop_over_batch"] = row["loop"]["wall_ms_median"] / row["batch"]["wall_ms_median"]
+
+        # the cost of every BLAS of the optimised pool
+        d_opt = d_work["batch"]
+        sah_one, sah_res, per = nt.BvhSahResult(), nt.BvhSahBatchResult(), (nt.BvhSahResult * num_blas)()
+
+        def sah_loop():
+            secs, costs = 0.0, []
+            for no, nb, wo, wb in ranges:
+                rc = L.ntr_bvh_sah_cost(d_opt.data_ptr() + no, nb, bufs[1].data_ptr() + wo, wb, C.byref(sah_one), C.c_void_p(stream))
+                assert rc == 0, L.ntr_last_error()
+                secs += sah_one.seconds
+                costs.append(sah_one.sahCost)
+            return secs, costs
+
+        def sah_batch():
+            rc = L.ntr_bvh_sah_cost_batch(num_blas, C.cast(arr, C.c_void_p), d_opt.data_ptr(), cn, bufs[1].data_ptr(), cw, C.cast(per, C.c_void_p),
+                                          C.byref(sah_res), C.c_void_p(stream))
+            assert rc == 0, L.ntr_last_error()
+            return sah_res.seconds, [p.sahCost for p in per]
+        sgpu, swall = {"loop": [], "batch": []}, {"loop": [], "batch": []}
+        costs = {}
+        for _ in range(args.warmup + args.reps):
+            for name, fn in (("loop", sah_loop), ("batch", sah_batch)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                secs, costs[name] = fn()
+                swall[name].append(time.perf_counter() - t0)
+                sgpu[name].append(secs)
+        assert np.array_equal(np.asarray(costs["loop"], F).view(np.uint32), np.asarray(costs["batch"], F).view(np.uint32)), "costs differ"
+        row["sah_cost"] = float(costs["batch"][0])
+        row["sah_loop"] = summary("loop", sgpu["loop"], swall["loop"], 2 * num_blas, num_blas)
+        row["sah_batch"] = summary("batch", sgpu["batch"], swall["batch"], 2, 1)
+        row["sah_wall_loop_over_batch"] = row["sah_loop"]["wall_ms_median"] / row["sah_batch"]["wall_ms_median"]
+        return row
+
+    if "optimize_batch" in args.parts:
+        for num_blas, tris_per_blas in ((1024, 1000), (16384, 64), (64, 16384), (1, 1 << 20)):
+            emit(step("optimize_batch %d x %d" % (num_blas, tris_per_blas), args.limit, lambda: optimize_batch_row(num_blas, tris_per_blas)))
+            nt.lbvh_release_workspace()
+
+    def optimize_forest_rows(t, cam):
+        """The forest after its one mesh has moved: the refitted BLAS, the same after 1, 2 and 4 treelet passes, and a rebuilt BLAS, each
+        under a TLAS brought to it, traced by the primary batch and an AO batch; time and node fetches per ray, and what each update costs."""
+        b = t.blas
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays = up(rays)
+        d_res, d_ids = (torch.zeros(max(n, na) * w, dtype=torch.uint8, device="cuda:0") for w in (16, 4))
+        built = [x.clone() for x in b.bufs]
+        fetches = lambda c, count: (c["numTopInnerVisits"] + c["numInstanceEntries"] + c["numInnerVisits"]) / count   # noqa: E731
+        out = []
+        for amp in (0.02, 0.1, 0.3):
+            d = float(np.linalg.norm(b.pos.max(axis=0) - b.pos.min(axis=0)))
+            moved = (b.pos + F(amp * d) * np.sin(F(7.0 / d) * b.pos[:, (1, 2, 0)] + F(0.5))).astype(F)
+            d_moved = up(moved)
+
+            def refit():
+                for x, src in zip(b.bufs, built):
+                    x.copy_(src)
+                r = nt.bvh_refit_batch([(b.ranges[0], 0, b.tri.shape[0], 0.0)], b.bufs[0].data_ptr(), b.nb, b.bufs[1].data_ptr(), b.wb,
+                                       b.bufs[2].data_ptr(), b.tri.shape[0], b.d_tri.data_ptr(), b.pos.shape[0], d_moved.data_ptr(), stream=stream)
+                tr = nt.tlas_refit(t.n, t.d_inst.data_ptr(), b.ranges, b.bufs[0].data_ptr(), b.nb, t.d_nodes.data_ptr(), t.res.nodesBytes,
+                                   t.res.rootLink, t.d_rec.data_ptr(), t.caps[1], stream=stream)
+                return (r.seconds + tr.seconds) * 1e3
+
+            def measure(variant, update_ms):
+                prim = median_rate(lambda: t.trace(n, False, d_rays, d_res, d_ids), n, args.reps, args.warmup)
+                res = d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE)
+                d_ao = up(host_ao_rays(rays, res, na, 7))
+                sp = t.stats(n, False, d_rays, d_res, d_ids, None).as_dict()
+                ao = median_rate(lambda: t.trace(na, True, d_ao, d_res, d_ids), na, args.reps, args.warmup)
+                sa = t.stats(na, True, d_ao, d_res, d_ids, None).as_dict()
+                cost = nt.bvh_sah_cost_batch(b.ranges, b.bufs[0].data_ptr(), b.nb, b.bufs[1].data_ptr(), b.wb, stream)[0][0].sahCost
+                out.append({"part": "optimize_forest", "amplitude": amp, "variant": variant, "update_ms": update_ms, "sah_cost": float(cost),
+                            "primary": prim, "primary_fetches_per_ray": fetches(sp, n), "ao": ao, "ao_fetches_per_ray": fetches(sa, na),
+                            "primary_hits": int(sp["numHits"])})
+            ms = step("forest refit %g" % amp, args.limit, refit)
+            step("forest refitted %g" % amp, args.limit, lambda: measure("refitted", ms))
+            for passes in (1, 2, 4):
+                ms = step("forest refit %g" % amp, args.limit, refit)
+                o = step("forest optimise %g %d" % (amp, passes), args.limit,
+                         lambda: nt.bvh_optimize_batch(b.ranges, b.bufs[0].data_ptr(), b.nb, passes, stream, entry_results=False)[0])
+                step("forest optimised %g %d" % (amp, passes), args.limit, lambda: measure("refit + %d passes" % passes, ms + o.seconds * 1e3))
+
+            def rebuild():
+                caps = nt.lbvh_capacity(b.tri.shape[0])
+                r = nt.ploc_build(b.tri.shape[0], b.d_tri.data_ptr(), b.pos.shape[0], d_moved.data_ptr(), moved.min(axis=0), moved.max(axis=0),
+                                  b.bufs[0].data_ptr(), caps[0], b.bufs[1].data_ptr(), caps[1], b.bufs[2].data_ptr(), caps[2], 8, stream)
+                assert (r.nodesBytes, r.triWoopBytes) == (b.nb, b.wb)
+                t.res = t.build()
+                return (r.seconds + t.res.seconds) * 1e3
+            ms = step("forest rebuild %g" % amp, args.limit, rebuild)
+            step("forest rebuilt %g" % amp, args.limit, lambda: measure("rebuilt", ms))
+            assert nt.trace_status() == 0, "traversal stack overflow"
+        for x, src in zip(b.bufs, built):
+            x.copy_(src)
+        t.res = t.build()
+        return out
+
     if "identity" in args.parts or "masks" in args.parts or "wide" in args.parts:
         tri, pos, cam = scenes.atrium()
         atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
@@ -514,7 +683,7 @@ def main():
         if "wide" in args.parts:
             emit(wide_frame("identity", t, cam))
 
-    if "forest" in args.parts or "masks" in args.parts or "wide" in args.parts:
+    if "forest" in args.parts or "masks" in args.parts or "wide" in args.parts or "optimize_forest" in args.parts:
         rng = np.random.default_rng(4096)
         g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
         t = step("forest tlas", args.limit, lambda: Tlas(soup, transforms(rotations(4096, rng), (g - 7.5) * 30.0), stream))
@@ -528,6 +697,9 @@ def main():
         if "wide" in args.parts:
             emit(wide_frame("forest", t, cam))
             emit(step("pool widen loop", args.limit, wide_pool_loop))
+        if "optimize_forest" in args.parts:
+            for row in optimize_forest_rows(t, cam):
+                emit(row)
 
     if "wide_sweep" in args.parts:
         for k in (1, 2, 4, 8, 16):
