@@ -361,7 +361,7 @@ NTR_API int ntr_trace_bvh_stats(const char* kernelName, int32_t numRays, int32_t
  *                    is the range in which the kernels' refactored divide is the hardware
  *                    divide (see csrc/trace_lane.h).
  *   NTR_BVH_NOTINY   every box coordinate is 0 or |x| >= 2^-93 (lets rays with an exactly-zero
- *                    origin component use the same path).
+ *                    origin component use the same path).  A NaN is neither: it withholds this flag as it does the other three box flags.
  *   NTR_BVH_ORDERED  every child box has lo <= hi on each axis: for a wave whose rays share the signs of their direction
  *                    components the kernels then know which of a slab's two quotients is the smaller one without comparing.
  *   NTR_BVH_WIDE_LEAVES  leaves hold two or more triangles on average (the device LBVH with leafSize 8; a host SAH tree built with

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void bvh_validate_kernel(const float4* __restr
             const float a = fabsf(c[k]);
             notFinite = notFinite || !(a < 0x1p100f);  // also true for NaN
             notFast = notFast || !(a < 0x1p55f);
-            tiny = tiny || (c[k] != 0.0f && a < 0x1p-93f);
+            tiny = tiny || !(c[k] == 0.0f || a >= 0x1p-93f);   // as the header words it: a NaN is neither
         }
     }
     const unsigned int bits = (__ballot(notFinite) != 0ull ? 1u : 0u) | (__ballot(notFast) != 0ull ? 2u : 0u) |

@@ -29,12 +29,15 @@ def _dot4(a, bx, by, bz, bw):
     return r
 
 
-def trace(nodes, woop, tri_index, rays, any_hit=False, max_stack=100, return_stats=False, inner_hook=None):
+def trace(nodes, woop, tri_index, rays, any_hit=False, max_stack=100, return_stats=False, inner_hook=None, divide=None):
     """Returns (id, t); with return_stats also the counters (inner nodes visited, triangle tests, leaf terminators
     read, hits) as the reference's RayStats defines them (CudaBVH.cpp:746-749, 1107-1111).
     inner_hook(ray indices, node visited (byte offset), node the ray holds afterwards): called once per lock-step inner step
-    (analysis scripts: which node follows which)."""
+    (analysis scripts: which node follows which).
+    divide(x, d): the slab test's quotient on float32 arrays; the default is the float32 `/` (sensitivity tests pass a worse one)."""
     n_inner = n_tri = n_leaf = 0
+    if divide is None:
+        divide = lambda x, d: x / d
     nodes_f = np.frombuffer(np.ascontiguousarray(nodes).tobytes(), dtype=F)
     nodes_i = nodes_f.view(np.int32)
     woop_f = np.frombuffer(np.ascontiguousarray(woop).tobytes(), dtype=F).reshape(-1, 4)
@@ -119,8 +122,8 @@ def trace(nodes, woop, tri_index, rays, any_hit=False, max_stack=100, return_sta
                 ex, ey, ez = dx[inner], dy[inner], dz[inner]
 
                 def box(lox, hix, loy, hiy, loz, hiz):
-                    t0x, t0y, t0z = (lox - rx) / ex, (loy - ry) / ey, (loz - rz) / ez
-                    t1x, t1y, t1z = (hix - rx) / ex, (hiy - ry) / ey, (hiz - rz) / ez
+                    t0x, t0y, t0z = divide(lox - rx, ex), divide(loy - ry, ey), divide(loz - rz, ez)
+                    t1x, t1y, t1z = divide(hix - rx, ex), divide(hiy - ry, ey), divide(hiz - rz, ez)
                     mn = _smax(_smax(_smin(t0x, t1x), _smin(t0y, t1y)), _smin(t0z, t1z))
                     mx = _smin(_smin(_smax(t0x, t1x), _smax(t0y, t1y)), _smax(t0z, t1z))
                     return mn, mx

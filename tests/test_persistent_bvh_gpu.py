@@ -13,6 +13,7 @@ from oracle import oracle
 import np_bvh_binned as bb
 import ray_sets
 from gpu_util import up
+from np_bvh_validate import expected_flags
 
 pytestmark = pytest.mark.gpu
 
@@ -96,26 +97,6 @@ def _assert_equal_to_spec(b, ref):
                medianFallbacks=r.medianFallbacks, costLeaves=r.costLeaves, depthLeaves=r.depthLeaves)
     assert got == st, (got, st)
     assert r.nodesBytes == ref["nodes"].nbytes and r.triWoopBytes == ref["woop"].nbytes and r.triIndexBytes == ref["tri_index"].nbytes
-
-
-def expected_flags(nodes, woop_bytes):
-    """ntr_bvh_validate's flags restated over a Compact node array."""
-    f = nodes.view(F).reshape(-1, 16)[:, :12].reshape(-1, 2)
-    a = np.abs(f)
-    flags = 0
-    if (a < F(2.0 ** 100)).all():
-        flags |= nt.BVH_FINITE
-    if (a < F(2.0 ** 55)).all():
-        flags |= nt.BVH_FASTDIV
-    if not ((f != 0) & (a < F(2.0 ** -93))).any():
-        flags |= nt.BVH_NOTINY
-    if (f[:, 0] <= f[:, 1]).all():
-        flags |= nt.BVH_ORDERED
-    ch = nodes.reshape(-1, 16)[:, 12:14].reshape(-1)
-    leaves = ch[ch < 0]
-    if leaves.size and float((~leaves).max()) / leaves.size >= 7.0:
-        flags |= nt.BVH_WIDE_LEAVES
-    return flags
 
 
 @pytest.mark.parametrize("name", ["cornell", "soup1500", "atrium", "t16", "t17", "stacked", "one", "flat", "zero_area"])
