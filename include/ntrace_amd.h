@@ -1176,6 +1176,76 @@ NTR_API int ntr_trace_instanced_wide_seeded_stats(int32_t numRays, int32_t anyHi
                                                   const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* may be NULL */,
                                                   NtrInstancedTraceStats* stats, void* stream);
 
+/* FAST slab arithmetic in the two-level trace, from device-resident flags (csrc/instanced_validate_kernels.hip,
+ * csrc/trace_instanced_fast_kernels.hip).  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_fast.py.  The records, the instance ids, the status word and the eight counters are ntr_trace_instanced_masked's
+ * (or, with a seed, ntr_trace_instanced_seeded's) in every word, for closest hit and any hit, whatever the flags say: in its range the
+ * FAST quotient is the IEEE divide bit for bit (ntr_selftest_division), so the flags and the vote only select between two exact forms
+ * of the inner-node step.  An opt-in entry point; nothing else launches these kernels.
+ * ntr_instanced_validate: a one-wave launch that clears the four words and one grid-stride launch over both node buffers (two kernels:
+ *   a memset node does not replay reliably in a captured graph); asynchronous on `stream`, capturable, allocates nothing and reads
+ *   nothing back.
+ *   layout      d_flags[0], d_flags[1]: the WITHHELD bits of the top-level tree and of the pool, bit values NTR_BVH_FINITE / FASTDIV /
+ *               NOTINY / ORDERED; d_flags[2], d_flags[3]: zero.  Withheld and not granted, so that an OR from any wave is the whole
+ *               protocol.  The trace reads FASTDIV and NOTINY; FINITE and ORDERED are recorded for the caller.
+ *   rule        ntr_bvh_validate's, word for word, for those four flags: the twelve box floats of every 64-byte node are tested, the
+ *               child words are not.  No NTR_BVH_WIDE_LEAVES, no refresh of a top-of-tree table.
+ *   extent      EVERY node slot in [0, bytes) of both buffers: the slack and the gaps of a pool count, whatever they hold.  That is
+ *               conservative: it can only withhold.  tlasNodesBytes == 0 (one instance: rootLink ~0), or d_tlasNodes == NULL, withholds
+ *               nothing for the top level.
+ *   consequence the tree of a one-triangle BLAS has an empty sibling box (lo = FLT_MAX, hi = -FLT_MAX): a pool that holds one has
+ *               FINITE, FASTDIV and ORDERED withheld for the whole pool, and FAST then runs on the top level only.  Per-BLAS flags are
+ *               out of scope.
+ *   when        after every call that rewrites a node box of either buffer, and before the next fast trace (on one stream, or in one
+ *               graph, in that order): ntr_ploc_build_batch and every other build into the pool, ntr_bvh_refit / ntr_bvh_refit_batch,
+ *               ntr_bvh_optimize / ntr_bvh_optimize_batch and ntr_bvh_reorder on the pool; ntr_tlas_build and ntr_tlas_refit on the top
+ *               level; any copy into the buffers.  Flags that grant what the buffers do not hold -- stale flags, or another pool's --
+ *               are a caller error: the records are then undefined (nothing outside the buffers is read all the same).  Flags that
+ *               wrongly WITHHOLD only cost speed.
+ *   errors      NTR_ERR_INVALID before any device work: a null d_flags or d_poolNodes; sizes that are not multiples of 64,
+ *               tlasNodesBytes above the Compact limit or poolNodesBytes outside the pool limits; d_flags, d_tlasNodes or d_poolNodes not
+ *               16-byte aligned.  Nothing else is refused: a capturing stream is accepted.
+ * ntr_instanced_flags_read: the GRANTED sets, the complement within the four bits; blocking (it synchronises `stream`), refused on a
+ *   capturing stream.
+ * ntr_trace_instanced_fast: ntr_trace_instanced_seeded's argument list with d_flags before `seconds`; vis may be NULL, and d_seedResults
+ *   may be NULL, which means unseeded (seedInstance is then ignored, and the rule is ntr_trace_instanced_masked's).  The loop is the
+ *   masked (seeded) one with one addition, a per-lane state `nice`: the lane's CURRENT ray may take FAST on its CURRENT level.
+ *   start       nice = !(d_flags[0] & FASTDIV) && the world ray is in the FAST ranges (directions 2^-40 <= |d| <= 2^20, origin
+ *               components 2^-36 <= |o| < 2^55, a zero origin component only when d_flags[0] does not withhold NOTINY)
+ *   entering    after the transform: the same test of the object ray against d_flags[1]
+ *   leaving     the world ray's value again
+ *   vote        one ballot per iteration of a wave: the iteration runs the FAST form of the inner-node step iff no live lane has
+ *               nice == false, else the GENERIC form; the choice is wave-uniform
+ *   flag words  read once per wave by the launch: a captured launch reads them at replay time, after a captured validate
+ * ntr_trace_instanced_fast_stats: the same records through the instrumented kernels, plus ntr_trace_instanced_stats's counters and
+ *   NtrInstancedFastStats (wave w is rays [64 w, 64 w + 64); all exact and equal to the spec's).  Blocks; refused on a capturing stream.
+ * Errors: NTR_ERR_INVALID before any device work for everything ntr_trace_instanced_seeded refuses (but a null d_seedResults), a null
+ *   d_flags and a d_flags that is not 16-byte aligned, null stats; numRays == 0 returns NTR_OK with the stats zeroed.  Without a device,
+ *   after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+typedef struct NtrInstancedFastStats {
+    uint64_t waveSteps;       /* iterations of a wave with at least one live lane, summed over the waves */
+    uint64_t fastWaveSteps;   /* those that took the FAST form */
+    uint64_t niceStarts;      /* rays that start live and nice */
+    uint64_t niceEntries;     /* entering steps that entered and leave the lane nice */
+} NtrInstancedFastStats;
+NTR_API int ntr_instanced_validate(const void* d_tlasNodes, int64_t tlasNodesBytes, const void* d_poolNodes, int64_t poolNodesBytes,
+                                   uint32_t* d_flags /* 4 words, 16-byte aligned */, void* stream);
+NTR_API int ntr_instanced_flags_read(const uint32_t* d_flags, uint32_t* tlasFlags, uint32_t* poolFlags, void* stream);
+NTR_API int ntr_trace_instanced_fast(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults /* NULL: unseeded */,
+                                     int32_t seedInstance, NtrRayResult* d_results /* may equal d_seedResults */, int32_t* d_instanceIDs,
+                                     const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                     int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                     int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                     const NtrInstanceVisibility* vis /* NULL: no masks */, const uint32_t* d_flags,
+                                     float* seconds /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_trace_instanced_fast_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                           int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs, const void* d_tlasNodes,
+                                           int64_t tlasNodesBytes, int32_t rootLink, const void* d_records, int32_t numInstances,
+                                           const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                           int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                           const NtrInstanceVisibility* vis /* may be NULL */, const uint32_t* d_flags,
+                                           NtrInstancedTraceStats* stats, NtrInstancedFastStats* fastStats, void* stream);
+
 /* In-place refit of 4-wide trees: the update path of an animated instanced frame for the wide two-level trace
  * (csrc/wide_refit_batch_kernels.hip, csrc/tlas_wide_refit_kernels.hip, csrc/wide_climb.h).  ntr_pool_widen and
  * ntr_tlas_widen block, read back and may change a wide tree's topology from frame to frame; these two calls keep the wide topology

@@ -69,6 +69,15 @@ class InstancedTraceStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class InstancedFastStats(C.Structure):
+    """NtrInstancedFastStats (the rule is tests/np_instanced_fast.py): iterations of a wave with a live lane, those that took
+    the FAST form of the step, rays that start live and nice, entering steps that leave the lane nice.  Wave w is rays [64 w, 64 w + 64)."""
+    _fields_ = [(n, C.c_uint64) for n in ("waveSteps", "fastWaveSteps", "niceStarts", "niceEntries")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class LbvhResult(C.Structure):
     _fields_ = [("numNodes", C.c_int32), ("numLeaves", C.c_int32), ("numLevels", C.c_int32), ("pad", C.c_int32),
                 ("nodesBytes", C.c_int64), ("triWoopBytes", C.c_int64), ("triIndexBytes", C.c_int64),
@@ -508,6 +517,13 @@ SYMBOLS = [
                                                   C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
     ("ntr_trace_instanced_wide_seeded_stats", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64,
                                                         _vp, C.POINTER(InstanceVisibility), C.POINTER(InstancedWideTraceStats), _vp]),
+    ("ntr_instanced_validate", C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    ("ntr_instanced_flags_read", C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), _vp]),
+    ("ntr_trace_instanced_fast", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                           C.POINTER(InstanceVisibility), _vp, C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_fast_stats", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                 C.POINTER(InstanceVisibility), _vp, C.POINTER(InstancedTraceStats),
+                                                 C.POINTER(InstancedFastStats), _vp]),
     ("ntr_pool_wide_refit", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.POINTER(WideRefitResult), _vp]),
     ("ntr_pool_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_wide_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
@@ -1388,6 +1404,53 @@ def trace_instanced_seeded_stats(num_rays, any_hit, d_rays, d_seed_results, seed
                   d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
                   d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
     return st
+
+
+def instanced_validate(d_tlas_nodes, tlas_nodes_bytes, d_pool_nodes, pool_nodes_bytes, d_flags, stream=0):
+    """ntr_instanced_validate: the withheld validate bits of the top-level tree and of the pool into d_flags[0] and d_flags[1] (four
+    words, 16-byte aligned; the rule is tests/np_instanced_fast.py, validate).  Asynchronous on `stream` and capturable; to be run
+    again after every call that rewrites a node box, before the next trace_instanced_fast."""
+    _check(lib().ntr_instanced_validate(_vp(d_tlas_nodes), int(tlas_nodes_bytes), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_flags),
+                                        _vp(stream)))
+
+
+def instanced_flags_read(d_flags, stream=0):
+    """ntr_instanced_flags_read -> (granted top-level flags, granted pool flags): the complement of d_flags[0] and d_flags[1] within
+    BVH_FINITE | BVH_FASTDIV | BVH_NOTINY | BVH_ORDERED.  Blocks."""
+    t, q = _u32(0), _u32(0)
+    _check(lib().ntr_instanced_flags_read(_vp(d_flags), C.byref(t), C.byref(q), _vp(stream)))
+    return int(t.value), int(q.value)
+
+
+def trace_instanced_fast(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                         num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, d_flags, vis=None,
+                         d_seed_results=0, seed_instance=-1, stream=0, timed=True):
+    """ntr_trace_instanced_fast: trace_instanced_masked's records -- trace_instanced_seeded's when d_seed_results is given -- with the
+    FAST slab test wherever the wave's rays and d_flags (instanced_validate's words, read by the launch) allow it; the rule is
+    tests/np_instanced_fast.py.  timed=True returns the GPU seconds; timed=False is asynchronous on `stream` (capturable) and returns
+    None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_instanced_fast(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
+                                          _vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link),
+                                          _vp(d_records), int(num_instances), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop),
+                                          int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
+                                          _vp(d_flags), C.byref(sec) if timed else None, _vp(stream)))
+    return float(sec.value) if timed else None
+
+
+def trace_instanced_fast_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                               num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, d_flags,
+                               vis=None, d_seed_results=0, seed_instance=-1, stream=0):
+    """ntr_trace_instanced_fast_stats: trace_instanced_fast's records through the instrumented kernels ->
+    (InstancedTraceStats, InstancedFastStats).  Blocks; refused on a capturing stream."""
+    st, fs = InstancedTraceStats(), InstancedFastStats()
+    _check(lib().ntr_trace_instanced_fast_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
+                                                _vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes), int(tlas_nodes_bytes),
+                                                int(root_link), _vp(d_records), int(num_instances), _vp(d_pool_nodes),
+                                                int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
+                                                C.byref(vis) if vis is not None else None, _vp(d_flags), C.byref(st), C.byref(fs),
+                                                _vp(stream)))
+    return st, fs
 
 
 def trace_instanced_wide_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes,

@@ -8,6 +8,9 @@
 //   NTR_TI_STATS    1: per-lane counters, summed into x.stats at the end
 //   NTR_TI_SEEDED   1: the ray starts from a seed record (InstancedSeed sd; the rule is tests/np_instanced_seeded.py): tmax from a seed that
 //                   is a hit, no traversal for an any-hit ray whose seed is a hit, and a lane that accepts nothing stores the seed's words
+//   NTR_TI_FAST     1: FAST slab arithmetic from device-resident flags (InstancedFast f and level_nice of
+//                   trace_instanced_fast_kernels.hip; the rule is tests/np_instanced_fast.py): a per-lane `nice` says that
+//                   the lane's current ray may take FAST on its current level, and the wave votes per iteration on the step's form
 // An include and not a function template because the unmasked variant must stay the kernel it was, instruction for instruction
 // (scripts/kernel_isa_diff.sh): with the loop in a __forceinline__ function that the kernels call, hipcc orders its passes differently and
 // allocates other registers, and every such change would have to be measured again.  No include guard: the text is meant
@@ -70,10 +73,38 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     // a degenerate ray (Ray::degenerate, Util.hpp:65) is a miss without traversal
     int node = (valid && r.tmin < r.tmax) ? p.rootLink : kSentinel;
 #endif
+#if NTR_TI_FAST
+    // the withheld bits of the two levels (ntr_instanced_validate), read by the launch: a replay sees what the last validate wrote
+    const unsigned int heldTlas = f.flags[0], heldPool = f.flags[1];
+    // `nice`: of the lane's current ray on its current level; level_nice sets r.rx, r.ry, r.rz when it says yes.  The instrumented
+    // variants hold it and niceStart as words pinned to vector registers (NTR_TI_NICE_PIN): as lane masks in scalar pairs they are
+    // SGPR spills in the seeded one
+#if NTR_TI_STATS
+    typedef unsigned int nice_t;
+#define NTR_TI_NICE_PIN(V) keep(V)
+#else
+    typedef bool nice_t;
+#define NTR_TI_NICE_PIN(V)
+#endif
+    nice_t nice = level_nice(r, heldTlas);
+    NTR_TI_NICE_PIN(nice);
+    nice_t niceStart = node != kSentinel && nice;
+    NTR_TI_NICE_PIN(niceStart);
+    // (STATS only.  The wave's two counters are kept by lane 0, in vector registers: as scalars they are six SGPR spills in the seeded
+    // instrumented kernel)
+    const unsigned int laneZero = lane == 0 ? 1u : 0u;
+    unsigned int waveSteps = 0u, fastSteps = 0u, niceEntries = 0u;
+#endif
 
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
     for (;;) {
         if (__ballot(node != kSentinel) == 0ull) break;
+#if NTR_TI_FAST
+        // the wave's vote, one ballot per iteration: FAST iff no live lane holds a ray that is not nice -- a scalar branch around the
+        // two instantiations of the step
+        const bool fastStep = __ballot(node != kSentinel && !nice) == 0ull;
+        if (STATS) { waveSteps += laneZero; fastSteps += fastStep ? laneZero : 0u; }
+#endif
         const bool top = inst < 0;
         const bool inner = (unsigned)node < (unsigned)kSentinel;
         const bool neg = node < 0;
@@ -108,10 +139,17 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
                 r.ox = o.x; r.oy = o.y; r.oz = o.z;
                 r.dx = dd.x; r.dy = dd.y; r.dz = dd.z;
                 inst = -1;
+#if NTR_TI_FAST
+                nice = level_nice(r, heldTlas);
+                NTR_TI_NICE_PIN(nice);
+#endif
             }
             node = stack_pop(st, spill);   // (any other such word is no link: it is dropped)
         } else if (top && inner) {
             if (STATS) ls.topInner++;
+#if NTR_TI_FAST
+            if (fastStep) inner_advance<true, 8>(a, b, c, d, r, node, st, spill, p.status); else
+#endif
             inner_advance<false, 8>(a, b, c, d, r, node, st, spill, p.status);
         } else if (top) {
             // entering instance ~node: its record is worldToObject (a, b, c) and nodesOffset, row offset, nodesBytes (d)
@@ -135,6 +173,11 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
                 inst = idx;
                 node = 0;
                 if (STATS) ls.entries++;
+#if NTR_TI_FAST
+                nice = level_nice(r, heldPool);
+                NTR_TI_NICE_PIN(nice);
+                if (STATS) niceEntries += nice ? 1u : 0u;
+#endif
             }
         } else {
             int row = -1;   // the BLAS's own row of a hit this step accepts
@@ -144,9 +187,15 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
                 const bool term = __float_as_uint(a.x) == kLeafTerm;
                 if (inner) ls.inner++;
                 else if (!term) ls.tris++;
+#if NTR_TI_FAST
+                if (fastStep) unified_advance<true, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status); else
+#endif
                 unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
                 if (!inner && (term || (!(anyHit && row >= 0) && __float_as_uint(d.x) == kLeafTerm))) ls.leaves++;
             } else {
+#if NTR_TI_FAST
+                if (fastStep) unified_advance<true, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status); else
+#endif
                 unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
             }
             if (row >= 0) {
@@ -184,5 +233,16 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
 #else
         atomicAdd(&x.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
 #endif
+#if NTR_TI_FAST
+        if (lane == 0) {   // (lane 0 of a launched wave is a ray)
+            atomicAdd(&x.stats[8], (unsigned long long)waveSteps);
+            atomicAdd(&x.stats[9], (unsigned long long)fastSteps);
+        }
+        atomicAdd(&x.stats[10], (unsigned long long)niceStart);
+        atomicAdd(&x.stats[11], (unsigned long long)niceEntries);
+#endif
     }
 }
+#if NTR_TI_FAST
+#undef NTR_TI_NICE_PIN
+#endif

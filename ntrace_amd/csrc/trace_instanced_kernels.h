@@ -38,7 +38,8 @@ struct InstancedExtras {
     const void* instMasks;         // numInstances words, or NULL: every instance 0xFFFFFFFF
     const uint32_t* rayMasks;      // numRays words, or NULL: every ray has rayMask
     uint32_t instMasksBytes, rayMask;
-    unsigned long long* stats;     // STATS: {top inner, entries, masked, inner, triangle tests, leaf terminators, hits}
+    unsigned long long* stats;     // STATS: {top inner, entries, masked, inner, triangle tests, leaf terminators, hits}; the fast variants
+                                   // (NTR_TI_FAST) add [8..11] = {wave steps, FAST wave steps, nice starts, nice entries}
 };
 struct InstancedLaneStats {
     unsigned int topInner, entries, masked, inner, tris, leaves;

@@ -9,7 +9,8 @@
 //   entering an instance        (top level, link ~i) push the exit marker, transform the ray by record i, go on at the BLAS's node 0
 //   leaving an instance         (the exit marker was popped) reload the world ray from d_rays -- one 32-byte load, rare against the
 //                               steps, for six registers less -- and pop again
-// Arithmetic is the GENERIC path only: a transformed ray need not lie in the FAST ranges, and the pool has no validate flags.
+// Arithmetic is the GENERIC path only: a transformed ray need not lie in the FAST ranges, and the pool has no validate flags.  (Both
+// are answered by an opt-in sibling, not here: trace_instanced_fast_kernels.hip, NTR_TI_FAST)
 // Fetches go through four wave-uniform range-checked descriptors (fetch64_four_buffers: the shape of fetch64_two_buffers): whatever a
 // link or an offset holds, a lane reads zeros and never faults.  Per lane beyond the single-level loop: nodesOffset, the row offset
 // and the instance index, which also says which level the lane is on (-1: the top level).
@@ -42,12 +43,14 @@ namespace {
 #define NTR_TI_MASKED 0
 #define NTR_TI_STATS 0
 #define NTR_TI_SEEDED 0
+#define NTR_TI_FAST 0
 #include "trace_instanced_body.h"
 #undef NTR_TI_KERNEL
 #undef NTR_TI_PARAMS
 #undef NTR_TI_MASKED
 #undef NTR_TI_STATS
 #undef NTR_TI_SEEDED
+#undef NTR_TI_FAST
 
 // The entry points' one body.  vis == NULL, or a vis that can refuse nothing (no arrays and rayMask all ones), launches the unmasked
 // kernel; stats != NULL launches the instrumented one and reads the counters back.  seeded: the seeded kernels (always the masked loop).

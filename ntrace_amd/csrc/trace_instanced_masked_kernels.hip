@@ -14,6 +14,7 @@ namespace {
 #define NTR_TI_PARAMS InstancedParams p, InstancedExtras x
 #define NTR_TI_MASKED 1
 #define NTR_TI_SEEDED 0
+#define NTR_TI_FAST 0
 
 #define NTR_TI_KERNEL trace_instanced_masked
 #define NTR_TI_STATS 0
@@ -30,6 +31,7 @@ namespace {
 #undef NTR_TI_PARAMS
 #undef NTR_TI_MASKED
 #undef NTR_TI_SEEDED
+#undef NTR_TI_FAST
 
 }  // namespace
 

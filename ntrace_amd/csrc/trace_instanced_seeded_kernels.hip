@@ -17,6 +17,7 @@ namespace {
 #define NTR_TI_PARAMS InstancedParams p, InstancedExtras x, InstancedSeed sd
 #define NTR_TI_MASKED 1
 #define NTR_TI_SEEDED 1
+#define NTR_TI_FAST 0
 
 #define NTR_TI_KERNEL trace_instanced_seeded
 #define NTR_TI_STATS 0
@@ -33,6 +34,7 @@ namespace {
 #undef NTR_TI_PARAMS
 #undef NTR_TI_MASKED
 #undef NTR_TI_SEEDED
+#undef NTR_TI_FAST
 
 }  // namespace
 

@@ -1,7 +1,7 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
 // and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen_batch (ntr_pool_widen for one BLAS) / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
 // ntr_trace_instanced_wide, and a static world over ntr_trace_bvh / ntr_trace_instanced_seeded / ntr_trace_instanced_wide_seeded (see the
-// header).
+// header), and the FAST path over ntr_instanced_validate / ntr_trace_instanced_fast.
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
@@ -9,7 +9,8 @@
 namespace FW {
 
 CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false),
-                                           m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false), m_world(-1)
+                                           m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false), m_world(-1),
+                                           m_traceFast(false), m_fastStale(true), m_fastValidations(0)
 {
     std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
     std::memset(&m_wideResult, 0, sizeof(m_wideResult));
@@ -46,6 +47,7 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_meshes.push_back(none);
     m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
+    m_fastStale = true;
     return (S32)m_ranges.size() - 1;
 }
 
@@ -62,6 +64,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     clearWorld();                                    // the pool is replaced: whatever BLAS the world named is gone
     m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
+    m_fastStale = true;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
     m_poolTriIndex.resizeDiscard(capI);
@@ -117,6 +120,7 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
     }
     m_built = false;
     m_widePool = m_wideTlas = false;             // this method refits the binary pool only: widen() again, or call refitBLASesWide
+    m_fastStale = true;
     const int rc = ntr_bvh_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
                                        m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
                                        (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
@@ -142,6 +146,7 @@ void CudaInstancedBVH::optimizeBLASes(const S32* blas, S32 num, S32 passes)
     std::vector<NtrBlasRange> sel;
     selectRanges(blas, num, sel, "optimise");
     m_widePool = m_wideTlas = false;             // the binary pool's topology changes: widen() again (m_built stays, see the header)
+    m_fastStale = true;                          // node boxes are rewritten
     const int rc = ntr_bvh_optimize_batch((int32_t)sel.size(), sel.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(), passes, NULL,
                                           &m_optimizeResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
@@ -196,6 +201,7 @@ void CudaInstancedBVH::setWorld(S32 blas, const char* kernelName)
     if (!kernelName || !kernelName[0]) fail("CudaInstancedBVH::setWorld: no kernel name");
     m_world = blas;
     m_worldKernel = kernelName;
+    m_fastStale = true;
     writeWorldRecord();                              // the TLAS never sees the world: m_built stays
 }
 
@@ -203,6 +209,7 @@ void CudaInstancedBVH::clearWorld(void)
 {
     if (m_world < 0) return;
     m_world = -1;
+    m_fastStale = true;
     m_instances.resize((S64)m_numInstances * sizeof(NtrInstance));
 }
 
@@ -221,6 +228,7 @@ void CudaInstancedBVH::build(S32 radius)
     if (ntr_tlas_capacity(m_numInstances, &capN, &capR) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_built = m_topology = m_wideTopology = false;
     m_wideTlas = false;
+    m_fastStale = true;
     m_tlasNodes.resizeDiscard(capN);
     m_records.resizeDiscard(capR);
     const int rc = ntr_tlas_build(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
@@ -236,6 +244,7 @@ void CudaInstancedBVH::refit(void)
     if (!m_topology || m_numInstances < 1)
         fail("CudaInstancedBVH: no TLAS to refit: call build() first, and again after the instance count or the BLASes have changed");
     m_wideTlas = false;
+    m_fastStale = true;
     const int rc = ntr_tlas_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
                                   m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL,
                                   m_result.nodesBytes, m_result.rootLink, m_records.getMutableCudaPtr(), m_records.getSize(), NULL,
@@ -323,6 +332,29 @@ void CudaInstancedBVH::refitWide(void)
     m_wideTlas = true;
 }
 
+const uint32_t* CudaInstancedBVH::currentFastFlags(void)
+{
+    if (m_fastStale) {
+        // on the trace's stream, ahead of it: asynchronous, nothing is read back
+        m_fastFlags.resizeDiscard(4 * sizeof(U32));
+        const int rc = ntr_instanced_validate(m_result.nodesBytes ? m_tlasNodes.getCudaPtr() : NULL, m_result.nodesBytes, m_poolNodes.getCudaPtr(),
+                                              m_poolNodes.getSize(), (uint32_t*)m_fastFlags.getMutableCudaPtr(), NULL);
+        if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+        m_fastStale = false;
+        m_fastValidations++;
+    }
+    return (const uint32_t*)m_fastFlags.getCudaPtr();
+}
+
+void CudaInstancedBVH::getFastFlags(U32& tlasFlags, U32& poolFlags)
+{
+    if (!m_built) fail("CudaInstancedBVH: No TLAS!");
+    uint32_t t = 0, p = 0;
+    if (ntr_instanced_flags_read(currentFastFlags(), &t, &p, NULL) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    tlasFlags = t;
+    poolFlags = p;
+}
+
 F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
 {
     const S32 numRays = rays.getSize();
@@ -354,6 +386,11 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
                                                  m_wideResult.nodesBytes, m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances,
                                                  m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(),
                                                  m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
+        else if (m_traceFast)
+            rc = ntr_trace_instanced_fast(numRays, anyHit, d_rays, d_results, m_numInstances, d_results, (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                          m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
+                                          m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                          (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentFastFlags(), &seconds, NULL);
         else
             rc = ntr_trace_instanced_seeded(numRays, anyHit, d_rays, d_results, m_numInstances, d_results, (int32_t*)instanceIDs.getMutableCudaPtr(),
                                             m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
@@ -372,6 +409,17 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
                                       m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
                                       m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis,
                                       &seconds, NULL);
+    } else if (m_traceFast) {
+        NtrInstanceVisibility vis;
+        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
+        vis.d_rayMasks = NULL;
+        vis.rayMask = rayMask;
+        vis.pad = 0;
+        rc = ntr_trace_instanced_fast(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(), NULL, -1,
+                                      (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                      m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
+                                      m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                      (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentFastFlags(), &seconds, NULL);
     } else if (!masks && rayMask == 0xFFFFFFFFu) {
         rc = ntr_trace_instanced(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
                                  (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),

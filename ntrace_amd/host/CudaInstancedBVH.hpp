@@ -59,6 +59,13 @@
 //                 setTraceWide and isWide() say so) in place over its records, and returns the sum of both GPU times.  Refuses a BLAS
 //                 index outside the pool; traceBatch still needs at least one instance and a current TLAS.  buildBLASes replaces the
 //                 pool and drops the world; clearWorld drops it and the extra record
+//   setTraceFast   the binary traceBatch takes ntr_trace_instanced_fast -- with a world set, its seeded form -- in place of
+//                 ntr_trace_instanced / _masked / _seeded: the same records in every word, with the FAST slab test wherever a wave's rays
+//                 and the validate flags of the two levels allow it.  Default false.  The flags live in a 16-byte device buffer that
+//                 buildBLASes, addBLAS, refitBLASes, optimizeBLASes, build, refit, setWorld and clearWorld mark stale; the next binary
+//                 traceBatch with the switch on runs ntr_instanced_validate ahead of the trace, on its stream, once.  The wide path is
+//                 untouched: with setTraceWide(true) and isWide() the switch is ignored.  A pool that holds a one-triangle BLAS has
+//                 FASTDIV withheld as a whole (include/ntrace_amd.h) and runs FAST on the top level only
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
 //   refitBLASes -> optimizeBLASes every so many frames -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch /
@@ -106,6 +113,11 @@ public:
     S32  getWorldBLAS(void) const { return m_world; }                            // -1: no world
     void setTraceWide(bool on) { m_traceWide = on; }
     bool getTraceWide(void) const { return m_traceWide; }
+    void setTraceFast(bool on) { m_traceFast = on; }
+    bool getTraceFast(void) const { return m_traceFast; }
+    bool isFastFlagsStale(void) const { return m_fastStale; }                    // the next fast traceBatch validates first
+    S32  getFastValidations(void) const { return m_fastValidations; }            // ntr_instanced_validate calls so far
+    void getFastFlags(U32& tlasFlags, U32& poolFlags);                           // the granted sets; validates if stale; needs isBuilt(); blocks
     bool isWide(void) const { return m_built && m_widePool && m_wideTlas; }      // the wide pool, TLAS and records are current
     bool isWidePoolCurrent(void) const { return m_widePool; }
     const NtrTlasWideResult& getWideResult(void) const { return m_wideResult; }            // of the last widen() (zero before)
@@ -170,6 +182,11 @@ private:
     void          writeWorldRecord(void);                                        // m_instances[m_numInstances], when a world is set
     S32           m_world;                                                       // -1: none
     std::string   m_worldKernel;
+    // the FAST path (setTraceFast): ntr_instanced_validate's four words and whether a node box was rewritten since they were written
+    const uint32_t* currentFastFlags(void);                                      // validates if stale
+    Buffer        m_fastFlags;
+    bool          m_traceFast, m_fastStale;
+    S32           m_fastValidations;
 };
 
 }  // namespace FW

@@ -11,6 +11,11 @@
 //                 widens when the CudaInstancedBVH is not wide -- that is, after each build() / refit() of the frame loop -- and the
 //                 batches are traced with setTraceWide(true), which is put back after each trace.  Nothing else of the frame changes:
 //                 the hit attributes, the AO rays and the reconstruction read the binary geometry, which the wide path keeps
+//   setFast       trace every binary batch of the frame with the FAST slab test where the rays and the validate flags allow it
+//                 (CudaInstancedBVH::setTraceFast); default false.  The batches are traced with setTraceFast(true) -- or
+//                 with whatever the CudaInstancedBVH itself was told, when this is off -- which is put back after each trace.  The
+//                 records are the same in every word, so nothing else of the frame changes.  The wide path is untouched: with
+//                 setWide(true) the switch is ignored
 //   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
 //                 diffuse frames the primary rays are traced and resolved at once
 //   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
@@ -41,6 +46,8 @@ public:
     void setRayMasks(U32 primaryMask = 0xFFFFFFFFu, U32 secondaryMask = 0xFFFFFFFFu);
     void setWide(bool on) { m_wide = on; }
     bool getWide(void) const { return m_wide; }
+    void setFast(bool on) { m_fast = on; }
+    bool getFast(void) const { return m_fast; }
 
     void beginFrame(const CameraView& camera, S32 w, S32 h);
     bool nextBatch(void);
@@ -57,7 +64,7 @@ public:
 
 private:
     void resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals);
-    F32  trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask);   // the CudaInstancedBVH's traceBatch, wide when setWide asked for it
+    F32  trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask);   // the CudaInstancedBVH's traceBatch, wide when setWide asked for it, fast when setFast did
     InstancedRenderer(const InstancedRenderer&);
     InstancedRenderer& operator=(const InstancedRenderer&);
 
@@ -69,7 +76,7 @@ private:
     F32        m_aoRadius;
     S32        m_numSamples;
     U32        m_primaryMask, m_secondaryMask;
-    bool       m_wide;
+    bool       m_wide, m_fast;
     RayGen     m_raygen;
     F32        m_cameraFar;
     RayBuffer  m_primaryRays, m_secondaryRays;

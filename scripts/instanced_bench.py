@@ -39,6 +39,12 @@ frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they we
                time, node fetches per ray (ntr_trace_instanced_stats), the BLAS's SAH cost and the update's own GPU time
   * wide_sweep (not in the default parts) the primary batch of `wide` over k x k x k grids of soup1000 for k = 1, 2, 4, 8, 16 (the last is
                the forest), the camera moved back with the grid: where in instance count the wide path starts to pay
+  * fast       (not in the default parts) the FAST slab test in the two-level trace (ntr_instanced_validate, ntr_trace_instanced_fast;
+               DESIGN.md 6w) over the identity and the forest frame: per batch (primary closest hit, host-made AO any hit)
+               ntr_trace_instanced_masked -- the kernel as it was: the yardstick -- and the fast launch ALTERNATED in this process,
+               each timed by its own stream events (median, min, max); the FAST share (fastWaveSteps / waveSteps, niceEntries /
+               numInstanceEntries) from ntr_trace_instanced_fast_stats; ntr_instanced_validate's own time and the flags it grants.  The
+               records, the instance ids and the eight counters of both paths are asserted equal before anything is timed
 Prints one JSON line per part.
 
     timeout -k 10 600 python scripts/instanced_bench.py --out instanced.json
@@ -250,7 +256,7 @@ def main():
         rows.append(row)
 
     soup = None
-    if any(p in args.parts for p in ("tlas", "forest", "masks", "wide", "wide_sweep", "optimize_forest")):
+    if any(p in args.parts for p in ("tlas", "forest", "masks", "wide", "wide_sweep", "optimize_forest", "fast")):
         tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
         soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
 
@@ -412,6 +418,60 @@ def main():
                 out[key]["algorithmic_bytes"] = int(st.algorithmic_bytes())
                 out[key]["fraction_of_peak"] = out[key]["algorithmic_bytes"] / (out[key]["ms_median"] * 1e-3) / PEAK_BYTES_PER_S
             out["wide_over_binary"] = out["wide"]["ms_median"] / out["binary"]["ms_median"]
+            return out
+        row["primary"] = batch("primary", n, False, d_rays)
+        row["ao"] = batch("ao", na, True, d_ao)
+        assert nt.trace_status() == 0, "traversal stack overflow"
+        return row
+
+    def fast_frame(frame_name, t, cam):
+        """The part `fast` over one frame: masked and fast launches alternated, the FAST share, the validate pass's own time."""
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays, d_res, d_ids, d_fres, d_fids = step(frame_name + " buffers", args.limit, lambda: [up(rays)] + [
+            torch.zeros(max(n, na) * b, dtype=torch.uint8, device="cuda:0") for b in (16, 4, 16, 4)])
+        d_flags = torch.zeros(16, dtype=torch.uint8, device="cuda:0")
+        b, r = t.blas, t.res
+        row = {"part": "fast", "frame": frame_name, "instances": t.n, "primary_rays": n, "ao_rays": na}
+
+        def validate():
+            nt.instanced_validate(t.d_nodes.data_ptr() if r.nodesBytes else 0, r.nodesBytes, b.bufs[0].data_ptr(), b.nb, d_flags.data_ptr(), stream)
+        row["validate_ms"] = step(frame_name + " validate", args.limit, lambda: median_event_ms(validate, args.reps, args.warmup))
+        row["validated_bytes"] = int(r.nodesBytes + b.nb)
+        row["granted_tlas_flags"], row["granted_pool_flags"] = nt.instanced_flags_read(d_flags.data_ptr(), stream)
+
+        def first_primary():
+            t.trace(n, False, d_rays, d_res, d_ids)
+            torch.cuda.synchronize()
+            return d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE).copy()
+        res = step(frame_name + " primary for the ao rays", args.limit, first_primary)
+        d_ao = step(frame_name + " ao upload", args.limit, lambda: up(host_ao_rays(rays, res, na, 7)))
+
+        def batch(name, count, any_hit, d_r):
+            def check():                                      # records and counters equal, before anything is timed
+                st = t.stats(count, any_hit, d_r, d_res, d_ids, None)
+                fst, ff = nt.trace_instanced_fast_stats(*t.args(count, any_hit, d_r, d_fres, d_fids), d_flags.data_ptr(), stream=stream)
+                t.trace_masked(count, any_hit, d_r, d_res, d_ids, None)
+                nt.trace_instanced_fast(*t.args(count, any_hit, d_r, d_fres, d_fids), d_flags.data_ptr(), stream=stream)
+                torch.cuda.synchronize()
+                assert torch.equal(d_res[:16 * count], d_fres[:16 * count]) and torch.equal(d_ids[:4 * count], d_fids[:4 * count]), \
+                    "%s %s: the fast launch's records differ from the masked launch's" % (frame_name, name)
+                assert st.as_dict() == fst.as_dict(), (st.as_dict(), fst.as_dict())
+                return st, ff
+            st, ff = step("%s %s records and counters" % (frame_name, name), args.limit, check)
+
+            def run():
+                m_secs, f_secs = [], []
+                for _ in range(args.warmup + args.reps):      # alternated: masked, fast, masked, fast, ...
+                    m_secs.append(t.trace_masked(count, any_hit, d_r, d_res, d_ids, None))
+                    f_secs.append(nt.trace_instanced_fast(*t.args(count, any_hit, d_r, d_fres, d_fids), d_flags.data_ptr(), stream=stream))
+                return m_secs[args.warmup:], f_secs[args.warmup:]
+            m_secs, f_secs = step("%s %s" % (frame_name, name), args.limit, run)
+            c, f = st.as_dict(), ff.as_dict()
+            out = {"masked": rate(m_secs, count), "fast": rate(f_secs, count), "counters": c, "fast_counters": f,
+                   "fast_wave_share": f["fastWaveSteps"] / max(f["waveSteps"], 1), "nice_entry_share": f["niceEntries"] / max(c["numInstanceEntries"], 1),
+                   "nice_start_share": f["niceStarts"] / count}
+            out["fast_over_masked"] = out["fast"]["ms_median"] / out["masked"]["ms_median"]
             return out
         row["primary"] = batch("primary", n, False, d_rays)
         row["ao"] = batch("ao", na, True, d_ao)
@@ -670,7 +730,7 @@ def main():
         t.res = t.build()
         return out
 
-    if "identity" in args.parts or "masks" in args.parts or "wide" in args.parts:
+    if "identity" in args.parts or "masks" in args.parts or "wide" in args.parts or "fast" in args.parts:
         tri, pos, cam = scenes.atrium()
         atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
         t = step("identity tlas", args.limit, lambda: Tlas(atrium, np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F), stream))
@@ -682,8 +742,10 @@ def main():
             emit(masks_frame("identity", t, cam))
         if "wide" in args.parts:
             emit(wide_frame("identity", t, cam))
+        if "fast" in args.parts:
+            emit(fast_frame("identity", t, cam))
 
-    if "forest" in args.parts or "masks" in args.parts or "wide" in args.parts or "optimize_forest" in args.parts:
+    if "forest" in args.parts or "masks" in args.parts or "wide" in args.parts or "optimize_forest" in args.parts or "fast" in args.parts:
         rng = np.random.default_rng(4096)
         g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
         t = step("forest tlas", args.limit, lambda: Tlas(soup, transforms(rotations(4096, rng), (g - 7.5) * 30.0), stream))
@@ -697,6 +759,8 @@ def main():
         if "wide" in args.parts:
             emit(wide_frame("forest", t, cam))
             emit(step("pool widen loop", args.limit, wide_pool_loop))
+        if "fast" in args.parts:
+            emit(fast_frame("forest", t, cam))
         if "optimize_forest" in args.parts:
             for row in optimize_forest_rows(t, cam):
                 emit(row)
