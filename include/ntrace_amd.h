@@ -1246,6 +1246,61 @@ NTR_API int ntr_trace_instanced_fast_stats(int32_t numRays, int32_t anyHit, cons
                                            const NtrInstanceVisibility* vis /* may be NULL */, const uint32_t* d_flags,
                                            NtrInstancedTraceStats* stats, NtrInstancedFastStats* fastStats, void* stream);
 
+/* FAST slab arithmetic in the two-level trace over 4-wide trees (csrc/instanced_validate_kernels.hip,
+ * csrc/trace_instanced_wide_fast_kernels.hip).  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_wide_fast.py.  The block above, point for point, over the wide buffers: the records, the instance ids, the status
+ * word and the seven counters are ntr_trace_instanced_wide's with `vis` (or, with a seed, ntr_trace_instanced_wide_seeded's) in every
+ * word, for closest hit and any hit, whatever the flags say.  Opt-in entry points; nothing else launches these kernels, and the wide
+ * kernels above stay what they were.
+ * ntr_instanced_wide_validate: ntr_instanced_validate over the wide top-level tree and the wide pool -- the same two launches,
+ *   asynchronous on `stream`, capturable, allocating nothing and reading nothing back.  A pass of its own because the binary buffers'
+ *   flags do not carry over: ntr_pool_wide_refit(rewriteRows = 1) + ntr_tlas_wide_refit update the wide trees without any binary refit,
+ *   after which the binary boxes, and whatever ntr_instanced_validate said of them, are stale.
+ *   layout      the same four words with the same meaning, WITHHELD bits: d_flags[0] the wide top level, d_flags[1] the wide pool,
+ *               d_flags[2] and d_flags[3] zero.  ntr_instanced_flags_read serves both layouts.
+ *   rule        ntr_bvh_validate's for FINITE, FASTDIV, NOTINY and ORDERED over EVERY 128-byte slot in [0, bytes) of both buffers: words
+ *               0..11 and 16..27 are twelve (lo, hi) pairs (rows 0, 1, 2, 4, 5, 6); words 12..15 (links) and 28..31 (count) are never
+ *               looked at.  Padding slots (k >= count: a copy of slot 0's box), empty slots below count, nodes that no link reaches and
+ *               slack behind the last BLAS count: all of this can only withhold.  wideTlasNodesBytes == 0, or d_wideTlasNodes == NULL
+ *               (one instance), withholds nothing for the top level.
+ *   when        after every call that rewrites a box of either wide buffer and before the next wide fast trace (on one stream, or in
+ *               one graph, in that order): ntr_pool_widen / ntr_pool_widen_batch, ntr_tlas_widen, ntr_pool_wide_refit,
+ *               ntr_tlas_wide_refit, any copy into the buffers.  Flags that grant what the buffers do not hold are a caller error with
+ *               undefined records (nothing outside the buffers is read all the same); flags that wrongly WITHHOLD only cost speed.
+ *   errors      NTR_ERR_INVALID before any device work: a null d_flags or d_widePoolNodes; sizes that are not multiples of 128,
+ *               wideTlasNodesBytes neither 0 nor within the wide limit, widePoolNodesBytes outside the wide pool limits; d_flags,
+ *               d_wideTlasNodes or d_widePoolNodes not 16-byte aligned.  A capturing stream is accepted.
+ * ntr_trace_instanced_wide_fast: ntr_trace_instanced_wide_seeded's argument list with d_flags before `seconds`; vis may be NULL, and
+ *   d_seedResults may be NULL, which means unseeded (seedInstance is then ignored).  The loop is the masked (seeded) wide one with the
+ *   per-lane `nice` of ntr_trace_instanced_fast: at the start from the world ray against d_flags[0], on entering an instance, after the
+ *   transform, from the object ray against d_flags[1], at the exit marker from the reloaded world ray against d_flags[0]; one ballot per
+ *   iteration, FAST iff no live lane has nice == false, and the wave then takes the FAST form of the wide-node step and of the triangle
+ *   step; the two flag words are read once per wave by the launch.  No prologue, no octant vote, no use of ORDERED.
+ * ntr_trace_instanced_wide_fast_stats: the same records through the instrumented kernels, plus ntr_trace_instanced_wide_stats's
+ *   counters and NtrInstancedFastStats with 6w's definitions; a step is one iteration of the device's wide loop (a triangle step also
+ *   takes the terminator behind its triangle).  Blocks; refused on a capturing stream.
+ * Errors: NTR_ERR_INVALID before any device work for everything ntr_trace_instanced_wide_seeded refuses (but a null d_seedResults), a
+ *   null d_flags and a d_flags that is not 16-byte aligned, null stats; numRays == 0 returns NTR_OK with the stats zeroed.  Without a
+ *   device, after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+NTR_API int ntr_instanced_wide_validate(const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, const void* d_widePoolNodes,
+                                        int64_t widePoolNodesBytes, uint32_t* d_flags /* 4 words, 16-byte aligned */, void* stream);
+NTR_API int ntr_trace_instanced_wide_fast(int32_t numRays, int32_t anyHit, const NtrRay* d_rays,
+                                          const NtrRayResult* d_seedResults /* NULL: unseeded */, int32_t seedInstance,
+                                          NtrRayResult* d_results /* may equal d_seedResults */, int32_t* d_instanceIDs,
+                                          const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink, const void* d_wideRecords,
+                                          int32_t numInstances, const void* d_widePoolNodes, int64_t widePoolNodesBytes,
+                                          const void* d_poolTriWoop, int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                          const NtrInstanceVisibility* vis /* NULL: no masks */, const uint32_t* d_flags,
+                                          float* seconds /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_trace_instanced_wide_fast_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
+                                                int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                                const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, int32_t rootLink,
+                                                const void* d_wideRecords, int32_t numInstances, const void* d_widePoolNodes,
+                                                int64_t widePoolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
+                                                const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis /* may be NULL */,
+                                                const uint32_t* d_flags, NtrInstancedTraceStats* stats, NtrInstancedFastStats* fastStats,
+                                                void* stream);
+
 /* In-place refit of 4-wide trees: the update path of an animated instanced frame for the wide two-level trace
  * (csrc/wide_refit_batch_kernels.hip, csrc/tlas_wide_refit_kernels.hip, csrc/wide_climb.h).  ntr_pool_widen and
  * ntr_tlas_widen block, read back and may change a wide tree's topology from frame to frame; these two calls keep the wide topology

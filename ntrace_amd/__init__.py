@@ -34,6 +34,7 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     bvh_sah_cost_batch, OPT_ERR_LINK, OPT_ERR_ROW, OPT_ERR_NO_TREE,
                     trace_instanced_wide, trace_instanced_wide_stats,
                     instanced_validate, instanced_flags_read, trace_instanced_fast, trace_instanced_fast_stats, InstancedFastStats,
+                    instanced_wide_validate, trace_instanced_wide_fast, trace_instanced_wide_fast_stats,
                     trace_instanced_seeded, trace_instanced_seeded_stats, trace_instanced_wide_seeded, trace_instanced_wide_seeded_stats,
                     WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
                     tlas_wide_refit_scratch_bytes)
@@ -66,6 +67,7 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "bvh_sah_cost_batch", "OPT_ERR_LINK", "OPT_ERR_ROW", "OPT_ERR_NO_TREE",
            "trace_instanced_wide", "trace_instanced_wide_stats",
            "instanced_validate", "instanced_flags_read", "trace_instanced_fast", "trace_instanced_fast_stats", "InstancedFastStats",
+           "instanced_wide_validate", "trace_instanced_wide_fast", "trace_instanced_wide_fast_stats",
            "trace_instanced_seeded", "trace_instanced_seeded_stats", "trace_instanced_wide_seeded", "trace_instanced_wide_seeded_stats",
            "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",
            "tlas_wide_refit_scratch_bytes"]

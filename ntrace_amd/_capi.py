@@ -524,6 +524,12 @@ SYMBOLS = [
     ("ntr_trace_instanced_fast_stats", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                                  C.POINTER(InstanceVisibility), _vp, C.POINTER(InstancedTraceStats),
                                                  C.POINTER(InstancedFastStats), _vp]),
+    ("ntr_instanced_wide_validate", C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    ("ntr_trace_instanced_wide_fast", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                C.POINTER(InstanceVisibility), _vp, C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_wide_fast_stats", C.c_int, [_i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64,
+                                                      _vp, C.POINTER(InstanceVisibility), _vp, C.POINTER(InstancedWideTraceStats),
+                                                      C.POINTER(InstancedFastStats), _vp]),
     ("ntr_pool_wide_refit", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.POINTER(WideRefitResult), _vp]),
     ("ntr_pool_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_wide_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
@@ -1475,6 +1481,47 @@ def trace_instanced_wide_seeded_stats(num_rays, any_hit, d_rays, d_seed_results,
                   d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
                   wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
     return st
+
+
+def instanced_wide_validate(d_wide_tlas_nodes, wide_tlas_nodes_bytes, d_wide_pool_nodes, wide_pool_nodes_bytes, d_flags, stream=0):
+    """ntr_instanced_wide_validate: the withheld validate bits of the wide top-level tree and of the wide pool into d_flags[0] and
+    d_flags[1] (four words, 16-byte aligned; the rule is tests/np_instanced_wide_fast.py, validate).  Asynchronous on `stream` and
+    capturable; to be run again after every call that rewrites a wide box, before the next trace_instanced_wide_fast.
+    instanced_flags_read reads these words too."""
+    _check(lib().ntr_instanced_wide_validate(_vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), _vp(d_wide_pool_nodes),
+                                             int(wide_pool_nodes_bytes), _vp(d_flags), _vp(stream)))
+
+
+def trace_instanced_wide_fast(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
+                              d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                              d_pool_tri_index, d_flags, vis=None, d_seed_results=0, seed_instance=-1, stream=0, timed=True):
+    """ntr_trace_instanced_wide_fast: trace_instanced_wide's records with `vis` -- trace_instanced_wide_seeded's when d_seed_results is
+    given -- with the FAST slab test wherever the wave's rays and d_flags (instanced_wide_validate's words, read by the launch) allow it;
+    the rule is tests/np_instanced_wide_fast.py.  timed=True returns the GPU seconds; timed=False is asynchronous on `stream`
+    (capturable) and returns None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_instanced_wide_fast(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
+                                               _vp(d_results), _vp(d_instance_ids), _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes),
+                                               int(root_link), _vp(d_wide_records), int(num_instances), _vp(d_wide_pool_nodes),
+                                               int(wide_pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
+                                               C.byref(vis) if vis is not None else None, _vp(d_flags), C.byref(sec) if timed else None,
+                                               _vp(stream)))
+    return float(sec.value) if timed else None
+
+
+def trace_instanced_wide_fast_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
+                                    d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                                    d_pool_tri_index, d_flags, vis=None, d_seed_results=0, seed_instance=-1, stream=0):
+    """ntr_trace_instanced_wide_fast_stats: trace_instanced_wide_fast's records through the instrumented kernels ->
+    (InstancedWideTraceStats, InstancedFastStats).  Blocks; refused on a capturing stream."""
+    st, fs = InstancedWideTraceStats(), InstancedFastStats()
+    _check(lib().ntr_trace_instanced_wide_fast_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
+                                                     _vp(d_results), _vp(d_instance_ids), _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes),
+                                                     int(root_link), _vp(d_wide_records), int(num_instances), _vp(d_wide_pool_nodes),
+                                                     int(wide_pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
+                                                     _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None, _vp(d_flags),
+                                                     C.byref(st), C.byref(fs), _vp(stream)))
+    return st, fs
 
 
 def _wide_refit_entries(entries):

@@ -10,11 +10,16 @@
 //   d_flags[2], d_flags[3]   zero
 // The rule is bvh_validate_kernel's (bvh_utils.hip) for those four flags: the twelve box floats of every 64-byte node, never the child
 // words; every node slot in [0, bytes) counts, a pool's slack and gaps too.
+// ntr_instanced_wide_validate (the rule is tests/np_instanced_wide_fast.py, validate) is the same pass over the 4-wide
+// buffers of the same scene, for ntr_trace_instanced_wide_fast: the all-wide update path runs no binary refit, so the binary buffers'
+// flags say nothing about the wide boxes.  The same two kernels serve it: a 128-byte wide node (wide_bvh.h) is rows 0..2 and 4..6 of
+// (lo, hi) pairs in Compact's box words, row 3 the links and row 7 the count -- every fourth float4 is skipped in either layout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ntr_internal.h"
 #include "instanced_bvh.h"
+#include "instanced_wide_bvh.h"
 
 namespace ntr {
 namespace {
@@ -27,7 +32,9 @@ __global__ __launch_bounds__(256) void instanced_validate_kernel(const float4* _
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, total = tlas4 + pool4;
     unsigned int held[2] = {0u, 0u};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        if ((i & 3) == 3) continue;   // the child words (both buffers are whole nodes, so the seam keeps i's phase)
+        // the child words of a 64-byte node; of a 128-byte wide node row 3, the links, and row 7, the count (both buffers are whole
+        // nodes, so the seam keeps i's phase)
+        if ((i & 3) == 3) continue;
         const bool top = i < tlas4;
         const float4 v = top ? tlas[i] : pool[i - tlas4];
         const float c[4] = {v.x, v.y, v.z, v.w};
@@ -77,6 +84,27 @@ extern "C" int ntr_instanced_validate(const void* d_tlasNodes, int64_t tlasNodes
     hipLaunchKernelGGL(instanced_flags_clear_kernel, dim3(1), dim3(64), 0, s, (unsigned int*)d_flags);
     hipLaunchKernelGGL(instanced_validate_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float4*)d_tlasNodes, tlas4,
                        (const float4*)d_poolNodes, pool4, (unsigned int*)d_flags);
+    NTR_HIP(hipGetLastError());
+    return NTR_OK;
+}
+
+extern "C" int ntr_instanced_wide_validate(const void* d_wideTlasNodes, int64_t wideTlasNodesBytes, const void* d_widePoolNodes,
+                                           int64_t widePoolNodesBytes, uint32_t* d_flags, void* stream)
+{
+    const char* fn = "ntr_instanced_wide_validate";
+    if (!d_flags || !d_widePoolNodes) return set_error(NTR_ERR_INVALID, "%s: null flags or null pool", fn);
+    if (wideTlasNodesBytes != 0)
+        if (const int rc = check_wide_bytes(fn, wideTlasNodesBytes)) return rc;
+    if (const int rc = check_wide_pool_bytes(fn, "widePoolNodesBytes", widePoolNodesBytes)) return rc;
+    if (((((uintptr_t)d_flags) | ((uintptr_t)d_wideTlasNodes) | ((uintptr_t)d_widePoolNodes)) & 15u) != 0)
+        return set_error(NTR_ERR_INVALID, "%s: the flags and the node buffers must be 16-byte aligned", fn);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t tlas4 = d_wideTlasNodes ? wideTlasNodesBytes / 16 : 0, pool4 = widePoolNodesBytes / 16;
+    int64_t blocks = (tlas4 + pool4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(instanced_flags_clear_kernel, dim3(1), dim3(64), 0, s, (unsigned int*)d_flags);
+    hipLaunchKernelGGL(instanced_validate_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const float4*)d_wideTlasNodes, tlas4,
+                       (const float4*)d_widePoolNodes, pool4, (unsigned int*)d_flags);
     NTR_HIP(hipGetLastError());
     return NTR_OK;
 }

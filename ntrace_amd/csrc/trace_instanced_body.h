@@ -9,7 +9,7 @@
 //   NTR_TI_SEEDED   1: the ray starts from a seed record (InstancedSeed sd; the rule is tests/np_instanced_seeded.py): tmax from a seed that
 //                   is a hit, no traversal for an any-hit ray whose seed is a hit, and a lane that accepts nothing stores the seed's words
 //   NTR_TI_FAST     1: FAST slab arithmetic from device-resident flags (InstancedFast f and level_nice of
-//                   trace_instanced_fast_kernels.hip; the rule is tests/np_instanced_fast.py): a per-lane `nice` says that
+//                   trace_instanced_nice.h; the rule is tests/np_instanced_fast.py): a per-lane `nice` says that
 //                   the lane's current ray may take FAST on its current level, and the wave votes per iteration on the step's form
 // An include and not a function template because the unmasked variant must stay the kernel it was, instruction for instruction
 // (scripts/kernel_isa_diff.sh): with the loop in a __forceinline__ function that the kernels call, hipcc orders its passes differently and

@@ -5,7 +5,7 @@
 // world ray on the top level and a different object ray inside every instance, and the flags must be readable by a captured frame:
 //   flags   two words on the device, the withheld bits of the top-level tree and of the pool (instanced_validate_kernels.hip), read
 //           once per wave by the launch -- a replay sees what the validate before it in the graph wrote
-//   nice    per lane: the CURRENT ray may take FAST on its CURRENT level (level_nice below: ray_is_nice against the level's granted
+//   nice    per lane: the CURRENT ray may take FAST on its CURRENT level (level_nice, trace_instanced_nice.h: ray_is_nice against the level's granted
 //           flags, and the level's FASTDIV).  Set at the start from the world ray, on entering an instance from the object ray, on
 //           leaving from the reloaded world ray; wherever it becomes true the three reciprocals are the ray's
 //   vote    one ballot per iteration: no live lane with nice == false -> inner_advance<true, 8> / unified_advance<true, 8>, else the
@@ -24,21 +24,10 @@
 #include "sched_state.h"
 #include "trace_lane.h"
 #include "trace_instanced_kernels.h"
+#include "trace_instanced_nice.h"
 
 namespace ntr {
 namespace {
-
-struct InstancedFast {
-    const uint32_t* flags;   // ntr_instanced_validate's four words: [0] withheld on the top level, [1] withheld in the pool
-};
-
-// `nice` of ray r on a level whose withheld bits are `held`; a nice ray gets its reciprocals (load_ray's, trace_lane.h)
-__device__ __forceinline__ bool level_nice(RayRegs& r, unsigned int held)
-{
-    const bool nice = !(held & NTR_BVH_FASTDIV) && ray_is_nice(r, ~held);
-    if (nice) { r.rx = exact_rcp(r.dx); r.ry = exact_rcp(r.dy); r.rz = exact_rcp(r.dz); }
-    return nice;
-}
 
 #define NTR_TI_MASKED 1
 #define NTR_TI_FAST 1

@@ -1,17 +1,21 @@
 // trace_instanced_wide_body.h -- the two-level trace over 4-wide trees, its kernel stated once: trace_instanced_wide_kernels.hip (the
-// three unseeded kernels) and trace_instanced_wide_seeded_kernels.hip (the seeded ones) include this text once each, after
-// trace_instanced_wide_kernels.h, with
+// three unseeded kernels) and trace_instanced_wide_seeded_kernels.hip (the seeded ones) include this text once each, and
+// trace_instanced_wide_fast_kernels.hip (the FAST ones, unseeded and seeded) twice, after trace_instanced_wide_kernels.h, with
 //   NTR_TIW_TEMPLATE   the template header: <bool MASKED, bool STATS>, or <bool STATS> for the seeded kernels (MASKED is then true)
 //   NTR_TIW_KERNEL     the kernel's name
 //   NTR_TIW_PARAMS     its parameters: InstancedWideParams p, and for the seeded kernels InstancedWideSeed sd
 //   NTR_TIW_SEEDED     1: the ray starts from a seed record (the rule is tests/np_instanced_seeded.py): tmax from a seed that is a hit,
 //                      no traversal for an any-hit ray whose seed is a hit, and a lane that accepts nothing stores the seed's words
+//   NTR_TIW_FAST       1: FAST slab arithmetic from device-resident flags (InstancedFast fl and level_nice of trace_instanced_nice.h;
+//                      DESIGN.md 6x; the rule is tests/np_instanced_wide_fast.py): a per-lane `nice` says that the lane's current ray may
+//                      take FAST on its current level, and the wave votes per iteration on the step's form.  The template header is
+//                      <bool STATS>, seeded or not: the fast kernels are the masked loop
 // An include and not a further template parameter for trace_instanced_body.h's reason: the unseeded kernels keep their names and stay,
 // instruction for instruction, what they were (scripts/kernel_isa_diff.sh).  No include guard.
 NTR_TIW_TEMPLATE
 __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
 {
-#if NTR_TIW_SEEDED
+#if NTR_TIW_SEEDED || NTR_TIW_FAST
     constexpr bool MASKED = true;   // the seeded kernels are the masked loop
 #endif
     __shared__ int s_stack[LDS_DEPTH][64];   // [entry][lane]
@@ -66,10 +70,31 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
     // a degenerate ray (Ray::degenerate, Util.hpp:65) is a miss without traversal
     int node = (valid && r.tmin < r.tmax) ? p.rootLink : kSentinel;
 #endif
+#if NTR_TIW_FAST
+    // the withheld bits of the two levels (ntr_instanced_wide_validate), read by the launch: a replay sees what the last validate wrote
+    const unsigned int heldTlas = fl.flags[0], heldPool = fl.flags[1];
+    // `nice`: of the lane's current ray on its current level; level_nice sets r.rx, r.ry, r.rz when it says yes.  The instrumented
+    // variants hold it and niceStart as words pinned to vector registers (NiceWord): as lane masks in scalar pairs they are an SGPR
+    // spill in the seeded one
+    typedef NiceWord<STATS> NicePin;
+    typename NicePin::type nice = level_nice(r, heldTlas);
+    NicePin::pin(nice);
+    typename NicePin::type niceStart = node != kSentinel && nice;
+    NicePin::pin(niceStart);
+    // (STATS only.  The wave's two counters are kept by lane 0, in vector registers, as in trace_instanced_body.h)
+    const unsigned int laneZero = lane == 0 ? 1u : 0u;
+    unsigned int waveSteps = 0u, fastSteps = 0u, niceEntries = 0u;
+#endif
 
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a, e = a, f = a, g = a;
     for (;;) {
         if (__ballot(node != kSentinel) == 0ull) break;
+#if NTR_TIW_FAST
+        // the wave's vote, one ballot per iteration: FAST iff no live lane holds a ray that is not nice -- a scalar branch around the
+        // two instantiations of the step
+        const bool fastStep = __ballot(node != kSentinel && !nice) == 0ull;
+        if (STATS) { waveSteps += laneZero; fastSteps += fastStep ? laneZero : 0u; }
+#endif
         const bool top = inst < 0;
         const bool inner = (unsigned)node < (unsigned)kSentinel;
         const bool neg = node < 0;
@@ -103,11 +128,18 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
                 r.ox = o.x; r.oy = o.y; r.oz = o.z;
                 r.dx = dd.x; r.dy = dd.y; r.dz = dd.z;
                 inst = -1;
+#if NTR_TIW_FAST
+                nice = level_nice(r, heldTlas);
+                NicePin::pin(nice);
+#endif
             }
             node = stack_pop(st, spill);   // (any other such word is no link: it is dropped)
         } else if (inner) {
             // a wide node of either level (a lane whose fetch lay beyond an extent read zeros: four links of 0, no candidate, a pop)
             if (STATS) { if (top) ls.topInner++; else ls.inner++; }
+#if NTR_TIW_FAST
+            if (fastStep) wide_advance<true>(a, b, c, d, e, f, g, r, node, st, spill, p.status); else
+#endif
             wide_advance<false>(a, b, c, d, e, f, g, r, node, st, spill, p.status);
         } else if (top) {
             // entering instance ~node: its record is worldToObject (a, b, c) and the wide offset, row offset and extent (d)
@@ -132,6 +164,11 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
                 inst = idx;
                 node = 0;
                 if (STATS) ls.entries++;
+#if NTR_TIW_FAST
+                nice = level_nice(r, heldPool);
+                NicePin::pin(nice);
+                if (STATS) niceEntries += nice ? 1u : 0u;
+#endif
             }
         } else {
             int row = -1;   // the BLAS's own row of a hit this step accepts
@@ -140,9 +177,15 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
                 // that came with a triangle -- unless an any-hit ray ended on that triangle
                 const bool term = __float_as_uint(a.x) == kLeafTerm;
                 if (!term) ls.tris++;
+#if NTR_TIW_FAST
+                if (fastStep) unified_advance<true, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status); else
+#endif
                 unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
                 if (term || (!(anyHit && row >= 0) && __float_as_uint(d.x) == kLeafTerm)) ls.leaves++;
             } else {
+#if NTR_TIW_FAST
+                if (fastStep) unified_advance<true, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status); else
+#endif
                 unified_advance<false, 8>(a, b, c, d, r, node, st, spill, anyHit, row, hitU, hitV, p.status);
             }
             if (row >= 0) {
@@ -179,6 +222,14 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
         atomicAdd(&p.stats[6], (unsigned long long)(seedKept || (hitAddr >= 0 && p.triIndex[hitAddr] != -1)));
 #else
         atomicAdd(&p.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
+#endif
+#if NTR_TIW_FAST
+        if (lane == 0) {   // (lane 0 of a launched wave is a ray)
+            atomicAdd(&p.stats[8], (unsigned long long)waveSteps);
+            atomicAdd(&p.stats[9], (unsigned long long)fastSteps);
+        }
+        atomicAdd(&p.stats[10], (unsigned long long)niceStart);
+        atomicAdd(&p.stats[11], (unsigned long long)niceEntries);
 #endif
     }
 }

@@ -15,7 +15,8 @@
 // sit under exec masks with a single wait, a kind that no lane holds is skipped by a scalar branch, and every fetch goes through a
 // wave-uniform range-checked descriptor: whatever a link, an offset or a record holds, a lane reads zeros and never faults.  Inside an
 // instance a wide node is fetched only below the record's extent, so an instance of extent 0 reads nothing.
-// Arithmetic is the GENERIC path only, as in the binary two-level trace.  The loop is stated once (trace_instanced_wide_body.h; its
+// Arithmetic is the GENERIC path only, as in the binary two-level trace (an opt-in sibling votes per wave and iteration between GENERIC
+// and FAST: trace_instanced_wide_fast_kernels.hip, NTR_TIW_FAST).  The loop is stated once (trace_instanced_wide_body.h; its
 // parameters and fetch are in trace_instanced_wide_kernels.h) and instantiated three ways here:
 //   trace_instanced_wide<false, false>   unmasked: vis == NULL, or a vis that can refuse nothing
 //   trace_instanced_wide<true, false>    visibility masks
@@ -41,11 +42,13 @@ namespace {
 #define NTR_TIW_KERNEL trace_instanced_wide
 #define NTR_TIW_PARAMS InstancedWideParams p
 #define NTR_TIW_SEEDED 0
+#define NTR_TIW_FAST 0
 #include "trace_instanced_wide_body.h"
 #undef NTR_TIW_TEMPLATE
 #undef NTR_TIW_KERNEL
 #undef NTR_TIW_PARAMS
 #undef NTR_TIW_SEEDED
+#undef NTR_TIW_FAST
 
 // The entry points' one body.  vis == NULL, or a vis that can refuse nothing (no arrays and rayMask all ones), launches the unmasked
 // kernel; stats != NULL launches the instrumented one and reads the counters back.  seeded: the seeded kernels of

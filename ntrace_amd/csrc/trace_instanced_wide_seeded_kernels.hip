@@ -18,11 +18,13 @@ namespace {
 #define NTR_TIW_KERNEL trace_instanced_wide_seeded
 #define NTR_TIW_PARAMS InstancedWideParams p, InstancedWideSeed sd
 #define NTR_TIW_SEEDED 1
+#define NTR_TIW_FAST 0
 #include "trace_instanced_wide_body.h"
 #undef NTR_TIW_TEMPLATE
 #undef NTR_TIW_KERNEL
 #undef NTR_TIW_PARAMS
 #undef NTR_TIW_SEEDED
+#undef NTR_TIW_FAST
 
 }  // namespace
 

@@ -9,7 +9,10 @@
 //   row 7      words 28..31   word 28 the child count (2..4), words 29..31 zero
 // A link < 0 is a leaf, ~link its first Woop row, copied verbatim from the binary tree; > 0 is 128 * index of a wide node; 0 is an empty
 // slot.  Slot k >= count has link 0 and a copy of slot 0's box: every box word of the wide tree is a box word of the binary tree, so
-// ntr_bvh_validate's flags for the binary tree hold for the wide one.  The stack sentinel stays kSentinel.
+// ntr_bvh_validate's flags for the binary tree hold for the wide one -- while the binary tree is current.  A wide tree that is refitted
+// on its own (ntr_pool_wide_refit with rewriteRows, ntr_tlas_wide_refit: no binary refit runs) leaves the binary boxes and their flags
+// behind; the two-level trace then validates the wide buffers themselves (ntr_instanced_wide_validate).  The stack
+// sentinel stays kSentinel.
 #pragma once
 #include "compact_bvh.h"
 

@@ -1,7 +1,8 @@
 // CudaInstancedBVH.cpp -- a pool of BLASes, instances and their top-level tree over ntr_tlas_build / ntr_tlas_refit / ntr_trace_instanced
 // and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen_batch (ntr_pool_widen for one BLAS) / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
 // ntr_trace_instanced_wide, and a static world over ntr_trace_bvh / ntr_trace_instanced_seeded / ntr_trace_instanced_wide_seeded (see the
-// header), and the FAST path over ntr_instanced_validate / ntr_trace_instanced_fast.
+// header), and the FAST path over ntr_instanced_validate / ntr_trace_instanced_fast, and over the wide trees
+// ntr_instanced_wide_validate / ntr_trace_instanced_wide_fast.
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
@@ -10,7 +11,8 @@ namespace FW {
 
 CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false),
                                            m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false), m_world(-1),
-                                           m_traceFast(false), m_fastStale(true), m_fastValidations(0)
+                                           m_traceFast(false), m_fastStale(true), m_fastValidations(0), m_traceWideFast(false),
+                                           m_wideFastStale(true), m_wideFastValidations(0)
 {
     std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
     std::memset(&m_wideResult, 0, sizeof(m_wideResult));
@@ -47,7 +49,7 @@ S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
     m_meshes.push_back(none);
     m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     return (S32)m_ranges.size() - 1;
 }
 
@@ -64,7 +66,7 @@ void CudaInstancedBVH::buildBLASes(S32 numMeshes, const NtrPlocBatchMesh* meshes
     clearWorld();                                    // the pool is replaced: whatever BLAS the world named is gone
     m_built = m_topology = m_wideTopology = m_blasTrisCurrent = false;
     m_widePool = m_wideTlas = false;
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     m_poolNodes.resizeDiscard(capN);
     m_poolTriWoop.resizeDiscard(capW);
     m_poolTriIndex.resizeDiscard(capI);
@@ -120,7 +122,7 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
     }
     m_built = false;
     m_widePool = m_wideTlas = false;             // this method refits the binary pool only: widen() again, or call refitBLASesWide
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     const int rc = ntr_bvh_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
                                        m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
                                        (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(), numVerts, (const float*)vtxPos.getCudaPtr(),
@@ -146,7 +148,7 @@ void CudaInstancedBVH::optimizeBLASes(const S32* blas, S32 num, S32 passes)
     std::vector<NtrBlasRange> sel;
     selectRanges(blas, num, sel, "optimise");
     m_widePool = m_wideTlas = false;             // the binary pool's topology changes: widen() again (m_built stays, see the header)
-    m_fastStale = true;                          // node boxes are rewritten
+    m_fastStale = m_wideFastStale = true;                          // node boxes are rewritten
     const int rc = ntr_bvh_optimize_batch((int32_t)sel.size(), sel.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(), passes, NULL,
                                           &m_optimizeResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
@@ -201,7 +203,7 @@ void CudaInstancedBVH::setWorld(S32 blas, const char* kernelName)
     if (!kernelName || !kernelName[0]) fail("CudaInstancedBVH::setWorld: no kernel name");
     m_world = blas;
     m_worldKernel = kernelName;
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     writeWorldRecord();                              // the TLAS never sees the world: m_built stays
 }
 
@@ -209,7 +211,7 @@ void CudaInstancedBVH::clearWorld(void)
 {
     if (m_world < 0) return;
     m_world = -1;
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     m_instances.resize((S64)m_numInstances * sizeof(NtrInstance));
 }
 
@@ -228,7 +230,7 @@ void CudaInstancedBVH::build(S32 radius)
     if (ntr_tlas_capacity(m_numInstances, &capN, &capR) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_built = m_topology = m_wideTopology = false;
     m_wideTlas = false;
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     m_tlasNodes.resizeDiscard(capN);
     m_records.resizeDiscard(capR);
     const int rc = ntr_tlas_build(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
@@ -244,7 +246,7 @@ void CudaInstancedBVH::refit(void)
     if (!m_topology || m_numInstances < 1)
         fail("CudaInstancedBVH: no TLAS to refit: call build() first, and again after the instance count or the BLASes have changed");
     m_wideTlas = false;
-    m_fastStale = true;
+    m_fastStale = m_wideFastStale = true;
     const int rc = ntr_tlas_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
                                   m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL,
                                   m_result.nodesBytes, m_result.rootLink, m_records.getMutableCudaPtr(), m_records.getSize(), NULL,
@@ -264,6 +266,7 @@ void CudaInstancedBVH::widen(void)
 {
     if (!m_built) fail("CudaInstancedBVH: no TLAS to widen: call build() or refit() first");
     const int32_t numBlas = (int32_t)m_ranges.size();
+    m_wideFastStale = true;                      // wide boxes are written
     if (!m_widePool) {
         int64_t cap = 0;
         if (ntr_pool_widen_capacity(numBlas, m_ranges.data(), &cap) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
@@ -315,6 +318,7 @@ void CudaInstancedBVH::refitBLASesWide(Buffer& triVtxIndex, S32 numVerts, Buffer
                                        0 /* the binary refit has written the rows */, NULL, &m_wideBlasRefitResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_widePool = true;                           // (refitBLASes dropped it: the wide boxes are the new ones again)
+    m_wideFastStale = true;
 }
 
 void CudaInstancedBVH::refitWide(void)
@@ -330,6 +334,7 @@ void CudaInstancedBVH::refitWide(void)
                                        &m_wideTlasRefitResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_wideTlas = true;
+    m_wideFastStale = true;
 }
 
 const uint32_t* CudaInstancedBVH::currentFastFlags(void)
@@ -351,6 +356,30 @@ void CudaInstancedBVH::getFastFlags(U32& tlasFlags, U32& poolFlags)
     if (!m_built) fail("CudaInstancedBVH: No TLAS!");
     uint32_t t = 0, p = 0;
     if (ntr_instanced_flags_read(currentFastFlags(), &t, &p, NULL) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    tlasFlags = t;
+    poolFlags = p;
+}
+
+const uint32_t* CudaInstancedBVH::currentWideFastFlags(void)
+{
+    if (m_wideFastStale) {
+        // over the wide buffers themselves: after the all-wide update path the binary boxes say nothing about them
+        m_wideFastFlags.resizeDiscard(4 * sizeof(U32));
+        const int rc = ntr_instanced_wide_validate(m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes,
+                                                   m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
+                                                   (uint32_t*)m_wideFastFlags.getMutableCudaPtr(), NULL);
+        if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+        m_wideFastStale = false;
+        m_wideFastValidations++;
+    }
+    return (const uint32_t*)m_wideFastFlags.getCudaPtr();
+}
+
+void CudaInstancedBVH::getWideFastFlags(U32& tlasFlags, U32& poolFlags)
+{
+    if (!isWide()) fail("CudaInstancedBVH: the wide trees are not current: call widen() first");
+    uint32_t t = 0, p = 0;
+    if (ntr_instanced_flags_read(currentWideFastFlags(), &t, &p, NULL) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     tlasFlags = t;
     poolFlags = p;
 }
@@ -380,7 +409,14 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
         vis.d_rayMasks = NULL;
         vis.rayMask = rayMask;
         vis.pad = 0;
-        if (m_traceWide && isWide())
+        if (m_traceWide && isWide() && m_traceWideFast)
+            rc = ntr_trace_instanced_wide_fast(numRays, anyHit, d_rays, d_results, m_numInstances, d_results,
+                                               (int32_t*)instanceIDs.getMutableCudaPtr(), m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL,
+                                               m_wideResult.nodesBytes, m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances,
+                                               m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(),
+                                               m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentWideFastFlags(),
+                                               &seconds, NULL);
+        else if (m_traceWide && isWide())
             rc = ntr_trace_instanced_wide_seeded(numRays, anyHit, d_rays, d_results, m_numInstances, d_results,
                                                  (int32_t*)instanceIDs.getMutableCudaPtr(), m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL,
                                                  m_wideResult.nodesBytes, m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances,
@@ -403,12 +439,20 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
         vis.d_rayMasks = NULL;
         vis.rayMask = rayMask;
         vis.pad = 0;
-        rc = ntr_trace_instanced_wide(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
-                                      (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                      m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes, m_result.rootLink,
-                                      m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
-                                      m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis,
-                                      &seconds, NULL);
+        if (m_traceWideFast)
+            rc = ntr_trace_instanced_wide_fast(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(), NULL, -1,
+                                               (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                               m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes,
+                                               m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(),
+                                               m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
+                                               (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentWideFastFlags(), &seconds, NULL);
+        else
+            rc = ntr_trace_instanced_wide(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
+                                          (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
+                                          m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes, m_result.rootLink,
+                                          m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
+                                          m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis,
+                                          &seconds, NULL);
     } else if (m_traceFast) {
         NtrInstanceVisibility vis;
         vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;

@@ -66,6 +66,13 @@
 //                 traceBatch with the switch on runs ntr_instanced_validate ahead of the trace, on its stream, once.  The wide path is
 //                 untouched: with setTraceWide(true) and isWide() the switch is ignored.  A pool that holds a one-triangle BLAS has
 //                 FASTDIV withheld as a whole (include/ntrace_amd.h) and runs FAST on the top level only
+//   setTraceWideFast   with setTraceWide(true) and isWide(), traceBatch takes ntr_trace_instanced_wide_fast -- with a world
+//                 set, its seeded form over ntr_trace_bvh's records in place -- in place of ntr_trace_instanced_wide / _wide_seeded: the
+//                 same records in every word.  Default false; setTraceFast keeps being ignored on the wide path.  A second 16-byte
+//                 device buffer holds the WIDE buffers' flags (ntr_instanced_wide_validate: after refitBLASesWide / refitWide's update
+//                 the wide boxes are what is traced, whatever the binary flags say); widen, refitBLASesWide, refitWide, setWorld,
+//                 clearWorld and everything that drops the wide pool or the wide TLAS mark it stale, and the next wide fast traceBatch
+//                 validates ahead of the trace, on its stream, once
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
 //   refitBLASes -> optimizeBLASes every so many frames -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch /
@@ -118,6 +125,11 @@ public:
     bool isFastFlagsStale(void) const { return m_fastStale; }                    // the next fast traceBatch validates first
     S32  getFastValidations(void) const { return m_fastValidations; }            // ntr_instanced_validate calls so far
     void getFastFlags(U32& tlasFlags, U32& poolFlags);                           // the granted sets; validates if stale; needs isBuilt(); blocks
+    void setTraceWideFast(bool on) { m_traceWideFast = on; }
+    bool getTraceWideFast(void) const { return m_traceWideFast; }
+    bool isWideFastFlagsStale(void) const { return m_wideFastStale; }            // the next wide fast traceBatch validates first
+    S32  getWideFastValidations(void) const { return m_wideFastValidations; }    // ntr_instanced_wide_validate calls so far
+    void getWideFastFlags(U32& tlasFlags, U32& poolFlags);                       // the granted sets; validates if stale; needs isWide(); blocks
     bool isWide(void) const { return m_built && m_widePool && m_wideTlas; }      // the wide pool, TLAS and records are current
     bool isWidePoolCurrent(void) const { return m_widePool; }
     const NtrTlasWideResult& getWideResult(void) const { return m_wideResult; }            // of the last widen() (zero before)
@@ -187,6 +199,11 @@ private:
     Buffer        m_fastFlags;
     bool          m_traceFast, m_fastStale;
     S32           m_fastValidations;
+    // the same for the wide path (setTraceWideFast): ntr_instanced_wide_validate's four words over the wide buffers
+    const uint32_t* currentWideFastFlags(void);                                  // validates if stale
+    Buffer        m_wideFastFlags;
+    bool          m_traceWideFast, m_wideFastStale;
+    S32           m_wideFastValidations;
 };
 
 }  // namespace FW

@@ -6,7 +6,7 @@ namespace FW {
 
 InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
     : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
-      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false), m_fast(false),
+      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false), m_fast(false), m_wideFast(false),
       m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
 {
 }
@@ -38,11 +38,12 @@ F32 InstancedRenderer::trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
 {
     struct Restore {   // the caller's flags come back on every path: traceBatch fails by throwing
         CudaInstancedBVH& bvh;
-        bool was, wasFast;
-        ~Restore() { bvh.setTraceWide(was); bvh.setTraceFast(wasFast); }
-    } restore = {m_bvh, m_bvh.getTraceWide(), m_bvh.getTraceFast()};
+        bool was, wasFast, wasWideFast;
+        ~Restore() { bvh.setTraceWide(was); bvh.setTraceFast(wasFast); bvh.setTraceWideFast(wasWideFast); }
+    } restore = {m_bvh, m_bvh.getTraceWide(), m_bvh.getTraceFast(), m_bvh.getTraceWideFast()};
     m_bvh.setTraceWide(m_wide);
     m_bvh.setTraceFast(m_fast || restore.wasFast);
+    m_bvh.setTraceWideFast(m_wideFast || restore.wasWideFast);
     return m_bvh.traceBatch(rays, instanceIDs, rayMask);
 }
 

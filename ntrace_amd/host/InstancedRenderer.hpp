@@ -16,6 +16,8 @@
 //                 with whatever the CudaInstancedBVH itself was told, when this is off -- which is put back after each trace.  The
 //                 records are the same in every word, so nothing else of the frame changes.  The wide path is untouched: with
 //                 setWide(true) the switch is ignored
+//   setWideFast   the same for the wide batches of a setWide(true) frame (CudaInstancedBVH::setTraceWideFast); default
+//                 false; in the manner of setFast: on, or whatever the CudaInstancedBVH itself was told, and put back after each trace
 //   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
 //                 diffuse frames the primary rays are traced and resolved at once
 //   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
@@ -48,6 +50,8 @@ public:
     bool getWide(void) const { return m_wide; }
     void setFast(bool on) { m_fast = on; }
     bool getFast(void) const { return m_fast; }
+    void setWideFast(bool on) { m_wideFast = on; }
+    bool getWideFast(void) const { return m_wideFast; }
 
     void beginFrame(const CameraView& camera, S32 w, S32 h);
     bool nextBatch(void);
@@ -64,7 +68,7 @@ public:
 
 private:
     void resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals);
-    F32  trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask);   // the CudaInstancedBVH's traceBatch, wide when setWide asked for it, fast when setFast did
+    F32  trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask);   // the CudaInstancedBVH's traceBatch, wide when setWide asked for it, fast when setFast / setWideFast did
     InstancedRenderer(const InstancedRenderer&);
     InstancedRenderer& operator=(const InstancedRenderer&);
 
@@ -76,7 +80,7 @@ private:
     F32        m_aoRadius;
     S32        m_numSamples;
     U32        m_primaryMask, m_secondaryMask;
-    bool       m_wide, m_fast;
+    bool       m_wide, m_fast, m_wideFast;
     RayGen     m_raygen;
     F32        m_cameraFar;
     RayBuffer  m_primaryRays, m_secondaryRays;

@@ -45,6 +45,13 @@ frame beside it (raygen_ao_single_ms).  The keys of earlier runs stay as they we
                each timed by its own stream events (median, min, max); the FAST share (fastWaveSteps / waveSteps, niceEntries /
                numInstanceEntries) from ntr_trace_instanced_fast_stats; ntr_instanced_validate's own time and the flags it grants.  The
                records, the instance ids and the eight counters of both paths are asserted equal before anything is timed
+  * wide_fast  (not in the default parts) the FAST slab test in the two-level trace over 4-wide trees (ntr_instanced_wide_validate,
+               ntr_trace_instanced_wide_fast) over the identity and the forest frame: per batch (primary closest hit,
+               host-made AO any hit) ntr_trace_instanced_wide with a vis that shows everything -- the kernel as it was: the yardstick --
+               and the wide fast launch ALTERNATED in this process, each timed by its own stream events (median, min, max), and for
+               context the binary fast launch of `fast` on the same frame; the FAST share from ntr_trace_instanced_wide_fast_stats;
+               ntr_instanced_wide_validate's own time and the flags it grants.  The records, the instance ids and the counters of both
+               wide paths are asserted equal before anything is timed
 Prints one JSON line per part.
 
     timeout -k 10 600 python scripts/instanced_bench.py --out instanced.json
@@ -256,7 +263,7 @@ def main():
         rows.append(row)
 
     soup = None
-    if any(p in args.parts for p in ("tlas", "forest", "masks", "wide", "wide_sweep", "optimize_forest", "fast")):
+    if any(p in args.parts for p in ("tlas", "forest", "masks", "wide", "wide_sweep", "optimize_forest", "fast", "wide_fast")):
         tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
         soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
 
@@ -472,6 +479,70 @@ def main():
                    "fast_wave_share": f["fastWaveSteps"] / max(f["waveSteps"], 1), "nice_entry_share": f["niceEntries"] / max(c["numInstanceEntries"], 1),
                    "nice_start_share": f["niceStarts"] / count}
             out["fast_over_masked"] = out["fast"]["ms_median"] / out["masked"]["ms_median"]
+            return out
+        row["primary"] = batch("primary", n, False, d_rays)
+        row["ao"] = batch("ao", na, True, d_ao)
+        assert nt.trace_status() == 0, "traversal stack overflow"
+        return row
+
+    def wide_fast_frame(frame_name, t, cam):
+        """The part `wide_fast` over one frame: wide and wide fast launches alternated, the FAST share, the wide validate pass's own time."""
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays, d_res, d_ids, d_fres, d_fids = step(frame_name + " buffers", args.limit, lambda: [up(rays)] + [
+            torch.zeros(max(n, na) * b, dtype=torch.uint8, device="cuda:0") for b in (16, 4, 16, 4)])
+        d_flags = torch.zeros(16, dtype=torch.uint8, device="cuda:0")
+        d_bflags = torch.zeros(16, dtype=torch.uint8, device="cuda:0")
+        b, r = t.blas, t.res
+        row = {"part": "wide_fast", "frame": frame_name, "instances": t.n, "primary_rays": n, "ao_rays": na}
+        step(frame_name + " widening", args.limit, lambda: t.widen())
+        wt, wp = int(t.wtlas_res.nodesBytes), int(t.wpool_res.nodesBytes)
+        everything = nt.InstanceVisibility(0, 0)
+
+        def validate():
+            nt.instanced_wide_validate(t.d_wtlas.data_ptr() if wt else 0, wt, t.d_wpool.data_ptr(), wp, d_flags.data_ptr(), stream)
+        row["wide_validate_ms"] = step(frame_name + " wide validate", args.limit, lambda: median_event_ms(validate, args.reps, args.warmup))
+        row["validated_bytes"] = wt + wp
+        row["granted_wide_tlas_flags"], row["granted_wide_pool_flags"] = nt.instanced_flags_read(d_flags.data_ptr(), stream)
+        nt.instanced_validate(t.d_nodes.data_ptr() if r.nodesBytes else 0, r.nodesBytes, b.bufs[0].data_ptr(), b.nb, d_bflags.data_ptr(), stream)
+
+        def first_primary():
+            t.trace(n, False, d_rays, d_res, d_ids)
+            torch.cuda.synchronize()
+            return d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE).copy()
+        res = step(frame_name + " primary for the ao rays", args.limit, first_primary)
+        d_ao = step(frame_name + " ao upload", args.limit, lambda: up(host_ao_rays(rays, res, na, 7)))
+
+        def batch(name, count, any_hit, d_r):
+            def check():                                      # records and counters equal, before anything is timed
+                st = nt.trace_instanced_wide_stats(*t.wide_args(count, any_hit, d_r, d_res, d_ids), vis=everything, stream=stream)
+                fst, ff = nt.trace_instanced_wide_fast_stats(*t.wide_args(count, any_hit, d_r, d_fres, d_fids), d_flags.data_ptr(), vis=everything,
+                                                             stream=stream)
+                nt.trace_instanced_wide(*t.wide_args(count, any_hit, d_r, d_res, d_ids), vis=everything, stream=stream)
+                nt.trace_instanced_wide_fast(*t.wide_args(count, any_hit, d_r, d_fres, d_fids), d_flags.data_ptr(), vis=everything, stream=stream)
+                torch.cuda.synchronize()
+                assert torch.equal(d_res[:16 * count], d_fres[:16 * count]) and torch.equal(d_ids[:4 * count], d_fids[:4 * count]), \
+                    "%s %s: the wide fast launch's records differ from the wide launch's" % (frame_name, name)
+                assert st.as_dict() == fst.as_dict(), (st.as_dict(), fst.as_dict())
+                return st, ff
+            st, ff = step("%s %s records and counters" % (frame_name, name), args.limit, check)
+
+            def run():
+                w_secs, f_secs = [], []
+                for _ in range(args.warmup + args.reps):      # alternated: wide, wide fast, wide, wide fast, ...
+                    w_secs.append(nt.trace_instanced_wide(*t.wide_args(count, any_hit, d_r, d_res, d_ids), vis=everything, stream=stream))
+                    f_secs.append(nt.trace_instanced_wide_fast(*t.wide_args(count, any_hit, d_r, d_fres, d_fids), d_flags.data_ptr(), vis=everything,
+                                                               stream=stream))
+                return w_secs[args.warmup:], f_secs[args.warmup:]
+            w_secs, f_secs = step("%s %s" % (frame_name, name), args.limit, run)
+            bf_secs = step("%s %s binary fast" % (frame_name, name), args.limit, lambda: [
+                nt.trace_instanced_fast(*t.args(count, any_hit, d_r, d_fres, d_fids), d_bflags.data_ptr(), stream=stream)
+                for _ in range(args.warmup + args.reps)][args.warmup:])
+            c, f = st.as_dict(), ff.as_dict()
+            out = {"wide": rate(w_secs, count), "wide_fast": rate(f_secs, count), "binary_fast": rate(bf_secs, count), "counters": c,
+                   "fast_counters": f, "fast_wave_share": f["fastWaveSteps"] / max(f["waveSteps"], 1),
+                   "nice_entry_share": f["niceEntries"] / max(c["numInstanceEntries"], 1), "nice_start_share": f["niceStarts"] / count}
+            out["wide_fast_over_wide"] = out["wide_fast"]["ms_median"] / out["wide"]["ms_median"]
             return out
         row["primary"] = batch("primary", n, False, d_rays)
         row["ao"] = batch("ao", na, True, d_ao)
@@ -730,7 +801,7 @@ def main():
         t.res = t.build()
         return out
 
-    if "identity" in args.parts or "masks" in args.parts or "wide" in args.parts or "fast" in args.parts:
+    if any(p in args.parts for p in ("identity", "masks", "wide", "fast", "wide_fast")):
         tri, pos, cam = scenes.atrium()
         atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
         t = step("identity tlas", args.limit, lambda: Tlas(atrium, np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F), stream))
@@ -744,8 +815,10 @@ def main():
             emit(wide_frame("identity", t, cam))
         if "fast" in args.parts:
             emit(fast_frame("identity", t, cam))
+        if "wide_fast" in args.parts:
+            emit(wide_fast_frame("identity", t, cam))
 
-    if "forest" in args.parts or "masks" in args.parts or "wide" in args.parts or "optimize_forest" in args.parts or "fast" in args.parts:
+    if any(p in args.parts for p in ("forest", "masks", "wide", "optimize_forest", "fast", "wide_fast")):
         rng = np.random.default_rng(4096)
         g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
         t = step("forest tlas", args.limit, lambda: Tlas(soup, transforms(rotations(4096, rng), (g - 7.5) * 30.0), stream))
@@ -761,6 +834,8 @@ def main():
             emit(step("pool widen loop", args.limit, wide_pool_loop))
         if "fast" in args.parts:
             emit(fast_frame("forest", t, cam))
+        if "wide_fast" in args.parts:
+            emit(wide_fast_frame("forest", t, cam))
         if "optimize_forest" in args.parts:
             for row in optimize_forest_rows(t, cam):
                 emit(row)
