@@ -1195,16 +1195,38 @@ def tlas_refit_scratch_bytes():
     return int(v.value)
 
 
+_ABSENT = object()   # an argument that an entry point does not have (None is a value: NULL)
+
+
+def _trace_two_level(name, out, num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                     num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, seed=_ABSENT,
+                     vis=_ABSENT, d_flags=_ABSENT):
+    """The one marshalling of the ntr_trace_instanced* entry points (binary or wide buffers alike).  After the rays `seed`, a
+    (d_seed_results, seed_instance) pair; after the pool `vis` and `d_flags`; then the out-arguments and the stream.  out: True or False
+    (`timed`: a float -> the seconds, or NULL -> None), or the classes of the stats -> one object of each (alone, or a tuple)."""
+    outs = [C.c_float(0.0)] if isinstance(out, bool) else [cls() for cls in out]
+    args = [int(num_rays), int(bool(any_hit)), _vp(d_rays)]
+    if seed is not _ABSENT:
+        args += [_vp(seed[0]), int(seed[1])]
+    args += [_vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances),
+             _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index)]
+    if vis is not _ABSENT:
+        args.append(C.byref(vis) if vis is not None else None)
+    if d_flags is not _ABSENT:
+        args.append(_vp(d_flags))
+    _check(getattr(lib(), name)(*args, *([None] if out is False else [C.byref(o) for o in outs]), _vp(stream)))
+    if isinstance(out, bool):
+        return float(outs[0].value) if out else None
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
 def trace_instanced(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances,
                     d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream=0, timed=True):
     """ntr_trace_instanced: closest or any hit through the top-level tree and the instances' trees.  timed=True returns the GPU seconds;
     timed=False is asynchronous on `stream` (capturable) and returns None."""
-    sec = C.c_float(0.0)
-    _check(lib().ntr_trace_instanced(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes),
-                                     int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances), _vp(d_pool_nodes),
-                                     int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
-                                     C.byref(sec) if timed else None, _vp(stream)))
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes,
+                            root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index,
+                            stream)
 
 
 def trace_instanced_masked(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
@@ -1213,25 +1235,18 @@ def trace_instanced_masked(num_rays, any_hit, d_rays, d_results, d_instance_ids,
     """ntr_trace_instanced_masked: trace_instanced with instance visibility (the rule is tests/np_instanced_masked.py).  vis: an
     InstanceVisibility, or None (NULL: no masks, the unmasked kernel).  timed=True returns the GPU seconds; timed=False is asynchronous
     on `stream` (capturable; the mask arrays are read at replay time) and returns None."""
-    sec = C.c_float(0.0)
-    _check(lib().ntr_trace_instanced_masked(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
-                                            _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances),
-                                            _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
-                                            _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
-                                            C.byref(sec) if timed else None, _vp(stream)))
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced_masked", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
+                            tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                            d_pool_tri_index, stream, vis=vis)
 
 
 def trace_instanced_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
                           num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0):
     """ntr_trace_instanced_stats: trace_instanced_masked's records through the instrumented kernel -> InstancedTraceStats.  Blocks; not
     a timed path; refused on a capturing stream."""
-    st = InstancedTraceStats()
-    _check(lib().ntr_trace_instanced_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
-                                           _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances),
-                                           _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
-                                           _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None, C.byref(st), _vp(stream)))
-    return st
+    return _trace_two_level("ntr_trace_instanced_stats", (InstancedTraceStats,), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
+                            tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                            d_pool_tri_index, stream, vis=vis)
 
 
 def instanced_hit_attributes(num_rays, d_results, d_instance_ids, geom, d_out_results=0, d_normals=0, stream=0):
@@ -1354,13 +1369,9 @@ def trace_instanced_wide(num_rays, any_hit, d_rays, d_results, d_instance_ids, d
     """ntr_trace_instanced_wide: trace_instanced_masked over 4-wide trees (tlas_widen, pool_widen); the rule is
     tests/np_instanced_wide.py.  vis: an InstanceVisibility or None.  timed=True returns the GPU seconds; timed=False is asynchronous on
     `stream` (capturable) and returns None."""
-    sec = C.c_float(0.0)
-    _check(lib().ntr_trace_instanced_wide(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
-                                          _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), int(root_link), _vp(d_wide_records),
-                                          int(num_instances), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes), _vp(d_pool_woop),
-                                          int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
-                                          C.byref(sec) if timed else None, _vp(stream)))
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced_wide", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes,
+                            wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop,
+                            pool_woop_bytes, d_pool_tri_index, stream, vis=vis)
 
 
 def trace_instanced_wide_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
@@ -1368,21 +1379,9 @@ def trace_instanced_wide_stats(num_rays, any_hit, d_rays, d_results, d_instance_
                                d_pool_tri_index, vis=None, stream=0):
     """ntr_trace_instanced_wide_stats: trace_instanced_wide's records through the instrumented kernel -> InstancedWideTraceStats
     (numTopInnerVisits and numInnerVisits count wide nodes).  Blocks; refused on a capturing stream."""
-    st = InstancedWideTraceStats()
-    _check(lib().ntr_trace_instanced_wide_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_instance_ids),
-                                                _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), int(root_link), _vp(d_wide_records),
-                                                int(num_instances), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes), _vp(d_pool_woop),
-                                                int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
-                                                C.byref(st), _vp(stream)))
-    return st
-
-
-def _trace_seeded(fn, out, num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes,
-                  root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream):
-    _check(fn(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance), _vp(d_results), _vp(d_instance_ids),
-              _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(num_instances), _vp(d_pool_nodes),
-              int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
-              out, _vp(stream)))
+    return _trace_two_level("ntr_trace_instanced_wide_stats", (InstancedWideTraceStats,), num_rays, any_hit, d_rays, d_results, d_instance_ids,
+                            d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
+                            wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, vis=vis)
 
 
 def trace_instanced_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes,
@@ -1393,11 +1392,9 @@ def trace_instanced_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_insta
     nothing keeps the seed's four words and, for a hit, seed_instance.  d_results may be d_seed_results.  The intended seed is trace_bvh
     of the world BLAS's range of the pool.  timed=True returns the GPU seconds; timed=False is asynchronous on `stream` (capturable) and
     returns None."""
-    sec = C.c_float(0.0)
-    _trace_seeded(lib().ntr_trace_instanced_seeded, C.byref(sec) if timed else None, num_rays, any_hit, d_rays, d_seed_results, seed_instance,
-                  d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
-                  d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced_seeded", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
+                            tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                            d_pool_tri_index, stream, seed=(d_seed_results, seed_instance), vis=vis)
 
 
 def trace_instanced_seeded_stats(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_tlas_nodes,
@@ -1405,11 +1402,9 @@ def trace_instanced_seeded_stats(num_rays, any_hit, d_rays, d_seed_results, seed
                                  pool_woop_bytes, d_pool_tri_index, vis=None, stream=0):
     """ntr_trace_instanced_seeded_stats: trace_instanced_seeded's records through the instrumented kernel -> InstancedTraceStats (the
     seed read adds 16 B per ray to algorithmic_bytes).  Blocks; refused on a capturing stream."""
-    st = InstancedTraceStats()
-    _trace_seeded(lib().ntr_trace_instanced_seeded_stats, C.byref(st), num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results,
-                  d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
-                  d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
-    return st
+    return _trace_two_level("ntr_trace_instanced_seeded_stats", (InstancedTraceStats,), num_rays, any_hit, d_rays, d_results, d_instance_ids,
+                            d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop,
+                            pool_woop_bytes, d_pool_tri_index, stream, seed=(d_seed_results, seed_instance), vis=vis)
 
 
 def instanced_validate(d_tlas_nodes, tlas_nodes_bytes, d_pool_nodes, pool_nodes_bytes, d_flags, stream=0):
@@ -1435,13 +1430,9 @@ def trace_instanced_fast(num_rays, any_hit, d_rays, d_results, d_instance_ids, d
     FAST slab test wherever the wave's rays and d_flags (instanced_validate's words, read by the launch) allow it; the rule is
     tests/np_instanced_fast.py.  timed=True returns the GPU seconds; timed=False is asynchronous on `stream` (capturable) and returns
     None."""
-    sec = C.c_float(0.0)
-    _check(lib().ntr_trace_instanced_fast(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
-                                          _vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link),
-                                          _vp(d_records), int(num_instances), _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_pool_woop),
-                                          int(pool_woop_bytes), _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None,
-                                          _vp(d_flags), C.byref(sec) if timed else None, _vp(stream)))
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced_fast", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
+                            tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                            d_pool_tri_index, stream, seed=(d_seed_results, seed_instance), vis=vis, d_flags=d_flags)
 
 
 def trace_instanced_fast_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
@@ -1449,14 +1440,9 @@ def trace_instanced_fast_stats(num_rays, any_hit, d_rays, d_results, d_instance_
                                vis=None, d_seed_results=0, seed_instance=-1, stream=0):
     """ntr_trace_instanced_fast_stats: trace_instanced_fast's records through the instrumented kernels ->
     (InstancedTraceStats, InstancedFastStats).  Blocks; refused on a capturing stream."""
-    st, fs = InstancedTraceStats(), InstancedFastStats()
-    _check(lib().ntr_trace_instanced_fast_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
-                                                _vp(d_results), _vp(d_instance_ids), _vp(d_tlas_nodes), int(tlas_nodes_bytes),
-                                                int(root_link), _vp(d_records), int(num_instances), _vp(d_pool_nodes),
-                                                int(pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
-                                                C.byref(vis) if vis is not None else None, _vp(d_flags), C.byref(st), C.byref(fs),
-                                                _vp(stream)))
-    return st, fs
+    return _trace_two_level("ntr_trace_instanced_fast_stats", (InstancedTraceStats, InstancedFastStats), num_rays, any_hit, d_rays, d_results,
+                            d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
+                            d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, seed=(d_seed_results, seed_instance), vis=vis, d_flags=d_flags)
 
 
 def trace_instanced_wide_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes,
@@ -1464,11 +1450,9 @@ def trace_instanced_wide_seeded(num_rays, any_hit, d_rays, d_seed_results, seed_
                                 d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0, timed=True):
     """ntr_trace_instanced_wide_seeded: trace_instanced_seeded over 4-wide trees (the rule is tests/np_instanced_seeded.py, trace_wide).
     timed=True returns the GPU seconds; timed=False is asynchronous on `stream` (capturable) and returns None."""
-    sec = C.c_float(0.0)
-    _trace_seeded(lib().ntr_trace_instanced_wide_seeded, C.byref(sec) if timed else None, num_rays, any_hit, d_rays, d_seed_results,
-                  seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances,
-                  d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced_wide_seeded", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes,
+                            wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop,
+                            pool_woop_bytes, d_pool_tri_index, stream, seed=(d_seed_results, seed_instance), vis=vis)
 
 
 def trace_instanced_wide_seeded_stats(num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results, d_instance_ids, d_wide_tlas_nodes,
@@ -1476,11 +1460,10 @@ def trace_instanced_wide_seeded_stats(num_rays, any_hit, d_rays, d_seed_results,
                                       wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, stream=0):
     """ntr_trace_instanced_wide_seeded_stats: trace_instanced_wide_seeded's records through the instrumented kernel ->
     InstancedWideTraceStats.  Blocks; refused on a capturing stream."""
-    st = InstancedWideTraceStats()
-    _trace_seeded(lib().ntr_trace_instanced_wide_seeded_stats, C.byref(st), num_rays, any_hit, d_rays, d_seed_results, seed_instance, d_results,
-                  d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
-                  wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis, stream)
-    return st
+    return _trace_two_level("ntr_trace_instanced_wide_seeded_stats", (InstancedWideTraceStats,), num_rays, any_hit, d_rays, d_results, d_instance_ids,
+                            d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
+                            wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, seed=(d_seed_results, seed_instance),
+                            vis=vis)
 
 
 def instanced_wide_validate(d_wide_tlas_nodes, wide_tlas_nodes_bytes, d_wide_pool_nodes, wide_pool_nodes_bytes, d_flags, stream=0):
@@ -1499,14 +1482,9 @@ def trace_instanced_wide_fast(num_rays, any_hit, d_rays, d_results, d_instance_i
     given -- with the FAST slab test wherever the wave's rays and d_flags (instanced_wide_validate's words, read by the launch) allow it;
     the rule is tests/np_instanced_wide_fast.py.  timed=True returns the GPU seconds; timed=False is asynchronous on `stream`
     (capturable) and returns None."""
-    sec = C.c_float(0.0)
-    _check(lib().ntr_trace_instanced_wide_fast(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
-                                               _vp(d_results), _vp(d_instance_ids), _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes),
-                                               int(root_link), _vp(d_wide_records), int(num_instances), _vp(d_wide_pool_nodes),
-                                               int(wide_pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_tri_index),
-                                               C.byref(vis) if vis is not None else None, _vp(d_flags), C.byref(sec) if timed else None,
-                                               _vp(stream)))
-    return float(sec.value) if timed else None
+    return _trace_two_level("ntr_trace_instanced_wide_fast", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes,
+                            wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop,
+                            pool_woop_bytes, d_pool_tri_index, stream, seed=(d_seed_results, seed_instance), vis=vis, d_flags=d_flags)
 
 
 def trace_instanced_wide_fast_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
@@ -1514,14 +1492,10 @@ def trace_instanced_wide_fast_stats(num_rays, any_hit, d_rays, d_results, d_inst
                                     d_pool_tri_index, d_flags, vis=None, d_seed_results=0, seed_instance=-1, stream=0):
     """ntr_trace_instanced_wide_fast_stats: trace_instanced_wide_fast's records through the instrumented kernels ->
     (InstancedWideTraceStats, InstancedFastStats).  Blocks; refused on a capturing stream."""
-    st, fs = InstancedWideTraceStats(), InstancedFastStats()
-    _check(lib().ntr_trace_instanced_wide_fast_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_seed_results), int(seed_instance),
-                                                     _vp(d_results), _vp(d_instance_ids), _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes),
-                                                     int(root_link), _vp(d_wide_records), int(num_instances), _vp(d_wide_pool_nodes),
-                                                     int(wide_pool_nodes_bytes), _vp(d_pool_woop), int(pool_woop_bytes),
-                                                     _vp(d_pool_tri_index), C.byref(vis) if vis is not None else None, _vp(d_flags),
-                                                     C.byref(st), C.byref(fs), _vp(stream)))
-    return st, fs
+    return _trace_two_level("ntr_trace_instanced_wide_fast_stats", (InstancedWideTraceStats, InstancedFastStats), num_rays, any_hit, d_rays, d_results,
+                            d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
+                            wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, seed=(d_seed_results, seed_instance),
+                            vis=vis, d_flags=d_flags)
 
 
 def _wide_refit_entries(entries):

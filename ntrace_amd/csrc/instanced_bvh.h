@@ -50,6 +50,14 @@ inline int check_pool_bytes(const char* fn, const char* what, int64_t bytes, int
     return NTR_OK;
 }
 
+// The top-level tree's root: node 0, or the link ~i of an instance that is the whole tree
+inline int check_root_link(const char* fn, int32_t rootLink, int32_t numInstances)
+{
+    if (!(rootLink == 0 || (rootLink < 0 && (int64_t)~rootLink < numInstances)))
+        return set_error(NTR_ERR_INVALID, "%s: rootLink %d is neither 0 nor an instance's link", fn, (int)rootLink);
+    return NTR_OK;
+}
+
 // BLAS k's range against the pool's node buffer and Compact's limits (the triWoop side has no buffer at build time: alignment and
 // the pool limit only)
 inline int check_blas_range(const char* fn, int k, const NtrBlasRange& r, int64_t poolNodesBytes)

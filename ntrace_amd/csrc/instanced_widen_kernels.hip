@@ -121,8 +121,7 @@ int ntr_tlas_widen(int32_t numInstances, const NtrInstance* d_instances, const v
     if (!d_instances || !d_wideRecords || !result) return set_error(NTR_ERR_INVALID, "%s: null buffer or result", fn);
     if ((((uintptr_t)d_instances) | ((uintptr_t)d_wideRecords) | ((uintptr_t)d_wideTlasNodes) | ((uintptr_t)d_tlasNodes)) & 15u)
         return set_error(NTR_ERR_INVALID, "%s: the buffers must be 16-byte aligned", fn);
-    if (!(rootLink == 0 || (rootLink < 0 && (int64_t)~rootLink < numInstances)))
-        return set_error(NTR_ERR_INVALID, "%s: rootLink %d is neither 0 nor an instance's link", fn, (int)rootLink);
+    if (const int rc = check_root_link(fn, rootLink, numInstances)) return rc;
     if (rootLink == 0) {
         if (!d_tlasNodes || !d_wideTlasNodes) return set_error(NTR_ERR_INVALID, "%s: null top-level buffer", fn);
         if (const int rc = check_nodes_bytes(fn, "tlasNodesBytes", tlasNodesBytes)) return rc;

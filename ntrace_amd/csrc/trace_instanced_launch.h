@@ -1,0 +1,151 @@
+// trace_instanced_launch.h -- host only: the launch of the two-level trace, stated once for its four units:
+//   trace_instanced_kernels.hip            ntr_trace_instanced, _masked, _stats, _seeded, _seeded_stats
+//   trace_instanced_fast_kernels.hip       ntr_trace_instanced_fast, _fast_stats
+//   trace_instanced_wide_kernels.hip       ntr_trace_instanced_wide, _wide_stats, _wide_seeded, _wide_seeded_stats
+//   trace_instanced_wide_fast_kernels.hip  ntr_trace_instanced_wide_fast, _wide_fast_stats
+// An entry point writes what it was given into a TwoLevelCall, with the few facts in which the units differ, and calls two_level_trace
+// with its unit's launch: the checks, the device state, the bracket (trace_launch.h) and the counters' unpacking are here; the kernels,
+// the fill of their parameters and the choice among them stay with the unit (trace_instanced_kernels.h: why the units are separate).
+// What the checks refuse, in which words and in which order, is pinned by tests/test_two_level_refusals_cpu.py.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "ntr_internal.h"
+#include "instanced_wide_bvh.h"
+#include "trace_launch.h"
+
+namespace ntr {
+
+// The two layouts: the unit and the cap of the top-level node buffer and of a BLAS in the pool, and the words of their refusals
+struct TwoLevelLayout {
+    int unit;
+    int64_t tlasMaxBytes;
+    const char *tlasRefusal, *poolNodesName;
+};
+constexpr TwoLevelLayout kTwoLevelBinary = {kNodeBytes, kMaxNodesBytes,
+                                            "%s: the top-level node buffer must be a multiple of 64 bytes, at most 0x%llx, and hold the root",
+                                            "poolNodesBytes"};
+constexpr TwoLevelLayout kTwoLevelWide = {kWideBytes, kMaxWideBytes,
+                                          "%s: the wide top-level node buffer must be a multiple of 128 bytes, at most 0x%llx, and hold the root",
+                                          "widePoolNodesBytes"};
+enum class TwoLevelSeed { kNone, kRequired, kOptional };
+
+// What an entry point was given, in the order of the widest parameter list (an entry point without an argument passes NULL, and -1 for
+// seedInstance), after the three facts about the entry point itself.
+struct TwoLevelCall {
+    const char* fn;
+    const TwoLevelLayout& layout;
+    TwoLevelSeed seed;
+    const char* validate;   // the FAST units: d_flags must be given, and this call writes them; NULL: no flags
+    int32_t numRays, anyHit;
+    const NtrRay* rays;
+    const NtrRayResult* seedResults;
+    int32_t seedInstance;
+    NtrRayResult* results;
+    int32_t* instanceIDs;
+    const void* tlas;
+    int64_t tlasBytes;
+    int32_t rootLink;
+    const void* records;
+    int32_t numInstances;
+    const void* poolNodes;
+    int64_t poolNodesBytes;
+    const void* poolTriWoop;
+    int64_t poolTriWoopBytes;
+    const int32_t* poolTriIndex;
+    const NtrInstanceVisibility* vis;
+    const uint32_t* d_flags;
+    float* seconds;
+    void* stream;
+    NtrInstancedTraceStats* stats;      // both NULL, or the instrumented kernel; a FAST unit takes both or neither
+    NtrInstancedFastStats* fastStats;
+};
+
+// Zeroes the out-arguments and checks the call.  *go: the call is good and has rays to trace (NTR_OK with !*go: numRays == 0, done).
+inline int two_level_check(const TwoLevelCall& c, bool* go)
+{
+    const char* fn = c.fn;
+    *go = false;
+    if (c.seconds) *c.seconds = 0.0f;
+    if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
+    if (c.fastStats) memset(c.fastStats, 0, sizeof(*c.fastStats));
+    if (c.validate && (c.stats != nullptr) != (c.fastStats != nullptr)) return set_error(NTR_ERR_INVALID, "%s: null stats", fn);
+    if (c.numRays < 0) return set_error(NTR_ERR_INVALID, "%s: numRays < 0", fn);
+    if (c.numRays == 0) return NTR_OK;
+    if (!c.rays || !c.results || !c.instanceIDs) return set_error(NTR_ERR_INVALID, "%s: null ray, result or instance id buffer", fn);
+    if (c.numInstances < 1 || (int64_t)c.numInstances * kRecordBytes > kPoolMaxBytes || !c.records || !c.poolNodes || !c.poolTriWoop ||
+        !c.poolTriIndex)
+        return set_error(NTR_ERR_INVALID, "%s: no instances or no pool", fn);
+    if (const int rc = check_root_link(fn, c.rootLink, c.numInstances)) return rc;
+    const TwoLevelLayout& l = c.layout;
+    if (c.tlasBytes < 0 || (c.tlasBytes % l.unit) != 0 || c.tlasBytes > l.tlasMaxBytes || (c.rootLink == 0 && (!c.tlas || c.tlasBytes < l.unit)))
+        return set_error(NTR_ERR_INVALID, l.tlasRefusal, fn, (unsigned long long)l.tlasMaxBytes);
+    if (const int rc = check_pool_bytes(fn, l.poolNodesName, c.poolNodesBytes, l.unit)) return rc;   // (check_wide_pool_bytes's words at 128)
+    if (const int rc = check_pool_bytes(fn, "poolTriWoopBytes", c.poolTriWoopBytes, kRowBytes)) return rc;
+    if (c.vis && ((((uintptr_t)c.vis->d_instanceMasks) | ((uintptr_t)c.vis->d_rayMasks)) & 3u) != 0)
+        return set_error(NTR_ERR_INVALID, "%s: a mask array must be 4-byte aligned", fn);
+    if (c.seed == TwoLevelSeed::kRequired && (!c.seedResults || (((uintptr_t)c.seedResults) & 15u) != 0))
+        return set_error(NTR_ERR_INVALID, "%s: the seed records must be given and 16-byte aligned", fn);
+    if (c.seed == TwoLevelSeed::kOptional && (((uintptr_t)c.seedResults) & 15u) != 0)
+        return set_error(NTR_ERR_INVALID, "%s: the seed records must be 16-byte aligned", fn);
+    if (c.validate && (!c.d_flags || (((uintptr_t)c.d_flags) & 15u) != 0))
+        return set_error(NTR_ERR_INVALID, "%s: the flags (%s) must be given and 16-byte aligned", fn, c.validate);
+    *go = true;
+    return NTR_OK;
+}
+
+// The fields that the parameter structs of the four units name alike: the kernels' P (InstancedParams, InstancedWideParams) ...
+template <class P>
+void two_level_fill(P& p, const TwoLevelCall& c, DeviceState* ds)
+{
+    p.numRays = c.numRays; p.anyHit = c.anyHit ? 1 : 0; p.rays = c.rays; p.results = c.results; p.instanceIDs = c.instanceIDs;
+    p.tlas = c.tlas; p.records = c.records; p.poolWoop = c.poolTriWoop;
+    p.tlasBytes = c.tlas ? (uint32_t)c.tlasBytes : 0u; p.recordsBytes = (uint32_t)((int64_t)c.numInstances * kRecordBytes);
+    p.poolWoopBytes = (uint32_t)c.poolTriWoopBytes;
+    p.triIndex = c.poolTriIndex; p.rootLink = c.rootLink; p.numInstances = c.numInstances; p.status = ds->status;
+}
+// ... and the visibility and counter fields (InstancedExtras, InstancedWideParams).  -> a mask can refuse something: without one the
+// unmasked kernel does
+template <class X>
+bool two_level_fill_visibility(X& x, const TwoLevelCall& c, DeviceState* ds)
+{
+    x.rayMask = 0xFFFFFFFFu;
+    if (c.vis) {
+        x.instMasks = c.vis->d_instanceMasks; x.instMasksBytes = c.vis->d_instanceMasks ? (uint32_t)((int64_t)c.numInstances * 4) : 0u;
+        x.rayMasks = c.vis->d_rayMasks; x.rayMask = c.vis->rayMask;
+    }
+    x.stats = ds->stats;   // STATS: the seven counters, and in the FAST units [8..11] (of 32 words)
+    return x.instMasks || x.rayMasks || x.rayMask != 0xFFFFFFFFu;
+}
+
+constexpr int kTwoLevelCounters = 7, kTwoLevelFastCounters = 12;   // the words an instrumented kernel adds to: [0..6], and [8..11] in the FAST units
+
+// The shared path of the entry points.  launch(ds, stream, blocks) fills the unit's parameters and enqueues the kernel that c asks for.
+template <class Launch>
+int two_level_trace(const TwoLevelCall& c, Launch&& launch)
+{
+    bool go = false;
+    if (const int rc = two_level_check(c, &go)) return rc;
+    if (!go) return NTR_OK;
+    DeviceState* ds = nullptr;
+    if (const int rc = current_device_state_ready(&ds)) return rc;
+    hipStream_t s = (hipStream_t)c.stream;
+    if (c.stats && stream_is_capturing(s)) return set_error(NTR_ERR_INVALID, "%s: the call reads its counters back and cannot be captured", c.fn);
+    unsigned long long h[kTwoLevelFastCounters] = {};
+    const int words = !c.stats ? 0 : c.fastStats ? kTwoLevelFastCounters : kTwoLevelCounters;
+    if (const int rc = launch_trace_rays(c.fn, ds, s, c.numRays, c.seconds, words, h, [&](unsigned int blocks) { launch(ds, s, blocks); })) return rc;
+    if (c.stats) {
+        c.stats->numRays = c.numRays;
+        c.stats->numTopInnerVisits = (int64_t)h[0]; c.stats->numInstanceEntries = (int64_t)h[1]; c.stats->numInstancesMasked = (int64_t)h[2];
+        c.stats->numInnerVisits = (int64_t)h[3]; c.stats->numTriTests = (int64_t)h[4]; c.stats->numLeafVisits = (int64_t)h[5];
+        c.stats->numHits = (int64_t)h[6];
+    }
+    if (c.fastStats) {
+        c.fastStats->waveSteps = h[8]; c.fastStats->fastWaveSteps = h[9]; c.fastStats->niceStarts = h[10]; c.fastStats->niceEntries = h[11];
+    }
+    return NTR_OK;
+}
+
+}  // namespace ntr

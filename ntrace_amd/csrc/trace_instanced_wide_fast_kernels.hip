@@ -14,16 +14,16 @@
 //           instantiations; a scalar branch, no per-lane divergence between the two forms
 // FAST equals GENERIC bit for bit in its range (trace_lane.h), so every result word, the instance ids, the status word and the seven
 // counters are ntr_trace_instanced_wide's / _wide_seeded's whatever the flags say -- as long as they grant nothing the buffers do not
-// hold.  Four kernels: trace_instanced_wide_fast<STATS> and trace_instanced_wide_fast_seeded<STATS>.  The entry points are here too:
-// trace_instanced_wide_kernels.hip stays as it was (trace_instanced_wide_kernels.h: why).
+// hold.  Four kernels: trace_instanced_wide_fast<STATS> and trace_instanced_wide_fast_seeded<STATS>, in a unit of their own
+// (trace_instanced_wide_kernels.h: why).  Of the host side the unit holds the fill of their parameters, the choice among them and the two
+// entry points; the launch around them is trace_instanced_launch.h's, shared with the three sibling units.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "ntr_internal.h"
 #include "instanced_wide_bvh.h"
-#include "device_scratch.h"
-#include "sched_state.h"
+#include "trace_instanced_launch.h"
 #include "trace_lane.h"
 #include "trace_wide_lane.h"
 #include "trace_instanced_wide_kernels.h"
@@ -54,96 +54,27 @@ namespace {
 #undef NTR_TIW_TEMPLATE
 #undef NTR_TIW_FAST
 
-// The two entry points' one body: trace_instanced_wide_impl's checks (trace_instanced_wide_kernels.hip) and d_flags; stats != NULL
-// launches an instrumented kernel and reads the eleven counters back.
-int trace_instanced_wide_fast_impl(const char* fn, int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
-                                   int32_t seedInstance, NtrRayResult* d_results, int32_t* d_instanceIDs, const void* d_wideTlasNodes,
-                                   int64_t wideTlasNodesBytes, int32_t rootLink, const void* d_wideRecords, int32_t numInstances,
-                                   const void* d_widePoolNodes, int64_t widePoolNodesBytes, const void* d_poolTriWoop, int64_t poolTriWoopBytes,
-                                   const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis, const uint32_t* d_flags, float* seconds,
-                                   void* stream, NtrInstancedTraceStats* stats, NtrInstancedFastStats* fastStats)
+// The unit's launch under the shared path (trace_instanced_launch.h): a seed launches a seeded kernel, stats != NULL an instrumented one.
+int trace_instanced_wide_fast_call(const TwoLevelCall& c)
 {
-    if (seconds) *seconds = 0.0f;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (fastStats) memset(fastStats, 0, sizeof(*fastStats));
-    if ((stats != nullptr) != (fastStats != nullptr)) return set_error(NTR_ERR_INVALID, "%s: null stats", fn);
-    if (numRays < 0) return set_error(NTR_ERR_INVALID, "%s: numRays < 0", fn);
-    if (numRays == 0) return NTR_OK;
-    if (!d_rays || !d_results || !d_instanceIDs) return set_error(NTR_ERR_INVALID, "%s: null ray, result or instance id buffer", fn);
-    if (numInstances < 1 || (int64_t)numInstances * kRecordBytes > kPoolMaxBytes || !d_wideRecords || !d_widePoolNodes || !d_poolTriWoop ||
-        !d_poolTriIndex)
-        return set_error(NTR_ERR_INVALID, "%s: no instances or no pool", fn);
-    if (!(rootLink == 0 || (rootLink < 0 && (int64_t)~rootLink < numInstances)))
-        return set_error(NTR_ERR_INVALID, "%s: rootLink %d is neither 0 nor an instance's link", fn, (int)rootLink);
-    if (wideTlasNodesBytes < 0 || (wideTlasNodesBytes % kWideBytes) != 0 || wideTlasNodesBytes > kMaxWideBytes ||
-        (rootLink == 0 && (!d_wideTlasNodes || wideTlasNodesBytes < kWideBytes)))
-        return set_error(NTR_ERR_INVALID, "%s: the wide top-level node buffer must be a multiple of 128 bytes, at most 0x%llx, and hold the root",
-                         fn, (unsigned long long)kMaxWideBytes);
-    if (const int rc = check_wide_pool_bytes(fn, "widePoolNodesBytes", widePoolNodesBytes)) return rc;
-    if (const int rc = check_pool_bytes(fn, "poolTriWoopBytes", poolTriWoopBytes, kRowBytes)) return rc;
-    if (vis && ((((uintptr_t)vis->d_instanceMasks) | ((uintptr_t)vis->d_rayMasks)) & 3u) != 0)
-        return set_error(NTR_ERR_INVALID, "%s: a mask array must be 4-byte aligned", fn);
-    if ((((uintptr_t)d_seedResults) & 15u) != 0) return set_error(NTR_ERR_INVALID, "%s: the seed records must be 16-byte aligned", fn);
-    if (!d_flags || (((uintptr_t)d_flags) & 15u) != 0)
-        return set_error(NTR_ERR_INVALID, "%s: the flags (ntr_instanced_wide_validate) must be given and 16-byte aligned", fn);
-
-    DeviceState* ds = nullptr;
-    if (const int rc = current_device_state_ready(&ds)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (stats && stream_is_capturing(s)) return set_error(NTR_ERR_INVALID, "%s: the call reads its counters back and cannot be captured", fn);
-    InstancedWideParams p{};
-    p.numRays = numRays; p.anyHit = anyHit ? 1 : 0; p.rays = d_rays; p.results = d_results; p.instanceIDs = d_instanceIDs;
-    p.tlas = d_wideTlasNodes; p.records = d_wideRecords; p.poolWide = d_widePoolNodes; p.poolWoop = d_poolTriWoop;
-    p.tlasBytes = d_wideTlasNodes ? (uint32_t)wideTlasNodesBytes : 0u; p.recordsBytes = (uint32_t)((int64_t)numInstances * kRecordBytes);
-    p.poolWideBytes = (uint32_t)widePoolNodesBytes; p.poolWoopBytes = (uint32_t)poolTriWoopBytes;
-    p.triIndex = d_poolTriIndex; p.rootLink = rootLink; p.numInstances = numInstances; p.status = ds->status;
-    p.rayMask = 0xFFFFFFFFu;
-    if (vis) {
-        p.instMasks = vis->d_instanceMasks; p.instMasksBytes = vis->d_instanceMasks ? (uint32_t)((int64_t)numInstances * 4) : 0u;
-        p.rayMasks = vis->d_rayMasks; p.rayMask = vis->rayMask;
-    }
-    p.stats = ds->stats;   // STATS: InstancedWideParams's seven, and at [8..11] {wave steps, FAST wave steps, nice starts, nice entries} (of 32 words)
-    InstancedFast fl{};
-    fl.flags = d_flags;
-    InstancedWideSeed sd{};
-    sd.seedResults = d_seedResults; sd.seedInstance = seedInstance;
-
-    StreamEvents<2> ev(s);   // the timed bracket
-    if (seconds) {
-        NTR_HIP(ev.create());
-        NTR_HIP(hipStreamSynchronize(s));
-        NTR_HIP(ev.record(0));
-    }
-    const dim3 grid((numRays + 63) / 64), block(64);
-    if (stats) NTR_HIP(hipMemsetAsync(ds->stats, 0, 12 * sizeof(unsigned long long), s));
-    if (d_seedResults) {
-        if (stats) hipLaunchKernelGGL((trace_instanced_wide_fast_seeded<true>), grid, block, 0, s, p, sd, fl);
-        else hipLaunchKernelGGL((trace_instanced_wide_fast_seeded<false>), grid, block, 0, s, p, sd, fl);
-    } else {
-        if (stats) hipLaunchKernelGGL((trace_instanced_wide_fast<true>), grid, block, 0, s, p, fl);
-        else hipLaunchKernelGGL((trace_instanced_wide_fast<false>), grid, block, 0, s, p, fl);
-    }
-    NTR_HIP(hipGetLastError());
-    if (seconds) {
-        NTR_HIP(ev.record(1));
-        float ms = 0.0f;
-        NTR_HIP(ev.elapsed(0, 1, &ms));
-        *seconds = ms * 1e-3f;
-        unsigned int bits = 0;
-        if (const int rc = status_fetch(ds, s, &bits)) return rc;
-        if (bits & NTR_STATUS_STACK_OVERFLOW) return set_error(NTR_ERR_OVERFLOW, "%s: traversal stack overflow", fn);
-    }
-    if (stats) {
-        unsigned long long h[12];
-        NTR_HIP(hipMemcpyAsync(h, ds->stats, sizeof(h), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        stats->numRays = numRays;
-        stats->numTopInnerVisits = (int64_t)h[0]; stats->numInstanceEntries = (int64_t)h[1]; stats->numInstancesMasked = (int64_t)h[2];
-        stats->numInnerVisits = (int64_t)h[3]; stats->numTriTests = (int64_t)h[4]; stats->numLeafVisits = (int64_t)h[5];
-        stats->numHits = (int64_t)h[6];
-        fastStats->waveSteps = h[8]; fastStats->fastWaveSteps = h[9]; fastStats->niceStarts = h[10]; fastStats->niceEntries = h[11];
-    }
-    return NTR_OK;
+    return two_level_trace(c, [&c](DeviceState* ds, hipStream_t s, unsigned int blocks) {
+        InstancedWideParams p{};
+        two_level_fill(p, c, ds);
+        p.poolWide = c.poolNodes; p.poolWideBytes = (uint32_t)c.poolNodesBytes;
+        two_level_fill_visibility(p, c, ds);
+        InstancedFast fl{};
+        fl.flags = c.d_flags;
+        InstancedWideSeed sd{};
+        sd.seedResults = c.seedResults; sd.seedInstance = c.seedInstance;
+        const dim3 grid(blocks), block(64);
+        if (c.seedResults) {
+            if (c.stats) hipLaunchKernelGGL((trace_instanced_wide_fast_seeded<true>), grid, block, 0, s, p, sd, fl);
+            else hipLaunchKernelGGL((trace_instanced_wide_fast_seeded<false>), grid, block, 0, s, p, sd, fl);
+        } else {
+            if (c.stats) hipLaunchKernelGGL((trace_instanced_wide_fast<true>), grid, block, 0, s, p, fl);
+            else hipLaunchKernelGGL((trace_instanced_wide_fast<false>), grid, block, 0, s, p, fl);
+        }
+    });
 }
 
 }  // namespace
@@ -158,10 +89,10 @@ extern "C" int ntr_trace_instanced_wide_fast(int32_t numRays, int32_t anyHit, co
                                              int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis,
                                              const uint32_t* d_flags, float* seconds, void* stream)
 {
-    return trace_instanced_wide_fast_impl("ntr_trace_instanced_wide_fast", numRays, anyHit, d_rays, d_seedResults, seedInstance, d_results,
-                                          d_instanceIDs, d_wideTlasNodes, wideTlasNodesBytes, rootLink, d_wideRecords, numInstances,
-                                          d_widePoolNodes, widePoolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex, vis, d_flags,
-                                          seconds, stream, nullptr, nullptr);
+    return trace_instanced_wide_fast_call({"ntr_trace_instanced_wide_fast", kTwoLevelWide, TwoLevelSeed::kOptional, "ntr_instanced_wide_validate",
+                                           numRays, anyHit, d_rays, d_seedResults, seedInstance, d_results, d_instanceIDs, d_wideTlasNodes,
+                                           wideTlasNodesBytes, rootLink, d_wideRecords, numInstances, d_widePoolNodes, widePoolNodesBytes,
+                                           d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex, vis, d_flags, seconds, stream, nullptr, nullptr});
 }
 
 extern "C" int ntr_trace_instanced_wide_fast_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, const NtrRayResult* d_seedResults,
@@ -172,11 +103,10 @@ extern "C" int ntr_trace_instanced_wide_fast_stats(int32_t numRays, int32_t anyH
                                                    const int32_t* d_poolTriIndex, const NtrInstanceVisibility* vis, const uint32_t* d_flags,
                                                    NtrInstancedTraceStats* stats, NtrInstancedFastStats* fastStats, void* stream)
 {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (fastStats) memset(fastStats, 0, sizeof(*fastStats));
-    if (!stats || !fastStats) return set_error(NTR_ERR_INVALID, "ntr_trace_instanced_wide_fast_stats: null stats");
-    return trace_instanced_wide_fast_impl("ntr_trace_instanced_wide_fast_stats", numRays, anyHit, d_rays, d_seedResults, seedInstance, d_results,
-                                          d_instanceIDs, d_wideTlasNodes, wideTlasNodesBytes, rootLink, d_wideRecords, numInstances,
-                                          d_widePoolNodes, widePoolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex, vis, d_flags,
-                                          nullptr, stream, stats, fastStats);
+    if (!stats && !fastStats) return set_error(NTR_ERR_INVALID, "ntr_trace_instanced_wide_fast_stats: null stats");   // (one of them: the shared check)
+    return trace_instanced_wide_fast_call({"ntr_trace_instanced_wide_fast_stats", kTwoLevelWide, TwoLevelSeed::kOptional,
+                                           "ntr_instanced_wide_validate", numRays, anyHit, d_rays, d_seedResults, seedInstance, d_results,
+                                           d_instanceIDs, d_wideTlasNodes, wideTlasNodesBytes, rootLink, d_wideRecords, numInstances,
+                                           d_widePoolNodes, widePoolNodesBytes, d_poolTriWoop, poolTriWoopBytes, d_poolTriIndex, vis, d_flags,
+                                           nullptr, stream, stats, fastStats});
 }

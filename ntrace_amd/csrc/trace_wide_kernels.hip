@@ -18,8 +18,7 @@
 
 #include "ntr_internal.h"
 #include "wide_bvh.h"
-#include "device_scratch.h"
-#include "sched_state.h"
+#include "trace_launch.h"
 #include "trace_lane.h"
 #include "trace_wide_lane.h"
 
@@ -124,33 +123,13 @@ int trace_wide_impl(const char* fn, int32_t numRays, int32_t anyHit, const NtrRa
     p.wide = d_wideNodes; p.woop = d_triWoop; p.wideBytes = (uint32_t)wideNodesBytes; p.woopBytes = (uint32_t)triWoopBytes;
     p.triIndex = d_triIndex; p.bvhFlags = bvhFlags; p.status = ds->status; p.stats = ds->stats;
 
-    StreamEvents<2> ev(s);   // the timed bracket
-    if (seconds) {
-        NTR_HIP(ev.create());
-        NTR_HIP(hipStreamSynchronize(s));
-        NTR_HIP(ev.record(0));
-    }
-    const dim3 grid((numRays + 63) / 64), block(64);
+    unsigned long long h[4] = {};
+    const int rc = launch_trace_rays(fn, ds, s, numRays, seconds, stats ? 4 : 0, h, [&](unsigned int blocks) {
+        if (stats) hipLaunchKernelGGL(trace_wide<true>, dim3(blocks), dim3(64), 0, s, p);
+        else hipLaunchKernelGGL(trace_wide<false>, dim3(blocks), dim3(64), 0, s, p);
+    });
+    if (rc != NTR_OK) return rc;
     if (stats) {
-        NTR_HIP(hipMemsetAsync(ds->stats, 0, 4 * sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(trace_wide<true>, grid, block, 0, s, p);
-    } else {
-        hipLaunchKernelGGL(trace_wide<false>, grid, block, 0, s, p);
-    }
-    NTR_HIP(hipGetLastError());
-    if (seconds) {
-        NTR_HIP(ev.record(1));
-        float ms = 0.0f;
-        NTR_HIP(ev.elapsed(0, 1, &ms));
-        *seconds = ms * 1e-3f;
-        unsigned int bits = 0;
-        if (const int rc = status_fetch(ds, s, &bits)) return rc;
-        if (bits & NTR_STATUS_STACK_OVERFLOW) return set_error(NTR_ERR_OVERFLOW, "%s: traversal stack overflow", fn);
-    }
-    if (stats) {
-        unsigned long long h[4];
-        NTR_HIP(hipMemcpyAsync(h, ds->stats, sizeof(h), hipMemcpyDeviceToHost, s));
-        NTR_HIP(hipStreamSynchronize(s));
         stats->numRays = numRays;
         stats->numInnerVisits = (int64_t)h[0]; stats->numTriTests = (int64_t)h[1]; stats->numLeafVisits = (int64_t)h[2]; stats->numHits = (int64_t)h[3];
     }

@@ -390,98 +390,62 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     instanceIDs.resizeDiscard((S64)numRays * sizeof(S32));
     if (!numRays) return 0.0f;
     if (!m_built) fail("CudaInstancedBVH: No TLAS!");
-    float seconds = 0.0f;
+    float seconds = 0.0f, worldSeconds = 0.0f;
     const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
+    const bool world = m_world >= 0, wide = m_traceWide && isWide();
+    const int32_t anyHit = rays.getNeedClosestHit() ? 0 : 1;
+    const NtrRay* d_rays = (const NtrRay*)rays.getRayBuffer().getCudaPtr();
+    NtrRayResult* d_results = (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr();
+    int32_t* d_ids = (int32_t*)instanceIDs.getMutableCudaPtr();
     int rc;
-    if (m_world >= 0) {
-        // the world's single-level trace on its range of the pool, then the seeded two-level trace over its records, in place
+    if (world) {
+        // the world's single-level trace on its range of the pool; the seeded two-level trace below then runs over its records, in place
         const NtrBlasRange& wr = m_ranges[m_world];
-        const int32_t anyHit = rays.getNeedClosestHit() ? 0 : 1;
-        const NtrRay* d_rays = (const NtrRay*)rays.getRayBuffer().getCudaPtr();
-        NtrRayResult* d_results = (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr();
-        float worldSeconds = 0.0f;
         rc = ntr_trace_bvh(m_worldKernel.c_str(), numRays, anyHit, d_rays, d_results, (const U8*)m_poolNodes.getCudaPtr() + wr.nodesOffset,
                            wr.nodesBytes, (const U8*)m_poolTriWoop.getCudaPtr() + wr.triWoopOffset, wr.triWoopBytes,
                            (const int32_t*)m_poolTriIndex.getCudaPtr() + wr.triWoopOffset / 16, BVHLayout_Compact, 0u, NULL, &worldSeconds);
         if (rc != NTR_OK) fail("CudaInstancedBVH: the world's trace: %s", ntr_last_error());
-        NtrInstanceVisibility vis;
-        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
-        vis.d_rayMasks = NULL;
-        vis.rayMask = rayMask;
-        vis.pad = 0;
-        if (m_traceWide && isWide() && m_traceWideFast)
-            rc = ntr_trace_instanced_wide_fast(numRays, anyHit, d_rays, d_results, m_numInstances, d_results,
-                                               (int32_t*)instanceIDs.getMutableCudaPtr(), m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL,
-                                               m_wideResult.nodesBytes, m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances,
-                                               m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(),
-                                               m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentWideFastFlags(),
-                                               &seconds, NULL);
-        else if (m_traceWide && isWide())
-            rc = ntr_trace_instanced_wide_seeded(numRays, anyHit, d_rays, d_results, m_numInstances, d_results,
-                                                 (int32_t*)instanceIDs.getMutableCudaPtr(), m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL,
-                                                 m_wideResult.nodesBytes, m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances,
-                                                 m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(),
-                                                 m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
-        else if (m_traceFast)
-            rc = ntr_trace_instanced_fast(numRays, anyHit, d_rays, d_results, m_numInstances, d_results, (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                          m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
-                                          m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                          (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentFastFlags(), &seconds, NULL);
-        else
-            rc = ntr_trace_instanced_seeded(numRays, anyHit, d_rays, d_results, m_numInstances, d_results, (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                            m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
-                                            m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                            (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
-        seconds += worldSeconds;
-    } else if (m_traceWide && isWide()) {
-        NtrInstanceVisibility vis;
-        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
-        vis.d_rayMasks = NULL;
-        vis.rayMask = rayMask;
-        vis.pad = 0;
-        if (m_traceWideFast)
-            rc = ntr_trace_instanced_wide_fast(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(), NULL, -1,
-                                               (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                               m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes,
-                                               m_result.rootLink, m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(),
-                                               m_widePoolResult.nodesBytes, m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                               (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentWideFastFlags(), &seconds, NULL);
-        else
-            rc = ntr_trace_instanced_wide(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
-                                          (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                          m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL, m_wideResult.nodesBytes, m_result.rootLink,
-                                          m_wideRecords.getCudaPtr(), m_numInstances, m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
-                                          m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis,
-                                          &seconds, NULL);
-    } else if (m_traceFast) {
-        NtrInstanceVisibility vis;
-        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
-        vis.d_rayMasks = NULL;
-        vis.rayMask = rayMask;
-        vis.pad = 0;
-        rc = ntr_trace_instanced_fast(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(), NULL, -1,
-                                      (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                      m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
-                                      m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                      (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, currentFastFlags(), &seconds, NULL);
-    } else if (!masks && rayMask == 0xFFFFFFFFu) {
-        rc = ntr_trace_instanced(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
-                                 (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                 m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
-                                 m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                 (const int32_t*)m_poolTriIndex.getCudaPtr(), &seconds, NULL);
-    } else {
-        NtrInstanceVisibility vis;
-        vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
-        vis.d_rayMasks = NULL;
-        vis.rayMask = rayMask;
-        vis.pad = 0;
-        rc = ntr_trace_instanced_masked(numRays, rays.getNeedClosestHit() ? 0 : 1, (const NtrRay*)rays.getRayBuffer().getCudaPtr(),
-                                        (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr(), (int32_t*)instanceIDs.getMutableCudaPtr(),
-                                        m_tlasNodes.getCudaPtr(), m_result.nodesBytes, m_result.rootLink, m_records.getCudaPtr(), m_numInstances,
-                                        m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_poolTriWoop.getCudaPtr(), m_poolTriWoop.getSize(),
-                                        (const int32_t*)m_poolTriIndex.getCudaPtr(), &vis, &seconds, NULL);
     }
+    const NtrRayResult* d_seed = world ? d_results : NULL;
+    const int32_t seedInstance = world ? m_numInstances : -1;
+    NtrInstanceVisibility vis;
+    vis.d_instanceMasks = masks ? (const uint32_t*)m_instanceMasks.getCudaPtr() : NULL;
+    vis.d_rayMasks = NULL;
+    vis.rayMask = rayMask;
+    vis.pad = 0;
+    // the trees of the state: the 4-wide buffers or the binary ones, over the pool's one set of Woop rows
+    const void* d_tlas = !wide ? m_tlasNodes.getCudaPtr() : m_wideResult.nodesBytes ? m_wideTlasNodes.getCudaPtr() : NULL;
+    const int64_t tlasBytes = wide ? m_wideResult.nodesBytes : m_result.nodesBytes;
+    const void* d_records = wide ? m_wideRecords.getCudaPtr() : m_records.getCudaPtr();
+    const void* d_nodes = wide ? m_widePoolNodes.getCudaPtr() : m_poolNodes.getCudaPtr();
+    const int64_t nodesBytes = wide ? m_widePoolResult.nodesBytes : m_poolNodes.getSize();
+    const void* d_woop = m_poolTriWoop.getCudaPtr();
+    const int64_t woopBytes = m_poolTriWoop.getSize();
+    const int32_t* d_index = (const int32_t*)m_poolTriIndex.getCudaPtr();
+    if (wide && m_traceWideFast)
+        rc = ntr_trace_instanced_wide_fast(numRays, anyHit, d_rays, d_seed, seedInstance, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink,
+                                           d_records, m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis,
+                                           currentWideFastFlags(), &seconds, NULL);
+    else if (wide && world)
+        rc = ntr_trace_instanced_wide_seeded(numRays, anyHit, d_rays, d_seed, seedInstance, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink,
+                                             d_records, m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &seconds, NULL);
+    else if (wide)
+        rc = ntr_trace_instanced_wide(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records, m_numInstances,
+                                      d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &seconds, NULL);
+    else if (m_traceFast)
+        rc = ntr_trace_instanced_fast(numRays, anyHit, d_rays, d_seed, seedInstance, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink,
+                                      d_records, m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, currentFastFlags(),
+                                      &seconds, NULL);
+    else if (world)
+        rc = ntr_trace_instanced_seeded(numRays, anyHit, d_rays, d_seed, seedInstance, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink,
+                                        d_records, m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &seconds, NULL);
+    else if (!masks && rayMask == 0xFFFFFFFFu)
+        rc = ntr_trace_instanced(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records, m_numInstances, d_nodes,
+                                 nodesBytes, d_woop, woopBytes, d_index, &seconds, NULL);
+    else
+        rc = ntr_trace_instanced_masked(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records, m_numInstances,
+                                        d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &seconds, NULL);
+    seconds += worldSeconds;
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     return seconds;
 }
