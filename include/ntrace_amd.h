@@ -830,6 +830,55 @@ NTR_API int ntr_tlas_refit(int32_t numInstances, const NtrInstance* d_instances,
 /* Bytes the TLAS refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_tlas_refit_scratch_bytes(int64_t* bytes);
 
+/* Instance update: the NtrInstance array from a hierarchy of transforms, composed and inverted on the device in one launch
+ * (csrc/instances_update_kernels.hip), and its restatement on the host (csrc/instances_update_host.cpp).  It is the
+ * device form of what a caller otherwise does on the host -- N calls of ntr_instance_invert and an upload of 112 B x N -- and the step
+ * that makes the instanced frame loop (ntr_bvh_refit_batch -> instances -> ntr_tlas_refit -> trace) capturable as a whole; flattening
+ * a hierarchy is also how "instances of instances" reach the two-level trace.  EXTENSION without a reference counterpart: the rule is
+ * the numpy spec tests/np_instance_update.py, which both forms equal byte for byte.
+ *   nodes       numNodes transforms: nodeLocal, 3x4 row-major binary32 (12 floats each), and nodeParent, -1 for a root (NULL: every
+ *               node is a root).  The order of the nodes is free: a parent may come after its child.
+ *   instances   instanceNode[i] names instance i's node (NULL: instance i uses node i, which needs numNodes >= numInstances);
+ *               blas[i] is copied through, reserved is zero
+ *   chain       from the instance's node up to a root: at most NTR_INSTANCE_MAX_CHAIN transforms
+ *   fold        from the root down, in binary64 without contraction: acc = local[root]; acc = acc o local[k] for every node below,
+ *               W[r][c] = (P[r][0] L[0][c] + P[r][1] L[1][c]) + P[r][2] L[2][c] and
+ *               W[r][3] = ((P[r][0] L[0][3] + P[r][1] L[1][3]) + P[r][2] L[2][3]) + P[r][3]; objectToWorld is acc rounded to binary32
+ *               once; worldToObject is ntr_instance_invert(objectToWorld) bit for bit.  One node per instance and no parents gives
+ *               exactly the array a loop over ntr_instance_invert makes.
+ *   errors      per instance.  NTR_INSTANCE_ERR_CHAIN: a node index outside [0, numNodes), a parent outside [-1, numNodes) or a
+ *               chain of more than 16 transforms (a cycle); both matrices of the instance are twelve +0.
+ *               NTR_INSTANCE_ERR_SINGULAR: a zero or non-finite determinant; objectToWorld as rounded, worldToObject twelve +0.
+ *   status      four words: the OR of the bits; the lowest bad instance index, 0xFFFFFFFF if none; the number of bad instances; zero
+ * ntr_instances_update: one thread per instance, which walks its own chain; a shared ancestor is recomputed by every instance below
+ *   it, so there is one launch, no scratch and one association order.  d_status (16 bytes, 16-byte aligned) is reset on `stream` ahead
+ *   of the kernel.  With result == NULL the call is asynchronous on `stream` and capturable from the first call on: it allocates nothing
+ *   and keeps nothing on the host.  With result != NULL it blocks, reads the status back and returns NTR_ERR_INVALID naming the first
+ *   bad instance when a bit is set, *result filled all the same.  A bad index is never followed: nothing outside the arrays is read.
+ *   d_nodeLocal and d_instances must be 16-byte aligned.  An array that is written to the NtrInstance array of a scene must not be
+ *   traced through a bad instance: read the status first (ntr_instances_status_read blocks on `stream`).
+ * ntr_instances_update_host: the same rule over host arrays, no device; NTR_ERR_INVALID naming the first bad instance when
+ *   status[0] != 0, out and status filled all the same.
+ * NTR_ERR_INVALID before anything is touched: a null required pointer, numInstances < 1, numNodes < 1, instanceNode == NULL with
+ *   numNodes < numInstances, misaligned device buffers, a captured call with a result.  Without a device, after these checks, the
+ *   device calls return NTR_ERR_NO_DEVICE / NTR_ERR_HIP. */
+#define NTR_INSTANCE_MAX_CHAIN 16
+#define NTR_INSTANCE_ERR_SINGULAR 1u
+#define NTR_INSTANCE_ERR_CHAIN 2u
+typedef struct NtrInstancesUpdateResult {
+    int32_t  numInstances, numNodes;
+    uint32_t statusBits, firstBad, numBad, pad;   /* the status words 0..2 */
+    float    seconds, updateMs;                   /* host wall clock of the call; GPU event time of the reset and the kernel */
+} NtrInstancesUpdateResult;
+NTR_API int ntr_instances_update(int32_t numNodes, const float* d_nodeLocal, const int32_t* d_nodeParent /* may be NULL */,
+                                 int32_t numInstances, const int32_t* d_instanceNode /* may be NULL */, const int32_t* d_blas,
+                                 NtrInstance* d_instances, uint32_t* d_status /* 16 bytes */,
+                                 NtrInstancesUpdateResult* result /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_instances_status_read(const uint32_t* d_status, uint32_t status[4], void* stream);
+NTR_API int ntr_instances_update_host(int32_t numNodes, const float* nodeLocal, const int32_t* nodeParent /* may be NULL */,
+                                      int32_t numInstances, const int32_t* instanceNode /* may be NULL */, const int32_t* blas,
+                                      NtrInstance* out, uint32_t status[4]);
+
 /* Many PLOC builds in one pass: every mesh of a batch becomes one BLAS of a pool, all of them in the same launches
  * (csrc/bvh_ploc_batch_kernels.hip; it stands here, not beside ntr_ploc_build, because it fills NtrBlasRange).  ntr_ploc_build is a
  * chain of some hundred launches and a read-back per four rounds whatever the mesh's size; a scene of a thousand small meshes pays that

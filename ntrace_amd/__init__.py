@@ -37,7 +37,9 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     instanced_wide_validate, trace_instanced_wide_fast, trace_instanced_wide_fast_stats,
                     trace_instanced_seeded, trace_instanced_seeded_stats, trace_instanced_wide_seeded, trace_instanced_wide_seeded_stats,
                     WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
-                    tlas_wide_refit_scratch_bytes)
+                    tlas_wide_refit_scratch_bytes,
+                    InstancesUpdateResult, instances_update, instances_status_read, instances_update_host, INSTANCE_MAX_CHAIN,
+                    INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -70,4 +72,6 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "instanced_wide_validate", "trace_instanced_wide_fast", "trace_instanced_wide_fast_stats",
            "trace_instanced_seeded", "trace_instanced_seeded_stats", "trace_instanced_wide_seeded", "trace_instanced_wide_seeded_stats",
            "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",
-           "tlas_wide_refit_scratch_bytes"]
+           "tlas_wide_refit_scratch_bytes",
+           "InstancesUpdateResult", "instances_update", "instances_status_read", "instances_update_host", "INSTANCE_MAX_CHAIN",
+           "INSTANCE_ERR_SINGULAR", "INSTANCE_ERR_CHAIN"]

@@ -241,6 +241,14 @@ class TlasRefitResult(C.Structure):
         return {k: (list(getattr(self, k)) if k.startswith("scene") else getattr(self, k)) for k, _ in self._fields_ if not k.startswith("pad")}
 
 
+class InstancesUpdateResult(C.Structure):
+    _fields_ = [("numInstances", C.c_int32), ("numNodes", C.c_int32), ("statusBits", C.c_uint32), ("firstBad", C.c_uint32),
+                ("numBad", C.c_uint32), ("pad", C.c_uint32), ("seconds", C.c_float), ("updateMs", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class BvhWideResult(C.Structure):
     _fields_ = [("nodesBytes", C.c_int64), ("numNodes", C.c_int32), ("counts", C.c_int32 * 3), ("numLeafLinks", C.c_int32),
                 ("height", C.c_int32), ("stackBound", C.c_int32), ("seconds", C.c_float)]
@@ -489,6 +497,9 @@ SYMBOLS = [
     ("ntr_tlas_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
     ("ntr_tlas_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_instances_update", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(InstancesUpdateResult), _vp]),
+    ("ntr_instances_status_read", C.c_int, [_vp, C.POINTER(_u32 * 4), _vp]),
+    ("ntr_instances_update_host", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(_u32 * 4)]),
     ("ntr_trace_instanced", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, C.POINTER(C.c_float), _vp]),
     ("ntr_trace_instanced_masked", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                              C.POINTER(InstanceVisibility), C.POINTER(C.c_float), _vp]),
@@ -1193,6 +1204,53 @@ def tlas_refit_scratch_bytes():
     v = _i64(0)
     _check(lib().ntr_tlas_refit_scratch_bytes(C.byref(v)))
     return int(v.value)
+
+
+INSTANCE_MAX_CHAIN = 16
+INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN = 1, 2
+
+
+def instances_update(num_nodes, d_node_local, d_node_parent, num_instances, d_instance_node, d_blas, d_instances, d_status, stream=0,
+                     blocking=True):
+    """ntr_instances_update: the NtrInstance array from a hierarchy of transforms, composed and inverted on the device in one launch (an
+    extension; the rule is tests/np_instance_update.py).  d_node_parent 0: every node is a root; d_instance_node 0: instance i uses node
+    i.  d_status: 16 bytes, reset ahead of the kernel.  blocking=True returns an InstancesUpdateResult; blocking=False passes result =
+    NULL: asynchronous on `stream` (capturable from the first call on) and returns None.  An NtrError raised after the device work (a
+    bad chain, a singular transform) carries .result, filled."""
+    res = InstancesUpdateResult() if blocking else None
+    try:
+        _check(lib().ntr_instances_update(int(num_nodes), _vp(d_node_local), _vp(d_node_parent), int(num_instances), _vp(d_instance_node),
+                                          _vp(d_blas), _vp(d_instances), _vp(d_status), C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def instances_status_read(d_status, stream=0):
+    """ntr_instances_status_read -> [bits, lowest bad instance (0xFFFFFFFF: none), bad instances, 0].  Blocks on `stream`."""
+    st = (_u32 * 4)()
+    _check(lib().ntr_instances_status_read(_vp(d_status), C.byref(st), _vp(stream)))
+    return [int(x) for x in st]
+
+
+def instances_update_host(node_local, node_parent, num_instances, instance_node, blas):
+    """ntr_instances_update_host (no device): -> (INSTANCE_DTYPE array, status: 4 uint32).  node_parent None: every node is a root;
+    instance_node None: instance i uses node i.  An NtrError for a bad instance carries .instances and .status, filled."""
+    local = np.ascontiguousarray(np.asarray(node_local, np.float32).reshape(-1, 12))
+    parent = None if node_parent is None else np.ascontiguousarray(node_parent, np.int32).reshape(local.shape[0])
+    node = None if instance_node is None else np.ascontiguousarray(instance_node, np.int32).reshape(int(num_instances))
+    blas = np.ascontiguousarray(blas, np.int32).reshape(max(int(num_instances), 0))
+    out = np.zeros(max(int(num_instances), 0), INSTANCE_DTYPE)
+    st = (_u32 * 4)()
+    try:
+        _check(lib().ntr_instances_update_host(local.shape[0], local.ctypes.data, None if parent is None else parent.ctypes.data,
+                                               int(num_instances), None if node is None else node.ctypes.data, blas.ctypes.data,
+                                               out.ctypes.data, C.byref(st)))
+    except NtrError as e:
+        e.instances, e.status = out, np.array(list(st), np.uint32)
+        raise
+    return out, np.array(list(st), np.uint32)
 
 
 _ABSENT = object()   # an argument that an entry point does not have (None is a value: NULL)

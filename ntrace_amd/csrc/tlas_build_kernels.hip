@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "ntr_internal.h"
+#include "instance_math.h"
 #include "instanced_bvh.h"
 #include "level_build.h"
 #include "ploc_rounds.h"
@@ -285,20 +286,9 @@ int ntr_instance_invert(const float objectToWorld[12], float worldToObject[12])
 {
     const char* fn = "ntr_instance_invert";
     if (!objectToWorld || !worldToObject) return set_error(NTR_ERR_INVALID, "%s: null", fn);
-    const float* f = objectToWorld;
     // binary64, every product rounded before the sum that uses it (the library is compiled without contraction); np_instanced.invert
-    const double m00 = f[0], m01 = f[1], m02 = f[2], t0 = f[3], m10 = f[4], m11 = f[5], m12 = f[6], t1 = f[7], m20 = f[8], m21 = f[9],
-                 m22 = f[10], t2 = f[11];
-    const double c00 = m11 * m22 - m12 * m21, c01 = m12 * m20 - m10 * m22, c02 = m10 * m21 - m11 * m20;
-    const double det = (m00 * c00 + m01 * c01) + m02 * c02;
-    if (!std::isfinite(det) || det == 0.0) return set_error(NTR_ERR_INVALID, "%s: the transform's determinant is zero or not finite", fn);
-    const double inv[3][3] = {{c00 / det, (m02 * m21 - m01 * m22) / det, (m01 * m12 - m02 * m11) / det},
-                              {c01 / det, (m00 * m22 - m02 * m20) / det, (m02 * m10 - m00 * m12) / det},
-                              {c02 / det, (m01 * m20 - m00 * m21) / det, (m00 * m11 - m01 * m10) / det}};
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) worldToObject[4 * r + c] = (float)inv[r][c];
-        worldToObject[4 * r + 3] = (float)-((inv[r][0] * t0 + inv[r][1] * t1) + inv[r][2] * t2);
-    }
+    if (!instance_invert(objectToWorld, worldToObject))
+        return set_error(NTR_ERR_INVALID, "%s: the transform's determinant is zero or not finite", fn);
     return NTR_OK;
 }
 

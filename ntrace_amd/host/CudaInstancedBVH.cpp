@@ -23,6 +23,7 @@ CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstan
     std::memset(&m_refitResult, 0, sizeof(m_refitResult));
     std::memset(&m_optimizeResult, 0, sizeof(m_optimizeResult));
     std::memset(&m_tlasRefitResult, 0, sizeof(m_tlasRefitResult));
+    std::memset(&m_instancesUpdateResult, 0, sizeof(m_instancesUpdateResult));
 }
 
 S32 CudaInstancedBVH::addBLAS(CudaBVH& bvh)
@@ -183,6 +184,41 @@ void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32
     m_numInstances = num;
     m_built = false;
     writeWorldRecord();
+}
+
+void CudaInstancedBVH::setInstancesDevice(S32 numNodes, Buffer& nodeLocal, Buffer* nodeParent, S32 num, Buffer* instanceNode, Buffer& blas, bool check)
+{
+    if (num < 1 || numNodes < 1) fail("CudaInstancedBVH: no instances");
+    if (!instanceNode && numNodes < num) fail("CudaInstancedBVH: without instanceNode instance i uses node i: %d nodes for %d instances", numNodes, num);
+    if (nodeLocal.getSize() < (S64)numNodes * 48 || (nodeParent && nodeParent->getSize() < (S64)numNodes * 4) ||
+        (instanceNode && instanceNode->getSize() < (S64)num * 4) || blas.getSize() < (S64)num * 4)
+        fail("CudaInstancedBVH: a transform or index buffer is smaller than its count");
+    const S32 total = num + (m_world >= 0 ? 1 : 0);  // a world's record lies behind the instances'
+    m_instances.resizeDiscard((S64)total * sizeof(NtrInstance));
+    m_instanceStatus.resizeDiscard(4 * sizeof(U32));
+    std::memset(&m_instancesUpdateResult, 0, sizeof(m_instancesUpdateResult));
+    const int rc = ntr_instances_update(numNodes, (const float*)nodeLocal.getCudaPtr(), nodeParent ? (const int32_t*)nodeParent->getCudaPtr() : NULL,
+                                        num, instanceNode ? (const int32_t*)instanceNode->getCudaPtr() : NULL, (const int32_t*)blas.getCudaPtr(),
+                                        (NtrInstance*)m_instances.getMutableCudaPtrDiscard(), (uint32_t*)m_instanceStatus.getMutableCudaPtrDiscard(),
+                                        check ? &m_instancesUpdateResult : NULL, NULL);
+    // the instance array has been rewritten whatever the status says: the state follows before a bad instance is reported
+    if (num != m_numInstances) {
+        m_topology = m_wideTopology = false;         // as setInstances: an unchanged count keeps the topology and the masks
+        m_instanceMasks.resizeDiscard(0);
+    }
+    m_numInstances = num;
+    m_built = false;
+    const std::string message = rc != NTR_OK ? ntr_last_error() : "";
+    if (rc == NTR_OK || m_instancesUpdateResult.statusBits != 0) writeWorldRecord();   // (the kernel ran: the array is the scene's)
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", message.c_str());
+}
+
+void CudaInstancedBVH::getInstanceStatus(U32 out[4])
+{
+    if (m_instanceStatus.getSize() != 4 * (S64)sizeof(U32)) fail("CudaInstancedBVH: no instance status: call setInstancesDevice first");
+    uint32_t st[4];
+    if (ntr_instances_status_read((const uint32_t*)m_instanceStatus.getCudaPtr(), st, NULL) != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    for (int k = 0; k < 4; k++) out[k] = st[k];
 }
 
 void CudaInstancedBVH::writeWorldRecord(void)

@@ -11,13 +11,23 @@
 //                 brings the TLAS to the new node-0 boxes; nothing else is needed
 //   setInstances  objectToWorld per instance; worldToObject by ntr_instance_invert.  With an unchanged count the TLAS built before stays
 //                 usable for refit()
+//   setInstancesDevice   setInstances for transforms that live on the device, and for a hierarchy of them: numNodes
+//                 local transforms (48 bytes each) with an optional parent per node, and per instance an optional node index and a
+//                 BLAS index, all in device buffers.  ntr_instances_update composes every instance's chain from its root down, inverts
+//                 and writes the instance array in one launch; no matrix crosses to the host.  The state follows setInstances exactly:
+//                 isBuilt() falls, an unchanged count keeps the topology for refit() and the masks, a world's record is kept.
+//                 check == true reads the status back and fails naming the first bad instance (a singular composition, a bad index,
+//                 a chain of more than 16); check == false reads nothing back -- with a world set its one record is still copied from
+//                 the host -- and leaves the status in a device buffer that getInstanceStatus reads: the caller then answers for not
+//                 tracing through a bad instance
 //   build         the TLAS and the instance records, from scratch: a blocking chain of launches (ntr_tlas_build)
 //   refit         keeps the topology of the last build() and rewrites the records and every box from the current instances and the
 //                 pool's current node-0 boxes in two launches (ntr_tlas_refit).  Needs a build() with the same instance
 //                 count; a changed count, addBLAS and buildBLASes invalidate it as they invalidate build().  The frame loop of a moving,
 //                 deforming scene is refitBLASes -> optimizeBLASes every so many frames -> setInstances -> refit -> traceBatch, with
 //                 build() every so many frames: a refit keeps the tree the old positions suggested, and its boxes overlap more the
-//                 further the instances travel
+//                 further the instances travel.  setInstancesDevice stands in for setInstances wherever the transforms are on the
+//                 device already: the loop then has no step that computes on the host
 //   optimizeBLASes   restructures the selected BLASes' treelets in place by ntr_bvh_optimize_batch, all in one pass: the
 //                 repair of BLASes whose refitted trees have degraded, short of buildBLASes (which replaces every BLAS and drops the
 //                 world).  It needs no mesh, so addBLAS trees may be selected.  Leaves, rows and triIndex stay.  isBuilt(), the binary
@@ -42,8 +52,8 @@
 //                 the topology of the last pool widening.  The TLAS flags fall as after refitBLASes
 //   refitWide     refit(), then the wide TLAS and the wide records in place by ntr_tlas_wide_refit.  Needs a build() and a widen() with
 //                 the current instance count since, and a current wide pool; afterwards isBuilt() && isWide().  The frame loop of a
-//                 moving, deforming scene on the wide path is refitBLASesWide -> setInstances -> refitWide -> traceBatch, with
-//                 build() + widen() every so many frames; none of its steps reads anything back but the results
+//                 moving, deforming scene on the wide path is refitBLASesWide -> setInstances (or setInstancesDevice) -> refitWide ->
+//                 traceBatch, with build() + widen() every so many frames; none of its steps reads anything back but the results
 //   setTraceWide  traceBatch takes the wide path (ntr_trace_instanced_wide) when isWide() and this was set; default false, so nothing
 //                 changes for existing callers.  The records may differ from the binary path's in rays within rounding of a box
 //                 surface (the spec tests/np_instanced_wide.py states the limit)
@@ -75,8 +85,8 @@
 //                 validates ahead of the trace, on its stream, once
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
-//   refitBLASes -> optimizeBLASes every so many frames -> setInstances -> refit -> InstancedRenderer::beginFrame -> nextBatch /
-//   traceBatch / updateResult per batch
+//   refitBLASes -> optimizeBLASes every so many frames -> setInstances (setInstancesDevice for transforms on the device) -> refit ->
+//   InstancedRenderer::beginFrame -> nextBatch / traceBatch / updateResult per batch
 // and with a static world set (setWorld, once) nothing of that loop changes: the world BLAS is left out of refitBLASes' selection, the
 // instances move, and every traceBatch of the frame is the world's single-level trace followed by the seeded two-level trace.
 #pragma once
@@ -107,6 +117,11 @@ public:
     // out[i]: ntr_bvh_sah_cost of the i-th selected BLAS (its seconds is 0); a BLAS may be named more than once.
     void measureBLASes(std::vector<NtrBvhSahResult>& out, const S32* blas = NULL, S32 num = -1);
     void setInstances(S32 num, const F32* objectToWorld /* num x 12 */, const S32* blas);
+    // nodeLocal: numNodes x 12 F32; nodeParent: numNodes S32, -1 a root (NULL: all roots); instanceNode: num S32 (NULL: instance i uses
+    // node i); blas: num S32.  All device-side inputs of ntr_instances_update.
+    void setInstancesDevice(S32 numNodes, Buffer& nodeLocal, Buffer* nodeParent, S32 num, Buffer* instanceNode, Buffer& blas, bool check = true);
+    void getInstanceStatus(U32 out[4]);                                          // the last setInstancesDevice's status words; blocks
+    const NtrInstancesUpdateResult& getInstancesUpdateResult(void) const { return m_instancesUpdateResult; }   // of the last checked setInstancesDevice (zero otherwise)
     void build(S32 radius = DefaultRadius);
     void refit(void);
     void setInstanceMasks(const U32* masks /* getNumInstances() words; NULL: all visible */);
@@ -182,6 +197,8 @@ private:
     NtrBvhOptimizeBatchResult m_optimizeResult;
     void          selectRanges(const S32* blas, S32 num, std::vector<NtrBlasRange>& out, const char* what) const;
     NtrTlasRefitResult m_tlasRefitResult;
+    Buffer        m_instanceStatus;                                              // setInstancesDevice's four status words, on the device
+    NtrInstancesUpdateResult m_instancesUpdateResult;
     // the wide path (widen): a second node buffer beside the pool, a wide TLAS and wide records
     std::vector<NtrWideBlasRange> m_wideRanges;
     Buffer        m_widePoolNodes, m_wideTlasNodes, m_wideRecords;
