@@ -879,6 +879,89 @@ NTR_API int ntr_instances_update_host(int32_t numNodes, const float* nodeLocal, 
                                       int32_t numInstances, const int32_t* instanceNode /* may be NULL */, const int32_t* blas,
                                       NtrInstance* out, uint32_t status[4]);
 
+/* Motion blur in instanced scenes: a time-sampled two-level trace (csrc/tlas_motion_refit_kernels.hip,
+ * csrc/trace_instanced_motion_kernels.hip).  Every other piece of the instanced path poses the scene at one instant; here
+ * each ray carries a time, and a moving instance is posed at that time when the ray enters it.  EXTENSION without a reference
+ * counterpart: the rule is the numpy spec tests/np_instanced_motion.py, which the refit equals byte for byte and the trace bit for bit
+ * in all four result words, the instance id and every counter.
+ *   keys        two NtrInstance arrays of numInstances entries: key 0 is the shutter's opening, key 1 its close (two
+ *               ntr_instances_update calls give exactly these).  The blas index and worldToObject are taken from key 0; of key 1 only
+ *               objectToWorld is read.  Instance i is MOVING iff any of the twelve objectToWorld words differs bitwise between the keys.
+ *   time        ray r has t_r = d_rayTimes[r], or the launch's scalar `time`; clamped by t > 0 ? (t < 1 ? t : 1) : 0, so a NaN gives 0
+ *   pose        for a moving instance, with u = 1.0f - t, each component of M(t) is a where t == 0 or a and b are the same word, b
+ *               where t == 1, otherwise u * a + t * b in binary32 with both products rounded before the sum.  M(0) and M(1) are the
+ *               keys bit for bit, and a component that does not move never changes.  worldToObject(t) is ntr_instance_invert's
+ *               function of M(t): binary64, each of the 12 results rounded once
+ *   boxes       the leaf box of a moving instance is the union, in the integer order, of its world box (ntr_tlas_refit's) under key 0
+ *               and under key 1: every corner moves on a straight line between its two end positions, up to rounding, so the union
+ *               bounds the sweep; no padding.  A static instance's box and the climb are ntr_tlas_refit's
+ *   records     record i is ntr_tlas_refit's record of key-0 instance i, except that word 15 is 1 for a moving instance, 0 otherwise.
+ *               No kernel but the motion trace reads word 15.  A later plain ntr_tlas_refit (or ntr_tlas_build) writes word 15 = 0 and
+ *               thereby FREEZES the scene at key 0, boxes included
+ *   motion keys beside the records, 128 bytes per instance: words 0..11 objectToWorld of key 0, words 16..27 objectToWorld of key 1,
+ *               every other word zero; written for every instance, static ones and ones with a bad blas index too
+ *   entering    the trace is ntr_trace_instanced_masked's with one change to the step "top level, link ~i"; the checks run in this
+ *               order: index in range; masks; room for the marker; then, if word 15 of the fetched record is non-zero, the two keys
+ *               are read from the motion key buffer at 128 * i (range checked: beyond min(motionKeysBytes, 0xFFFFFF00) a read returns
+ *               zeros), M(t_r) is formed and inverted -- a zero or non-finite determinant makes the step a pop: no marker, no
+ *               transform, nothing else touched, counted as numSingular and as neither an entry nor a masked step; then the marker is
+ *               pushed and the ray transformed by worldToObject(t_r).  A static instance's step is the masked kernel's, from the
+ *               record alone
+ *   bytes       the masked formula plus 128 (numMovingEntries + numSingular), plus 4 numRays when per-ray times are given
+ * ntr_tlas_motion_refit: ntr_tlas_refit over d_instances0 with the three changes above (swept leaf boxes, word 15, the motion key
+ *   buffer), and ntr_tlas_refit's contract in every respect not named here: result == NULL is asynchronous on `stream` and capturable
+ *   (two launches, one for N == 1, no read-back, no memset), the tolerant walk and its error bits, the cached range table and its
+ *   rule for captured calls, one call per device at a time.  Its scratch is a per-device grow-only pool of its own
+ *   (ntr_tlas_motion_refit_scratch_bytes) that ntr_lbvh_release_workspace returns.  It also requires d_instances1 non-null and 16-byte
+ *   aligned, d_motionKeys non-null and 16-byte aligned, motionKeysCapacity >= 128 * numInstances.  numMoving counts the moving
+ *   instances among all numInstances.  The topology is whatever ntr_tlas_build made at key 0.
+ * ntr_trace_instanced_motion: ntr_trace_instanced_masked's arguments plus `motion`.  With motion == NULL the call IS
+ *   ntr_trace_instanced_masked -- the same launch, and its refusals name that function.  seconds == NULL is asynchronous on `stream` and
+ *   capturable; the times, the keys and the records are read by the launch, so a replay sees what is there at replay time.
+ * ntr_trace_instanced_motion_stats: the same records through the instrumented kernel, plus ntr_trace_instanced_stats's counters and the
+ *   two of NtrInstancedMotionStats.  It blocks and is refused on a capturing stream.  With motion == NULL it is
+ *   ntr_trace_instanced_stats and the motion counters are zero.
+ * Errors: NTR_ERR_INVALID before any device work for everything ntr_trace_instanced_masked refuses, in its words and order, then: a
+ *   d_rayTimes that is not 4-byte aligned, a d_motionKeys that is null or not 16-byte aligned, motionKeysBytes < 128 * numInstances;
+ *   a null stats or motionStats.  numRays == 0 returns NTR_OK with the stats zeroed; without a device, after these checks,
+ *   NTR_ERR_NO_DEVICE / NTR_ERR_HIP.
+ * Not combinable with the 4-wide trees, the seeded / world form or FAST; ntr_instanced_hit_attributes gives the normal at key 0. */
+typedef struct NtrTlasMotionRefitResult {
+    NtrTlasRefitResult refit;           /* as ntr_tlas_refit reports it */
+    int32_t numMoving, pad;             /* instances whose objectToWorld differs between the keys */
+} NtrTlasMotionRefitResult;
+typedef struct NtrInstanceMotion {      /* host struct of device pointers */
+    const void*  d_motionKeys;          /* what ntr_tlas_motion_refit wrote: 128 bytes per instance, 16-byte aligned */
+    int64_t      motionKeysBytes;       /* at least 128 * numInstances */
+    const float* d_rayTimes;            /* numRays floats, or NULL: every ray has `time` */
+    float        time, pad;
+} NtrInstanceMotion;
+typedef struct NtrInstancedMotionStats {
+    int64_t numMovingEntries;           /* entering steps that entered a moving instance (counted in numInstanceEntries too) */
+    int64_t numSingular;                /* entering steps popped because M(t) has no inverse */
+} NtrInstancedMotionStats;
+NTR_API int ntr_tlas_motion_refit(int32_t numInstances, const NtrInstance* d_instances0, const NtrInstance* d_instances1, int32_t numBlas,
+                                  const NtrBlasRange* blasRanges, const void* d_poolNodes, int64_t poolNodesBytes, void* d_tlasNodes,
+                                  int64_t tlasNodesBytes, int32_t rootLink, void* d_records, int64_t recordsCapacity, void* d_motionKeys,
+                                  int64_t motionKeysCapacity, float* d_sceneBox /* may be NULL: 6 floats */,
+                                  NtrTlasMotionRefitResult* result /* NULL: asynchronous */, void* stream);
+/* Bytes the motion refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_tlas_motion_refit_scratch_bytes(int64_t* bytes);
+NTR_API int ntr_trace_instanced_motion(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                       const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                       int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                       int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                       const NtrInstanceVisibility* vis /* NULL: no masks */,
+                                       const NtrInstanceMotion* motion /* NULL: ntr_trace_instanced_masked */,
+                                       float* seconds /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_trace_instanced_motion_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                             int32_t* d_instanceIDs, const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink,
+                                             const void* d_records, int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes,
+                                             const void* d_poolTriWoop, int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                             const NtrInstanceVisibility* vis /* may be NULL */,
+                                             const NtrInstanceMotion* motion /* may be NULL */, NtrInstancedTraceStats* stats,
+                                             NtrInstancedMotionStats* motionStats, void* stream);
+
 /* Many PLOC builds in one pass: every mesh of a batch becomes one BLAS of a pool, all of them in the same launches
  * (csrc/bvh_ploc_batch_kernels.hip; it stands here, not beside ntr_ploc_build, because it fills NtrBlasRange).  ntr_ploc_build is a
  * chain of some hundred launches and a read-back per four rounds whatever the mesh's size; a scene of a thousand small meshes pays that

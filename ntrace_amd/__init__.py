@@ -39,7 +39,9 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     WideRefitEntry, WideRefitResult, pool_wide_refit, pool_wide_refit_scratch_bytes, tlas_wide_refit,
                     tlas_wide_refit_scratch_bytes,
                     InstancesUpdateResult, instances_update, instances_status_read, instances_update_host, INSTANCE_MAX_CHAIN,
-                    INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN)
+                    INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN,
+                    TlasMotionRefitResult, InstanceMotion, InstancedMotionStats, tlas_motion_refit, tlas_motion_refit_scratch_bytes,
+                    trace_instanced_motion, trace_instanced_motion_stats)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -74,4 +76,6 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "WideRefitEntry", "WideRefitResult", "pool_wide_refit", "pool_wide_refit_scratch_bytes", "tlas_wide_refit",
            "tlas_wide_refit_scratch_bytes",
            "InstancesUpdateResult", "instances_update", "instances_status_read", "instances_update_host", "INSTANCE_MAX_CHAIN",
-           "INSTANCE_ERR_SINGULAR", "INSTANCE_ERR_CHAIN"]
+           "INSTANCE_ERR_SINGULAR", "INSTANCE_ERR_CHAIN",
+           "TlasMotionRefitResult", "InstanceMotion", "InstancedMotionStats", "tlas_motion_refit", "tlas_motion_refit_scratch_bytes",
+           "trace_instanced_motion", "trace_instanced_motion_stats"]

@@ -241,6 +241,38 @@ class TlasRefitResult(C.Structure):
         return {k: (list(getattr(self, k)) if k.startswith("scene") else getattr(self, k)) for k, _ in self._fields_ if not k.startswith("pad")}
 
 
+class TlasMotionRefitResult(C.Structure):
+    """NtrTlasMotionRefitResult: ntr_tlas_refit's result and the number of instances that move between the two keys."""
+    _fields_ = [("refit", TlasRefitResult), ("numMoving", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return dict(self.refit.as_dict(), numMoving=int(self.numMoving))
+
+
+class InstanceMotion(C.Structure):
+    """NtrInstanceMotion: the motion key buffer tlas_motion_refit wrote (128 bytes per instance) and the rays' times -- a device array
+    of num_rays floats, or 0: every ray has `time`."""
+    _fields_ = [("d_motionKeys", C.c_void_p), ("motionKeysBytes", C.c_int64), ("d_rayTimes", C.c_void_p), ("time", C.c_float),
+                ("pad", C.c_float)]
+
+    def __init__(self, d_motion_keys=0, motion_keys_bytes=0, d_ray_times=0, time=0.0):
+        super().__init__(int(d_motion_keys) or None, int(motion_keys_bytes), int(d_ray_times) or None, float(time), 0.0)
+
+
+class InstancedMotionStats(C.Structure):
+    """NtrInstancedMotionStats (the rule is tests/np_instanced_motion.py): entering steps that entered a moving instance, and entering
+    steps popped because the instance has no inverse at the ray's time."""
+    _fields_ = [(n, C.c_int64) for n in ("numMovingEntries", "numSingular")]
+
+    def algorithmic_bytes(self, stats, instance_masks=False, ray_masks=False, ray_times=False):
+        """include/ntrace_amd.h: the masked formula of `stats` (an InstancedTraceStats), 128 B per pose, 4 B per ray with per-ray times."""
+        return (stats.algorithmic_bytes(instance_masks, ray_masks) + 128 * (self.numMovingEntries + self.numSingular)
+                + (4 * stats.numRays if ray_times else 0))
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class InstancesUpdateResult(C.Structure):
     _fields_ = [("numInstances", C.c_int32), ("numNodes", C.c_int32), ("statusBits", C.c_uint32), ("firstBad", C.c_uint32),
                 ("numBad", C.c_uint32), ("pad", C.c_uint32), ("seconds", C.c_float), ("updateMs", C.c_float)]
@@ -497,6 +529,14 @@ SYMBOLS = [
     ("ntr_tlas_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
     ("ntr_tlas_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_tlas_motion_refit", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                        C.POINTER(TlasMotionRefitResult), _vp]),
+    ("ntr_tlas_motion_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_trace_instanced_motion", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                             C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion), C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_motion_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                   C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion), C.POINTER(InstancedTraceStats),
+                                                   C.POINTER(InstancedMotionStats), _vp]),
     ("ntr_instances_update", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(InstancesUpdateResult), _vp]),
     ("ntr_instances_status_read", C.c_int, [_vp, C.POINTER(_u32 * 4), _vp]),
     ("ntr_instances_update_host", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(_u32 * 4)]),
@@ -1206,6 +1246,34 @@ def tlas_refit_scratch_bytes():
     return int(v.value)
 
 
+def tlas_motion_refit(num_instances, d_instances0, d_instances1, ranges, d_pool_nodes, pool_nodes_bytes, d_tlas_nodes, tlas_nodes_bytes,
+                      root_link, d_records, records_cap, d_motion_keys, motion_keys_cap, d_scene_box=0, stream=0, blocking=True):
+    """ntr_tlas_motion_refit: tlas_refit over two keys of the instances (shutter open, shutter close): swept leaf boxes, word 15 of a
+    moving instance's record, and the motion key buffer (128 bytes per instance) that trace_instanced_motion reads; the rule is
+    tests/np_instanced_motion.py.  blocking=True returns a TlasMotionRefitResult; blocking=False passes result = NULL: asynchronous on
+    `stream` (capturable) and returns None.  An NtrError raised after the device work carries .result, filled."""
+    if isinstance(ranges, BlasPool):
+        ranges = ranges.ranges
+    arr = (BlasRange * max(len(ranges), 1))(*[BlasRange(*[int(x) for x in r]) for r in ranges])
+    res = TlasMotionRefitResult() if blocking else None
+    try:
+        _check(lib().ntr_tlas_motion_refit(int(num_instances), _vp(d_instances0), _vp(d_instances1), len(ranges), C.cast(arr, _vp),
+                                           _vp(d_pool_nodes), int(pool_nodes_bytes), _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link),
+                                           _vp(d_records), int(records_cap), _vp(d_motion_keys), int(motion_keys_cap), _vp(d_scene_box),
+                                           C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def tlas_motion_refit_scratch_bytes():
+    """ntr_tlas_motion_refit_scratch_bytes: bytes the motion refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_tlas_motion_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
 INSTANCE_MAX_CHAIN = 16
 INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN = 1, 2
 
@@ -1258,9 +1326,9 @@ _ABSENT = object()   # an argument that an entry point does not have (None is a 
 
 def _trace_two_level(name, out, num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
                      num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, seed=_ABSENT,
-                     vis=_ABSENT, d_flags=_ABSENT):
+                     vis=_ABSENT, d_flags=_ABSENT, motion=_ABSENT):
     """The one marshalling of the ntr_trace_instanced* entry points (binary or wide buffers alike).  After the rays `seed`, a
-    (d_seed_results, seed_instance) pair; after the pool `vis` and `d_flags`; then the out-arguments and the stream.  out: True or False
+    (d_seed_results, seed_instance) pair; after the pool `vis`, `d_flags` and `motion`; then the out-arguments and the stream.  out: True or False
     (`timed`: a float -> the seconds, or NULL -> None), or the classes of the stats -> one object of each (alone, or a tuple)."""
     outs = [C.c_float(0.0)] if isinstance(out, bool) else [cls() for cls in out]
     args = [int(num_rays), int(bool(any_hit)), _vp(d_rays)]
@@ -1272,6 +1340,8 @@ def _trace_two_level(name, out, num_rays, any_hit, d_rays, d_results, d_instance
         args.append(C.byref(vis) if vis is not None else None)
     if d_flags is not _ABSENT:
         args.append(_vp(d_flags))
+    if motion is not _ABSENT:
+        args.append(C.byref(motion) if motion is not None else None)
     _check(getattr(lib(), name)(*args, *([None] if out is False else [C.byref(o) for o in outs]), _vp(stream)))
     if isinstance(out, bool):
         return float(outs[0].value) if out else None
@@ -1305,6 +1375,27 @@ def trace_instanced_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, 
     return _trace_two_level("ntr_trace_instanced_stats", (InstancedTraceStats,), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
                             tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
                             d_pool_tri_index, stream, vis=vis)
+
+
+def trace_instanced_motion(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                           num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, motion=None,
+                           stream=0, timed=True):
+    """ntr_trace_instanced_motion: trace_instanced_masked with time-sampled instance transforms (the rule is
+    tests/np_instanced_motion.py).  motion: an InstanceMotion over what tlas_motion_refit wrote, or None (NULL: trace_instanced_masked).
+    timed=False is asynchronous on `stream` (capturable; times, keys and records are read at replay time) and returns None."""
+    return _trace_two_level("ntr_trace_instanced_motion", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
+                            tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                            d_pool_tri_index, stream, vis=vis, motion=motion)
+
+
+def trace_instanced_motion_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                                 num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None,
+                                 motion=None, stream=0):
+    """ntr_trace_instanced_motion_stats: trace_instanced_motion's records through the instrumented kernel ->
+    (InstancedTraceStats, InstancedMotionStats).  Blocks; refused on a capturing stream."""
+    return _trace_two_level("ntr_trace_instanced_motion_stats", (InstancedTraceStats, InstancedMotionStats), num_rays, any_hit, d_rays, d_results,
+                            d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
+                            d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, vis=vis, motion=motion)
 
 
 def instanced_hit_attributes(num_rays, d_results, d_instance_ids, geom, d_out_results=0, d_normals=0, stream=0):

@@ -6,7 +6,11 @@
 //             must read nothing is given that offset
 //   top level Compact nodes whose leaf links are ~i, i an instance; rootLink is 0, or ~0 when the one instance is the whole tree
 //   record i  16 words: 0..11 worldToObject (3x4 row-major), 12 nodesOffset in bytes, 13 triWoopOffset / 16 (rows; triIndex entries
-//             too), 14 nodesBytes, 15 zero
+//             too), 14 nodesBytes, 15 zero -- or, after ntr_tlas_motion_refit (tlas_motion_refit_kernels.hip), 1 for an
+//             instance that moves within the shutter.  Only the motion kernels (trace_instanced_motion_kernels.hip) read word 15: every
+//             other kernel takes words 0..14 and traces the scene at key 0
+//   motion    key entry i, beside the records, 32 words: 0..11 objectToWorld at the shutter's opening (key 0), 16..27 objectToWorld at
+//             its close (key 1), every other word zero.  Written for every instance, moving or not
 //   marker    kExitMarker on the traversal stack, below an instance's entries: a positive word above kSentinel, so neither an inner
 //             link (< kSentinel), nor a leaf link (< 0), nor the sentinel
 #pragma once
@@ -22,7 +26,8 @@ namespace ntr {
 
 constexpr int64_t kPoolMaxBytes = 0xFFFFFF00ll;
 constexpr int kRecordWords = 16, kRecordBytes = 64;
-constexpr int kRecNodesOffset = 12, kRecRowOffset = 13, kRecNodesBytes = 14;
+constexpr int kRecNodesOffset = 12, kRecRowOffset = 13, kRecNodesBytes = 14, kRecMoving = 15;
+constexpr int kMotionKeyBytes = 128, kMotionKey1Bytes = 64;   // a motion key entry, and where key 1 starts in it
 constexpr int kExitMarker = kSentinel + 1;
 static_assert(kRecordBytes == kNodeBytes, "a record is fetched like a node");
 static_assert(kExitMarker > kSentinel, "the marker is neither a link nor the sentinel");

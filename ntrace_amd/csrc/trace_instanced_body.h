@@ -11,6 +11,9 @@
 //   NTR_TI_FAST     1: FAST slab arithmetic from device-resident flags (InstancedFast f and level_nice of
 //                   trace_instanced_nice.h; the rule is tests/np_instanced_fast.py): a per-lane `nice` says that
 //                   the lane's current ray may take FAST on its current level, and the wave votes per iteration on the step's form
+//   NTR_TI_MOTION   1 (optional; undefined means 0): motion blur (InstancedMotion mo; the rule is tests/np_instanced_motion.py):
+//                   the ray carries a time, and the entering step poses an instance whose record has word 15 set at that time -- two
+//                   keys from the motion key buffer, twelve lerps and the binary64 inverse, behind a wave-uniform branch
 // An include and not a function template because the unmasked variant must stay the kernel it was, instruction for instruction
 // (scripts/kernel_isa_diff.sh): with the loop in a __forceinline__ function that the kernels call, hipcc orders its passes differently and
 // allocates other registers, and every such change would have to be measured again.  No include guard: the text is meant
@@ -38,6 +41,13 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
         rayMask = x.rayMasks ? x.rayMasks[valid ? rayIdx : 0] : x.rayMask;
     }
     InstancedLaneStats ls = {0u, 0u, 0u, 0u, 0u, 0u};
+#if NTR_TI_MOTION
+    // the ray's time, clamped so that a NaN gives 0; the key buffer's descriptor is built from kernel arguments only
+    const Rsrc rKeys = make_rsrc(mo.keys, mo.keysBytes);
+    float rayTime = mo.rayTimes ? mo.rayTimes[valid ? rayIdx : 0] : mo.time;
+    rayTime = rayTime > 0.0f ? (rayTime < 1.0f ? rayTime : 1.0f) : 0.0f;
+    unsigned int movingEntries = 0u, singularSteps = 0u;   // (STATS only)
+#endif
 
     RayRegs r;   // the current form: the world ray on the top level, the object ray inside an instance
     {
@@ -162,7 +172,19 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
             } else if (st.sp >= LDS_DEPTH + SPILL_DEPTH) {
                 atomicOr(p.status, NTR_STATUS_STACK_OVERFLOW);   // no room for the marker: the instance is not entered
                 node = stack_pop(st, spill);
-            } else {
+            } else
+#if NTR_TI_MOTION
+            // a record whose word 15 is set names a moving instance: worldToObject(t) replaces the record's rows a, b, c.  The wave
+            // votes, so one that enters only static instances runs the masked kernel's step behind one scalar branch
+            if (__ballot(__float_as_uint(d.w) != 0u) != 0ull && __float_as_uint(d.w) != 0u && !motion_pose(rKeys, idx, rayTime, a, b, c)) {
+                if (STATS) singularSteps++;
+                node = stack_pop(st, spill);         // no inverse at this time: no marker, no transform
+            } else
+#endif
+            {
+#if NTR_TI_MOTION
+                if (STATS) movingEntries += __float_as_uint(d.w) != 0u ? 1u : 0u;
+#endif
                 stack_push(st, spill, kExitMarker, p.status);
                 const float ox = dot4(a, r.ox, r.oy, r.oz, 1.0f), oy = dot4(b, r.ox, r.oy, r.oz, 1.0f), oz = dot4(c, r.ox, r.oy, r.oz, 1.0f);
                 const float dx = dot4(a, r.dx, r.dy, r.dz, 0.0f), dy = dot4(b, r.dx, r.dy, r.dz, 0.0f), dz = dot4(c, r.dx, r.dy, r.dz, 0.0f);
@@ -232,6 +254,10 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
         atomicAdd(&x.stats[6], (unsigned long long)(seedKept || (hitAddr >= 0 && p.triIndex[hitAddr] != -1)));
 #else
         atomicAdd(&x.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
+#endif
+#if NTR_TI_MOTION
+        atomicAdd(&x.stats[12], (unsigned long long)movingEntries);
+        atomicAdd(&x.stats[13], (unsigned long long)singularSteps);
 #endif
 #if NTR_TI_FAST
         if (lane == 0) {   // (lane 0 of a launched wave is a ray)

@@ -1,8 +1,9 @@
-// trace_instanced_launch.h -- host only: the launch of the two-level trace, stated once for its four units:
+// trace_instanced_launch.h -- host only: the launch of the two-level trace, stated once for its five units:
 //   trace_instanced_kernels.hip            ntr_trace_instanced, _masked, _stats, _seeded, _seeded_stats
 //   trace_instanced_fast_kernels.hip       ntr_trace_instanced_fast, _fast_stats
 //   trace_instanced_wide_kernels.hip       ntr_trace_instanced_wide, _wide_stats, _wide_seeded, _wide_seeded_stats
 //   trace_instanced_wide_fast_kernels.hip  ntr_trace_instanced_wide_fast, _wide_fast_stats
+//   trace_instanced_motion_kernels.hip     ntr_trace_instanced_motion, _motion_stats
 // An entry point writes what it was given into a TwoLevelCall, with the few facts in which the units differ, and calls two_level_trace
 // with its unit's launch: the checks, the device state, the bracket (trace_launch.h) and the counters' unpacking are here; the kernels,
 // the fill of their parameters and the choice among them stay with the unit (trace_instanced_kernels.h: why the units are separate).
@@ -61,6 +62,8 @@ struct TwoLevelCall {
     void* stream;
     NtrInstancedTraceStats* stats;      // both NULL, or the instrumented kernel; a FAST unit takes both or neither
     NtrInstancedFastStats* fastStats;
+    const NtrInstanceMotion* motion;    // the motion unit: given; every other unit leaves the two NULL
+    NtrInstancedMotionStats* motionStats;   // with stats, or NULL
 };
 
 // Zeroes the out-arguments and checks the call.  *go: the call is good and has rays to trace (NTR_OK with !*go: numRays == 0, done).
@@ -71,6 +74,7 @@ inline int two_level_check(const TwoLevelCall& c, bool* go)
     if (c.seconds) *c.seconds = 0.0f;
     if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
     if (c.fastStats) memset(c.fastStats, 0, sizeof(*c.fastStats));
+    if (c.motionStats) memset(c.motionStats, 0, sizeof(*c.motionStats));
     if (c.validate && (c.stats != nullptr) != (c.fastStats != nullptr)) return set_error(NTR_ERR_INVALID, "%s: null stats", fn);
     if (c.numRays < 0) return set_error(NTR_ERR_INVALID, "%s: numRays < 0", fn);
     if (c.numRays == 0) return NTR_OK;
@@ -92,6 +96,13 @@ inline int two_level_check(const TwoLevelCall& c, bool* go)
         return set_error(NTR_ERR_INVALID, "%s: the seed records must be 16-byte aligned", fn);
     if (c.validate && (!c.d_flags || (((uintptr_t)c.d_flags) & 15u) != 0))
         return set_error(NTR_ERR_INVALID, "%s: the flags (%s) must be given and 16-byte aligned", fn, c.validate);
+    if (c.motion) {
+        if ((((uintptr_t)c.motion->d_rayTimes) & 3u) != 0) return set_error(NTR_ERR_INVALID, "%s: the ray times must be 4-byte aligned", fn);
+        if (!c.motion->d_motionKeys || (((uintptr_t)c.motion->d_motionKeys) & 15u) != 0)
+            return set_error(NTR_ERR_INVALID, "%s: the motion keys (ntr_tlas_motion_refit) must be given and 16-byte aligned", fn);
+        if (c.motion->motionKeysBytes < (int64_t)kMotionKeyBytes * c.numInstances)
+            return set_error(NTR_ERR_INVALID, "%s: motionKeysBytes below 128 * numInstances", fn);
+    }
     *go = true;
     return NTR_OK;
 }
@@ -120,7 +131,8 @@ bool two_level_fill_visibility(X& x, const TwoLevelCall& c, DeviceState* ds)
     return x.instMasks || x.rayMasks || x.rayMask != 0xFFFFFFFFu;
 }
 
-constexpr int kTwoLevelCounters = 7, kTwoLevelFastCounters = 12;   // the words an instrumented kernel adds to: [0..6], and [8..11] in the FAST units
+// the words an instrumented kernel adds to: [0..6], [8..11] in the FAST units, [12..13] in the motion unit
+constexpr int kTwoLevelCounters = 7, kTwoLevelFastCounters = 12, kTwoLevelMotionCounters = 14;
 
 // The shared path of the entry points.  launch(ds, stream, blocks) fills the unit's parameters and enqueues the kernel that c asks for.
 template <class Launch>
@@ -133,8 +145,8 @@ int two_level_trace(const TwoLevelCall& c, Launch&& launch)
     if (const int rc = current_device_state_ready(&ds)) return rc;
     hipStream_t s = (hipStream_t)c.stream;
     if (c.stats && stream_is_capturing(s)) return set_error(NTR_ERR_INVALID, "%s: the call reads its counters back and cannot be captured", c.fn);
-    unsigned long long h[kTwoLevelFastCounters] = {};
-    const int words = !c.stats ? 0 : c.fastStats ? kTwoLevelFastCounters : kTwoLevelCounters;
+    unsigned long long h[kTwoLevelMotionCounters] = {};
+    const int words = !c.stats ? 0 : c.motionStats ? kTwoLevelMotionCounters : c.fastStats ? kTwoLevelFastCounters : kTwoLevelCounters;
     if (const int rc = launch_trace_rays(c.fn, ds, s, c.numRays, c.seconds, words, h, [&](unsigned int blocks) { launch(ds, s, blocks); })) return rc;
     if (c.stats) {
         c.stats->numRays = c.numRays;
@@ -145,6 +157,7 @@ int two_level_trace(const TwoLevelCall& c, Launch&& launch)
     if (c.fastStats) {
         c.fastStats->waveSteps = h[8]; c.fastStats->fastWaveSteps = h[9]; c.fastStats->niceStarts = h[10]; c.fastStats->niceEntries = h[11];
     }
+    if (c.motionStats) { c.motionStats->numMovingEntries = (int64_t)h[12]; c.motionStats->numSingular = (int64_t)h[13]; }
     return NTR_OK;
 }
 

@@ -2,7 +2,7 @@
 // and ntr_trace_instanced_masked, and the wide path over ntr_pool_widen_batch (ntr_pool_widen for one BLAS) / ntr_tlas_widen / ntr_pool_wide_refit / ntr_tlas_wide_refit /
 // ntr_trace_instanced_wide, and a static world over ntr_trace_bvh / ntr_trace_instanced_seeded / ntr_trace_instanced_wide_seeded (see the
 // header), and the FAST path over ntr_instanced_validate / ntr_trace_instanced_fast, and over the wide trees
-// ntr_instanced_wide_validate / ntr_trace_instanced_wide_fast.
+// ntr_instanced_wide_validate / ntr_trace_instanced_wide_fast, and motion blur over ntr_tlas_motion_refit / ntr_trace_instanced_motion.
 #include "CudaInstancedBVH.hpp"
 
 #include <cstring>
@@ -12,8 +12,10 @@ namespace FW {
 CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstances(0), m_built(false), m_topology(false),
                                            m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false), m_world(-1),
                                            m_traceFast(false), m_fastStale(true), m_fastValidations(0), m_traceWideFast(false),
-                                           m_wideFastStale(true), m_wideFastValidations(0)
+                                           m_wideFastStale(true), m_wideFastValidations(0), m_rayTimes(NULL), m_time(0.0f),
+                                           m_hasMotion(false), m_motionStale(true), m_motionRefits(0)
 {
+    std::memset(&m_motionRefitResult, 0, sizeof(m_motionRefitResult));
     std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
     std::memset(&m_wideResult, 0, sizeof(m_wideResult));
     std::memset(&m_wideBlasRefitResult, 0, sizeof(m_wideBlasRefitResult));
@@ -180,9 +182,11 @@ void CudaInstancedBVH::setInstances(S32 num, const F32* objectToWorld, const S32
     if (num != m_numInstances) {
         m_topology = m_wideTopology = false;         // an unchanged count keeps the TLAS's topology for refit() ...
         m_instanceMasks.resizeDiscard(0);            // ... and the instance masks: with another count they would name other instances
+        clearMotion();                               // ... and key 1 of the motion
     }
     m_numInstances = num;
     m_built = false;
+    m_motionStale = true;
     writeWorldRecord();
 }
 
@@ -203,11 +207,13 @@ void CudaInstancedBVH::setInstancesDevice(S32 numNodes, Buffer& nodeLocal, Buffe
                                         check ? &m_instancesUpdateResult : NULL, NULL);
     // the instance array has been rewritten whatever the status says: the state follows before a bad instance is reported
     if (num != m_numInstances) {
-        m_topology = m_wideTopology = false;         // as setInstances: an unchanged count keeps the topology and the masks
+        m_topology = m_wideTopology = false;         // as setInstances: an unchanged count keeps the topology, the masks and key 1
         m_instanceMasks.resizeDiscard(0);
+        clearMotion();
     }
     m_numInstances = num;
     m_built = false;
+    m_motionStale = true;
     const std::string message = rc != NTR_OK ? ntr_last_error() : "";
     if (rc == NTR_OK || m_instancesUpdateResult.statusBits != 0) writeWorldRecord();   // (the kernel ran: the array is the scene's)
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", message.c_str());
@@ -267,6 +273,7 @@ void CudaInstancedBVH::build(S32 radius)
     m_built = m_topology = m_wideTopology = false;
     m_wideTlas = false;
     m_fastStale = m_wideFastStale = true;
+    m_motionStale = true;                        // the build writes records without moving flags and boxes of key 0 alone
     m_tlasNodes.resizeDiscard(capN);
     m_records.resizeDiscard(capR);
     const int rc = ntr_tlas_build(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
@@ -283,6 +290,7 @@ void CudaInstancedBVH::refit(void)
         fail("CudaInstancedBVH: no TLAS to refit: call build() first, and again after the instance count or the BLASes have changed");
     m_wideTlas = false;
     m_fastStale = m_wideFastStale = true;
+    m_motionStale = true;                        // as build(): the moving flags are cleared, the scene is frozen at key 0
     const int rc = ntr_tlas_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
                                   m_poolNodes.getCudaPtr(), m_poolNodes.getSize(), m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL,
                                   m_result.nodesBytes, m_result.rootLink, m_records.getMutableCudaPtr(), m_records.getSize(), NULL,
@@ -296,6 +304,59 @@ void CudaInstancedBVH::refit(void)
         m_result.sceneMax[a] = m_tlasRefitResult.sceneMax[a];
     }
     m_built = true;
+}
+
+void CudaInstancedBVH::setMotionKey(S32 num, const F32* objectToWorld1)
+{
+    if (num < 1 || !objectToWorld1) fail("CudaInstancedBVH: no motion key");
+    if (num != m_numInstances) fail("CudaInstancedBVH: the motion key names %d instances, setInstances %d", num, m_numInstances);
+    m_instances1.resizeDiscard((S64)num * sizeof(NtrInstance));
+    NtrInstance* inst = (NtrInstance*)m_instances1.getMutablePtrDiscard();
+    std::memset(inst, 0, (size_t)num * sizeof(NtrInstance));   // of key 1 only objectToWorld is read
+    for (S32 i = 0; i < num; i++) std::memcpy(inst[i].objectToWorld, objectToWorld1 + 12 * (size_t)i, sizeof(inst[i].objectToWorld));
+    m_hasMotion = m_motionStale = true;
+}
+
+void CudaInstancedBVH::setMotionKeyDevice(S32 num, Buffer& instances1)
+{
+    if (num < 1) fail("CudaInstancedBVH: no motion key");
+    if (num != m_numInstances) fail("CudaInstancedBVH: the motion key names %d instances, setInstances %d", num, m_numInstances);
+    if (instances1.getSize() < (S64)num * (S64)sizeof(NtrInstance)) fail("CudaInstancedBVH: the motion key's buffer is smaller than its count");
+    m_instances1.resizeDiscard((S64)num * sizeof(NtrInstance));
+    m_instances1.setRange(0, instances1, 0, (S64)num * sizeof(NtrInstance));
+    m_hasMotion = m_motionStale = true;
+}
+
+void CudaInstancedBVH::clearMotion(void)
+{
+    // the records keep their moving flags, which only the motion trace reads, and the boxes still bound the sweep: m_built stays
+    m_hasMotion = false;
+    m_motionStale = true;
+    m_instances1.resizeDiscard(0);
+}
+
+void CudaInstancedBVH::refitMotion(void)
+{
+    if (!m_hasMotion) fail("CudaInstancedBVH: no motion key: call setMotionKey first");
+    if (!m_built) fail("CudaInstancedBVH: No TLAS!");
+    m_wideTlas = false;                          // the binary boxes become the swept ones: as refit()
+    m_fastStale = m_wideFastStale = true;
+    m_motionKeys.resizeDiscard((S64)m_numInstances * 128);
+    const int rc = ntr_tlas_motion_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (const NtrInstance*)m_instances1.getCudaPtr(),
+                                         (int32_t)m_ranges.size(), m_ranges.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(),
+                                         m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL, m_result.nodesBytes, m_result.rootLink,
+                                         m_records.getMutableCudaPtr(), m_records.getSize(), m_motionKeys.getMutableCudaPtrDiscard(),
+                                         m_motionKeys.getSize(), NULL, &m_motionRefitResult, NULL);
+    m_motionRefits++;
+    if (rc != NTR_OK) {
+        m_built = false;                         // a part of the tree kept stale boxes
+        fail("CudaInstancedBVH: %s", ntr_last_error());
+    }
+    for (int a = 0; a < 3; a++) {
+        m_result.sceneMin[a] = m_motionRefitResult.refit.sceneMin[a];
+        m_result.sceneMax[a] = m_motionRefitResult.refit.sceneMax[a];
+    }
+    m_motionStale = false;
 }
 
 void CudaInstancedBVH::widen(void)
@@ -425,7 +486,17 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     const S32 numRays = rays.getSize();
     instanceIDs.resizeDiscard((S64)numRays * sizeof(S32));
     if (!numRays) return 0.0f;
+    if (m_hasMotion) {
+        // motion over the 4-wide trees, the FAST form and the seeded / world form does not exist: neither is ignored silently
+        if (m_traceWide) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceWide: clearMotion() or setTraceWide(false)");
+        if (m_traceWideFast) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceWideFast: clearMotion() or setTraceWideFast(false)");
+        if (m_traceFast) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceFast: clearMotion() or setTraceFast(false)");
+        if (m_world >= 0) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setWorld: clearMotion() or clearWorld()");
+    }
     if (!m_built) fail("CudaInstancedBVH: No TLAS!");
+    if (m_hasMotion && m_rayTimes && m_rayTimes->getSize() < (S64)numRays * (S64)sizeof(F32))
+        fail("CudaInstancedBVH: setRayTimes' buffer holds fewer than %d times", numRays);
+    if (m_hasMotion && m_motionStale) refitMotion();
     float seconds = 0.0f, worldSeconds = 0.0f;
     const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
     const bool world = m_world >= 0, wide = m_traceWide && isWide();
@@ -458,7 +529,16 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     const void* d_woop = m_poolTriWoop.getCudaPtr();
     const int64_t woopBytes = m_poolTriWoop.getSize();
     const int32_t* d_index = (const int32_t*)m_poolTriIndex.getCudaPtr();
-    if (wide && m_traceWideFast)
+    if (m_hasMotion) {
+        NtrInstanceMotion motion;
+        motion.d_motionKeys = m_motionKeys.getCudaPtr();
+        motion.motionKeysBytes = m_motionKeys.getSize();
+        motion.d_rayTimes = m_rayTimes ? (const float*)m_rayTimes->getCudaPtr() : NULL;
+        motion.time = m_time;
+        motion.pad = 0.0f;
+        rc = ntr_trace_instanced_motion(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records, m_numInstances,
+                                        d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &motion, &seconds, NULL);
+    } else if (wide && m_traceWideFast)
         rc = ntr_trace_instanced_wide_fast(numRays, anyHit, d_rays, d_seed, seedInstance, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink,
                                            d_records, m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis,
                                            currentWideFastFlags(), &seconds, NULL);

@@ -83,6 +83,19 @@
 //                 the wide boxes are what is traced, whatever the binary flags say); widen, refitBLASesWide, refitWide, setWorld,
 //                 clearWorld and everything that drops the wide pool or the wide TLAS mark it stale, and the next wide fast traceBatch
 //                 validates ahead of the trace, on its stream, once
+//   setMotionKey   motion blur: a second key of the instances' transforms, the shutter's close, beside setInstances' (the
+//                 shutter's opening): num x 12 F32 on the host, or -- setMotionKeyDevice -- an NtrInstance array on the device, which
+//                 is what a second ntr_instances_update fills (only its objectToWorld is read).  num must be getNumInstances().
+//                 While hasMotion(), traceBatch takes ntr_trace_instanced_motion with setRayTimes' per-ray times (a Buffer of F32,
+//                 one per ray, that stays the caller's; NULL: none) or else setTime's scalar.  refitMotion() is ntr_tlas_motion_refit
+//                 over the current tree: swept leaf boxes, the moving flags in the records, the motion key buffer; it needs isBuilt().
+//                 Staleness, as the FAST flags': setMotionKey, setMotionKeyDevice, setInstances, setInstancesDevice, build and refit
+//                 mark the motion refit stale -- build() and refit() write records without moving flags and boxes of key 0 alone -- and
+//                 the class then reports hasMotion() with isMotionStale(); the next traceBatch with motion calls refitMotion() first,
+//                 exactly once.  clearMotion() drops key 1: traceBatch is the static one again, over boxes that still bound the sweep
+//                 until the next refit().  setInstances with another count clears the motion, as it clears the masks.
+//                 Not combinable: with motion set and setTraceWide, setTraceFast or setTraceWideFast on, or a world set, traceBatch
+//                 fail()s with a message naming the switch; it ignores neither silently.  InstancedRenderer knows nothing of motion.
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
 //   refitBLASes -> optimizeBLASes every so many frames -> setInstances (setInstancesDevice for transforms on the device) -> refit ->
@@ -125,6 +138,18 @@ public:
     void build(S32 radius = DefaultRadius);
     void refit(void);
     void setInstanceMasks(const U32* masks /* getNumInstances() words; NULL: all visible */);
+    void setMotionKey(S32 num, const F32* objectToWorld1 /* num x 12 */);        // key 1; num == getNumInstances()
+    void setMotionKeyDevice(S32 num, Buffer& instances1 /* num NtrInstance */);
+    void clearMotion(void);
+    bool hasMotion(void) const { return m_hasMotion; }
+    bool isMotionStale(void) const { return m_motionStale; }                     // the next traceBatch with motion calls refitMotion() first
+    void refitMotion(void);
+    S32  getMotionRefits(void) const { return m_motionRefits; }                  // ntr_tlas_motion_refit calls so far
+    const NtrTlasMotionRefitResult& getMotionRefitResult(void) const { return m_motionRefitResult; }   // of the last refitMotion (zero before)
+    void setRayTimes(Buffer* times) { m_rayTimes = times; }                      // F32 per ray, the caller's; NULL: every ray has setTime's
+    void setTime(F32 time) { m_time = time; }
+    Buffer& getMotionKeyBuffer(void) { return m_motionKeys; }                    // 128 bytes per instance, as refitMotion wrote them
+    Buffer& getMotionInstanceBuffer(void) { return m_instances1; }               // key 1: NtrInstance per instance
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask = 0xFFFFFFFFu);   // GPU seconds
     void widen(void);
     void refitBLASesWide(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas = NULL, S32 num = 0, F32 epsilon = 0.0f);
@@ -221,6 +246,13 @@ private:
     Buffer        m_wideFastFlags;
     bool          m_traceWideFast, m_wideFastStale;
     S32           m_wideFastValidations;
+    // motion blur (setMotionKey): key 1 of the instances, what ntr_tlas_motion_refit wrote beside the records, the rays' times
+    Buffer        m_instances1, m_motionKeys;
+    Buffer*       m_rayTimes;
+    F32           m_time;
+    bool          m_hasMotion, m_motionStale;
+    S32           m_motionRefits;
+    NtrTlasMotionRefitResult m_motionRefitResult;
 };
 
 }  // namespace FW
