@@ -425,6 +425,28 @@ NTR_API int ntr_raygen_ao_normals(NtrRay* d_outRays, int32_t* d_outIDToSlot, int
                                   int32_t firstInputSlot, int32_t numInputRays, int32_t numSamples, float maxDist,
                                   uint32_t kernelSeed, void* stream);
 
+/* The times of a motion-blurred frame's rays (csrc/ray_times_kernels.hip): what ntr_trace_instanced_motion and
+ * ntr_instanced_hit_attributes_motion take as NtrInstanceMotion::d_rayTimes.  EXTENSION without a reference counterpart: the rule is the
+ * numpy spec tests/np_instanced_motion_frame.py, which the device equals bit for bit.  Both calls are asynchronous on `stream` and
+ * capturable; they allocate nothing and read nothing back.
+ * ntr_ray_times_primary: one hashed time per PIXEL in the shutter [open, close].  Integer arithmetic mod 2^32, binary32, no contraction:
+ *   id = d_slotToID ? d_slotToID[s] : s;  x = (uint32)id + (seed + 1) * 0x9E3779B9;
+ *   x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16;
+ *   u = (float)(x >> 8) * 2^-24 (exact, in [0, 1 - 2^-24]);  span = close - open;  t = open + u * span (the product rounded, then the
+ *   sum);  d_times[s] = t < close ? t : close.  With open = 0, close = 1 the time is u bit for bit.
+ *   The time depends on the pixel id, not on the slot: ntr_ray_morton_sort and the pixel table may reorder the rays without changing a
+ *   pixel's time; another seed per accumulated frame gives another sample.
+ * ntr_ray_times_secondary: d_outTimes[k * numSamples + j] = d_inTimes[firstInputSlot + k] for k < numInputRays, j < numSamples, the
+ *   word verbatim (a NaN included) -- ntr_raygen_ao_normals' slot rule, so a secondary ray sees its instance where its primary ray saw
+ *   it.  Nothing outside that window is written.
+ * NTR_ERR_INVALID (before any device work): a negative count or slot, numSamples < 1, numInputRays * numSamples >= 2^31, open or close
+ * not finite or not 0 <= open <= close <= 1; then, when there is a time to write, a null buffer or a times pointer that is not 4-byte
+ * aligned.  Zero rays return NTR_OK.  Without a device, after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP. */
+NTR_API int ntr_ray_times_primary(int32_t numRays, const int32_t* d_slotToID /* NULL: id = slot */, uint32_t seed, float open, float close,
+                                  float* d_times, void* stream);
+NTR_API int ntr_ray_times_secondary(const float* d_inTimes, int32_t firstInputSlot, int32_t numInputRays, int32_t numSamples,
+                                    float* d_outTimes, void* stream);
+
 /* rayGenShadowKernel (src/rt/ray/RayGenKernels.cu:240-301; RayGen::shadow, RayGen.cpp:114-150): numSamples rays per input ray
  * [firstInputSlot, +numInputRays) from its hit point (backed off 1e-2 along the ray) towards quasi-random points of the cube of
  * half-edge lightRadius around lightPos; tmax = the distance to that point, rays of missed inputs are degenerate (tmax = -1).
@@ -925,7 +947,8 @@ NTR_API int ntr_instances_update_host(int32_t numNodes, const float* nodeLocal, 
  *   d_rayTimes that is not 4-byte aligned, a d_motionKeys that is null or not 16-byte aligned, motionKeysBytes < 128 * numInstances;
  *   a null stats or motionStats.  numRays == 0 returns NTR_OK with the stats zeroed; without a device, after these checks,
  *   NTR_ERR_NO_DEVICE / NTR_ERR_HIP.
- * Not combinable with the 4-wide trees, the seeded / world form or FAST; ntr_instanced_hit_attributes gives the normal at key 0. */
+ * Not combinable with the 4-wide trees, the seeded / world form or FAST; ntr_instanced_hit_attributes gives the normal at key 0,
+ * ntr_instanced_hit_attributes_motion (below) the normal at the ray's time. */
 typedef struct NtrTlasMotionRefitResult {
     NtrTlasRefitResult refit;           /* as ntr_tlas_refit reports it */
     int32_t numMoving, pad;             /* instances whose objectToWorld differs between the keys */
@@ -1102,6 +1125,30 @@ NTR_API int ntr_instanced_hit_attributes(int32_t numRays, const NtrRayResult* d_
                                          const NtrInstancedGeometry* geom,
                                          NtrRayResult* d_outResults /* may be NULL; may equal d_results */,
                                          float* d_normals /* may be NULL; 4 floats per ray */, void* stream);
+
+/* ntr_instanced_hit_attributes with the normal at the RAY'S time (csrc/instanced_motion_attr_kernels.hip): the attributes
+ * of the hits ntr_trace_instanced_motion wrote.  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_motion_frame.py (hit_attributes_motion), which the device equals in every word.  `motion` is what the trace took:
+ * the key buffer ntr_tlas_motion_refit wrote, d_rayTimes or the scalar `time`.  The call is ntr_instanced_hit_attributes in every
+ * respect -- the resolution rule, the id rewrite, the cross product, the transpose, the normalisation, the (0, 0, 0, 0) cases, the
+ * in-place and one-NULL-output forms, the range checks before every read -- except where W comes from for a resolved ray r of
+ * instance i:
+ *   time        t_r = d_rayTimes[r] or `time`, clamped by t > 0 ? (t < 1 ? t : 1) : 0
+ *   moving      instance i is moving iff words 0..11 and 16..27 of its 128-byte key entry differ bitwise (this call has no records)
+ *   static      W = geom->d_instances[i].worldToObject, as ntr_instanced_hit_attributes
+ *   moving      W = ntr_instance_invert's function (binary64) of M(t_r), the trace's lerp of the two keys: the matrix the trace
+ *               transformed that ray with.  No inverse: the id is still resolved, the normal is (0, 0, 0, 0)
+ *   unchanged   the blas index comes from geom->d_instances (key 0); d_vtxPos is the current mesh (BLASes deforming within the shutter
+ *               are out of scope)
+ * With motion == NULL the call IS ntr_instanced_hit_attributes, and its refusals name that function.
+ * NTR_ERR_INVALID (before any device work): everything ntr_instanced_hit_attributes refuses, in its words and order, then: a d_rayTimes
+ * that is not 4-byte aligned, a d_motionKeys that is null or not 16-byte aligned, motionKeysBytes < 128 * geom->numInstances.
+ * numRays == 0 returns NTR_OK.  Without a device, after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP. */
+NTR_API int ntr_instanced_hit_attributes_motion(int32_t numRays, const NtrRayResult* d_results, const int32_t* d_instanceIDs,
+                                                const NtrInstancedGeometry* geom,
+                                                const NtrInstanceMotion* motion /* NULL: ntr_instanced_hit_attributes */,
+                                                NtrRayResult* d_outResults /* may be NULL; may equal d_results */,
+                                                float* d_normals /* may be NULL; 4 floats per ray */, void* stream);
 
 /* 4-wide BVH: an out-of-place pass that turns any BVHLayout_Compact tree into 4-wide nodes, and the trace that walks them
  * (csrc/bvh_widen_kernels.hip, csrc/trace_wide_kernels.hip, csrc/wide_bvh.h).  EXTENSION without a reference counterpart: the rule is the

@@ -41,7 +41,8 @@ from ._capi import (BvhView, RAY_DTYPE, RESULT_DTYPE, HostBvh, KernelConfig, Ntr
                     InstancesUpdateResult, instances_update, instances_status_read, instances_update_host, INSTANCE_MAX_CHAIN,
                     INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN,
                     TlasMotionRefitResult, InstanceMotion, InstancedMotionStats, tlas_motion_refit, tlas_motion_refit_scratch_bytes,
-                    trace_instanced_motion, trace_instanced_motion_stats)
+                    trace_instanced_motion, trace_instanced_motion_stats, instanced_hit_attributes_motion, ray_times_primary,
+                    ray_times_secondary)
 
 BVHLayout_Compact = 4
 BVH_FINITE, BVH_FASTDIV, BVH_NOTINY, BVH_ORDERED, BVH_WIDE_LEAVES = 1, 2, 4, 8, 16
@@ -78,4 +79,5 @@ __all__ = ["BvhView", "RAY_DTYPE", "RESULT_DTYPE", "HostBvh", "KernelConfig", "N
            "InstancesUpdateResult", "instances_update", "instances_status_read", "instances_update_host", "INSTANCE_MAX_CHAIN",
            "INSTANCE_ERR_SINGULAR", "INSTANCE_ERR_CHAIN",
            "TlasMotionRefitResult", "InstanceMotion", "InstancedMotionStats", "tlas_motion_refit", "tlas_motion_refit_scratch_bytes",
-           "trace_instanced_motion", "trace_instanced_motion_stats"]
+           "trace_instanced_motion", "trace_instanced_motion_stats", "instanced_hit_attributes_motion", "ray_times_primary",
+           "ray_times_secondary"]

@@ -546,6 +546,9 @@ SYMBOLS = [
     ("ntr_trace_instanced_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                             C.POINTER(InstanceVisibility), C.POINTER(InstancedTraceStats), _vp]),
     ("ntr_instanced_hit_attributes", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), _vp, _vp, _vp]),
+    ("ntr_instanced_hit_attributes_motion", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), C.POINTER(InstanceMotion), _vp, _vp, _vp]),
+    ("ntr_ray_times_primary", C.c_int, [_i32, _vp, _u32, C.c_float, C.c_float, _vp, _vp]),
+    ("ntr_ray_times_secondary", C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     ("ntr_bvh_widen_capacity", C.c_int, [_i64, C.POINTER(_i64)]),
     ("ntr_bvh_widen", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhWideResult), _vp]),
     ("ntr_bvh_widen_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
@@ -1405,6 +1408,29 @@ def instanced_hit_attributes(num_rays, d_results, d_instance_ids, geom, d_out_re
     Asynchronous on `stream` and capturable."""
     _check(lib().ntr_instanced_hit_attributes(int(num_rays), _vp(d_results), _vp(d_instance_ids), C.byref(geom) if geom is not None else None,
                                               _vp(d_out_results), _vp(d_normals), _vp(stream)))
+
+
+def instanced_hit_attributes_motion(num_rays, d_results, d_instance_ids, geom, motion, d_out_results=0, d_normals=0, stream=0):
+    """ntr_instanced_hit_attributes_motion: instanced_hit_attributes with the normal of a moving instance's hit at the ray's time (the
+    rule is tests/np_instanced_motion_frame.py).  motion: the InstanceMotion trace_instanced_motion took, or None (NULL:
+    instanced_hit_attributes).  Asynchronous on `stream` and capturable."""
+    _check(lib().ntr_instanced_hit_attributes_motion(int(num_rays), _vp(d_results), _vp(d_instance_ids), C.byref(geom) if geom is not None else None,
+                                                     C.byref(motion) if motion is not None else None, _vp(d_out_results), _vp(d_normals),
+                                                     _vp(stream)))
+
+
+def ray_times_primary(num_rays, d_slot_to_id, seed, open, close, d_times, stream=0):
+    """ntr_ray_times_primary: one hashed time per pixel id (d_slot_to_id, or 0: id = slot) and seed in the shutter [open, close]; the
+    rule is tests/np_instanced_motion_frame.py.  Asynchronous on `stream` and capturable."""
+    _check(lib().ntr_ray_times_primary(int(num_rays), _vp(d_slot_to_id), int(seed) & 0xFFFFFFFF, float(open), float(close), _vp(d_times),
+                                       _vp(stream)))
+
+
+def ray_times_secondary(d_in_times, first_input_slot, num_input_rays, num_samples, d_out_times, stream=0):
+    """ntr_ray_times_secondary: output slot k * num_samples + j takes the time of input slot first_input_slot + k (raygen_ao_normals'
+    slot rule), the word verbatim.  Asynchronous on `stream` and capturable."""
+    _check(lib().ntr_ray_times_secondary(_vp(d_in_times), int(first_input_slot), int(num_input_rays), int(num_samples), _vp(d_out_times),
+                                         _vp(stream)))
 
 
 def bvh_widen_capacity(nodes_bytes):

@@ -17,15 +17,13 @@
 #include <stdint.h>
 
 #include "ntr_internal.h"
+#include "instanced_attr.h"
 
 namespace ntr {
 namespace {
 
-constexpr int IHA_BLOCK = 256;
-static_assert(sizeof(NtrInstance) == 112 && offsetof(NtrInstance, worldToObject) == 48 && offsetof(NtrInstance, blas) == 96,
-              "the instance row is read as three 16-byte loads at byte 48 and a word at byte 96");
-static_assert(sizeof(NtrBlasTris) == 8, "NtrBlasTris is read as one 8-byte load");
-
+// (instanced_attr.h states these steps once more, as functions, for instanced_motion_attr_kernels.hip: this kernel calling them compiles
+// to other code than it had, so its text stays as it was -- DESIGN.md 6ab)
 __global__ __launch_bounds__(IHA_BLOCK) void instanced_hit_attributes_kernel(int numRays, const int4* results, const int* __restrict__ instanceIDs,
                                                                              const NtrInstance* __restrict__ inst, int numInstances,
                                                                              const int2* __restrict__ blasTris, int numBlas,
@@ -91,16 +89,7 @@ int ntr_instanced_hit_attributes(int32_t numRays, const NtrRayResult* d_results,
     const char* fn = "ntr_instanced_hit_attributes";
     if (numRays < 0) return set_error(NTR_ERR_INVALID, "%s: numRays < 0", fn);
     if (numRays == 0) return NTR_OK;
-    if (!geom) return set_error(NTR_ERR_INVALID, "%s: geom is null", fn);
-    if (!geom->d_instances || !geom->d_blasTris || !geom->d_triVtxIndex || !geom->d_vtxPos)
-        return set_error(NTR_ERR_INVALID, "%s: a null pointer in geom (d_instances, d_blasTris, d_triVtxIndex and d_vtxPos are all needed)", fn);
-    if (geom->numInstances < 1 || geom->numBlas < 1 || geom->numTrisTotal < 1 || geom->numVerts < 1)
-        return set_error(NTR_ERR_INVALID, "%s: numInstances, numBlas, numTrisTotal and numVerts must all be >= 1", fn);
-    if (!d_results || !d_instanceIDs) return set_error(NTR_ERR_INVALID, "%s: d_results or d_instanceIDs is null", fn);
-    if (!d_outResults && !d_normals) return set_error(NTR_ERR_INVALID, "%s: both outputs are null (pass d_outResults, d_normals or both)", fn);
-    if (((uintptr_t)d_results | (uintptr_t)d_outResults | (uintptr_t)d_normals | (uintptr_t)geom->d_instances) & 15u)
-        return set_error(NTR_ERR_INVALID, "%s: d_results, d_outResults, d_normals and geom->d_instances must be 16-byte aligned", fn);
-    if (((uintptr_t)geom->d_blasTris) & 7u) return set_error(NTR_ERR_INVALID, "%s: geom->d_blasTris must be 8-byte aligned", fn);
+    if (attr_check(fn, d_results, d_instanceIDs, geom, d_outResults, d_normals) != NTR_OK) return NTR_ERR_INVALID;
 
     int dev = 0;
     NTR_HIP(hipGetDevice(&dev));

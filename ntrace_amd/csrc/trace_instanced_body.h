@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     // the ray's time, clamped so that a NaN gives 0; the key buffer's descriptor is built from kernel arguments only
     const Rsrc rKeys = make_rsrc(mo.keys, mo.keysBytes);
     float rayTime = mo.rayTimes ? mo.rayTimes[valid ? rayIdx : 0] : mo.time;
-    rayTime = rayTime > 0.0f ? (rayTime < 1.0f ? rayTime : 1.0f) : 0.0f;
+    rayTime = motion_clamp_time(rayTime);
     unsigned int movingEntries = 0u, singularSteps = 0u;   // (STATS only)
 #endif
 

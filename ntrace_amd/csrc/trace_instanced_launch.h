@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "ntr_internal.h"
+#include "instance_motion.h"
 #include "instanced_wide_bvh.h"
 #include "trace_launch.h"
 
@@ -96,13 +97,7 @@ inline int two_level_check(const TwoLevelCall& c, bool* go)
         return set_error(NTR_ERR_INVALID, "%s: the seed records must be 16-byte aligned", fn);
     if (c.validate && (!c.d_flags || (((uintptr_t)c.d_flags) & 15u) != 0))
         return set_error(NTR_ERR_INVALID, "%s: the flags (%s) must be given and 16-byte aligned", fn, c.validate);
-    if (c.motion) {
-        if ((((uintptr_t)c.motion->d_rayTimes) & 3u) != 0) return set_error(NTR_ERR_INVALID, "%s: the ray times must be 4-byte aligned", fn);
-        if (!c.motion->d_motionKeys || (((uintptr_t)c.motion->d_motionKeys) & 15u) != 0)
-            return set_error(NTR_ERR_INVALID, "%s: the motion keys (ntr_tlas_motion_refit) must be given and 16-byte aligned", fn);
-        if (c.motion->motionKeysBytes < (int64_t)kMotionKeyBytes * c.numInstances)
-            return set_error(NTR_ERR_INVALID, "%s: motionKeysBytes below 128 * numInstances", fn);
-    }
+    if (c.motion && motion_check(fn, c.motion, c.numInstances) != NTR_OK) return NTR_ERR_INVALID;
     *go = true;
     return NTR_OK;
 }

@@ -4,7 +4,7 @@
 //   time    per lane, one register through the loop: d_rayTimes[r] or the launch's scalar, clamped to [0, 1] (a NaN gives 0)
 //   moving  word 15 of the fetched record, which ntr_tlas_motion_refit (tlas_motion_refit_kernels.hip) sets and no other kernel reads:
 //           the record came with the step's one fetch, so a static instance costs no further load
-//   pose    motion_pose: the instance's two keys (two 48-byte loads from the motion key buffer at 128 * i, through a range-checked
+//   pose    motion_pose (the arithmetic is instance_motion.h's): the instance's two keys (two 48-byte loads from the motion key buffer at 128 * i, through a range-checked
 //           descriptor: beyond the extent they return zeros, and a zero matrix is singular), twelve lerps in binary32 and
 //           instance_invert (instance_math.h: binary64, the function ntr_instance_invert and ntr_instances_update use).  Its three rows
 //           replace the record's in the registers the fetch wrote, and the masked kernel's transform goes on from there.  No inverse
@@ -21,6 +21,7 @@
 
 #include "ntr_internal.h"
 #include "instance_math.h"
+#include "instance_motion.h"
 #include "instanced_bvh.h"
 #include "trace_instanced_launch.h"
 #include "trace_lane.h"
@@ -38,34 +39,15 @@ struct InstancedMotion {
     float time;
 };
 
-// M(t) component (tests/np_instanced_motion.py, lerp): the keys themselves at the two ends and wherever they are the same word
-__device__ __forceinline__ float motion_lerp(float a, float b, float t, float u)
-{
-    const float v = u * a + t * b;   // (both products rounded: the library is built without contraction)
-    return (t == 0.0f || __float_as_uint(a) == __float_as_uint(b)) ? a : (t == 1.0f ? b : v);
-}
-
-// worldToObject(t) of moving instance idx into the rows a, b, c; false, and the rows untouched, where M(t) has no inverse
+// worldToObject(t) of moving instance idx into the rows a, b, c; false, and the rows untouched, where M(t) has no inverse.  The loads
+// are this unit's; the lerps and the inverse are instance_motion.h's, shared with instanced_motion_attr_kernels.hip
 __device__ __forceinline__ bool motion_pose(Rsrc rKeys, int idx, float t, float4& a, float4& b, float4& c)
 {
     // 128 * idx may pass 2^32 for an index no key buffer can hold (a descriptor ends below 2^32): such a lane reads nothing
     const int ofs = (unsigned)idx < (unsigned)(kPoolMaxBytes / kMotionKeyBytes) ? idx * kMotionKeyBytes : kNoNode;
     const float4 k0[3] = {ld4(rKeys, ofs), ld4(rKeys, ofs + 16), ld4(rKeys, ofs + 32)};
     const float4 k1[3] = {ld4(rKeys, ofs + kMotionKey1Bytes), ld4(rKeys, ofs + kMotionKey1Bytes + 16), ld4(rKeys, ofs + kMotionKey1Bytes + 32)};
-    const float u = 1.0f - t;
-    float m[12], w[12];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        m[4 * r + 0] = motion_lerp(k0[r].x, k1[r].x, t, u);
-        m[4 * r + 1] = motion_lerp(k0[r].y, k1[r].y, t, u);
-        m[4 * r + 2] = motion_lerp(k0[r].z, k1[r].z, t, u);
-        m[4 * r + 3] = motion_lerp(k0[r].w, k1[r].w, t, u);
-    }
-    if (!instance_invert(m, w)) return false;
-    a = make_float4(w[0], w[1], w[2], w[3]);
-    b = make_float4(w[4], w[5], w[6], w[7]);
-    c = make_float4(w[8], w[9], w[10], w[11]);
-    return true;
+    return motion_pose_keys(k0, k1, t, a, b, c);
 }
 
 #define NTR_TI_PARAMS InstancedParams p, InstancedExtras x, InstancedMotion mo

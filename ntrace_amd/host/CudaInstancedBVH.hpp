@@ -95,7 +95,9 @@
 //                 exactly once.  clearMotion() drops key 1: traceBatch is the static one again, over boxes that still bound the sweep
 //                 until the next refit().  setInstances with another count clears the motion, as it clears the masks.
 //                 Not combinable: with motion set and setTraceWide, setTraceFast or setTraceWideFast on, or a world set, traceBatch
-//                 fail()s with a message naming the switch; it ignores neither silently.  InstancedRenderer knows nothing of motion.
+//                 fail()s with a message naming the switch; it ignores neither silently.  InstancedRenderer::setMotionBlur (DESIGN.md
+//                 6ab) renders motion-blurred frames over this class: it points setRayTimes at each batch's hashed times for the
+//                 trace (getRayTimes: the caller's pointer comes back after it) and takes the normals at the same times.
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
 //   refitBLASes -> optimizeBLASes every so many frames -> setInstances (setInstancesDevice for transforms on the device) -> refit ->
@@ -147,7 +149,9 @@ public:
     S32  getMotionRefits(void) const { return m_motionRefits; }                  // ntr_tlas_motion_refit calls so far
     const NtrTlasMotionRefitResult& getMotionRefitResult(void) const { return m_motionRefitResult; }   // of the last refitMotion (zero before)
     void setRayTimes(Buffer* times) { m_rayTimes = times; }                      // F32 per ray, the caller's; NULL: every ray has setTime's
+    Buffer* getRayTimes(void) const { return m_rayTimes; }
     void setTime(F32 time) { m_time = time; }
+    F32  getTime(void) const { return m_time; }
     Buffer& getMotionKeyBuffer(void) { return m_motionKeys; }                    // 128 bytes per instance, as refitMotion wrote them
     Buffer& getMotionInstanceBuffer(void) { return m_instances1; }               // key 1: NtrInstance per instance
     F32  traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask = 0xFFFFFFFFu);   // GPU seconds

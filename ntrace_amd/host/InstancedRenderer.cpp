@@ -1,5 +1,6 @@
 // InstancedRenderer.cpp -- Renderer's batching over a CudaInstancedBVH: every traced batch goes through ntr_instanced_hit_attributes
-// before ntr_raygen_ao_normals, ntr_count_hits or ntr_reconstruct sees it (see the header).
+// before ntr_raygen_ao_normals, ntr_count_hits or ntr_reconstruct sees it (see the header).  Under setMotionBlur every batch has a
+// time per ray: the trace and ntr_instanced_hit_attributes_motion read the same buffer.
 #include "InstancedRenderer.hpp"
 
 namespace FW {
@@ -7,6 +8,7 @@ namespace FW {
 InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
     : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
       m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false), m_fast(false), m_wideFast(false),
+      m_motionBlur(false), m_motionSeed(0), m_shutterOpen(0.0f), m_shutterClose(1.0f),
       m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
 {
 }
@@ -34,13 +36,24 @@ void InstancedRenderer::setRayMasks(U32 primaryMask, U32 secondaryMask)
     m_secondaryMask = secondaryMask;
 }
 
-F32 InstancedRenderer::trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
+void InstancedRenderer::setMotionBlur(bool on, U32 seed, F32 open, F32 close)
 {
-    struct Restore {   // the caller's flags come back on every path: traceBatch fails by throwing
+    if (!(open >= 0.0f && open <= close && close <= 1.0f)) fail("InstancedRenderer::setMotionBlur: the shutter must be 0 <= open <= close <= 1");
+    m_motionBlur = on;
+    m_motionSeed = seed;
+    m_shutterOpen = open;
+    m_shutterClose = close;
+}
+
+F32 InstancedRenderer::trace(RayBuffer& rays, Buffer& instanceIDs, Buffer& times, U32 rayMask)
+{
+    struct Restore {   // the caller's flags and times come back on every path: traceBatch fails by throwing
         CudaInstancedBVH& bvh;
         bool was, wasFast, wasWideFast;
-        ~Restore() { bvh.setTraceWide(was); bvh.setTraceFast(wasFast); bvh.setTraceWideFast(wasWideFast); }
-    } restore = {m_bvh, m_bvh.getTraceWide(), m_bvh.getTraceFast(), m_bvh.getTraceWideFast()};
+        Buffer* wasTimes;
+        ~Restore() { bvh.setTraceWide(was); bvh.setTraceFast(wasFast); bvh.setTraceWideFast(wasWideFast); bvh.setRayTimes(wasTimes); }
+    } restore = {m_bvh, m_bvh.getTraceWide(), m_bvh.getTraceFast(), m_bvh.getTraceWideFast(), m_bvh.getRayTimes()};
+    if (m_motionBlur) m_bvh.setRayTimes(&times);
     m_bvh.setTraceWide(m_wide);
     m_bvh.setTraceFast(m_fast || restore.wasFast);
     m_bvh.setTraceWideFast(m_wideFast || restore.wasWideFast);
@@ -48,7 +61,7 @@ F32 InstancedRenderer::trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask)
 }
 
 // the batch's records with pool triangle ids and, for a batch that secondary rays start from, the world-space normals
-void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals)
+void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& times, Buffer& resolved, Buffer* normals)
 {
     const S32 n = rays.getSize();
     resolved.resizeDiscard((S64)n * sizeof(NtrRayResult));
@@ -63,14 +76,29 @@ void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& re
     g.d_blasTris = (const NtrBlasTris*)m_bvh.getBLASTrisBuffer().getCudaPtr();
     g.d_triVtxIndex = (const int32_t*)m_triVtxIndex->getCudaPtr();
     g.d_vtxPos = (const float*)m_vtxPos->getCudaPtr();
-    const int rc = ntr_instanced_hit_attributes(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(), &g,
-                                                (NtrRayResult*)resolved.getMutableCudaPtr(), normals ? (float*)normals->getMutableCudaPtr() : NULL,
-                                                NULL);
+    int rc;
+    if (m_motionBlur) {   // the key buffer and the times the trace has just read: the normal of the pose the ray hit
+        if (times.getSize() < (S64)n * (S64)sizeof(F32)) fail("InstancedRenderer: the batch has no times");
+        NtrInstanceMotion motion;
+        motion.d_motionKeys = m_bvh.getMotionKeyBuffer().getCudaPtr();
+        motion.motionKeysBytes = m_bvh.getMotionKeyBuffer().getSize();
+        motion.d_rayTimes = (const float*)times.getCudaPtr();
+        motion.time = 0.0f;
+        motion.pad = 0.0f;
+        rc = ntr_instanced_hit_attributes_motion(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(),
+                                                 &g, &motion, (NtrRayResult*)resolved.getMutableCudaPtr(),
+                                                 normals ? (float*)normals->getMutableCudaPtr() : NULL, NULL);
+    } else
+        rc = ntr_instanced_hit_attributes(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(), &g,
+                                          (NtrRayResult*)resolved.getMutableCudaPtr(), normals ? (float*)normals->getMutableCudaPtr() : NULL, NULL);
     if (rc != NTR_OK) fail("InstancedRenderer: %s", ntr_last_error());
 }
 
 void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
 {
+    if (m_motionBlur && !m_bvh.hasMotion())
+        fail("InstancedRenderer: setMotionBlur is on and the CudaInstancedBVH has no motion key: call setMotionKey (or setMotionKeyDevice) with the "
+             "shutter's closing transforms, or setMotionBlur(false)");
     if (!m_triVtxIndex)
         fail("InstancedRenderer: no geometry: call setGeometry() with the index and vertex buffers CudaInstancedBVH::buildBLASes was given");
     const S32 meshless = m_bvh.getFirstMeshlessBLAS();
@@ -83,9 +111,10 @@ void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
     if (w < 1 || h < 1) fail("InstancedRenderer::beginFrame: bad frame size");
     if (m_wide && !m_bvh.isWide()) m_bvh.widen();   // after each build() / refit() of the frame loop
     m_raygen.primary(m_primaryRays, camera.position, camera.nscreenToWorld, w, h, camera.cameraFar, 0);
+    if (m_motionBlur) m_raygen.primaryTimes(m_primaryTimes, m_primaryRays, m_motionSeed, m_shutterOpen, m_shutterClose);
     if (m_rayType != RayType_Primary) {   // Renderer.cpp:482-488
-        trace(m_primaryRays, m_primaryIDs, m_primaryMask);
-        resolve(m_primaryRays, m_primaryIDs, m_primaryResolved, &m_primaryNormals);
+        trace(m_primaryRays, m_primaryIDs, m_primaryTimes, m_primaryMask);
+        resolve(m_primaryRays, m_primaryIDs, m_primaryTimes, m_primaryResolved, &m_primaryNormals);
     }
     m_cameraFar = camera.cameraFar;
     m_newBatch = true;
@@ -120,6 +149,9 @@ bool InstancedRenderer::nextBatch(void)
     default:
         return false;
     }
+    // a secondary ray inherits its primary ray's time: input slot m_batchStart / m_numSamples + k made slots k * m_numSamples + j
+    if (m_motionBlur && m_batchRays == &m_secondaryRays)
+        m_raygen.secondaryTimes(m_secondaryTimes, m_primaryTimes, m_batchStart / m_numSamples, m_secondaryRays.getSize() / m_numSamples, m_numSamples);
     return true;
 }
 
@@ -128,8 +160,9 @@ F32 InstancedRenderer::traceBatch(void)
     if (!m_batchRays) fail("InstancedRenderer::traceBatch: no batch");
     const bool primary = m_batchRays == &m_primaryRays;
     Buffer& ids = primary ? m_primaryIDs : m_secondaryIDs;
-    const F32 sec = trace(*m_batchRays, ids, primary ? m_primaryMask : m_secondaryMask);
-    resolve(*m_batchRays, ids, *m_batchResolved, primary ? &m_primaryNormals : NULL);
+    Buffer& times = primary ? m_primaryTimes : m_secondaryTimes;
+    const F32 sec = trace(*m_batchRays, ids, times, primary ? m_primaryMask : m_secondaryMask);
+    resolve(*m_batchRays, ids, times, *m_batchResolved, primary ? &m_primaryNormals : NULL);
     return sec;
 }
 

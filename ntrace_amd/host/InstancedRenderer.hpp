@@ -18,6 +18,16 @@
 //                 setWide(true) the switch is ignored
 //   setWideFast   the same for the wide batches of a setWide(true) frame (CudaInstancedBVH::setTraceWideFast); default
 //                 false; in the manner of setFast: on, or whatever the CudaInstancedBVH itself was told, and put back after each trace
+//   setMotionBlur motion-blurred frames over a CudaInstancedBVH with a motion key (setMotionKey); default off, and off
+//                 every path is what it was: the batches are traced as the CudaInstancedBVH stands, the caller's setRayTimes
+//                 included, and resolved at key 0.  On: beginFrame fails unless the CudaInstancedBVH hasMotion(), then gives every
+//                 pixel one hashed time in the shutter [open, close] (ntr_ray_times_primary over the primary slot-to-id table; another
+//                 seed per accumulated frame gives another sample); every batch is traced with setRayTimes pointing at its times -- the
+//                 caller's pointer is put back after each trace -- and resolved by ntr_instanced_hit_attributes_motion with the same key
+//                 buffer and times, so the normal is the one of the pose the ray hit; an AO or diffuse ray inherits its primary
+//                 ray's time (ntr_ray_times_secondary): it sees its instance where its primary ray saw it.  Primary, AO and diffuse
+//                 frames all work.  setWide, setFast, setWideFast and a world stay not combinable with motion: the
+//                 CudaInstancedBVH's traceBatch refuses each by name, and the refusal is passed on
 //   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
 //                 diffuse frames the primary rays are traced and resolved at once
 //   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
@@ -52,6 +62,8 @@ public:
     bool getFast(void) const { return m_fast; }
     void setWideFast(bool on) { m_wideFast = on; }
     bool getWideFast(void) const { return m_wideFast; }
+    void setMotionBlur(bool on, U32 seed = 0, F32 open = 0.0f, F32 close = 1.0f);
+    bool getMotionBlur(void) const { return m_motionBlur; }
 
     void beginFrame(const CameraView& camera, S32 w, S32 h);
     bool nextBatch(void);
@@ -65,10 +77,14 @@ public:
     Buffer&    getPrimaryResolvedBuffer(void) { return m_primaryResolved; }   // NtrRayResult per primary slot, ids of pool triangles
     Buffer&    getPrimaryNormalBuffer(void) { return m_primaryNormals; }      // 4 floats per primary slot
     Buffer&    getBatchResolvedBuffer(void) { return *m_batchResolved; }      // NtrRayResult per slot of the current batch
+    Buffer&    getPrimaryTimeBuffer(void) { return m_primaryTimes; }          // setMotionBlur: F32 per primary slot
+    Buffer&    getBatchTimeBuffer(void) { return m_batchRays == &m_primaryRays ? m_primaryTimes : m_secondaryTimes; }   // F32 per slot of the current batch
 
 private:
-    void resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& resolved, Buffer* normals);
-    F32  trace(RayBuffer& rays, Buffer& instanceIDs, U32 rayMask);   // the CudaInstancedBVH's traceBatch, wide when setWide asked for it, fast when setFast / setWideFast did
+    // times: the batch's, read when setMotionBlur is on
+    void resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& times, Buffer& resolved, Buffer* normals);
+    // the CudaInstancedBVH's traceBatch, wide when setWide asked for it, fast when setFast / setWideFast did, at `times` under setMotionBlur
+    F32  trace(RayBuffer& rays, Buffer& instanceIDs, Buffer& times, U32 rayMask);
     InstancedRenderer(const InstancedRenderer&);
     InstancedRenderer& operator=(const InstancedRenderer&);
 
@@ -81,11 +97,15 @@ private:
     S32        m_numSamples;
     U32        m_primaryMask, m_secondaryMask;
     bool       m_wide, m_fast, m_wideFast;
+    bool       m_motionBlur;
+    U32        m_motionSeed;
+    F32        m_shutterOpen, m_shutterClose;
     RayGen     m_raygen;
     F32        m_cameraFar;
     RayBuffer  m_primaryRays, m_secondaryRays;
     Buffer     m_primaryIDs, m_secondaryIDs;             // S32 per slot: the instance of the hit
     Buffer     m_primaryResolved, m_primaryNormals, m_secondaryResolved;
+    Buffer     m_primaryTimes, m_secondaryTimes;         // setMotionBlur: F32 per slot
     bool       m_newBatch;
     RayBuffer* m_batchRays;
     Buffer*    m_batchResolved;

@@ -65,6 +65,25 @@ bool RayGen::aoNormals(RayBuffer& orays, RayBuffer& irays, Buffer& normals, int 
     return true;
 }
 
+void RayGen::primaryTimes(Buffer& times, RayBuffer& rays, U32 seed, F32 open, F32 close)
+{
+    times.resizeDiscard((S64)rays.getSize() * (S64)sizeof(F32));
+    check(ntr_ray_times_primary(rays.getSize(), rays.getSize() ? (const int32_t*)rays.getSlotToIDBuffer().getCudaPtr() : NULL, seed, open, close,
+                                rays.getSize() ? (float*)times.getMutableCudaPtr() : NULL, NULL), "ntr_ray_times_primary");
+    check(ntr_stream_synchronize(NULL), "sync");
+}
+
+void RayGen::secondaryTimes(Buffer& times, Buffer& inTimes, S32 firstInputSlot, S32 numInputRays, int numSamples)
+{
+    if (firstInputSlot < 0 || numInputRays < 0 || inTimes.getSize() < ((S64)firstInputSlot + numInputRays) * (S64)sizeof(F32))
+        fail("RayGen::secondaryTimes: fewer input times than input slots");
+    times.resizeDiscard((S64)numInputRays * (S64)FW::max(numSamples, 0) * (S64)sizeof(F32));
+    const bool any = numInputRays > 0 && numSamples > 0;
+    check(ntr_ray_times_secondary(any ? (const float*)inTimes.getCudaPtr() : NULL, firstInputSlot, numInputRays, numSamples,
+                                  any ? (float*)times.getMutableCudaPtr() : NULL, NULL), "ntr_ray_times_secondary");
+    check(ntr_stream_synchronize(NULL), "sync");
+}
+
 bool RayGen::shadow(RayBuffer& orays, RayBuffer& irays, int numSamples, const Vec3f& lightPos, float lightRadius, bool& newBatch, U32 randomSeed)
 {
     S32 lo, hi;

@@ -47,6 +47,11 @@ public:
     // ao over per-ray normals (ntr_raygen_ao_normals; no counterpart in the reference): normals holds 4 floats per slot of irays, as
     // ntr_instanced_hit_attributes writes them; batching() exactly as ao()
     bool aoNormals(RayBuffer& orays, RayBuffer& irays, Buffer& normals, int numSamples, float maxDist, bool& newBatch, U32 randomSeed = 0);
+    // the times of a motion-blurred frame's rays (ntr_ray_times_primary / ntr_ray_times_secondary; no counterpart in the reference):
+    // one hashed time per pixel of `rays` in [open, close] -- times is resized to one F32 per slot -- and, for the batch aoNormals made
+    // from the input slots [firstInputSlot, +numInputRays), each input ray's time for its numSamples rays
+    void primaryTimes(Buffer& times, RayBuffer& rays, U32 seed, F32 open, F32 close);
+    void secondaryTimes(Buffer& times, Buffer& inTimes, S32 firstInputSlot, S32 numInputRays, int numSamples);
     // RayGen::shadow (src/rt/ray/RayGen.cpp:114-150): numSamples any-hit rays per input ray towards the area light
     bool shadow(RayBuffer& orays, RayBuffer& irays, int numSamples, const Vec3f& lightPos, float lightRadius, bool& newBatch, U32 randomSeed = 0);
 
