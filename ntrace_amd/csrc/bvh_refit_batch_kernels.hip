@@ -12,8 +12,8 @@
 // load of its own).  A group never spans two child slots, so none spans two BLASes.  The arrival protocol and its memory ordering are
 // bvh_climb.h's and are not restated.  A malformed tree is never followed: the thread sets an error bit and stops; entries share no
 // node, so every other entry is refitted completely.
-// No host read-back unless a result is asked for, and no memset node on the asynchronous path: the first launch re-initialises the
-// arrival counters, and the counters of the blocking form, which is never captured, are the one memset.
+// The held entry table, the refusals of a captured call, the bracket of the blocking form and the fold of its counter slots are
+// refit_launch.h's.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -31,6 +31,7 @@
 #include "device_scratch.h"
 #include "instanced_bvh.h"
 #include "level_build.h"
+#include "refit_launch.h"
 
 namespace ntr {
 namespace {
@@ -49,9 +50,8 @@ struct RbEntry {
 };
 static_assert(sizeof(RbEntry) == 32, "RbEntry must be 32 bytes");
 
-// Counters of the blocking form, as bvh_refit_kernels.hip's: a workgroup adds to the slot of its number modulo RB_STAT_SLOTS and the
-// host sums the slots.  bad is the maximum of ~entry over the entries with an error, so 0 says none and the lowest entry wins.
-constexpr int RB_STAT_SLOTS = 256;
+// A counter slot of the blocking form (refit_launch.h).  bad is the maximum of ~entry over the entries with an error, so 0 says none and the
+// lowest entry wins.
 struct RbStats {
     unsigned int innerLinks, leafLinks, rows, err, bad;
     unsigned int pad[11];        // a slot per 64-byte line
@@ -59,6 +59,7 @@ struct RbStats {
 static_assert(sizeof(RbStats) == 64, "RbStats must be 64 bytes");
 
 DeviceScratchPool g_rbPool;
+RefitHeld g_rbHeld[kMaxDevices];
 
 __global__ __launch_bounds__(RB_BLOCK) void refit_batch_topology(int numEntries, int totalSlots, const int* __restrict__ starts,
                                                                  const RbEntry* __restrict__ table, const int* __restrict__ poolNodes,
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(RB_BLOCK) void refit_batch_topology(int numEntries,
         }
     }
     if (!stats) return;
-    stats += blockIdx.x % RB_STAT_SLOTS;
+    stats += blockIdx.x % kRefitStatSlots;
     if (err) atomicMax(&stats->bad, ~(unsigned int)e);   // (rare) the entry is the lane's own: a wave covers several
     // one add per wave and counter
     inner = wave_sum_u32(inner);
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(RB_BLOCK) void refit_batch_climb(int numEntries, in
                            tri + 3 * (size_t)E.firstTri, numVerts, pos, err, rows, lo, hi);
     const unsigned int groupErr = leaf ? (unsigned int)((__ballot(err != 0) >> groupShift) & ((1ull << G) - 1ull)) : 0u;
     if (stats) {                                 // uniform; the whole wave is here: nobody has returned yet
-        RbStats* mine = stats + blockIdx.x % RB_STAT_SLOTS;
+        RbStats* mine = stats + blockIdx.x % kRefitStatSlots;
         if (err) atomicMax(&mine->bad, ~(unsigned int)e);
         const unsigned int waveRows = wave_sum_u32(rows), waveErr = wave_or_u32(err);
         if ((threadIdx.x & 63) == 0) {
@@ -144,7 +145,7 @@ struct RbLayout {
     RbLayout(int64_t entries, int64_t slots)
     {
         ScratchCarver c;
-        stats = c.take(sizeof(RbStats) * RB_STAT_SLOTS);
+        stats = c.take(sizeof(RbStats) * kRefitStatSlots);
         starts = c.take((size_t)(entries + 1) * 4);
         table = c.take((size_t)entries * sizeof(RbEntry));
         parent = c.take((size_t)slots * 4);
@@ -152,15 +153,6 @@ struct RbLayout {
         end = c.off;
     }
 };
-
-// What the device's table holds, per device: the table the last call uploaded.  valid is cleared whenever the pool has been released
-// or has to grow (the next call finds it smaller than it needs), so a table on the host never vouches for bytes that are gone.
-struct RbUploaded {
-    bool valid = false;
-    std::vector<int> starts;
-    std::vector<RbEntry> table;
-};
-RbUploaded g_rbUploaded[kMaxDevices];
 
 }  // namespace
 }  // namespace ntr
@@ -187,8 +179,10 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
     if (((uintptr_t)d_poolNodes | (uintptr_t)d_poolTriWoop) & 15u)
         return set_error(NTR_ERR_INVALID, "%s: the pool's nodes and triWoop must be 16-byte aligned", fn);
 
-    std::vector<int> starts((size_t)numEntries + 1);
-    std::vector<RbEntry> table((size_t)numEntries);
+    RefitTable held = {2, {}, {0, 0}, {0, 0}};   // the running sums, then the entries: 8 words each
+    std::vector<uint32_t> &starts = held.words[0], &table = held.words[1];
+    starts = std::vector<uint32_t>((size_t)numEntries + 1);
+    table = std::vector<uint32_t>((size_t)numEntries * (sizeof(RbEntry) / 4));
     int64_t totalSlots = 0, totalRows = 0;
     for (int k = 0; k < numEntries; k++) {
         const NtrRefitBatchEntry& en = entries[k];
@@ -201,7 +195,7 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
                              (int)en.numTris, (int)numTrisTotal);
         if (!std::isfinite(en.epsilon) || en.epsilon < 0.0f)
             return set_error(NTR_ERR_INVALID, "%s: entry %d: epsilon must be finite and >= 0", fn, k);
-        RbEntry& E = table[k];
+        RbEntry E;
         E.nodeBase = (int)(en.range.nodesOffset / kNodeBytes);
         E.numSlots = (int)(en.range.nodesBytes / kNodeBytes);
         E.rowBase = (int)(en.range.triWoopOffset / kRowBytes);
@@ -210,7 +204,8 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
         E.numTris = en.numTris;
         E.eps = en.epsilon;
         E.pad = 0;
-        starts[k] = (int)totalSlots;
+        memcpy(&table[(size_t)k * (sizeof(RbEntry) / 4)], &E, sizeof(E));
+        starts[k] = (uint32_t)totalSlots;
         totalSlots += E.numSlots;
         totalRows += E.numRows;
         // disjoint ranges inside a pool of at most kPoolMaxBytes keep totalSlots below 2^26; overlapping ones are refused below, but
@@ -218,7 +213,7 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
         if (totalSlots > kPoolMaxBytes / kNodeBytes)
             return set_error(NTR_ERR_INVALID, "%s: the entries' node ranges are longer in all than a pool can be: some overlap", fn);
     }
-    starts[numEntries] = (int)totalSlots;
+    starts[numEntries] = (uint32_t)totalSlots;
     {
         int other = -1;
         int bad = first_range_overlap(numEntries, [&](int k) { return entries[k].range.nodesOffset; },
@@ -232,47 +227,17 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
     }
 
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    NTR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) return set_error(NTR_ERR_INVALID, "device index %d out of range", dev);
     const RbLayout lay(numEntries, totalSlots);
-    RbUploaded& up = g_rbUploaded[dev];
-    if (g_rbPool.held() < lay.end) up.valid = false;   // released, never reserved, or about to be regrown
-    const bool same = up.valid && up.starts == starts && up.table.size() == table.size() &&
-                      memcmp(up.table.data(), table.data(), table.size() * sizeof(RbEntry)) == 0;
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && result) return set_error(NTR_ERR_INVALID, "%s: a captured call cannot read a result back (pass result = NULL)", fn);
-    if (capturing && !same)
-        return set_error(NTR_ERR_INVALID, "%s: a captured call uploads and allocates nothing: the device must hold this entry table already "
-                         "-- make one uncaptured call with the same entries first (and none with other entries, and no "
-                         "ntr_lbvh_release_workspace, between it and the capture)", fn);
+    held.offset[0] = lay.starts;
+    held.offset[1] = lay.table;
     void* base = nullptr;
-    if (const int rc = g_rbPool.reserve(lay.end, &base)) return rc;
+    if (const int rc = refit_hold_table(fn, kRefitEntryWords, g_rbPool, g_rbHeld, s, result != nullptr, lay.end, held, &base)) return rc;
     int* d_starts = at<int>(base, lay.starts);
     RbEntry* d_table = at<RbEntry>(base, lay.table);
     unsigned int *parent = at<unsigned int>(base, lay.parent), *arrive = at<unsigned int>(base, lay.arrive);
-    if (!same) {
-        // the host copy is what the upload reads and what the next call compares with: the upload is waited for, so the copy never
-        // changes under it.  A loop of calls with one table (a frame loop) pays this once
-        up.valid = false;
-        up.starts.swap(starts);
-        up.table.swap(table);
-        NTR_HIP(hipMemcpyAsync(d_starts, up.starts.data(), up.starts.size() * 4, hipMemcpyHostToDevice, s));
-        NTR_HIP(hipMemcpyAsync(d_table, up.table.data(), up.table.size() * sizeof(RbEntry), hipMemcpyHostToDevice, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        up.valid = true;
-    }
     RbStats* stats = result ? at<RbStats>(base, lay.stats) : nullptr;
 
-    StreamEvents<2> ev(s);
-    if (result) {
-        NTR_HIP(ev.create());
-        NTR_HIP(ev.record(0));
-        NTR_HIP(hipMemsetAsync(stats, 0, sizeof(RbStats) * RB_STAT_SLOTS, s));
-    }
     const int slots = (int)totalSlots;
-    hipLaunchKernelGGL(refit_batch_topology, dim3((slots + RB_BLOCK - 1) / RB_BLOCK), dim3(RB_BLOCK), 0, s, (int)numEntries, slots,
-                       (const int*)d_starts, (const RbEntry*)d_table, (const int*)d_poolNodes, parent, arrive, stats);
     // lanes per leaf from the mean leaf size the selection's extents imply (a tree has one leaf more than inner nodes), by
     // ntr_bvh_refit's thresholds: a choice of speed only
     const double leaves = (double)totalSlots + (double)numEntries;
@@ -283,22 +248,21 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
     hipLaunchKernelGGL(refit_batch_climb<G>, grid, dim3(RB_BLOCK), 0, s, (int)numEntries, slots, (const int*)d_starts, (const RbEntry*)d_table, \
                        (int*)d_poolNodes, (float4*)d_poolTriWoop, d_poolTriIndex, d_triVtxIndex, numVerts, d_vtxPos,                        \
                        (const unsigned int*)parent, arrive, d_blasBoxes, stats)
-    if (group == 1) NTR_RB_CLIMB(1); else if (group == 4) NTR_RB_CLIMB(4); else NTR_RB_CLIMB(8);
+    std::vector<char> host;
+    float seconds = 0.0f;
+    const int rc = refit_bracket(s, result != nullptr, stats, sizeof(RbStats) * kRefitStatSlots, &host, &seconds, [&] {
+        hipLaunchKernelGGL(refit_batch_topology, dim3((slots + RB_BLOCK - 1) / RB_BLOCK), dim3(RB_BLOCK), 0, s, (int)numEntries, slots,
+                           (const int*)d_starts, (const RbEntry*)d_table, (const int*)d_poolNodes, parent, arrive, stats);
+        if (group == 1) NTR_RB_CLIMB(1); else if (group == 4) NTR_RB_CLIMB(4); else NTR_RB_CLIMB(8);
+    });
 #undef NTR_RB_CLIMB
-    NTR_HIP(hipGetLastError());
-    if (!result) return NTR_OK;
+    if (rc != NTR_OK || !result) return rc;
 
-    NTR_HIP(ev.record(1));
-    std::vector<RbStats> slotsHost(RB_STAT_SLOTS);   // the copy is waited for right here
-    NTR_HIP(hipMemcpyAsync(slotsHost.data(), stats, sizeof(RbStats) * RB_STAT_SLOTS, hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
     uint64_t inner = 0, leafLinks = 0, rows = 0;
     unsigned int err = 0, bad = 0;
-    for (const RbStats& v : slotsHost) {
+    refit_fold_slots<RbStats>(host.data(), [&](const RbStats& v) {
         inner += v.innerLinks; leafLinks += v.leafLinks; rows += v.rows; err |= v.err; bad = std::max(bad, v.bad);
-    }
-    float ms = 0.0f;
-    NTR_HIP(ev.elapsed(0, 1, &ms));
+    });
     result->numEntries = numEntries;
     result->lanesPerLeaf = group;
     result->numNodes = (int64_t)numEntries + (int64_t)inner;
@@ -306,7 +270,7 @@ int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries, v
     result->numRows = (int64_t)rows;
     result->firstBadEntry = err ? (int32_t)~bad : -1;
     result->errBits = (int32_t)err;
-    result->seconds = ms * 1e-3f;
+    result->seconds = seconds;
     if (err)
         return set_error(NTR_ERR_LAYOUT, "%s: entry %d: malformed tree (error bits 0x%x over all entries: 1 child link, 2 leaf row outside "
                          "the extents, 4 triangle index, 8 vertex index out of range); the parts above such a place were left as they were, "

@@ -16,7 +16,12 @@
 // The arrival protocol and its memory ordering are bvh_climb.h's and are not restated.  A bad part is never followed, as in
 // tlas_refit_kernels.hip: a link that names no slot, a leaf link beyond the instances and an instance whose blas index (key 0's) names
 // no BLAS are skipped; such an instance keeps its record but its key entry is written all the same (it depends on the transforms only).
-// No host read-back unless a result is asked for, and no memset node on the asynchronous path.
+// What the two binary top-level refits share is stated once: the error bits, the load of node 0, the leaf's climb, the scene-box write,
+// the scratch layout, the argument checks and the range table are tlas_refit_parts.h's (this entry point adds its second instance array
+// and the motion keys where they stand in the order of the checks); the held range table, the refusals of a captured call and the
+// bracket of the blocking form are refit_launch.h's.  Two parts are deliberately NOT shared, because a kernel built
+// over the shared function came out with other code (scripts/kernel_isa_diff.sh): the classification of a slot's two links in
+// tmr_prepare, as in tlr_prepare, and tmr_prepare's wave fold, which has the moving counter between the shared fold's statements.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -31,16 +36,16 @@
 #include "device_scratch.h"
 #include "instanced_bvh.h"
 #include "level_build.h"
+#include "refit_launch.h"
+#include "tlas_refit_parts.h"
 #include "tlas_world_box.h"
 
 namespace ntr {
 namespace {
 
 constexpr int TMR_BLOCK = 256;
-enum : unsigned int { TMR_ERR_BLAS = 1u, TMR_ERR_LINK = 2u, TMR_ERR_LEAF = 4u };
 
-// Counters of the blocking form, as tlas_refit_kernels.hip's, and the moving instances
-constexpr int TMR_STAT_SLOTS = 256;
+// A counter slot of the blocking form (refit_launch.h): tlas_refit_kernels.hip's counters and the moving instances
 struct TmrStats {
     unsigned int innerLinks, leafLinks, err, moving;
     unsigned int pad[12];        // a slot per 64-byte line
@@ -48,6 +53,7 @@ struct TmrStats {
 static_assert(sizeof(TmrStats) == 64, "TmrStats must be 64 bytes");
 
 DeviceScratchPool g_tmrPool;
+RefitHeld g_tmrHeld[kMaxDevices];
 
 // objectToWorld of instance i: 48 bytes at the start of a 112-byte struct of a 16-byte aligned array
 __device__ __forceinline__ void tmr_load_key(const NtrInstance* __restrict__ inst, int i, uint4 (&m)[3])
@@ -94,8 +100,8 @@ __device__ __forceinline__ void tmr_write_record(const NtrInstance* __restrict__
 __device__ __forceinline__ void tmr_instance_box(const NtrInstance* __restrict__ inst0, const NtrInstance* __restrict__ inst1, int i,
                                                  const uint4 range, const char* __restrict__ poolNodes, float (&wlo)[3], float (&whi)[3])
 {
-    const float4* nd = (const float4*)(poolNodes + range.x);   // (the host has checked the range against the pool)
-    const float4 n0 = nd[0], n1 = nd[1], nz = nd[2];
+    float4 n0, n1, nz;
+    tlas_load_node0(poolNodes, range, n0, n1, nz);
     uint4 a[3], b[3];
     tmr_load_key(inst0, i, a);
     tmr_load_key(inst1, i, b);
@@ -135,10 +141,10 @@ __global__ __launch_bounds__(TMR_BLOCK) void tmr_prepare(int n, int numSlots, co
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             inner += kind[k] == LINK_INNER ? 1u : 0u;
-            if (kind[k] == LINK_BAD) err |= TMR_ERR_LINK;
+            if (kind[k] == LINK_BAD) err |= TLAS_ERR_LINK;
             if (kind[k] == LINK_LEAF) {
                 leaf += 1u;
-                if (leaf_row(nodes[(size_t)idx * kNodeWords + kLinkWord + k]) >= n) err |= TMR_ERR_LEAF;
+                if (leaf_row(nodes[(size_t)idx * kNodeWords + kLinkWord + k]) >= n) err |= TLAS_ERR_LEAF;
             }
         }
     }
@@ -146,12 +152,13 @@ __global__ __launch_bounds__(TMR_BLOCK) void tmr_prepare(int n, int numSlots, co
         const bool mv = tmr_write_key(inst0, inst1, idx, keys);
         moving = mv ? 1u : 0u;
         const int b = inst0[idx].blas;
-        if (b < 0 || b >= numBlas) err |= TMR_ERR_BLAS;
+        if (b < 0 || b >= numBlas) err |= TLAS_ERR_BLAS;
         else tmr_write_record(inst0, idx, table[b], mv, records);
     }
     if (!stats) return;
-    stats += blockIdx.x % TMR_STAT_SLOTS;
-    // one add per wave and counter
+    stats += blockIdx.x % kRefitStatSlots;
+    // one add per wave and counter: tlas_fold_counters (tlas_refit_parts.h) with `moving` between its statements, and kept as text --
+    // over the shared fold, with the moving counter beside it, the kernel came out with other code (scripts/kernel_isa_diff.sh)
     inner = wave_sum_u32(inner);
     leaf = wave_sum_u32(leaf);
     moving = wave_sum_u32(moving);
@@ -181,29 +188,7 @@ __global__ __launch_bounds__(TMR_BLOCK) void tmr_climb(int n, int numSlots, cons
     if (b < 0 || b >= numBlas) return;
     float wlo[3], whi[3];
     tmr_instance_box(inst0, inst1, i, table[b], poolNodes, wlo, whi);
-    float box[6] = {wlo[0], whi[0], wlo[1], whi[1], wlo[2], whi[2]};
-    rf_publish_box(nodes, node, k, box);
-    float sib[6];
-    climb(
-        node, k, numSlots, nodes, parent, arrive, [&](int pn, int pk) { rf_publish_box(nodes, pn, pk, box); },
-        [&](int nd, int sk) { rf_acquire_box(nodes, nd, sk, sib); },
-        [&](int nd, int) {
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                box[2 * q] = ord_min(box[2 * q], sib[2 * q]);
-                box[2 * q + 1] = ord_max(box[2 * q + 1], sib[2 * q + 1]);
-            }
-            if (nd == 0) {                       // the root reports to no parent
-                if (sceneBox) {
-                    sceneBox[0] = box[0]; sceneBox[1] = box[2]; sceneBox[2] = box[4];
-                    sceneBox[3] = box[1]; sceneBox[4] = box[3]; sceneBox[5] = box[5];
-                }
-                if (sceneCopy) {
-                    sceneCopy[0] = box[0]; sceneCopy[1] = box[2]; sceneCopy[2] = box[4];
-                    sceneCopy[3] = box[1]; sceneCopy[4] = box[3]; sceneCopy[5] = box[5];
-                }
-            }
-        });
+    tlas_leaf_climb(node, k, numSlots, nodes, parent, arrive, wlo, whi, sceneBox, sceneCopy);
 }
 
 // N == 1: one thread
@@ -217,42 +202,15 @@ __global__ __launch_bounds__(64) void tmr_single(const NtrInstance* __restrict__
     if (stats) stats->moving = mv ? 1u : 0u;
     const int b = inst0[0].blas;
     if (b < 0 || b >= numBlas) {
-        if (stats) stats->err = TMR_ERR_BLAS;
+        if (stats) stats->err = TLAS_ERR_BLAS;
         return;
     }
     const uint4 range = table[b];
     tmr_write_record(inst0, 0, range, mv, records);
     float wlo[3], whi[3];
     tmr_instance_box(inst0, inst1, 0, range, poolNodes, wlo, whi);
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        if (sceneBox) { sceneBox[q] = wlo[q]; sceneBox[3 + q] = whi[q]; }
-        if (sceneCopy) { sceneCopy[q] = wlo[q]; sceneCopy[3 + q] = whi[q]; }
-    }
+    tlas_write_scene_box(sceneBox, sceneCopy, wlo, whi);
 }
-
-struct TmrLayout {
-    size_t stats, scene, zeroBytes, table, parent, arrive, end;
-    TmrLayout(int64_t slots, int64_t numBlas)
-    {
-        ScratchCarver c;
-        stats = c.take(sizeof(TmrStats) * TMR_STAT_SLOTS);   // one zeroed block: the counters and the blocking form's scene box
-        scene = c.take(6 * sizeof(float));
-        zeroBytes = c.off;
-        table = c.take((size_t)numBlas * 16);
-        parent = c.take((size_t)slots * 4);
-        arrive = c.take((size_t)slots * 4);
-        end = c.off;
-    }
-};
-
-// What the device's range table holds, per device (tlas_refit_kernels.hip's rule; this unit's pool has a table of its own)
-struct TmrUploaded {
-    bool valid = false;
-    int slots = 0;
-    std::vector<uint32_t> table;
-};
-TmrUploaded g_tmrUploaded[kMaxDevices];
 
 }  // namespace
 }  // namespace ntr
@@ -268,100 +226,55 @@ int ntr_tlas_motion_refit(int32_t numInstances, const NtrInstance* d_instances0,
 {
     const char* fn = "ntr_tlas_motion_refit";
     if (result) memset(result, 0, sizeof(*result));
-    if (numInstances < 1 || (int64_t)numInstances - 1 > kMaxNodes || numBlas < 1 || !d_instances0 || !d_instances1 || !blasRanges ||
-        !d_poolNodes || !d_records || !d_motionKeys || (!d_tlasNodes && numInstances > 1))
-        return set_error(NTR_ERR_INVALID, "%s: bad arguments (1 <= numInstances <= %lld, numBlas >= 1, non-null buffers)", fn,
-                         (long long)kMaxNodes + 1);
+    const TlasBinaryArgs args = {numInstances, d_instances0, numBlas, blasRanges, d_poolNodes, poolNodesBytes, d_tlasNodes, tlasNodesBytes,
+                                 rootLink, d_records, recordsCapacity};
+    if (const int rc = tlas_binary_check_extents(fn, args, d_instances1 && d_motionKeys)) return rc;
     const int n = numInstances, slots = numInstances - 1;
-    if (tlasNodesBytes != (int64_t)kNodeBytes * slots)
-        return set_error(NTR_ERR_INVALID, "%s: tlasNodesBytes must be 64 * (numInstances - 1), the extent ntr_tlas_build reported", fn);
-    if (rootLink != (n == 1 ? leaf_link(0) : 0))
-        return set_error(NTR_ERR_INVALID, "%s: rootLink must be 0, or ~0 for one instance, as ntr_tlas_build reported it", fn);
-    if (recordsCapacity < (int64_t)kRecordBytes * n) return set_error(NTR_ERR_INVALID, "%s: recordsCapacity below 64 * numInstances", fn);
     if (motionKeysCapacity < (int64_t)kMotionKeyBytes * n)
         return set_error(NTR_ERR_INVALID, "%s: motionKeysCapacity below 128 * numInstances", fn);
-    if (((uintptr_t)d_poolNodes | (uintptr_t)d_records | (uintptr_t)d_tlasNodes | (uintptr_t)d_instances0 | (uintptr_t)d_instances1 |
-         (uintptr_t)d_motionKeys) & 15u)
-        return set_error(NTR_ERR_INVALID, "%s: the buffers must be 16-byte aligned", fn);
-    if (const int rc = check_pool_bytes(fn, "poolNodesBytes", poolNodesBytes, kNodeBytes)) return rc;
-    std::vector<uint32_t> table(4 * (size_t)numBlas);
-    for (int k = 0; k < numBlas; k++) {
-        if (const int rc = check_blas_range(fn, k, blasRanges[k], poolNodesBytes)) return rc;
-        table[4 * k] = (uint32_t)blasRanges[k].nodesOffset;
-        table[4 * k + 1] = (uint32_t)(blasRanges[k].triWoopOffset / kRowBytes);
-        table[4 * k + 2] = (uint32_t)blasRanges[k].nodesBytes;
-        table[4 * k + 3] = 0u;
-    }
+    const TlasRefitLayout lay(slots, numBlas);
+    RefitTable held = {1, {}, {lay.table, 0}, {slots, 0}};
+    if (const int rc = tlas_binary_range_table(fn, args, (uintptr_t)d_instances1 | (uintptr_t)d_motionKeys, held.words[0])) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    NTR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) return set_error(NTR_ERR_INVALID, "device index %d out of range", dev);
-    const TmrLayout lay(slots, numBlas);
-    TmrUploaded& up = g_tmrUploaded[dev];
-    if (g_tmrPool.held() < lay.end) up.valid = false;   // released, never reserved, or about to be regrown
-    const bool same = up.valid && up.table == table;
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && result) return set_error(NTR_ERR_INVALID, "%s: a captured call cannot read a result back (pass result = NULL)", fn);
-    if (capturing && !(same && up.slots == slots))
-        return set_error(NTR_ERR_INVALID, "%s: a captured call uploads and allocates nothing: the device must hold this range table already "
-                         "-- make one uncaptured call with the same ranges and instance count first (and none with others, and no "
-                         "ntr_lbvh_release_workspace, between it and the capture)", fn);
     void* base = nullptr;
-    if (const int rc = g_tmrPool.reserve(lay.end, &base)) return rc;
+    if (const int rc = refit_hold_table(fn, kRefitRangeWords, g_tmrPool, g_tmrHeld, s, result != nullptr, lay.end, held, &base)) return rc;
     uint4* d_table = at<uint4>(base, lay.table);
     unsigned int *parent = at<unsigned int>(base, lay.parent), *arrive = at<unsigned int>(base, lay.arrive);
-    if (!same) {
-        // the host copy is what the upload reads and what the next call compares with: the upload is waited for
-        up.valid = false;
-        up.table.swap(table);
-        NTR_HIP(hipMemcpyAsync(d_table, up.table.data(), up.table.size() * 4, hipMemcpyHostToDevice, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        up.valid = true;
-    }
-    if (!capturing) up.slots = slots;
     TmrStats* stats = result ? at<TmrStats>(base, lay.stats) : nullptr;
     float* sceneCopy = result ? at<float>(base, lay.scene) : nullptr;
 
-    StreamEvents<2> ev(s);
-    if (result) {
-        NTR_HIP(ev.create());
-        NTR_HIP(ev.record(0));
-        NTR_HIP(hipMemsetAsync(at<char>(base, 0), 0, lay.zeroBytes, s));
-    }
-    if (n == 1) {
-        hipLaunchKernelGGL(tmr_single, dim3(1), dim3(64), 0, s, d_instances0, d_instances1, (int)numBlas, (const uint4*)d_table,
-                           (const char*)d_poolNodes, (uint4*)d_records, (uint4*)d_motionKeys, d_sceneBox, sceneCopy, stats);
-    } else {
-        hipLaunchKernelGGL(tmr_prepare, dim3((n + TMR_BLOCK - 1) / TMR_BLOCK), dim3(TMR_BLOCK), 0, s, n, slots, d_instances0, d_instances1,
-                           (int)numBlas, (const uint4*)d_table, (const int*)d_tlasNodes, (uint4*)d_records, (uint4*)d_motionKeys, parent, arrive,
-                           stats);
-        hipLaunchKernelGGL(tmr_climb, dim3((unsigned int)((2ll * slots + TMR_BLOCK - 1) / TMR_BLOCK)), dim3(TMR_BLOCK), 0, s, n, slots,
-                           d_instances0, d_instances1, (int)numBlas, (const uint4*)d_table, (const char*)d_poolNodes, (int*)d_tlasNodes,
-                           (const unsigned int*)parent, arrive, d_sceneBox, sceneCopy);
-    }
-    NTR_HIP(hipGetLastError());
-    if (!result) return NTR_OK;
+    std::vector<char> host;
+    float seconds = 0.0f;
+    const int rc = refit_bracket(s, result != nullptr, base, lay.zeroBytes, &host, &seconds, [&] {
+        if (n == 1) {
+            hipLaunchKernelGGL(tmr_single, dim3(1), dim3(64), 0, s, d_instances0, d_instances1, (int)numBlas, (const uint4*)d_table,
+                               (const char*)d_poolNodes, (uint4*)d_records, (uint4*)d_motionKeys, d_sceneBox, sceneCopy, stats);
+        } else {
+            hipLaunchKernelGGL(tmr_prepare, dim3((n + TMR_BLOCK - 1) / TMR_BLOCK), dim3(TMR_BLOCK), 0, s, n, slots, d_instances0, d_instances1,
+                               (int)numBlas, (const uint4*)d_table, (const int*)d_tlasNodes, (uint4*)d_records, (uint4*)d_motionKeys, parent, arrive,
+                               stats);
+            hipLaunchKernelGGL(tmr_climb, dim3((unsigned int)((2ll * slots + TMR_BLOCK - 1) / TMR_BLOCK)), dim3(TMR_BLOCK), 0, s, n, slots,
+                               d_instances0, d_instances1, (int)numBlas, (const uint4*)d_table, (const char*)d_poolNodes, (int*)d_tlasNodes,
+                               (const unsigned int*)parent, arrive, d_sceneBox, sceneCopy);
+        }
+    });
+    if (rc != NTR_OK || !result) return rc;
 
-    NTR_HIP(ev.record(1));
-    std::vector<char> host(lay.zeroBytes);       // the copy is waited for right here
-    NTR_HIP(hipMemcpyAsync(host.data(), at<char>(base, 0), lay.zeroBytes, hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
     uint64_t inner = 0, leafLinks = 0, moving = 0;
     unsigned int err = 0;
-    const TmrStats* hs = (const TmrStats*)(host.data() + lay.stats);
-    for (int k = 0; k < TMR_STAT_SLOTS; k++) { inner += hs[k].innerLinks; leafLinks += hs[k].leafLinks; moving += hs[k].moving; err |= hs[k].err; }
-    float ms = 0.0f;
-    NTR_HIP(ev.elapsed(0, 1, &ms));
+    refit_fold_slots<TmrStats>(host.data() + lay.stats, [&](const TmrStats& v) {
+        inner += v.innerLinks; leafLinks += v.leafLinks; moving += v.moving; err |= v.err;
+    });
     NtrTlasRefitResult& rr = result->refit;
     rr.numNodes = n == 1 ? 0 : (int32_t)(1 + inner);
     rr.numLeaves = n == 1 ? 1 : (int32_t)leafLinks;
     rr.errBits = (int32_t)err;
     memcpy(rr.sceneMin, host.data() + lay.scene, 3 * sizeof(float));
     memcpy(rr.sceneMax, host.data() + lay.scene + 3 * sizeof(float), 3 * sizeof(float));
-    rr.seconds = ms * 1e-3f;
+    rr.seconds = seconds;
     result->numMoving = (int32_t)moving;
-    if (err & TMR_ERR_BLAS)
+    if (err & TLAS_ERR_BLAS)
         return set_error(NTR_ERR_INVALID, "%s: an instance's blas index lies outside [0, %d) (error bits 0x%x); its record, its leaf box and "
                          "the boxes above it were left as they were, everything else was refitted", fn, (int)numBlas, err);
     if (err)

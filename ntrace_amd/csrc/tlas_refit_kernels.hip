@@ -8,16 +8,18 @@
 //   tlr_climb     one thread per child slot: a leaf link ~i forms instance i's world box (tlr_world_box), publishes it into the node
 //                 and runs the climb of bvh_climb.h with the integer-order union
 //   tlr_single    N == 1 has no node: record 0 and the scene box in one small launch
-// tlr_world_box (tlas_world_box.h: the wide top-level refit shares it) holds the statements of tl_boxes (tlas_build_kernels.hip), which
-// does NOT call it: built over a shared function tl_boxes
-// came out with other code than before (the operands of twelve additions commuted; scripts/kernel_isa_diff.sh), so that file was left
-// as it was.  A change to the world-box rule is made in both places; tests/test_tlas_refit_gpu.py demands that the refit
-// of a fresh build changes no byte at every size it runs.
+// tlr_world_box (tlas_world_box.h: the wide and the motion refit share it) holds the statements of tl_boxes (tlas_build_kernels.hip),
+// which does NOT call it: built over a shared function, tl_boxes came out with other code than before (the operands of twelve additions
+// commuted; scripts/kernel_isa_diff.sh), so that file was left as it was.  A change to the world-box rule is made in both
+// places; tests/test_tlas_refit_gpu.py demands that the refit of a fresh build changes no byte at every size it runs.
 // The arrival protocol and its memory ordering are bvh_climb.h's and are not restated.  A bad part is never followed: a link that names
 // no slot, a leaf link beyond the instances and an instance whose blas index names no BLAS are skipped, so their ancestors keep an
 // arrival short and stay as they are; everything else is refitted completely.
-// No host read-back unless a result is asked for, and no memset node on the asynchronous path: the first launch re-initialises the
-// arrival counters, and the counters of the blocking form, which is never captured, are the one memset.
+// What the three top-level refits share on the device, the argument checks and the range table are tlas_refit_parts.h's; the held
+// table, the refusals of a captured call and the bracket of the blocking form are refit_launch.h's.  One part is
+// deliberately NOT shared: the classification of a node slot's two links in tlr_prepare (and, word for word, in tmr_prepare) -- built
+// over a shared function, by reference, by value or over the kinds alone, the kernel came out with other code (other branches around
+// the leaf_row test; scripts/kernel_isa_diff.sh), so both kernels keep the text.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -32,17 +34,16 @@
 #include "device_scratch.h"
 #include "instanced_bvh.h"
 #include "level_build.h"
+#include "refit_launch.h"
+#include "tlas_refit_parts.h"
 #include "tlas_world_box.h"
 
 namespace ntr {
 namespace {
 
 constexpr int TLR_BLOCK = 256;
-enum : unsigned int { TLR_ERR_BLAS = 1u, TLR_ERR_LINK = 2u, TLR_ERR_LEAF = 4u };
 
-// Counters of the blocking form, as bvh_refit_batch_kernels.hip's: a workgroup adds to the slot of its number modulo TLR_STAT_SLOTS and
-// the host sums the slots.  The scene box of the blocking form (6 floats, zero while the root has not been refitted) lies behind them.
-constexpr int TLR_STAT_SLOTS = 256;
+// A counter slot of the blocking form (refit_launch.h)
 struct TlrStats {
     unsigned int innerLinks, leafLinks, err;
     unsigned int pad[13];        // a slot per 64-byte line
@@ -50,6 +51,7 @@ struct TlrStats {
 static_assert(sizeof(TlrStats) == 64, "TlrStats must be 64 bytes");
 
 DeviceScratchPool g_tlrPool;
+RefitHeld g_tlrHeld[kMaxDevices];
 
 // Record i (instanced_bvh.h) of an instance whose blas index the caller has checked; range is the table's entry of its BLAS
 __device__ __forceinline__ void tlr_write_record(const NtrInstance* __restrict__ inst, int i, const uint4 range, uint4* __restrict__ records)
@@ -66,8 +68,8 @@ __device__ __forceinline__ void tlr_write_record(const NtrInstance* __restrict__
 __device__ __forceinline__ void tlr_instance_box(const NtrInstance* __restrict__ inst, int i, const uint4 range, const char* __restrict__ poolNodes,
                                                  float (&wlo)[3], float (&whi)[3])
 {
-    const float4* nd = (const float4*)(poolNodes + range.x);   // (the host has checked the range against the pool)
-    const float4 n0 = nd[0], n1 = nd[1], nz = nd[2];
+    float4 n0, n1, nz;
+    tlas_load_node0(poolNodes, range, n0, n1, nz);
     float m[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) m[k] = inst[i].objectToWorld[k];
@@ -87,29 +89,21 @@ __global__ __launch_bounds__(TLR_BLOCK) void tlr_prepare(int n, int numSlots, co
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             inner += kind[k] == LINK_INNER ? 1u : 0u;
-            if (kind[k] == LINK_BAD) err |= TLR_ERR_LINK;
+            if (kind[k] == LINK_BAD) err |= TLAS_ERR_LINK;
             if (kind[k] == LINK_LEAF) {
                 leaf += 1u;
-                if (leaf_row(nodes[(size_t)idx * kNodeWords + kLinkWord + k]) >= n) err |= TLR_ERR_LEAF;
+                if (leaf_row(nodes[(size_t)idx * kNodeWords + kLinkWord + k]) >= n) err |= TLAS_ERR_LEAF;
             }
         }
     }
     if (idx < n) {
         const int b = inst[idx].blas;
-        if (b < 0 || b >= numBlas) err |= TLR_ERR_BLAS;
+        if (b < 0 || b >= numBlas) err |= TLAS_ERR_BLAS;
         else tlr_write_record(inst, idx, table[b], records);
     }
     if (!stats) return;
-    stats += blockIdx.x % TLR_STAT_SLOTS;
-    // one add per wave and counter
-    inner = wave_sum_u32(inner);
-    leaf = wave_sum_u32(leaf);
-    err = wave_or_u32(err);
-    if ((threadIdx.x & 63) == 0) {
-        if (inner) atomicAdd(&stats->innerLinks, inner);
-        if (leaf) atomicAdd(&stats->leafLinks, leaf);
-        if (err) atomicOr(&stats->err, err);
-    }
+    stats += blockIdx.x % kRefitStatSlots;
+    tlas_fold_counters(stats, inner, leaf, err);
 }
 
 __global__ __launch_bounds__(TLR_BLOCK) void tlr_climb(int n, int numSlots, const NtrInstance* __restrict__ inst, int numBlas,
@@ -128,29 +122,7 @@ __global__ __launch_bounds__(TLR_BLOCK) void tlr_climb(int n, int numSlots, cons
     if (b < 0 || b >= numBlas) return;
     float wlo[3], whi[3];
     tlr_instance_box(inst, i, table[b], poolNodes, wlo, whi);
-    float box[6] = {wlo[0], whi[0], wlo[1], whi[1], wlo[2], whi[2]};
-    rf_publish_box(nodes, node, k, box);
-    float sib[6];
-    climb(
-        node, k, numSlots, nodes, parent, arrive, [&](int pn, int pk) { rf_publish_box(nodes, pn, pk, box); },
-        [&](int nd, int sk) { rf_acquire_box(nodes, nd, sk, sib); },
-        [&](int nd, int) {
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                box[2 * q] = ord_min(box[2 * q], sib[2 * q]);
-                box[2 * q + 1] = ord_max(box[2 * q + 1], sib[2 * q + 1]);
-            }
-            if (nd == 0) {                       // the root reports to no parent
-                if (sceneBox) {
-                    sceneBox[0] = box[0]; sceneBox[1] = box[2]; sceneBox[2] = box[4];
-                    sceneBox[3] = box[1]; sceneBox[4] = box[3]; sceneBox[5] = box[5];
-                }
-                if (sceneCopy) {
-                    sceneCopy[0] = box[0]; sceneCopy[1] = box[2]; sceneCopy[2] = box[4];
-                    sceneCopy[3] = box[1]; sceneCopy[4] = box[3]; sceneCopy[5] = box[5];
-                }
-            }
-        });
+    tlas_leaf_climb(node, k, numSlots, nodes, parent, arrive, wlo, whi, sceneBox, sceneCopy);
 }
 
 // N == 1: one thread
@@ -161,43 +133,15 @@ __global__ __launch_bounds__(64) void tlr_single(const NtrInstance* __restrict__
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const int b = inst[0].blas;
     if (b < 0 || b >= numBlas) {
-        if (stats) stats->err = TLR_ERR_BLAS;
+        if (stats) stats->err = TLAS_ERR_BLAS;
         return;
     }
     const uint4 range = table[b];
     tlr_write_record(inst, 0, range, records);
     float wlo[3], whi[3];
     tlr_instance_box(inst, 0, range, poolNodes, wlo, whi);
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        if (sceneBox) { sceneBox[q] = wlo[q]; sceneBox[3 + q] = whi[q]; }
-        if (sceneCopy) { sceneCopy[q] = wlo[q]; sceneCopy[3 + q] = whi[q]; }
-    }
+    tlas_write_scene_box(sceneBox, sceneCopy, wlo, whi);
 }
-
-struct TlrLayout {
-    size_t stats, scene, zeroBytes, table, parent, arrive, end;
-    TlrLayout(int64_t slots, int64_t numBlas)
-    {
-        ScratchCarver c;
-        stats = c.take(sizeof(TlrStats) * TLR_STAT_SLOTS);   // one zeroed block: the counters and the blocking form's scene box
-        scene = c.take(6 * sizeof(float));
-        zeroBytes = c.off;
-        table = c.take((size_t)numBlas * 16);
-        parent = c.take((size_t)slots * 4);
-        arrive = c.take((size_t)slots * 4);
-        end = c.off;
-    }
-};
-
-// What the device's range table holds, per device: the table the last uncaptured call uploaded and that call's node count.  valid is
-// cleared whenever the pool has been released or has to grow, so a table on the host never vouches for bytes that are gone.
-struct TlrUploaded {
-    bool valid = false;
-    int slots = 0;
-    std::vector<uint32_t> table;
-};
-TlrUploaded g_tlrUploaded[kMaxDevices];
 
 }  // namespace
 }  // namespace ntr
@@ -212,95 +156,48 @@ int ntr_tlas_refit(int32_t numInstances, const NtrInstance* d_instances, int32_t
 {
     const char* fn = "ntr_tlas_refit";
     if (result) memset(result, 0, sizeof(*result));
-    if (numInstances < 1 || (int64_t)numInstances - 1 > kMaxNodes || numBlas < 1 || !d_instances || !blasRanges || !d_poolNodes || !d_records ||
-        (!d_tlasNodes && numInstances > 1))
-        return set_error(NTR_ERR_INVALID, "%s: bad arguments (1 <= numInstances <= %lld, numBlas >= 1, non-null buffers)", fn,
-                         (long long)kMaxNodes + 1);
+    const TlasBinaryArgs args = {numInstances, d_instances, numBlas, blasRanges, d_poolNodes, poolNodesBytes, d_tlasNodes, tlasNodesBytes,
+                                 rootLink, d_records, recordsCapacity};
+    if (const int rc = tlas_binary_check_extents(fn, args)) return rc;
     const int n = numInstances, slots = numInstances - 1;
-    if (tlasNodesBytes != (int64_t)kNodeBytes * slots)
-        return set_error(NTR_ERR_INVALID, "%s: tlasNodesBytes must be 64 * (numInstances - 1), the extent ntr_tlas_build reported", fn);
-    if (rootLink != (n == 1 ? leaf_link(0) : 0))
-        return set_error(NTR_ERR_INVALID, "%s: rootLink must be 0, or ~0 for one instance, as ntr_tlas_build reported it", fn);
-    if (recordsCapacity < (int64_t)kRecordBytes * n) return set_error(NTR_ERR_INVALID, "%s: recordsCapacity below 64 * numInstances", fn);
-    if (((uintptr_t)d_poolNodes | (uintptr_t)d_records | (uintptr_t)d_tlasNodes | (uintptr_t)d_instances) & 15u)
-        return set_error(NTR_ERR_INVALID, "%s: the buffers must be 16-byte aligned", fn);
-    if (const int rc = check_pool_bytes(fn, "poolNodesBytes", poolNodesBytes, kNodeBytes)) return rc;
-    std::vector<uint32_t> table(4 * (size_t)numBlas);
-    for (int k = 0; k < numBlas; k++) {
-        if (const int rc = check_blas_range(fn, k, blasRanges[k], poolNodesBytes)) return rc;
-        table[4 * k] = (uint32_t)blasRanges[k].nodesOffset;
-        table[4 * k + 1] = (uint32_t)(blasRanges[k].triWoopOffset / kRowBytes);
-        table[4 * k + 2] = (uint32_t)blasRanges[k].nodesBytes;
-        table[4 * k + 3] = 0u;
-    }
+    const TlasRefitLayout lay(slots, numBlas);
+    RefitTable held = {1, {}, {lay.table, 0}, {slots, 0}};
+    if (const int rc = tlas_binary_range_table(fn, args, 0, held.words[0])) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    NTR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) return set_error(NTR_ERR_INVALID, "device index %d out of range", dev);
-    const TlrLayout lay(slots, numBlas);
-    TlrUploaded& up = g_tlrUploaded[dev];
-    if (g_tlrPool.held() < lay.end) up.valid = false;   // released, never reserved, or about to be regrown
-    const bool same = up.valid && up.table == table;
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && result) return set_error(NTR_ERR_INVALID, "%s: a captured call cannot read a result back (pass result = NULL)", fn);
-    if (capturing && !(same && up.slots == slots))
-        return set_error(NTR_ERR_INVALID, "%s: a captured call uploads and allocates nothing: the device must hold this range table already "
-                         "-- make one uncaptured call with the same ranges and instance count first (and none with others, and no "
-                         "ntr_lbvh_release_workspace, between it and the capture)", fn);
     void* base = nullptr;
-    if (const int rc = g_tlrPool.reserve(lay.end, &base)) return rc;
+    if (const int rc = refit_hold_table(fn, kRefitRangeWords, g_tlrPool, g_tlrHeld, s, result != nullptr, lay.end, held, &base)) return rc;
     uint4* d_table = at<uint4>(base, lay.table);
     unsigned int *parent = at<unsigned int>(base, lay.parent), *arrive = at<unsigned int>(base, lay.arrive);
-    if (!same) {
-        // the host copy is what the upload reads and what the next call compares with: the upload is waited for, so the copy never
-        // changes under it.  A frame loop over one pool pays this once
-        up.valid = false;
-        up.table.swap(table);
-        NTR_HIP(hipMemcpyAsync(d_table, up.table.data(), up.table.size() * 4, hipMemcpyHostToDevice, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        up.valid = true;
-    }
-    if (!capturing) up.slots = slots;
     TlrStats* stats = result ? at<TlrStats>(base, lay.stats) : nullptr;
     float* sceneCopy = result ? at<float>(base, lay.scene) : nullptr;
 
-    StreamEvents<2> ev(s);
-    if (result) {
-        NTR_HIP(ev.create());
-        NTR_HIP(ev.record(0));
-        NTR_HIP(hipMemsetAsync(at<char>(base, 0), 0, lay.zeroBytes, s));
-    }
-    if (n == 1) {
-        hipLaunchKernelGGL(tlr_single, dim3(1), dim3(64), 0, s, d_instances, (int)numBlas, (const uint4*)d_table, (const char*)d_poolNodes,
-                           (uint4*)d_records, d_sceneBox, sceneCopy, stats);
-    } else {
-        hipLaunchKernelGGL(tlr_prepare, dim3((n + TLR_BLOCK - 1) / TLR_BLOCK), dim3(TLR_BLOCK), 0, s, n, slots, d_instances, (int)numBlas,
-                           (const uint4*)d_table, (const int*)d_tlasNodes, (uint4*)d_records, parent, arrive, stats);
-        hipLaunchKernelGGL(tlr_climb, dim3((unsigned int)((2ll * slots + TLR_BLOCK - 1) / TLR_BLOCK)), dim3(TLR_BLOCK), 0, s, n, slots, d_instances,
-                           (int)numBlas, (const uint4*)d_table, (const char*)d_poolNodes, (int*)d_tlasNodes, (const unsigned int*)parent, arrive,
-                           d_sceneBox, sceneCopy);
-    }
-    NTR_HIP(hipGetLastError());
-    if (!result) return NTR_OK;
+    std::vector<char> host;
+    float seconds = 0.0f;
+    const int rc = refit_bracket(s, result != nullptr, base, lay.zeroBytes, &host, &seconds, [&] {
+        if (n == 1) {
+            hipLaunchKernelGGL(tlr_single, dim3(1), dim3(64), 0, s, d_instances, (int)numBlas, (const uint4*)d_table, (const char*)d_poolNodes,
+                               (uint4*)d_records, d_sceneBox, sceneCopy, stats);
+        } else {
+            hipLaunchKernelGGL(tlr_prepare, dim3((n + TLR_BLOCK - 1) / TLR_BLOCK), dim3(TLR_BLOCK), 0, s, n, slots, d_instances, (int)numBlas,
+                               (const uint4*)d_table, (const int*)d_tlasNodes, (uint4*)d_records, parent, arrive, stats);
+            hipLaunchKernelGGL(tlr_climb, dim3((unsigned int)((2ll * slots + TLR_BLOCK - 1) / TLR_BLOCK)), dim3(TLR_BLOCK), 0, s, n, slots, d_instances,
+                               (int)numBlas, (const uint4*)d_table, (const char*)d_poolNodes, (int*)d_tlasNodes, (const unsigned int*)parent, arrive,
+                               d_sceneBox, sceneCopy);
+        }
+    });
+    if (rc != NTR_OK || !result) return rc;
 
-    NTR_HIP(ev.record(1));
-    std::vector<char> host(lay.zeroBytes);       // the copy is waited for right here
-    NTR_HIP(hipMemcpyAsync(host.data(), at<char>(base, 0), lay.zeroBytes, hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
     uint64_t inner = 0, leafLinks = 0;
     unsigned int err = 0;
-    const TlrStats* hs = (const TlrStats*)(host.data() + lay.stats);
-    for (int k = 0; k < TLR_STAT_SLOTS; k++) { inner += hs[k].innerLinks; leafLinks += hs[k].leafLinks; err |= hs[k].err; }
-    float ms = 0.0f;
-    NTR_HIP(ev.elapsed(0, 1, &ms));
+    refit_fold_slots<TlrStats>(host.data() + lay.stats, [&](const TlrStats& v) { inner += v.innerLinks; leafLinks += v.leafLinks; err |= v.err; });
     result->numNodes = n == 1 ? 0 : (int32_t)(1 + inner);
     result->numLeaves = n == 1 ? 1 : (int32_t)leafLinks;
     result->errBits = (int32_t)err;
     memcpy(result->sceneMin, host.data() + lay.scene, 3 * sizeof(float));
     memcpy(result->sceneMax, host.data() + lay.scene + 3 * sizeof(float), 3 * sizeof(float));
-    result->seconds = ms * 1e-3f;
-    if (err & TLR_ERR_BLAS)
+    result->seconds = seconds;
+    if (err & TLAS_ERR_BLAS)
         return set_error(NTR_ERR_INVALID, "%s: an instance's blas index lies outside [0, %d) (error bits 0x%x); its record, its leaf box and "
                          "the boxes above it were left as they were, everything else was refitted", fn, (int)numBlas, err);
     if (err)

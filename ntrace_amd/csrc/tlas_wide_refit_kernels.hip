@@ -12,8 +12,9 @@
 // The arrival protocol and its memory ordering are wide_climb.h's and are not restated.  A bad part is never followed: a link that names
 // no wide node, a leaf link beyond the instances and an instance whose blas index names no BLAS are skipped, so their ancestors keep an
 // arrival short and stay as they are; everything else is refitted completely.
-// No host read-back unless a result is asked for, and no memset node on the asynchronous path: the first launch re-initialises the
-// arrival counters, and the counters of the blocking form, which is never captured, are the one memset.
+// The error bits, the wave fold of the counters, the scene-box write and the scratch layout are tlas_refit_parts.h's; the held range
+// table, the refusals of a captured call and the bracket of the blocking form are refit_launch.h's.  The 4-wide
+// classification of tlw_prepare, the checks and the table (wide ranges beside the binary ones) are this unit's own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -26,6 +27,8 @@
 #include "device_scratch.h"
 #include "instanced_wide_bvh.h"
 #include "level_build.h"
+#include "refit_launch.h"
+#include "tlas_refit_parts.h"
 #include "tlas_world_box.h"
 #include "wide_climb.h"
 
@@ -33,11 +36,8 @@ namespace ntr {
 namespace {
 
 constexpr int TLW_BLOCK = 256;
-enum : unsigned int { TLW_ERR_BLAS = 1u, TLW_ERR_LINK = 2u, TLW_ERR_LEAF = 4u };
 
-// Counters of the blocking form, as tlas_refit_kernels.hip's; the scene box of the blocking form (6 floats, zero while the root has not
-// been refitted) lies behind them.
-constexpr int TLW_STAT_SLOTS = 256;
+// A counter slot of the blocking form (refit_launch.h), as tlas_refit_kernels.hip's
 struct TlwStats {
     unsigned int innerLinks, leafLinks, err;
     unsigned int pad[13];        // a slot per 64-byte line
@@ -45,6 +45,7 @@ struct TlwStats {
 static_assert(sizeof(TlwStats) == 64, "TlwStats must be 64 bytes");
 
 DeviceScratchPool g_tlwPool;
+RefitHeld g_tlwHeld[kMaxDevices];
 
 // The world box of instance i, whose blas index the caller has checked, from the current root of its wide BLAS: range.x is the wide
 // BLAS's offset in the wide pool (the host has checked the range against the pool).  -> false: the root's count word lies outside 2..4
@@ -82,33 +83,25 @@ __global__ __launch_bounds__(TLW_BLOCK) void tlw_prepare(int n, int numNodes, co
     unsigned int inner = 0, leaf = 0, err = 0;
     if (idx < numNodes) {
         int kind[kWideChildren];
-        if (!wide_topology_node(idx, numNodes, nodes, parent, arrive, kind)) err |= TLW_ERR_LINK;
+        if (!wide_topology_node(idx, numNodes, nodes, parent, arrive, kind)) err |= TLAS_ERR_LINK;
 #pragma unroll
         for (int k = 0; k < kWideChildren; k++) {
             inner += kind[k] == LINK_INNER ? 1u : 0u;
-            if (kind[k] == LINK_BAD) err |= TLW_ERR_LINK;
+            if (kind[k] == LINK_BAD) err |= TLAS_ERR_LINK;
             if (kind[k] == LINK_LEAF) {
                 leaf += 1u;
-                if (leaf_row(nodes[(size_t)idx * kWideWords + kWideLinkWord + k]) >= n) err |= TLW_ERR_LEAF;
+                if (leaf_row(nodes[(size_t)idx * kWideWords + kWideLinkWord + k]) >= n) err |= TLAS_ERR_LEAF;
             }
         }
     }
     if (idx < n) {
         const int b = inst[idx].blas;
-        if (b < 0 || b >= numBlas) err |= TLW_ERR_BLAS;
+        if (b < 0 || b >= numBlas) err |= TLAS_ERR_BLAS;
         wide_write_record(inst, idx, numBlas, table, records);   // (with the empty extent for such an instance)
     }
     if (!stats) return;
-    stats += blockIdx.x % TLW_STAT_SLOTS;
-    // one add per wave and counter
-    inner = wave_sum_u32(inner);
-    leaf = wave_sum_u32(leaf);
-    err = wave_or_u32(err);
-    if ((threadIdx.x & 63) == 0) {
-        if (inner) atomicAdd(&stats->innerLinks, inner);
-        if (leaf) atomicAdd(&stats->leafLinks, leaf);
-        if (err) atomicOr(&stats->err, err);
-    }
+    stats += blockIdx.x % kRefitStatSlots;
+    tlas_fold_counters(stats, inner, leaf, err);
 }
 
 __global__ __launch_bounds__(TLW_BLOCK) void tlw_climb(int n, int numNodes, const NtrInstance* __restrict__ inst, int numBlas,
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(TLW_BLOCK) void tlw_climb(int n, int numNodes, cons
     if (link > 0) {                              // an inner slot arrives with the owner of its node
         // a node named by two links: one namer's parent word was overwritten, and that namer says so
         if (stats && is_wide_link(link, numNodes) && !wide_names_child(parent, node, k, link))
-            atomicOr(&stats[blockIdx.x % TLW_STAT_SLOTS].err, TLW_ERR_LINK);
+            atomicOr(&stats[blockIdx.x % kRefitStatSlots].err, TLAS_ERR_LINK);
         return;
     }
     if (link < 0) {                              // (an empty slot keeps its box and only arrives)
@@ -151,41 +144,13 @@ __global__ __launch_bounds__(64) void tlw_single(const NtrInstance* __restrict__
     wide_write_record(inst, 0, numBlas, table, records);
     const int b = inst[0].blas;
     if (b < 0 || b >= numBlas) {
-        if (stats) stats->err = TLW_ERR_BLAS;
+        if (stats) stats->err = TLAS_ERR_BLAS;
         return;
     }
     float wlo[3], whi[3];
     if (!tlw_instance_box(inst, 0, table[b], widePool, wlo, whi)) return;
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        if (sceneBox) { sceneBox[q] = wlo[q]; sceneBox[3 + q] = whi[q]; }
-        if (sceneCopy) { sceneCopy[q] = wlo[q]; sceneCopy[3 + q] = whi[q]; }
-    }
+    tlas_write_scene_box(sceneBox, sceneCopy, wlo, whi);
 }
-
-struct TlwLayout {
-    size_t stats, scene, zeroBytes, table, parent, arrive, end;
-    TlwLayout(int64_t nodes, int64_t numBlas)
-    {
-        ScratchCarver c;
-        stats = c.take(sizeof(TlwStats) * TLW_STAT_SLOTS);   // one zeroed block: the counters and the blocking form's scene box
-        scene = c.take(6 * sizeof(float));
-        zeroBytes = c.off;
-        table = c.take((size_t)numBlas * 16);
-        parent = c.take((size_t)nodes * 4);
-        arrive = c.take((size_t)nodes * 4);
-        end = c.off;
-    }
-};
-
-// What the device's range table holds, per device: the table the last uncaptured call uploaded and that call's counts.  valid is
-// cleared whenever the pool has been released or has to grow, so a table on the host never vouches for bytes that are gone.
-struct TlwUploaded {
-    bool valid = false;
-    int instances = 0, nodes = 0;
-    std::vector<uint32_t> table;
-};
-TlwUploaded g_tlwUploaded[kMaxDevices];
 
 }  // namespace
 }  // namespace ntr
@@ -217,7 +182,10 @@ int ntr_tlas_wide_refit(int32_t numInstances, const NtrInstance* d_instances, in
         return set_error(NTR_ERR_INVALID, "%s: the buffers must be 16-byte aligned", fn);
     if (const int rc = check_wide_pool_bytes(fn, "widePoolNodesBytes", widePoolNodesBytes)) return rc;
     if (!wide_box_granules_aligned()) return set_error(NTR_ERR_INVALID, "%s: a wide box is not three aligned 8-byte granules", fn);
-    std::vector<uint32_t> table(4 * (size_t)numBlas);
+    const TlasRefitLayout lay(numNodes, numBlas);
+    RefitTable held = {1, {}, {lay.table, 0}, {n, numNodes}};
+    std::vector<uint32_t>& table = held.words[0];
+    table = std::vector<uint32_t>(4 * (size_t)numBlas);
     for (int k = 0; k < numBlas; k++) {
         const NtrBlasRange& r = blasRanges[k];
         const NtrWideBlasRange& w = wideRanges[k];
@@ -235,73 +203,40 @@ int ntr_tlas_wide_refit(int32_t numInstances, const NtrInstance* d_instances, in
     }
 
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    NTR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) return set_error(NTR_ERR_INVALID, "device index %d out of range", dev);
-    const TlwLayout lay(numNodes, numBlas);
-    TlwUploaded& up = g_tlwUploaded[dev];
-    if (g_tlwPool.held() < lay.end) up.valid = false;   // released, never reserved, or about to be regrown
-    const bool same = up.valid && up.table == table;
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && result) return set_error(NTR_ERR_INVALID, "%s: a captured call cannot read a result back (pass result = NULL)", fn);
-    if (capturing && !(same && up.instances == n && up.nodes == numNodes))
-        return set_error(NTR_ERR_INVALID, "%s: a captured call uploads and allocates nothing: the device must hold this range table already "
-                         "-- make one uncaptured call with the same ranges, instance count and extent first (and none with others, and no "
-                         "ntr_lbvh_release_workspace, between it and the capture)", fn);
     void* base = nullptr;
-    if (const int rc = g_tlwPool.reserve(lay.end, &base)) return rc;
+    if (const int rc = refit_hold_table(fn, kRefitRangeExtentWords, g_tlwPool, g_tlwHeld, s, result != nullptr, lay.end, held, &base)) return rc;
     uint4* d_table = at<uint4>(base, lay.table);
     unsigned int *parent = at<unsigned int>(base, lay.parent), *arrive = at<unsigned int>(base, lay.arrive);
-    if (!same) {
-        // the host copy is what the upload reads and what the next call compares with: the upload is waited for, so the copy never
-        // changes under it.  A frame loop over one pool pays this once
-        up.valid = false;
-        up.table.swap(table);
-        NTR_HIP(hipMemcpyAsync(d_table, up.table.data(), up.table.size() * 4, hipMemcpyHostToDevice, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        up.valid = true;
-    }
-    if (!capturing) { up.instances = n; up.nodes = numNodes; }
     TlwStats* stats = result ? at<TlwStats>(base, lay.stats) : nullptr;
     float* sceneCopy = result ? at<float>(base, lay.scene) : nullptr;
 
-    StreamEvents<2> ev(s);
-    if (result) {
-        NTR_HIP(ev.create());
-        NTR_HIP(ev.record(0));
-        NTR_HIP(hipMemsetAsync(at<char>(base, 0), 0, lay.zeroBytes, s));
-    }
-    if (n == 1) {
-        hipLaunchKernelGGL(tlw_single, dim3(1), dim3(64), 0, s, d_instances, (int)numBlas, (const uint4*)d_table, (const char*)d_widePoolNodes,
-                           (uint4*)d_wideRecords, d_sceneBox, sceneCopy, stats);
-    } else {
-        const int threads = std::max(n, numNodes);
-        hipLaunchKernelGGL(tlw_prepare, dim3((threads + TLW_BLOCK - 1) / TLW_BLOCK), dim3(TLW_BLOCK), 0, s, n, numNodes, d_instances, (int)numBlas,
-                           (const uint4*)d_table, (const int*)d_wideTlasNodes, (uint4*)d_wideRecords, parent, arrive, stats);
-        hipLaunchKernelGGL(tlw_climb, dim3((unsigned int)((4ll * numNodes + TLW_BLOCK - 1) / TLW_BLOCK)), dim3(TLW_BLOCK), 0, s, n, numNodes,
-                           d_instances, (int)numBlas, (const uint4*)d_table, (const char*)d_widePoolNodes, (int*)d_wideTlasNodes,
-                           (const unsigned int*)parent, arrive, d_sceneBox, sceneCopy, stats);
-    }
-    NTR_HIP(hipGetLastError());
-    if (!result) return NTR_OK;
+    std::vector<char> host;
+    float seconds = 0.0f;
+    const int rc = refit_bracket(s, result != nullptr, base, lay.zeroBytes, &host, &seconds, [&] {
+        if (n == 1) {
+            hipLaunchKernelGGL(tlw_single, dim3(1), dim3(64), 0, s, d_instances, (int)numBlas, (const uint4*)d_table, (const char*)d_widePoolNodes,
+                               (uint4*)d_wideRecords, d_sceneBox, sceneCopy, stats);
+        } else {
+            const int threads = std::max(n, numNodes);
+            hipLaunchKernelGGL(tlw_prepare, dim3((threads + TLW_BLOCK - 1) / TLW_BLOCK), dim3(TLW_BLOCK), 0, s, n, numNodes, d_instances, (int)numBlas,
+                               (const uint4*)d_table, (const int*)d_wideTlasNodes, (uint4*)d_wideRecords, parent, arrive, stats);
+            hipLaunchKernelGGL(tlw_climb, dim3((unsigned int)((4ll * numNodes + TLW_BLOCK - 1) / TLW_BLOCK)), dim3(TLW_BLOCK), 0, s, n, numNodes,
+                               d_instances, (int)numBlas, (const uint4*)d_table, (const char*)d_widePoolNodes, (int*)d_wideTlasNodes,
+                               (const unsigned int*)parent, arrive, d_sceneBox, sceneCopy, stats);
+        }
+    });
+    if (rc != NTR_OK || !result) return rc;
 
-    NTR_HIP(ev.record(1));
-    std::vector<char> host(lay.zeroBytes);       // the copy is waited for right here
-    NTR_HIP(hipMemcpyAsync(host.data(), at<char>(base, 0), lay.zeroBytes, hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
     uint64_t inner = 0, leafLinks = 0;
     unsigned int err = 0;
-    const TlwStats* hs = (const TlwStats*)(host.data() + lay.stats);
-    for (int k = 0; k < TLW_STAT_SLOTS; k++) { inner += hs[k].innerLinks; leafLinks += hs[k].leafLinks; err |= hs[k].err; }
-    float ms = 0.0f;
-    NTR_HIP(ev.elapsed(0, 1, &ms));
+    refit_fold_slots<TlwStats>(host.data() + lay.stats, [&](const TlwStats& v) { inner += v.innerLinks; leafLinks += v.leafLinks; err |= v.err; });
     result->numNodes = n == 1 ? 0 : (int32_t)(1 + inner);
     result->numLeaves = n == 1 ? 1 : (int32_t)leafLinks;
     result->errBits = (int32_t)err;
     memcpy(result->sceneMin, host.data() + lay.scene, 3 * sizeof(float));
     memcpy(result->sceneMax, host.data() + lay.scene + 3 * sizeof(float), 3 * sizeof(float));
-    result->seconds = ms * 1e-3f;
-    if (err & TLW_ERR_BLAS)
+    result->seconds = seconds;
+    if (err & TLAS_ERR_BLAS)
         return set_error(NTR_ERR_INVALID, "%s: an instance's blas index lies outside [0, %d) (error bits 0x%x); its record has the empty extent, "
                          "its leaf box and the boxes above it were left as they were, everything else was refitted", fn, (int)numBlas, err);
     if (err)

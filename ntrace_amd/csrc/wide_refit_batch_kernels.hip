@@ -12,8 +12,8 @@
 // never spans two slots, so none spans two BLASes.  The arrival protocol and its memory ordering are wide_climb.h's and are not
 // restated.  A malformed tree is never followed: the thread sets an error bit and stops; entries share no node, so every other entry is
 // refitted completely.
-// No host read-back unless a result is asked for, and no memset node on the asynchronous path: the first launch re-initialises the
-// arrival counters, and the counters of the blocking form, which is never captured, are the one memset.
+// The held entry table, the refusals of a captured call, the bracket of the blocking form and the fold of its counter slots are
+// refit_launch.h's.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -30,6 +30,7 @@
 #include "device_scratch.h"
 #include "instanced_wide_bvh.h"
 #include "level_build.h"
+#include "refit_launch.h"
 #include "wide_climb.h"
 
 namespace ntr {
@@ -48,9 +49,8 @@ struct WrEntry {
 };
 static_assert(sizeof(WrEntry) == 32, "WrEntry must be 32 bytes");
 
-// Counters of the blocking form, as bvh_refit_batch_kernels.hip's: a workgroup adds to the slot of its number modulo WR_STAT_SLOTS and
-// the host sums the slots.  bad is the maximum of ~entry over the entries with an error, so 0 says none and the lowest entry wins.
-constexpr int WR_STAT_SLOTS = 256;
+// A counter slot of the blocking form (refit_launch.h).  bad is the maximum of ~entry over the entries with an error, so 0 says none and the
+// lowest entry wins.
 struct WrStats {
     unsigned int innerLinks, leafLinks, rows, err, bad;
     unsigned int pad[11];        // a slot per 64-byte line
@@ -58,6 +58,7 @@ struct WrStats {
 static_assert(sizeof(WrStats) == 64, "WrStats must be 64 bytes");
 
 DeviceScratchPool g_wrPool;
+RefitHeld g_wrHeld[kMaxDevices];
 
 // The entry of listed node `node` (< starts[numEntries]): the last e with starts[e] <= node.  Every entry has a node, so starts rises strictly.
 __device__ __forceinline__ int wr_entry_of(const int* __restrict__ starts, int numEntries, int node)
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(WR_BLOCK) void wide_refit_prepare(int numEntries, i
         }
     }
     if (!stats) return;
-    stats += blockIdx.x % WR_STAT_SLOTS;
+    stats += blockIdx.x % kRefitStatSlots;
     if (err) atomicMax(&stats->bad, ~(unsigned int)e);   // (rare) the entry is the lane's own: a wave covers several
     // one add per wave and counter
     inner = wave_sum_u32(inner);
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(WR_BLOCK) void wide_refit_climb(int numEntries, int
     if (link > 0 && sub == 0 && is_wide_link(link, E.numNodes) && !wide_names_child(parent + first, node, k, link)) err |= RF_ERR_LINK;
     const unsigned int groupErr = leaf ? (unsigned int)((__ballot(err != 0) >> groupShift) & ((1ull << G) - 1ull)) : 0u;
     if (stats) {                                 // uniform; the whole wave is here: nobody has returned yet
-        WrStats* mine = stats + blockIdx.x % WR_STAT_SLOTS;
+        WrStats* mine = stats + blockIdx.x % kRefitStatSlots;
         if (err) atomicMax(&mine->bad, ~(unsigned int)e);
         const unsigned int waveRows = wave_sum_u32(rows), waveErr = wave_or_u32(err);
         if ((threadIdx.x & 63) == 0) {
@@ -169,7 +170,7 @@ struct WrLayout {
     WrLayout(int64_t entries, int64_t nodes)
     {
         ScratchCarver c;
-        stats = c.take(sizeof(WrStats) * WR_STAT_SLOTS);
+        stats = c.take(sizeof(WrStats) * kRefitStatSlots);
         starts = c.take((size_t)(entries + 1) * 4);
         table = c.take((size_t)entries * sizeof(WrEntry));
         parent = c.take((size_t)nodes * 4);
@@ -177,33 +178,6 @@ struct WrLayout {
         end = c.off;
     }
 };
-
-// What the device's table holds, per device: the table the last call uploaded.  valid is cleared whenever the pool has been released
-// or has to grow (the next call finds it smaller than it needs), so a table on the host never vouches for bytes that are gone.
-struct WrUploaded {
-    bool valid = false;
-    std::vector<int> starts;
-    std::vector<WrEntry> table;
-};
-WrUploaded g_wrUploaded[kMaxDevices];
-
-// Two ranges [off, off + len) of the same buffer overlap: found by a sort over the entries' indices, not a quadratic scan
-template <class Off, class Len>
-int wr_first_overlap(int n, Off off, Len len, int* other)
-{
-    std::vector<int> order((size_t)n);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return off(a) != off(b) ? off(a) < off(b) : a < b; });
-    int bad = -1;
-    for (int i = 1; i < n; i++) {
-        const int p = order[i - 1], q = order[i];
-        if (off(q) < off(p) + len(p)) {
-            const int hiE = std::max(p, q);
-            if (bad < 0 || hiE < bad) { bad = hiE; *other = std::min(p, q); }
-        }
-    }
-    return bad;
-}
 
 }  // namespace
 }  // namespace ntr
@@ -232,8 +206,10 @@ int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, vo
         return set_error(NTR_ERR_INVALID, "%s: the wide pool's nodes and the pool's triWoop must be 16-byte aligned", fn);
     if (!wide_box_granules_aligned()) return set_error(NTR_ERR_INVALID, "%s: a wide box is not three aligned 8-byte granules", fn);
 
-    std::vector<int> starts((size_t)numEntries + 1);
-    std::vector<WrEntry> table((size_t)numEntries);
+    RefitTable held = {2, {}, {0, 0}, {0, 0}};   // the running sums, then the entries: 8 words each
+    std::vector<uint32_t> &starts = held.words[0], &table = held.words[1];
+    starts = std::vector<uint32_t>((size_t)numEntries + 1);
+    table = std::vector<uint32_t>((size_t)numEntries * (sizeof(WrEntry) / 4));
     int64_t totalNodes = 0, totalTris = 0, totalLeaves = 0;
     for (int k = 0; k < numEntries; k++) {
         const NtrWideRefitEntry& en = entries[k];
@@ -251,7 +227,7 @@ int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, vo
                              (int)en.numTris, (int)numTrisTotal);
         if (!std::isfinite(en.epsilon) || en.epsilon < 0.0f)
             return set_error(NTR_ERR_INVALID, "%s: entry %d: epsilon must be finite and >= 0", fn, k);
-        WrEntry& E = table[k];
+        WrEntry E;
         E.nodeBase = (int)(en.wideNodesOffset / kWideBytes);
         E.numNodes = (int)(en.wideNodesBytes / kWideBytes);
         E.rowBase = (int)(en.triWoopOffset / kRowBytes);
@@ -260,7 +236,8 @@ int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, vo
         E.numTris = en.numTris;
         E.eps = en.epsilon;
         E.pad = 0;
-        starts[k] = (int)totalNodes;
+        memcpy(&table[(size_t)k * (sizeof(WrEntry) / 4)], &E, sizeof(E));
+        starts[k] = (uint32_t)totalNodes;
         totalNodes += E.numNodes;
         // a leaf is a terminator row: rows = 3 * triangle references + leaves, and these builders reference a triangle once (a tree with
         // duplicated references reads as one of more, smaller leaves: a choice of speed only)
@@ -271,61 +248,31 @@ int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, vo
         if (totalNodes > kPoolMaxBytes / kWideBytes)
             return set_error(NTR_ERR_INVALID, "%s: the entries' node ranges are longer in all than a wide pool can be: some overlap", fn);
     }
-    starts[numEntries] = (int)totalNodes;
+    starts[numEntries] = (uint32_t)totalNodes;
     {
         int other = -1;
-        int bad = wr_first_overlap(numEntries, [&](int k) { return entries[k].wideNodesOffset; },
+        int bad = first_range_overlap(numEntries, [&](int k) { return entries[k].wideNodesOffset; },
                                    [&](int k) { return entries[k].wideNodesBytes; }, &other);
         if (bad >= 0)
             return set_error(NTR_ERR_INVALID, "%s: entries %d and %d overlap in the wide pool's nodes: a BLAS is refitted once per call", fn, other, bad);
-        bad = wr_first_overlap(numEntries, [&](int k) { return entries[k].triWoopOffset; },
+        bad = first_range_overlap(numEntries, [&](int k) { return entries[k].triWoopOffset; },
                                [&](int k) { return entries[k].triWoopBytes; }, &other);
         if (bad >= 0)
             return set_error(NTR_ERR_INVALID, "%s: entries %d and %d overlap in the pool's rows: a BLAS is refitted once per call", fn, other, bad);
     }
 
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0;
-    NTR_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) return set_error(NTR_ERR_INVALID, "device index %d out of range", dev);
     const WrLayout lay(numEntries, totalNodes);
-    WrUploaded& up = g_wrUploaded[dev];
-    if (g_wrPool.held() < lay.end) up.valid = false;   // released, never reserved, or about to be regrown
-    const bool same = up.valid && up.starts == starts && up.table.size() == table.size() &&
-                      memcmp(up.table.data(), table.data(), table.size() * sizeof(WrEntry)) == 0;
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && result) return set_error(NTR_ERR_INVALID, "%s: a captured call cannot read a result back (pass result = NULL)", fn);
-    if (capturing && !same)
-        return set_error(NTR_ERR_INVALID, "%s: a captured call uploads and allocates nothing: the device must hold this entry table already "
-                         "-- make one uncaptured call with the same entries first (and none with other entries, and no "
-                         "ntr_lbvh_release_workspace, between it and the capture)", fn);
+    held.offset[0] = lay.starts;
+    held.offset[1] = lay.table;
     void* base = nullptr;
-    if (const int rc = g_wrPool.reserve(lay.end, &base)) return rc;
+    if (const int rc = refit_hold_table(fn, kRefitEntryWords, g_wrPool, g_wrHeld, s, result != nullptr, lay.end, held, &base)) return rc;
     int* d_starts = at<int>(base, lay.starts);
     WrEntry* d_table = at<WrEntry>(base, lay.table);
     unsigned int *parent = at<unsigned int>(base, lay.parent), *arrive = at<unsigned int>(base, lay.arrive);
-    if (!same) {
-        // the host copy is what the upload reads and what the next call compares with: the upload is waited for, so the copy never
-        // changes under it.  A loop of calls with one table (a frame loop) pays this once
-        up.valid = false;
-        up.starts.swap(starts);
-        up.table.swap(table);
-        NTR_HIP(hipMemcpyAsync(d_starts, up.starts.data(), up.starts.size() * 4, hipMemcpyHostToDevice, s));
-        NTR_HIP(hipMemcpyAsync(d_table, up.table.data(), up.table.size() * sizeof(WrEntry), hipMemcpyHostToDevice, s));
-        NTR_HIP(hipStreamSynchronize(s));
-        up.valid = true;
-    }
     WrStats* stats = result ? at<WrStats>(base, lay.stats) : nullptr;
 
-    StreamEvents<2> ev(s);
-    if (result) {
-        NTR_HIP(ev.create());
-        NTR_HIP(ev.record(0));
-        NTR_HIP(hipMemsetAsync(stats, 0, sizeof(WrStats) * WR_STAT_SLOTS, s));
-    }
     const int total = (int)totalNodes;
-    hipLaunchKernelGGL(wide_refit_prepare, dim3((total + WR_BLOCK - 1) / WR_BLOCK), dim3(WR_BLOCK), 0, s, (int)numEntries, total,
-                       (const int*)d_starts, (const WrEntry*)d_table, (const int*)d_widePoolNodes, parent, arrive, stats);
     // lanes per leaf from the selection's mean leaf size, by ntr_bvh_refit's thresholds -- the quantity ntr_bvh_refit_batch forms from
     // the binary extents, which a wide extent does not give: a choice of speed only
     const double meanTris = (double)totalTris / (double)totalLeaves;
@@ -335,26 +282,25 @@ int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, vo
     hipLaunchKernelGGL((wide_refit_climb<G, RW>), grid, dim3(WR_BLOCK), 0, s, (int)numEntries, total, (const int*)d_starts,                \
                        (const WrEntry*)d_table, (int*)d_widePoolNodes, (float4*)d_poolTriWoop, d_poolTriIndex, d_triVtxIndex, numVerts,    \
                        d_vtxPos, (const unsigned int*)parent, arrive, d_blasBoxes, stats)
-    if (rewriteRows) {
-        if (group == 1) NTR_WR_CLIMB(1, true); else if (group == 4) NTR_WR_CLIMB(4, true); else NTR_WR_CLIMB(8, true);
-    } else {
-        if (group == 1) NTR_WR_CLIMB(1, false); else if (group == 4) NTR_WR_CLIMB(4, false); else NTR_WR_CLIMB(8, false);
-    }
+    std::vector<char> host;
+    float seconds = 0.0f;
+    const int rc = refit_bracket(s, result != nullptr, stats, sizeof(WrStats) * kRefitStatSlots, &host, &seconds, [&] {
+        hipLaunchKernelGGL(wide_refit_prepare, dim3((total + WR_BLOCK - 1) / WR_BLOCK), dim3(WR_BLOCK), 0, s, (int)numEntries, total,
+                           (const int*)d_starts, (const WrEntry*)d_table, (const int*)d_widePoolNodes, parent, arrive, stats);
+        if (rewriteRows) {
+            if (group == 1) NTR_WR_CLIMB(1, true); else if (group == 4) NTR_WR_CLIMB(4, true); else NTR_WR_CLIMB(8, true);
+        } else {
+            if (group == 1) NTR_WR_CLIMB(1, false); else if (group == 4) NTR_WR_CLIMB(4, false); else NTR_WR_CLIMB(8, false);
+        }
+    });
 #undef NTR_WR_CLIMB
-    NTR_HIP(hipGetLastError());
-    if (!result) return NTR_OK;
+    if (rc != NTR_OK || !result) return rc;
 
-    NTR_HIP(ev.record(1));
-    std::vector<WrStats> slotsHost(WR_STAT_SLOTS);   // the copy is waited for right here
-    NTR_HIP(hipMemcpyAsync(slotsHost.data(), stats, sizeof(WrStats) * WR_STAT_SLOTS, hipMemcpyDeviceToHost, s));
-    NTR_HIP(hipStreamSynchronize(s));
     uint64_t inner = 0, leafLinks = 0, rows = 0;
     unsigned int err = 0, bad = 0;
-    for (const WrStats& v : slotsHost) {
+    refit_fold_slots<WrStats>(host.data(), [&](const WrStats& v) {
         inner += v.innerLinks; leafLinks += v.leafLinks; rows += v.rows; err |= v.err; bad = std::max(bad, v.bad);
-    }
-    float ms = 0.0f;
-    NTR_HIP(ev.elapsed(0, 1, &ms));
+    });
     result->numEntries = numEntries;
     result->lanesPerLeaf = group;
     result->numNodes = (int64_t)numEntries + (int64_t)inner;
@@ -362,7 +308,7 @@ int ntr_pool_wide_refit(int32_t numEntries, const NtrWideRefitEntry* entries, vo
     result->numRows = (int64_t)rows;
     result->firstBadEntry = err ? (int32_t)~bad : -1;
     result->errBits = (int32_t)err;
-    result->seconds = ms * 1e-3f;
+    result->seconds = seconds;
     if (err)
         return set_error(NTR_ERR_LAYOUT, "%s: entry %d: malformed wide tree (error bits 0x%x over all entries: 1 a link that names no wide node, "
                          "a node named twice or a count word outside 2..4, 2 leaf row outside the extents, 4 triangle index, 8 vertex index "
