@@ -947,7 +947,8 @@ NTR_API int ntr_instances_update_host(int32_t numNodes, const float* nodeLocal, 
  *   d_rayTimes that is not 4-byte aligned, a d_motionKeys that is null or not 16-byte aligned, motionKeysBytes < 128 * numInstances;
  *   a null stats or motionStats.  numRays == 0 returns NTR_OK with the stats zeroed; without a device, after these checks,
  *   NTR_ERR_NO_DEVICE / NTR_ERR_HIP.
- * Not combinable with the 4-wide trees, the seeded / world form or FAST; ntr_instanced_hit_attributes gives the normal at key 0,
+ * Not combinable with the seeded / world form or FAST (over the 4-wide trees: ntr_tlas_wide_motion_refit and
+ * ntr_trace_instanced_wide_motion, below); ntr_instanced_hit_attributes gives the normal at key 0,
  * ntr_instanced_hit_attributes_motion (below) the normal at the ray's time. */
 typedef struct NtrTlasMotionRefitResult {
     NtrTlasRefitResult refit;           /* as ntr_tlas_refit reports it */
@@ -1548,6 +1549,72 @@ NTR_API int ntr_tlas_wide_refit(int32_t numInstances, const NtrInstance* d_insta
                                 NtrTlasRefitResult* result /* NULL: asynchronous */, void* stream);
 /* Bytes the wide top-level refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_tlas_wide_refit_scratch_bytes(int64_t* bytes);
+
+/* Motion blur over the 4-wide trees: the swept wide refit and the timed wide trace (csrc/tlas_wide_motion_refit_kernels.hip,
+ * csrc/trace_instanced_wide_motion_kernels.hip).  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_wide_motion.py, which the refit equals byte for byte and the trace bit for bit in all four result words, the
+ * instance id and every counter.  Keys, time, pose, the moving flag, the 128-byte motion key entry, the entering step's order of checks
+ * and singular poses are ntr_tlas_motion_refit's and ntr_trace_instanced_motion's (above); the wide loop is ntr_trace_instanced_wide's;
+ * the wide leaf box is ntr_tlas_wide_refit's.
+ * ntr_tlas_wide_motion_refit: ntr_tlas_wide_refit over two instance arrays, d_instances0 the shutter's opening and d_instances1 its
+ *   close, with the three changes ntr_tlas_motion_refit makes to ntr_tlas_refit:
+ *   records     wide record i is ntr_tlas_widen's record of key-0 instance i; word 15 is 1 where the twelve objectToWorld words differ
+ *               bitwise between the keys, else 0.  No kernel but the wide motion trace reads word 15.  A later plain
+ *               ntr_tlas_wide_refit or ntr_tlas_widen writes word 15 = 0 and thereby FREEZES the scene at key 0, boxes included
+ *   motion keys entry i is written for every instance, byte for byte what ntr_tlas_motion_refit writes for the same two arrays: the
+ *               all-wide update path needs no binary motion refit, and one key buffer serves both trees
+ *   boxes       the box of a leaf ~i is the union, in the integer order, of instance i's world box under key 0 and under key 1, both
+ *               from the union of the root slots of i's wide BLAS (the pool's node 0 is not read); a static instance's box is
+ *               ntr_tlas_wide_refit's.  The climb is ntr_tlas_wide_refit's
+ *   N == 1: no node, rootLink ~0, wideTlasNodesBytes 0; one small launch writes record 0, key entry 0 and the scene box.
+ *   The contract is ntr_tlas_wide_refit's in every respect not named here: result == NULL is asynchronous on `stream` and capturable
+ *   (two launches, no read-back, no memset); the blocking form is refused on a capturing stream; a bad part is never followed and the
+ *   error bits are unchanged; the held range table and its rule for captured calls; a per-device grow-only scratch pool of its own
+ *   (ntr_tlas_wide_motion_refit_scratch_bytes) that ntr_lbvh_release_workspace returns; one call per device at a time.  It also
+ *   requires d_instances1 non-null and 16-byte aligned, d_motionKeys non-null and 16-byte aligned, and motionKeysCapacity >=
+ *   128 * numInstances, refused where ntr_tlas_motion_refit refuses them in the order of the checks.  numMoving counts the moving
+ *   instances among all numInstances.
+ * ntr_trace_instanced_wide_motion: ntr_trace_instanced_wide's arguments plus `motion`.  With motion == NULL the call IS
+ *   ntr_trace_instanced_wide -- the same launch, and its refusals name that function.  Otherwise the masked wide loop with
+ *   ntr_trace_instanced_motion's entering step: index in range; masks; room for the marker; then, if word 15 of the fetched wide record
+ *   is non-zero, the two keys are read from the motion key buffer at 128 * i (range checked: beyond min(motionKeysBytes, 0xFFFFFF00) a
+ *   read returns zeros, and a zero matrix is singular), M(t_r) is formed and inverted -- no inverse makes the step a pop, counted as
+ *   numSingular only -- then the marker is pushed and the ray transformed by worldToObject(t_r).  seconds == NULL is asynchronous on
+ *   `stream` and capturable; times, keys and records are read by the launch, so a replay sees what is there at replay time.
+ * ntr_trace_instanced_wide_motion_stats: the same records through the instrumented kernel, plus ntr_trace_instanced_wide_stats's
+ *   counters and the two of NtrInstancedMotionStats.  It blocks and is refused on a capturing stream.  With motion == NULL it is
+ *   ntr_trace_instanced_wide_stats and the motion counters are zero.
+ * Algorithmic bytes: ntr_trace_instanced_wide's formula plus 128 (numMovingEntries + numSingular), plus 4 numRays with per-ray times.
+ * Errors: NTR_ERR_INVALID before any device work for everything ntr_trace_instanced_wide refuses, in its words and order, then the
+ *   three motion refusals of ntr_trace_instanced_motion in its words; a null stats or motionStats.  numRays == 0 returns NTR_OK with
+ *   the stats zeroed; without a device, after these checks, NTR_ERR_NO_DEVICE / NTR_ERR_HIP.
+ * ntr_instanced_hit_attributes_motion takes no records and works behind a wide motion trace unchanged.
+ * Out of scope: the seeded / world form, FAST, more than two keys, BLASes that deform within the shutter, a TLAS build over swept
+ * boxes (the topology is whatever ntr_tlas_build and ntr_tlas_widen made at key 0). */
+NTR_API int ntr_tlas_wide_motion_refit(int32_t numInstances, const NtrInstance* d_instances0, const NtrInstance* d_instances1,
+                                       int32_t numBlas, const NtrBlasRange* blasRanges, const NtrWideBlasRange* wideRanges,
+                                       const void* d_widePoolNodes, int64_t widePoolNodesBytes, void* d_wideTlasNodes,
+                                       int64_t wideTlasNodesBytes, int32_t rootLink, void* d_wideRecords, int64_t recordsCapacity,
+                                       void* d_motionKeys, int64_t motionKeysCapacity, float* d_sceneBox /* may be NULL: 6 floats */,
+                                       NtrTlasMotionRefitResult* result /* NULL: asynchronous */, void* stream);
+/* Bytes the wide motion refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_tlas_wide_motion_refit_scratch_bytes(int64_t* bytes);
+NTR_API int ntr_trace_instanced_wide_motion(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                            int32_t* d_instanceIDs, const void* d_wideTlasNodes, int64_t wideTlasNodesBytes,
+                                            int32_t rootLink, const void* d_wideRecords, int32_t numInstances,
+                                            const void* d_widePoolNodes, int64_t widePoolNodesBytes, const void* d_poolTriWoop,
+                                            int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                            const NtrInstanceVisibility* vis /* NULL: no masks */,
+                                            const NtrInstanceMotion* motion /* NULL: ntr_trace_instanced_wide */,
+                                            float* seconds /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_trace_instanced_wide_motion_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                                  int32_t* d_instanceIDs, const void* d_wideTlasNodes, int64_t wideTlasNodesBytes,
+                                                  int32_t rootLink, const void* d_wideRecords, int32_t numInstances,
+                                                  const void* d_widePoolNodes, int64_t widePoolNodesBytes, const void* d_poolTriWoop,
+                                                  int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                                  const NtrInstanceVisibility* vis /* may be NULL */,
+                                                  const NtrInstanceMotion* motion /* may be NULL */, NtrInstancedTraceStats* stats,
+                                                  NtrInstancedMotionStats* motionStats, void* stream);
 
 /* On-device refit: keep a BVHLayout_Compact tree's topology and recompute its boxes and Woop rows from moved vertex positions
  * (csrc/bvh_refit_kernels.hip).  EXTENSION without a reference counterpart (the reference's scenes are static): the rule is pinned by

@@ -588,6 +588,14 @@ SYMBOLS = [
     ("ntr_pool_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_tlas_wide_refit", C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, C.POINTER(TlasRefitResult), _vp]),
     ("ntr_tlas_wide_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_tlas_wide_motion_refit", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                             C.POINTER(TlasMotionRefitResult), _vp]),
+    ("ntr_tlas_wide_motion_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_trace_instanced_wide_motion", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                  C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion), C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_wide_motion_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                        C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion),
+                                                        C.POINTER(InstancedTraceStats), C.POINTER(InstancedMotionStats), _vp]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(BvhRefitBatchResult), _vp]),
@@ -1736,6 +1744,60 @@ def tlas_wide_refit_scratch_bytes():
     v = _i64(0)
     _check(lib().ntr_tlas_wide_refit_scratch_bytes(C.byref(v)))
     return int(v.value)
+
+
+def tlas_wide_motion_refit(num_instances, d_instances0, d_instances1, ranges, wide_ranges, d_wide_pool_nodes, wide_pool_nodes_bytes,
+                           d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, records_cap, d_motion_keys, motion_keys_cap,
+                           d_scene_box=0, stream=0, blocking=True):
+    """ntr_tlas_wide_motion_refit: tlas_wide_refit over two keys of the instances (shutter open, shutter close): swept leaf boxes from
+    the wide roots, word 15 of a moving instance's wide record, and the motion key buffer (128 bytes per instance, tlas_motion_refit's
+    bytes) that trace_instanced_wide_motion reads; the rule is tests/np_instanced_wide_motion.py.  blocking=True returns a
+    TlasMotionRefitResult; blocking=False passes result = NULL: asynchronous on `stream` (capturable) and returns None.  An NtrError
+    raised after the device work carries .result, filled."""
+    arr, n = _blas_ranges(ranges)
+    warr = _wide_ranges(wide_ranges)
+    res = TlasMotionRefitResult() if blocking else None
+    try:
+        _check(lib().ntr_tlas_wide_motion_refit(int(num_instances), _vp(d_instances0), _vp(d_instances1), n, C.cast(arr, _vp),
+                                                C.cast(warr, _vp), _vp(d_wide_pool_nodes), int(wide_pool_nodes_bytes),
+                                                _vp(d_wide_tlas_nodes), int(wide_tlas_nodes_bytes), int(root_link), _vp(d_wide_records),
+                                                int(records_cap), _vp(d_motion_keys), int(motion_keys_cap), _vp(d_scene_box),
+                                                C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def tlas_wide_motion_refit_scratch_bytes():
+    """ntr_tlas_wide_motion_refit_scratch_bytes: bytes the wide motion refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_tlas_wide_motion_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def trace_instanced_wide_motion(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
+                                d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                                d_pool_tri_index, vis=None, motion=None, stream=0, timed=True):
+    """ntr_trace_instanced_wide_motion: trace_instanced_wide with time-sampled instance transforms (the rule is
+    tests/np_instanced_wide_motion.py).  motion: an InstanceMotion over what tlas_wide_motion_refit wrote, or None (NULL:
+    trace_instanced_wide).  timed=False is asynchronous on `stream` (capturable; times, keys and records are read at replay time) and
+    returns None."""
+    return _trace_two_level("ntr_trace_instanced_wide_motion", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids,
+                            d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances, d_wide_pool_nodes,
+                            wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, vis=vis, motion=motion)
+
+
+def trace_instanced_wide_motion_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link,
+                                      d_wide_records, num_instances, d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                                      d_pool_tri_index, vis=None, motion=None, stream=0):
+    """ntr_trace_instanced_wide_motion_stats: trace_instanced_wide_motion's records through the instrumented kernel ->
+    (InstancedWideTraceStats, InstancedMotionStats); the latter's algorithmic_bytes(stats, ...) is then the wide formula plus the poses
+    and the times.  Blocks; refused on a capturing stream."""
+    return _trace_two_level("ntr_trace_instanced_wide_motion_stats", (InstancedWideTraceStats, InstancedMotionStats), num_rays, any_hit, d_rays,
+                            d_results, d_instance_ids, d_wide_tlas_nodes, wide_tlas_nodes_bytes, root_link, d_wide_records, num_instances,
+                            d_wide_pool_nodes, wide_pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, vis=vis,
+                            motion=motion)
 
 
 def bvh_refit(d_nodes, nodes_bytes, d_woop, woop_bytes, d_idx, idx_bytes, num_tris, d_tri, num_verts, d_pos, epsilon=0.0, d_scene_box=0,

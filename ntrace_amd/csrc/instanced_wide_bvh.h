@@ -7,8 +7,15 @@
 //               links stay relative to the BLAS's own start.  The buffer is at most kPoolMaxBytes long
 //   wide TLAS   ntr_bvh_widen applied to the top-level node buffer; leaf links ~i pass through verbatim.  N == 1: no node, rootLink ~0
 //   record i    16 words: 0..11 worldToObject, 12 the wide BLAS's offset in the wide pool, 13 triWoopOffset / 16 (as the binary record),
-//               14 the wide BLAS's extent, 15 zero.  An instance whose blas index lies outside [0, numBlas) gets offset, row offset and
-//               extent 0: a lane inside an instance fetches a wide node only below the extent, so nothing of such an instance is read
+//               14 the wide BLAS's extent, 15 zero -- or, after ntr_tlas_wide_motion_refit (tlas_wide_motion_refit_kernels.hip), 1 for an
+//               instance that moves within the shutter, as word 15 of the binary record (instanced_bvh.h, kRecMoving).  Only the wide
+//               motion kernels (trace_instanced_wide_motion_kernels.hip) read word 15: every other wide trace kernel takes x, y, z of
+//               the record's fourth row in its entering step and nothing else of it (trace_instanced_wide_body.h; the w that
+//               wide_advance reads is a wide NODE's fourth link), ntr_instanced_wide_validate reads node buffers only, the attribute
+//               kernels take no records, and the writers (wide_write_record below: ntr_tlas_widen, ntr_tlas_wide_refit) write 0 --
+//               searched in csrc/ when the word was given its meaning.  An instance whose blas index lies outside
+//               [0, numBlas) gets offset, row offset and extent 0: a lane inside an instance fetches a wide node only below the extent,
+//               so nothing of such an instance is read
 //   marker      kExitMarker, as in instanced_bvh.h
 #pragma once
 #include <hip/hip_runtime.h>

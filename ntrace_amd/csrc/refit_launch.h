@@ -1,6 +1,6 @@
-// refit_launch.h -- host only: the protocol of an in-place refit call, stated once for the five entry points that keep a small table on
-// the device between calls (tlas_refit_, tlas_wide_refit_, tlas_motion_refit_, bvh_refit_batch_, wide_refit_batch_kernels.hip;
-// DESIGN.md 6ac).  A unit keeps its argument checks, the construction of its table, its ScratchCarver layout, its kernels and the
+// refit_launch.h -- host only: the protocol of an in-place refit call, stated once for the six entry points that keep a small table on
+// the device between calls (tlas_refit_, tlas_wide_refit_, tlas_motion_refit_, tlas_wide_motion_refit_, bvh_refit_batch_,
+// wide_refit_batch_kernels.hip).  A unit keeps its argument checks, the construction of its table, its ScratchCarver layout, its kernels and the
 // filling of its result; what is here is the held-table rule, the bracket of the blocking form and the fold of the counter slots.
 //   the held table   the device keeps the table of the last uncaptured call in the unit's scratch pool, and the host keeps a copy to
 //                    compare the next call's table with: a frame loop over one pool uploads once.  A copy on the host never vouches for

@@ -14,7 +14,8 @@
 // arrival short and stay as they are; everything else is refitted completely.
 // The error bits, the wave fold of the counters, the scene-box write and the scratch layout are tlas_refit_parts.h's; the held range
 // table, the refusals of a captured call and the bracket of the blocking form are refit_launch.h's.  The 4-wide
-// classification of tlw_prepare, the checks and the table (wide ranges beside the binary ones) are this unit's own.
+// classification of tlw_prepare is this unit's own; the checks and the table (wide ranges beside the binary ones) are
+// tlas_wide_refit_parts.h's, shared with tlas_wide_motion_refit_kernels.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -29,6 +30,7 @@
 #include "level_build.h"
 #include "refit_launch.h"
 #include "tlas_refit_parts.h"
+#include "tlas_wide_refit_parts.h"
 #include "tlas_world_box.h"
 #include "wide_climb.h"
 
@@ -52,19 +54,8 @@ RefitHeld g_tlwHeld[kMaxDevices];
 __device__ __forceinline__ bool tlw_instance_box(const NtrInstance* __restrict__ inst, int i, const uint4 range, const char* __restrict__ widePool,
                                                  float (&wlo)[3], float (&whi)[3])
 {
-    const float* root = (const float*)(widePool + range.x);
-    const int count = ((const int*)root)[kWideCountWord];
-    if (!wide_count_ok(count)) return false;
     float b[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) b[j] = root[wide_box_word(0, j)];
-    for (int s = 1; s < count; s++) {
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            b[2 * q] = ord_min(b[2 * q], root[wide_box_word(s, 2 * q)]);
-            b[2 * q + 1] = ord_max(b[2 * q + 1], root[wide_box_word(s, 2 * q + 1)]);
-        }
-    }
+    if (!tlw_root_box(widePool, range, b)) return false;
     float m[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) m[k] = inst[i].objectToWorld[k];
@@ -166,41 +157,13 @@ int ntr_tlas_wide_refit(int32_t numInstances, const NtrInstance* d_instances, in
 {
     const char* fn = "ntr_tlas_wide_refit";
     if (result) memset(result, 0, sizeof(*result));
-    if (numInstances < 1 || (int64_t)numInstances * kRecordBytes > kPoolMaxBytes || numBlas < 1 || !d_instances || !blasRanges || !wideRanges ||
-        !d_widePoolNodes || !d_wideRecords || (!d_wideTlasNodes && numInstances > 1))
-        return set_error(NTR_ERR_INVALID, "%s: bad arguments (1 <= numInstances <= %lld, numBlas >= 1, non-null buffers)", fn,
-                         (long long)(kPoolMaxBytes / kRecordBytes));
-    const int n = numInstances;
-    if (n == 1 ? wideTlasNodesBytes != 0 : check_wide_bytes(fn, wideTlasNodesBytes) != NTR_OK)
-        return set_error(NTR_ERR_INVALID, "%s: wideTlasNodesBytes must be the extent ntr_tlas_widen reported: a multiple of 128 in [128, 0x%llx], "
-                         "0 for one instance", fn, (unsigned long long)kMaxWideBytes);
-    const int numNodes = (int)(wideTlasNodesBytes / kWideBytes);
-    if (rootLink != (n == 1 ? leaf_link(0) : 0))
-        return set_error(NTR_ERR_INVALID, "%s: rootLink must be 0, or ~0 for one instance, as ntr_tlas_build reported it", fn);
-    if (recordsCapacity < (int64_t)kRecordBytes * n) return set_error(NTR_ERR_INVALID, "%s: recordsCapacity below 64 * numInstances", fn);
-    if (((uintptr_t)d_widePoolNodes | (uintptr_t)d_wideRecords | (uintptr_t)d_wideTlasNodes | (uintptr_t)d_instances) & 15u)
-        return set_error(NTR_ERR_INVALID, "%s: the buffers must be 16-byte aligned", fn);
-    if (const int rc = check_wide_pool_bytes(fn, "widePoolNodesBytes", widePoolNodesBytes)) return rc;
-    if (!wide_box_granules_aligned()) return set_error(NTR_ERR_INVALID, "%s: a wide box is not three aligned 8-byte granules", fn);
+    const TlasWideArgs args = {numInstances, d_instances, numBlas, blasRanges, wideRanges, d_widePoolNodes, widePoolNodesBytes, d_wideTlasNodes,
+                               wideTlasNodesBytes, rootLink, d_wideRecords, recordsCapacity};
+    if (const int rc = tlas_wide_check_extents(fn, args)) return rc;
+    const int n = numInstances, numNodes = (int)(wideTlasNodesBytes / kWideBytes);
     const TlasRefitLayout lay(numNodes, numBlas);
     RefitTable held = {1, {}, {lay.table, 0}, {n, numNodes}};
-    std::vector<uint32_t>& table = held.words[0];
-    table = std::vector<uint32_t>(4 * (size_t)numBlas);
-    for (int k = 0; k < numBlas; k++) {
-        const NtrBlasRange& r = blasRanges[k];
-        const NtrWideBlasRange& w = wideRanges[k];
-        if (r.triWoopOffset < 0 || (r.triWoopOffset % kRowBytes) != 0 || r.triWoopOffset > kPoolMaxBytes - kRowBytes)
-            return set_error(NTR_ERR_INVALID, "%s: BLAS %d: triWoopOffset must be a multiple of 16 inside a pool of at most 0x%llx bytes", fn, k,
-                             (unsigned long long)kPoolMaxBytes);
-        if (w.nodesOffset < 0 || (w.nodesOffset % kWideBytes) != 0 || w.nodesBytes < kWideBytes || (w.nodesBytes % kWideBytes) != 0 ||
-            w.nodesBytes > kMaxWideBytes || w.nodesOffset > widePoolNodesBytes - w.nodesBytes)
-            return set_error(NTR_ERR_INVALID, "%s: wide BLAS %d: offset and extent must be multiples of 128 inside the wide pool's %lld bytes", fn,
-                             k, (long long)widePoolNodesBytes);
-        table[4 * k] = (uint32_t)w.nodesOffset;
-        table[4 * k + 1] = (uint32_t)(r.triWoopOffset / kRowBytes);
-        table[4 * k + 2] = (uint32_t)w.nodesBytes;
-        table[4 * k + 3] = 0u;
-    }
+    if (const int rc = tlas_wide_range_table(fn, args, 0, held.words[0])) return rc;
 
     hipStream_t s = (hipStream_t)stream;
     void* base = nullptr;

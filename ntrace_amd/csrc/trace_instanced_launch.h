@@ -1,9 +1,10 @@
-// trace_instanced_launch.h -- host only: the launch of the two-level trace, stated once for its five units:
+// trace_instanced_launch.h -- host only: the launch of the two-level trace, stated once for its six units:
 //   trace_instanced_kernels.hip            ntr_trace_instanced, _masked, _stats, _seeded, _seeded_stats
 //   trace_instanced_fast_kernels.hip       ntr_trace_instanced_fast, _fast_stats
 //   trace_instanced_wide_kernels.hip       ntr_trace_instanced_wide, _wide_stats, _wide_seeded, _wide_seeded_stats
 //   trace_instanced_wide_fast_kernels.hip  ntr_trace_instanced_wide_fast, _wide_fast_stats
 //   trace_instanced_motion_kernels.hip     ntr_trace_instanced_motion, _motion_stats
+//   trace_instanced_wide_motion_kernels.hip  ntr_trace_instanced_wide_motion, _wide_motion_stats
 // An entry point writes what it was given into a TwoLevelCall, with the few facts in which the units differ, and calls two_level_trace
 // with its unit's launch: the checks, the device state, the bracket (trace_launch.h) and the counters' unpacking are here; the kernels,
 // the fill of their parameters and the choice among them stay with the unit (trace_instanced_kernels.h: why the units are separate).
@@ -63,7 +64,7 @@ struct TwoLevelCall {
     void* stream;
     NtrInstancedTraceStats* stats;      // both NULL, or the instrumented kernel; a FAST unit takes both or neither
     NtrInstancedFastStats* fastStats;
-    const NtrInstanceMotion* motion;    // the motion unit: given; every other unit leaves the two NULL
+    const NtrInstanceMotion* motion;    // the two motion units: given; every other unit leaves the two NULL
     NtrInstancedMotionStats* motionStats;   // with stats, or NULL
 };
 
@@ -126,7 +127,7 @@ bool two_level_fill_visibility(X& x, const TwoLevelCall& c, DeviceState* ds)
     return x.instMasks || x.rayMasks || x.rayMask != 0xFFFFFFFFu;
 }
 
-// the words an instrumented kernel adds to: [0..6], [8..11] in the FAST units, [12..13] in the motion unit
+// the words an instrumented kernel adds to: [0..6], [8..11] in the FAST units, [12..13] in the motion units
 constexpr int kTwoLevelCounters = 7, kTwoLevelFastCounters = 12, kTwoLevelMotionCounters = 14;
 
 // The shared path of the entry points.  launch(ds, stream, blocks) fills the unit's parameters and enqueues the kernel that c asks for.

@@ -4,7 +4,7 @@
 //   time    per lane, one register through the loop: d_rayTimes[r] or the launch's scalar, clamped to [0, 1] (a NaN gives 0)
 //   moving  word 15 of the fetched record, which ntr_tlas_motion_refit (tlas_motion_refit_kernels.hip) sets and no other kernel reads:
 //           the record came with the step's one fetch, so a static instance costs no further load
-//   pose    motion_pose (the arithmetic is instance_motion.h's): the instance's two keys (two 48-byte loads from the motion key buffer at 128 * i, through a range-checked
+//   pose    motion_pose (trace_motion_pose.h; the arithmetic is instance_motion.h's): the instance's two keys (two 48-byte loads from the motion key buffer at 128 * i, through a range-checked
 //           descriptor: beyond the extent they return zeros, and a zero matrix is singular), twelve lerps in binary32 and
 //           instance_invert (instance_math.h: binary64, the function ntr_instance_invert and ntr_instances_update use).  Its three rows
 //           replace the record's in the registers the fetch wrote, and the masked kernel's transform goes on from there.  No inverse
@@ -27,29 +27,12 @@
 #include "trace_lane.h"
 #include "trace_fetch.h"
 #include "trace_instanced_kernels.h"
+#include "trace_motion_pose.h"
 
 namespace ntr {
 namespace {
 
-// What the motion kernels take beside InstancedParams and InstancedExtras
-struct InstancedMotion {
-    const void* keys;          // the motion key buffer: 128 bytes per instance (instanced_bvh.h)
-    const float* rayTimes;     // numRays words, or NULL: every ray has `time`
-    uint32_t keysBytes;        // the descriptor's range
-    float time;
-};
-
-// worldToObject(t) of moving instance idx into the rows a, b, c; false, and the rows untouched, where M(t) has no inverse.  The loads
-// are this unit's; the lerps and the inverse are instance_motion.h's, shared with instanced_motion_attr_kernels.hip
-__device__ __forceinline__ bool motion_pose(Rsrc rKeys, int idx, float t, float4& a, float4& b, float4& c)
-{
-    // 128 * idx may pass 2^32 for an index no key buffer can hold (a descriptor ends below 2^32): such a lane reads nothing
-    const int ofs = (unsigned)idx < (unsigned)(kPoolMaxBytes / kMotionKeyBytes) ? idx * kMotionKeyBytes : kNoNode;
-    const float4 k0[3] = {ld4(rKeys, ofs), ld4(rKeys, ofs + 16), ld4(rKeys, ofs + 32)};
-    const float4 k1[3] = {ld4(rKeys, ofs + kMotionKey1Bytes), ld4(rKeys, ofs + kMotionKey1Bytes + 16), ld4(rKeys, ofs + kMotionKey1Bytes + 32)};
-    return motion_pose_keys(k0, k1, t, a, b, c);
-}
-
+// InstancedMotion, the kernels' motion parameters, and motion_pose, the key loads, are trace_motion_pose.h's, shared with the wide unit
 #define NTR_TI_PARAMS InstancedParams p, InstancedExtras x, InstancedMotion mo
 #define NTR_TI_MASKED 1
 #define NTR_TI_SEEDED 0

@@ -1,6 +1,7 @@
 // trace_instanced_wide_body.h -- the two-level trace over 4-wide trees, its kernel stated once: trace_instanced_wide_kernels.hip (the
 // three unseeded kernels) and trace_instanced_wide_seeded_kernels.hip (the seeded ones) include this text once each, and
-// trace_instanced_wide_fast_kernels.hip (the FAST ones, unseeded and seeded) twice, after trace_instanced_wide_kernels.h, with
+// trace_instanced_wide_fast_kernels.hip (the FAST ones, unseeded and seeded) twice, and trace_instanced_wide_motion_kernels.hip (the two
+// motion kernels) once, after trace_instanced_wide_kernels.h, with
 //   NTR_TIW_TEMPLATE   the template header: <bool MASKED, bool STATS>, or <bool STATS> for the seeded kernels (MASKED is then true)
 //   NTR_TIW_KERNEL     the kernel's name
 //   NTR_TIW_PARAMS     its parameters: InstancedWideParams p, and for the seeded kernels InstancedWideSeed sd
@@ -10,6 +11,10 @@
 //                      DESIGN.md 6x; the rule is tests/np_instanced_wide_fast.py): a per-lane `nice` says that the lane's current ray may
 //                      take FAST on its current level, and the wave votes per iteration on the step's form.  The template header is
 //                      <bool STATS>, seeded or not: the fast kernels are the masked loop
+//   NTR_TIW_MOTION     1 (optional; undefined means 0): motion blur (InstancedMotion mo of trace_motion_pose.h; the rule is
+//                      tests/np_instanced_wide_motion.py): the ray carries a time, and the entering step poses an instance whose record
+//                      has word 15 set at that time -- trace_instanced_body.h's addition under NTR_TI_MOTION, in the same place.  The
+//                      template header is <bool STATS>: the motion kernels are the masked loop
 // An include and not a further template parameter for trace_instanced_body.h's reason: the unseeded kernels keep their names and stay,
 // instruction for instruction, what they were (scripts/kernel_isa_diff.sh).  No include guard.
 NTR_TIW_TEMPLATE
@@ -17,6 +22,9 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
 {
 #if NTR_TIW_SEEDED || NTR_TIW_FAST
     constexpr bool MASKED = true;   // the seeded kernels are the masked loop
+#endif
+#if NTR_TIW_MOTION
+    constexpr bool MASKED = true;   // so are the motion kernels
 #endif
     __shared__ int s_stack[LDS_DEPTH][64];   // [entry][lane]
     const int lane = threadIdx.x;
@@ -35,6 +43,13 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
         rayMask = p.rayMasks ? p.rayMasks[valid ? rayIdx : 0] : p.rayMask;
     }
     InstancedLaneStats ls = {0u, 0u, 0u, 0u, 0u, 0u};
+#if NTR_TIW_MOTION
+    // the ray's time, clamped so that a NaN gives 0; the key buffer's descriptor is built from kernel arguments only
+    const Rsrc rKeys = make_rsrc(mo.keys, mo.keysBytes);
+    float rayTime = mo.rayTimes ? mo.rayTimes[valid ? rayIdx : 0] : mo.time;
+    rayTime = motion_clamp_time(rayTime);
+    unsigned int movingEntries = 0u, singularSteps = 0u;   // (STATS only)
+#endif
 
     RayRegs r;   // the current form: the world ray on the top level, the object ray inside an instance
     {
@@ -152,7 +167,19 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
             } else if (st.sp >= LDS_DEPTH + SPILL_DEPTH) {
                 atomicOr(p.status, NTR_STATUS_STACK_OVERFLOW);   // no room for the marker: the instance is not entered
                 node = stack_pop(st, spill);
-            } else {
+            } else
+#if NTR_TIW_MOTION
+            // a record whose word 15 is set names a moving instance: worldToObject(t) replaces the record's rows a, b, c.  The wave
+            // votes, so one that enters only static instances runs the masked kernel's step behind one scalar branch
+            if (__ballot(__float_as_uint(d.w) != 0u) != 0ull && __float_as_uint(d.w) != 0u && !motion_pose(rKeys, idx, rayTime, a, b, c)) {
+                if (STATS) singularSteps++;
+                node = stack_pop(st, spill);         // no inverse at this time: no marker, no transform
+            } else
+#endif
+            {
+#if NTR_TIW_MOTION
+                if (STATS) movingEntries += __float_as_uint(d.w) != 0u ? 1u : 0u;
+#endif
                 stack_push(st, spill, kExitMarker, p.status);
                 const float ox = dot4(a, r.ox, r.oy, r.oz, 1.0f), oy = dot4(b, r.ox, r.oy, r.oz, 1.0f), oz = dot4(c, r.ox, r.oy, r.oz, 1.0f);
                 const float dx = dot4(a, r.dx, r.dy, r.dz, 0.0f), dy = dot4(b, r.dx, r.dy, r.dz, 0.0f), dz = dot4(c, r.dx, r.dy, r.dz, 0.0f);
@@ -222,6 +249,10 @@ __global__ __launch_bounds__(64) void NTR_TIW_KERNEL(NTR_TIW_PARAMS)
         atomicAdd(&p.stats[6], (unsigned long long)(seedKept || (hitAddr >= 0 && p.triIndex[hitAddr] != -1)));
 #else
         atomicAdd(&p.stats[6], (unsigned long long)(hitAddr >= 0 && p.triIndex[hitAddr] != -1));
+#endif
+#if NTR_TIW_MOTION
+        atomicAdd(&p.stats[12], (unsigned long long)movingEntries);
+        atomicAdd(&p.stats[13], (unsigned long long)singularSteps);
 #endif
 #if NTR_TIW_FAST
         if (lane == 0) {   // (lane 0 of a launched wave is a ray)

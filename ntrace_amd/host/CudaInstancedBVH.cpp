@@ -13,9 +13,11 @@ CudaInstancedBVH::CudaInstancedBVH(void) : m_blasTrisCurrent(false), m_numInstan
                                            m_wideTopology(false), m_widePool(false), m_wideTlas(false), m_traceWide(false), m_world(-1),
                                            m_traceFast(false), m_fastStale(true), m_fastValidations(0), m_traceWideFast(false),
                                            m_wideFastStale(true), m_wideFastValidations(0), m_rayTimes(NULL), m_time(0.0f),
-                                           m_hasMotion(false), m_motionStale(true), m_motionRefits(0)
+                                           m_hasMotion(false), m_motionStale(true), m_motionRefits(0),
+                                           m_traceWideMotion(false), m_wideMotionCurrent(false), m_motionWideRefits(0)
 {
     std::memset(&m_motionRefitResult, 0, sizeof(m_motionRefitResult));
+    std::memset(&m_motionWideRefitResult, 0, sizeof(m_motionWideRefitResult));
     std::memset(&m_widePoolResult, 0, sizeof(m_widePoolResult));
     std::memset(&m_wideResult, 0, sizeof(m_wideResult));
     std::memset(&m_wideBlasRefitResult, 0, sizeof(m_wideBlasRefitResult));
@@ -388,6 +390,7 @@ void CudaInstancedBVH::widen(void)
                                   m_wideRecords.getSize(), &m_wideResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_wideTlas = m_wideTopology = true;
+    m_wideMotionCurrent = false;                 // the wide records have no moving flags, the wide boxes are the binary tree's
 }
 
 void CudaInstancedBVH::refitBLASesWide(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas, S32 num, F32 epsilon)
@@ -431,6 +434,27 @@ void CudaInstancedBVH::refitWide(void)
                                        &m_wideTlasRefitResult, NULL);
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
     m_wideTlas = true;
+    m_wideFastStale = true;
+    m_wideMotionCurrent = false;                 // word 15 = 0 everywhere: the wide trees are frozen at key 0
+}
+
+void CudaInstancedBVH::refitMotionWide(void)
+{
+    if (!m_topology || !m_wideTopology || m_numInstances < 1)
+        fail("CudaInstancedBVH: no wide TLAS for the motion refit: call build() and widen() first, and again after the instance count or the BLASes "
+             "have changed");
+    if (!m_widePool) fail("CudaInstancedBVH: the wide pool is not current: call refitBLASesWide() in place of refitBLASes(), or widen()");
+    refitMotion();                               // the binary TLAS, its records and the motion keys stay current
+    m_wideMotionCurrent = false;
+    const int rc = ntr_tlas_wide_motion_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(),
+                                              (const NtrInstance*)m_instances1.getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
+                                              m_wideRanges.data(), m_widePoolNodes.getCudaPtr(), m_widePoolResult.nodesBytes,
+                                              m_wideResult.nodesBytes ? m_wideTlasNodes.getMutableCudaPtr() : NULL, m_wideResult.nodesBytes,
+                                              m_result.rootLink, m_wideRecords.getMutableCudaPtr(), m_wideRecords.getSize(),
+                                              m_motionKeys.getMutableCudaPtr(), m_motionKeys.getSize(), NULL, &m_motionWideRefitResult, NULL);
+    m_motionWideRefits++;
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    m_wideTlas = m_wideMotionCurrent = true;
     m_wideFastStale = true;
 }
 
@@ -488,7 +512,9 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     if (!numRays) return 0.0f;
     if (m_hasMotion) {
         // motion over the 4-wide trees, the FAST form and the seeded / world form does not exist: neither is ignored silently
-        if (m_traceWide) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceWide: clearMotion() or setTraceWide(false)");
+        // (over the 4-wide trees only by opting in: setTraceWideMotion)
+        if (m_traceWide && !m_traceWideMotion)
+            fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceWide: clearMotion() or setTraceWide(false)");
         if (m_traceWideFast) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceWideFast: clearMotion() or setTraceWideFast(false)");
         if (m_traceFast) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceFast: clearMotion() or setTraceFast(false)");
         if (m_world >= 0) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setWorld: clearMotion() or clearWorld()");
@@ -496,7 +522,9 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     if (!m_built) fail("CudaInstancedBVH: No TLAS!");
     if (m_hasMotion && m_rayTimes && m_rayTimes->getSize() < (S64)numRays * (S64)sizeof(F32))
         fail("CudaInstancedBVH: setRayTimes' buffer holds fewer than %d times", numRays);
-    if (m_hasMotion && m_motionStale) refitMotion();
+    if (m_hasMotion && m_traceWide) {            // (m_traceWideMotion: checked above) both trees, the wide one in place, exactly once
+        if (isMotionWideStale()) refitMotionWide();
+    } else if (m_hasMotion && m_motionStale) refitMotion();
     float seconds = 0.0f, worldSeconds = 0.0f;
     const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
     const bool world = m_world >= 0, wide = m_traceWide && isWide();
@@ -536,8 +564,10 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
         motion.d_rayTimes = m_rayTimes ? (const float*)m_rayTimes->getCudaPtr() : NULL;
         motion.time = m_time;
         motion.pad = 0.0f;
-        rc = ntr_trace_instanced_motion(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records, m_numInstances,
-                                        d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &motion, &seconds, NULL);
+        rc = wide ? ntr_trace_instanced_wide_motion(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records,
+                                                    m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &motion, &seconds, NULL)
+                  : ntr_trace_instanced_motion(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records,
+                                               m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &motion, &seconds, NULL);
     } else if (wide && m_traceWideFast)
         rc = ntr_trace_instanced_wide_fast(numRays, anyHit, d_rays, d_seed, seedInstance, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink,
                                            d_records, m_numInstances, d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis,

@@ -94,10 +94,20 @@
 //                 the class then reports hasMotion() with isMotionStale(); the next traceBatch with motion calls refitMotion() first,
 //                 exactly once.  clearMotion() drops key 1: traceBatch is the static one again, over boxes that still bound the sweep
 //                 until the next refit().  setInstances with another count clears the motion, as it clears the masks.
-//                 Not combinable: with motion set and setTraceWide, setTraceFast or setTraceWideFast on, or a world set, traceBatch
-//                 fail()s with a message naming the switch; it ignores neither silently.  InstancedRenderer::setMotionBlur (DESIGN.md
-//                 6ab) renders motion-blurred frames over this class: it points setRayTimes at each batch's hashed times for the
-//                 trace (getRayTimes: the caller's pointer comes back after it) and takes the normals at the same times.
+//                 Not combinable: with motion set and setTraceWide (unless setTraceWideMotion opts in, below), setTraceFast or
+//                 setTraceWideFast on, or a world set, traceBatch fail()s with a message naming the switch; it ignores neither silently.
+//                 InstancedRenderer::setMotionBlur renders motion-blurred frames over this class: it points setRayTimes
+//                 at each batch's hashed times for the trace (getRayTimes: the caller's pointer comes back after it) and takes the
+//                 normals at the same times.
+//   setTraceWideMotion   motion over the 4-wide trees, opt-in, default false: with hasMotion(), setTraceWide(true) and this on,
+//                 traceBatch takes ntr_trace_instanced_wide_motion.  Off, every refusal above is what it was; without setTraceWide(true)
+//                 the switch changes nothing and the launch is the binary motion launch.  setTraceWideFast, setTraceFast and a world
+//                 stay refused with motion.  refitMotionWide() is refitMotion(), then ntr_tlas_wide_motion_refit in place over the wide
+//                 TLAS and the wide records (swept wide boxes, the moving flags, the same key buffer); it needs what refitWide() needs
+//                 -- a build() and a widen() with the current instance count since, and a current wide pool -- and afterwards
+//                 isBuilt() && isWide() && !isMotionStale().  Staleness is setMotionKey's rule, and widen() and refitWide() -- which
+//                 write wide records without moving flags -- make the wide side stale too (isMotionWideStale()): the next traceBatch on
+//                 the wide motion path calls refitMotionWide() first, exactly once.
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and the mesh buffers and carries Renderer's batching for
 // primary, AO and diffuse frames.  Per frame, the loop of a moving, deforming scene is
 //   refitBLASes -> optimizeBLASes every so many frames -> setInstances (setInstancesDevice for transforms on the device) -> refit ->
@@ -148,6 +158,12 @@ public:
     void refitMotion(void);
     S32  getMotionRefits(void) const { return m_motionRefits; }                  // ntr_tlas_motion_refit calls so far
     const NtrTlasMotionRefitResult& getMotionRefitResult(void) const { return m_motionRefitResult; }   // of the last refitMotion (zero before)
+    void setTraceWideMotion(bool on) { m_traceWideMotion = on; }                 // motion over the 4-wide trees, with setTraceWide(true)
+    bool getTraceWideMotion(void) const { return m_traceWideMotion; }
+    void refitMotionWide(void);
+    bool isMotionWideStale(void) const { return m_motionStale || !m_wideMotionCurrent || !m_wideTlas; }   // the next wide motion traceBatch refits first
+    S32  getMotionWideRefits(void) const { return m_motionWideRefits; }          // ntr_tlas_wide_motion_refit calls so far
+    const NtrTlasMotionRefitResult& getMotionWideRefitResult(void) const { return m_motionWideRefitResult; }   // of the last refitMotionWide (zero before)
     void setRayTimes(Buffer* times) { m_rayTimes = times; }                      // F32 per ray, the caller's; NULL: every ray has setTime's
     Buffer* getRayTimes(void) const { return m_rayTimes; }
     void setTime(F32 time) { m_time = time; }
@@ -192,6 +208,7 @@ public:
     S32  getNumBLAS(void) const { return (S32)m_ranges.size(); }
     S32  getNumInstances(void) const { return m_numInstances; }
     const NtrBlasRange&  getBLASRange(S32 i) const { return m_ranges[i]; }
+    const NtrWideBlasRange& getWideBLASRange(S32 i) const { return m_wideRanges[i]; }   // of the wide pool; needs isWidePoolCurrent()
     const NtrTlasResult& getBuildResult(void) const { return m_result; }
     const NtrPlocBatchResult& getBLASBuildResult(void) const { return m_blasResult; }   // of the last buildBLASes (zero before)
     const NtrBvhRefitBatchResult& getBLASRefitResult(void) const { return m_refitResult; }   // of the last refitBLASes (zero before)
@@ -257,6 +274,10 @@ private:
     bool          m_hasMotion, m_motionStale;
     S32           m_motionRefits;
     NtrTlasMotionRefitResult m_motionRefitResult;
+    // motion over the 4-wide trees (setTraceWideMotion): the wide records hold the moving flags and the wide boxes the sweep
+    bool          m_traceWideMotion, m_wideMotionCurrent;
+    S32           m_motionWideRefits;
+    NtrTlasMotionRefitResult m_motionWideRefitResult;
 };
 
 }  // namespace FW

@@ -7,7 +7,7 @@ namespace FW {
 
 InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
     : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
-      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false), m_fast(false), m_wideFast(false),
+      m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false), m_fast(false), m_wideFast(false), m_wideMotion(false),
       m_motionBlur(false), m_motionSeed(0), m_shutterOpen(0.0f), m_shutterClose(1.0f),
       m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
 {
@@ -49,12 +49,17 @@ F32 InstancedRenderer::trace(RayBuffer& rays, Buffer& instanceIDs, Buffer& times
 {
     struct Restore {   // the caller's flags and times come back on every path: traceBatch fails by throwing
         CudaInstancedBVH& bvh;
-        bool was, wasFast, wasWideFast;
+        bool was, wasFast, wasWideFast, wasWideMotion;
         Buffer* wasTimes;
-        ~Restore() { bvh.setTraceWide(was); bvh.setTraceFast(wasFast); bvh.setTraceWideFast(wasWideFast); bvh.setRayTimes(wasTimes); }
-    } restore = {m_bvh, m_bvh.getTraceWide(), m_bvh.getTraceFast(), m_bvh.getTraceWideFast(), m_bvh.getRayTimes()};
+        ~Restore()
+        {
+            bvh.setTraceWide(was); bvh.setTraceFast(wasFast); bvh.setTraceWideFast(wasWideFast); bvh.setTraceWideMotion(wasWideMotion);
+            bvh.setRayTimes(wasTimes);
+        }
+    } restore = {m_bvh, m_bvh.getTraceWide(), m_bvh.getTraceFast(), m_bvh.getTraceWideFast(), m_bvh.getTraceWideMotion(), m_bvh.getRayTimes()};
     if (m_motionBlur) m_bvh.setRayTimes(&times);
     m_bvh.setTraceWide(m_wide);
+    m_bvh.setTraceWideMotion(m_wideMotion || restore.wasWideMotion);
     m_bvh.setTraceFast(m_fast || restore.wasFast);
     m_bvh.setTraceWideFast(m_wideFast || restore.wasWideFast);
     return m_bvh.traceBatch(rays, instanceIDs, rayMask);

@@ -26,8 +26,13 @@
 //                 caller's pointer is put back after each trace -- and resolved by ntr_instanced_hit_attributes_motion with the same key
 //                 buffer and times, so the normal is the one of the pose the ray hit; an AO or diffuse ray inherits its primary
 //                 ray's time (ntr_ray_times_secondary): it sees its instance where its primary ray saw it.  Primary, AO and diffuse
-//                 frames all work.  setWide, setFast, setWideFast and a world stay not combinable with motion: the
-//                 CudaInstancedBVH's traceBatch refuses each by name, and the refusal is passed on
+//                 frames all work.  setWide (without setWideMotion), setFast, setWideFast and a world stay not combinable with motion:
+//                 the CudaInstancedBVH's traceBatch refuses each by name, and the refusal is passed on
+//   setWideMotion motion-blurred frames over the 4-wide trees (CudaInstancedBVH::setTraceWideMotion); default false; in the
+//                 manner of setFast: on, or whatever the CudaInstancedBVH itself was told, and put back after each trace.  With it on,
+//                 setWide(true) and setMotionBlur(true), primary, AO and diffuse frames run over the wide trees: the first batch after
+//                 beginFrame's widen() refits both trees over the two keys (refitMotionWide); times, attributes at the ray's time and
+//                 inherited secondary times are exactly setMotionBlur's -- ntr_instanced_hit_attributes_motion takes no records
 //   beginFrame    w x h primary rays from the camera's position and nscreenToWorld (its width and height are not read); for AO and
 //                 diffuse frames the primary rays are traced and resolved at once
 //   nextBatch / traceBatch / updateResult / getTotalNumRays  as Renderer's.  Every traced batch is resolved by
@@ -62,6 +67,8 @@ public:
     bool getFast(void) const { return m_fast; }
     void setWideFast(bool on) { m_wideFast = on; }
     bool getWideFast(void) const { return m_wideFast; }
+    void setWideMotion(bool on) { m_wideMotion = on; }
+    bool getWideMotion(void) const { return m_wideMotion; }
     void setMotionBlur(bool on, U32 seed = 0, F32 open = 0.0f, F32 close = 1.0f);
     bool getMotionBlur(void) const { return m_motionBlur; }
 
@@ -77,6 +84,8 @@ public:
     Buffer&    getPrimaryResolvedBuffer(void) { return m_primaryResolved; }   // NtrRayResult per primary slot, ids of pool triangles
     Buffer&    getPrimaryNormalBuffer(void) { return m_primaryNormals; }      // 4 floats per primary slot
     Buffer&    getBatchResolvedBuffer(void) { return *m_batchResolved; }      // NtrRayResult per slot of the current batch
+    Buffer&    getPrimaryInstanceIDBuffer(void) { return m_primaryIDs; }      // S32 per primary slot: the instance of the hit (AO, diffuse)
+    Buffer&    getBatchInstanceIDBuffer(void) { return m_batchRays == &m_primaryRays ? m_primaryIDs : m_secondaryIDs; }   // of the current batch
     Buffer&    getPrimaryTimeBuffer(void) { return m_primaryTimes; }          // setMotionBlur: F32 per primary slot
     Buffer&    getBatchTimeBuffer(void) { return m_batchRays == &m_primaryRays ? m_primaryTimes : m_secondaryTimes; }   // F32 per slot of the current batch
 
@@ -96,7 +105,7 @@ private:
     F32        m_aoRadius;
     S32        m_numSamples;
     U32        m_primaryMask, m_secondaryMask;
-    bool       m_wide, m_fast, m_wideFast;
+    bool       m_wide, m_fast, m_wideFast, m_wideMotion;
     bool       m_motionBlur;
     U32        m_motionSeed;
     F32        m_shutterOpen, m_shutterClose;
