@@ -1661,6 +1661,68 @@ NTR_API int ntr_bvh_refit(void* d_nodes, int64_t nodesBytes, void* d_triWoop, in
 /* Bytes the refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_bvh_refit_scratch_bytes(int64_t* bytes);
 
+/* Deformation motion blur over one BVHLayout_Compact tree: a refit to TWO vertex arrays (csrc/bvh_motion_refit_kernels.hip) and a trace
+ * that poses boxes and triangles at each ray's time (csrc/trace_motion_kernels.hip).  EXTENSION without a reference counterpart: the rule
+ * is the numpy spec tests/np_bvh_motion.py, whose docstring is the normative text; ntr_bvh_motion_refit equals its motion_refit byte for
+ * byte and ntr_trace_bvh_motion its trace in all four result words and every counter.  One mesh topology (d_triVtxIndex, numTris), two
+ * position arrays: d_vtxPos0 is the shutter's opening, d_vtxPos1 its close.  Any Compact tree, whatever built it; single level only
+ * (not inside ntr_trace_instanced_*), binary trees only, two keys only, no FAST flags.
+ * ntr_bvh_motion_refit
+ *   d_nodes0, d_triWoop  in place, exactly what ntr_bvh_refit(d_vtxPos0) writes and leaves alone: afterwards ntr_trace_bvh over them is the
+ *                        scene at the shutter's opening
+ *   d_nodes1             nodesBytes, written: first a copy of d_nodes0 as it was handed in (the caller need not initialise it), then the
+ *                        boxes ntr_bvh_refit(d_vtxPos1) writes -- so links, split words and slots no link reaches are d_nodes0's
+ *   d_vertRows0/1        triWoopBytes each, written: zero-filled, then for every row group r, r+1, r+2 of a reached leaf the rows
+ *                        (x, y, z, 0) of vertices 0, 1, 2 of triangle d_triIndex[r] under that key, and at a reached leaf's terminator row
+ *                        (0, 0, 0, 0x80000000).  The terminator lives in W: a vertex x of -0.0f is the terminator's word
+ *   d_sceneBox           optional, 6 floats min.xyz max.xyz: the union of the two keys' scene boxes
+ *   result               ntr_bvh_refit's counts (the same for both keys) and the GPU time of the whole call
+ * The protocol is ntr_bvh_refit's in every respect: launches only on `stream`, which re-initialise their own state (no memset or copy
+ * node); result == NULL is asynchronous and capturable after one uncaptured call on a tree at least as large; result != NULL blocks and
+ * reports a malformed tree as NTR_ERR_LAYOUT (never followed; skipped silently when result == NULL); a per-device grow-only pool (12 B
+ * per node slot and 16 KB of counters) that ntr_lbvh_release_workspace returns and that must not regrow or be released while a graph
+ * lives.  One refit per device at a time.
+ * NTR_ERR_INVALID (before any device work): ntr_bvh_refit's cases; a null d_nodes1, d_vertRows0, d_vertRows1 or d_vtxPos1; node, Woop or
+ * vertex-row buffers not 16-byte aligned; any of those four buffers overlapping another buffer of the call.
+ * ntr_trace_bvh_motion / _stats
+ *   time         ray r has time d_rayTimes[r] when d_rayTimes is given, else `time`; clamped by t > 0 ? (t < 1 ? t : 1) : 0 (NaN -> 0).
+ *                The times are read by the kernel -- at replay when the call was captured; `time` is then the value at capture
+ *   pose         per word a at t == 0, b at t == 1, else fl(fl((1 - t) a) + fl(t b)).  NOT ntr_trace_instanced_motion's lerp: no "same
+ *                word" shortcut, so that the posed box contains the posed triangle exactly, with no padding (a vertex that does not move
+ *                may wobble by an ulp inside the shutter; its Woop rows are recomputed from the posed vertices anyway)
+ *   inner node   the twelve box words posed from d_nodes0 and d_nodes1, links from d_nodes0, then ntr_trace_bvh's exact slab test and order
+ *   triangle     a row group is a terminator iff the W word of d_vertRows0's row is 0x80000000; otherwise the nine vertex words are
+ *                posed, woop_rows.h gives the Woop rows and ntr_trace_bvh's triangle test runs on them
+ *   consequences at time 0 / 1 the records are ntr_trace_bvh's over the tree refitted to d_vtxPos0 / d_vtxPos1, word for word; at a scalar
+ *                time t they are ntr_trace_bvh's over the posed static tree
+ *   counters     NtrTraceStats as ntr_trace_bvh_stats fills it; algorithmic bytes are 128 per inner visit, 96 per triangle test, 16 per
+ *                terminator, 48 per ray and 4 more per ray with d_rayTimes
+ * seconds == NULL: asynchronous on `stream` and capturable; a traversal stack overflow (16 LDS + 88 scratch entries) is the sticky bit
+ * of ntr_trace_status.  seconds != NULL: drains the stream, times the launch and reports an overflow as NTR_ERR_OVERFLOW.  The _stats form
+ * runs the instrumented kernel, blocks and is refused on a capturing stream.
+ * NTR_ERR_INVALID (before any device work): numRays < 0; a null ray, result or tree buffer or a null motion; nodesBytes not a multiple
+ * of 64 in [64, 0x76543200]; vertRowsBytes not a multiple of 16 in [16, 0xFFFFFF00]; d_rayTimes not 4-byte aligned.  numRays == 0 ->
+ * NTR_OK, 0 seconds.  Without a device: NTR_ERR_NO_DEVICE / NTR_ERR_HIP (no CPU fallback). */
+NTR_API int ntr_bvh_motion_refit(void* d_nodes0, int64_t nodesBytes, void* d_nodes1, void* d_triWoop, int64_t triWoopBytes,
+                                 const int32_t* d_triIndex, int64_t triIndexBytes,
+                                 void* d_vertRows0, void* d_vertRows1 /* triWoopBytes each */,
+                                 int32_t numTris, const int32_t* d_triVtxIndex, int32_t numVerts, const float* d_vtxPos0,
+                                 const float* d_vtxPos1, float epsilon, float* d_sceneBox /* may be NULL */,
+                                 NtrBvhRefitResult* result /* NULL: asynchronous, capturable */, void* stream);
+/* Bytes the motion refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_motion_refit_scratch_bytes(int64_t* bytes);
+typedef struct NtrBvhMotion {
+    const void *d_nodes1, *d_vertRows0, *d_vertRows1;   /* ntr_bvh_motion_refit's */
+    const float* d_rayTimes;                             /* may be NULL: every ray has `time` */
+    float time;
+} NtrBvhMotion;
+NTR_API int ntr_trace_bvh_motion(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                 const void* d_nodes0, int64_t nodesBytes, int64_t vertRowsBytes, const int32_t* d_triIndex,
+                                 const NtrBvhMotion* motion, void* stream, float* seconds /* NULL: asynchronous, capturable */);
+NTR_API int ntr_trace_bvh_motion_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                       const void* d_nodes0, int64_t nodesBytes, int64_t vertRowsBytes, const int32_t* d_triIndex,
+                                       const NtrBvhMotion* motion, void* stream, NtrTraceStats* stats);   /* blocking, instrumented kernel */
+
 /* On-device treelet restructuring: raise the quality of a BVHLayout_Compact tree in place, whatever built or refitted it
  * (csrc/bvh_optimize_kernels.hip).  EXTENSION without a reference counterpart: the rule is pinned by the numpy spec
  * tests/np_bvh_optimize.py (its docstring is the normative text), not by reference lines.  The algorithm is the treelet part of Karras

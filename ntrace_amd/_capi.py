@@ -344,6 +344,16 @@ class BvhRefitResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class BvhMotion(C.Structure):
+    """NtrBvhMotion: what bvh_motion_refit wrote beside the key-0 tree (the key-1 nodes and the two keys' vertex rows) and the rays'
+    times -- a device array of num_rays floats, or 0: every ray has `time`."""
+    _fields_ = [("d_nodes1", C.c_void_p), ("d_vertRows0", C.c_void_p), ("d_vertRows1", C.c_void_p), ("d_rayTimes", C.c_void_p),
+                ("time", C.c_float)]
+
+    def __init__(self, d_nodes1=0, d_vert_rows0=0, d_vert_rows1=0, d_ray_times=0, time=0.0):
+        super().__init__(int(d_nodes1) or None, int(d_vert_rows0) or None, int(d_vert_rows1) or None, int(d_ray_times) or None, float(time))
+
+
 class BvhOptimizeResult(C.Structure):
     _fields_ = [("passes", C.c_int32), ("numNodes", C.c_int32), ("numLeafLinks", C.c_int32), ("pad", C.c_int32),
                 ("formed", C.c_int32 * 8), ("rewritten", C.c_int32 * 8), ("heightBefore", C.c_int32 * 8), ("heightAfter", C.c_int32 * 8),
@@ -598,6 +608,11 @@ SYMBOLS = [
                                                         C.POINTER(InstancedTraceStats), C.POINTER(InstancedMotionStats), _vp]),
     ("ntr_bvh_refit", C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _vp, C.c_float, _vp, C.POINTER(BvhRefitResult), _vp]),
     ("ntr_bvh_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_motion_refit", C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _vp, C.c_float, _vp,
+                                       C.POINTER(BvhRefitResult), _vp]),
+    ("ntr_bvh_motion_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_trace_bvh_motion", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(BvhMotion), _vp, C.POINTER(C.c_float)]),
+    ("ntr_trace_bvh_motion_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(BvhMotion), _vp, C.POINTER(TraceStats)]),
     ("ntr_bvh_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(BvhRefitBatchResult), _vp]),
     ("ntr_bvh_refit_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
@@ -1817,6 +1832,46 @@ def bvh_refit_scratch_bytes():
     v = _i64(0)
     _check(lib().ntr_bvh_refit_scratch_bytes(C.byref(v)))
     return int(v.value)
+
+
+def bvh_motion_refit(d_nodes0, nodes_bytes, d_nodes1, d_woop, woop_bytes, d_idx, idx_bytes, d_vert_rows0, d_vert_rows1, num_tris, d_tri,
+                     num_verts, d_pos0, d_pos1, epsilon=0.0, d_scene_box=0, stream=0, blocking=True):
+    """ntr_bvh_motion_refit: refit a Compact tree to two vertex arrays for deformation motion blur (an extension; the rule is
+    tests/np_bvh_motion.py): d_nodes0 and d_woop in place as bvh_refit(d_pos0), d_nodes1 the key-1 boxes, d_vert_rows0 / 1 (woop_bytes
+    each) the triangles' vertices under either key.  blocking=True returns a BvhRefitResult; blocking=False passes result = NULL: the
+    call is asynchronous on `stream` (capturable) and returns None."""
+    res = BvhRefitResult() if blocking else None
+    _check(lib().ntr_bvh_motion_refit(_vp(d_nodes0), int(nodes_bytes), _vp(d_nodes1), _vp(d_woop), int(woop_bytes), _vp(d_idx), int(idx_bytes),
+                                      _vp(d_vert_rows0), _vp(d_vert_rows1), int(num_tris), _vp(d_tri), int(num_verts), _vp(d_pos0),
+                                      _vp(d_pos1), float(epsilon), _vp(d_scene_box), C.byref(res) if blocking else None, _vp(stream)))
+    return res
+
+
+def bvh_motion_refit_scratch_bytes():
+    """ntr_bvh_motion_refit_scratch_bytes: bytes the motion refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_motion_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def trace_bvh_motion(num_rays, any_hit, d_rays, d_results, d_nodes0, nodes_bytes, vert_rows_bytes, d_tri_index, motion, stream=0, timed=True):
+    """ntr_trace_bvh_motion: closest or any hit through a tree that bvh_motion_refit prepared, every ray at its own time (the rule is
+    tests/np_bvh_motion.py).  motion: a BvhMotion, or None (NULL: refused).  timed=True returns the GPU seconds; timed=False is
+    asynchronous on `stream` (capturable) and returns None."""
+    sec = C.c_float(0.0)
+    _check(lib().ntr_trace_bvh_motion(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_nodes0), int(nodes_bytes),
+                                      int(vert_rows_bytes), _vp(d_tri_index), C.byref(motion) if motion is not None else None, _vp(stream),
+                                      C.byref(sec) if timed else None))
+    return float(sec.value) if timed else None
+
+
+def trace_bvh_motion_stats(num_rays, any_hit, d_rays, d_results, d_nodes0, nodes_bytes, vert_rows_bytes, d_tri_index, motion, stream=0):
+    """ntr_trace_bvh_motion_stats: trace_bvh_motion's records through the instrumented kernel -> TraceStats.  Blocks."""
+    st = TraceStats()
+    _check(lib().ntr_trace_bvh_motion_stats(int(num_rays), int(bool(any_hit)), _vp(d_rays), _vp(d_results), _vp(d_nodes0), int(nodes_bytes),
+                                            int(vert_rows_bytes), _vp(d_tri_index), C.byref(motion) if motion is not None else None,
+                                            _vp(stream), C.byref(st)))
+    return st
 
 
 def _refit_entries(entries):

@@ -65,9 +65,44 @@ void CudaBVH::refit(Scene& scene, F32 epsilon)
                                  (const int32_t*)m_triIndex.getCudaPtr(), m_triIndex.getSize(), scene.getNumTriangles(),
                                  (const int32_t*)scene.getTriVtxIndexBuffer().getCudaPtr(), scene.getNumVertices(),
                                  (const float*)scene.getVtxPosBuffer().getCudaPtr(), epsilon, NULL, &res, NULL);
+    dropMotion();             // the tree is static again, whatever the call left
     if (rc != NTR_OK) fail("CudaBVH::refit: %s", ntr_last_error());
     m_refitResult = res;
     invalidateTraceFlags();   // FASTDIV / NOTINY / ORDERED and the top-of-tree table depend on the boxes
+}
+
+void CudaBVH::dropMotion(void)
+{
+    m_hasMotion = false;
+    m_nodes1.reset();
+    m_vertRows[0].reset();
+    m_vertRows[1].reset();
+}
+
+void CudaBVH::refitMotion(Scene& scene, const Vec3f* key1Positions, F32 epsilon)
+{
+    if (m_layout != BVHLayout_Compact) fail("CudaBVH::refitMotion: only BVHLayout_Compact is supported");
+    if (!key1Positions) fail("CudaBVH::refitMotion: no key-1 positions");
+    m_hasMotion = false;
+    m_nodes1.resizeDiscard(m_nodes.getSize());
+    m_vertRows[0].resizeDiscard(m_triWoop.getSize());
+    m_vertRows[1].resizeDiscard(m_triWoop.getSize());
+    Buffer pos1(key1Positions, (S64)scene.getNumVertices() * (S64)sizeof(Vec3f));
+    NtrBvhRefitResult res = NtrBvhRefitResult();
+    const int rc = ntr_bvh_motion_refit(m_nodes.getMutableCudaPtr(), m_nodes.getSize(), m_nodes1.getMutableCudaPtrDiscard(),
+                                        m_triWoop.getMutableCudaPtr(), m_triWoop.getSize(), (const int32_t*)m_triIndex.getCudaPtr(),
+                                        m_triIndex.getSize(), m_vertRows[0].getMutableCudaPtrDiscard(),
+                                        m_vertRows[1].getMutableCudaPtrDiscard(), scene.getNumTriangles(),
+                                        (const int32_t*)scene.getTriVtxIndexBuffer().getCudaPtr(), scene.getNumVertices(),
+                                        (const float*)scene.getVtxPosBuffer().getCudaPtr(), (const float*)pos1.getCudaPtr(), epsilon, NULL,
+                                        &res, NULL);
+    invalidateTraceFlags();   // the key-0 boxes were rewritten, also after a failure half way
+    if (rc != NTR_OK) {
+        dropMotion();
+        fail("CudaBVH::refitMotion: %s", ntr_last_error());
+    }
+    m_refitResult = res;
+    m_hasMotion = true;
 }
 
 void CudaBVH::optimize(int passes)
@@ -76,6 +111,7 @@ void CudaBVH::optimize(int passes)
     NtrBvhOptimizeResult res = NtrBvhOptimizeResult();
     const int rc = ntr_bvh_optimize(m_nodes.getMutableCudaPtr(), m_nodes.getSize(), passes, &res, NULL);
     invalidateTraceFlags();   // the flags and the top-of-tree table depend on the boxes, also after a failure half way
+    dropMotion();             // key 1's nodes hold the old topology
     if (rc != NTR_OK) fail("CudaBVH::optimize: %s", ntr_last_error());
     m_optimizeResult = res;
 }
@@ -91,6 +127,7 @@ void CudaBVH::reorder(void)
                                    (int32_t*)triIndex.getMutableCudaPtrDiscard(), triIndex.getSize(), &res, NULL);
     // NTR_ERR_LAYOUT after the work leaves a complete, traceable output; every other failure leaves the tree as it was
     if (rc != NTR_OK) fail("CudaBVH::reorder: %s", ntr_last_error());
+    dropMotion();             // key 1's nodes and the vertex rows are in the old order
     m_nodes.swap(nodes);
     m_triWoop.swap(triWoop);
     m_triIndex.swap(triIndex);

@@ -45,6 +45,18 @@ public:
     virtual F32 getRefitEpsilon(void) const { return 0.0f; }
     const NtrBvhRefitResult& getRefitResult(void) const { return m_refitResult; }   // of the last refit (zero before the first)
 
+    // Mirror extension: deformation motion blur (ntr_bvh_motion_refit; the rule is tests/np_bvh_motion.py).  Key 0, the shutter's
+    // opening, is the scene's CURRENT vertex positions, as for refit(); key 1, its close, is key1Positions: scene.getNumVertices()
+    // host vectors.  The tree's own buffers come out as refit() leaves them; the object owns the key-1 node buffer and the two keys'
+    // vertex rows, and hasMotion() says that they are current.  A CudaBVHTracer with a time or ray times set then traces every ray at
+    // its own time (ntr_trace_bvh_motion).  A later refit(), optimize() or reorder() drops the motion state: the tree is static again,
+    // at whatever that call leaves.  Blocking; fails (FW::fail) with the library's message, the motion state then dropped.
+    void        refitMotion(Scene& scene, const Vec3f* key1Positions, F32 epsilon);
+    void        refitMotion(Scene& scene, const Vec3f* key1Positions) { refitMotion(scene, key1Positions, getRefitEpsilon()); }
+    bool        hasMotion(void) const { return m_hasMotion; }
+    Buffer&     getMotionNodeBuffer(void) { return m_nodes1; }                // key 1's nodes (empty without motion)
+    Buffer&     getVertRowsBuffer(int key) { return m_vertRows[key ? 1 : 0]; } // a key's vertex rows (empty without motion)
+
     // Mirror extension (no counterpart in the reference): restructure the tree's treelets on the device for a lower SAH cost
     // (ntr_bvh_optimize on this tree's node buffer; triangles and leaves stay), then invalidateTraceFlags().  Works on a tree of any
     // origin, fresh or refitted.  Leaf depths change with the topology: whoever cached ntr_bvh_leaf_depths recomputes them
@@ -77,6 +89,10 @@ protected:
     U32       m_flags;
     bool      m_flagsValid;
     NtrBvhRefitResult m_refitResult;
+    void      dropMotion(void);
+    Buffer    m_nodes1;
+    Buffer    m_vertRows[2];
+    bool      m_hasMotion = false;
     NtrBvhOptimizeResult m_optimizeResult = NtrBvhOptimizeResult();
     NtrBvhSahResult   m_sahResult = NtrBvhSahResult();
     NtrBvhReorderResult m_reorderResult = NtrBvhReorderResult();

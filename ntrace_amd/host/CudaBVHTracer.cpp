@@ -33,6 +33,31 @@ F32 CudaBVHTracer::traceRange(RayBuffer& rays, S32 first, S32 count)
     if (!m_bvh) fail("CudaBVHTracer: No BVH!");
     if (m_bvh->getLayout() != getDesiredBVHLayout()) fail("CudaBVHTracer: Incorrect BVH layout!");
 
+    if (m_rayTimes || m_timeSet) {
+        CudaBVH* mb = dynamic_cast<CudaBVH*>(m_bvh);
+        if (!mb || mb->getLayout() != BVHLayout_Compact)
+            fail("CudaBVHTracer: ray times need a BVHLayout_Compact CudaBVH: a kd-tree or a wide tree has no deformation motion blur");
+        if (mb->hasMotion()) {
+            if (m_rayTimes && m_rayTimes->getSize() < (S64)rays.getSize() * (S64)sizeof(F32))
+                fail("CudaBVHTracer: the ray times hold fewer than one float per ray");
+            NtrBvhMotion motion = NtrBvhMotion();
+            motion.d_nodes1 = mb->getMotionNodeBuffer().getCudaPtr();
+            motion.d_vertRows0 = mb->getVertRowsBuffer(0).getCudaPtr();
+            motion.d_vertRows1 = mb->getVertRowsBuffer(1).getCudaPtr();
+            motion.d_rayTimes = m_rayTimes ? (const float*)m_rayTimes->getCudaPtr() + first : NULL;
+            motion.time = m_time;
+            float sec = 0.0f;
+            const int mrc = ntr_trace_bvh_motion(numRays, rays.getNeedClosestHit() ? 0 : 1,
+                                                 (const NtrRay*)rays.getRayBuffer().getCudaPtr() + first,
+                                                 (NtrRayResult*)rays.getResultBuffer().getMutableCudaPtr() + first,
+                                                 mb->getNodeBuffer().getCudaPtr(), mb->getNodeBuffer().getSize(),
+                                                 mb->getVertRowsBuffer(0).getSize(), (const int32_t*)mb->getTriIndexBuffer().getCudaPtr(),
+                                                 &motion, NULL, &sec);
+            if (mrc != NTR_OK) fail("CudaBVHTracer: %s", ntr_last_error());
+            return sec;
+        }
+    }
+
     U32 flags = 0;
     if (CudaBVH* cb = dynamic_cast<CudaBVH*>(m_bvh)) flags = cb->getTraceFlags();
 

@@ -22,6 +22,14 @@ public:
     F32               traceRange(RayBuffer& rays, S32 first, S32 count);
     // Dispatch hint for the next traceBatch / traceRange calls (ntr_trace_bvh_hinted; NULL = none).  No counterpart in the reference.
     void              setSchedHint(NtrSchedHint* hint) { m_hint = hint; }
+    // Deformation motion blur (no counterpart in the reference): the time of the rays of the next traceBatch / traceRange calls --
+    // one float per ray slot of the batch (setRayTimes; NULL = none) or one for all (setTime; clearTime() takes it back).  With either
+    // set, a CudaBVH that hasMotion() (CudaBVH::refitMotion) is traced by ntr_trace_bvh_motion, every ray at its own time; a CudaBVH
+    // without motion is traced as ever.  Anything that is not a Compact CudaBVH -- a kd-tree, a wide tree -- fails by name.  The kernel
+    // name, the trace flags and the scheduling hint do not apply to the motion launch.
+    void              setRayTimes(Buffer* times) { m_rayTimes = times; }
+    void              setTime(F32 time) { m_time = time; m_timeSet = true; }
+    void              clearTime(void) { m_timeSet = false; }
 
     const KernelConfig& getKernelConfig(void) const { return m_kernelConfig; }
 
@@ -30,6 +38,9 @@ private:
     KernelConfig m_kernelConfig;
     CudaAS*      m_bvh;
     NtrSchedHint* m_hint;
+    Buffer*      m_rayTimes = NULL;
+    F32          m_time = 0.0f;
+    bool         m_timeSet = false;
 };
 
 }  // namespace FW
