@@ -986,6 +986,79 @@ NTR_API int ntr_trace_instanced_motion_stats(int32_t numRays, int32_t anyHit, co
                                              const NtrInstanceMotion* motion /* may be NULL */, NtrInstancedTraceStats* stats,
                                              NtrInstancedMotionStats* motionStats, void* stream);
 
+/* Deforming BLASes in the motion-blurred two-level trace (csrc/tlas_deform_refit_kernels.hip, csrc/trace_instanced_deform_kernels.hip,
+ * DESIGN.md 6ag): instances that move AND meshes that deform within the shutter, in one instanced scene.  It joins the two halves above
+ * and below: ntr_tlas_motion_refit / ntr_trace_instanced_motion (rigid motion, every BLAS frozen at key 0) and ntr_bvh_motion_refit /
+ * ntr_trace_bvh_motion (deformation over one tree).  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_deform.py, which the refit equals byte for byte and the trace bit for bit in all four result words, the instance
+ * id and every counter.
+ *   pool, key 1  beside d_poolNodes, d_poolTriWoop and d_poolTriIndex the pool has d_poolNodes1 (poolNodesBytes) and d_poolVertRows0,
+ *                d_poolVertRows1 (poolTriWoopBytes each).  For a deforming BLAS the four slices at its NtrBlasRange hold what
+ *                ntr_bvh_motion_refit wrote when it was handed pool + offset.  For a BLAS that is not deforming nothing of the three
+ *                buffers is ever read; the caller need not initialise those bytes
+ *   deforming    d_blasDeforming: numBlas words ON THE DEVICE, non-zero: that BLAS deforms.  The refit's kernels read it, so a replay
+ *                of a captured refit sees the current flags
+ *   leaf box     instance i has BLAS b.  K = {key 0's objectToWorld, key 1's} if the instance is moving, else {key 0's}; J =
+ *                {d_poolNodes, d_poolNodes1} if b deforms, else {d_poolNodes}.  The box is the union, in the integer order, of the
+ *                instance's world box (ntr_tlas_refit's) over ALL pairs of K x J: up to four boxes.  A posed point is M(t) c(t) with
+ *                both factors linear in t -- a quadratic Bezier curve that lies in the hull of the four products, not of its two ends.
+ *                No padding
+ *   word 15      bit 0: moving, as ntr_tlas_motion_refit writes it; bit 1: the instance's BLAS deforms.  Records with bit 1 set are
+ *                meant for ntr_trace_instanced_deform ONLY: ntr_trace_instanced_motion takes any non-zero word 15 for "moving".  A later
+ *                ntr_tlas_refit or ntr_tlas_motion_refit rewrites word 15 without bit 1
+ *   trace        ntr_trace_instanced_motion's, with two changed bottom-level steps for a lane inside an instance whose record has bit 1
+ *                (remembered from the entering step to the exit marker; bit 0 alone decides the instance's pose): the inner step poses
+ *                the twelve box words from d_poolNodes and d_poolNodes1 at nodesOffset + node (links from d_poolNodes) and the triangle
+ *                step is ntr_trace_bvh_motion's at the pool's row offset -- a terminator iff the W word of d_poolVertRows0's row is
+ *                0x80000000, otherwise nine posed vertex words, their Woop rows and the unchanged test.  The pose is
+ *                ntr_trace_bvh_motion's (no "same word" shortcut).  In every other instance each step is ntr_trace_instanced_motion's
+ *   bytes        the motion formula plus 64 per deforming inner visit and 48 per deforming triangle test
+ * ntr_tlas_deform_refit: ntr_tlas_motion_refit plus d_poolNodes1 and d_blasDeforming, and its contract in every respect not named here
+ *   (result == NULL is asynchronous and capturable: launches only, no memset or copy node; the tolerant walk; the cached range table;
+ *   a scratch pool of its own, ntr_tlas_deform_refit_scratch_bytes).  With no flag set every byte it writes is ntr_tlas_motion_refit's.
+ *   It also requires d_poolNodes1 non-null and 16-byte aligned and d_blasDeforming non-null and 4-byte aligned.
+ * ntr_trace_instanced_deform / _deform_stats: ntr_trace_instanced_motion's arguments plus `deform`.  With deform == NULL the call IS
+ *   ntr_trace_instanced_motion (_motion_stats, and the three deform counters are zero).  NTR_ERR_INVALID before any device work for
+ *   everything ntr_trace_instanced_motion refuses, in its words and order, then: a null motion with a non-null deform; a null
+ *   d_poolNodes1, d_poolVertRows0 or d_poolVertRows1; one of them not 16-byte aligned; one of them overlapping another buffer of the
+ *   call; a null stats, motionStats or deformStats.  The _stats form blocks and is refused on a capturing stream.
+ * Not combinable with the 4-wide trees, FAST, or the seeded / world form; ntr_instanced_hit_attributes_motion gives a deforming BLAS's
+ * normal at key 0; two keys only. */
+typedef struct NtrTlasDeformRefitResult {
+    NtrTlasMotionRefitResult motion;    /* as ntr_tlas_motion_refit reports it */
+    int32_t numDeforming, pad;          /* instances whose BLAS deforms */
+} NtrTlasDeformRefitResult;
+typedef struct NtrInstanceDeform {      /* host struct of device pointers; the extents are the call's poolNodesBytes and poolTriWoopBytes */
+    const void *d_poolNodes1, *d_poolVertRows0, *d_poolVertRows1;
+} NtrInstanceDeform;
+typedef struct NtrInstancedDeformStats {
+    int64_t numDeformEntries;           /* entering steps that entered an instance of a deforming BLAS (in numInstanceEntries too) */
+    int64_t numDeformInnerVisits;       /* inner steps inside such instances (in numInnerVisits too) */
+    int64_t numDeformTriTests;          /* triangle tests inside such instances (in numTriTests too) */
+} NtrInstancedDeformStats;
+NTR_API int ntr_tlas_deform_refit(int32_t numInstances, const NtrInstance* d_instances0, const NtrInstance* d_instances1, int32_t numBlas,
+                                  const NtrBlasRange* blasRanges, const void* d_poolNodes, const void* d_poolNodes1, int64_t poolNodesBytes,
+                                  const uint32_t* d_blasDeforming, void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink,
+                                  void* d_records, int64_t recordsCapacity, void* d_motionKeys, int64_t motionKeysCapacity,
+                                  float* d_sceneBox /* may be NULL: 6 floats */, NtrTlasDeformRefitResult* result /* NULL: asynchronous */,
+                                  void* stream);
+/* Bytes the deform refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_tlas_deform_refit_scratch_bytes(int64_t* bytes);
+NTR_API int ntr_trace_instanced_deform(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results, int32_t* d_instanceIDs,
+                                       const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink, const void* d_records,
+                                       int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes, const void* d_poolTriWoop,
+                                       int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                       const NtrInstanceVisibility* vis /* NULL: no masks */, const NtrInstanceMotion* motion,
+                                       const NtrInstanceDeform* deform /* NULL: ntr_trace_instanced_motion */,
+                                       float* seconds /* NULL: asynchronous */, void* stream);
+NTR_API int ntr_trace_instanced_deform_stats(int32_t numRays, int32_t anyHit, const NtrRay* d_rays, NtrRayResult* d_results,
+                                             int32_t* d_instanceIDs, const void* d_tlasNodes, int64_t tlasNodesBytes, int32_t rootLink,
+                                             const void* d_records, int32_t numInstances, const void* d_poolNodes, int64_t poolNodesBytes,
+                                             const void* d_poolTriWoop, int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                             const NtrInstanceVisibility* vis /* may be NULL */, const NtrInstanceMotion* motion,
+                                             const NtrInstanceDeform* deform /* may be NULL */, NtrInstancedTraceStats* stats,
+                                             NtrInstancedMotionStats* motionStats, NtrInstancedDeformStats* deformStats, void* stream);
+
 /* Many PLOC builds in one pass: every mesh of a batch becomes one BLAS of a pool, all of them in the same launches
  * (csrc/bvh_ploc_batch_kernels.hip; it stands here, not beside ntr_ploc_build, because it fills NtrBlasRange).  ntr_ploc_build is a
  * chain of some hundred launches and a read-back per four rounds whatever the mesh's size; a scene of a thousand small meshes pays that

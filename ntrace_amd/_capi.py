@@ -273,6 +273,37 @@ class InstancedMotionStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TlasDeformRefitResult(C.Structure):
+    """NtrTlasDeformRefitResult: ntr_tlas_motion_refit's result and the number of instances whose BLAS deforms."""
+    _fields_ = [("motion", TlasMotionRefitResult), ("numDeforming", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return dict(self.motion.as_dict(), numDeforming=int(self.numDeforming))
+
+
+class InstanceDeform(C.Structure):
+    """NtrInstanceDeform: the pool's key-1 buffers -- the second key's nodes (the pool's node bytes) and the two keys' vertex rows (the
+    pool's row bytes each), as bvh_motion_refit wrote them at pool + offset for every deforming BLAS."""
+    _fields_ = [("d_poolNodes1", C.c_void_p), ("d_poolVertRows0", C.c_void_p), ("d_poolVertRows1", C.c_void_p)]
+
+    def __init__(self, d_pool_nodes1=0, d_pool_vert_rows0=0, d_pool_vert_rows1=0):
+        super().__init__(int(d_pool_nodes1) or None, int(d_pool_vert_rows0) or None, int(d_pool_vert_rows1) or None)
+
+
+class InstancedDeformStats(C.Structure):
+    """NtrInstancedDeformStats (the rule is tests/np_instanced_deform.py): entries into, inner visits in and triangle tests in instances
+    of deforming BLASes; each is counted in InstancedTraceStats too."""
+    _fields_ = [(n, C.c_int64) for n in ("numDeformEntries", "numDeformInnerVisits", "numDeformTriTests")]
+
+    def algorithmic_bytes(self, stats, motion_stats, instance_masks=False, ray_masks=False, ray_times=False):
+        """include/ntrace_amd.h: the motion formula, 64 B more per deforming inner visit and 48 B more per deforming triangle test."""
+        return (motion_stats.algorithmic_bytes(stats, instance_masks, ray_masks, ray_times) + 64 * self.numDeformInnerVisits
+                + 48 * self.numDeformTriTests)
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class InstancesUpdateResult(C.Structure):
     _fields_ = [("numInstances", C.c_int32), ("numNodes", C.c_int32), ("statusBits", C.c_uint32), ("firstBad", C.c_uint32),
                 ("numBad", C.c_uint32), ("pad", C.c_uint32), ("seconds", C.c_float), ("updateMs", C.c_float)]
@@ -542,6 +573,16 @@ SYMBOLS = [
     ("ntr_tlas_motion_refit", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
                                         C.POINTER(TlasMotionRefitResult), _vp]),
     ("ntr_tlas_motion_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_tlas_deform_refit", C.c_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                        C.POINTER(TlasDeformRefitResult), _vp]),
+    ("ntr_tlas_deform_refit_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_trace_instanced_deform", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                             C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion), C.POINTER(InstanceDeform),
+                                             C.POINTER(C.c_float), _vp]),
+    ("ntr_trace_instanced_deform_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                                   C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion), C.POINTER(InstanceDeform),
+                                                   C.POINTER(InstancedTraceStats), C.POINTER(InstancedMotionStats),
+                                                   C.POINTER(InstancedDeformStats), _vp]),
     ("ntr_trace_instanced_motion", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
                                              C.POINTER(InstanceVisibility), C.POINTER(InstanceMotion), C.POINTER(C.c_float), _vp]),
     ("ntr_trace_instanced_motion_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
@@ -1300,6 +1341,36 @@ def tlas_motion_refit_scratch_bytes():
     return int(v.value)
 
 
+def tlas_deform_refit(num_instances, d_instances0, d_instances1, ranges, d_pool_nodes, d_pool_nodes1, pool_nodes_bytes, d_blas_deforming,
+                      d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, records_cap, d_motion_keys, motion_keys_cap, d_scene_box=0,
+                      stream=0, blocking=True):
+    """ntr_tlas_deform_refit: tlas_motion_refit over a pool in which some BLASes deform within the shutter: leaf boxes over {key 0, key 1
+    of the instance} x {key 0, key 1 of the BLAS}, bit 1 of record word 15; the rule is tests/np_instanced_deform.py.  d_pool_nodes1: the
+    pool's second node buffer; d_blas_deforming: one uint32 per BLAS on the device.  blocking=True returns a TlasDeformRefitResult;
+    blocking=False passes result = NULL: asynchronous on `stream` (capturable) and returns None."""
+    if isinstance(ranges, BlasPool):
+        ranges = ranges.ranges
+    arr = (BlasRange * max(len(ranges), 1))(*[BlasRange(*[int(x) for x in r]) for r in ranges])
+    res = TlasDeformRefitResult() if blocking else None
+    try:
+        _check(lib().ntr_tlas_deform_refit(int(num_instances), _vp(d_instances0), _vp(d_instances1), len(ranges), C.cast(arr, _vp),
+                                           _vp(d_pool_nodes), _vp(d_pool_nodes1), int(pool_nodes_bytes), _vp(d_blas_deforming),
+                                           _vp(d_tlas_nodes), int(tlas_nodes_bytes), int(root_link), _vp(d_records), int(records_cap),
+                                           _vp(d_motion_keys), int(motion_keys_cap), _vp(d_scene_box), C.byref(res) if blocking else None,
+                                           _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def tlas_deform_refit_scratch_bytes():
+    """ntr_tlas_deform_refit_scratch_bytes: bytes the deform refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_tlas_deform_refit_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
 INSTANCE_MAX_CHAIN = 16
 INSTANCE_ERR_SINGULAR, INSTANCE_ERR_CHAIN = 1, 2
 
@@ -1352,7 +1423,7 @@ _ABSENT = object()   # an argument that an entry point does not have (None is a 
 
 def _trace_two_level(name, out, num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
                      num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, seed=_ABSENT,
-                     vis=_ABSENT, d_flags=_ABSENT, motion=_ABSENT):
+                     vis=_ABSENT, d_flags=_ABSENT, motion=_ABSENT, deform=_ABSENT):
     """The one marshalling of the ntr_trace_instanced* entry points (binary or wide buffers alike).  After the rays `seed`, a
     (d_seed_results, seed_instance) pair; after the pool `vis`, `d_flags` and `motion`; then the out-arguments and the stream.  out: True or False
     (`timed`: a float -> the seconds, or NULL -> None), or the classes of the stats -> one object of each (alone, or a tuple)."""
@@ -1368,6 +1439,8 @@ def _trace_two_level(name, out, num_rays, any_hit, d_rays, d_results, d_instance
         args.append(_vp(d_flags))
     if motion is not _ABSENT:
         args.append(C.byref(motion) if motion is not None else None)
+    if deform is not _ABSENT:
+        args.append(C.byref(deform) if deform is not None else None)
     _check(getattr(lib(), name)(*args, *([None] if out is False else [C.byref(o) for o in outs]), _vp(stream)))
     if isinstance(out, bool):
         return float(outs[0].value) if out else None
@@ -1422,6 +1495,28 @@ def trace_instanced_motion_stats(num_rays, any_hit, d_rays, d_results, d_instanc
     return _trace_two_level("ntr_trace_instanced_motion_stats", (InstancedTraceStats, InstancedMotionStats), num_rays, any_hit, d_rays, d_results,
                             d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes,
                             d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, vis=vis, motion=motion)
+
+
+def trace_instanced_deform(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                           num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None, motion=None,
+                           deform=None, stream=0, timed=True):
+    """ntr_trace_instanced_deform: trace_instanced_motion over a pool in which some BLASes deform (the rule is
+    tests/np_instanced_deform.py).  deform: an InstanceDeform over the pool's key-1 buffers, or None (NULL: trace_instanced_motion).
+    timed=False is asynchronous on `stream` (capturable) and returns None."""
+    return _trace_two_level("ntr_trace_instanced_deform", bool(timed), num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes,
+                            tlas_nodes_bytes, root_link, d_records, num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes,
+                            d_pool_tri_index, stream, vis=vis, motion=motion, deform=deform)
+
+
+def trace_instanced_deform_stats(num_rays, any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records,
+                                 num_instances, d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, vis=None,
+                                 motion=None, deform=None, stream=0):
+    """ntr_trace_instanced_deform_stats: trace_instanced_deform's records through the instrumented kernel ->
+    (InstancedTraceStats, InstancedMotionStats, InstancedDeformStats).  Blocks; refused on a capturing stream."""
+    return _trace_two_level("ntr_trace_instanced_deform_stats", (InstancedTraceStats, InstancedMotionStats, InstancedDeformStats), num_rays,
+                            any_hit, d_rays, d_results, d_instance_ids, d_tlas_nodes, tlas_nodes_bytes, root_link, d_records, num_instances,
+                            d_pool_nodes, pool_nodes_bytes, d_pool_woop, pool_woop_bytes, d_pool_tri_index, stream, vis=vis, motion=motion,
+                            deform=deform)
 
 
 def instanced_hit_attributes(num_rays, d_results, d_instance_ids, geom, d_out_results=0, d_normals=0, stream=0):

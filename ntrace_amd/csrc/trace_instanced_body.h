@@ -14,6 +14,12 @@
 //   NTR_TI_MOTION   1 (optional; undefined means 0): motion blur (InstancedMotion mo; the rule is tests/np_instanced_motion.py):
 //                   the ray carries a time, and the entering step poses an instance whose record has word 15 set at that time -- two
 //                   keys from the motion key buffer, twelve lerps and the binary64 inverse, behind a wave-uniform branch
+//   NTR_TI_DEFORM   1 (optional; undefined means 0; on top of NTR_TI_MASKED 1 and NTR_TI_MOTION 1): deforming BLASes (InstancedDeform df;
+//                   DESIGN.md 6ag; the rule is tests/np_instanced_deform.py): bit 0 of record word 15 is "moving", bit 1 says that the
+//                   instance's BLAS deforms.  A lane that enters remembers bit 1 until its exit marker; behind ONE wave-uniform branch on
+//                   the ballot of such lanes a second fetch brings the second key's box rows, or the two keys' vertex rows, and the
+//                   words are posed at the ray's time before the unchanged steps run.  A wave with no lane in a deforming BLAS runs
+//                   the motion kernel's iteration after that one scalar branch
 // An include and not a function template because the unmasked variant must stay the kernel it was, instruction for instruction
 // (scripts/kernel_isa_diff.sh): with the loop in a __forceinline__ function that the kernels call, hipcc orders its passes differently and
 // allocates other registers, and every such change would have to be measured again.  No include guard: the text is meant
@@ -47,6 +53,18 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
     float rayTime = mo.rayTimes ? mo.rayTimes[valid ? rayIdx : 0] : mo.time;
     rayTime = motion_clamp_time(rayTime);
     unsigned int movingEntries = 0u, singularSteps = 0u;   // (STATS only)
+#endif
+#if NTR_TI_DEFORM
+    // the second key's nodes and the two keys' vertex rows, with the extents of the pool's nodes and rows: range-checked descriptors
+    // built from kernel arguments, so a bad link reads zeros and never faults
+    const u32x4 rNodes1 = rsrc_words(df.nodes1, p.poolNodesBytes), rVerts0 = rsrc_words(df.verts0, p.poolWoopBytes),
+                rVerts1 = rsrc_words(df.verts1, p.poolWoopBytes);
+    const float rayTimeU = 1.0f - rayTime;
+    bool deform = false;                  // inside an instance whose BLAS deforms: bit 1 of the entered record's word 15
+    unsigned int deformEntries = 0u, deformInner = 0u, deformTris = 0u;   // (STATS only)
+#define NTR_TI_MOVING(W) ((__float_as_uint(W) & 1u) != 0u)
+#else
+#define NTR_TI_MOVING(W) (__float_as_uint(W) != 0u)
 #endif
 
     RayRegs r;   // the current form: the world ray on the top level, the object ray inside an instance
@@ -107,6 +125,10 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
 #endif
 
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
+#if NTR_TI_DEFORM
+    float4 e = a, f = a, g = a;           // the second key's rows of a lane in a deforming BLAS
+    unsigned int nextW = 0u;              // ... and the w word of the vertex row behind its triangle
+#endif
     for (;;) {
         if (__ballot(node != kSentinel) == 0ull) break;
 #if NTR_TI_FAST
@@ -135,11 +157,24 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
             // 0x0FFFFFF0 is at or beyond the end of any mask array (4 * numInstances <= kPoolMaxBytes / 16): it reads 0 and touches nothing
             const unsigned long long enter = __ballot(top && neg);
             fetch64_four_buffers_and_word(rTlas, rRec, rNodes, rWoop, rMasks, ofs, (int)((unsigned)ofs >> 4), __ballot(top && inner), enter,
-                                          __ballot(!top && inner), __ballot(!top && neg), instMasks ? enter : 0ull, a, b, c, d, instMask);
+                                          __ballot(!top && inner),
+#if NTR_TI_DEFORM
+                                          __ballot(!top && neg && !deform),   // (a deforming BLAS's Woop rows are key 0's: not read)
+#else
+                                          __ballot(!top && neg),
+#endif
+                                          instMasks ? enter : 0ull, a, b, c, d, instMask);
         } else {
             fetch64_four_buffers(rTlas, rRec, rNodes, rWoop, ofs, __ballot(top && inner), __ballot(top && neg), __ballot(!top && inner),
                                  __ballot(!top && neg), a, b, c, d);
         }
+#if NTR_TI_DEFORM
+        // the one wave-uniform branch: lanes inside a deforming BLAS (`deform` implies !top; the marker and the sentinel are neither
+        // inner nor neg) fetch what the pose needs at the same offset, with one wait
+        const unsigned long long deformN = __ballot(deform && inner), deformT = __ballot(deform && neg);
+        const bool deformWave = (deformN | deformT) != 0ull;
+        if (deformWave) fetch_deform_rows(rNodes1, rVerts0, rVerts1, ofs, deformN, deformT, a, b, c, e, f, g, nextW);
+#endif
         if (node == kSentinel) {
             // done: waits for the wave
         } else if (!inner && !neg) {
@@ -149,6 +184,9 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
                 r.ox = o.x; r.oy = o.y; r.oz = o.z;
                 r.dx = dd.x; r.dy = dd.y; r.dz = dd.z;
                 inst = -1;
+#if NTR_TI_DEFORM
+                deform = false;
+#endif
 #if NTR_TI_FAST
                 nice = level_nice(r, heldTlas);
                 NTR_TI_NICE_PIN(nice);
@@ -176,14 +214,18 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
 #if NTR_TI_MOTION
             // a record whose word 15 is set names a moving instance: worldToObject(t) replaces the record's rows a, b, c.  The wave
             // votes, so one that enters only static instances runs the masked kernel's step behind one scalar branch
-            if (__ballot(__float_as_uint(d.w) != 0u) != 0ull && __float_as_uint(d.w) != 0u && !motion_pose(rKeys, idx, rayTime, a, b, c)) {
+            if (__ballot(NTR_TI_MOVING(d.w)) != 0ull && NTR_TI_MOVING(d.w) && !motion_pose(rKeys, idx, rayTime, a, b, c)) {
                 if (STATS) singularSteps++;
                 node = stack_pop(st, spill);         // no inverse at this time: no marker, no transform
             } else
 #endif
             {
 #if NTR_TI_MOTION
-                if (STATS) movingEntries += __float_as_uint(d.w) != 0u ? 1u : 0u;
+                if (STATS) movingEntries += NTR_TI_MOVING(d.w) ? 1u : 0u;
+#endif
+#if NTR_TI_DEFORM
+                deform = (__float_as_uint(d.w) & 2u) != 0u;
+                if (STATS) deformEntries += deform ? 1u : 0u;
 #endif
                 stack_push(st, spill, kExitMarker, p.status);
                 const float ox = dot4(a, r.ox, r.oy, r.oz, 1.0f), oy = dot4(b, r.ox, r.oy, r.oz, 1.0f), oz = dot4(c, r.ox, r.oy, r.oz, 1.0f);
@@ -203,6 +245,40 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
             }
         } else {
             int row = -1;   // the BLAS's own row of a hit this step accepts
+#if NTR_TI_DEFORM
+            // an inner lane of a deforming BLAS poses its twelve box words in place (the links are key 0's) and goes on with the others
+            if (deformWave && deform && inner) {
+                if (STATS) deformInner++;
+                a = motion_deform_lerp4(a, e, rayTime, rayTimeU); b = motion_deform_lerp4(b, f, rayTime, rayTimeU);
+                c = motion_deform_lerp4(c, g, rayTime, rayTimeU);
+            }
+            // a triangle lane of a deforming BLAS: the terminator is the W word of key 0's vertex row (a vertex x of -0.0f is the same
+            // word as the terminator); otherwise nine posed words, their Woop rows and the unchanged triangle test
+            if (deformWave && deform && neg) {
+                bool leafDone = __float_as_uint(a.w) == kLeafTerm;
+                if (!leafDone) {
+                    if (STATS) { ls.tris++; deformTris++; }
+                    float4 w0, w1, w2;
+                    woop_rows_verts(motion_deform_lerp(a.x, e.x, rayTime, rayTimeU), motion_deform_lerp(a.y, e.y, rayTime, rayTimeU),
+                                    motion_deform_lerp(a.z, e.z, rayTime, rayTimeU), motion_deform_lerp(b.x, f.x, rayTime, rayTimeU),
+                                    motion_deform_lerp(b.y, f.y, rayTime, rayTimeU), motion_deform_lerp(b.z, f.z, rayTime, rayTimeU),
+                                    motion_deform_lerp(c.x, g.x, rayTime, rayTimeU), motion_deform_lerp(c.y, g.y, rayTime, rayTimeU),
+                                    motion_deform_lerp(c.z, g.z, rayTime, rayTimeU), w0, w1, w2);
+                    bool terminated = false;
+                    if (triangle_step(w0, w1, w2, r, hitU, hitV)) {
+                        row = leaf_row(node);
+                        terminated = anyHit;
+                    }
+                    if (terminated) node = kSentinel;
+                    else if (nextW == kLeafTerm) leafDone = true;   // the terminator came with this triangle
+                    else node -= kTriRows;
+                }
+                if (leafDone) {
+                    if (STATS) ls.leaves++;
+                    node = stack_pop(st, spill);
+                }
+            } else
+#endif
             if (STATS) {
                 // counted at the call site, from the row just fetched: a triangle test unless word 0 is the terminator; a terminator read for
                 // the row itself or for the word that came with a triangle -- unless an any-hit ray ended on that triangle
@@ -259,6 +335,11 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
         atomicAdd(&x.stats[12], (unsigned long long)movingEntries);
         atomicAdd(&x.stats[13], (unsigned long long)singularSteps);
 #endif
+#if NTR_TI_DEFORM
+        atomicAdd(&x.stats[14], (unsigned long long)deformEntries);
+        atomicAdd(&x.stats[15], (unsigned long long)deformInner);
+        atomicAdd(&x.stats[16], (unsigned long long)deformTris);
+#endif
 #if NTR_TI_FAST
         if (lane == 0) {   // (lane 0 of a launched wave is a ray)
             atomicAdd(&x.stats[8], (unsigned long long)waveSteps);
@@ -272,3 +353,4 @@ __global__ __launch_bounds__(64) void NTR_TI_KERNEL(NTR_TI_PARAMS)
 #if NTR_TI_FAST
 #undef NTR_TI_NICE_PIN
 #endif
+#undef NTR_TI_MOVING

@@ -23,6 +23,7 @@
 #include "instance_motion.h"
 #include "trace_launch.h"
 #include "trace_lane.h"
+#include "trace_deform_pose.h"
 #include "woop_rows.h"
 
 namespace ntr {
@@ -41,17 +42,7 @@ struct MotionParams {
     unsigned long long* stats;               // STATS: {inner nodes visited, triangle tests, leaf terminators, hits}
 };
 
-// deform_lerp of the spec, per word: the keys themselves at the two ends, both products rounded in between; u = 1.0f - t
-__device__ __forceinline__ float motion_deform_lerp(float a, float b, float t, float u)
-{
-    const float v = u * a + t * b;
-    return t == 0.0f ? a : (t == 1.0f ? b : v);
-}
-__device__ __forceinline__ float4 motion_deform_lerp4(const float4& a, const float4& b, float t, float u)
-{
-    return make_float4(motion_deform_lerp(a.x, b.x, t, u), motion_deform_lerp(a.y, b.y, t, u), motion_deform_lerp(a.z, b.z, t, u),
-                       motion_deform_lerp(a.w, b.w, t, u));
-}
+// motion_deform_lerp, deform_lerp of the spec per word, is trace_deform_pose.h's, shared with the two-level unit
 
 // Lanes of maskN fetch rows 0..3 of the node at byte offset `ofs` of nodes0 into a..d and rows 0..2 of nodes1 into e..g; lanes of maskT
 // rows 0..2 at `ofs` of verts0 into a..c, of verts1 into e..g, and the w word of verts0's row behind them into nextW (range-checked:

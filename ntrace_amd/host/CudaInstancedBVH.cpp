@@ -139,6 +139,60 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
     if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
 }
 
+void CudaInstancedBVH::refitBLASesMotion(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos0, Buffer& vtxPos1, const S32* blas, S32 num, F32 epsilon)
+{
+    num = selectionSize(blas, num, getNumBLAS(), "refit (call buildBLASes first)");
+    meshTriangles(triVtxIndex, numVerts, vtxPos0);
+    meshTriangles(triVtxIndex, numVerts, vtxPos1);
+    for (S32 i = 0; i < num; i++) {
+        const S32 b = selectedBLAS(blas, i, getNumBLAS());
+        if (m_meshes[b].numTris < 1) fail("CudaInstancedBVH: BLAS %d came through addBLAS and has no mesh here: refit its CudaBVH and add it again", b);
+    }
+    // BLASes that an earlier call made deforming stay so while their second key is still the pool's
+    const bool keep = hasDeform() && m_deformFlags.size() == m_ranges.size();
+    if (!keep) m_deformFlags.assign(m_ranges.size(), 0u);
+    m_state.wrote(W::PoolBoxes);                 // key 0 is refitted in place, as refitBLASes: refit() or build() again
+    m_state.wrote(W::PoolKey1);
+    if (keep) {
+        m_poolNodes1.resize(m_poolNodes.getSize());
+        m_poolVertRows0.resize(m_poolTriWoop.getSize());
+        m_poolVertRows1.resize(m_poolTriWoop.getSize());
+    } else {
+        m_poolNodes1.resizeDiscard(m_poolNodes.getSize());
+        m_poolVertRows0.resizeDiscard(m_poolTriWoop.getSize());
+        m_poolVertRows1.resizeDiscard(m_poolTriWoop.getSize());
+    }
+    m_hasDeform = false;
+    U8 *nodes0 = (U8*)m_poolNodes.getMutableCudaPtr(), *nodes1 = (U8*)m_poolNodes1.getMutableCudaPtr(), *woop = (U8*)m_poolTriWoop.getMutableCudaPtr();
+    U8 *rows0 = (U8*)m_poolVertRows0.getMutableCudaPtr(), *rows1 = (U8*)m_poolVertRows1.getMutableCudaPtr();
+    const U8* index = (const U8*)m_poolTriIndex.getCudaPtr();
+    for (S32 i = 0; i < num; i++) {
+        const S32 b = selectedBLAS(blas, i, getNumBLAS());
+        const NtrBlasRange& r = m_ranges[b];
+        NtrBvhRefitResult res;
+        const int rc = ntr_bvh_motion_refit(nodes0 + r.nodesOffset, r.nodesBytes, nodes1 + r.nodesOffset, woop + r.triWoopOffset, r.triWoopBytes,
+                                            (const int32_t*)(index + r.triWoopOffset / 4), r.triWoopBytes / 4, rows0 + r.triWoopOffset,
+                                            rows1 + r.triWoopOffset, m_meshes[b].numTris,
+                                            (const int32_t*)triVtxIndex.getCudaPtr() + 3 * (size_t)m_meshes[b].firstTri, numVerts,
+                                            (const float*)vtxPos0.getCudaPtr(), (const float*)vtxPos1.getCudaPtr(), epsilon, NULL, &res, NULL);
+        if (rc != NTR_OK) fail("CudaInstancedBVH: BLAS %d: %s", b, ntr_last_error());
+        m_deformFlags[(size_t)b] = 1u;
+    }
+    m_blasDeforming.resizeDiscard((S64)m_deformFlags.size() * sizeof(U32));
+    m_blasDeforming.set(m_deformFlags.data(), (S64)m_deformFlags.size() * sizeof(U32));
+    m_hasDeform = true;
+    m_state.made(P::PoolDeform);
+}
+
+void CudaInstancedBVH::clearDeform(void)
+{
+    // the pool stays refitted to key 0 and the TLAS's boxes still bound the sweep: isBuilt() stays, as after clearMotion()
+    m_hasDeform = false;
+    m_deformFlags.assign(m_ranges.size(), 0u);
+    m_state.wrote(W::PoolKey1);
+    m_state.lost(P::PoolDeform);
+}
+
 void CudaInstancedBVH::selectRanges(const S32* blas, S32 num, std::vector<NtrBlasRange>& out, const char* what) const
 {
     num = selectionSize(blas, num, getNumBLAS(), what);
@@ -330,12 +384,22 @@ void CudaInstancedBVH::clearMotion(void)
 
 void CudaInstancedBVH::refitMotion(void)
 {
-    if (!m_hasMotion) fail("CudaInstancedBVH: no motion key: call setMotionKey first");
+    const bool deform = hasDeform();
+    if (!m_hasMotion && !deform) fail("CudaInstancedBVH: no motion key: call setMotionKey first");
     if (!isBuilt()) fail("CudaInstancedBVH: No TLAS!");
     const bool wasCurrent = !isMotionStale();
     m_state.wrote(W::TlasBoxes);                 // the binary boxes become the swept ones: as refit()
     m_motionKeys.resizeDiscard((S64)m_numInstances * 128);
-    const int rc = ntr_tlas_motion_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (const NtrInstance*)m_instances1.getCudaPtr(),
+    // with deforming BLASes the leaf boxes are the unions over both keys of the instances AND of the BLASes, and the records say which
+    // instances' BLASes deform; without a motion key the instances' key 1 is key 0
+    const int rc = deform
+        ? ntr_tlas_deform_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(),
+                                (const NtrInstance*)(m_hasMotion ? m_instances1 : m_instances).getCudaPtr(), (int32_t)m_ranges.size(), m_ranges.data(),
+                                m_poolNodes.getCudaPtr(), m_poolNodes1.getCudaPtr(), m_poolNodes.getSize(),
+                                (const uint32_t*)m_blasDeforming.getCudaPtr(), m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL,
+                                m_result.nodesBytes, m_result.rootLink, m_records.getMutableCudaPtr(), m_records.getSize(),
+                                m_motionKeys.getMutableCudaPtrDiscard(), m_motionKeys.getSize(), NULL, &m_deformRefitResult, NULL)
+        : ntr_tlas_motion_refit(m_numInstances, (const NtrInstance*)m_instances.getCudaPtr(), (const NtrInstance*)m_instances1.getCudaPtr(),
                                          (int32_t)m_ranges.size(), m_ranges.data(), m_poolNodes.getCudaPtr(), m_poolNodes.getSize(),
                                          m_result.nodesBytes ? m_tlasNodes.getMutableCudaPtr() : NULL, m_result.nodesBytes, m_result.rootLink,
                                          m_records.getMutableCudaPtr(), m_records.getSize(), m_motionKeys.getMutableCudaPtrDiscard(),
@@ -346,6 +410,7 @@ void CudaInstancedBVH::refitMotion(void)
         if (wasCurrent) m_state.made(P::MotionRefit);   // outside the table: a failed call leaves isMotionStale() as it was
         fail("CudaInstancedBVH: %s", ntr_last_error());
     }
+    if (deform) m_motionRefitResult = m_deformRefitResult.motion;
     takeSceneBox(m_result, m_motionRefitResult.refit);
     m_state.made(P::MotionRefit);
 }
@@ -501,12 +566,23 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
         if (m_traceFast) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setTraceFast: clearMotion() or setTraceFast(false)");
         if (m_world >= 0) fail("CudaInstancedBVH: motion (setMotionKey) is not combinable with setWorld: clearMotion() or clearWorld()");
     }
+    const bool deform = hasDeform();
+    if (deform) {
+        // deforming BLASes exist over the binary trees only, without FAST flags and without a seed: nothing is ignored silently
+        if (m_traceWideMotion)
+            fail("CudaInstancedBVH: deforming BLASes (refitBLASesMotion) are not combinable with setTraceWideMotion: clearDeform() or setTraceWideMotion(false)");
+        if (m_traceWide) fail("CudaInstancedBVH: deforming BLASes (refitBLASesMotion) are not combinable with setTraceWide: clearDeform() or setTraceWide(false)");
+        if (m_traceWideFast) fail("CudaInstancedBVH: deforming BLASes (refitBLASesMotion) are not combinable with setTraceWideFast: clearDeform() or setTraceWideFast(false)");
+        if (m_traceFast) fail("CudaInstancedBVH: deforming BLASes (refitBLASesMotion) are not combinable with setTraceFast: clearDeform() or setTraceFast(false)");
+        if (m_world >= 0) fail("CudaInstancedBVH: deforming BLASes (refitBLASesMotion) are not combinable with setWorld: clearDeform() or clearWorld()");
+    }
     if (!isBuilt()) fail("CudaInstancedBVH: No TLAS!");
-    if (m_hasMotion && m_rayTimes && m_rayTimes->getSize() < (S64)numRays * (S64)sizeof(F32))
+    const bool timed = m_hasMotion || deform;    // the rays carry times
+    if (timed && m_rayTimes && m_rayTimes->getSize() < (S64)numRays * (S64)sizeof(F32))
         fail("CudaInstancedBVH: setRayTimes' buffer holds fewer than %d times", numRays);
-    if (m_hasMotion && m_traceWide) {            // (m_traceWideMotion: checked above) both trees, the wide one in place, exactly once
+    if (m_hasMotion && m_traceWide) {            // (m_traceWideMotion: checked above; never with deform) both trees, the wide one in place, exactly once
         if (isMotionWideStale()) refitMotionWide();
-    } else if (m_hasMotion && isMotionStale()) refitMotion();
+    } else if (timed && isMotionStale()) refitMotion();
     float seconds = 0.0f, worldSeconds = 0.0f;
     const bool masks = m_instanceMasks.getSize() == (S64)m_numInstances * (S64)sizeof(U32);
     const bool world = m_world >= 0, wide = m_traceWide && isWide();
@@ -535,7 +611,13 @@ F32 CudaInstancedBVH::traceBatch(RayBuffer& rays, Buffer& instanceIDs, U32 rayMa
     const void* d_woop = m_poolTriWoop.getCudaPtr();
     const int64_t woopBytes = m_poolTriWoop.getSize();
     const int32_t* d_index = (const int32_t*)m_poolTriIndex.getCudaPtr();
-    if (m_hasMotion) {
+    if (deform) {
+        const NtrInstanceMotion motion = {m_motionKeys.getCudaPtr(), m_motionKeys.getSize(),
+                                          m_rayTimes ? (const float*)m_rayTimes->getCudaPtr() : NULL, m_time, 0.0f};
+        const NtrInstanceDeform df = {m_poolNodes1.getCudaPtr(), m_poolVertRows0.getCudaPtr(), m_poolVertRows1.getCudaPtr()};
+        rc = ntr_trace_instanced_deform(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records, m_numInstances,
+                                        d_nodes, nodesBytes, d_woop, woopBytes, d_index, &vis, &motion, &df, &seconds, NULL);
+    } else if (m_hasMotion) {
         const NtrInstanceMotion motion = {m_motionKeys.getCudaPtr(), m_motionKeys.getSize(),
                                           m_rayTimes ? (const float*)m_rayTimes->getCudaPtr() : NULL, m_time, 0.0f};
         rc = wide ? ntr_trace_instanced_wide_motion(numRays, anyHit, d_rays, d_results, d_ids, d_tlas, tlasBytes, m_result.rootLink, d_records,

@@ -68,6 +68,14 @@
 //                 traceBatch takes ntr_trace_instanced_wide_motion, after refitMotionWide() if isMotionWideStale(); else the binary launch
 //   refitMotionWide  refitMotion(), then ntr_tlas_wide_motion_refit in place over the wide TLAS and records; needs what refitWide() and
 //                 refitMotion() need.  writes: TlasBoxes, WideTlas; makes: MotionRefit, WideTlas, WideMotionRefit
+//   refitBLASesMotion   deformation inside the shutter: refits the selected BLASes to TWO vertex arrays, the shutter's opening
+//                 and its close (ntr_bvh_motion_refit at pool + offset, one call per BLAS; a batch form is a later step), into the pool and
+//                 into key-1 buffers that this object owns -- the second key's nodes, the two keys' vertex rows and a flag per BLAS -- and
+//                 marks them deforming.  While hasDeform(), refitMotion() takes ntr_tlas_deform_refit (without a motion key it passes key 0
+//                 twice) and traceBatch ntr_trace_instanced_deform, after refitMotion() if isMotionStale().  A later refitBLASes,
+//                 optimizeBLASes, buildBLASes or addBLAS leaves the second key stale: hasDeform() drops and the scene is key 0's again.
+//                 clearDeform() drops it by hand.  With hasDeform(), setTraceWide, setTraceFast, setTraceWideFast, setTraceWideMotion and a
+//                 world are not combinable: traceBatch fail()s naming the switch.  writes: PoolBoxes, PoolKey1; makes: PoolDeform
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and carries Renderer's batching.  Per frame, a moving, deforming
 // scene is refitBLASes -> optimizeBLASes every so many frames -> setInstances (or setInstancesDevice: no step then computes on the host) ->
 // refit -> InstancedRenderer::beginFrame -> nextBatch / traceBatch / updateResult per batch, with build() every so many frames; on the wide
@@ -117,6 +125,15 @@ public:
     void refitMotion(void);
     S32  getMotionRefits(void) const { return m_motionRefits; }                  // ntr_tlas_motion_refit calls so far
     const NtrTlasMotionRefitResult& getMotionRefitResult(void) const { return m_motionRefitResult; }   // of the last refitMotion (zero before)
+    // blas: num indices of BLASes, each at most once (NULL: all of them), each with a mesh of buildBLASes; vtxPos0 / vtxPos1: the shutter's
+    // opening and close over the triangles buildBLASes saw
+    void refitBLASesMotion(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos0, Buffer& vtxPos1, const S32* blas = NULL, S32 num = -1, F32 epsilon = 0.f);
+    void clearDeform(void);
+    bool hasDeform(void) const { return m_hasDeform && m_state.isPoolDeformCurrent(); }
+    const NtrTlasDeformRefitResult& getDeformRefitResult(void) const { return m_deformRefitResult; }   // of the last refitMotion with hasDeform() (zero before)
+    Buffer& getPoolNode1Buffer(void) { return m_poolNodes1; }                    // the second key's nodes; with getPoolVertRowBuffer(0 / 1) NtrInstanceDeform
+    Buffer& getPoolVertRowBuffer(S32 key) { return key ? m_poolVertRows1 : m_poolVertRows0; }
+    Buffer& getBLASDeformingBuffer(void) { return m_blasDeforming; }             // U32 per BLAS, on the device
     void setTraceWideMotion(bool on) { m_traceWideMotion = on; }                 // motion over the 4-wide trees, with setTraceWide(true)
     bool getTraceWideMotion(void) const { return m_traceWideMotion; }
     void refitMotionWide(void);
@@ -225,6 +242,11 @@ private:
     bool          m_hasMotion = false, m_traceWideMotion = false;                // key 1 is set; motion over the 4-wide trees (setTraceWideMotion)
     S32           m_motionRefits = 0, m_motionWideRefits = 0;
     NtrTlasMotionRefitResult m_motionRefitResult = {}, m_motionWideRefitResult = {};
+    // deforming BLASes (refitBLASesMotion): the pool's key-1 buffers and the flag per BLAS that ntr_tlas_deform_refit reads
+    Buffer        m_poolNodes1, m_poolVertRows0, m_poolVertRows1, m_blasDeforming;
+    std::vector<U32> m_deformFlags;                                              // per BLAS, as m_ranges
+    bool          m_hasDeform = false;
+    NtrTlasDeformRefitResult m_deformRefitResult = {};
 };
 
 }  // namespace FW

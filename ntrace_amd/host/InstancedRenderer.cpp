@@ -101,6 +101,9 @@ void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& ti
 
 void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
 {
+    if (m_motionBlur && m_bvh.hasDeform())
+        fail("InstancedRenderer: setMotionBlur is not combinable with deforming BLASes (CudaInstancedBVH::refitBLASesMotion): the normals of their "
+             "hits would be key 0's; clearDeform() or setMotionBlur(false)");
     if (m_motionBlur && !m_bvh.hasMotion())
         fail("InstancedRenderer: setMotionBlur is on and the CudaInstancedBVH has no motion key: call setMotionKey (or setMotionKeyDevice) with the "
              "shutter's closing transforms, or setMotionBlur(false)");

@@ -21,6 +21,7 @@ public:
         TlasBoxes,         // the binary TLAS's boxes and the records: build, refit, refitMotion
         WidePool,          // the wide pool's nodes: widen, refitBLASesWide
         WideTlas,          // the wide TLAS and the wide records: widen, refitWide, refitMotionWide
+        PoolKey1,          // the pool's key-1 buffers (second key's nodes, vertex rows, deforming flags): refitBLASesMotion, clearDeform
         Count
     };
     enum class Product {   // what can be current
@@ -34,6 +35,7 @@ public:
         MotionRefit,       // the binary boxes are the swept ones, the records hold the moving flags
         WideMotionRefit,   // the same of the wide TLAS and records
         BlasTris,          // the device table of the meshes buildBLASes remembers
+        PoolDeform,        // the pool's key-1 buffers and flags belong to the pool's current boxes: hasDeform()
         Count
     };
     explicit InstancedState(unsigned products = 0u) : m_products(products) {}
@@ -49,7 +51,9 @@ public:
              : p == Product::FastFlags ? voidedBy(Product::WidePool) | bit(Write::TlasTopology) | bit(Write::TlasBoxes) | bit(Write::World)
              : p == Product::WideFastFlags ? voidedBy(Product::FastFlags) | bit(Write::WidePool) | bit(Write::WideTlas)
              : p == Product::MotionRefit ? bit(Write::Instances) | bit(Write::InstanceCount) | bit(Write::MotionKey) | bit(Write::TlasTopology) | bit(Write::TlasBoxes)
+                                          | bit(Write::PoolKey1)
              : p == Product::WideMotionRefit ? bit(Write::WideTlas)
+             : p == Product::PoolDeform ? voidedBy(Product::WidePool)   // a plain refit or an optimize leaves the second key's nodes stale
              : /* BlasTris */ bit(Write::PoolTrees);
     }
     static constexpr bool voids(Write w, Product p) { return (voidedBy(p) & bit(w)) != 0u; }
@@ -66,6 +70,7 @@ public:
     bool isFastFlagsStale(void) const { return !has(Product::FastFlags); }
     bool isWideFastFlagsStale(void) const { return !has(Product::WideFastFlags); }
     bool isMotionStale(void) const { return !has(Product::MotionRefit); }
+    bool isPoolDeformCurrent(void) const { return has(Product::PoolDeform); }
     bool isMotionWideStale(void) const { return isMotionStale() || !has(Product::WideMotionRefit) || !has(Product::WideTlas); }
     bool mayRefit(void) const { return has(Product::TlasTopology); }
     bool mayRefitWide(void) const { return mayRefit() && has(Product::WideTopology); }

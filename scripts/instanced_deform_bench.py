@@ -1,0 +1,221 @@
+#!/usr/bin/env python
+"""What deforming BLASes cost in the motion-blurred two-level trace (ntr_trace_instanced_deform, ntr_tlas_deform_refit), over
+the two frames of scripts/instanced_motion_bench.py: the 1920 x 1080 primary batch (closest hit) and 2^20 host-made AO rays (any hit)
+through ONE identity instance of atrium() and through the forest of 4 096 instances of soup1000, whose instances all move.
+  * none      no BLAS is flagged, per-ray times: the deform launch against the motion launch over the same buffers -- the price of the
+              new kernel on scenes that do not use it.  The records must be equal.
+  * time0     every BLAS deforms (np_bvh_refit.deform at 0.05), every ray at time 0: the deform launch against the motion launch over
+              the same buffers, whose Woop rows are key 0's.  The records must be equal: this is the kernel's own cost
+  * hashed    every BLAS deforms, random times in [0, 1): against the motion launch over the same buffers (the meshes frozen at key 0
+              inside the swept boxes), with the counters and the algorithmic bytes
+  * refit     ntr_tlas_deform_refit against ntr_tlas_motion_refit, both asynchronous (two launches each), by stream events
+  * blas      the per-BLAS loop of ntr_bvh_motion_refit against ntr_bvh_refit_batch over a pool of --blases copies of soup1000 (a
+              Compact tree's links are relative to its own start, so a copy at another offset is a BLAS), both asynchronous: whether a
+              batch form of the motion refit is worth building
+Both launches get the same visibility, a ray mask of 0x7FFFFFFF that refuses nothing.  Launches are alternated, five runs after two
+warm-ups; every figure is the median with its minimum and maximum.  One JSON line per row; --out writes them as a list.  Every GPU step
+runs under a time limit of its own.
+
+    timeout -k 10 600 python scripts/instanced_deform_bench.py --out instanced_deform.json
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402
+
+import ntrace_amd as nt  # noqa: E402
+from ntrace_amd import scenes  # noqa: E402
+from instanced_bench import Blas, Tlas, host_ao_rays, rotations, step, transforms, up  # noqa: E402
+from instanced_motion_bench import key1, spread  # noqa: E402
+from np_bvh_refit import deform  # noqa: E402
+
+F = np.float32
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--ao-rays", type=int, default=1 << 20)
+    ap.add_argument("--blases", type=int, default=256)
+    ap.add_argument("--limit", type=int, default=120, help="seconds a GPU step may take")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    stream = torch.cuda.current_stream().cuda_stream
+    rows = []
+
+    def emit(row):
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+
+    def pose(b, d_nodes, d_nodes1, d_woop, d_v0, d_v1, d_pos1, k=0, blocking=False):
+        """ntr_bvh_motion_refit of copy k of BLAS b inside pool buffers"""
+        nt.bvh_motion_refit(d_nodes.data_ptr() + k * b.nb, b.nb, d_nodes1.data_ptr() + k * b.nb, d_woop.data_ptr() + k * b.wb, b.wb,
+                            b.bufs[2].data_ptr(), b.wb // 4, d_v0.data_ptr() + k * b.wb, d_v1.data_ptr() + k * b.wb, b.tri.shape[0], b.d_tri.data_ptr(),
+                            b.pos.shape[0], b.d_pos.data_ptr(), d_pos1.data_ptr(), 0.0, stream=stream, blocking=blocking)
+
+    def frame(name, t, tf, cam):
+        b, r = t.blas, t.res
+        rays, _ = scenes.primary_rays(cam, args.width, args.height)
+        n, na = rays.shape[0], args.ao_rays
+        d_rays, d_res, d_ids, d_mres, d_mids = step(name + " buffers", args.limit, lambda: [up(rays)] + [
+            torch.zeros(max(n, na) * w, dtype=torch.uint8, device="cuda:0") for w in (16, 4, 16, 4)])
+        hashed = np.random.default_rng(11).random(max(n, na)).astype(F)
+        d_times = up(hashed)
+        d_keys = torch.zeros(128 * t.n, dtype=torch.uint8, device="cuda:0")
+        d_inst1 = up(nt.make_instances(key1(tf), np.zeros(t.n, np.int32)))
+        d_nodes1, d_v0, d_v1 = (torch.zeros(c, dtype=torch.uint8, device="cuda:0") for c in (b.nb, b.wb, b.wb))
+        d_pos1, d_flags = up(deform(b.pos, 0.05)), up(np.zeros(1, np.uint32))
+        motion = nt.InstanceMotion(d_keys.data_ptr(), 128 * t.n, d_times.data_ptr(), 0.0)
+        dfm = nt.InstanceDeform(d_nodes1.data_ptr(), d_v0.data_ptr(), d_v1.data_ptr())
+        vis = nt.InstanceVisibility(0, 0, 0x7FFFFFFF)         # refuses nothing, and selects the masked loop
+
+        def tail():
+            return (t.d_nodes.data_ptr() if r.nodesBytes else 0, r.nodesBytes, r.rootLink, t.d_rec.data_ptr(), 64 * t.n, d_keys.data_ptr(), 128 * t.n,
+                    0, stream)
+
+        def deform_refit(blocking):
+            return nt.tlas_deform_refit(t.n, t.d_inst.data_ptr(), d_inst1.data_ptr(), b.ranges, b.bufs[0].data_ptr(), d_nodes1.data_ptr(), b.nb,
+                                        d_flags.data_ptr(), *tail(), blocking)
+
+        def motion_refit(blocking):
+            return nt.tlas_motion_refit(t.n, t.d_inst.data_ptr(), d_inst1.data_ptr(), b.ranges, b.bufs[0].data_ptr(), b.nb, *tail(), blocking)
+
+        # key 0 of the pool is refitted in place before anything is traced, so every part runs over the same key-0 bytes
+        step(name + " BLAS motion refit", args.limit, lambda: pose(b, b.bufs[0], d_nodes1, b.bufs[1], d_v0, d_v1, d_pos1, blocking=True))
+
+        def first_primary():
+            motion_refit(True)
+            nt.trace_instanced_motion(*t.args(n, False, d_rays, d_res, d_ids), vis=vis, motion=nt.InstanceMotion(d_keys.data_ptr(), 128 * t.n, 0, 0.0),
+                                      stream=stream)
+            torch.cuda.synchronize()
+            return d_res.cpu().numpy()[:16 * n].view(nt.RESULT_DTYPE).copy()
+        res = step(name + " primary for the ao rays", args.limit, first_primary)
+        d_ao = step(name + " ao upload", args.limit, lambda: up(host_ao_rays(rays, res, na, 7)))
+
+        def batch(what, count, any_hit, d_r, equal):
+            def check():                                      # records (where they must be equal) and counters, before anything is timed
+                mst, mm = nt.trace_instanced_motion_stats(*t.args(count, any_hit, d_r, d_res, d_ids), vis=vis, motion=motion, stream=stream)
+                dst, dm, dd = nt.trace_instanced_deform_stats(*t.args(count, any_hit, d_r, d_mres, d_mids), vis=vis, motion=motion, deform=dfm,
+                                                              stream=stream)
+                torch.cuda.synchronize()
+                if equal:
+                    assert torch.equal(d_res[:16 * count], d_mres[:16 * count]) and torch.equal(d_ids[:4 * count], d_mids[:4 * count]), \
+                        "%s %s: the deform launch's records differ from the motion launch's" % (name, what)
+                    assert mst.as_dict() == dst.as_dict() and mm.as_dict() == dm.as_dict()
+                return dst, dm, dd
+            dst, dm, dd = step("%s %s records and counters" % (name, what), args.limit, check)
+
+            def run():
+                a, m = [], []
+                for _ in range(args.warmup + args.reps):      # alternated: motion, deform, motion, deform, ...
+                    a.append(nt.trace_instanced_motion(*t.args(count, any_hit, d_r, d_res, d_ids), vis=vis, motion=motion, stream=stream))
+                    m.append(nt.trace_instanced_deform(*t.args(count, any_hit, d_r, d_mres, d_mids), vis=vis, motion=motion, deform=dfm, stream=stream))
+                return a[args.warmup:], m[args.warmup:]
+            a, m = step("%s %s" % (name, what), args.limit, run)
+            out = {"rays": count, "motion_ms": spread(a, 1e3), "deform_ms": spread(m, 1e3),
+                   "deform_counters": dict(dst.as_dict(), **dm.as_dict(), **dd.as_dict()),
+                   "deform_algorithmic_bytes": int(dd.algorithmic_bytes(dst, dm, ray_times=True))}
+            out["deform_over_motion"] = out["deform_ms"]["median"] / out["motion_ms"]["median"]
+            out["deform_inner_visits_per_ray"] = dd.numDeformInnerVisits / count
+            out["deform_tri_tests_per_ray"] = dd.numDeformTriTests / count
+            return out
+
+        for part, flag, times in (("none", 0, hashed), ("time0", 1, np.zeros_like(hashed)), ("hashed", 1, hashed)):
+            d_flags.copy_(up(np.full(1, flag, np.uint32)))
+            d_times.copy_(up(times))
+            rr = step("%s %s deform refit" % (name, part), args.limit, lambda: deform_refit(True))
+            row = {"part": part, "frame": name, "instances": t.n, "moving": int(rr.motion.numMoving), "deforming": int(rr.numDeforming)}
+            row["primary"] = batch(part + " primary", n, False, d_rays, part != "hashed")
+            row["ao"] = batch(part + " ao", na, True, d_ao, part != "hashed")
+            emit(row)
+
+        def refits():
+            p, m = [], []
+            for _ in range(args.warmup + args.reps):          # alternated: motion, deform, motion, deform, ...
+                p.append(timed(lambda: motion_refit(False)))
+                m.append(timed(lambda: deform_refit(False)))
+            return p[args.warmup:], m[args.warmup:]
+        p, m = step(name + " refits", args.limit, refits)
+        row = {"part": "refit", "frame": name, "instances": t.n, "tlas_motion_refit_ms": spread(p), "tlas_deform_refit_ms": spread(m),
+               "scratch_bytes": nt.tlas_deform_refit_scratch_bytes()}
+        row["deform_over_motion"] = row["tlas_deform_refit_ms"]["median"] / row["tlas_motion_refit_ms"]["median"]
+        emit(row)
+        assert nt.trace_status() == 0, "traversal stack overflow"
+
+    def blas_loop(b, copies):
+        """The per-BLAS loop of ntr_bvh_motion_refit against ntr_bvh_refit_batch over `copies` copies of BLAS b in one pool"""
+        d_nodes, d_woop = b.bufs[0][:b.nb].repeat(copies), b.bufs[1][:b.wb].repeat(copies)
+        d_idx = b.bufs[2][:b.wb // 4].repeat(copies)
+        d_nodes1, d_v0, d_v1 = torch.zeros_like(d_nodes), torch.zeros_like(d_woop), torch.zeros_like(d_woop)
+        d_pos1 = up(deform(b.pos, 0.05))
+        entries = [((k * b.nb, b.nb, k * b.wb, b.wb), 0, b.tri.shape[0]) for k in range(copies)]
+
+        def batch(blocking):
+            return nt.bvh_refit_batch(entries, d_nodes.data_ptr(), d_nodes.numel(), d_woop.data_ptr(), d_woop.numel(), d_idx.data_ptr(), b.tri.shape[0],
+                                      b.d_tri.data_ptr(), b.pos.shape[0], b.d_pos.data_ptr(), 0, stream, blocking)
+
+        def loop(blocking=False):
+            for k in range(copies):
+                nt.bvh_motion_refit(d_nodes.data_ptr() + k * b.nb, b.nb, d_nodes1.data_ptr() + k * b.nb, d_woop.data_ptr() + k * b.wb, b.wb,
+                                    d_idx.data_ptr() + k * (b.wb // 4), b.wb // 4, d_v0.data_ptr() + k * b.wb, d_v1.data_ptr() + k * b.wb,
+                                    b.tri.shape[0], b.d_tri.data_ptr(), b.pos.shape[0], b.d_pos.data_ptr(), d_pos1.data_ptr(), 0.0, stream=stream,
+                                    blocking=blocking)
+
+        def run():
+            batch(True)                                       # once blocking: the scratch and the held table
+            nt.bvh_motion_refit(d_nodes.data_ptr(), b.nb, d_nodes1.data_ptr(), d_woop.data_ptr(), b.wb, d_idx.data_ptr(), b.wb // 4, d_v0.data_ptr(),
+                                d_v1.data_ptr(), b.tri.shape[0], b.d_tri.data_ptr(), b.pos.shape[0], b.d_pos.data_ptr(), d_pos1.data_ptr(), 0.0,
+                                stream=stream)
+            p, m = [], []
+            for _ in range(args.warmup + args.reps):          # alternated: batch, loop, batch, loop, ...
+                p.append(timed(lambda: batch(False)))
+                m.append(timed(loop))
+            return p[args.warmup:], m[args.warmup:]
+        p, m = step("blas refits, %d copies" % copies, args.limit, run)
+        row = {"part": "blas", "blases": copies, "triangles_per_blas": int(b.tri.shape[0]), "refit_batch_ms": spread(p), "motion_refit_loop_ms": spread(m)}
+        row["loop_over_batch"] = row["motion_refit_loop_ms"]["median"] / row["refit_batch_ms"]["median"]
+        emit(row)
+
+    tri, pos, cam = scenes.atrium()
+    atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
+    tf = np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F)
+    frame("identity", step("identity tlas", args.limit, lambda: Tlas(atrium, tf, stream)), tf, cam)
+
+    tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
+    soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
+    rng = np.random.default_rng(4096)
+    g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+    tf = transforms(rotations(4096, rng), (g - 7.5) * 30.0)
+    cam = dict(eye=(40.0, 60.0, -420.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
+    frame("forest", step("forest tlas", args.limit, lambda: Tlas(soup, tf, stream)), tf, cam)
+    for copies in (1, args.blases):
+        blas_loop(soup, copies)
+
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
