@@ -390,6 +390,47 @@ NTR_API int ntr_selftest_division_hard(int32_t xExp, int32_t dExp, uint64_t* pai
  * with NTR_BVH_NOTINY in bvhFlags) disagree (must be 0 for every bit pattern).  Diagnostic, blocking. */
 NTR_API int ntr_selftest_ray_class(const NtrRay* d_rays, int32_t numRays, uint32_t bvhFlags, uint32_t* mismatches, void* stream);
 
+/* ---- device self tests of the shared device toolkit (radix_sort.h, device_prims.h) on inputs of the caller's choice: the production
+ * templates run as they stand and their results come back word for word (tests/test_device_prims_gpu.py compares them with the numpy
+ * references of tests/np_device_prims.py).  Diagnostic, blocking. ---- */
+
+/* Sorts n key words with ONE instantiation onesweep_pass_kernel<items, mode, skipTrivial> of those the builders and the ray sort launch:
+ * mode 0 with items 8, 16, 24 or 32 (skipTrivial 0) or items 8 (skipTrivial 1); mode 2 with items 8 (skipTrivial 0 or 1).  Mode 1 has no
+ * user and is not offered.
+ *   mode 0: d_keys[i] is the key of element i (stride must be 1), d_vals[i] its value; d_vals == NULL: the value of element i is i.
+ *   mode 2: the key word of element i is d_keys[d_vals[i] * stride], stride 1 or 6, every value in [0, n); the first pass fetches the word
+ *           and the others run in mode 0 on the dense (word, value) pairs, as the users chain them.
+ * passes (host): numPasses (1 .. 16) pairs (shift, pass number), shift in [0, 24], pass number in [0, 125] (the tile state's status
+ * bits hold no more).  The digit histograms of all passes are taken on the device, the tile state is cleared once, the passes ping-pong
+ * between two buffers of the library; the inputs are not written.  d_keysOut / d_valsOut (n words each) receive the last pass's keys and
+ * values, *errWord the passes' error word (0, or 2 after a look-back that gave up waiting).  forceTicket != 0 hands every pass the
+ * ticket counter whatever the grid size; otherwise the pass decides as it does for its users. */
+NTR_API int ntr_selftest_onesweep(int32_t items, int32_t mode, int32_t skipTrivial, int32_t n, const uint32_t* d_keys, int32_t stride,
+                                  const int32_t* d_vals, int32_t numPasses, const int32_t* passes, int32_t forceTicket,
+                                  uint32_t* d_keysOut, int32_t* d_valsOut, uint32_t* errWord, void* stream);
+/* The three-launch exclusive scan of n items of `type` (scan_local_store in workgroups of `threads` = 256 or 1024, scan_block_sums, the
+ * add): d_prefix[i] = in[0] + .. + in[i - 1], *total (host, one item) the sum of all.  NTR_SCAN_U4: four 32-bit counters per item. */
+#define NTR_SCAN_U32 0
+#define NTR_SCAN_I32 1
+#define NTR_SCAN_U64 2
+#define NTR_SCAN_U4 3
+NTR_API int ntr_selftest_scan(int32_t type, int32_t threads, int32_t n, const void* d_in, void* d_prefix, void* total, void* stream);
+/* scan_block_sums alone, one workgroup of `threads`, on nb >= 0 sums: d_out[i] = d_in[0] + .. + d_in[i - 1] (d_out == d_in: in place),
+ * the grand total to *total (host, one item) unless it is NULL. */
+NTR_API int ntr_selftest_scan_block_sums(int32_t type, int32_t threads, int32_t nb, const void* d_in, void* d_out, void* total, void* stream);
+/* The order-preserving float encoding on n (1 .. 2048) float words: d_single[i][6] = ord_enc, ord_dec(ord_enc), ord_enc_int,
+ * ord_dec_int(ord_enc_int), ord_to_int(ord_enc), ord_from_int(ord_to_int(ord_enc)) of word i; d_pairs[i * n + j][2] = ord_min, ord_max of
+ * (word i, word j) as float words, for every ordered pair. */
+NTR_API int ntr_selftest_float_order(int32_t n, const uint32_t* d_words, uint32_t* d_single, uint32_t* d_pairs, void* stream);
+/* Lane i of m (a multiple of 64: whole waves) merges box i (d_boxes[i][6]: min x y z, max x y z) into group d_group[i] (in [0, groups), or
+ * -1: none), once with atomic_max_box per lane and once word by word through wave_grouped_atomic.  d_groupsOut[path][group][26], path 0 the
+ * plain merge, 1 the grouped one: the six words, the group's member count, its corners by words_box without grow, with grow by eps, with
+ * count 0, and words_area.  d_foldsOut[i][6]: wave_min_u32, wave_max_u32, wave_sum_u32, wave_or_u32 of d_lane32 over lane i's wave and
+ * wave_min_u64 of d_lane64 (low, high word), as lane i received them. */
+NTR_API int ntr_selftest_box_words(int32_t m, const float* d_boxes, const int32_t* d_group, int32_t groups, float eps,
+                                   const uint32_t* d_lane32, const uint64_t* d_lane64, uint32_t* d_groupsOut, uint32_t* d_foldsOut,
+                                   void* stream);
+
 /* ---- ray production (callers of the hot path) -------- */
 
 /* PixelTable::recalculate (src/rt/ray/PixelTable.cpp:57-143): 8x8 pixel blocks in Morton

@@ -515,6 +515,11 @@ SYMBOLS = [
     ("ntr_selftest_division", C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_u32), _vp]),
     ("ntr_selftest_division_hard", C.c_int, [_i32, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp]),
     ("ntr_selftest_ray_class", C.c_int, [_vp, _i32, _u32, C.POINTER(_u32), _vp]),
+    ("ntr_selftest_onesweep", C.c_int, [_i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp, C.POINTER(_u32), _vp]),
+    ("ntr_selftest_scan", C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    ("ntr_selftest_scan_block_sums", C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    ("ntr_selftest_float_order", C.c_int, [_i32, _vp, _vp, _vp, _vp]),
+    ("ntr_selftest_box_words", C.c_int, [_i32, _vp, _vp, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     ("ntr_trace_bvh_stats", C.c_int, [C.c_char_p, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _u32, _vp,
                                       C.POINTER(TraceStats)]),
     ("ntr_bvh_validate", C.c_int, [_vp, _i64, C.POINTER(_u32), _vp]),
@@ -986,6 +991,50 @@ def selftest_ray_class(d_rays, num_rays, bvh_flags, stream=0):
     m = _u32(0)
     _check(lib().ntr_selftest_ray_class(_vp(d_rays), int(num_rays), int(bvh_flags), C.byref(m), _vp(stream)))
     return int(m.value)
+
+
+SCAN_U32, SCAN_I32, SCAN_U64, SCAN_U4 = 0, 1, 2, 3
+_SCAN_ITEM_BYTES = {SCAN_U32: 4, SCAN_I32: 4, SCAN_U64: 8, SCAN_U4: 16}
+# the (ITEMS, MODE, SKIP_TRIVIAL) instantiations of the one-sweep pass that the builders and the ray sort launch (mode 1 has no user)
+ONESWEEP_COMBOS = ((8, 0, False), (16, 0, False), (24, 0, False), (32, 0, False), (8, 2, False), (8, 0, True), (8, 2, True))
+ONESWEEP_MAX_PASS = 125
+
+
+def selftest_onesweep(items, mode, skip_trivial, n, d_keys, stride, d_vals, passes, force_ticket, d_keys_out, d_vals_out, stream=0):
+    """ntr_selftest_onesweep: n keys through the passes [(shift, pass number), ...] of one production instantiation of the one-sweep
+    radix pass; the last pass's keys and values to d_keys_out / d_vals_out.  Returns the passes' error word (0: no look-back gave up)."""
+    flat = (_i32 * (2 * len(passes)))(*[int(x) for p in passes for x in p])
+    err = _u32(0xFFFFFFFF)
+    _check(lib().ntr_selftest_onesweep(int(items), int(mode), int(bool(skip_trivial)), int(n), _vp(d_keys), int(stride), _vp(d_vals), len(passes),
+                                       flat, int(bool(force_ticket)), _vp(d_keys_out), _vp(d_vals_out), C.byref(err), _vp(stream)))
+    return int(err.value)
+
+
+def selftest_scan(scan_type, threads, n, d_in, d_prefix, stream=0):
+    """ntr_selftest_scan: the three-launch exclusive scan of n items into d_prefix; returns the total as the item's bytes"""
+    total = (C.c_uint8 * 16)()
+    _check(lib().ntr_selftest_scan(int(scan_type), int(threads), int(n), _vp(d_in), _vp(d_prefix), C.cast(total, _vp), _vp(stream)))
+    return bytes(total)[:_SCAN_ITEM_BYTES[scan_type]]
+
+
+def selftest_scan_block_sums(scan_type, threads, nb, d_in, d_out, want_total=True, stream=0):
+    """ntr_selftest_scan_block_sums: scan_block_sums alone on nb sums (d_out == d_in: in place); the total's bytes, or None if not asked for"""
+    total = (C.c_uint8 * 16)()
+    _check(lib().ntr_selftest_scan_block_sums(int(scan_type), int(threads), int(nb), _vp(d_in), _vp(d_out),
+                                              C.cast(total, _vp) if want_total else None, _vp(stream)))
+    return bytes(total)[:_SCAN_ITEM_BYTES[scan_type]] if want_total else None
+
+
+def selftest_float_order(n, d_words, d_single, d_pairs, stream=0):
+    """ntr_selftest_float_order: the encodings of n float words to d_single [n][6], ord_min / ord_max of every ordered pair to d_pairs [n][n][2]"""
+    _check(lib().ntr_selftest_float_order(int(n), _vp(d_words), _vp(d_single), _vp(d_pairs), _vp(stream)))
+
+
+def selftest_box_words(m, d_boxes, d_group, groups, eps, d_lane32, d_lane64, d_groups_out, d_folds_out, stream=0):
+    """ntr_selftest_box_words: m boxes merged into their groups by atomic_max_box and through wave_grouped_atomic, decoded to
+    d_groups_out [2][groups][26]; the wave folds of the lane words to d_folds_out [m][6]"""
+    _check(lib().ntr_selftest_box_words(int(m), _vp(d_boxes), _vp(d_group), int(groups), float(eps), _vp(d_lane32), _vp(d_lane64),
+                                        _vp(d_groups_out), _vp(d_folds_out), _vp(stream)))
 
 
 def trace_bvh_stats(kernel, num_rays, any_hit, d_rays, d_results, d_nodes, nodes_bytes, d_woop, woop_bytes,

@@ -751,4 +751,54 @@ int ntr_selftest_division_hard(int32_t xExp, int32_t dExp, uint64_t* pairs, uint
     return NTR_OK;
 }
 
+// ---- self tests of the shared device toolkit (selftest_prims_kernels.hip): the argument checks ----
+int ntr_selftest_onesweep(int32_t items, int32_t mode, int32_t skipTrivial, int32_t n, const uint32_t* d_keys, int32_t stride, const int32_t* d_vals,
+                          int32_t numPasses, const int32_t* passes, int32_t forceTicket, uint32_t* d_keysOut, int32_t* d_valsOut, uint32_t* errWord,
+                          void* stream)
+{
+    if (!selftest_onesweep_offered(items, mode, skipTrivial))
+        return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: no user launches onesweep_pass_kernel<%d, %d, %d>", items, mode, skipTrivial);
+    if (n < 1 || n >= (1 << 28)) return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: n must be in [1, 2^28)");
+    if (!d_keys || !d_keysOut || !d_valsOut || !errWord || !passes || (mode == 2 && !d_vals))
+        return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: null argument");
+    if (mode == 0 ? stride != 1 : (stride != 1 && stride != 6)) return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: stride must be 1 (mode 2: 1 or 6)");
+    if (numPasses < 1 || numPasses > kSelftestMaxPasses) return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: 1 to %d passes", kSelftestMaxPasses);
+    for (int p = 0; p < numPasses; p++) {
+        if (passes[2 * p] < 0 || passes[2 * p] > 24) return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: shift %d outside [0, 24]", passes[2 * p]);
+        if (passes[2 * p + 1] < 0 || passes[2 * p + 1] > kSelftestMaxPassNumber)
+            return set_error(NTR_ERR_INVALID, "ntr_selftest_onesweep: pass number %d outside [0, %d]", passes[2 * p + 1], kSelftestMaxPassNumber);
+    }
+    *errWord = 0;
+    return selftest_onesweep_run(items, mode, skipTrivial, n, d_keys, stride, d_vals, numPasses, passes, forceTicket, d_keysOut, d_valsOut, errWord,
+                                 (hipStream_t)stream);
+}
+
+int ntr_selftest_scan(int32_t type, int32_t threads, int32_t n, const void* d_in, void* d_prefix, void* total, void* stream)
+{
+    if (type < NTR_SCAN_U32 || type > NTR_SCAN_U4 || (threads != 256 && threads != 1024) || n < 1 || n >= (1 << 28) || !d_in || !d_prefix || !total)
+        return set_error(NTR_ERR_INVALID, "ntr_selftest_scan: bad argument");
+    return selftest_scan_run(type, threads, n, d_in, d_prefix, total, (hipStream_t)stream);
+}
+
+int ntr_selftest_scan_block_sums(int32_t type, int32_t threads, int32_t nb, const void* d_in, void* d_out, void* total, void* stream)
+{
+    if (type < NTR_SCAN_U32 || type > NTR_SCAN_U4 || (threads != 256 && threads != 1024) || nb < 0 || nb >= (1 << 28) || (nb > 0 && (!d_in || !d_out)))
+        return set_error(NTR_ERR_INVALID, "ntr_selftest_scan_block_sums: bad argument");
+    return selftest_block_sums_run(type, threads, nb, d_in, d_out, total, (hipStream_t)stream);
+}
+
+int ntr_selftest_float_order(int32_t n, const uint32_t* d_words, uint32_t* d_single, uint32_t* d_pairs, void* stream)
+{
+    if (n < 1 || n > 2048 || !d_words || !d_single || !d_pairs) return set_error(NTR_ERR_INVALID, "ntr_selftest_float_order: bad argument (1 to 2048 words)");
+    return selftest_float_order_run(n, d_words, d_single, d_pairs, (hipStream_t)stream);
+}
+
+int ntr_selftest_box_words(int32_t m, const float* d_boxes, const int32_t* d_group, int32_t groups, float eps, const uint32_t* d_lane32,
+                           const uint64_t* d_lane64, uint32_t* d_groupsOut, uint32_t* d_foldsOut, void* stream)
+{
+    if (m < 64 || (m & 63) || m > (1 << 24) || groups < 1 || groups > (1 << 20) || !d_boxes || !d_group || !d_lane32 || !d_lane64 || !d_groupsOut || !d_foldsOut)
+        return set_error(NTR_ERR_INVALID, "ntr_selftest_box_words: bad argument (whole waves: m a multiple of 64)");
+    return selftest_box_words_run(m, d_boxes, d_group, groups, eps, d_lane32, d_lane64, d_groupsOut, d_foldsOut, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -27,6 +27,18 @@ bool stream_is_capturing(hipStream_t s);
 size_t lbvh_sort_scratch_bytes(int n);
 int lbvh_sort_codes(int n, const int32_t* d_tri, const float* d_pos, const float sceneMin[3], const float sceneMax[3], void* scratch,
                     hipStream_t s, const unsigned int** keys, const int** idx, const unsigned int** errWord);
+
+// selftest_prims_kernels.hip: the device self tests of radix_sort.h and device_prims.h; their arguments are checked in ntr_api.cpp
+constexpr int kSelftestMaxPasses = 16;   // passes of one ntr_selftest_onesweep call
+constexpr int kSelftestMaxPassNumber = 125;   // OS_MAX_PASSES - 1 (radix_sort.h; asserted where both are seen)
+bool selftest_onesweep_offered(int items, int mode, int skipTrivial);
+int selftest_onesweep_run(int items, int mode, int skipTrivial, int n, const uint32_t* d_keys, int stride, const int32_t* d_vals, int numPasses,
+                          const int32_t* passes, int forceTicket, uint32_t* d_keysOut, int32_t* d_valsOut, uint32_t* errWord, hipStream_t s);
+int selftest_scan_run(int type, int threads, int n, const void* d_in, void* d_prefix, void* total, hipStream_t s);
+int selftest_block_sums_run(int type, int threads, int nb, const void* d_in, void* d_out, void* total, hipStream_t s);
+int selftest_float_order_run(int n, const uint32_t* d_words, uint32_t* d_single, uint32_t* d_pairs, hipStream_t s);
+int selftest_box_words_run(int m, const float* d_boxes, const int32_t* d_group, int groups, float eps, const uint32_t* d_lane32,
+                           const uint64_t* d_lane64, uint32_t* d_groupsOut, uint32_t* d_foldsOut, hipStream_t s);
 }  // namespace ntr
 
 // sched_state.cpp: (re)build the top-of-tree box table cached for this node buffer (dispatch-order prediction)

@@ -2,6 +2,8 @@
 // rounded `/`, bit for bit.  ntr_selftest_division / ntr_selftest_division_hard in the C-ABI (tests/test_trace_gpu.py).
 // ... and of the FAST path's admission test: ray_class, the integer form the kernels run, against the rule as the float ranges state it
 // (trace_lane.h).  ntr_selftest_ray_class (tests/test_wave_setup_gpu.py).
+// The self tests of the shared device toolkit (radix_sort.h, device_prims.h) are in selftest_prims_kernels.hip: ntr_selftest_onesweep,
+// ntr_selftest_scan, ntr_selftest_scan_block_sums, ntr_selftest_float_order, ntr_selftest_box_words (tests/test_device_prims_gpu.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -143,6 +143,34 @@ def test_multi_gpu_partition_and_diagnostics_argument_checks():
     assert L.ntr_selftest_division_hard(0, 0, None, C.byref(bad), None) == -1
     assert L.ntr_selftest_division_hard(52, 0, C.byref(pairs), C.byref(bad), None) == -1    # operands would leave the FASTDIV range
     assert L.ntr_selftest_division_hard(0, -41, C.byref(pairs), C.byref(bad), None) == -1
+    # the device toolkit's self tests: every refusal comes before any device work (the pointers are never followed)
+    err = C.c_uint32(0)
+    p4 = (C.c_int32 * 8)(0, 0, 8, 1, 16, 2, 24, 3)
+    k = C.c_void_p(256)
+    sweep = lambda items=8, mode=0, skip=0, n=100, keys=k, stride=1, vals=None, np_=4, passes=p4, out_k=k, out_v=k, e=C.byref(err): \
+        L.ntr_selftest_onesweep(items, mode, skip, n, keys, stride, vals, np_, passes, 0, out_k, out_v, e, None)
+    for combo in ((8, 1, 0), (8, 1, 1), (8, 3, 0), (12, 0, 0), (16, 0, 1), (16, 2, 0), (32, 2, 1), (8, 0, 2), (0, 0, 0)):   # no user launches these
+        assert sweep(*combo) == -1 and "no user launches" in L.ntr_last_error().decode()
+    for n in (0, -1, 1 << 28, 0x7FFFFFFF):
+        assert sweep(n=n) == -1
+    assert nt.ONESWEEP_MAX_PASS == 125
+    for bad_pass in ((C.c_int32 * 2)(0, 126), (C.c_int32 * 2)(0, -1), (C.c_int32 * 2)(25, 0), (C.c_int32 * 2)(-8, 0)):
+        assert sweep(np_=1, passes=bad_pass) == -1
+    assert sweep(np_=0) == -1 and sweep(np_=17) == -1 and sweep(passes=None) == -1
+    assert sweep(stride=6) == -1 and sweep(mode=2, vals=k, stride=2) == -1 and sweep(mode=2, vals=None) == -1
+    assert sweep(keys=None) == -1 and sweep(out_k=None) == -1 and sweep(out_v=None) == -1 and sweep(e=None) == -1
+    tot = (C.c_uint8 * 16)()
+    for args in ((4, 256, 10, k, k, tot), (-1, 256, 10, k, k, tot), (0, 512, 10, k, k, tot), (0, 256, 0, k, k, tot), (0, 256, 1 << 28, k, k, tot),
+                 (0, 256, 10, None, k, tot), (0, 256, 10, k, None, tot), (0, 256, 10, k, k, None)):
+        assert L.ntr_selftest_scan(*args, None) == -1
+    for args in ((4, 256, 10, k, k, tot), (0, 64, 10, k, k, tot), (0, 1024, -1, k, k, tot), (3, 1024, 10, None, k, tot), (3, 1024, 10, k, None, None)):
+        assert L.ntr_selftest_scan_block_sums(*args, None) == -1
+    for args in ((0, k, k, k), (2049, k, k, k), (10, None, k, k), (10, k, None, k), (10, k, k, None)):
+        assert L.ntr_selftest_float_order(*args, None) == -1
+    box = lambda m=64, boxes=k, group=k, groups=1, l32=k, l64=k, og=k, of=k: \
+        L.ntr_selftest_box_words(m, boxes, group, groups, C.c_float(0.0), l32, l64, og, of, None)
+    assert box(m=0) == -1 and box(m=63) == -1 and box(m=65) == -1 and box(groups=0) == -1
+    assert box(boxes=None) == -1 and box(group=None) == -1 and box(l32=None) == -1 and box(l64=None) == -1 and box(og=None) == -1 and box(of=None) == -1
     # dispatch hints from a prediction: argument checks come before any device work
     assert L.ntr_sched_hint_predict(None, None, 16, None) == -1
     assert L.ntr_secondary_block_costs(None, 0, 0, 8, None, 0, None, None) == 0          # an empty batch: nothing to do
