@@ -1199,6 +1199,40 @@ NTR_API int ntr_bvh_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* en
 /* Bytes the batch refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
 NTR_API int ntr_bvh_refit_batch_scratch_bytes(int64_t* bytes);
 
+/* Many two-key refits in one pass: the update path of a pool whose BLASes deform inside the shutter (ntr_trace_instanced_deform above),
+ * the listed BLASes in the same three launches and a fourth for the boxes (csrc/bvh_motion_refit_batch_kernels.hip).
+ * ntr_bvh_motion_refit (below) at pool + offset gives the same bytes, three launches per BLAS.  EXTENSION without a reference
+ * counterpart: the rule is the numpy spec tests/np_motion_refit_batch.py -- np_bvh_motion.motion_refit over every entry's slices.
+ *   pool        the five buffers ntr_trace_instanced_deform reads: d_poolNodes0 and d_poolNodes1 (poolNodesBytes each), d_poolTriWoop,
+ *               d_poolVertRows0 and d_poolVertRows1 (poolTriWoopBytes each), and d_poolTriIndex, which is never written
+ *   bytes       every entry's slices of the five buffers hold what ntr_bvh_motion_refit writes when handed pool + offset,
+ *               d_triVtxIndex + 3 * firstTri, numTris and the entry's epsilon: nodes0 and the Woop rows refitted to d_vtxPos0 in place,
+ *               nodes1 a copy of nodes0 refitted to d_vtxPos1, the vertex rows zero but for the leaves' vertices under either key and
+ *               the terminator (0, 0, 0, 0x80000000) in the w word; a leaf whose walk met an error keeps zero rows.  Every byte outside
+ *               the listed ranges is untouched: the three key-1 buffers need no initialisation by the caller
+ *   d_blasBoxes optional, 6 floats per entry in entry order, min.xyz max.xyz: the union, in the total order, of the two keys' node-0
+ *               boxes -- ntr_bvh_motion_refit's d_sceneBox for that BLAS
+ *   counts      the sums of what ntr_bvh_motion_refit reports per entry (both keys walk the same leaves: counted once)
+ * Entries, lanesPerLeaf, the two forms (result == NULL is asynchronous and capturable: launches only, no memset or copy node, no
+ * read-back; result != NULL blocks, times and reports), the malformed tree (never followed; NTR_ERR_LAYOUT with *result filled and the
+ * lowest bad entry named, every other entry refitted completely; skipped silently by the asynchronous form), the held entry table and
+ * the rule for a captured call are ntr_bvh_refit_batch's in every respect.  The table (32 B per entry and two running sums, over node
+ * slots and over rows), the topology arrays (12 B per listed node slot), 48 B of boxes per entry and 16 KB of counters live in a
+ * per-device grow-only pool of its own (ntr_bvh_motion_refit_batch_scratch_bytes) that ntr_lbvh_release_workspace returns.
+ * NTR_ERR_INVALID (before any device work): ntr_bvh_refit_batch's cases in its order, then a null d_poolNodes1, d_poolVertRows0,
+ * d_poolVertRows1 or d_vtxPos1; one of d_poolNodes0, d_poolNodes1, d_poolTriWoop, d_poolVertRows0, d_poolVertRows1 not 16-byte aligned;
+ * one of d_poolNodes1, d_poolVertRows0, d_poolVertRows1, d_vtxPos1 overlapping another buffer of the call (the pools' whole extents). */
+NTR_API int ntr_bvh_motion_refit_batch(int32_t numEntries, const NtrRefitBatchEntry* entries,
+                                       void* d_poolNodes0, int64_t poolNodesBytes, void* d_poolNodes1,
+                                       void* d_poolTriWoop, int64_t poolTriWoopBytes, const int32_t* d_poolTriIndex,
+                                       void* d_poolVertRows0, void* d_poolVertRows1,
+                                       int32_t numTrisTotal, const int32_t* d_triVtxIndex, int32_t numVerts,
+                                       const float* d_vtxPos0, const float* d_vtxPos1,
+                                       float* d_blasBoxes /* may be NULL: 6 floats per entry */,
+                                       NtrBvhRefitBatchResult* result /* NULL: asynchronous, capturable */, void* stream);
+/* Bytes the batched motion refit's per-device scratch pool holds on the current device (0 after ntr_lbvh_release_workspace). */
+NTR_API int ntr_bvh_motion_refit_batch_scratch_bytes(int64_t* bytes);
+
 /* Instanced frames: what a two-level hit needs before anything indexes by triangle, in one launch with a thread per ray
  * (csrc/instanced_attr_kernels.hip).  ntr_trace_instanced leaves (id, t, u, v) and an instance id per ray; that id is the
  * BLAS's own triangle id, relative to its mesh's firstTri.  This call turns it into the pool triangle g -- so that ntr_reconstruct,

@@ -661,6 +661,9 @@ SYMBOLS = [
     ("ntr_trace_bvh_motion_stats", C.c_int, [_i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(BvhMotion), _vp, C.POINTER(TraceStats)]),
     ("ntr_bvh_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(BvhRefitBatchResult), _vp]),
     ("ntr_bvh_refit_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
+    ("ntr_bvh_motion_refit_batch", C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp,
+                                             C.POINTER(BvhRefitBatchResult), _vp]),
+    ("ntr_bvh_motion_refit_batch_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_optimize", C.c_int, [_vp, _i64, _i32, C.POINTER(BvhOptimizeResult), _vp]),
     ("ntr_bvh_optimize_scratch_bytes", C.c_int, [C.POINTER(_i64)]),
     ("ntr_bvh_sah_cost", C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(BvhSahResult), _vp]),
@@ -2050,6 +2053,34 @@ def bvh_refit_batch_scratch_bytes():
     """ntr_bvh_refit_batch_scratch_bytes: bytes the batch refit's scratch pool holds on the current device."""
     v = _i64(0)
     _check(lib().ntr_bvh_refit_batch_scratch_bytes(C.byref(v)))
+    return int(v.value)
+
+
+def bvh_motion_refit_batch(entries, d_pool_nodes0, pool_nodes_bytes, d_pool_nodes1, d_pool_woop, pool_woop_bytes, d_pool_idx, d_pool_vert_rows0,
+                           d_pool_vert_rows1, num_tris_total, d_tri, num_verts, d_pos0, d_pos1, d_blas_boxes=0, stream=0, blocking=True):
+    """ntr_bvh_motion_refit_batch: refit the listed BLASes of a pool (entries as for bvh_refit_batch) to the two vertex arrays d_pos0 and
+    d_pos1 in one pass; every BLAS's slices of the five pool buffers come out byte for byte as bvh_motion_refit at pool + offset leaves
+    them (the rule is tests/np_motion_refit_batch.py).  blocking=True returns a BvhRefitBatchResult; blocking=False passes result = NULL:
+    asynchronous on `stream` (capturable) and returns None.  An NtrError for a malformed tree (NTR_ERR_LAYOUT, after the work) carries
+    .result, filled: firstBadEntry, errBits and the counts."""
+    n = len(entries)
+    arr = _refit_entries(entries)
+    res = BvhRefitBatchResult() if blocking else None
+    try:
+        _check(lib().ntr_bvh_motion_refit_batch(n, C.cast(arr, _vp), _vp(d_pool_nodes0), int(pool_nodes_bytes), _vp(d_pool_nodes1),
+                                                _vp(d_pool_woop), int(pool_woop_bytes), _vp(d_pool_idx), _vp(d_pool_vert_rows0),
+                                                _vp(d_pool_vert_rows1), int(num_tris_total), _vp(d_tri), int(num_verts), _vp(d_pos0),
+                                                _vp(d_pos1), _vp(d_blas_boxes), C.byref(res) if blocking else None, _vp(stream)))
+    except NtrError as e:
+        e.result = res
+        raise
+    return res
+
+
+def bvh_motion_refit_batch_scratch_bytes():
+    """ntr_bvh_motion_refit_batch_scratch_bytes: bytes the batched motion refit's scratch pool holds on the current device."""
+    v = _i64(0)
+    _check(lib().ntr_bvh_motion_refit_batch_scratch_bytes(C.byref(v)))
     return int(v.value)
 
 

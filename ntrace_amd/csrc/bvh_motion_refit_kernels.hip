@@ -11,7 +11,8 @@
 //   motion_prepare     one thread per node slot and per row: copies the slot to nodes1, makes the topology step of bvh_climb.h (the
 //                      parent words serve both keys, each key has arrival counters of its own), zeroes its row of both vertex-row
 //                      buffers
-//   motion_climb<G, 0> key 0: refit_leaf_rows with the row rewrite over pos0, the leaf's vertex rows and terminator into vertRows0,
+//   motion_climb<G, 0> key 0: refit_leaf_rows with the row rewrite over pos0, the leaf's vertex rows and terminator into vertRows0
+//                      (bvh_motion_leaf.h, shared with bvh_motion_refit_batch_kernels.hip),
 //                      refit_leaf_climb in nodes0
 //   motion_climb<G, 1> key 1, a launch of its own AFTER key 0's: refit_leaf_rows without the rewrite (it reads the rows only to find the
 //                      terminators, which key 0's launch has finished writing around) over pos1, vertRows1, the climb in nodes1
@@ -28,6 +29,7 @@
 
 #include "ntr_internal.h"
 #include "bvh_climb.h"
+#include "bvh_motion_leaf.h"
 #include "bvh_refit_leaf.h"
 #include "device_prims.h"
 #include "device_scratch.h"
@@ -84,32 +86,6 @@ __global__ __launch_bounds__(MR_BLOCK) void motion_prepare(int numSlots, int num
         if (inner) atomicAdd(&stats->innerLinks, inner);
         if (leaf) atomicAdd(&stats->leafLinks, leaf);
         if (err) atomicOr(&stats->err, err);
-    }
-}
-
-// The vertex rows of a leaf that refit_leaf_rows<G> has walked without an error in any lane of the group (so every row, triangle and
-// vertex index met here is inside its extent): the same walk, lane `sub` at the row groups sub, sub + G, ...
-template <int G>
-__device__ __forceinline__ void motion_leaf_vertex_rows(int link, int sub, int groupShift, int numRows, const float4* woop, const int* triIndex,
-                                                        const int* tri, const float* pos, uint4* vertRows)
-{
-    for (long long r0 = (long long)leaf_row(link);; r0 += 3 * G) {   // the trip count is uniform within a group
-        const long long r = r0 + 3 * sub;
-        const bool inside = r < numRows;
-        const bool term = !inside || __float_as_uint(woop[r].x) == kLeafTerm;
-        const unsigned int terms = (unsigned int)((__ballot(term) >> groupShift) & ((1ull << G) - 1ull));
-        const int first = terms ? __ffs((int)terms) - 1 : G;
-        if (sub == first) {
-            if (inside) vertRows[r] = make_uint4(0u, 0u, 0u, kLeafTerm);   // in w: a vertex's x may be -0.0f, the terminator's word
-        } else if (sub < first && r + 2 < numRows) {
-            const int t = triIndex[r];
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const size_t v = (size_t)tri[3 * (size_t)t + j];
-                vertRows[r + j] = make_uint4(__float_as_uint(pos[3 * v]), __float_as_uint(pos[3 * v + 1]), __float_as_uint(pos[3 * v + 2]), 0u);
-            }
-        }
-        if (terms) break;
     }
 }
 

@@ -116,10 +116,9 @@ S32 CudaInstancedBVH::getFirstMeshlessBLAS(void) const
     return -1;
 }
 
-void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas, S32 num, F32 epsilon)
+// The selection (`num` as selectionSize gave it) as ntr_bvh_refit_batch's and ntr_bvh_motion_refit_batch's entries
+std::vector<NtrRefitBatchEntry> CudaInstancedBVH::refitEntries(const S32* blas, S32 num, F32 epsilon) const
 {
-    num = selectionSize(blas, num, getNumBLAS(), "refit (call buildBLASes first)");
-    const S64 numTris = meshTriangles(triVtxIndex, numVerts, vtxPos);
     std::vector<NtrRefitBatchEntry> entries((size_t)num);
     for (S32 i = 0; i < num; i++) {
         const S32 b = selectedBLAS(blas, i, getNumBLAS());
@@ -131,6 +130,14 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
         e.epsilon = epsilon;
         e.pad = 0;
     }
+    return entries;
+}
+
+void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos, const S32* blas, S32 num, F32 epsilon)
+{
+    num = selectionSize(blas, num, getNumBLAS(), "refit (call buildBLASes first)");
+    const S64 numTris = meshTriangles(triVtxIndex, numVerts, vtxPos);
+    const std::vector<NtrRefitBatchEntry> entries = refitEntries(blas, num, epsilon);
     m_state.wrote(W::PoolBoxes);                 // this method refits the binary pool only: widen() again, or call refitBLASesWide
     const int rc = ntr_bvh_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
                                        m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(), (const int32_t*)m_poolTriIndex.getCudaPtr(),
@@ -142,12 +149,9 @@ void CudaInstancedBVH::refitBLASes(Buffer& triVtxIndex, S32 numVerts, Buffer& vt
 void CudaInstancedBVH::refitBLASesMotion(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos0, Buffer& vtxPos1, const S32* blas, S32 num, F32 epsilon)
 {
     num = selectionSize(blas, num, getNumBLAS(), "refit (call buildBLASes first)");
-    meshTriangles(triVtxIndex, numVerts, vtxPos0);
+    const S64 numTris = meshTriangles(triVtxIndex, numVerts, vtxPos0);
     meshTriangles(triVtxIndex, numVerts, vtxPos1);
-    for (S32 i = 0; i < num; i++) {
-        const S32 b = selectedBLAS(blas, i, getNumBLAS());
-        if (m_meshes[b].numTris < 1) fail("CudaInstancedBVH: BLAS %d came through addBLAS and has no mesh here: refit its CudaBVH and add it again", b);
-    }
+    const std::vector<NtrRefitBatchEntry> entries = refitEntries(blas, num, epsilon);
     // BLASes that an earlier call made deforming stay so while their second key is still the pool's
     const bool keep = hasDeform() && m_deformFlags.size() == m_ranges.size();
     if (!keep) m_deformFlags.assign(m_ranges.size(), 0u);
@@ -163,21 +167,14 @@ void CudaInstancedBVH::refitBLASesMotion(Buffer& triVtxIndex, S32 numVerts, Buff
         m_poolVertRows1.resizeDiscard(m_poolTriWoop.getSize());
     }
     m_hasDeform = false;
-    U8 *nodes0 = (U8*)m_poolNodes.getMutableCudaPtr(), *nodes1 = (U8*)m_poolNodes1.getMutableCudaPtr(), *woop = (U8*)m_poolTriWoop.getMutableCudaPtr();
-    U8 *rows0 = (U8*)m_poolVertRows0.getMutableCudaPtr(), *rows1 = (U8*)m_poolVertRows1.getMutableCudaPtr();
-    const U8* index = (const U8*)m_poolTriIndex.getCudaPtr();
-    for (S32 i = 0; i < num; i++) {
-        const S32 b = selectedBLAS(blas, i, getNumBLAS());
-        const NtrBlasRange& r = m_ranges[b];
-        NtrBvhRefitResult res;
-        const int rc = ntr_bvh_motion_refit(nodes0 + r.nodesOffset, r.nodesBytes, nodes1 + r.nodesOffset, woop + r.triWoopOffset, r.triWoopBytes,
-                                            (const int32_t*)(index + r.triWoopOffset / 4), r.triWoopBytes / 4, rows0 + r.triWoopOffset,
-                                            rows1 + r.triWoopOffset, m_meshes[b].numTris,
-                                            (const int32_t*)triVtxIndex.getCudaPtr() + 3 * (size_t)m_meshes[b].firstTri, numVerts,
-                                            (const float*)vtxPos0.getCudaPtr(), (const float*)vtxPos1.getCudaPtr(), epsilon, NULL, &res, NULL);
-        if (rc != NTR_OK) fail("CudaInstancedBVH: BLAS %d: %s", b, ntr_last_error());
-        m_deformFlags[(size_t)b] = 1u;
-    }
+    const int rc = ntr_bvh_motion_refit_batch(num, entries.data(), m_poolNodes.getMutableCudaPtr(), m_poolNodes.getSize(),
+                                              m_poolNodes1.getMutableCudaPtr(), m_poolTriWoop.getMutableCudaPtr(), m_poolTriWoop.getSize(),
+                                              (const int32_t*)m_poolTriIndex.getCudaPtr(), m_poolVertRows0.getMutableCudaPtr(),
+                                              m_poolVertRows1.getMutableCudaPtr(), (int32_t)numTris, (const int32_t*)triVtxIndex.getCudaPtr(),
+                                              numVerts, (const float*)vtxPos0.getCudaPtr(), (const float*)vtxPos1.getCudaPtr(), NULL,
+                                              &m_blasMotionRefitResult, NULL);
+    if (rc != NTR_OK) fail("CudaInstancedBVH: %s", ntr_last_error());
+    for (S32 i = 0; i < num; i++) m_deformFlags[(size_t)selectedBLAS(blas, i, getNumBLAS())] = 1u;
     m_blasDeforming.resizeDiscard((S64)m_deformFlags.size() * sizeof(U32));
     m_blasDeforming.set(m_deformFlags.data(), (S64)m_deformFlags.size() * sizeof(U32));
     m_hasDeform = true;

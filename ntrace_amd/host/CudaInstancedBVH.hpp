@@ -69,7 +69,7 @@
 //   refitMotionWide  refitMotion(), then ntr_tlas_wide_motion_refit in place over the wide TLAS and records; needs what refitWide() and
 //                 refitMotion() need.  writes: TlasBoxes, WideTlas; makes: MotionRefit, WideTlas, WideMotionRefit
 //   refitBLASesMotion   deformation inside the shutter: refits the selected BLASes to TWO vertex arrays, the shutter's opening
-//                 and its close (ntr_bvh_motion_refit at pool + offset, one call per BLAS; a batch form is a later step), into the pool and
+//                 and its close (one ntr_bvh_motion_refit_batch over the selection; getBLASMotionRefitResult), into the pool and
 //                 into key-1 buffers that this object owns -- the second key's nodes, the two keys' vertex rows and a flag per BLAS -- and
 //                 marks them deforming.  While hasDeform(), refitMotion() takes ntr_tlas_deform_refit (without a motion key it passes key 0
 //                 twice) and traceBatch ntr_trace_instanced_deform, after refitMotion() if isMotionStale().  A later refitBLASes,
@@ -188,6 +188,7 @@ public:
     const NtrTlasResult& getBuildResult(void) const { return m_result; }
     const NtrPlocBatchResult& getBLASBuildResult(void) const { return m_blasResult; }   // of the last buildBLASes (zero before)
     const NtrBvhRefitBatchResult& getBLASRefitResult(void) const { return m_refitResult; }   // of the last refitBLASes (zero before)
+    const NtrBvhRefitBatchResult& getBLASMotionRefitResult(void) const { return m_blasMotionRefitResult; }   // of the last refitBLASesMotion (zero before)
     const NtrBvhOptimizeBatchResult& getBLASOptimizeResult(void) const { return m_optimizeResult; }   // of the last optimizeBLASes (zero before)
     const NtrTlasRefitResult& getRefitResult(void) const { return m_tlasRefitResult; }       // of the last refit (zero before)
     Buffer& getPoolNodeBuffer(void) { return m_poolNodes; }
@@ -212,9 +213,11 @@ private:
     NtrTlasResult m_result = {};
     NtrPlocBatchResult m_blasResult = {};
     NtrBvhRefitBatchResult m_refitResult = {};
+    NtrBvhRefitBatchResult m_blasMotionRefitResult = {};
     NtrBvhOptimizeBatchResult m_optimizeResult = {};
     NtrTlasRefitResult m_tlasRefitResult = {};
     void          selectRanges(const S32* blas, S32 num, std::vector<NtrBlasRange>& out, const char* what) const;
+    std::vector<NtrRefitBatchEntry> refitEntries(const S32* blas, S32 num, F32 epsilon) const;
     Buffer        m_instanceStatus;                                              // setInstancesDevice's four status words, on the device
     NtrInstancesUpdateResult m_instancesUpdateResult = {};
     // the wide path (widen): a second node buffer beside the pool, a wide TLAS and wide records

@@ -9,9 +9,10 @@ through ONE identity instance of atrium() and through the forest of 4 096 instan
   * hashed    every BLAS deforms, random times in [0, 1): against the motion launch over the same buffers (the meshes frozen at key 0
               inside the swept boxes), with the counters and the algorithmic bytes
   * refit     ntr_tlas_deform_refit against ntr_tlas_motion_refit, both asynchronous (two launches each), by stream events
-  * blas      the per-BLAS loop of ntr_bvh_motion_refit against ntr_bvh_refit_batch over a pool of --blases copies of soup1000 (a
-              Compact tree's links are relative to its own start, so a copy at another offset is a BLAS), both asynchronous: whether a
-              batch form of the motion refit is worth building
+  * blas      ntr_bvh_motion_refit_batch against the per-BLAS loop of ntr_bvh_motion_refit that it replaces and against
+              ntr_bvh_refit_batch, over a pool of 1 and of --blases copies of soup1000 (a Compact tree's links are relative to its own
+              start, so a copy at another offset is a BLAS), all asynchronous and alternated in one run; and over --many-blases copies
+              the two batch calls alone.  --parts blas runs this part only
 Both launches get the same visibility, a ray mask of 0x7FFFFFFF that refuses nothing.  Launches are alternated, five runs after two
 warm-ups; every figure is the median with its minimum and maximum.  One JSON line per row; --out writes them as a list.  Every GPU step
 runs under a time limit of its own.
@@ -58,6 +59,8 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--ao-rays", type=int, default=1 << 20)
     ap.add_argument("--blases", type=int, default=256)
+    ap.add_argument("--many-blases", type=int, default=1024, help="copies for the two batch calls alone")
+    ap.add_argument("--parts", default="frames,blas", help="comma-separated: frames (none, time0, hashed, refit), blas")
     ap.add_argument("--limit", type=int, default=120, help="seconds a GPU step may take")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -163,8 +166,9 @@ def main():
         emit(row)
         assert nt.trace_status() == 0, "traversal stack overflow"
 
-    def blas_loop(b, copies):
-        """The per-BLAS loop of ntr_bvh_motion_refit against ntr_bvh_refit_batch over `copies` copies of BLAS b in one pool"""
+    def blas_loop(b, copies, with_loop=True):
+        """ntr_bvh_motion_refit_batch against the per-BLAS loop of ntr_bvh_motion_refit and against ntr_bvh_refit_batch over `copies`
+        copies of BLAS b in one pool"""
         d_nodes, d_woop = b.bufs[0][:b.nb].repeat(copies), b.bufs[1][:b.wb].repeat(copies)
         d_idx = b.bufs[2][:b.wb // 4].repeat(copies)
         d_nodes1, d_v0, d_v1 = torch.zeros_like(d_nodes), torch.zeros_like(d_woop), torch.zeros_like(d_woop)
@@ -175,6 +179,11 @@ def main():
             return nt.bvh_refit_batch(entries, d_nodes.data_ptr(), d_nodes.numel(), d_woop.data_ptr(), d_woop.numel(), d_idx.data_ptr(), b.tri.shape[0],
                                       b.d_tri.data_ptr(), b.pos.shape[0], b.d_pos.data_ptr(), 0, stream, blocking)
 
+        def motion_batch(blocking):
+            return nt.bvh_motion_refit_batch(entries, d_nodes.data_ptr(), d_nodes.numel(), d_nodes1.data_ptr(), d_woop.data_ptr(), d_woop.numel(),
+                                             d_idx.data_ptr(), d_v0.data_ptr(), d_v1.data_ptr(), b.tri.shape[0], b.d_tri.data_ptr(), b.pos.shape[0],
+                                             b.d_pos.data_ptr(), d_pos1.data_ptr(), 0, stream, blocking)
+
         def loop(blocking=False):
             for k in range(copies):
                 nt.bvh_motion_refit(d_nodes.data_ptr() + k * b.nb, b.nb, d_nodes1.data_ptr() + k * b.nb, d_woop.data_ptr() + k * b.wb, b.wb,
@@ -183,34 +192,58 @@ def main():
                                     blocking=blocking)
 
         def run():
-            batch(True)                                       # once blocking: the scratch and the held table
+            batch(True)                                       # once blocking: the scratch and the held tables
+            res = motion_batch(True)
             nt.bvh_motion_refit(d_nodes.data_ptr(), b.nb, d_nodes1.data_ptr(), d_woop.data_ptr(), b.wb, d_idx.data_ptr(), b.wb // 4, d_v0.data_ptr(),
                                 d_v1.data_ptr(), b.tri.shape[0], b.d_tri.data_ptr(), b.pos.shape[0], b.d_pos.data_ptr(), d_pos1.data_ptr(), 0.0,
                                 stream=stream)
-            p, m = [], []
-            for _ in range(args.warmup + args.reps):          # alternated: batch, loop, batch, loop, ...
+            if with_loop:                                     # the batch call's bytes are the loop's, before anything is timed
+                mine = [x.clone() for x in (d_nodes, d_nodes1, d_woop, d_v0, d_v1)]
+                loop()
+                torch.cuda.synchronize()
+                for name, x, y in zip(("nodes0", "nodes1", "triWoop", "vertRows0", "vertRows1"), mine, (d_nodes, d_nodes1, d_woop, d_v0, d_v1)):
+                    fx, fy = x.view(torch.float32), y.view(torch.float32)    # Woop words that are NaN on both sides compare equal
+                    same = torch.equal(x, y) or (name == "triWoop" and bool(((x.view(torch.int32) == y.view(torch.int32)) |
+                                                                           (fx.isnan() & fy.isnan())).all()))
+                    assert same, "ntr_bvh_motion_refit_batch differs from the loop in " + name
+            p, q, m = [], [], []
+            for _ in range(args.warmup + args.reps):          # alternated: batch, motion batch, loop, batch, ...
                 p.append(timed(lambda: batch(False)))
-                m.append(timed(loop))
-            return p[args.warmup:], m[args.warmup:]
-        p, m = step("blas refits, %d copies" % copies, args.limit, run)
-        row = {"part": "blas", "blases": copies, "triangles_per_blas": int(b.tri.shape[0]), "refit_batch_ms": spread(p), "motion_refit_loop_ms": spread(m)}
-        row["loop_over_batch"] = row["motion_refit_loop_ms"]["median"] / row["refit_batch_ms"]["median"]
+                q.append(timed(lambda: motion_batch(False)))
+                if with_loop:
+                    m.append(timed(loop))
+            return p[args.warmup:], q[args.warmup:], m[args.warmup:], res
+        p, q, m, res = step("blas refits, %d copies" % copies, args.limit, run)
+        row = {"part": "blas", "blases": copies, "triangles_per_blas": int(b.tri.shape[0]), "lanes_per_leaf": int(res.lanesPerLeaf),
+               "refit_batch_ms": spread(p), "motion_refit_batch_ms": spread(q),
+               "scratch_bytes": nt.bvh_motion_refit_batch_scratch_bytes()}
+        row["motion_batch_over_batch"] = row["motion_refit_batch_ms"]["median"] / row["refit_batch_ms"]["median"]
+        if with_loop:
+            row["motion_refit_loop_ms"] = spread(m)
+            row["loop_over_motion_batch"] = row["motion_refit_loop_ms"]["median"] / row["motion_refit_batch_ms"]["median"]
+            row["loop_over_batch"] = row["motion_refit_loop_ms"]["median"] / row["refit_batch_ms"]["median"]
         emit(row)
 
-    tri, pos, cam = scenes.atrium()
-    atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
-    tf = np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F)
-    frame("identity", step("identity tlas", args.limit, lambda: Tlas(atrium, tf, stream)), tf, cam)
+    parts = set(args.parts.split(","))
+    assert parts and parts <= {"frames", "blas"}, "--parts takes frames and blas"
+    if "frames" in parts:
+        tri, pos, cam = scenes.atrium()
+        atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
+        tf = np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F)
+        frame("identity", step("identity tlas", args.limit, lambda: Tlas(atrium, tf, stream)), tf, cam)
 
     tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
     soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
-    rng = np.random.default_rng(4096)
-    g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
-    tf = transforms(rotations(4096, rng), (g - 7.5) * 30.0)
-    cam = dict(eye=(40.0, 60.0, -420.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
-    frame("forest", step("forest tlas", args.limit, lambda: Tlas(soup, tf, stream)), tf, cam)
-    for copies in (1, args.blases):
-        blas_loop(soup, copies)
+    if "frames" in parts:
+        rng = np.random.default_rng(4096)
+        g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+        tf = transforms(rotations(4096, rng), (g - 7.5) * 30.0)
+        cam = dict(eye=(40.0, 60.0, -420.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
+        frame("forest", step("forest tlas", args.limit, lambda: Tlas(soup, tf, stream)), tf, cam)
+    if "blas" in parts:
+        for copies in (1, args.blases):
+            blas_loop(soup, copies)
+        blas_loop(soup, args.many_blases, with_loop=False)
 
     if args.out:
         with open(args.out, "w") as f:
