@@ -1063,8 +1063,8 @@ NTR_API int ntr_trace_instanced_motion_stats(int32_t numRays, int32_t anyHit, co
  *   everything ntr_trace_instanced_motion refuses, in its words and order, then: a null motion with a non-null deform; a null
  *   d_poolNodes1, d_poolVertRows0 or d_poolVertRows1; one of them not 16-byte aligned; one of them overlapping another buffer of the
  *   call; a null stats, motionStats or deformStats.  The _stats form blocks and is refused on a capturing stream.
- * Not combinable with the 4-wide trees, FAST, or the seeded / world form; ntr_instanced_hit_attributes_motion gives a deforming BLAS's
- * normal at key 0; two keys only. */
+ * Not combinable with the 4-wide trees, FAST, or the seeded / world form; the normal of a deforming BLAS's hit at the ray's time is
+ * ntr_instanced_hit_attributes_deform's (below); two keys only. */
 typedef struct NtrTlasDeformRefitResult {
     NtrTlasMotionRefitResult motion;    /* as ntr_tlas_motion_refit reports it */
     int32_t numDeforming, pad;          /* instances whose BLAS deforms */
@@ -1287,8 +1287,8 @@ NTR_API int ntr_instanced_hit_attributes(int32_t numRays, const NtrRayResult* d_
  *   static      W = geom->d_instances[i].worldToObject, as ntr_instanced_hit_attributes
  *   moving      W = ntr_instance_invert's function (binary64) of M(t_r), the trace's lerp of the two keys: the matrix the trace
  *               transformed that ray with.  No inverse: the id is still resolved, the normal is (0, 0, 0, 0)
- *   unchanged   the blas index comes from geom->d_instances (key 0); d_vtxPos is the current mesh (BLASes deforming within the shutter
- *               are out of scope)
+ *   unchanged   the blas index comes from geom->d_instances (key 0); d_vtxPos is the current mesh (BLASes deforming within the shutter:
+ *               ntr_instanced_hit_attributes_deform, below)
  * With motion == NULL the call IS ntr_instanced_hit_attributes, and its refusals name that function.
  * NTR_ERR_INVALID (before any device work): everything ntr_instanced_hit_attributes refuses, in its words and order, then: a d_rayTimes
  * that is not 4-byte aligned, a d_motionKeys that is null or not 16-byte aligned, motionKeysBytes < 128 * geom->numInstances.
@@ -1296,6 +1296,37 @@ NTR_API int ntr_instanced_hit_attributes(int32_t numRays, const NtrRayResult* d_
 NTR_API int ntr_instanced_hit_attributes_motion(int32_t numRays, const NtrRayResult* d_results, const int32_t* d_instanceIDs,
                                                 const NtrInstancedGeometry* geom,
                                                 const NtrInstanceMotion* motion /* NULL: ntr_instanced_hit_attributes */,
+                                                NtrRayResult* d_outResults /* may be NULL; may equal d_results */,
+                                                float* d_normals /* may be NULL; 4 floats per ray */, void* stream);
+
+/* ntr_instanced_hit_attributes_motion with the TRIANGLE at the ray's time too (csrc/instanced_deform_attr_kernels.hip):
+ * the attributes of the hits ntr_trace_instanced_deform wrote.  EXTENSION without a reference counterpart: the rule is the numpy spec
+ * tests/np_instanced_deform_frame.py (hit_attributes_deform), which the device equals in every word.  `motion` is what the trace took;
+ * `deform` names the second vertex key and the per-BLAS flags ntr_tlas_deform_refit read.  The call is
+ * ntr_instanced_hit_attributes_motion in every respect -- the resolution rule, the id rewrite, the moving test, W at the ray's time,
+ * the transpose, the normalisation, the (0, 0, 0, 0) cases, the in-place and one-NULL-output forms, the range checks before every read
+ * -- except where the three vertices come from for a resolved ray r of instance i with b = geom->d_instances[i].blas:
+ *   time        t_r = d_rayTimes[r] or `time`, clamped by t > 0 ? (t < 1 ? t : 1) : 0: the time the trace posed that ray's triangle with
+ *   static      d_blasDeforming[b] == 0: the vertices are geom->d_vtxPos's; nothing of d_vtxPos1 is read
+ *   deforming   d_blasDeforming[b] != 0: each of the nine words is ntr_trace_bvh_motion's pose of the two keys' words -- a at t_r == 0,
+ *               b at t_r == 1, (1 - t_r) * a + t_r * b with both products rounded in between (no "same word" shortcut).  The vertex
+ *               rows ntr_bvh_motion_refit writes are the vertices' words verbatim, so this is, bit for bit, the triangle the ray was
+ *               tested against
+ *   unchanged   the cross product, in its rounding order, over the posed words; a posed triangle whose cross product has length 0 or
+ *               a non-finite length resolves the id and gives (0, 0, 0, 0)
+ * geom->d_vtxPos is the shutter's opening and d_vtxPos1 its close: the two arrays ntr_bvh_motion_refit(_batch) was given, numVerts
+ * vertices each.  The flags are read on the device, so a replay of a captured call sees the current ones.
+ * With deform == NULL the call IS ntr_instanced_hit_attributes_motion, and its refusals name that function.
+ * NTR_ERR_INVALID (before any device work): everything ntr_instanced_hit_attributes_motion refuses, in its words and order, then: a null
+ * motion with a non-null deform (ntr_trace_instanced_deform's rule), a null d_vtxPos1 or d_blasDeforming, either of them not 4-byte
+ * aligned.  numRays == 0 returns NTR_OK.  Without a device, after these checks: NTR_ERR_NO_DEVICE / NTR_ERR_HIP. */
+typedef struct NtrInstancedDeformGeometry {   /* host struct of device pointers */
+    const float*    d_vtxPos1;        /* 3 per vertex, geom->numVerts of them: the shutter's close; geom->d_vtxPos is its opening */
+    const uint32_t* d_blasDeforming;  /* geom->numBlas words on the device, as ntr_tlas_deform_refit reads them */
+} NtrInstancedDeformGeometry;
+NTR_API int ntr_instanced_hit_attributes_deform(int32_t numRays, const NtrRayResult* d_results, const int32_t* d_instanceIDs,
+                                                const NtrInstancedGeometry* geom, const NtrInstanceMotion* motion,
+                                                const NtrInstancedDeformGeometry* deform /* NULL: ntr_instanced_hit_attributes_motion */,
                                                 NtrRayResult* d_outResults /* may be NULL; may equal d_results */,
                                                 float* d_normals /* may be NULL; 4 floats per ray */, void* stream);
 

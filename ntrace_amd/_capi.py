@@ -290,6 +290,15 @@ class InstanceDeform(C.Structure):
         super().__init__(int(d_pool_nodes1) or None, int(d_pool_vert_rows0) or None, int(d_pool_vert_rows1) or None)
 
 
+class InstancedDeformGeometry(C.Structure):
+    """NtrInstancedDeformGeometry: the vertices at the shutter's close (3 floats per vertex, as many as InstancedGeometry's d_pos, which
+    holds the opening) and the per-BLAS deforming flags on the device, as tlas_deform_refit reads them."""
+    _fields_ = [("d_vtxPos1", C.c_void_p), ("d_blasDeforming", C.c_void_p)]
+
+    def __init__(self, d_pos1=0, d_blas_deforming=0):
+        super().__init__(int(d_pos1) or None, int(d_blas_deforming) or None)
+
+
 class InstancedDeformStats(C.Structure):
     """NtrInstancedDeformStats (the rule is tests/np_instanced_deform.py): entries into, inner visits in and triangle tests in instances
     of deforming BLASes; each is counted in InstancedTraceStats too."""
@@ -603,6 +612,8 @@ SYMBOLS = [
                                             C.POINTER(InstanceVisibility), C.POINTER(InstancedTraceStats), _vp]),
     ("ntr_instanced_hit_attributes", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), _vp, _vp, _vp]),
     ("ntr_instanced_hit_attributes_motion", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), C.POINTER(InstanceMotion), _vp, _vp, _vp]),
+    ("ntr_instanced_hit_attributes_deform", C.c_int, [_i32, _vp, _vp, C.POINTER(InstancedGeometry), C.POINTER(InstanceMotion),
+                                                      C.POINTER(InstancedDeformGeometry), _vp, _vp, _vp]),
     ("ntr_ray_times_primary", C.c_int, [_i32, _vp, _u32, C.c_float, C.c_float, _vp, _vp]),
     ("ntr_ray_times_secondary", C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     ("ntr_bvh_widen_capacity", C.c_int, [_i64, C.POINTER(_i64)]),
@@ -1586,6 +1597,16 @@ def instanced_hit_attributes_motion(num_rays, d_results, d_instance_ids, geom, m
     instanced_hit_attributes).  Asynchronous on `stream` and capturable."""
     _check(lib().ntr_instanced_hit_attributes_motion(int(num_rays), _vp(d_results), _vp(d_instance_ids), C.byref(geom) if geom is not None else None,
                                                      C.byref(motion) if motion is not None else None, _vp(d_out_results), _vp(d_normals),
+                                                     _vp(stream)))
+
+
+def instanced_hit_attributes_deform(num_rays, d_results, d_instance_ids, geom, motion, deform, d_out_results=0, d_normals=0, stream=0):
+    """ntr_instanced_hit_attributes_deform: instanced_hit_attributes_motion with the triangle of a deforming BLAS's hit posed at the ray's
+    time too (the rule is tests/np_instanced_deform_frame.py).  motion: the InstanceMotion trace_instanced_deform took; deform: an
+    InstancedDeformGeometry, or None (NULL: instanced_hit_attributes_motion).  Asynchronous on `stream` and capturable."""
+    _check(lib().ntr_instanced_hit_attributes_deform(int(num_rays), _vp(d_results), _vp(d_instance_ids), C.byref(geom) if geom is not None else None,
+                                                     C.byref(motion) if motion is not None else None,
+                                                     C.byref(deform) if deform is not None else None, _vp(d_out_results), _vp(d_normals),
                                                      _vp(stream)))
 
 

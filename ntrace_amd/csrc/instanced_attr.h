@@ -1,8 +1,9 @@
 // instanced_attr.h -- the steps of a two-level hit's attributes, stated once for the units that resolve hits
 // (instanced_attr_kernels.hip: ntr_instanced_hit_attributes; instanced_motion_attr_kernels.hip: ntr_instanced_hit_attributes_motion;
-// DESIGN.md 6p, 6ab; the rule is tests/np_instanced_frame.py).  The units differ in where worldToObject comes from and in nothing else:
-// the resolution with its range checks, the object-space normal, the transpose and the normalisation are here, and so are the
-// refusals the two entry points share, worded once with the caller's name.
+// instanced_deform_attr_kernels.hip: ntr_instanced_hit_attributes_deform; the rule is
+// tests/np_instanced_frame.py).  The units differ in where worldToObject and the nine vertex words come from and in nothing else: the
+// resolution with its range checks, the object-space normal, the transpose and the normalisation are here, and so are the refusals the
+// entry points share, worded once with the caller's name.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -36,16 +37,32 @@ __device__ __forceinline__ int attr_resolve(int id, int i, const NtrInstance* __
     return -1;
 }
 
-// the object-space normal (Scene.cpp:112's cross product)
-__device__ __forceinline__ void attr_object_normal(const float* __restrict__ pos, int va, int vb, int vc, float& ox, float& oy, float& oz)
+// a triangle's nine vertex words, a.xyz b.xyz c.xyz: 12-byte rows, so nine scalar loads
+__device__ __forceinline__ void attr_load_triangle(const float* __restrict__ pos, int va, int vb, int vc, float (&p)[9])
 {
     const float* pa = pos + 3 * (size_t)va;
     const float* pb = pos + 3 * (size_t)vb;
     const float* pc = pos + 3 * (size_t)vc;
-    const float ax = pa[0], ay = pa[1], az = pa[2];
-    const float e1x = pb[0] - ax, e1y = pb[1] - ay, e1z = pb[2] - az;
-    const float e2x = pc[0] - ax, e2y = pc[1] - ay, e2z = pc[2] - az;
+    p[0] = pa[0], p[1] = pa[1], p[2] = pa[2];
+    p[3] = pb[0], p[4] = pb[1], p[5] = pb[2];
+    p[6] = pc[0], p[7] = pc[1], p[8] = pc[2];
+}
+
+// the object-space normal of nine vertex words (Scene.cpp:112's cross product)
+__device__ __forceinline__ void attr_cross(const float (&p)[9], float& ox, float& oy, float& oz)
+{
+    const float ax = p[0], ay = p[1], az = p[2];
+    const float e1x = p[3] - ax, e1y = p[4] - ay, e1z = p[5] - az;
+    const float e2x = p[6] - ax, e2y = p[7] - ay, e2z = p[8] - az;
     ox = e1y * e2z - e1z * e2y, oy = e1z * e2x - e1x * e2z, oz = e1x * e2y - e1y * e2x;
+}
+
+// the object-space normal of a triangle of `pos`
+__device__ __forceinline__ void attr_object_normal(const float* __restrict__ pos, int va, int vb, int vc, float& ox, float& oy, float& oz)
+{
+    float p[9];
+    attr_load_triangle(pos, va, vb, vc, p);
+    attr_cross(p, ox, oy, oz);
 }
 
 // through the transpose of worldToObject's linear part (rows w0, w1, w2): the inverse transpose of objectToWorld; (0, 0, 0, 0) where the

@@ -75,7 +75,9 @@
 //                 twice) and traceBatch ntr_trace_instanced_deform, after refitMotion() if isMotionStale().  A later refitBLASes,
 //                 optimizeBLASes, buildBLASes or addBLAS leaves the second key stale: hasDeform() drops and the scene is key 0's again.
 //                 clearDeform() drops it by hand.  With hasDeform(), setTraceWide, setTraceFast, setTraceWideFast, setTraceWideMotion and a
-//                 world are not combinable: traceBatch fail()s naming the switch.  writes: PoolBoxes, PoolKey1; makes: PoolDeform
+//                 world are not combinable: traceBatch fail()s naming the switch.  InstancedRenderer::setMotionBlur with setDeformGeometry
+//                  resolves every batch at the ray's time, the triangle posed too, reading getBLASDeformingBuffer.
+//                 writes: PoolBoxes, PoolKey1; makes: PoolDeform
 // Rendering: InstancedRenderer (InstancedRenderer.hpp) sits over this class and carries Renderer's batching.  Per frame, a moving, deforming
 // scene is refitBLASes -> optimizeBLASes every so many frames -> setInstances (or setInstancesDevice: no step then computes on the host) ->
 // refit -> InstancedRenderer::beginFrame -> nextBatch / traceBatch / updateResult per batch, with build() every so many frames; on the wide

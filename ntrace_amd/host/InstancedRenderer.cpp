@@ -1,12 +1,13 @@
 // InstancedRenderer.cpp -- Renderer's batching over a CudaInstancedBVH: every traced batch goes through ntr_instanced_hit_attributes
 // before ntr_raygen_ao_normals, ntr_count_hits or ntr_reconstruct sees it (see the header).  Under setMotionBlur every batch has a
-// time per ray: the trace and ntr_instanced_hit_attributes_motion read the same buffer.
+// time per ray: the trace and ntr_instanced_hit_attributes_motion read the same buffer; over deforming BLASes (setDeformGeometry) the
+// attributes are ntr_instanced_hit_attributes_deform's, which poses the hit triangle at that time too.
 #include "InstancedRenderer.hpp"
 
 namespace FW {
 
 InstancedRenderer::InstancedRenderer(CudaInstancedBVH& bvh)
-    : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
+    : m_bvh(bvh), m_triVtxIndex(NULL), m_vtxPos(NULL), m_vtxPos1(NULL), m_numVerts(0), m_rayType(RayType_Primary), m_aoRadius(1.0f), m_numSamples(32),
       m_primaryMask(0xFFFFFFFFu), m_secondaryMask(0xFFFFFFFFu), m_wide(false), m_fast(false), m_wideFast(false), m_wideMotion(false),
       m_motionBlur(false), m_motionSeed(0), m_shutterOpen(0.0f), m_shutterClose(1.0f),
       m_raygen(1 << 20), m_cameraFar(0.0f), m_newBatch(true), m_batchRays(NULL), m_batchResolved(NULL), m_batchStart(0)
@@ -20,6 +21,14 @@ void InstancedRenderer::setGeometry(Buffer& triVtxIndex, S32 numVerts, Buffer& v
     m_triVtxIndex = &triVtxIndex;
     m_vtxPos = &vtxPos;
     m_numVerts = numVerts;
+}
+
+void InstancedRenderer::setDeformGeometry(Buffer& vtxPos1)
+{
+    if (m_numVerts < 1) fail("InstancedRenderer::setDeformGeometry: no geometry: call setGeometry() first");
+    if (vtxPos1.getSize() < (S64)m_numVerts * (S64)(3 * sizeof(F32)))
+        fail("InstancedRenderer::setDeformGeometry: the buffer holds fewer than %d vertices (setGeometry's numVerts)", m_numVerts);
+    m_vtxPos1 = &vtxPos1;
 }
 
 void InstancedRenderer::setParams(RayType rayType, F32 aoRadius, S32 numSamples)
@@ -90,9 +99,17 @@ void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& ti
         motion.d_rayTimes = (const float*)times.getCudaPtr();
         motion.time = 0.0f;
         motion.pad = 0.0f;
-        rc = ntr_instanced_hit_attributes_motion(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(),
-                                                 &g, &motion, (NtrRayResult*)resolved.getMutableCudaPtr(),
-                                                 normals ? (float*)normals->getMutableCudaPtr() : NULL, NULL);
+        NtrInstancedDeformGeometry deform;   // over deforming BLASes the triangle is posed too: the one the trace tested
+        const bool deforming = m_bvh.hasDeform();
+        if (deforming) {
+            if (!m_vtxPos1 || m_vtxPos1->getSize() < (S64)m_numVerts * (S64)(3 * sizeof(F32))) fail("InstancedRenderer: no closing vertices");
+            deform.d_vtxPos1 = (const float*)m_vtxPos1->getCudaPtr();
+            deform.d_blasDeforming = (const uint32_t*)m_bvh.getBLASDeformingBuffer().getCudaPtr();
+        }
+        rc = ntr_instanced_hit_attributes_deform(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(),
+                                                 &g, &motion, deforming ? &deform : NULL /* ntr_instanced_hit_attributes_motion */,
+                                                 (NtrRayResult*)resolved.getMutableCudaPtr(), normals ? (float*)normals->getMutableCudaPtr() : NULL,
+                                                 NULL);
     } else
         rc = ntr_instanced_hit_attributes(n, (const NtrRayResult*)rays.getResultBuffer().getCudaPtr(), (const int32_t*)instanceIDs.getCudaPtr(), &g,
                                           (NtrRayResult*)resolved.getMutableCudaPtr(), normals ? (float*)normals->getMutableCudaPtr() : NULL, NULL);
@@ -101,10 +118,11 @@ void InstancedRenderer::resolve(RayBuffer& rays, Buffer& instanceIDs, Buffer& ti
 
 void InstancedRenderer::beginFrame(const CameraView& camera, S32 w, S32 h)
 {
-    if (m_motionBlur && m_bvh.hasDeform())
-        fail("InstancedRenderer: setMotionBlur is not combinable with deforming BLASes (CudaInstancedBVH::refitBLASesMotion): the normals of their "
-             "hits would be key 0's; clearDeform() or setMotionBlur(false)");
-    if (m_motionBlur && !m_bvh.hasMotion())
+    if (m_motionBlur && m_bvh.hasDeform() && (!m_vtxPos1 || m_vtxPos1->getSize() < (S64)m_numVerts * (S64)(3 * sizeof(F32))))
+        fail("InstancedRenderer: setMotionBlur is not combinable with deforming BLASes (CudaInstancedBVH::refitBLASesMotion) without their closing "
+             "vertices: the normals of their hits would be key 0's; call setDeformGeometry with the closing vertices refitBLASesMotion was given, "
+             "clearDeform() or setMotionBlur(false)");
+    if (m_motionBlur && !m_bvh.hasMotion() && !m_bvh.hasDeform())
         fail("InstancedRenderer: setMotionBlur is on and the CudaInstancedBVH has no motion key: call setMotionKey (or setMotionKeyDevice) with the "
              "shutter's closing transforms, or setMotionBlur(false)");
     if (!m_triVtxIndex)

@@ -20,7 +20,8 @@
 //                 false; in the manner of setFast: on, or whatever the CudaInstancedBVH itself was told, and put back after each trace
 //   setMotionBlur motion-blurred frames over a CudaInstancedBVH with a motion key (setMotionKey); default off, and off
 //                 every path is what it was: the batches are traced as the CudaInstancedBVH stands, the caller's setRayTimes
-//                 included, and resolved at key 0.  On: beginFrame fails unless the CudaInstancedBVH hasMotion(), then gives every
+//                 included, and resolved at key 0.  On: beginFrame fails unless the CudaInstancedBVH hasMotion() or hasDeform() (a scene
+//                 that only deforms renders blurred frames: refitMotion() passes key 0 twice), then gives every
 //                 pixel one hashed time in the shutter [open, close] (ntr_ray_times_primary over the primary slot-to-id table; another
 //                 seed per accumulated frame gives another sample); every batch is traced with setRayTimes pointing at its times -- the
 //                 caller's pointer is put back after each trace -- and resolved by ntr_instanced_hit_attributes_motion with the same key
@@ -28,6 +29,14 @@
 //                 ray's time (ntr_ray_times_secondary): it sees its instance where its primary ray saw it.  Primary, AO and diffuse
 //                 frames all work.  setWide (without setWideMotion), setFast, setWideFast and a world stay not combinable with motion:
 //                 the CudaInstancedBVH's traceBatch refuses each by name, and the refusal is passed on
+//   setDeformGeometry  motion-blurred frames over deforming BLASes (CudaInstancedBVH::refitBLASesMotion): the closing vertices
+//                 refitBLASesMotion was last given -- setGeometry's vertex buffer holds the opening ones -- borrowed, not copied; refused
+//                 when the buffer is smaller than numVerts * 12 bytes.  Under setMotionBlur with hasDeform(), every batch is resolved by
+//                 ntr_instanced_hit_attributes_deform with the CudaInstancedBVH's flag buffer (getBLASDeformingBuffer): the normal is the one
+//                 of the triangle posed at the ray's time, the triangle ntr_trace_instanced_deform tested.  The trace and the inherited
+//                 secondary times are setMotionBlur's, unchanged.  Without it (or after clearDeformGeometry) beginFrame refuses
+//                 setMotionBlur over deforming BLASes, as the normals would be key 0's.  Once hasDeform() drops (refitBLASes, clearDeform)
+//                 the frames are the motion path's again.  Without setMotionBlur a deforming scene keeps key-0 normals and the scalar time
 //   setWideMotion motion-blurred frames over the 4-wide trees (CudaInstancedBVH::setTraceWideMotion); default false; in the
 //                 manner of setFast: on, or whatever the CudaInstancedBVH itself was told, and put back after each trace.  With it on,
 //                 setWide(true) and setMotionBlur(true), primary, AO and diffuse frames run over the wide trees: the first batch after
@@ -59,6 +68,8 @@ public:
     explicit InstancedRenderer(CudaInstancedBVH& bvh);
 
     void setGeometry(Buffer& triVtxIndex, S32 numVerts, Buffer& vtxPos);
+    void setDeformGeometry(Buffer& vtxPos1);
+    void clearDeformGeometry(void) { m_vtxPos1 = NULL; }
     void setParams(RayType rayType, F32 aoRadius, S32 numSamples);
     void setRayMasks(U32 primaryMask = 0xFFFFFFFFu, U32 secondaryMask = 0xFFFFFFFFu);
     void setWide(bool on) { m_wide = on; }
@@ -100,6 +111,7 @@ private:
     CudaInstancedBVH& m_bvh;
     Buffer*    m_triVtxIndex;
     Buffer*    m_vtxPos;
+    Buffer*    m_vtxPos1;                                // setDeformGeometry: the closing vertices, or NULL
     S32        m_numVerts;
     RayType    m_rayType;
     F32        m_aoRadius;

@@ -13,6 +13,11 @@ through ONE identity instance of atrium() and through the forest of 4 096 instan
               ntr_bvh_refit_batch, over a pool of 1 and of --blases copies of soup1000 (a Compact tree's links are relative to its own
               start, so a copy at another offset is a BLAS), all asynchronous and alternated in one run; and over --many-blases copies
               the two batch calls alone.  --parts blas runs this part only
+  * frame     frames over deforming BLASes (ntr_instanced_hit_attributes_deform), on the two primary batches with every BLAS
+              deforming and one hashed time per pixel: the new attributes launch against ntr_instanced_hit_attributes_motion on the same
+              records, and a whole --frame-samples-sample AO frame through the six calls (primary times, trace, attributes,
+              ntr_raygen_ao_normals, secondary times, any-hit trace) with the blur's deform path against the motion path, all
+              asynchronous on one stream, by stream events.  --parts frame runs this part only
 Both launches get the same visibility, a ray mask of 0x7FFFFFFF that refuses nothing.  Launches are alternated, five runs after two
 warm-ups; every figure is the median with its minimum and maximum.  One JSON line per row; --out writes them as a list.  Every GPU step
 runs under a time limit of its own.
@@ -60,7 +65,9 @@ def main():
     ap.add_argument("--ao-rays", type=int, default=1 << 20)
     ap.add_argument("--blases", type=int, default=256)
     ap.add_argument("--many-blases", type=int, default=1024, help="copies for the two batch calls alone")
-    ap.add_argument("--parts", default="frames,blas", help="comma-separated: frames (none, time0, hashed, refit), blas")
+    ap.add_argument("--frame-samples", type=int, default=8, help="AO samples per primary hit of the frame part")
+    ap.add_argument("--frame-radius", type=float, default=5.0)
+    ap.add_argument("--parts", default="frames,blas", help="comma-separated: frames (none, time0, hashed, refit), blas, frame")
     ap.add_argument("--limit", type=int, default=120, help="seconds a GPU step may take")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -166,6 +173,79 @@ def main():
         emit(row)
         assert nt.trace_status() == 0, "traversal stack overflow"
 
+    def shaded_frame(name, t, tf, cam):
+        """The attributes launch and the whole AO frame over scene t with its one BLAS deforming: the deform path against the motion path"""
+        b, r = t.blas, t.res
+        rays, s2i = scenes.primary_rays(cam, args.width, args.height)
+        n, ns = rays.shape[0], args.frame_samples
+        m = n * ns
+        d_rays, d_s2i = step(name + " frame rays", args.limit, lambda: (up(rays), up(s2i.astype(np.int32))))
+        z = lambda c: torch.zeros(c, dtype=torch.uint8, device="cuda:0")      # noqa: E731
+        d_times, d_res, d_ids, d_out, d_nrm, d_out0, d_nrm0 = z(4 * n), z(16 * n), z(4 * n), z(16 * n), z(16 * n), z(16 * n), z(16 * n)
+        d_srays, d_si2s, d_ss2i, d_stimes, d_sres, d_sids = step(name + " frame buffers", args.limit,
+                                                                 lambda: (z(32 * m), z(4 * m), z(4 * m), z(4 * m), z(16 * m), z(4 * m)))
+        d_keys = z(128 * t.n)
+        d_inst1 = up(nt.make_instances(key1(tf), np.zeros(t.n, np.int32)))
+        d_nodes1, d_v0, d_v1 = z(b.nb), z(b.wb), z(b.wb)
+        d_pos1, d_flags = up(deform(b.pos, 0.05)), up(np.ones(1, np.uint32))
+        dfm = nt.InstanceDeform(d_nodes1.data_ptr(), d_v0.data_ptr(), d_v1.data_ptr())
+        geom = nt.InstancedGeometry(t.n, 1, b.tri.shape[0], b.pos.shape[0], t.d_inst.data_ptr(), b.d_blas_tris.data_ptr(), b.d_tri.data_ptr(),
+                                    b.d_pos.data_ptr())
+        dgeom = nt.InstancedDeformGeometry(d_pos1.data_ptr(), d_flags.data_ptr())
+        vis = nt.InstanceVisibility(0, 0, 0x7FFFFFFF)
+        pm = nt.InstanceMotion(d_keys.data_ptr(), 128 * t.n, d_times.data_ptr(), 0.0)
+        sm = nt.InstanceMotion(d_keys.data_ptr(), 128 * t.n, d_stimes.data_ptr(), 0.0)
+        step(name + " BLAS motion refit", args.limit, lambda: pose(b, b.bufs[0], d_nodes1, b.bufs[1], d_v0, d_v1, d_pos1, blocking=True))
+        rr = step(name + " deform refit", args.limit, lambda: nt.tlas_deform_refit(
+            t.n, t.d_inst.data_ptr(), d_inst1.data_ptr(), b.ranges, b.bufs[0].data_ptr(), d_nodes1.data_ptr(), b.nb, d_flags.data_ptr(),
+            t.d_nodes.data_ptr() if r.nodesBytes else 0, r.nodesBytes, r.rootLink, t.d_rec.data_ptr(), 64 * t.n, d_keys.data_ptr(), 128 * t.n, 0, stream,
+            True))
+
+        def six(deforming):
+            """The six calls of one AO frame, asynchronous on the stream"""
+            trace = (lambda *a, **k: nt.trace_instanced_deform(*a, deform=dfm, **k)) if deforming else nt.trace_instanced_motion
+            nt.ray_times_primary(n, d_s2i.data_ptr(), 0, 0.0, 1.0, d_times.data_ptr(), stream)
+            trace(*t.args(n, False, d_rays, d_res, d_ids), vis=vis, motion=pm, stream=stream, timed=False)
+            nt.instanced_hit_attributes_deform(n, d_res.data_ptr(), d_ids.data_ptr(), geom, pm, dgeom if deforming else None, d_out.data_ptr(),
+                                               d_nrm.data_ptr(), stream)
+            nt.raygen_ao_normals(d_srays.data_ptr(), d_si2s.data_ptr(), d_ss2i.data_ptr(), d_rays.data_ptr(), d_out.data_ptr(), d_nrm.data_ptr(), 0, n, ns,
+                                 args.frame_radius, 7, stream)
+            nt.ray_times_secondary(d_times.data_ptr(), 0, n, ns, d_stimes.data_ptr(), stream)
+            trace(*t.args(m, True, d_srays, d_sres, d_sids), vis=vis, motion=sm, stream=stream, timed=False)
+
+        def counts():
+            six(True)
+            torch.cuda.synchronize()
+            hits = int((d_out.view(torch.int32)[::4] >= 0).sum())
+            return hits, int((d_sres.view(torch.int32)[::4] >= 0).sum())
+        hits, occluded = step(name + " frame once", args.limit, counts)          # (it leaves the deform trace's records for the launches below)
+
+        def launches():
+            a, q = [], []
+            for _ in range(args.warmup + args.reps):          # alternated: motion, deform, motion, deform, ...
+                a.append(timed(lambda: nt.instanced_hit_attributes_motion(n, d_res.data_ptr(), d_ids.data_ptr(), geom, pm, d_out0.data_ptr(),
+                                                                            d_nrm0.data_ptr(), stream)))
+                q.append(timed(lambda: nt.instanced_hit_attributes_deform(n, d_res.data_ptr(), d_ids.data_ptr(), geom, pm, dgeom, d_out.data_ptr(),
+                                                                            d_nrm.data_ptr(), stream)))
+            assert torch.equal(d_out, d_out0), "the two attribute calls resolve different ids"
+            return a[args.warmup:], q[args.warmup:], int((d_nrm.view(torch.int32).view(-1, 4) != d_nrm0.view(torch.int32).view(-1, 4)).any(dim=1).sum())
+        a, q, differ = step(name + " attribute launches", args.limit, launches)
+
+        def frames():
+            f0, f1 = [], []
+            for _ in range(args.warmup + args.reps):          # alternated: motion path, deform path, ...
+                f0.append(timed(lambda: six(False)))
+                f1.append(timed(lambda: six(True)))
+            return f0[args.warmup:], f1[args.warmup:]
+        f0, f1 = step(name + " frames", args.limit, frames)
+        row = {"part": "frame", "frame": name, "instances": t.n, "moving": int(rr.motion.numMoving), "deforming": int(rr.numDeforming), "rays": n,
+               "samples": ns, "primary_hits": hits, "ao_rays_occluded": occluded, "normals_that_differ": differ,
+               "attributes_motion_ms": spread(a), "attributes_deform_ms": spread(q), "frame_motion_ms": spread(f0), "frame_deform_ms": spread(f1)}
+        row["attributes_deform_over_motion"] = row["attributes_deform_ms"]["median"] / row["attributes_motion_ms"]["median"]
+        row["frame_deform_over_motion"] = row["frame_deform_ms"]["median"] / row["frame_motion_ms"]["median"]
+        emit(row)
+        assert nt.trace_status() == 0, "traversal stack overflow"
+
     def blas_loop(b, copies, with_loop=True):
         """ntr_bvh_motion_refit_batch against the per-BLAS loop of ntr_bvh_motion_refit and against ntr_bvh_refit_batch over `copies`
         copies of BLAS b in one pool"""
@@ -225,21 +305,27 @@ def main():
         emit(row)
 
     parts = set(args.parts.split(","))
-    assert parts and parts <= {"frames", "blas"}, "--parts takes frames and blas"
-    if "frames" in parts:
+    assert parts and parts <= {"frames", "blas", "frame"}, "--parts takes frames, blas and frame"
+    if parts & {"frames", "frame"}:
         tri, pos, cam = scenes.atrium()
         atrium = step("atrium BLAS", args.limit, lambda: Blas(tri, pos, stream))
         tf = np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], F)
-        frame("identity", step("identity tlas", args.limit, lambda: Tlas(atrium, tf, stream)), tf, cam)
+        if "frames" in parts:
+            frame("identity", step("identity tlas", args.limit, lambda: Tlas(atrium, tf, stream)), tf, cam)
+        if "frame" in parts:
+            shaded_frame("identity", step("identity tlas", args.limit, lambda: Tlas(atrium, tf, stream)), tf, cam)
 
     tri, pos = scenes.random_soup(1000, seed=1100, walls=False)[:2]
     soup = step("soup1000 BLAS", args.limit, lambda: Blas(tri, pos, stream))
-    if "frames" in parts:
+    if parts & {"frames", "frame"}:
         rng = np.random.default_rng(4096)
         g = np.stack(np.meshgrid(*[np.arange(16)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
         tf = transforms(rotations(4096, rng), (g - 7.5) * 30.0)
         cam = dict(eye=(40.0, 60.0, -420.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_deg=60.0, far=2000.0)
-        frame("forest", step("forest tlas", args.limit, lambda: Tlas(soup, tf, stream)), tf, cam)
+        if "frames" in parts:
+            frame("forest", step("forest tlas", args.limit, lambda: Tlas(soup, tf, stream)), tf, cam)
+        if "frame" in parts:
+            shaded_frame("forest", step("forest tlas", args.limit, lambda: Tlas(soup, tf, stream)), tf, cam)
     if "blas" in parts:
         for copies in (1, args.blases):
             blas_loop(soup, copies)
